@@ -4,13 +4,15 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--cells-config C4]
                     [--variant auto|valu|mfma|mfma4|mfma4x2] [--no-cpu-baseline] [--no-cells] [--no-call-level]
+                    [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one image pair with all inputs resident in
 HBM: the per-cell solve (assemble + eigen-solve kernels) and the backward warp
 (set-up + gather kernels).  The two halves of the metric are timed in two regions of
 exactly K steps each, both bracketed by a barrier and a device synchronise:
 ``value`` = cells * K * N / t_solve (homographies/s), ``warp.value`` = canvas pixels
-* K * N / t_warp (Mpix/s), ``ms_per_step`` = (t_solve + t_warp) / K.
+* K * N / t_warp (Mpix/s), ``ms_per_step`` = (t_solve + t_warp) / K.  Every other timed region of the run (the objects
+below) takes ``extra_steps`` = min(K, 50) steps, so that the run's length follows K * ``ms_per_step`` plus a fixed part.
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a child
 ``python -m torch.distributed.run --nproc-per-node N bench.py ...`` before anything touches the
@@ -44,6 +46,10 @@ every phase; a failure ends in a non-zero exit code with ``bench_failed`` on std
 WORLD_SIZE=1, MASTER_ADDR / MASTER_PORT) runs ONE rank through an ``nccl`` group and every collective
 of the multi-rank paths - first contact with RCCL on a one-GPU box; ``APAP_BENCH_SELFTEST=1`` is the
 launch + rendezvous + one collective without a GPU.
+
+``--dump-outputs DIR`` writes what the headline's timed path computed in its last step, as its caller receives it, to
+``DIR/*.npy`` (see ``dump_outputs``): the inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
 """
 import os
 
@@ -77,6 +83,9 @@ PEAK_FP64_TFLOPS = 78.6
 PEAK_HBM_GBS = 8000.0
 # algorithmic flops per (cell, keypoint) of K1, SURVEY.md 8(d): 8 (weight) + 48 (24 FMAs) + 2
 K1_FLOPS_PER_CELL_POINT = 58.0
+#: the most timed steps of any region other than the headline's two (the default --steps: a default run times every region as
+#: many times as the headline)
+EXTRA_STEPS = 50
 VARIANTS = {"auto": 0, "valu": 1, "mfma": 2, "mfma4": 3, "mfma4x2": 4}
 
 
@@ -620,6 +629,23 @@ def selftest(rank, world):
 
 
 # --------------------------------------------------------------------------------------------- main
+DUMP_CANVAS_SAMPLES = 1 << 21       # canvas bytes kept by --dump-outputs: 8 MB of float32 values + 16 MB of float64 indices
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: the outputs of the timed path's last step (rank 0), copied back after the timed regions.
+    ``H.npy``: the float32 homography grid, (batch, rows, cols, 3, 3), whole.  ``canvas_sample.npy``: the warped uint8
+    canvas as float32 at a fixed, seeded sample of its flat positions (the whole canvas in float32 would be ~108 MB at C3),
+    ``canvas_sample_index.npy``: those positions (float64, sorted)."""
+    os.makedirs(out_dir, exist_ok=True)
+    H = res.H.cpu().numpy().reshape(res.batch, res.rows, res.cols, 3, 3).astype(np.float32)
+    canvas = res.out.cpu().numpy().reshape(-1)
+    idx = np.sort(np.random.default_rng(0).choice(canvas.size, size=min(DUMP_CANVAS_SAMPLES, canvas.size), replace=False))
+    np.save(os.path.join(out_dir, "H.npy"), H)
+    np.save(os.path.join(out_dir, "canvas_sample.npy"), canvas[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "canvas_sample_index.npy"), idx.astype(np.float64))
+
+
 def roofline_k2(config, res, kern, kern_plain, tj, fused):
     """K2 (k_eigen_denorm) against HBM: counter bytes per launch (profiles/pmc_traffic.json: 2 x FETCH_SIZE - its reads are
     16 bytes per lane, the case the guide's correction doubles - + WRITE_SIZE) and the bytes the algorithm needs, over the
@@ -783,7 +809,14 @@ def main():
     ap.add_argument("--cpu-rows", type=int, default=400)
     ap.add_argument("--cpu-pool", type=int, default=-1,
                     help="workers of the all-cores CPU row (-1 = every core this process may use, 0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step (H grid, canvas sample) to DIR/*.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    # --steps is the number of timed steps of the headline (`value`, `ms_per_step`); every other timed region of the run
+    # (extras, configs, pairs, cells, kernel times) takes at most EXTRA_STEPS steps, so that the run's length follows the headline's
+    xs = min(a.steps, EXTRA_STEPS)
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(self_launch(a.gpus))       # nothing above this line touches the GPU
@@ -905,13 +938,15 @@ def main():
     t_solve = timed(run_solve, a.steps)
     t_warp = timed(run_warp, a.steps)
     assert int(res.status.cpu()[0]) == 0, "device status word set during the timed region"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res)
     canvas_resident = res.out.clone()
     # the same two halves as separate services: the solve alone, and the warp of a grid from anywhere (its own set-up launch)
     for _ in range(a.warmup):
         res.solve_plain(stream)
         res.warp_standalone(stream)
-    t_solve_plain = timed(lambda: res.solve_plain(stream), a.steps)
-    t_warp_alone = timed(lambda: res.warp_standalone(stream), a.steps)
+    t_solve_plain = timed(lambda: res.solve_plain(stream), xs)
+    t_warp_alone = timed(lambda: res.warp_standalone(stream), xs)
     assert torch.equal(res.out, canvas_resident), "stand-alone warp and resident warp step disagree"
     del canvas_resident
     res.solve(stream)       # leave the resident tables in place for what follows
@@ -921,7 +956,7 @@ def main():
         condition(lambda: fn(stream))
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(a.steps):
+        for _ in range(xs):
             fn(stream)
         torch.cuda.synchronize()
         return time.perf_counter() - t0
@@ -938,7 +973,7 @@ def main():
             res.warp(stream, i, o)
         for _ in range(len(cold)):
             warp_cold()
-        t_warp_cold = timed(warp_cold, a.steps)
+        t_warp_cold = timed(warp_cold, xs)
         assert torch.equal(cold[0][1], res.out), "cold-cache canvas differs from the warm one"
 
     # two warps of the pair in flight at once (two streams, two canvases): the set-up kernel, the ramp and the tail of one
@@ -951,7 +986,7 @@ def main():
         res.warp_lane2()
     for _ in range(a.warmup):
         warp_pair_of_lanes()
-    t_warp2 = timed(warp_pair_of_lanes, a.steps)
+    t_warp2 = timed(warp_pair_of_lanes, xs)
     assert torch.equal(res.second_lane()[0], res.out), "second lane's canvas differs"
 
     t_stitch = extra(res.stitch)
@@ -963,25 +998,25 @@ def main():
     # per-kernel durations, HIP events on the launch stream (rank-local)
     condition(lambda: res.solve(stream))
     ctx.set("profile", 1)
-    for _ in range(a.steps):
+    for _ in range(xs):
         res.solve(stream)
         res.warp(stream)
         res.equalize(stream)
         res.ransac(stream)
     torch.cuda.synchronize()
     kern = read_kernel_ms(ctx)
-    for _ in range(a.steps):            # the set-up launch of the stand-alone warp (the resident step has none)
+    for _ in range(xs):                 # the set-up launch of the stand-alone warp (the resident step has none)
         res.warp_standalone(stream)
     torch.cuda.synchronize()
     kern["invert"] = read_kernel_ms(ctx)["invert"]
-    for _ in range(a.steps):            # K2 without the warp-ready tail (the stand-alone solve)
+    for _ in range(xs):                 # K2 without the warp-ready tail (the stand-alone solve)
         res.solve_plain(stream)
     torch.cuda.synchronize()
     kern_plain = read_kernel_ms(ctx)
     res.solve(stream)
     kern_cold = None
     if cold:
-        for _ in range(max(a.steps, len(cold))):
+        for _ in range(max(xs, len(cold))):
             warp_cold()
         torch.cuda.synchronize()
         kern_cold = read_kernel_ms(ctx)
@@ -1001,12 +1036,12 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / n
     condition(lambda: res.warp(stream))
-    k3_warm_ms = back_to_back(lambda: res.warp(stream), max(a.steps, 20))
+    k3_warm_ms = back_to_back(lambda: res.warp(stream), max(xs, 20))
     k3_cold_ms = None
     if cold:
         for _ in range(len(cold)):
             warp_cold()
-        k3_cold_ms = back_to_back(warp_cold, max(a.steps, len(cold)))
+        k3_cold_ms = back_to_back(warp_cold, max(xs, len(cold)))
 
     # a caller's FIRST solve from an idle chip (clocks down): one call, bracketed by synchronisation
     from_idle = []
@@ -1023,10 +1058,10 @@ def main():
     configs_obj = modes_obj = None
     if world == 1 and not a.no_configs:
         phase("configs C1, C2; opt-in solve forms")
-        configs_obj = {c: small_config(c, dev, stream, a.steps, timed, condition, back_to_back) for c in ("C1", "C2") if c != a.config}
+        configs_obj = {c: small_config(c, dev, stream, xs, timed, condition, back_to_back) for c in ("C1", "C2") if c != a.config}
         if a.batch == 1 and a.variant == "auto":
             H_default = res.H.cpu().numpy().reshape(res.rows, res.cols, 3, 3)
-            modes_obj = opt_in_modes(a.config, pair, dev, stream, a.steps, timed, condition, H_default, kern["assemble"])
+            modes_obj = opt_in_modes(a.config, pair, dev, stream, xs, timed, condition, H_default, kern["assemble"])
 
     # ------------------------------------------------------------------ pairs as BASELINE config 5 states them
     c5_obj = None
@@ -1039,13 +1074,13 @@ def main():
             condition(lambda: pb.solve(stream))
             for _ in range(a.warmup):
                 pb.solve(stream)
-        t_c5 = timed((lambda: pb.solve(stream)) if pb is not None else (lambda: None), a.steps)
+        t_c5 = timed((lambda: pb.solve(stream)) if pb is not None else (lambda: None), xs)
         # the warp half of config 5: this rank's pairs in one set-up launch + one gather launch (grid.z = pair)
         if pb is not None:
             for _ in range(max(a.warmup, 2)):
                 pb.warp(stream)
             pb.check_against_single_launches(stream, which=sorted({0, pb.batch - 1}))
-        w_steps = max(4, a.steps // 4)          # a step is 64 / N pairs: ~1 ms
+        w_steps = max(4, xs // 4)               # a step is 64 / N pairs: ~1 ms
         t_c5w = timed((lambda: pb.warp(stream)) if pb is not None else (lambda: None), w_steps)
         # ... and with the geometry tables kept from the first call (they depend on the edges and the canvas only)
         t_c5g = timed((lambda: pb.warp(stream, N.WARP_CELLS | N.WARP_GATHER)) if pb is not None else (lambda: None), w_steps)
@@ -1060,7 +1095,7 @@ def main():
                 torch.cuda.synchronize()
                 assert torch.equal(pb.out, canv), "whole-job canvases differ from the batched warp's"
             del canv
-        j_steps = max(3, a.steps // 8)
+        j_steps = max(3, xs // 8)
         t_job_seq = timed((lambda: pb.whole_job(False)) if pb is not None else (lambda: None), j_steps)
         t_job = timed((lambda: pb.whole_job(True)) if pb is not None else (lambda: None), j_steps)
         if pb is not None:
@@ -1078,8 +1113,8 @@ def main():
             c5_pixels = int(tt.cpu()[0])
         c5_obj = {"workload": f"C5: {total_pairs} independent 3840x2160 pairs, 2000 correspondences, 100x100 mesh each; "
                               f"{len(mine)} per rank in ONE batched launch", "world_size": world, "scaling": "strong",
-                  "value": total_pairs * cells_c5 * a.steps / t_c5, "unit": "homographies/s",
-                  "solve_ms_per_step": t_c5 / a.steps * 1e3, "pairs_per_s": total_pairs * a.steps / t_c5,
+                  "value": total_pairs * cells_c5 * xs / t_c5, "unit": "homographies/s",
+                  "solve_ms_per_step": t_c5 / xs * 1e3, "pairs_per_s": total_pairs * xs / t_c5,
                   "pairs_per_rank": len(mine), "collectives_per_step": "none (independent pairs)",
                   "whole_job": {"pairs_per_s": total_pairs * j_steps / t_job, "ms_per_step": t_job / j_steps * 1e3,
                                 "one_stream_ms_per_step": t_job_seq / j_steps * 1e3, "groups": a.c5_chunks, "steps": j_steps,
@@ -1131,21 +1166,21 @@ def main():
         for _ in range(a.warmup):
             cs.solve()
             cs.warp()
-        tc_solve = timed(cs.solve, a.steps)
+        tc_solve = timed(cs.solve, xs)
         tc_other = None
         if world > 1:           # the other form of the solve (one launch + one gather / two launches, first gather overlapped)
             co = ShardedSolver(cp, dev, dist, ctx=ctx, overlap=not cs.overlap)
             co.broadcast_inputs()
             for _ in range(a.warmup + 3):
                 co.solve()
-            tc_other = timed(co.solve, a.steps)
+            tc_other = timed(co.solve, xs)
             del co
-        tc_warp = timed(cs.warp, a.steps)
-        tc_bands = timed(lambda: cs.warp(gather=False), a.steps)      # the canvas left distributed: no collective
-        tc_step = timed(cs.step, a.steps)                             # solve + H gather in flight + own band + wait
+        tc_warp = timed(cs.warp, xs)
+        tc_bands = timed(lambda: cs.warp(gather=False), xs)           # the canvas left distributed: no collective
+        tc_step = timed(cs.step, xs)                                  # solve + H gather in flight + own band + wait
         assert int(cs.status.cpu()[0]) == 0
         ctx.set("profile", 1)
-        for _ in range(min(a.steps, 10)):
+        for _ in range(min(xs, 10)):
             cs.solve()
             cs.warp()
         torch.cuda.synchronize()
@@ -1161,7 +1196,7 @@ def main():
             c_out = torch.empty((1, cp.final_h, cp.final_w, 3), dtype=torch.uint8, device=dev)
             for _ in range(5):
                 wp.gather(c_img, out=c_out)
-            c_ms = back_to_back(lambda: wp.gather(c_img, out=c_out), max(a.steps, 20))
+            c_ms = back_to_back(lambda: wp.gather(c_img, out=c_out), max(xs, 20))
             assert torch.equal(c_out[0], cs.warp()) and int(wp.status.cpu()[0]) == 0
             c_nz = int((c_out[0].amax(dim=2) > 0).sum().cpu())
             c_bytes = 6 * c_nz + 3 * (cp.final_w * cp.final_h - c_nz)
@@ -1178,17 +1213,17 @@ def main():
                         f"correspondences, {cs.rows}x{cs.cols} mesh, canvas {cp.final_w}x{cp.final_h}; mesh rows and canvas "
                         f"rows sharded over the ranks",
             "world_size": world, "backend": ("rccl (nccl)" if backend == "nccl" else backend) if world > 1 else "none (1 rank)",
-            "scaling": "strong", "value": cs.cells_total * a.steps / tc_solve, "unit": "homographies/s",
-            "solve_ms_per_step": tc_solve / a.steps * 1e3,
-            "warp": {"value": cp.final_w * cp.final_h * a.steps / tc_warp / 1e6, "unit": "Mpix/s",
-                     "ms_per_step": tc_warp / a.steps * 1e3,
+            "scaling": "strong", "value": cs.cells_total * xs / tc_solve, "unit": "homographies/s",
+            "solve_ms_per_step": tc_solve / xs * 1e3,
+            "warp": {"value": cp.final_w * cp.final_h * xs / tc_warp / 1e6, "unit": "Mpix/s",
+                     "ms_per_step": tc_warp / xs * 1e3,
                      "note": "row bands + all-gather: the whole canvas on every rank after every step"},
-            "warp_bands_only": {"value": cp.final_w * cp.final_h * a.steps / tc_bands / 1e6, "unit": "Mpix/s",
-                                "ms_per_step": tc_bands / a.steps * 1e3,
+            "warp_bands_only": {"value": cp.final_w * cp.final_h * xs / tc_bands / 1e6, "unit": "Mpix/s",
+                                "ms_per_step": tc_bands / xs * 1e3,
                                 "note": "row bands left where they are computed (no collective): the part of the warp that "
                                         "shards; SURVEY.md 8e expects the gathered form to be transfer-dominated.  Bands are aligned to the "
                                         "mesh rows a rank solved: its set-up kernel inverts 1 / world of the cells"},
-            "pipelined_step": {"ms_per_step": tc_step / a.steps * 1e3,
+            "pipelined_step": {"ms_per_step": tc_step / xs * 1e3,
                                "note": "ShardedSolver.step(): each rank solves its mesh rows, starts the all-gather of the H grid, "
                                        "warps ITS band (the canvas rows of its own mesh rows, from its own rows of the grid) "
                                        "while the gather runs, then waits: solve + warp_bands_only with the collective hidden"},
@@ -1196,7 +1231,7 @@ def main():
             "collectives_per_step": "solve: the H grid (36 B per cell) in 2 all-gathers, the first beside the second half's "
                                     "kernels; warp: 1 all-gather of the canvas bands" if world > 1 else "none",
             "collectives_overlapped": bool(cs.overlap),
-            "solve_other_form_ms_per_step": None if tc_other is None else tc_other / a.steps * 1e3,
+            "solve_other_form_ms_per_step": None if tc_other is None else tc_other / xs * 1e3,
             "solve_forms_note": "solve_ms_per_step is ShardedSolver's default for this world size (two launches per rank with the "
                                 "first all-gather beside the second for 2-4 ranks, one launch + one gather above: a model, "
                                 "cvx_proj_amd/dist.py); solve_other_form_ms_per_step is the other form on the same ranks",
@@ -1239,7 +1274,7 @@ def main():
                      "collectives_per_step": "none (independent pairs)"}
         line = {
             "metric": METRIC, "value": units_solve * a.steps / t_solve, "unit": "homographies/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "conditioning_ms": a.condition_ms,
+            "n_gpus": world, "steps": a.steps, "extra_steps": xs, "warmup": a.warmup, "conditioning_ms": a.condition_ms,
             "ms_per_step": (t_solve + t_warp) / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"{a.config}: {CONFIGS[a.config][0]}x{CONFIGS[a.config][1]} pair, "
@@ -1255,13 +1290,13 @@ def main():
                           "every cell warp ready (apap_solve_warp_batch_device), the warp step is the gather kernel alone "
                           "(apap_warp_batch_device, APAP_WARP_GATHER); the per-cell set-up is inside solve_ms_per_step") if res.resident
                          else "solve and stand-alone warp (a batch of pairs per solve launch)",
-            "standalone": {"solve_ms_per_step": t_solve_plain / a.steps * 1e3, "value": units_solve * a.steps / t_solve_plain,
-                           "warp_ms_per_step": t_warp_alone / a.steps * 1e3,
-                           "warp_value": units_warp * a.steps / t_warp_alone / 1e6, "warp_unit": "Mpix/s",
+            "standalone": {"solve_ms_per_step": t_solve_plain / xs * 1e3, "value": units_solve * xs / t_solve_plain,
+                           "warp_ms_per_step": t_warp_alone / xs * 1e3,
+                           "warp_value": units_warp * xs / t_warp_alone / 1e6, "warp_unit": "Mpix/s",
                            "note": "the two halves as separate services: apap_solve_device (H grid only) and apap_warp_device on a "
                                    "grid from anywhere (its own set-up launch: inverses, records, lookup tables, then the gather)"},
-            "warp_two_in_flight": {"value": 2 * units_warp * a.steps / t_warp2 / 1e6, "unit": "Mpix/s",
-                                   "ms_per_pair": t_warp2 / a.steps / 2 * 1e3,
+            "warp_two_in_flight": {"value": 2 * units_warp * xs / t_warp2 / 1e6, "unit": "Mpix/s",
+                                   "ms_per_pair": t_warp2 / xs / 2 * 1e3,
                                    "note": "the same warp step issued twice per step on two streams into two canvases: one warp "
                                            "step alone leaves the chip partly idle (a set-up kernel of one wave per SIMD, then 1.45 "
                                            "generations of waves that compute together and wait together); a second, independent one "
@@ -1272,12 +1307,12 @@ def main():
             "pair_per_rank": per_rank_obj,
             "cells": cells_obj,
             "stitch": {
-                "value": pair.final_w * pair.final_h * a.steps / t_stitch / 1e6, "unit": "Mpix/s (rank 0)",
-                "ms_per_step": t_stitch / a.steps * 1e3,
+                "value": pair.final_w * pair.final_h * xs / t_stitch / 1e6, "unit": "Mpix/s (rank 0)",
+                "ms_per_step": t_stitch / xs * 1e3,
                 "note": "fused warp + paste + uniform_blend, apap.py:258-262; extra, not in `value`"},
             "equalize": {
-                "value": pair.shape[0] * pair.shape[1] * a.steps / t_eq / 1e6, "unit": "Mpix/s (rank 0)",
-                "ms_per_step": t_eq / a.steps * 1e3,
+                "value": pair.shape[0] * pair.shape[1] * xs / t_eq / 1e6, "unit": "Mpix/s (rank 0)",
+                "ms_per_step": t_eq / xs * 1e3,
                 "roofline": {"kernels": "k_eq_hist + k_eq_apply", "bound": "hbm",
                              "achieved": 3.0 * pair.img.size / ((kern["eq_hist"] + kern["eq_apply"]) * 1e-3) / 1e9,
                              "peak": PEAK_HBM_GBS, "unit": "GB/s",
@@ -1285,7 +1320,7 @@ def main():
                 "note": "per-channel cv.equalizeHist of the 4K source image, utils.py:85-91; algorithmic "
                         "traffic 3 bytes per image byte (read, read, write); extra, not in `value`"},
             "ransac": {
-                "ms_per_call": t_ransac / a.steps * 1e3, "hypotheses": N.RANSAC_ITERATIONS, "points": res.n,
+                "ms_per_call": t_ransac / xs * 1e3, "hypotheses": N.RANSAC_ITERATIONS, "points": res.n,
                 "inliers": int(res.r_res.cpu()[1]),
                 "note": "device half of the seed homography (4-point hypotheses, 5 px), baseline_stitch_test.py:42; "
                         "three small latency-bound kernels (fusing the selection into the scoring kernel's last block was measured in round 6: slower, profiles/r06_frontend_fusion.txt); extra, not in `value`"},
@@ -1323,8 +1358,8 @@ def main():
                                         "kernels + synchronisation; `value` is the steady state after conditioning_ms of load"},
         }
         if cold:
-            line["warp_cold"] = {"value": units_warp * a.steps / t_warp_cold / 1e6, "unit": "Mpix/s",
-                                 "ms_per_step": t_warp_cold / a.steps * 1e3, "buffer_sets": len(cold),
+            line["warp_cold"] = {"value": units_warp * xs / t_warp_cold / 1e6, "unit": "Mpix/s",
+                                 "ms_per_step": t_warp_cold / xs * 1e3, "buffer_sets": len(cold),
                                  "bytes_rotated": len(cold) * (res.img.numel() + res.out.numel())}
             line["roofline_warp_cold"] = {
                 "kernel": k3_name, "cache": "cold", "bound": "hbm",

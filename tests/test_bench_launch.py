@@ -49,3 +49,31 @@ def test_cpu_baseline_rows_on_a_small_config():
     assert out["cores"] == 1 and out["value"] > 0 and out["warp_value"] > 0
     assert out["all_cores"]["cores"] == 2 and out["all_cores"]["value"] > 0
     assert out["default_blas_threads"]["value"] > 0 and "error" not in out["default_blas_threads"]
+
+
+def test_dump_outputs_writes_the_grid_and_a_fixed_canvas_sample(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files under 64 MB, the grid whole, the canvas sample the same positions every run."""
+    import types
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    rows, cols, h, w = 4, 5, 300, 400
+    res = types.SimpleNamespace(batch=1, rows=rows, cols=cols,
+                                H=torch.from_numpy(rng.random((rows * cols, 9), dtype=np.float32)),
+                                out=torch.from_numpy(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), res)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["H.npy", "canvas_sample.npy", "canvas_sample_index.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) < 64 << 20
+    H = np.load(tmp_path / "a" / "H.npy")
+    assert H.dtype == np.float32 and np.array_equal(H.reshape(-1, 9), res.H.numpy())
+    idx = np.load(tmp_path / "a" / "canvas_sample_index.npy")
+    vals = np.load(tmp_path / "a" / "canvas_sample.npy")
+    assert idx.dtype == np.float64 and vals.dtype == np.float32 and len(idx) == min(bench.DUMP_CANVAS_SAMPLES, h * w * 3)
+    assert np.array_equal(vals, res.out.numpy().reshape(-1)[idx.astype(np.int64)].astype(np.float32))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
