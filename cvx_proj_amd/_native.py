@@ -59,6 +59,21 @@ class ApapValueError(ApapError, ValueError):
 
 _ERROR_CLASSES = {ERR_SINGULAR: ApapSingularError, ERR_INDEX: ApapIndexError, ERR_INVALID_ARG: ApapValueError}
 
+# bits of the device status word of the resident entry points (APAP_STATUS_* of include/apap_hip.h)
+STATUS_SINGULAR, STATUS_INDEX, STATUS_UNPREPARED = 1, 2, 4
+
+
+def raise_for_status(word, who):
+    """Raise what the host-buffer calls make of a device status word (``status_to_code`` of csrc/apap_capi.hip: the same
+    bits in the same order, the same exception classes and wording); return quietly when none of the bits is set."""
+    if word & STATUS_SINGULAR:
+        raise ApapSingularError(ERR_SINGULAR, f"{who}: Singular matrix")
+    if word & STATUS_INDEX:
+        raise ApapIndexError(ERR_INDEX, f"{who}: index 0 is out of bounds for axis 0 with size 0 (mesh edges do not cover the canvas)")
+    if word & STATUS_UNPREPARED:
+        raise ApapValueError(ERR_INVALID_ARG, f"{who}: the warp workspace holds no lookup tables for this mesh / canvas "
+                                              "(APAP_WARP_GEOMETRY)")
+
 
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
@@ -141,11 +156,12 @@ SIGNATURES = {
 }
 
 _lib = None
+_torch_at_load = False      # was torch in the process when the library was loaded?  (cvx_proj_amd.resident refuses otherwise)
 
 
 def lib():
     """Load the shared library once.  Raises ApapError (never falls back) if absent."""
-    global _lib
+    global _lib, _torch_at_load
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise ApapError(ERR_NO_DEVICE, f"{LIB_PATH} not built; run `python -c 'import __graft_entry__ as g; "
@@ -154,14 +170,16 @@ def lib():
         # file).  When torch is ALREADY imported its copy is in the process and this library binds to it; otherwise the RPATH
         # to /opt/rocm/lib is used and NO torch is imported on the library's behalf (2.3 s against 0.4 s of start-up for a
         # command that needs none: python -m cvx_proj_amd.apap).  The rule for a process that uses both: import torch BEFORE
-        # the first call into this module (cvx_proj_amd.pipeline and cvx_proj_amd.dist do so at their top; a later
-        # `import torch` would find /opt/rocm's runtime under its own SONAME and see no GPU).  APAP_HIP_PRELOAD_TORCH=1
-        # restores the old behaviour (torch imported here first, if it is installed).
+        # the first call into this module (a later `import torch` would find /opt/rocm's runtime under its own SONAME and see
+        # no GPU).  Whether it was kept is recorded here; cvx_proj_amd.resident, the one module through which the package uses
+        # torch (pipeline and dist import it), refuses to load in a process that broke it.  APAP_HIP_PRELOAD_TORCH=1 restores
+        # the old behaviour (torch imported here first, if it is installed).
         if "torch" not in sys.modules and os.environ.get("APAP_HIP_PRELOAD_TORCH", "0") == "1":
             try:
                 import torch  # noqa: F401
             except ImportError:
                 pass
+        _torch_at_load = "torch" in sys.modules
         handle = C.CDLL(LIB_PATH)
         # a build of another ABI generation keeps the symbol names but not the argument lists: refuse it
         got = handle.apap_abi_version() if hasattr(handle, "apap_abi_version") else 1

@@ -1588,7 +1588,7 @@ __global__ __launch_bounds__(256) void k_invert_cells(const T *__restrict__ H, i
     double m[9], r[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) m[k] = (double)H[(size_t)cell * 9 + k];
-    if (!inv3(m, r)) atomicOr(status, apap::kStatusSingular);
+    if (!inv3(m, r)) atomicOr(status, APAP_STATUS_SINGULAR);
     double *p = hinv_pad + (size_t)cell * APAP_HINV_STRIDE;
 #pragma unroll
     for (int k = 0; k < 9; ++k) p[k] = (double)(T)r[k];  // the inverse in the grid's own dtype, widened once
@@ -1617,7 +1617,7 @@ __host__ __device__ __forceinline__ unsigned warp_stamp16(int mesh_rows, int mes
 }
 __device__ __forceinline__ bool warp_tables_ready(int have, int mesh_rows, int mesh_cols, int final_w, int final_h, int *status) {
     if (__builtin_expect(have == warp_stamp(mesh_rows, mesh_cols, final_w, final_h), 1)) return true;
-    if ((threadIdx.x & 63) == 0) atomicOr(status, apap::kStatusUnprepared);
+    if ((threadIdx.x & 63) == 0) atomicOr(status, APAP_STATUS_UNPREPARED);
     return false;
 }
 
@@ -1642,7 +1642,7 @@ __global__ __launch_bounds__(256) void k_cell_lut(const double *__restrict__ mes
     bool bad = first < 0;
     if (c < 0) c += ncell;
     bad = bad || c < 0 || c >= ncell;
-    if (bad) { atomicOr(status, apap::kStatusIndex); c = 0; }
+    if (bad) { atomicOr(status, APAP_STATUS_INDEX); c = 0; }
     lut[t] = c;
 }
 
@@ -1847,7 +1847,7 @@ __device__ __forceinline__ void warp_cell_tables(const double (&m)[9], int er, i
                            : fast_origin(mesh_w, n_w, ec, final_w, x0, sx);
     const bool oky = edges ? fast_origin_of(edges->h0, edges->h1, er >= 0 && er + 1 < n_h, final_h, y0, sy)
                            : fast_origin(mesh_h, n_h, er, final_h, y0, sy);
-    if (!inv3(m, r)) atomicOr(status, apap::kStatusSingular);
+    if (!inv3(m, r)) atomicOr(status, APAP_STATUS_SINGULAR);
     double2 *p = reinterpret_cast<double2 *>(hinv_pad + (size_t)cell * APAP_HINV_STRIDE);
     // the inverse rounded to the grid's dtype (what the reference stores back, apap.py:203),
     // widened once here instead of nine v_cvt_f64_f32 per pixel in the warp kernel
@@ -1966,7 +1966,7 @@ __global__ __launch_bounds__(256) void k_warp_setup(const T *__restrict__ H, int
         bool bad = lo >= n_e;
         if (c < 0) c += ncell;  // Python's index -1
         bad = bad || c < 0 || c >= ncell;
-        if (bad) { atomicOr(status, apap::kStatusIndex); c = 0; }
+        if (bad) { atomicOr(status, APAP_STATUS_INDEX); c = 0; }
         lut[(is_row ? 0 : final_h) + idx] = c;
         // the fast kernel's entry: cell and distance from the cell's anchor, or the extra cell
         int x0 = 0, span = 1;
@@ -2416,7 +2416,7 @@ __global__ __launch_bounds__(256) void k_warp_fast(const uint8_t *__restrict__ i
     }
     const bool ready = (rr[0] >> 16) == warp_stamp16(mesh_rows, mesh_cols, final_w, final_h);
     const unsigned cmask = ready ? 0xffffu : 0u;
-    if (!ready && lane == 0) atomicOr(status, apap::kStatusUnprepared);
+    if (!ready && lane == 0) atomicOr(status, APAP_STATUS_UNPREPARED);
 #pragma unroll
     for (int t = 0; t < kRows; ++t) rr[t] &= cmask;
 #pragma unroll
@@ -2578,7 +2578,7 @@ __global__ __launch_bounds__(256) void k_flatten(const float *__restrict__ H, in
     double m[9], r[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) m[k] = (double)H[(size_t)cell * 9 + k];
-    if (!inv3(m, r)) atomicOr(status, apap::kStatusSingular);
+    if (!inv3(m, r)) atomicOr(status, APAP_STATUS_SINGULAR);
     float f[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) f[k] = (float)r[k];

@@ -17,12 +17,12 @@ CPU fallback in this module.
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _native
+from .resident import WarpPlan, hip_solve, hip_solve_batch, hip_warp_batch, hip_warp_rows, solve_workspace_bytes, \
+    warp_workspace_bytes
 
 
 def row_partition(rows, world):
@@ -35,192 +35,6 @@ def row_partition(rows, world):
         out.append((start, start + size))
         start += size
     return out
-
-
-def hip_solve(table, denorm, vertices, gamma, sigma, ctx=None, out=None, work=None):
-    """Default ``solve_fn``: resident-data C-ABI call on the tensors' device.  ``out`` (>= cells x 9 float32)
-    and ``work`` (uint8 scratch) are reused when given and large enough - a solver that runs every step keeps
-    them - else allocated."""
-    if not table.is_cuda:
-        raise _native.ApapError(_native.ERR_NO_DEVICE, "hip_solve needs CUDA/HIP tensors; there is no CPU fallback")
-    cells = vertices.shape[0]
-    n = table.shape[0]
-    H = out[:cells] if out is not None and out.shape[0] >= cells else torch.empty((cells, 9), dtype=torch.float32, device=table.device)
-    if cells == 0:
-        return H
-    nbytes = max(_native.lib().apap_solve_workspace_bytes(_native._h(ctx), n, cells), 256)
-    if work is None or work.numel() < nbytes:
-        work = torch.empty(nbytes, dtype=torch.uint8, device=table.device)
-    stream = torch.cuda.current_stream(table.device).cuda_stream
-    _native.check(_native.lib().apap_solve_device(_native._h(ctx), table.data_ptr(), n, vertices.data_ptr(), cells, float(gamma),
-                                                  float(sigma), denorm.data_ptr(), H.data_ptr(), work.data_ptr(),
-                                                  nbytes, ctypes.c_void_p(stream)))
-    return H
-
-
-def hip_warp_rows(img, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, row_begin, row_count, out_band, shape, ctx=None,
-                  work=None, status=None):
-    """Default ``warp_fn``: resident-data C-ABI call warping canvas rows
-    ``[row_begin, row_begin + row_count)`` into ``out_band``.  ``work`` / ``status`` are reused when given."""
-    if not img.is_cuda:
-        raise _native.ApapError(_native.ERR_NO_DEVICE, "hip_warp_rows needs CUDA/HIP tensors; there is no CPU fallback")
-    rows, cols = shape
-    nbytes = _native.lib().apap_warp_workspace_bytes(rows, cols, final_w, final_h)
-    if work is None or work.numel() < nbytes:
-        work = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=img.device)
-    stream = torch.cuda.current_stream(img.device).cuda_stream
-    _native.check(_native.lib().apap_warp_rows_device(
-        _native._h(ctx), img.data_ptr(), img.shape[0], img.shape[1], H.data_ptr(), rows, cols, mesh_w.data_ptr(), mesh_w.numel(),
-        mesh_h.data_ptr(), mesh_h.numel(), final_w, final_h, off_x, off_y, row_begin, row_count, out_band.data_ptr(),
-        work.data_ptr(), nbytes, status.data_ptr(), ctypes.c_void_p(stream)))
-    return status
-
-
-def hip_solve_batch(tables, denorms, vertices, gamma, sigma, ctx=None):
-    """Several pairs (equal keypoint and cell counts, one shared mesh) in ONE launch:
-    ``tables`` (B, n, 32), ``denorms`` (B, 36), ``vertices`` (cells, 2) -> H (B, cells, 9)."""
-    if not tables.is_cuda:
-        raise _native.ApapError(_native.ERR_NO_DEVICE, "hip_solve_batch needs CUDA/HIP tensors; there is no CPU fallback")
-    batch, n = tables.shape[0], tables.shape[1]
-    cells = vertices.shape[0]
-    H = torch.empty((batch, cells, 9), dtype=torch.float32, device=tables.device)
-    nbytes = max(_native.lib().apap_solve_batch_workspace_bytes(_native._h(ctx), n, cells, batch), 256)
-    work = torch.empty(nbytes, dtype=torch.uint8, device=tables.device)
-    stream = torch.cuda.current_stream(tables.device).cuda_stream
-    _native.check(_native.lib().apap_solve_batch_device(_native._h(ctx), tables.data_ptr(), n, vertices.data_ptr(), 0, cells,
-                                                        float(gamma), float(sigma), denorms.data_ptr(), H.data_ptr(),
-                                                        batch, work.data_ptr(), nbytes, ctypes.c_void_p(stream)))
-    return H
-
-
-def hip_warp_batch(imgs, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, shape, out=None, centers=None, ctx=None,
-                   work=None, status=None, phases=_native.WARP_ALL, rows=None, hinv_out=None):
-    """Backward warp of a BATCH of independent pairs in one set of launches (``apap_warp_batch_device``, grid.z = pair):
-    ``imgs`` (B, h, w, 3) uint8 - or (h, w, 3): one image for every pair -, ``H`` (B, cells, 9) float32 (what
-    ``hip_solve_batch`` returns), one set of edges, canvas size and offsets for all -> canvases (B, final_h, final_w, 3).
-    ``centers`` (B, ch, cw, 3) or (ch, cw, 3): the fused stitch (warp + paste + uniform_blend).  ``phases``: which of
-    geometry tables / per-cell set-up / gather run on ``work`` (a caller that keeps ``work`` runs the geometry once).
-    ``rows`` = (row_begin, row_count): a band of every canvas; ``out`` is then (B, row_count, final_w, 3)."""
-    if not H.is_cuda:
-        raise _native.ApapError(_native.ERR_NO_DEVICE, "hip_warp_batch needs CUDA/HIP tensors; there is no CPU fallback")
-    mrows, mcols = shape
-    batch = H.shape[0]
-    dev = H.device
-    row_begin, row_count = (0, final_h) if rows is None else rows
-    one_img = imgs.dim() == 3
-    ih, iw = (imgs.shape[0], imgs.shape[1]) if one_img else (imgs.shape[1], imgs.shape[2])
-    if out is None:
-        out = torch.empty((batch, row_count, final_w, 3), dtype=torch.uint8, device=dev)
-    nbytes = _native.lib().apap_warp_batch_workspace_bytes(mrows, mcols, final_w, final_h, batch)
-    if work is None or work.numel() < nbytes:
-        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    c_ptr, c_stride, ch, cw = None, 0, 0, 0
-    if centers is not None:
-        one_c = centers.dim() == 3
-        ch, cw = (centers.shape[0], centers.shape[1]) if one_c else (centers.shape[1], centers.shape[2])
-        c_ptr, c_stride = centers.data_ptr(), 0 if one_c else ch * cw * 3
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _native.check(_native.lib().apap_warp_batch_device(
-        _native._h(ctx), imgs.data_ptr(), 0 if one_img else ih * iw * 3, ih, iw, c_ptr, c_stride, ch, cw, H.data_ptr(), mrows, mcols,
-        mesh_w.data_ptr(), mesh_w.numel(), mesh_h.data_ptr(), mesh_h.numel(), final_w, final_h, off_x, off_y, row_begin, row_count,
-        out.data_ptr(), row_count * final_w * 3, None if hinv_out is None else hinv_out.data_ptr(), batch, int(phases),
-        work.data_ptr(), work.numel(), status.data_ptr(), ctypes.c_void_p(stream)))
-    return out, status
-
-
-class WarpPlan:
-    """One mesh / canvas geometry's warp workspace, kept between pairs (what the resident callers - ``Pipeline``, ``bench.py`` -
-    hold): the canvas row / column -> cell tables are built ONCE, here (``APAP_WARP_GEOMETRY``: they depend on the edges,
-    the canvas size and the offsets only); ``solve()`` is the per-cell solve whose tail leaves every cell warp ready in
-    this workspace (``apap_solve_warp_batch_device``); ``cells()`` does that for a grid that came from elsewhere
-    (``APAP_WARP_CELLS``); ``gather()`` is K3 alone (``APAP_WARP_GATHER``).  ``batch`` pairs share the geometry."""
-
-    def __init__(self, mesh, shape, final_w, final_h, off_x, off_y, dev, batch=1, ctx=None):
-        self.rows, self.cols = shape
-        self.geo = (int(final_w), int(final_h), int(off_x), int(off_y))
-        self.dev, self.batch, self.ctx = dev, int(batch), ctx
-        self.mesh_w = torch.from_numpy(np.ascontiguousarray(mesh[0], dtype=np.float64)).to(dev)
-        self.mesh_h = torch.from_numpy(np.ascontiguousarray(mesh[1], dtype=np.float64)).to(dev)
-        self.nbytes = _native.lib().apap_warp_batch_workspace_bytes(self.rows, self.cols, self.geo[0], self.geo[1], self.batch)
-        if not self.nbytes:
-            raise ValueError("WarpPlan: bad geometry")
-        self.work = torch.zeros(self.nbytes, dtype=torch.uint8, device=dev)
-        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._phase(_native.WARP_GEOMETRY)
-        # The kernels only OR bits into the status word.  What the geometry phase found (bit 1: the edges do not cover the
-        # canvas) holds for the plan's whole life and is kept apart; the word itself then serves one pair at a time
-        # (begin() before a pair's phases, status_word() after them), so that one pair's singular grid is not every later pair's.
-        self.geo_status = int(self.status.cpu()[0])
-        self.status.zero_()
-
-    def begin(self):
-        """Clear the per-pair status bits (singular cell, unprepared workspace) before a pair's phases."""
-        self.status.zero_()
-
-    def status_word(self):
-        """This pair's status bits together with the geometry phase's (synchronises)."""
-        return int(self.status.cpu()[0]) | self.geo_status
-
-    def _phase(self, phases, imgs=None, H=None, out=None, centers=None, rows=None, hinv_out=None):
-        fw, fh, ox, oy = self.geo
-        row_begin, row_count = (0, fh) if rows is None else rows
-        i_ptr, i_stride, ih, iw = None, 0, 0, 0
-        if imgs is not None:
-            one = imgs.dim() == 3
-            ih, iw = (imgs.shape[0], imgs.shape[1]) if one else (imgs.shape[1], imgs.shape[2])
-            i_ptr, i_stride = imgs.data_ptr(), 0 if one else ih * iw * 3
-        c_ptr, c_stride, ch, cw = None, 0, 0, 0
-        if centers is not None:
-            one_c = centers.dim() == 3
-            ch, cw = (centers.shape[0], centers.shape[1]) if one_c else (centers.shape[1], centers.shape[2])
-            c_ptr, c_stride = centers.data_ptr(), 0 if one_c else ch * cw * 3
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        _native.check(_native.lib().apap_warp_batch_device(
-            _native._h(self.ctx), i_ptr, i_stride, ih, iw, c_ptr, c_stride, ch, cw, None if H is None else H.data_ptr(), self.rows,
-            self.cols, self.mesh_w.data_ptr(), self.mesh_w.numel(), self.mesh_h.data_ptr(), self.mesh_h.numel(), fw, fh, ox, oy,
-            row_begin, row_count, None if out is None else out.data_ptr(), row_count * fw * 3,
-            None if hinv_out is None else hinv_out.data_ptr(), self.batch, int(phases), self.work.data_ptr(), self.nbytes,
-            self.status.data_ptr(), ctypes.c_void_p(stream)))
-
-    def solve(self, tables, denorms, vertices, gamma, sigma, out=None, work=None):
-        """``tables`` (B, n, 32) or (n, 32), ``denorms`` (B, 36) or (36,), ``vertices`` (cells, 2) -> H (B * cells, 9) float32, and
-        every cell's inverse / record / exact floats in this plan's workspace."""
-        if not tables.is_cuda:
-            raise _native.ApapError(_native.ERR_NO_DEVICE, "WarpPlan.solve needs CUDA/HIP tensors; there is no CPU fallback")
-        n = tables.shape[-2]
-        cells = self.rows * self.cols
-        if vertices.shape[0] != cells:
-            raise ValueError(f"WarpPlan.solve: {vertices.shape[0]} vertices for a {self.rows} x {self.cols} mesh")
-        H = out if out is not None else torch.empty((self.batch * cells, 9), dtype=torch.float32, device=self.dev)
-        lib = _native.lib()
-        nb = max(lib.apap_solve_batch_workspace_bytes(_native._h(self.ctx), n, cells, self.batch), 256)
-        if work is None or work.numel() < nb:
-            work = torch.empty(nb, dtype=torch.uint8, device=self.dev)
-        fw, fh, ox, oy = self.geo
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        _native.check(lib.apap_solve_warp_batch_device(
-            _native._h(self.ctx), tables.data_ptr(), n, vertices.data_ptr(), 0, float(gamma), float(sigma), denorms.data_ptr(),
-            H.data_ptr(), self.batch, work.data_ptr(), work.numel(), self.rows, self.cols, self.mesh_w.data_ptr(), self.mesh_w.numel(),
-            self.mesh_h.data_ptr(), self.mesh_h.numel(), fw, fh, ox, oy, self.work.data_ptr(), self.nbytes, self.status.data_ptr(),
-            ctypes.c_void_p(stream)))
-        return H
-
-    def cells(self, H, hinv_out=None):
-        """Per-cell set-up from a grid that was not solved into this plan (``H`` (B * cells, 9) float32)."""
-        self._phase(_native.WARP_CELLS, H=H, hinv_out=hinv_out)
-
-    def gather(self, imgs, out=None, centers=None, rows=None):
-        """K3: ``imgs`` (B, h, w, 3) or (h, w, 3) -> canvases (B, rows, final_w, 3)."""
-        fw, fh, _, _ = self.geo
-        n = fh if rows is None else rows[1]
-        if out is None:
-            out = torch.empty((self.batch, n, fw, 3), dtype=torch.uint8, device=self.dev)
-        self._phase(_native.WARP_GATHER, imgs=imgs, out=out, centers=centers, rows=rows)
-        return out
 
 
 # Rehearsals only (tests/_dist_gpu_ranks.py, tests/test_dist_gloo.py): True = a process group of ONE rank does not take the
@@ -253,6 +67,8 @@ class ShardedSolver:
     No multi-GPU hardware was available to this builder: the rule is a model, and ``bench.py`` times both forms on
     whatever it runs on.  What hides the collective at any size is ``step()``: the gather runs beside the rank's own
     warp band.  Every buffer of the step (shard grids, gather buffers, scratch, status) is allocated here, once.
+    ``status`` (``status_word()``): the device status word of the solver's warps, warp plan's geometry bits included.  It is
+    sticky: the kernels OR bits in over the solver's whole life and nothing clears them, so one check covers every step.
 
     ``same_bits=True`` makes the shards sum every cell's keypoints in the order the whole mesh would on one GPU
     (``APAP_OPT_PLAN_CELLS``): the gathered grid then equals the single-GPU grid bit for bit for any number of
@@ -319,10 +135,7 @@ class ShardedSolver:
         self._pending = []
         self._solve_kw = dict(self._kw)
         if solve_fn is hip_solve:                   # the engine's scratch: sized once for the larger launch
-            lib = _native.lib()
-            nb = max([max(lib.apap_solve_workspace_bytes(_native._h(ctx), self.n, v.shape[0]),
-                          lib.apap_solve_batch_workspace_bytes(_native._h(ctx), self.n, v.shape[0], 1), 256) if v.shape[0] else 256
-                      for v in self._vert])
+            nb = max(solve_workspace_bytes(ctx, self.n, v.shape[0]) for v in self._vert)
             self._solve_kw["work"] = torch.empty(nb, dtype=torch.uint8, device=dev)
         # the resident warp form (default engine, bands aligned to the rank's mesh rows): a WarpPlan over the rank's OWN mesh
         # rows - canvas row / column tables built once, the per-cell half in the tail of the rank's solve -, so that a warp
@@ -335,9 +148,8 @@ class ShardedSolver:
         self._want_plan = bool(resident_warp)
 
     def status_word(self):
-        """The device status bits of this solver's warps (the plan's geometry bits included; synchronises)."""
-        geo = self._plan.geo_status if self._plan is not None else 0
-        return int(self.status.cpu()[0]) | geo
+        """``status`` as an int (synchronises)."""
+        return int(self.status.cpu()[0])
 
     def broadcast_inputs(self):
         """Keypoint table (n x 256 B) and de-normalisation block from rank 0 to every rank:
@@ -468,7 +280,7 @@ class ShardedSolver:
         self.mesh_h = torch.from_numpy(self._own_edges).to(self.dev)
         if self.warp_fn is hip_warp_rows:       # the engine's scratch and status word: once
             if self._make_plan() is None:       # (the plan carries its own)
-                nb = _native.lib().apap_warp_workspace_bytes(self._warp_shape[0], self._warp_shape[1], p.final_w, p.final_h)
+                nb = warp_workspace_bytes(self._warp_shape, p.final_w, p.final_h)
                 self._warp_kw = dict(self._kw, work=torch.empty(nb, dtype=torch.uint8, device=self.dev), status=self.status)
         else:
             self._warp_kw = dict(self._kw)
@@ -611,9 +423,7 @@ def warp_pairs(pairs, grids, dev, dist=None, warp_fn=hip_warp_batch, gather=Fals
         else:
             out, status = warp_fn(imgs, H, mesh_w, mesh_h, p0.final_w, p0.final_h, p0.off_x, p0.off_y, (rows, cols), **kw)
             word = int(status.cpu()[0]) if status is not None else 0
-        if word != 0:
-            code = _native.ERR_SINGULAR if word & 1 else _native.ERR_INDEX if word & 2 else _native.ERR_INVALID_ARG
-            raise _native._ERROR_CLASSES[code](code, "warp_pairs: device status word %d" % word)
+        _native.raise_for_status(word, "warp_pairs")
         canv = {k: out[i] for i, k in enumerate(mine)}
     if not gather:
         return canv

@@ -38,11 +38,7 @@ class Pipeline:
     """Resident APAP pass.  ``device``: HIP device index (-1 = current); ``ctx``: a ``_native.Context``."""
 
     def __init__(self, device=-1, ctx=None):
-        import sys
-        if _native._lib is not None and "torch" not in sys.modules:
-            raise _native.ApapError(_native.ERR_HIP, "cvx_proj_amd's library was loaded before torch was imported: this process already "
-                                                     "runs /opt/rocm's HIP runtime, torch would not see the GPU through it.  Import torch "
-                                                     "before the first call into cvx_proj_amd (or set APAP_HIP_PRELOAD_TORCH=1)")
+        from . import resident  # noqa: F401  (imported here, not at the top: `python -m cvx_proj_amd.apap` needs no torch)
         import torch
         if not torch.cuda.is_available():
             raise _native.ApapError(_native.ERR_NO_DEVICE, "Pipeline needs a HIP device; there is no CPU fallback")
@@ -134,7 +130,7 @@ class Pipeline:
         """The warp workspace of one mesh / canvas geometry: the canvas row / column -> cell tables are built when the geometry is
         first seen (they do not depend on H) and kept - a CLI run over the pictures of one case, or a caller streaming pairs of one
         size, meets a handful of geometries."""
-        from .dist import WarpPlan
+        from .resident import WarpPlan
         key = (rows, cols, fw, fh, ox, oy, mesh.tobytes())
         plan = self._plans.get(key)
         if plan is None:
@@ -162,7 +158,8 @@ class Pipeline:
         left on the critical path (0.5 ms of the 1.04).  ``self.trace = True`` records HIP events at the stage boundaries
         (``self.device_marks``)."""
         import time
-        torch, lib = self.torch, _native.lib()
+        from .resident import hip_solve, hip_warp_batch, solve_workspace_bytes, warp_workspace_bytes
+        torch = self.torch
         t0 = time.perf_counter()
         early = None
         trace = self.trace
@@ -227,39 +224,34 @@ class Pipeline:
                 if plan is not None:
                     plan.vertices = d_vert.clone()
             d_H = self._get("H", (cells, 9), torch.float32)
-            nb = max(lib.apap_solve_workspace_bytes(self._h, n, cells), 256)
-            d_work = self._get("solve_work", (nb,), torch.uint8)
+            d_work = self._get("solve_work", (solve_workspace_bytes(self.ctx, n, cells),), torch.uint8)
             if plan is not None:
-                # the solve that leaves every cell warp ready in the plan's workspace (apap_solve_warp_batch_device)
-                plan.begin()        # this pair's status bits; the geometry phase's are kept in plan.geo_status
+                # the solve whose tail leaves every cell warp ready in the plan's workspace
+                plan.begin()        # the status word back to the geometry phase's bits
                 mark("small uploads done")
                 plan.solve(d_table, d_den, d_vert, float(gamma), float(sigma), out=d_H, work=d_work)
                 mark("solve done")
             else:
-                _native.check(lib.apap_solve_device(self._h, d_table.data_ptr(), n, d_vert.data_ptr(), cells, float(gamma), float(sigma),
-                                                    d_den.data_ptr(), d_H.data_ptr(), d_work.data_ptr(), nb, stream))
+                hip_solve(d_table, d_den, d_vert, gamma, sigma, ctx=self.ctx, out=d_H, work=d_work)
             # output stage apap.py:250-264 on the resident grid
             d_flat = self._get("flat", (cells, 9), torch.float64)
             d_status = plan.status if plan is not None else self._get("status", (1,), torch.int32)     # one word for every stage
             if plan is None:
                 d_status.zero_()
-            _native.check(lib.apap_flatten_device(self._h, d_H.data_ptr(), cells, d_flat.data_ptr(), d_status.data_ptr(), stream))
+            _native.check(_native.lib().apap_flatten_device(self._h, d_H.data_ptr(), cells, d_flat.data_ptr(), d_status.data_ptr(), stream))
             flat_ready = torch.cuda.Event()
             flat_ready.record(main)
             d_out = None
             if other_img is not None:
-                img = np.ascontiguousarray(other_img, dtype=np.uint8)
                 if early is not None:
                     d_img, d_cen, ev = early
                     main.wait_event(ev)
                     mark("image here")
-                    cen = center_img
                 else:
-                    d_img = self._up("img", img, torch.uint8)       # blocks the host while the GPU solves
+                    d_img = self._up("img", np.ascontiguousarray(other_img, dtype=np.uint8), torch.uint8)   # blocks the host while the GPU solves
                     d_cen = None
                     if center_img is not None:
-                        cen = np.ascontiguousarray(center_img, dtype=np.uint8)
-                        d_cen = self._up("center", cen, torch.uint8)
+                        d_cen = self._up("center", np.ascontiguousarray(center_img, dtype=np.uint8), torch.uint8)
                 d_out = self._get("canvas", (fh, fw, 3), torch.uint8)
                 if plan is not None:
                     plan.gather(d_img, out=d_out.view(1, fh, fw, 3), centers=d_cen)
@@ -267,14 +259,9 @@ class Pipeline:
                 else:
                     d_mw = self._up("mesh_w", mesh[0], torch.float64)
                     d_mh = self._up("mesh_h", mesh[1], torch.float64)
-                    wb = lib.apap_warp_workspace_bytes(rows, cols, fw, fh)
-                    d_ww = self._get("warp_work", (wb,), torch.uint8)
-                    _native.check(lib.apap_warp_batch_device(self._h, d_img.data_ptr(), 0, img.shape[0], img.shape[1],
-                                                             None if d_cen is None else d_cen.data_ptr(), 0,
-                                                             0 if d_cen is None else cen.shape[0], 0 if d_cen is None else cen.shape[1],
-                                                             d_H.data_ptr(), rows, cols, d_mw.data_ptr(), mesh.shape[1], d_mh.data_ptr(),
-                                                             mesh.shape[1], fw, fh, ox, oy, 0, fh, d_out.data_ptr(), 0, None, 1,
-                                                             _native.WARP_ALL, d_ww.data_ptr(), wb, d_status.data_ptr(), stream))
+                    d_ww = self._get("warp_work", (warp_workspace_bytes((rows, cols), fw, fh),), torch.uint8)
+                    hip_warp_batch(d_img, d_H.view(1, cells, 9), d_mw, d_mh, fw, fh, ox, oy, (rows, cols), out=d_out.view(1, fh, fw, 3),
+                                   centers=d_cen, ctx=self.ctx, work=d_ww, status=d_status)
             # the status word follows the last kernel into page-locked memory: read after the final synchronisation, no copy of its own
             if getattr(self, "_status_host", None) is None:
                 self._status_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
@@ -311,7 +298,7 @@ class Pipeline:
                     flat = self._flat_host[:cells * 9].numpy().reshape(cells, 9).copy()
                 canvas = self._down(d_out) if d_out is not None else None      # (synchronises the main stream)
             main.synchronize()
-            status = int(self._status_host[0]) | (plan.geo_status if plan is not None else 0)
+            status = int(self._status_host[0])
             grid = self._down(d_H).reshape(rows, cols, 3, 3) if want_grid else None
         t3 = time.perf_counter()
         if marks:
@@ -319,11 +306,5 @@ class Pipeline:
             self.device_marks = [(n, marks[0][1].elapsed_time(e) * 1e3) for n, e in marks]
         self.timeline = {"host_setup_ms": (t1 - t0) * 1e3, "upload_and_enqueue_ms": (t2 - t1) * 1e3,
                          "sync_and_download_ms": (t3 - t2) * 1e3, "total_ms": (t3 - t0) * 1e3}
-        if status & 1:
-            raise _native.ApapSingularError(_native.ERR_SINGULAR, "Singular matrix")
-        if status & 4:
-            raise _native.ApapValueError(_native.ERR_INVALID_ARG, "warp workspace without lookup tables for this geometry")
-        if status & 2:
-            raise _native.ApapIndexError(_native.ERR_INDEX, "index 0 is out of bounds for axis 0 with size 0 (mesh edges do not "
-                                                             "cover the canvas)")
+        _native.raise_for_status(status, "Pipeline.run_pair")
         return (flat, canvas, grid) if want_grid else (flat, canvas)

@@ -1,0 +1,190 @@
+"""The resident (``*_device``) entry points of ``libapap_hip.so`` on torch tensors, launched on the current stream of the
+tensors' device: every solve through ``apap_solve_batch_device`` or ``apap_solve_warp_batch_device``, every warp through
+``apap_warp_batch_device`` (the C ABI's single-pair forms wrap these).  ``pipeline`` and ``dist`` reach the GPU through this
+module.  No CPU fallback.  Importing it in a process that loaded the library before torch raises ``_native.ApapError``."""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _native
+
+if _native._lib is not None and not _native._torch_at_load:
+    raise _native.ApapError(_native.ERR_HIP, "cvx_proj_amd's library was loaded before torch was imported: torch cannot see the GPU "
+                                             "in this process.  Import torch first (or set APAP_HIP_PRELOAD_TORCH=1)")
+
+import torch  # noqa: E402
+
+
+def solve_workspace_bytes(ctx, n, cells, batch=1):
+    """Scratch of a solve of ``batch`` pairs of ``n`` keypoints over ``cells`` cells (at least 256 bytes)."""
+    return max(_native.lib().apap_solve_batch_workspace_bytes(_native._h(ctx), n, cells, batch), 256)
+
+
+def warp_workspace_bytes(shape, final_w, final_h, batch=1):
+    """Workspace of a warp of ``batch`` pairs over a ``shape`` = (rows, cols) mesh onto a final_w x final_h canvas."""
+    return _native.lib().apap_warp_batch_workspace_bytes(shape[0], shape[1], final_w, final_h, batch)
+
+
+def _scratch(work, nbytes, dev):
+    """``work`` when it holds ``nbytes``, else a new uint8 tensor of that size."""
+    return work if work is not None and work.numel() >= nbytes else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _needs_device(t, who):
+    if not t.is_cuda:
+        raise _native.ApapError(_native.ERR_NO_DEVICE, f"{who} needs CUDA/HIP tensors; there is no CPU fallback")
+
+
+def _solve(tables, denorms, vertices, gamma, sigma, batch, ctx=None, out=None, work=None):
+    """``apap_solve_batch_device``: ``batch`` pairs (``tables`` (batch, n, 32) or (n, 32), ``denorms`` (batch, 36) or (36,)) over
+    one set of ``vertices`` (cells, 2) -> H (batch * cells, 9) float32.  ``out`` and ``work`` are used when large enough."""
+    n, cells, dev = tables.shape[-2], vertices.shape[0], tables.device
+    H = out[:batch * cells] if out is not None and out.shape[0] >= batch * cells else \
+        torch.empty((batch * cells, 9), dtype=torch.float32, device=dev)
+    if cells == 0:
+        return H
+    work = _scratch(work, solve_workspace_bytes(ctx, n, cells, batch), dev)
+    _native.check(_native.lib().apap_solve_batch_device(_native._h(ctx), tables.data_ptr(), n, vertices.data_ptr(), 0, cells,
+                                                        float(gamma), float(sigma), denorms.data_ptr(), H.data_ptr(), batch,
+                                                        work.data_ptr(), work.numel(), _stream(dev)))
+    return H
+
+
+def _image(t):
+    """(pointer, stride in bytes, h, w) of one (h, w, 3) image shared by every pair, of a (B, h, w, 3) stack, or of None."""
+    if t is None:
+        return None, 0, 0, 0
+    if t.dim() == 3:
+        return t.data_ptr(), 0, t.shape[0], t.shape[1]
+    return t.data_ptr(), t.shape[1] * t.shape[2] * 3, t.shape[1], t.shape[2]
+
+
+def _warp(ctx, phases, shape, mesh_w, mesh_h, final_w, final_h, off_x, off_y, batch, work, status, imgs=None, H=None, out=None,
+          centers=None, rows=None, hinv_out=None):
+    """``apap_warp_batch_device`` on ``work``'s device.  ``rows`` = (row_begin, row_count), default the whole canvas."""
+    row_begin, row_count = (0, final_h) if rows is None else rows
+    i_ptr, i_stride, ih, iw = _image(imgs)
+    c_ptr, c_stride, ch, cw = _image(centers)
+    _native.check(_native.lib().apap_warp_batch_device(
+        _native._h(ctx), i_ptr, i_stride, ih, iw, c_ptr, c_stride, ch, cw, None if H is None else H.data_ptr(), shape[0], shape[1],
+        mesh_w.data_ptr(), mesh_w.numel(), mesh_h.data_ptr(), mesh_h.numel(), final_w, final_h, off_x, off_y, row_begin, row_count,
+        None if out is None else out.data_ptr(), row_count * final_w * 3, None if hinv_out is None else hinv_out.data_ptr(), batch,
+        int(phases), work.data_ptr(), work.numel(), status.data_ptr(), _stream(work.device)))
+
+
+def hip_solve(table, denorm, vertices, gamma, sigma, ctx=None, out=None, work=None):
+    """Default ``solve_fn`` of :mod:`cvx_proj_amd.dist`: one pair, H (cells, 9) float32.  ``out`` (>= cells x 9 float32) and
+    ``work`` (uint8 scratch) are reused when given and large enough - a solver that runs every step keeps them - else allocated."""
+    _needs_device(table, "hip_solve")
+    return _solve(table, denorm, vertices, gamma, sigma, 1, ctx, out, work)
+
+
+def hip_solve_batch(tables, denorms, vertices, gamma, sigma, ctx=None):
+    """Several pairs (equal keypoint and cell counts, one shared mesh) in ONE launch:
+    ``tables`` (B, n, 32), ``denorms`` (B, 36), ``vertices`` (cells, 2) -> H (B, cells, 9)."""
+    _needs_device(tables, "hip_solve_batch")
+    batch = tables.shape[0]
+    return _solve(tables, denorms, vertices, gamma, sigma, batch, ctx).view(batch, vertices.shape[0], 9)
+
+
+def hip_warp_rows(img, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, row_begin, row_count, out_band, shape, ctx=None,
+                  work=None, status=None):
+    """Default ``warp_fn`` of :mod:`cvx_proj_amd.dist`: warps canvas rows ``[row_begin, row_begin + row_count)`` of one pair into
+    ``out_band``.  ``work`` / ``status`` are reused when given."""
+    _needs_device(img, "hip_warp_rows")
+    return hip_warp_batch(img, H.view(1, -1, 9), mesh_w, mesh_h, final_w, final_h, off_x, off_y, shape, out=out_band, ctx=ctx,
+                          work=work, status=status, rows=(row_begin, row_count))[1]
+
+
+def hip_warp_batch(imgs, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, shape, out=None, centers=None, ctx=None,
+                   work=None, status=None, phases=_native.WARP_ALL, rows=None, hinv_out=None):
+    """Backward warp of a BATCH of independent pairs in one set of launches (``apap_warp_batch_device``, grid.z = pair):
+    ``imgs`` (B, h, w, 3) uint8 - or (h, w, 3): one image for every pair -, ``H`` (B, cells, 9) float32 (what
+    ``hip_solve_batch`` returns), one set of edges, canvas size and offsets for all -> canvases (B, final_h, final_w, 3).
+    ``centers`` (B, ch, cw, 3) or (ch, cw, 3): the fused stitch (warp + paste + uniform_blend).  ``phases``: which of
+    geometry tables / per-cell set-up / gather run on ``work`` (a caller that keeps ``work`` runs the geometry once).
+    ``rows`` = (row_begin, row_count): a band of every canvas; ``out`` is then (B, row_count, final_w, 3)."""
+    _needs_device(H, "hip_warp_batch")
+    batch, dev = H.shape[0], H.device
+    if out is None:
+        out = torch.empty((batch, final_h if rows is None else rows[1], final_w, 3), dtype=torch.uint8, device=dev)
+    work = _scratch(work, warp_workspace_bytes(shape, final_w, final_h, batch), dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _warp(ctx, phases, shape, mesh_w, mesh_h, final_w, final_h, off_x, off_y, batch, work, status, imgs=imgs, H=H, out=out,
+          centers=centers, rows=rows, hinv_out=hinv_out)
+    return out, status
+
+
+class WarpPlan:
+    """One mesh / canvas geometry's warp workspace, kept between pairs (what the resident callers - ``Pipeline``, ``bench.py`` -
+    hold): the canvas row / column -> cell tables are built ONCE, here (``APAP_WARP_GEOMETRY``: they depend on the edges,
+    the canvas size and the offsets only); ``solve()`` is the per-cell solve whose tail leaves every cell warp ready in
+    this workspace (``apap_solve_warp_batch_device``); ``cells()`` does that for a grid that came from elsewhere
+    (``APAP_WARP_CELLS``); ``gather()`` is K3 alone (``APAP_WARP_GATHER``).  ``batch`` pairs share the geometry.
+    ``status``: the device status word of the plan's phases.  The geometry phase's bits (``geo_status``) hold for the plan's
+    life and stay in it; ``begin()`` drops the others (kernels only OR bits in) before a pair, so one pair's singular grid is
+    not every later pair's."""
+
+    def __init__(self, mesh, shape, final_w, final_h, off_x, off_y, dev, batch=1, ctx=None):
+        self.rows, self.cols = shape
+        self.geo = (int(final_w), int(final_h), int(off_x), int(off_y))
+        self.dev, self.batch, self.ctx = dev, int(batch), ctx
+        self.mesh_w = torch.from_numpy(np.ascontiguousarray(mesh[0], dtype=np.float64)).to(dev)
+        self.mesh_h = torch.from_numpy(np.ascontiguousarray(mesh[1], dtype=np.float64)).to(dev)
+        self.nbytes = warp_workspace_bytes(shape, self.geo[0], self.geo[1], self.batch)
+        if not self.nbytes:
+            raise ValueError("WarpPlan: bad geometry")
+        self.work = torch.zeros(self.nbytes, dtype=torch.uint8, device=dev)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._phase(_native.WARP_GEOMETRY)
+        self.geo_status = int(self.status.cpu()[0])      # the geometry phase's bits, what begin() re-seeds the word with
+
+    def begin(self):
+        """Drop the per-pair status bits (singular cell, unprepared workspace) before a pair's phases."""
+        self.status.fill_(self.geo_status)
+
+    def status_word(self):
+        """``status`` as an int (synchronises)."""
+        return int(self.status.cpu()[0])
+
+    def _phase(self, phases, **kw):
+        fw, fh, ox, oy = self.geo
+        _warp(self.ctx, phases, (self.rows, self.cols), self.mesh_w, self.mesh_h, fw, fh, ox, oy, self.batch, self.work,
+              self.status, **kw)
+
+    def solve(self, tables, denorms, vertices, gamma, sigma, out=None, work=None):
+        """``tables`` (B, n, 32) or (n, 32), ``denorms`` (B, 36) or (36,), ``vertices`` (cells, 2) -> H (B * cells, 9) float32, and
+        every cell's inverse / record / exact floats in this plan's workspace."""
+        _needs_device(tables, "WarpPlan.solve")
+        n = tables.shape[-2]
+        cells = self.rows * self.cols
+        if vertices.shape[0] != cells:
+            raise ValueError(f"WarpPlan.solve: {vertices.shape[0]} vertices for a {self.rows} x {self.cols} mesh")
+        H = out if out is not None else torch.empty((self.batch * cells, 9), dtype=torch.float32, device=self.dev)
+        work = _scratch(work, solve_workspace_bytes(self.ctx, n, cells, self.batch), self.dev)
+        fw, fh, ox, oy = self.geo
+        _native.check(_native.lib().apap_solve_warp_batch_device(
+            _native._h(self.ctx), tables.data_ptr(), n, vertices.data_ptr(), 0, float(gamma), float(sigma), denorms.data_ptr(),
+            H.data_ptr(), self.batch, work.data_ptr(), work.numel(), self.rows, self.cols, self.mesh_w.data_ptr(), self.mesh_w.numel(),
+            self.mesh_h.data_ptr(), self.mesh_h.numel(), fw, fh, ox, oy, self.work.data_ptr(), self.nbytes, self.status.data_ptr(),
+            _stream(self.dev)))
+        return H
+
+    def cells(self, H, hinv_out=None):
+        """Per-cell set-up from a grid that was not solved into this plan (``H`` (B * cells, 9) float32)."""
+        self._phase(_native.WARP_CELLS, H=H, hinv_out=hinv_out)
+
+    def gather(self, imgs, out=None, centers=None, rows=None):
+        """K3: ``imgs`` (B, h, w, 3) or (h, w, 3) -> canvases (B, rows, final_w, 3)."""
+        fw, fh, _, _ = self.geo
+        if out is None:
+            out = torch.empty((self.batch, fh if rows is None else rows[1], fw, 3), dtype=torch.uint8, device=self.dev)
+        self._phase(_native.WARP_GATHER, imgs=imgs, out=out, centers=centers, rows=rows)
+        return out

@@ -45,6 +45,13 @@ extern "C" {
 #define APAP_ERR_INDEX 5       /* mesh edges do not cover the canvas (reference: IndexError) */
 #define APAP_ERR_WORKSPACE 6   /* caller-provided workspace too small                        */
 
+/* Bits of the device status word (the int *d_status of the resident entry points).  Kernels only OR bits into it, so a
+ * caller zeroes it before the calls whose findings it wants.  The host-buffer calls turn it into an error code, testing
+ * the bits in this order: SINGULAR -> APAP_ERR_SINGULAR, INDEX -> APAP_ERR_INDEX, UNPREPARED -> APAP_ERR_INVALID_ARG. */
+#define APAP_STATUS_SINGULAR 1   /* a cell's 3x3 inverse met an exact-zero pivot (reference: LinAlgError)        */
+#define APAP_STATUS_INDEX 2      /* mesh edges do not cover the canvas (reference: IndexError)                 */
+#define APAP_STATUS_UNPREPARED 4 /* a gather on a warp workspace without lookup tables for this mesh / canvas */
+
 /* Doubles per keypoint in the device point table (see apap_host_build_table). */
 #define APAP_TABLE_STRIDE 32
 /* Doubles in the de-normalisation block: inv(C2), C1, inv(N2), N1 (3x3 row-major each). */
@@ -302,7 +309,7 @@ int apap_solve_batch_device(apap_ctx *ctx, const double *d_tables, int n, const 
  * exact-path floats in the warp workspace - what APAP_WARP_CELLS would compute from the stored grid, bit for bit (one
  * device function serves both).  The warp that follows runs apap_warp_batch_device(... phases = APAP_WARP_GATHER ...) on that
  * workspace (APAP_WARP_GEOMETRY once per mesh / canvas geometry, before or after).  cells = mesh_rows * mesh_cols; the mesh
- * edges, canvas size and offsets are the warp's.  d_status: the warp's status word (bit 0: a singular cell).  Meshes beyond
+ * edges, canvas size and offsets are the warp's.  d_status: the warp's status word (APAP_STATUS_*).  Meshes beyond
  * 4096 edges per axis: APAP_ERR_INVALID_ARG (solve and warp them with the separate entry points). */
 int apap_solve_warp_batch_device(apap_ctx *ctx, const double *d_tables, int n, const double *d_vertices, long long vertices_stride,
                                  double gamma, double sigma, const double *d_denorms, float *d_H, int batch, void *d_work,
@@ -316,9 +323,8 @@ int apap_weights_device(apap_ctx *ctx, const double *d_table, int n, const doubl
 
 size_t apap_warp_workspace_bytes(int mesh_rows, int mesh_cols, int final_w, int final_h);
 
-/* Backward warp on resident data.  d_status: one int the kernels OR error bits into
- * (bit 0: singular cell, bit 1: index error); zero it before the call.  d_Hinv_out
- * may be NULL. */
+/* Backward warp on resident data.  d_status: the status word (APAP_STATUS_*); zero it
+ * before the call.  d_Hinv_out may be NULL. */
 int apap_warp_device(apap_ctx *ctx, const uint8_t *d_img, int img_h, int img_w, const float *d_Hfwd, int mesh_rows,
                      int mesh_cols, const double *d_mesh_w, int n_w, const double *d_mesh_h,
                      int n_h, int final_w, int final_h, int off_x, int off_y, uint8_t *d_out,
@@ -355,8 +361,8 @@ int apap_warp_rows_device(apap_ctx *ctx, const uint8_t *d_img, int img_h, int im
  *   APAP_WARP_GATHER    K3, reading what the other two left in the workspace.
  * A caller that warps many grids over one geometry runs GEOMETRY once and CELLS | GATHER per grid; APAP_WARP_ALL is the
  * one-call form.  A GATHER on a workspace whose tables were never built, or were built for another mesh shape / canvas
- * size, touches nothing and sets bit 2 (value 4) of *d_status (the tables carry a stamp of the sizes they were built for;
- * bits 0 and 1 are the singular cell and the uncovered canvas of the reference's LinAlgError / IndexError).  d_work: apap_warp_batch_workspace_bytes(...) bytes; the layout is private but stable between calls
+ * size, touches nothing and sets APAP_STATUS_UNPREPARED in *d_status (the tables carry a stamp of the sizes they were built
+ * for).  d_work: apap_warp_batch_workspace_bytes(...) bytes; the layout is private but stable between calls
  * with equal (mesh_rows, mesh_cols, final_w, final_h, batch). */
 #define APAP_WARP_GEOMETRY 1
 #define APAP_WARP_CELLS 2

@@ -32,8 +32,33 @@ def test_version_and_constants(native):
     assert int(re.search(r"#define APAP_TABLE_STRIDE (\d+)", text).group(1)) == native.TABLE_STRIDE
     assert int(re.search(r"#define APAP_DENORM_DOUBLES (\d+)", text).group(1)) == native.DENORM_DOUBLES
     for name, val in (("OK", 0), ("ERR_INVALID_ARG", 1), ("ERR_NO_DEVICE", 2), ("ERR_HIP", 3), ("ERR_SINGULAR", 4),
-                      ("ERR_INDEX", 5), ("ERR_WORKSPACE", 6)):
+                      ("ERR_INDEX", 5), ("ERR_WORKSPACE", 6), ("STATUS_SINGULAR", 1), ("STATUS_INDEX", 2), ("STATUS_UNPREPARED", 4)):
         assert int(re.search(rf"#define APAP_{name} (\d+)", text).group(1)) == val == getattr(native, name)
+    # the status bits have one definition: the public header's
+    internal = open(os.path.join(ROOT, "cvx_proj_amd", "csrc", "apap_internal.h")).read()
+    assert not re.search(r"Status\w*\s*=", internal)
+
+
+def test_raise_for_status_decodes_like_the_host_buffer_calls(native):
+    """_native.raise_for_status follows status_to_code of csrc/apap_capi.hip: the same bits tested in the same order, mapped
+    to the same error codes and exception classes, for every combination of the three bits."""
+    src = open(os.path.join(ROOT, "cvx_proj_amd", "csrc", "apap_capi.hip")).read()
+    body = src[src.index("int status_to_code("):]
+    body = body[:body.index("return APAP_OK;")]
+    order = re.findall(r"status & APAP_(STATUS_\w+)\)\s*return apap::fail\(APAP_(ERR_\w+)", body)
+    assert order == [("STATUS_SINGULAR", "ERR_SINGULAR"), ("STATUS_INDEX", "ERR_INDEX"), ("STATUS_UNPREPARED", "ERR_INVALID_ARG")]
+    classes = {"ERR_SINGULAR": native.ApapSingularError, "ERR_INDEX": native.ApapIndexError, "ERR_INVALID_ARG": native.ApapValueError}
+    assert native.raise_for_status(0, "t") is None
+    for word in range(1, 8):
+        bit, err = next((b, e) for b, e in order if word & getattr(native, b))
+        with pytest.raises(classes[err]) as e:
+            native.raise_for_status(word, "t")
+        assert type(e.value) is classes[err] and e.value.code == getattr(native, err), word
+        assert str(e.value).startswith(f"[apap_hip error {e.value.code}] t: ")
+        if bit == "STATUS_SINGULAR":
+            assert "Singular matrix" in str(e.value) and isinstance(e.value, np.linalg.LinAlgError)
+        if bit == "STATUS_INDEX":
+            assert "index 0 is out of bounds for axis 0 with size 0" in str(e.value) and isinstance(e.value, IndexError)
 
 
 def test_contexts_hold_the_options_not_the_process(native):
@@ -162,6 +187,23 @@ def test_plan_cells_option_fixes_the_launch_plan(native):
     with pytest.raises(native.ApapError):
         ctx.set("plan_cells", -1)
     ctx.close()
+
+
+def test_the_resident_modules_refuse_a_library_loaded_before_torch():
+    """One HIP runtime per process: a library loaded while torch was not yet imported makes torch blind to the GPU, whether
+    torch comes later or never.  cvx_proj_amd.resident (and so dist and Pipeline) refuses to load then; torch first works."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    load = "from cvx_proj_amd import _native; _native.lib(); "
+    dist, pipe = "import cvx_proj_amd.dist", "from cvx_proj_amd.pipeline import Pipeline; Pipeline()"
+    cases = [(load, dist, "refused"), (load + "import torch", dist, "refused"), (load + "import torch", pipe, "refused"),
+             ("import torch; " + load, dist, "loaded")]
+    for setup, stmt, want in cases:
+        code = (f"{setup}\ntry: {stmt}\nexcept _native.ApapError as e: print('refused' if 'before torch' in str(e) else e)\n"
+                "else: print('loaded')")
+        r = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and r.stdout.strip() == want, (code, r.stdout, r.stderr[-1500:])
 
 
 def test_the_command_line_needs_no_torch():

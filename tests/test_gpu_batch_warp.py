@@ -3,6 +3,7 @@ apap.py:186-217 once per pair): ``apap_warp_batch_device`` (grid.z = pair) again
 (tests/golden/c5_warp_k*.npz, made by make_golden.py C5warp), against one launch per pair, and against the oracle;
 the separable phases (geometry tables once, per-cell set-up + gather per grid), bands, shared images, the fused stitch.
 Run on the GPU box: ``python -m pytest tests -m gpu``."""
+import copy
 import hashlib
 
 import numpy as np
@@ -66,7 +67,7 @@ def test_c5_batched_warp_vs_reference(native, golden):
     for k in range(4):
         assert torch.equal(again[k], canv[k]) and torch.equal(again2[3 - k], canv[k])
     # the kernels only OR bits into a plan's status word.  A singular grid on a kept plan must fail THAT call and not
-    # every later one on the same plan; what the geometry phase found is kept apart (plan.geo_status)
+    # every later one on the same plan; what the geometry phase found (plan.geo_status) stays in the word for the plan's life
     bad = [g.copy() for g in grids]
     bad[2][17, 5] = 0.0                    # one singular cell
     with pytest.raises(np.linalg.LinAlgError):
@@ -75,6 +76,22 @@ def test_c5_batched_warp_vs_reference(native, golden):
     assert list(plans.values()) == [plan] and plan.geo_status == 0 and plan.status_word() == 0
     for k in range(4):
         assert torch.equal(after[k], canv[k])
+    # row edges that stop short of the canvas: the geometry phase's bit is in .status from the start, after begin() and after
+    # a singular pair followed by a good one (the singular cell outranks it, like status_to_code ranks them)
+    short = [copy.copy(p) for p in pairs]
+    for p in short:
+        p.mesh = p0.mesh.copy()
+        p.mesh[1, -1] = p0.final_h - 5.0
+    splans = {}
+    with pytest.raises(np.linalg.LinAlgError):
+        warp_pairs(short, bad, dev, plans=splans)
+    (sp,) = splans.values()
+    assert sp.geo_status == native.STATUS_INDEX and sp.status_word() == native.STATUS_INDEX | native.STATUS_SINGULAR
+    sp.begin()
+    assert int(sp.status.cpu()[0]) == native.STATUS_INDEX == sp.status_word()
+    with pytest.raises(IndexError):
+        warp_pairs(short, grids, dev, plans=splans)
+    assert list(splans.values()) == [sp] and int(sp.status.cpu()[0]) == native.STATUS_INDEX == sp.status_word()
     # ... and another context is another plan (a plan is bound to its context's options)
     other = native.Context(warp_rows=4)
     warp_pairs(pairs, grids, dev, plans=plans, ctx=other)
@@ -417,7 +434,7 @@ def test_gather_on_an_unprepared_workspace_reports_and_touches_nothing(native):
                 out.fill_(7)
                 plan.gather(img, out=out)
                 torch.cuda.synchronize()
-                assert int(plan.status.cpu()[0]) == 4, (opts, what)
+                assert int(plan.status.cpu()[0]) == native.STATUS_UNPREPARED, (opts, what)
                 assert bool((out == 7).all()), (opts, what)
             plan.work.copy_(good)                 # and the prepared tables still serve
             plan.status.zero_()

@@ -149,4 +149,4 @@ def test_single_process_sharded_solver_keeps_a_warp_plan(native):
     s3 = ShardedSolver(q, dev)
     s3.solve()
     s3.warp()
-    assert s3._plan is None and not s3._aligned and int(s3.status.cpu()[0]) & 2
+    assert s3._plan is None and not s3._aligned and int(s3.status.cpu()[0]) == native.STATUS_INDEX == s3.status_word()
