@@ -280,8 +280,10 @@ __device__ __forceinline__ double cell_weight_sq_tab(double vx, double vy, doubl
 }
 
 // w^2 in float32 for the opt-in tolerance tier (APAP_OPT_WEIGHTS_F32 with APAP_OPT_MOMENTS = 24): v_sqrt_f32 and
-// v_exp_f32 (1 ulp each), 9 vector instructions instead of 24.  w^2 carries ~2e-7 relative error: the float32 grid moves by
-// at most one ulp in a few per cent of its entries (tests/studies/moments24_study.py), like the 24-sum table itself.
+// v_exp_f32 (1 ulp each), 9 vector instructions instead of 24.  With x = d * neg_scale the argument of the exp2, the relative
+// error of w^2 grows with |x| (the rounding of x itself) and with the float32 rounding of the coordinates; below x = -126
+// v_exp_f32 flushes the result to 0 (oracle/weight_spec.py states the bound).  K2 therefore
+// re-solves every cell whose trace falls below kTraceFloorW32 from float64 weights (the careful path).
 //   neg_scale = -2 log2(e) / sigma^2;  NaN coordinates give gamma^2 (v_max_f32 drops the NaN), as in the float64 chain
 __device__ __forceinline__ double cell_weight_sq_f32(float vx, float vy, float2 s, float neg_scale, float gamma2) {
     const float dx = vx - s.x;
@@ -289,6 +291,25 @@ __device__ __forceinline__ double cell_weight_sq_f32(float vx, float vy, float2 
     const float d = __builtin_amdgcn_sqrtf(__builtin_fmaf(dx, dx, dy * dy));
     return (double)fmaxf(__builtin_amdgcn_exp2f(d * neg_scale), gamma2);
 }
+
+// The gamma^2 that K1 clamps w^2 at.  exp(-d / sigma^2) <= 1, so from gamma = 1 on every weight IS gamma and any constant
+// weight gives the same singular vector: where gamma^2 would leave a chain's range (float32: 1.8e19^2 is inf; float64: the
+// sums and the squares K2 forms of them overflow long before 1.34e154^2 does) the chain takes 1 instead.  Below the cut the
+// value is gamma * gamma as ever (the default grids' bits).  The careful path works on gamma itself, never on this.
+constexpr double kGammaCutF64 = 0x1p128;
+__host__ __device__ inline double k1_gamma2(double gamma, bool w32) {
+    if (gamma >= (w32 ? 1.0 : kGammaCutF64)) return 1.0;
+    return gamma > 0.0 ? gamma * gamma : 0.0;
+}
+
+// K2 sends a cell to the careful path when its trace is below this (or not finite).  Float64 weights: 1e-280, where the sums
+// of w^2 start to lose digits to underflow.  Float32 weights: 2^-40 - a cell above it has a largest w^2 of at least
+// 2^-40 / (n max_k |r_k|^2), so that its dominant weights are normal float32 numbers whose exponent argument is small enough
+// for the bound of oracle/weight_spec.py; cells below it (far-away keypoints, a float32 gamma^2 that underflows, a cluster
+// across x = -126 whose farther half v_exp_f32 flushes to 0) are the ones whose float32 weights can be wrong by their whole
+// size, and they get float64 weights instead.
+constexpr double kTraceFloorF64 = 1e-280;
+constexpr double kTraceFloorW32 = 0x1p-40;
 
 // A 24-sum table (apap_host_build_table24) carries this quiet-NaN bit pattern in column 28 of every row; the kernels refuse
 // a table of the other layout (their grids come out NaN) instead of reading one layout as the other.
@@ -1165,7 +1186,8 @@ __device__ __forceinline__ void eigen_denorm_cell(const double (&m)[kMoments], c
                                                   int pick_rank, int careful, const double *__restrict__ table, int n,
                                                   double vx, double vy, double gamma, double inv_sigma,
                                                   float *__restrict__ out /* 9 floats, or nullptr */,
-                                                  const WarpEmit &we, int pair, int cell, const CellEdges &edges, bool m24 = false) {
+                                                  const WarpEmit &we, int pair, int cell, const CellEdges &edges, bool m24 = false,
+                                                  double trace_floor = kTraceFloorF64) {
     // A^T W^2 A = [[S0, 0, S1], [0, S0, S2], [S1^T, S2^T, S3]]  (3x3 blocks)
     double a[45];
 #pragma unroll
@@ -1187,7 +1209,8 @@ __device__ __forceinline__ void eigen_denorm_cell(const double (&m)[kMoments], c
     const double gap_tol = kGapTol * trace;
     // The sums are of w^2: where every weight is below ~1e-140 they underflow (partly or entirely)
     // although the weights themselves - what the reference's SVD works on - are ordinary numbers.
-    const bool underflowed = !(trace >= 1e-280) || !(trace < 1.797e308);   // also NaN / inf sums
+    // (Float32 weights: a higher floor, see kTraceFloorW32.)
+    const bool underflowed = !(trace >= trace_floor) || !(trace < 1.797e308);   // also NaN / inf sums
 
     double h[9];
     bool have = false;
@@ -1257,7 +1280,7 @@ __global__ __launch_bounds__(64) void k_eigen_denorm(const double *__restrict__ 
                                                      float *__restrict__ H, BatchStride bs,
                                                      const double *__restrict__ table, int n,
                                                      const double *__restrict__ vertices, double gamma,
-                                                     double inv_sigma, int careful, const WarpEmit we) {
+                                                     double inv_sigma, int careful, double trace_floor, const WarpEmit we) {
     moments += (long long)blockIdx.z * bs.moments;
     denorm += (long long)blockIdx.z * bs.denorm;
     H += (long long)blockIdx.z * bs.H;
@@ -1297,7 +1320,7 @@ __global__ __launch_bounds__(64) void k_eigen_denorm(const double *__restrict__ 
     }
     float *out = cell < cells ? H + (size_t)cell * 9 : nullptr;
     eigen_denorm_cell<kUseInverseIteration>(m, denorm, pick_rank, careful, table, n, vertices[2 * cc], vertices[2 * cc + 1],
-                                            gamma, inv_sigma, out, we, (int)blockIdx.z, cell, edges, kM24);
+                                            gamma, inv_sigma, out, we, (int)blockIdx.z, cell, edges, kM24, trace_floor);
     if (!layout_ok && out) {      // the caller's table has the other layout (wave-uniform): nothing computed from it is an answer
 #pragma unroll
         for (int k = 0; k < 9; ++k) out[k] = __builtin_nanf("");
@@ -1341,7 +1364,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(const double *__r
     __shared__ double s_denorm[APAP_DENORM_DOUBLES];
     const double den_stage = denorm[min(tid, APAP_DENORM_DOUBLES - 1)];
     static_assert(kExpN % kSmallThreads == 0, "exp table entries per thread");
-    const double gamma2 = gamma > 0.0 ? gamma * gamma : 0.0;
+    const double gamma2 = k1_gamma2(gamma, false);
     const double scaled_inv_sigma2 = 2.0 * inv_sigma * kExpScale;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2770,7 +2793,8 @@ static int solve_batch_impl(apap_ctx *ctx, const double *d_tables, int n, const 
     hipStream_t s = (hipStream_t)stream;
     const double inv_sigma = 1.0 / (sigma * sigma);  // apap.py:142
     const double inv_sigma2 = 2.0 * inv_sigma;       // K1 evaluates exp(-2 d / sigma^2) = w^2
-    const double gamma2 = gamma > 0.0 ? gamma * gamma : 0.0;
+    const double gamma2 = k1_gamma2(gamma, w32);
+    const double trace_floor = w32 ? kTraceFloorW32 : kTraceFloorF64;   // K2's route to the careful path (see kTraceFloorW32)
     double *moments = (double *)d_work;
     BatchStride bs;
     bs.table = (long long)n * APAP_TABLE_STRIDE;
@@ -2823,7 +2847,7 @@ static int solve_batch_impl(apap_ctx *ctx, const double *d_tables, int n, const 
     {
         ProfScope prof(ctx, APAP_PROF_EIGEN, s);
         const dim3 grid(p.cell_tiles, 1, batch);
-#define APAP_K2_ARGS moments, p.splits, cells, p.cells_pad, d_denorms, pick_rank, d_H, bs, d_tables, n, d_vertices, gamma, inv_sigma, careful, we
+#define APAP_K2_ARGS moments, p.splits, cells, p.cells_pad, d_denorms, pick_rank, d_H, bs, d_tables, n, d_vertices, gamma, inv_sigma, careful, trace_floor, we
         const bool jacobi = apap::opt(ctx, APAP_OPT_EIGEN_SOLVER) == APAP_EIGEN_JACOBI;
         if (jacobi && m24) hipLaunchKernelGGL((k_eigen_denorm<false, true>), grid, dim3(64), 0, s, APAP_K2_ARGS);
         else if (jacobi) hipLaunchKernelGGL((k_eigen_denorm<false, false>), grid, dim3(64), 0, s, APAP_K2_ARGS);

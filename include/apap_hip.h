@@ -142,13 +142,26 @@ typedef struct apap_ctx apap_ctx;
                                       reference's.  24 (opt-in): the 24 sums of the EXACT products (SURVEY.md section 8a:
                                       [[S0,0,Sx],[0,S0,Sy],[Sx,Sy,Sr]]) - a quarter less matrix-pipe work in K1, a fifth less
                                       slab traffic; NOT bit-identical: one float32 ulp in a few per cent of a grid's entries
-                                      (reprojection-RMSE delta < 1e-4 px on BASELINE's configurations, tests/test_gpu_moments24.py).
+                                      on BASELINE's configurations (tests/test_gpu_moments24.py), where gamma^2 = 0.25 floors
+                                      every weight.  Off them (gamma ~ 0, small sigma) the sums' rounding moves H by up to
+                                      ~ eps x the cell's condition number: far more than one ulp on ill-conditioned cells, still
+                                      within that bound (tests/test_gpu_weight_range.py).
                                       The device entry points then expect the table of apap_host_build_table24 (a table of the
                                       other layout gives NaN grids); the host-buffer entry points build the right one themselves.
                                       No fused small-mesh launch, no VALU variant in this mode                             */
 #define APAP_OPT_WEIGHTS_F32 12     /* 0 (default).  1 (opt-in, honoured with APAP_OPT_MOMENTS = 24 only): K1 evaluates w^2 in
-                                      float32 (v_sqrt_f32, v_exp_f32: ~2e-7 relative) instead of float64; the sums stay
-                                      float64.  Same class of result as MOMENTS = 24 alone (one float32 ulp here and there)  */
+                                      float32 (v_sqrt_f32, v_exp_f32) instead of float64; the sums stay float64.  With
+                                      w^2 = 2^x, x = -2 log2(e) d / sigma^2, the relative error of a w^2 is at most
+                                      (6 |x| + 4) 2^-24 + 2 log2(e) ln(2) c / sigma^2 (c: what the float32 rounding of the
+                                      vertex and keypoint coordinates moves d by, <= 2^-24 (|v| + |s|) per axis): ~2e-7 only
+                                      near x = 0, 5e-5 at x = -126; below x = -126 w^2 is 0 (v_exp_f32 flushes subnormals).
+                                      So K2 re-solves every cell whose trace is below 2^-40 from float64 weights (the careful
+                                      path, with APAP_OPT_CAREFUL = 1): the cells kept on float32 weights are those whose
+                                      normal matrix is within the bound above (oracle/weight_spec.py, tests/test_weight_spec.py).
+                                      Their H then differs from the default's by up to ~ bound x the cell's condition number;
+                                      with gamma^2 flooring every weight (BASELINE's gamma = 0.5, sigma = 100: |x| <= 2) that
+                                      is the class of MOMENTS = 24 alone (one float32 ulp here and there).  gamma >= 1 makes
+                                      every weight gamma: this chain then clamps at 1 (gamma^2 overflows float32 at 1.8e19)  */
 #define APAP_OPT_COUNT 13
 apap_ctx *apap_ctx_create(void);
 void apap_ctx_destroy(apap_ctx *ctx); /* frees the pooled device buffers and pending events; NULL is a no-op */
