@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("APAP_HIP_LIB") or os.path.join(_HERE, "libapap_hip.so
 OK, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_SINGULAR, ERR_INDEX, ERR_WORKSPACE = range(7)
 ABI_VERSION = 6          # APAP_ABI_VERSION of include/apap_hip.h
 # kernel slots of apap_ctx_profile_read (include/apap_hip.h)
-PROF_NAMES = ("assemble", "eigen", "invert", "lut", "warp", "eq_hist", "eq_apply", "ransac")
+PROF_NAMES = ("assemble", "eigen", "invert", "lut", "warp", "eq_hist", "eq_apply", "ransac", "spectral")
 PROF_SLOTS = len(PROF_NAMES)
 TABLE_STRIDE = 32
 DENORM_DOUBLES = 36
@@ -61,6 +61,7 @@ _ERROR_CLASSES = {ERR_SINGULAR: ApapSingularError, ERR_INDEX: ApapIndexError, ER
 
 # bits of the device status word of the resident entry points (APAP_STATUS_* of include/apap_hip.h)
 STATUS_SINGULAR, STATUS_INDEX, STATUS_UNPREPARED = 1, 2, 4
+STATUS_NO_CONVERGENCE = 8     # the spectral eigen-solver hit its restart cap (a warning, not an error)
 
 
 def raise_for_status(word, who):
@@ -153,6 +154,12 @@ SIGNATURES = {
     "apap_ransac_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "apap_ransac_device": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, C.c_int, C.c_ulonglong, _vp, _vp, _vp, _vp,
                                      C.c_size_t, _vp]),
+    "apap_spectral_weights": (C.c_int, [_vp, _f32p, _f32p, _f32p, _f32p, C.c_int, _f64p, _f64p, _f32p, _f32p, _f64p, _f32p,
+                                        _f32p, _f64p, C.c_int]),
+    "apap_spectral_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "apap_spectral_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _f64p, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       C.c_size_t, _vp]),
+    "apap_spectral_affinity": (C.c_int, [_vp, _f32p, _f32p, _f32p, _f32p, C.c_int, _f64p, _f64p, _f64p, C.c_int]),
 }
 
 _lib = None
@@ -519,3 +526,65 @@ def find_homography_ransac(src, dst, thresh=5.0, iterations=RANSAC_ITERATIONS, s
     if inliers.value < 4:
         return None, mask.reshape(-1, 1)
     return H.reshape(3, 3), mask.reshape(-1, 1)
+
+
+# ---------------------------------------------------------------- spectral weights (spectral_method.py:66-133)
+SPECTRAL_DIM = 128
+SPECTRAL_PARAMS = 6          # epi_weight, affinity_eps, aff_thresh, em_radius, score_thresh, max_restarts
+SPECTRAL_INFO = 6            # lambda, gap, steps, status, restarts, residual
+
+
+def spectral_params(epi_weight=0.5, affinity_eps=30.0, aff_thresh=0.5, em_radius=6.0, score_thresh=0.4, max_restarts=0):
+    """The ``params`` block of the spectral entry points (defaults: the reference's options.py; max_restarts 0 = 30)."""
+    return np.array([epi_weight, affinity_eps, aff_thresh, em_radius, score_thresh, max_restarts], dtype=np.float64)
+
+
+def _spectral_inputs(src, dst, c_feats, o_feats, F):
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    dst = np.ascontiguousarray(dst, dtype=np.float32)
+    c = np.ascontiguousarray(c_feats, dtype=np.float32)
+    o = np.ascontiguousarray(o_feats, dtype=np.float32)
+    F = np.ascontiguousarray(F, dtype=np.float64)
+    if src.ndim != 2 or src.shape[1] != 2 or dst.shape != src.shape:
+        raise ValueError(f"src/dst must both be (n, 2); got {src.shape} and {dst.shape}")
+    n = src.shape[0]
+    if c.shape != (n, SPECTRAL_DIM) or o.shape != (n, SPECTRAL_DIM):
+        raise ValueError(f"descriptors must be ({n}, {SPECTRAL_DIM}); got {c.shape} and {o.shape}")
+    if F.shape != (3, 3):
+        raise ValueError(f"F must be 3 x 3; got {F.shape}")
+    if n == 0:
+        raise ValueError("no matches: the reference's np.hstack of the empty point arrays fails (spectral_method.py:105)")
+    return src, dst, c, o, F, n
+
+
+def spectral_weights(src, dst, c_feats, o_feats, F, params, Hg=None, mask=None, device=-1, ctx=None):
+    """``apap_spectral_weights``: (segment float64, ransac_mask float32, original_mask float32, info (6,) float64)."""
+    src, dst, c, o, F, n = _spectral_inputs(src, dst, c_feats, o_feats, F)
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    if params.shape != (SPECTRAL_PARAMS,):
+        raise ValueError(f"params must hold {SPECTRAL_PARAMS} values")
+    Hg = None if Hg is None else np.ascontiguousarray(Hg, dtype=np.float32)
+    if Hg is not None and Hg.shape != (3, 3):
+        raise ValueError(f"Hg must be 3 x 3; got {Hg.shape}")
+    mask = None if mask is None or Hg is not None else np.ascontiguousarray(mask, dtype=np.float32).ravel()
+    if mask is not None and mask.shape != (n,):
+        raise ValueError(f"mask must hold {n} values; got {mask.shape}")
+    seg = np.empty(n, np.float64)
+    rm = np.empty(n, np.float32)
+    om = np.empty(n, np.float32)
+    info = np.empty(SPECTRAL_INFO, np.float64)
+    check(lib().apap_spectral_weights(_h(ctx), _ptr(src, C.c_float), _ptr(dst, C.c_float), _ptr(c, C.c_float), _ptr(o, C.c_float),
+                                      n, _ptr(F, C.c_double), _ptr(params, C.c_double), _ptr(Hg, C.c_float), _ptr(mask, C.c_float),
+                                      _ptr(seg, C.c_double), _ptr(rm, C.c_float), _ptr(om, C.c_float), _ptr(info, C.c_double),
+                                      device))
+    return seg, rm, om, info
+
+
+def spectral_affinity(src, dst, c_feats, o_feats, F, params=None, device=-1, ctx=None):
+    """``apap_spectral_affinity``: the reference's dense M, (n, n) float64, n <= 8192."""
+    src, dst, c, o, F, n = _spectral_inputs(src, dst, c_feats, o_feats, F)
+    params = spectral_params() if params is None else np.ascontiguousarray(params, dtype=np.float64)
+    M = np.empty((n, n), np.float64)
+    check(lib().apap_spectral_affinity(_h(ctx), _ptr(src, C.c_float), _ptr(dst, C.c_float), _ptr(c, C.c_float), _ptr(o, C.c_float),
+                                       n, _ptr(F, C.c_double), _ptr(params, C.c_double), _ptr(M, C.c_double), device))
+    return M

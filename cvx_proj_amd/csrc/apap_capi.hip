@@ -710,3 +710,118 @@ int apap_find_homography_ransac(apap_ctx *ctx, const float *src, const float *ds
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ spectral weights (spectral_method.py:66-133)
+// The inputs and outputs of one call share one pooled device buffer (parts 256-byte aligned); the Lanczos workspace is a
+// second one.
+namespace {
+struct SpecIo {
+    size_t src, dst, c, o, F, Hg, mask, seg, rm, om, info, M, total;
+};
+SpecIo spec_io(int n, bool dense) {
+    SpecIo io{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    const size_t pts = (size_t)n * 2 * sizeof(float), feats = (size_t)n * APAP_SPECTRAL_DIM * sizeof(float);
+    io.src = take(pts);
+    io.dst = take(pts);
+    io.c = take(feats);
+    io.o = take(feats);
+    io.F = take(9 * sizeof(double));
+    io.Hg = take(9 * sizeof(float));
+    io.mask = take((size_t)n * sizeof(float));
+    io.seg = take((size_t)n * sizeof(double));
+    io.rm = take((size_t)n * sizeof(float));
+    io.om = take((size_t)n * sizeof(float));
+    io.info = take(APAP_SPECTRAL_INFO * sizeof(double));
+    io.M = take(dense ? (size_t)n * n * sizeof(double) : 0);
+    io.total = off;
+    return io;
+}
+
+int spec_upload(char *d, const SpecIo &io, const float *src, const float *dst, const float *c_feats, const float *o_feats, int n,
+                const double *F) {
+    const size_t pts = (size_t)n * 2 * sizeof(float), feats = (size_t)n * APAP_SPECTRAL_DIM * sizeof(float);
+    APAP_HIP_TRY(hipMemcpyAsync(d + io.src, src, pts, hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + io.dst, dst, pts, hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + io.c, c_feats, feats, hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + io.o, o_feats, feats, hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + io.F, F, 9 * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    return APAP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int apap_spectral_weights(apap_ctx *ctx, const float *src, const float *dst, const float *c_feats, const float *o_feats, int n,
+                          const double *F, const double *params, const float *Hg_or_null, const float *mask_in_or_null,
+                          double *segment_out, float *ransac_mask_out, float *original_mask_out, double *info_out, int device) {
+    if (!src || !dst || !c_feats || !o_feats || !F || !params || !segment_out || !ransac_mask_out || !original_mask_out || !info_out)
+        return apap::fail(APAP_ERR_INVALID_ARG, "apap_spectral_weights: null argument");
+    if (!Hg_or_null && !mask_in_or_null)
+        return apap::fail(APAP_ERR_INVALID_ARG, "apap_spectral_weights: no initial mask (neither Hg nor a mask): the reference's "
+                                                "init_ransac=False path fails on `None *= float` (spectral_method.py:131)");
+    if (n < 1 || n > (1 << 26)) return apap::fail(APAP_ERR_INVALID_ARG, "apap_spectral_weights: n=%d (need 1 .. 2^26 matches)", n);
+    PoolLock pl(ctx);
+    int dev;
+    int rc = select_device(device, &dev);
+    if (rc) return rc;
+    const SpecIo io = spec_io(n, false);
+    const size_t work_bytes = apap_spectral_workspace_bytes(n);
+    void *d_io, *d_work;
+    if ((rc = slot_get(pl.pool, S_AUX, io.total, dev, &d_io))) return rc;
+    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
+    char *d = (char *)d_io;
+    if ((rc = spec_upload(d, io, src, dst, c_feats, o_feats, n, F))) return rc;
+    if (Hg_or_null) APAP_HIP_TRY(hipMemcpyAsync(d + io.Hg, Hg_or_null, 9 * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    else APAP_HIP_TRY(hipMemcpyAsync(d + io.mask, mask_in_or_null, (size_t)n * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    rc = apap::spectral_run(ctx, (const float *)(d + io.src), (const float *)(d + io.dst), (const float *)(d + io.c),
+                            (const float *)(d + io.o), n, (const double *)(d + io.F), params,
+                            Hg_or_null ? (const float *)(d + io.Hg) : nullptr, Hg_or_null ? nullptr : (const float *)(d + io.mask),
+                            (double *)(d + io.seg), (float *)(d + io.rm), (float *)(d + io.om), (double *)(d + io.info), nullptr,
+                            d_work, work_bytes, nullptr, 1);
+    if (rc) {
+        (void)hipStreamSynchronize(nullptr);
+        return rc;
+    }
+    APAP_HIP_TRY(hipMemcpyAsync(segment_out, d + io.seg, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(ransac_mask_out, d + io.rm, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(original_mask_out, d + io.om, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(info_out, d + io.info, APAP_SPECTRAL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    return APAP_OK;
+}
+
+int apap_spectral_affinity(apap_ctx *ctx, const float *src, const float *dst, const float *c_feats, const float *o_feats, int n,
+                           const double *F, const double *params, double *M_out, int device) {
+    if (!src || !dst || !c_feats || !o_feats || !F || !params || !M_out)
+        return apap::fail(APAP_ERR_INVALID_ARG, "apap_spectral_affinity: null argument");
+    if (n < 1 || n > 8192) return apap::fail(APAP_ERR_INVALID_ARG, "apap_spectral_affinity: n=%d (the dense M is for 1 .. 8192 matches)", n);
+    PoolLock pl(ctx);
+    int dev;
+    int rc = select_device(device, &dev);
+    if (rc) return rc;
+    const SpecIo io = spec_io(n, true);
+    const size_t work_bytes = apap_spectral_workspace_bytes(n);
+    void *d_io, *d_work;
+    if ((rc = slot_get(pl.pool, S_AUX, io.total, dev, &d_io))) return rc;
+    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
+    char *d = (char *)d_io;
+    if ((rc = spec_upload(d, io, src, dst, c_feats, o_feats, n, F))) return rc;
+    rc = apap::spectral_affinity_run((const float *)(d + io.src), (const float *)(d + io.dst), (const float *)(d + io.c),
+                                     (const float *)(d + io.o), n, (const double *)(d + io.F), params, (double *)(d + io.M), d_work,
+                                     work_bytes, nullptr);
+    if (rc) {
+        (void)hipStreamSynchronize(nullptr);
+        return rc;
+    }
+    APAP_HIP_TRY(hipMemcpyAsync(M_out, d + io.M, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    return APAP_OK;
+}
+
+}  // extern "C"

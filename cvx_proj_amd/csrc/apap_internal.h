@@ -95,4 +95,14 @@ int warp_phase(apap_ctx *ctx, const uint8_t *d_img, int img_h, int img_w, const 
 
 constexpr int kMoments = 30;       // distinct sums of A^T W^2 A
 
+// The spectral weights (apap_spectral.hip).  spectral_run is apap_spectral_device; with sync_each = 1 (the host-buffer
+// entry point) it waits for every restart cycle and enqueues no more once the device reports convergence.
+int spectral_run(apap_ctx *ctx, const float *d_src, const float *d_dst, const float *d_c, const float *d_o, int n,
+                 const double *d_F, const double *params, const float *d_Hg, const float *d_mask, double *d_segment,
+                 float *d_ransac, float *d_original, double *d_info, int *d_status, void *d_work, size_t work_bytes,
+                 void *stream, int sync_each);
+// Set-up and the dense M (n x n doubles) on `stream`.
+int spectral_affinity_run(const float *d_src, const float *d_dst, const float *d_c, const float *d_o, int n, const double *d_F,
+                          const double *params, double *d_M, void *d_work, size_t work_bytes, void *stream);
+
 }  // namespace apap

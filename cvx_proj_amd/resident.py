@@ -188,3 +188,36 @@ class WarpPlan:
             out = torch.empty((self.batch, fh if rows is None else rows[1], fw, 3), dtype=torch.uint8, device=self.dev)
         self._phase(_native.WARP_GATHER, imgs=imgs, out=out, centers=centers, rows=rows)
         return out
+
+
+def spectral_workspace_bytes(n):
+    """Scratch of ``hip_spectral`` for ``n`` matches: O(n), no n x n buffer."""
+    return _native.lib().apap_spectral_workspace_bytes(n)
+
+
+def hip_spectral(src, dst, c_feats, o_feats, F, params, Hg=None, mask=None, status=None, ctx=None, work=None):
+    """``apap_spectral_device`` on the current stream of the tensors' device: calculate_M's weights of resident data.
+    src / dst (n, 2) float32, c_feats / o_feats (n, 128) float32, F (3, 3) float64, Hg (3, 3) float32 or ``mask`` (n,)
+    float32 on the device; ``params``: host ``_native.spectral_params(...)``.  Returns (segment float64, ransac_mask
+    float32, original_mask float32, info (6,) float64) as device tensors, not synchronised.  ``status`` (int32, 1
+    element) receives STATUS_NO_CONVERGENCE when the restart cap is hit (also in info[3])."""
+    _needs_device(src, "hip_spectral")
+    dev, n = src.device, src.shape[0]
+    for t, want in ((src, torch.float32), (dst, torch.float32), (c_feats, torch.float32), (o_feats, torch.float32),
+                    (F, torch.float64)):
+        if t.dtype != want or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"hip_spectral: inputs must be contiguous {want} tensors on {dev}")
+    if dst.shape != src.shape or c_feats.shape != (n, _native.SPECTRAL_DIM) or o_feats.shape != c_feats.shape or F.shape != (3, 3):
+        raise ValueError("hip_spectral: shapes (n, 2), (n, 2), (n, 128), (n, 128), (3, 3) expected")
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    seg = torch.empty(n, dtype=torch.float64, device=dev)
+    rm = torch.empty(n, dtype=torch.float32, device=dev)
+    om = torch.empty(n, dtype=torch.float32, device=dev)
+    info = torch.empty(_native.SPECTRAL_INFO, dtype=torch.float64, device=dev)
+    work = _scratch(work, spectral_workspace_bytes(n), dev)
+    _native.check(_native.lib().apap_spectral_device(
+        _native._h(ctx), src.data_ptr(), dst.data_ptr(), c_feats.data_ptr(), o_feats.data_ptr(), n, F.data_ptr(),
+        params.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), None if Hg is None else Hg.data_ptr(),
+        None if mask is None or Hg is not None else mask.data_ptr(), seg.data_ptr(), rm.data_ptr(), om.data_ptr(), info.data_ptr(),
+        None if status is None else status.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
+    return seg, rm, om, info

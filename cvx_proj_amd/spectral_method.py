@@ -1,0 +1,191 @@
+"""Spectral match weighting of the reference's ``pyviz/spectral_method.py`` (the script every shell driver of the reference
+runs), the part that needs neither OpenCV nor cvxpy: ``calculate_M`` (:66-133) and its helpers, on the GPU.
+
+* ``calculate_M``: same signature and return value as the reference's.  The dense N x N affinity and its full SVD are
+  replaced by ``apap_spectral_weights``: a restarted Lanczos iteration in fp64 whose matrix-vector products recompute the
+  float32 affinity tile by tile (no N x N buffer).  ``segment`` agrees with the reference's ``|U[:, 0]| / max`` to about
+  N eps / gap; both masks are computed from it exactly as the reference does (include/apap_hip.h).
+* ``spectral_weights``: the same on arrays (what ``cv_to_array`` returns), with the options as keywords.
+* ``recompute_matching``, ``match_RANSAC``, ``cv_to_array``, ``normalized_feature``: the reference's helpers.
+  ``match_RANSAC`` uses THIS REPOSITORY's GPU RANSAC (``_native.find_homography_ransac``), not OpenCV's: sampler, adaptive
+  stopping and refinement differ, so its mask is not cv.findHomography's (as in ``baseline_stitch_test``).
+* ``skew_symmetric_transform``, ``fundamental``, ``get_fundamental``: utils.py:162-186, host numpy.
+
+Keypoints and matches are duck-typed: anything with ``.pt`` and ``.queryIdx`` / ``.trainIdx`` (OpenCV's KeyPoint / DMatch
+or simple stand-ins).  ``opts`` is any object with ``epi_weight``, ``affinity_eps``, ``aff_thresh``, ``em_radius`` and
+``score_thresh`` attributes.  No CPU fallback.
+"""
+from __future__ import annotations
+
+import warnings
+from typing import NamedTuple
+
+import numpy as np
+
+from . import _native
+
+__all__ = ["calculate_M", "spectral_weights", "SpectralResult", "recompute_matching", "match_RANSAC", "cv_to_array",
+           "normalized_feature", "skew_symmetric_transform", "fundamental", "get_fundamental"]
+
+
+class SpectralResult(NamedTuple):
+    segment: np.ndarray         # (n,) float64: |v| / max|v|, entries below 1e-6 zeroed
+    ransac_mask: np.ndarray     # (n,) float32: the initial mask x aff_thresh, segment where segment > aff_thresh
+    original_mask: np.ndarray   # (n,) float32: the initial mask
+    H: object                   # Hg, or the RANSAC homography (None when RANSAC found no model)
+    lam: float                  # the eigenvalue of largest |lambda| (Rayleigh quotient of the returned vector)
+    gap: float                  # relative gap (|l1| - |l2|) / |l1| of the last tridiagonal solve (NaN if none)
+    steps: int                  # Lanczos steps (matrix-vector products)
+    restarts: int
+    residual: float             # last measured |M v - lambda v| / |lambda|
+    converged: bool
+
+
+def cv_to_array(source, target, matches, is_pts=True):
+    """utils.py:133-140."""
+    if is_pts:
+        src = np.float32([source[m.queryIdx].pt for m in matches])
+        dst = np.float32([target[m.trainIdx].pt for m in matches])
+    else:
+        src = np.stack([source[m.queryIdx] for m in matches], axis=0)
+        dst = np.stack([target[m.trainIdx] for m in matches], axis=0)
+    return src, dst
+
+
+def normalized_feature(feats_cp, feats_op, match):
+    """utils.py:153-160."""
+    feat_c = feats_cp[match.queryIdx]
+    feat_o = feats_op[match.trainIdx]
+    return feat_c / np.linalg.norm(feat_c), feat_o / np.linalg.norm(feat_o)
+
+
+def match_RANSAC(kpts_cp, kpts_op, matches, swap=False, device=-1, ctx=None):
+    """spectral_method.py:25-33 with this repository's GPU RANSAC (5 px) in place of cv.findHomography: (H, mask float32)."""
+    if swap:
+        dst_pts, src_pts = cv_to_array(kpts_cp, kpts_op, matches)
+    else:
+        src_pts, dst_pts = cv_to_array(kpts_cp, kpts_op, matches)
+    H, mask = _native.find_homography_ransac(src_pts, dst_pts, 5.0, device=device, ctx=ctx)
+    return H, mask.astype(np.float32).ravel()
+
+
+def _params(opts, max_restarts):
+    return _native.spectral_params(opts.epi_weight, opts.affinity_eps, opts.aff_thresh, getattr(opts, "em_radius", 6.0),
+                                   getattr(opts, "score_thresh", 0.4), 0 if max_restarts is None else max_restarts)
+
+
+def _descriptors(feats_cp, feats_op, matches):
+    # cv_to_array(..., is_pts=False): np.stack keeps the descriptors' dtype (float32 from SIFT)
+    return cv_to_array(feats_cp, feats_op, matches, is_pts=False)
+
+
+def recompute_matching(kpts_cp, feats_cp, kpts_op, feats_op, matches, H, opts, device=-1, ctx=None):
+    """spectral_method.py:35-64 on the GPU (the set-up kernel of the spectral weights, in float32): 1.0 where the match's
+    other-image keypoint, mapped through H, lies within ``opts.em_radius`` of its centre keypoint and the normalised
+    descriptors' score exceeds ``opts.score_thresh``."""
+    src, dst = cv_to_array(kpts_cp, kpts_op, matches)
+    c, o = _descriptors(feats_cp, feats_op, matches)
+    seg, rm, om, info = _native.spectral_weights(src, dst, c, o, np.eye(3), _params(opts, 1), Hg=H, device=device, ctx=ctx)
+    return om
+
+
+def _result(seg, rm, om, info, H):
+    status = int(info[3])
+    res = SpectralResult(seg, rm, om, H, float(info[0]), float(info[1]), int(info[2]), int(info[4]), float(info[5]),
+                         not status & _native.STATUS_NO_CONVERGENCE)
+    if not res.converged:
+        warnings.warn(f"spectral weights: the eigen-solver did not reach |Mv - lambda v| <= 1e-13 |lambda| in {res.restarts} "
+                      f"restarts (last residual {res.residual:.3e}, gap {res.gap:.3e}); the best Ritz vector is used",
+                      RuntimeWarning, stacklevel=3)
+    return res
+
+
+def spectral_weights(src_pts, dst_pts, c_feats, o_feats, F, *, epi_weight=0.5, affinity_eps=30.0, aff_thresh=0.5, Hg=None,
+                     mask=None, em_radius=6.0, score_thresh=0.4, swap=True, max_restarts=None, device=-1, ctx=None):
+    """calculate_M on arrays.  src_pts / dst_pts (n, 2), c_feats / o_feats (n, 128) raw descriptors, F (3, 3).
+    The initial mask: recompute_matching with ``Hg``; else ``mask`` (what match_RANSAC returned); else the GPU RANSAC of
+    this repository (``swap`` as in match_RANSAC).  Returns a SpectralResult; warns (RuntimeWarning) when the solver hit
+    its restart cap (``max_restarts``, default 30)."""
+    src = np.ascontiguousarray(src_pts, dtype=np.float32)
+    dst = np.ascontiguousarray(dst_pts, dtype=np.float32)
+    params = _native.spectral_params(epi_weight, affinity_eps, aff_thresh, em_radius, score_thresh,
+                                     0 if max_restarts is None else max_restarts)
+    H = Hg
+    if Hg is None and mask is None:
+        if src.ndim != 2 or len(src) == 0:
+            raise ValueError(f"no matches, or points not (n, 2): {src.shape}")
+        a, b = (dst, src) if swap else (src, dst)
+        H, m = _native.find_homography_ransac(a, b, 5.0, device=device, ctx=ctx)
+        mask = m.astype(np.float32).ravel()
+    seg, rm, om, info = _native.spectral_weights(src, dst, c_feats, o_feats, F, params, Hg=Hg, mask=mask, device=device, ctx=ctx)
+    return _result(seg, rm, om, info, H)
+
+
+def calculate_M(kpts_cp, feats_cp, kpts_op, feats_op, F, matches, opts, verbose=False, swap=True, init_ransac=True, Hg=None,
+                device=-1, ctx=None):
+    """spectral_method.py:66-133: ``(segment float64, H, ransac_mask float32, original_mask float32)``."""
+    if not init_ransac:
+        # the reference computes M and its SVD, then fails on `ransac_mask *= opts.aff_thresh` with ransac_mask = None
+        raise TypeError("unsupported operand type(s) for *=: 'NoneType' and 'float'")
+    if len(matches) == 0:
+        raise ValueError("all the input array dimensions except for the concatenation axis must match exactly "
+                         "(no matches: np.hstack at spectral_method.py:105)")
+    src, dst = cv_to_array(kpts_cp, kpts_op, matches)
+    c, o = _descriptors(feats_cp, feats_op, matches)
+    mask = None
+    H = Hg
+    if Hg is None:
+        H, mask = match_RANSAC(kpts_cp, kpts_op, matches, swap, device=device, ctx=ctx)
+    res = spectral_weights(src, dst, c, o, F, epi_weight=opts.epi_weight, affinity_eps=opts.affinity_eps,
+                           aff_thresh=opts.aff_thresh, Hg=Hg, mask=mask, em_radius=getattr(opts, "em_radius", 6.0),
+                           score_thresh=getattr(opts, "score_thresh", 0.4), max_restarts=getattr(opts, "max_restarts", None),
+                           device=device, ctx=ctx)
+    if verbose:
+        # :119-126; the matrix plot needs matplotlib and the dense M (n <= 8192)
+        M = _native.spectral_affinity(src, dst, c, o, F, _params(opts, 0), device=device, ctx=ctx)
+        for i, m_value in enumerate(res.original_mask):
+            print(f"Matching score: {M[i, i]:.4f}\tvalid match: {m_value > 0}/{res.segment[i]}")
+        try:
+            import matplotlib.pyplot as plt
+        except ImportError:
+            plt = None
+        if plt is not None:
+            plt.imshow(M)
+            plt.colorbar()
+            plt.tight_layout()
+            plt.show()
+    return res.segment, H, res.ransac_mask, res.original_mask
+
+
+# ------------------------------------------------------------------ utils.py:162-186
+def skew_symmetric_transform(t):
+    """utils.py:162-168 (float32, as the reference)."""
+    x, y, z = t
+    return np.float32([[0, -z, y], [z, 0, -x], [-y, x, 0]])
+
+
+def fundamental(Rc, Ro, tc, to, K):
+    """utils.py:171-178: F from the two camera poses and the intrinsics."""
+    Ro_inv = np.linalg.inv(Ro)
+    Rr = Ro_inv @ Rc
+    tr = Ro_inv @ (tc - to)
+    ss_t = skew_symmetric_transform(tr)
+    K_inv = np.linalg.inv(K)
+    return K_inv.T @ ss_t @ Rr @ K_inv
+
+
+def get_fundamental(case_idx, center_idx, img_idx, root="../diff_1/raw_data"):
+    """utils.py:180-186.  Reads ``{root}/case{i}/Parameters.xlsx`` (needs pandas with an xlsx reader, and scipy)."""
+    import pandas as pd
+    from scipy.spatial.transform import Rotation as Rot
+
+    path = f"{root}/case{case_idx}/Parameters.xlsx"
+    poses = pd.read_excel(path, sheet_name="Parameters of UAV").to_numpy()[..., 1:].astype(np.float32)
+    position, euler_angles = poses[..., :3], poses[..., 3:]
+    Rs = []
+    for euler in euler_angles:
+        euler[1] = -euler[1]
+        Rs.append(Rot.from_euler("yzx", euler, degrees=True).as_matrix())
+    R = np.stack(Rs, axis=0)
+    K = pd.read_excel(path, sheet_name="Parameters of camera").to_numpy()[..., 1:].astype(np.float32)
+    return fundamental(R[center_idx - 1], R[img_idx - 1], position[center_idx - 1], position[img_idx - 1], K)

@@ -51,6 +51,7 @@ extern "C" {
 #define APAP_STATUS_SINGULAR 1   /* a cell's 3x3 inverse met an exact-zero pivot (reference: LinAlgError)        */
 #define APAP_STATUS_INDEX 2      /* mesh edges do not cover the canvas (reference: IndexError)                 */
 #define APAP_STATUS_UNPREPARED 4 /* a gather on a warp workspace without lookup tables for this mesh / canvas */
+#define APAP_STATUS_NO_CONVERGENCE 8 /* the spectral eigen-solver hit its restart cap: the best Ritz vector is kept */
 
 /* Doubles per keypoint in the device point table (see apap_host_build_table). */
 #define APAP_TABLE_STRIDE 32
@@ -83,7 +84,8 @@ extern "C" {
 #define APAP_PROF_EQ_HIST 5  /* E1: per-channel histogram               */
 #define APAP_PROF_EQ_APPLY 6 /* E2: table rebuild + mapping             */
 #define APAP_PROF_RANSAC 7   /* R1-R3: hypotheses, scoring, selection   */
-#define APAP_PROF_SLOTS 8
+#define APAP_PROF_SPECTRAL 8 /* spectral weights: set-up, Lanczos, finish */
+#define APAP_PROF_SLOTS 9
 
 /* ABI generation.  Generation 2 put `apap_ctx *` first in every compute entry point while keeping the
  * symbol names of generation 1: a caller built against the old header would still link and then pass a
@@ -441,6 +443,57 @@ size_t apap_ransac_workspace_bytes(int n, int iterations);
 int apap_ransac_device(apap_ctx *ctx, const float *d_src, const float *d_dst, int n, double thresh, int iterations,
                        unsigned long long seed, double *d_H_best, uint8_t *d_mask, int *d_result, void *d_work,
                        size_t work_bytes, void *stream);
+
+/* ------------------------------------------------- spectral match weighting --- */
+/* calculate_M of spectral_method.py:66-133, the step every shell driver of the reference runs:
+ *     M_ii = match_score_i + epi_weight / (1 + |dst_i^T F src_i|)                              (:104-114)
+ *     M_ij = max(4.5 - (|src_i - src_j|^2 - |dst_i - dst_j|^2)^2 / (2 affinity_eps^2), 0)      (:116-124)
+ *     U, _, _ = np.linalg.svd(M); segment = |U[:, 0]| / max|U[:, 0]|; segment[segment < 1e-6] = 0  (:125-128)
+ *     bool_mask = segment > aff_thresh; ransac_mask *= aff_thresh; ransac_mask[bool_mask] = segment[bool_mask]  (:129-132)
+ * M is never stored: its off-diagonal float32 entries (every operation rounded as numpy does) are recomputed inside each
+ * fp64 matrix-vector product of a restarted Lanczos iteration (basis of 64, full re-orthogonalisation, start vector
+ * 1/sqrt(n)).  U[:, 0] of a symmetric M is the eigenvector of largest |lambda| (M is not positive definite: lambda may be
+ * negative).  Converged: |M v - lambda v| <= 1e-13 |lambda|.  Otherwise, after the restart cap, the last Ritz vector is
+ * used and APAP_STATUS_NO_CONVERGENCE is reported.
+ *   src, dst        n x 2 float32 (cv_to_array: src = kpts_cp[queryIdx], dst = kpts_op[trainIdx])
+ *   c_feats, o_feats  n x APAP_SPECTRAL_DIM float32 descriptors, NOT normalised (the call normalises, :109-110)
+ *   F               3 x 3 float64, row-major
+ *   params          APAP_SPECTRAL_PARAMS doubles, indexed by APAP_SPECTRAL_* below (max_restarts 0 = the default, 30)
+ *   Hg_or_null      3 x 3 float32: the initial mask is recompute_matching(Hg) (:35-64), in float32; or NULL and
+ *   mask_in_or_null n float32: the initial mask (what match_RANSAC returned).  Both NULL: APAP_ERR_INVALID_ARG (the
+ *                   reference's init_ransac=False fails on `None *= float`, :131)
+ *   segment_out     n float64;  ransac_mask_out, original_mask_out  n float32
+ *   info_out        APAP_SPECTRAL_INFO doubles: lambda, relative gap (|l1| - |l2|) / |l1| of the last tridiagonal (NaN if
+ *                   none had two Ritz values), Lanczos steps, status word (APAP_STATUS_NO_CONVERGENCE or 0), restarts,
+ *                   last measured |M v - lambda v| / |lambda|
+ * The host-buffer call waits for each restart cycle and stops at convergence; it returns APAP_OK also when the cap is hit
+ * (the status is in info_out[3]).  n >= 1. */
+#define APAP_SPECTRAL_DIM 128
+#define APAP_SPECTRAL_EPI_WEIGHT 0
+#define APAP_SPECTRAL_AFFINITY_EPS 1
+#define APAP_SPECTRAL_AFF_THRESH 2
+#define APAP_SPECTRAL_EM_RADIUS 3
+#define APAP_SPECTRAL_SCORE_THRESH 4
+#define APAP_SPECTRAL_MAX_RESTARTS 5
+#define APAP_SPECTRAL_PARAMS 6
+#define APAP_SPECTRAL_INFO 6
+int apap_spectral_weights(apap_ctx *ctx, const float *src, const float *dst, const float *c_feats, const float *o_feats, int n,
+                          const double *F, const double *params, const float *Hg_or_null, const float *mask_in_or_null,
+                          double *segment_out, float *ransac_mask_out, float *original_mask_out, double *info_out, int device);
+/* Scratch of the resident form: O(n) (about 620 n bytes; the Krylov basis is 512 n of it), no n x n buffer. */
+size_t apap_spectral_workspace_bytes(int n);
+/* Resident form: every pointer but `params` (host) is a device pointer; d_work 256-byte aligned, points 8-byte aligned.
+ * Enqueues the set-up, max_restarts restart cycles and the finish on `stream` without waiting: the launches of the cycles
+ * after convergence read the device's `converged` word and return at once.  d_info: APAP_SPECTRAL_INFO doubles;
+ * d_status (may be NULL): APAP_STATUS_NO_CONVERGENCE is OR-ed into it when the cap is hit. */
+int apap_spectral_device(apap_ctx *ctx, const float *d_src, const float *d_dst, const float *d_c_feats, const float *d_o_feats,
+                         int n, const double *d_F, const double *params, const float *d_Hg_or_null,
+                         const float *d_mask_in_or_null, double *d_segment, float *d_ransac_mask, float *d_original_mask,
+                         double *d_info, int *d_status, void *d_work, size_t work_bytes, void *stream);
+/* The dense M itself (n <= 8192: n x n float64, row-major), for the reference's verbose path (plt.imshow(M), :119-126)
+ * and for parity tests.  Same inputs as apap_spectral_weights; params' thresholds are not used. */
+int apap_spectral_affinity(apap_ctx *ctx, const float *src, const float *dst, const float *c_feats, const float *o_feats, int n,
+                           const double *F, const double *params, double *M_out, int device);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,176 @@
+"""Spectral weights (spectral_method.py:66-133) without a GPU: the C ABI surface, the workspace size, the argument errors
+and a numpy restatement of the float32 affinity against the reference's own M (tests/golden/spectral_*.npz)."""
+import ctypes
+import glob
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT
+
+NEW_SYMBOLS = ("apap_spectral_weights", "apap_spectral_workspace_bytes", "apap_spectral_device", "apap_spectral_affinity")
+
+
+def fixtures_with_m():
+    return sorted(p for p in glob.glob(os.path.join(GOLDEN, "spectral_*.npz")) if "M_off" in np.load(p).files)
+
+
+class KP:
+    def __init__(self, x, y):
+        self.pt = (float(x), float(y))
+
+
+class DM:
+    def __init__(self, q, t):
+        self.queryIdx, self.trainIdx = q, t
+
+
+class Opts:
+    epi_weight, affinity_eps, aff_thresh, em_radius, score_thresh = 0.5, 30.0, 0.5, 6.0, 0.4
+
+
+def test_new_symbols_exported_and_bound(native):
+    handle = ctypes.CDLL(native.LIB_PATH)
+    header = open(os.path.join(ROOT, "include", "apap_hip.h")).read()
+    for name in NEW_SYMBOLS:
+        assert re.search(rf"\b{name}\(", header), name
+        assert hasattr(handle, name) and name in native.SIGNATURES
+    assert int(re.search(r"#define APAP_STATUS_NO_CONVERGENCE (\d+)", header).group(1)) == native.STATUS_NO_CONVERGENCE == 8
+    assert int(re.search(r"#define APAP_PROF_SPECTRAL (\d+)", header).group(1)) == native.PROF_NAMES.index("spectral") == 8
+    assert int(re.search(r"#define APAP_PROF_SLOTS (\d+)", header).group(1)) == native.PROF_SLOTS == 9
+    assert native.lib().apap_abi_version() == 6
+
+
+def test_workspace_grows_linearly(native):
+    f = native.lib().apap_spectral_workspace_bytes
+    assert f(0) == 0
+    sizes = {n: f(n) for n in (1000, 2000, 4000, 8000, 16000, 32000)}
+    per = [sizes[n] / n for n in sizes]
+    assert max(per) < 700 and min(per) > 512          # the 64-vector basis is 512 n bytes; no n x n term
+    assert sizes[32000] < 2.1 * sizes[16000]
+
+
+def test_no_device_raises(native):
+    if native.lib().apap_device_count() > 0:
+        pytest.skip("a GPU is visible")
+    rng = np.random.default_rng(0)
+    n = 16
+    args = (rng.random((n, 2), np.float32), rng.random((n, 2), np.float32), rng.random((n, 128), np.float32),
+            rng.random((n, 128), np.float32), np.eye(3))
+    with pytest.raises(native.ApapError) as e:
+        native.spectral_weights(*args, native.spectral_params(), mask=np.ones(n, np.float32))
+    assert e.value.code == native.ERR_NO_DEVICE
+    with pytest.raises(native.ApapError) as e:
+        native.spectral_affinity(*args)
+    assert e.value.code == native.ERR_NO_DEVICE
+
+
+def test_argument_errors(native):
+    from cvx_proj_amd import spectral_method as S
+    rng = np.random.default_rng(1)
+    n = 8
+    src, dst = rng.random((n, 2), np.float32), rng.random((n, 2), np.float32)
+    c, o = rng.random((n, 128), np.float32), rng.random((n, 128), np.float32)
+    with pytest.raises(ValueError):
+        S.spectral_weights(src, dst[:5], c, o, np.eye(3), mask=np.ones(n))
+    with pytest.raises(ValueError):
+        S.spectral_weights(src, dst, c[:, :64], o[:, :64], np.eye(3), mask=np.ones(n))
+    with pytest.raises(ValueError):
+        S.spectral_weights(src, dst, c, o, np.eye(2), mask=np.ones(n))
+    with pytest.raises(ValueError):
+        S.spectral_weights(src, dst, c, o, np.eye(3), mask=np.ones(n + 1))
+    with pytest.raises(ValueError):     # n = 0: the reference's np.hstack raises ValueError
+        native.spectral_weights(np.zeros((0, 2)), np.zeros((0, 2)), np.zeros((0, 128)), np.zeros((0, 128)), np.eye(3),
+                                native.spectral_params(), mask=np.zeros(0))
+    kc, ko = [KP(*p) for p in src], [KP(*p) for p in dst]
+    matches = [DM(i, i) for i in range(n)]
+    with pytest.raises(ValueError):
+        S.calculate_M([], [], [], [], np.eye(3), [], Opts())
+    with pytest.raises(TypeError):      # init_ransac=False: `None *= float` in the reference
+        S.calculate_M(kc, c, ko, o, np.eye(3), matches, Opts(), init_ransac=False)
+    # the C ABI refuses a call without an initial mask, and bad restart caps
+    lib = native.lib()
+    f32 = ctypes.POINTER(ctypes.c_float)
+    seg, info = np.empty(n), np.empty(6)
+    rm, om = np.empty(n, np.float32), np.empty(n, np.float32)
+    F = np.eye(3)
+    params = native.spectral_params()
+    rc = lib.apap_spectral_weights(None, src.ctypes.data_as(f32), dst.ctypes.data_as(f32), c.ctypes.data_as(f32),
+                                   o.ctypes.data_as(f32), n, F.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                   params.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), None, None,
+                                   seg.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), rm.ctypes.data_as(f32),
+                                   om.ctypes.data_as(f32), info.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), -1)
+    assert rc == native.ERR_INVALID_ARG and "init_ransac" in native.last_error()
+
+
+def off_diagonal_f32(src, dst, affinity_eps):
+    """spectral_method.py:116-123 restated: every step float32, rounded separately, the diagonal set to 0."""
+    src = np.asarray(src, np.float32)
+    dst = np.asarray(dst, np.float32)
+    rcp = np.float32(1 / 2 / (affinity_eps ** 2))
+    ds = src[:, None, :] - src[None, :, :]
+    dd = dst[:, None, :] - dst[None, :, :]
+    s = ds[..., 0] * ds[..., 0] + ds[..., 1] * ds[..., 1]
+    d = dd[..., 0] * dd[..., 0] + dd[..., 1] * dd[..., 1]
+    t = s - d
+    off = np.maximum(np.float32(4.5) - (t * t) * rcp, np.float32(0))
+    np.fill_diagonal(off, 0)
+    assert off.dtype == np.float32
+    return off
+
+
+@pytest.mark.parametrize("path", fixtures_with_m(), ids=os.path.basename)
+def test_off_diagonal_restatement_matches_reference_bit_for_bit(path):
+    g = np.load(path)
+    off = off_diagonal_f32(g["src"], g["dst"], float(g["opts"][1]))
+    assert off.view(np.uint32).tobytes() == g["M_off"].view(np.uint32).tobytes()
+
+
+def test_fixture_set_is_complete():
+    names = {os.path.basename(p)[len("spectral_"):-4] for p in glob.glob(os.path.join(GOLDEN, "spectral_*.npz"))}
+    assert {"n1", "n2", "n7", "n64_hg", "n500", "n500_hg", "clusters", "disjoint", "negative", "n2000", "n5000"} <= names
+    assert np.load(os.path.join(GOLDEN, "spectral_negative.npz"))["lam"] < 0
+    assert len(fixtures_with_m()) >= 9
+
+
+def test_fundamental_matches_utils_formula():
+    from cvx_proj_amd.spectral_method import fundamental, skew_symmetric_transform
+    t = np.array([1.0, -2.0, 0.5])
+    S = skew_symmetric_transform(t)
+    assert S.dtype == np.float32 and np.allclose(S @ t, 0) and np.allclose(S, -S.T)
+    K = np.float32([[800, 0, 320], [0, 800, 240], [0, 0, 1]])
+    F = fundamental(np.eye(3), np.eye(3), np.zeros(3, np.float32), np.float32([1, 0, 0]), K)
+    x = np.array([100.0, 50.0, 1.0])
+    assert abs(x @ F @ x) < 1e-12          # a pure x-translation: a point and itself lie on one epipolar line
+
+
+def pairwise128(a):
+    """numpy's float32 pairwise sum of 128 terms (8 accumulators) along the last axis, as the set-up kernel sums."""
+    r = a[..., :8].copy()
+    for i in range(8, 128, 8):
+        r = r + a[..., i:i + 8]
+    return ((r[..., 0] + r[..., 1]) + (r[..., 2] + r[..., 3])) + ((r[..., 4] + r[..., 5]) + (r[..., 6] + r[..., 7]))
+
+
+@pytest.mark.parametrize("path", fixtures_with_m(), ids=os.path.basename)
+def test_diagonal_order_within_tolerance(path):
+    """The set-up kernel's summation order (comments of csrc/apap_spectral.hip), restated in numpy: match_score bit for bit
+    with the reference's float32 sum, the fp64 diagonal within 4 ulp of the reference's (whose F @ x goes through BLAS)."""
+    g = np.load(path)
+    c = g["c_feats"].astype(np.float32)
+    o = g["o_feats"].astype(np.float32)
+    nc = np.sqrt(pairwise128(c * c))[:, None]
+    no = np.sqrt(pairwise128(o * o))[:, None]
+    ms = pairwise128((c / nc) * (o / no))
+    cr = c / np.linalg.norm(c, axis=-1, keepdims=True)
+    orr = o / np.linalg.norm(o, axis=-1, keepdims=True)
+    assert np.array_equal(ms, np.sum(cr * orr, axis=-1))
+    F = g["F"]
+    x, y = g["src"][:, 0].astype(np.float64), g["src"][:, 1].astype(np.float64)
+    u, v = g["dst"][:, 0].astype(np.float64), g["dst"][:, 1].astype(np.float64)
+    e = [(F[r, 0] * x + F[r, 1] * y) + F[r, 2] for r in range(3)]
+    epi = np.abs((u * e[0] + v * e[1]) + e[2])
+    diag = ms.astype(np.float64) + float(g["opts"][0]) / (1.0 + epi)
+    assert (np.abs(diag - g["M_diag"]) <= 4 * np.spacing(np.abs(g["M_diag"]))).all()
