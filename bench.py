@@ -3,7 +3,7 @@
 4K pair / 200x200 mesh / 2000 keypoints configuration of BASELINE.json (C3).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--cells-config C4]
-                    [--variant auto|valu|mfma|mfma4|mfma4x2] [--no-cpu-baseline] [--no-cells] [--no-call-level]
+                    [--variant auto|valu|mfma|mfma4|mfma4x2] [--full [--no-cpu-baseline] [--no-cells] [--no-call-level]]
                     [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one image pair with all inputs resident in
@@ -11,12 +11,17 @@ HBM: the per-cell solve (assemble + eigen-solve kernels) and the backward warp
 (set-up + gather kernels).  The two halves of the metric are timed in two regions of
 exactly K steps each, both bracketed by a barrier and a device synchronise:
 ``value`` = cells * K * N / t_solve (homographies/s), ``warp.value`` = canvas pixels
-* K * N / t_warp (Mpix/s), ``ms_per_step`` = (t_solve + t_warp) / K.  Every other timed region of the run (the objects
-below) takes ``extra_steps`` = min(K, 50) steps, so that the run's length follows K * ``ms_per_step`` plus a fixed part.
+* K * N / t_warp (Mpix/s), ``ms_per_step`` = (t_solve + t_warp) / K.
+
+A plain run does only what that headline needs: it sets up the pair, conditions the clock and warms up, times the K steps,
+writes ``--dump-outputs`` and prints the line (``value``, ``warp``, ``ms_per_step``, ``pair_per_rank`` and the configuration).
+``--full`` goes on to measure everything below in the same process and adds it to the same line; every timed region of
+that part takes ``extra_steps`` = min(K, 50) steps, so that the run's length follows K * ``ms_per_step`` plus a fixed part.
+The ``--no-*`` switches leave objects out of a ``--full`` run and do nothing without it.
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a child
 ``python -m torch.distributed.run --nproc-per-node N bench.py ...`` before anything touches the
-GPU); under torch.distributed.run it is one rank per GPU over RCCL.  Every run measures BOTH ways
+GPU); under torch.distributed.run it is one rank per GPU over RCCL.  A ``--full`` run measures BOTH ways
 the path shards and puts both in the one JSON line:
 
 * the headline (``value``, ``pair_per_rank``): every rank owns a 4K pair (config C3) - independent
@@ -28,7 +33,7 @@ the path shards and puts both in the one JSON line:
   per pair, per-rank solve, all-gather of the H grid; warp by canvas-row bands + all-gather - strong
   scaling.  At N = 1 it is the single-GPU baseline of that curve.
 
-Further objects: ``roofline`` for the dominant kernel (K1, timed live with HIP events on the launch
+Further objects of ``--full``: ``roofline`` for the dominant kernel (K1, timed live with HIP events on the launch
 stream); ``roofline_warp`` / ``roofline_warp_cold`` for K3 on the headline canvas (launches back to back,
 source and canvas warm / rotated through 640 MB), ``cells.roofline_warp`` for the same kernel on the
 cells configuration's canvas and ``pairs.warp.roofline`` for the batched warp of config 5; ``standalone``
@@ -787,6 +792,9 @@ def main():
     ap.add_argument("--cells-config", default="C4", choices=sorted(CONFIGS),
                     help="the ONE pair whose mesh rows are sharded over the ranks in the `cells` object")
     ap.add_argument("--variant", default="auto", choices=sorted(VARIANTS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else (kernel times, rooflines, other configurations, "
+                         "pairs, cells, call level, CPU baseline) and add it to the line; the --no-* switches leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cells", action="store_true", help="skip the `cells` (strong-scaling) object")
     ap.add_argument("--no-call-level", action="store_true")
@@ -814,7 +822,7 @@ def main():
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
-    # --steps is the number of timed steps of the headline (`value`, `ms_per_step`); every other timed region of the run
+    # --steps is the number of timed steps of the headline (`value`, `ms_per_step`); every other timed region of a --full run
     # (extras, configs, pairs, cells, kernel times) takes at most EXTRA_STEPS steps, so that the run's length follows the headline's
     xs = min(a.steps, EXTRA_STEPS)
 
@@ -856,6 +864,14 @@ def main():
         if rank == 0:
             print(json.dumps({"bench_phase": name, "n_gpus": world, "backend": backend, "t": round(time.time() - T0, 2)}),
                   file=sys.stderr, flush=True)
+
+    def finish(line):
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
     phase("process group up")
     if dist is not None:
         # one tiny collective first: if the transport is broken this fails within the timeout, before any long phase
@@ -940,6 +956,38 @@ def main():
     assert int(res.status.cpu()[0]) == 0, "device status word set during the timed region"
     if a.dump_outputs and rank == 0:
         dump_outputs(a.dump_outputs, res)
+    line = None
+    if rank == 0:
+        line = {
+            "metric": METRIC, "value": units_solve * a.steps / t_solve, "unit": "homographies/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "conditioning_ms": a.condition_ms,
+            "ms_per_step": (t_solve + t_warp) / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"{a.config}: {CONFIGS[a.config][0]}x{CONFIGS[a.config][1]} pair, "
+                                   f"{res.n} correspondences, {res.rows}x{res.cols} mesh, canvas "
+                                   f"{pair.final_w}x{pair.final_h}", "mode": "pairs", "variant": a.variant,
+                       "pairs_per_solve_launch": a.batch,
+                       "launch": "hip graph replay" if a.graph else "eager",
+                       "parallelism": f"pairsx{world}"},
+            "warp": {"value": units_warp * a.steps / t_warp / 1e6, "unit": "Mpix/s",
+                     "ms_per_step": t_warp / a.steps * 1e3},
+            "solve_ms_per_step": t_solve / a.steps * 1e3,
+            "step_form": ("resident pipeline: canvas row / column tables built once per geometry, the eigen-solve kernel's tail leaves "
+                          "every cell warp ready (apap_solve_warp_batch_device), the warp step is the gather kernel alone "
+                          "(apap_warp_batch_device, APAP_WARP_GATHER); the per-cell set-up is inside solve_ms_per_step") if res.resident
+                         else "solve and stand-alone warp (a batch of pairs per solve launch)",
+            "pair_per_rank": {"workload": f"{a.config} x {world} (one pair per rank)", "world_size": world, "scaling": "weak",
+                              "value": units_solve * a.steps / t_solve, "unit": "homographies/s",
+                              "solve_ms_per_step": t_solve / a.steps * 1e3,
+                              "warp": {"value": units_warp * a.steps / t_warp / 1e6, "unit": "Mpix/s",
+                                       "ms_per_step": t_warp / a.steps * 1e3},
+                              "collectives_per_step": "none (independent pairs)"},
+        }
+    if not a.full:
+        finish(line)
+        return
+
+    # ------------------------------------------------------------------ --full: everything else, added to the same line
     canvas_resident = res.out.clone()
     # the same two halves as separate services: the solve alone, and the warp of a grid from anywhere (its own set-up launch)
     for _ in range(a.warmup):
@@ -1266,30 +1314,8 @@ def main():
         out_pixels = pair.final_w * pair.final_h
         nz = int((res.out.view(-1, 3).amax(dim=1) > 0).sum().cpu())
         warp_bytes = 6 * nz + 3 * (out_pixels - nz)
-        per_rank_obj = {"workload": f"{a.config} x {world} (one pair per rank)", "world_size": world, "scaling": "weak",
-                     "value": units_solve * a.steps / t_solve, "unit": "homographies/s",
-                     "solve_ms_per_step": t_solve / a.steps * 1e3,
-                     "warp": {"value": units_warp * a.steps / t_warp / 1e6, "unit": "Mpix/s",
-                              "ms_per_step": t_warp / a.steps * 1e3},
-                     "collectives_per_step": "none (independent pairs)"}
-        line = {
-            "metric": METRIC, "value": units_solve * a.steps / t_solve, "unit": "homographies/s",
-            "n_gpus": world, "steps": a.steps, "extra_steps": xs, "warmup": a.warmup, "conditioning_ms": a.condition_ms,
-            "ms_per_step": (t_solve + t_warp) / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{a.config}: {CONFIGS[a.config][0]}x{CONFIGS[a.config][1]} pair, "
-                                   f"{res.n} correspondences, {res.rows}x{res.cols} mesh, canvas "
-                                   f"{pair.final_w}x{pair.final_h}", "mode": "pairs", "variant": a.variant,
-                       "pairs_per_solve_launch": a.batch,
-                       "launch": "hip graph replay" if a.graph else "eager",
-                       "parallelism": f"pairsx{world}"},
-            "warp": {"value": units_warp * a.steps / t_warp / 1e6, "unit": "Mpix/s",
-                     "ms_per_step": t_warp / a.steps * 1e3},
-            "solve_ms_per_step": t_solve / a.steps * 1e3,
-            "step_form": ("resident pipeline: canvas row / column tables built once per geometry, the eigen-solve kernel's tail leaves "
-                          "every cell warp ready (apap_solve_warp_batch_device), the warp step is the gather kernel alone "
-                          "(apap_warp_batch_device, APAP_WARP_GATHER); the per-cell set-up is inside solve_ms_per_step") if res.resident
-                         else "solve and stand-alone warp (a batch of pairs per solve launch)",
+        line.update({
+            "extra_steps": xs,
             "standalone": {"solve_ms_per_step": t_solve_plain / xs * 1e3, "value": units_solve * xs / t_solve_plain,
                            "warp_ms_per_step": t_warp_alone / xs * 1e3,
                            "warp_value": units_warp * xs / t_warp_alone / 1e6, "warp_unit": "Mpix/s",
@@ -1304,7 +1330,6 @@ def main():
             "configs": configs_obj,
             "moments24": modes_obj,
             "pairs": c5_obj,
-            "pair_per_rank": per_rank_obj,
             "cells": cells_obj,
             "stitch": {
                 "value": pair.final_w * pair.final_h * xs / t_stitch / 1e6, "unit": "Mpix/s (rank 0)",
@@ -1356,7 +1381,7 @@ def main():
                                 "ms": t_idle * 1e3,
                                 "note": "ONE solve call from an idle chip (0.4 s pause before it, median of 3), launch + both "
                                         "kernels + synchronisation; `value` is the steady state after conditioning_ms of load"},
-        }
+        })
         if cold:
             line["warp_cold"] = {"value": units_warp * xs / t_warp_cold / 1e6, "unit": "Mpix/s",
                                  "ms_per_step": t_warp_cold / xs * 1e3, "buffer_sets": len(cold),
@@ -1376,10 +1401,7 @@ def main():
         if world == 1 and not a.no_cpu_baseline:
             workers = usable_cores() if a.cpu_pool < 0 else a.cpu_pool
             line["cpu_baseline"] = cpu_baseline(a.config, a.cpu_cells, a.cpu_rows, min(workers, 256))
-        print(json.dumps(line), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(line)
 
 
 if __name__ == "__main__":

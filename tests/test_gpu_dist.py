@@ -66,7 +66,7 @@ def test_bench_self_launch_reports_pairs_and_cells(native):
     """`python bench.py --gpus 2` (no torchrun around it): both sharding modes in the one JSON line,
     each with the world size it saw; the cells leg's roofline is priced on rank 0's own shard."""
     env = clean_env(APAP_BENCH_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                         "--config", "C2", "--cells-config", "C2", "--no-cpu-baseline", "--c5-pairs", "6", "--cold-mb", "0"],
                        env=env, capture_output=True,
                        text=True, timeout=600)
@@ -98,7 +98,7 @@ def test_bench_with_a_one_rank_rccl_group():
     env = clean_env(APAP_BENCH_FORCE_GROUP="1")
     env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()))
     env.pop("APAP_BENCH_BACKEND", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--condition-ms", "0", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--condition-ms", "0", "--no-cpu-baseline",
                         "--no-call-level", "--cells-config", "C2", "--c5-pairs", "4"], env=env, capture_output=True, text=True, timeout=500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -9,7 +9,7 @@ CFG=${1:-C3}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 for r in $(seq ${ROUNDS:-2}); do
   for L in "" $ROOT/tools/variants/lib_*.so; do
-    APAP_HIP_LIB=$L python $ROOT/bench.py --config $CFG --steps 30 --no-cpu-baseline --no-cells --no-call-level 2>/dev/null | python -c "
+    APAP_HIP_LIB=$L python $ROOT/bench.py --config $CFG --steps 30 --full --no-cpu-baseline --no-cells --no-call-level 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['kernels_ms']
 print('$CFG %-40s H/s=%.3e  assemble=%.1f us eigen=%.1f us' % ('${L##*/}' or 'in-tree', d['value'], k['assemble']*1e3, k['eigen']*1e3))"

@@ -14,5 +14,5 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/pmc_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT/pmc_x"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 150 rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$OUT/pmc_x" -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-cells --no-call-level --steps 3 --warmup 1 "$@" > /dev/null 2> "$OUT/err.txt" || { echo "pass [$C] failed:" >&2; grep -m2 -E "exceeds|error code" "$OUT/err.txt" >&2; exit 1; }
+timeout -k 10 150 rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$OUT/pmc_x" -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-cells --no-call-level --steps 3 --warmup 1 "$@" > /dev/null 2> "$OUT/err.txt" || { echo "pass [$C] failed:" >&2; grep -m2 -E "exceeds|error code" "$OUT/err.txt" >&2; exit 1; }
 python3 "$ROOT/tools/summarize_prof.py" "$OUT" | grep -v "^=="
