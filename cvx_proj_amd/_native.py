@@ -62,6 +62,8 @@ _ERROR_CLASSES = {ERR_SINGULAR: ApapSingularError, ERR_INDEX: ApapIndexError, ER
 # bits of the device status word of the resident entry points (APAP_STATUS_* of include/apap_hip.h)
 STATUS_SINGULAR, STATUS_INDEX, STATUS_UNPREPARED = 1, 2, 4
 STATUS_NO_CONVERGENCE = 8     # the spectral eigen-solver hit its restart cap (a warning, not an error)
+STATUS_MODEL_DEGENERATE = 16  # M-step: fewer than 4 selected matches or a rank-deficient system (H is NaN)
+STATUS_MODEL_NO_CONVERGENCE = 32  # M-step: the interior-point method hit its iteration cap (a warning, not an error)
 
 
 def raise_for_status(word, who):
@@ -160,6 +162,13 @@ SIGNATURES = {
     "apap_spectral_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _f64p, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        C.c_size_t, _vp]),
     "apap_spectral_affinity": (C.c_int, [_vp, _f32p, _f32p, _f32p, _f32p, C.c_int, _f64p, _f64p, _f64p, C.c_int]),
+    "apap_model_solve": (C.c_int, [_vp, _f32p, _f32p, _f32p, C.c_int, _f64p, _f32p, _f64p, C.c_int]),
+    "apap_model_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "apap_model_solve_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _f64p, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "apap_spectral_em": (C.c_int, [_vp, _f32p, _f32p, _f32p, _f32p, C.c_int, _f64p, _f64p, _f64p, C.c_int, _f32p, _f32p, _f64p,
+                                   _f64p, _f32p, _f32p, _f64p, C.c_int]),
+    "apap_spectral_em_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _f64p, _f64p, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 
 _lib = None
@@ -588,3 +597,78 @@ def spectral_affinity(src, dst, c_feats, o_feats, F, params=None, device=-1, ctx
     check(lib().apap_spectral_affinity(_h(ctx), _ptr(src, C.c_float), _ptr(dst, C.c_float), _ptr(c, C.c_float), _ptr(o, C.c_float),
                                        n, _ptr(F, C.c_double), _ptr(params, C.c_double), _ptr(M, C.c_double), device))
     return M
+
+
+# ---------------------------------------------------------------- M-step and EM loop (spectral_method.py:165-241)
+MODEL_LMS, MODEL_SDP = 0, 1
+MODEL_PARAMS = 6
+MODEL_INFO = 24
+MODEL_INFO_OBJECTIVE, MODEL_INFO_R, MODEL_INFO_T, MODEL_INFO_GAP, MODEL_INFO_ITERS, MODEL_INFO_STATUS, MODEL_INFO_COUNT = range(7)
+MODEL_INFO_Z, MODEL_INFO_H = 7, 16
+MODEL_FLOOR = 1e-3      # model_solve: `if w <= 1e-3: continue`
+
+
+def model_params(mode, du=1.0, dv=1.0, floor=MODEL_FLOOR, swap=True, max_iter=0):
+    """The ``params`` block of the M-step entry points (``floor=None`` keeps every match; max_iter 0 = 80)."""
+    return np.array([mode, du, dv, -np.inf if floor is None else floor, 1.0 if swap else 0.0, max_iter], dtype=np.float64)
+
+
+def _model_inputs(pts_c, pts_o, weights):
+    pc = np.ascontiguousarray(pts_c, dtype=np.float32)
+    po = np.ascontiguousarray(pts_o, dtype=np.float32)
+    w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+    if pc.ndim != 2 or pc.shape[1] != 2 or po.shape != pc.shape or w.shape != (pc.shape[0],):
+        raise ValueError(f"pts_c / pts_o must be (n, 2) and weights (n,); got {pc.shape}, {po.shape}, {w.shape}")
+    return pc, po, w
+
+
+def model_solve(pts_c, pts_o, weights, params, device=-1, ctx=None):
+    """``apap_model_solve``: (H float32 3 x 3, info (24,) float64).  Raises ApapValueError for bad arguments or a degenerate
+    selection and ApapSingularError when the inverse meets a zero pivot; the info block is on the exception as ``.info``
+    (all NaN when the kernels did not run).  Points and weights are rounded to float32 (the rows of model_solve)."""
+    pc, po, w = _model_inputs(pts_c, pts_o, weights)
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    if params.shape != (MODEL_PARAMS,):
+        raise ValueError(f"params must hold {MODEL_PARAMS} values")
+    H = np.full((3, 3), np.nan, np.float32)
+    info = np.full(MODEL_INFO, np.nan)
+    code = lib().apap_model_solve(_h(ctx), _ptr(pc, C.c_float), _ptr(po, C.c_float), _ptr(w, C.c_float), len(pc),
+                                  _ptr(params, C.c_double), _ptr(H, C.c_float), _ptr(info, C.c_double), device)
+    _check_with_info(code, info)
+    return H, info
+
+
+def _check_with_info(code, info):
+    try:
+        check(code)
+    except ApapError as e:
+        e.info = info
+        raise
+
+
+def spectral_em(src, dst, c_feats, o_feats, F, spec_params, model_params_, em_steps, mask, device=-1, ctx=None):
+    """``apap_spectral_em``: per round (H (k, 3, 3) float32, model info (k, 24), segment (k, n) float64, ransac_mask (k, n)
+    float32, original_mask (k, n) float32, spectral info (k, 6)).  Errors as model_solve (``.info`` holds every round's
+    outputs as the tuple above; H and the model info all NaN when the kernels did not run)."""
+    src, dst, c, o, F, n = _spectral_inputs(src, dst, c_feats, o_feats, F)
+    sp = np.ascontiguousarray(spec_params, dtype=np.float64)
+    mp = np.ascontiguousarray(model_params_, dtype=np.float64)
+    if sp.shape != (SPECTRAL_PARAMS,) or mp.shape != (MODEL_PARAMS,):
+        raise ValueError("spectral / model parameter blocks of the wrong size")
+    mask = np.ascontiguousarray(mask, dtype=np.float32).ravel()
+    if mask.shape != (n,):
+        raise ValueError(f"mask must hold {n} values; got {mask.shape}")
+    k = int(em_steps)
+    H = np.full((k, 3, 3), np.nan, np.float32)
+    info = np.full((k, MODEL_INFO), np.nan)
+    seg = np.empty((k, n), np.float64)
+    rm = np.empty((k, n), np.float32)
+    om = np.empty((k, n), np.float32)
+    sinfo = np.empty((k, SPECTRAL_INFO), np.float64)
+    code = lib().apap_spectral_em(_h(ctx), _ptr(src, C.c_float), _ptr(dst, C.c_float), _ptr(c, C.c_float), _ptr(o, C.c_float), n,
+                                  _ptr(F, C.c_double), _ptr(sp, C.c_double), _ptr(mp, C.c_double), k, _ptr(mask, C.c_float),
+                                  _ptr(H, C.c_float), _ptr(info, C.c_double), _ptr(seg, C.c_double), _ptr(rm, C.c_float),
+                                  _ptr(om, C.c_float), _ptr(sinfo, C.c_double), device)
+    out = (H, info, seg, rm, om, sinfo)
+    _check_with_info(code, out)
+    return out

@@ -4,6 +4,7 @@
 // through the "_device" entry points and copy the results back.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -821,6 +822,146 @@ int apap_spectral_affinity(apap_ctx *ctx, const float *src, const float *dst, co
     }
     APAP_HIP_TRY(hipMemcpyAsync(M_out, d + io.M, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
     APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    return APAP_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ M-step and EM loop (spectral_method.py:165-241)
+// The M-step's own decoding of its status bits (status_to_code above keeps its three): a degenerate selection is
+// APAP_ERR_INVALID_ARG, a zero pivot of the inverse APAP_ERR_SINGULAR (numpy: LinAlgError); the iteration cap is reported
+// in the info block only.
+namespace {
+int model_status_code(int status, const char *who, int round) {
+    if (status & APAP_STATUS_MODEL_DEGENERATE)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: round %d: fewer than 4 selected matches, or they do not determine a homography "
+                                                "(rank-deficient system)", who, round);
+    if (status & APAP_STATUS_SINGULAR) return apap::fail(APAP_ERR_SINGULAR, "%s: round %d: Singular matrix", who, round);
+    return APAP_OK;
+}
+
+struct ModelIo {
+    size_t pc, po, w, H, info, total;
+};
+ModelIo model_io(int n) {
+    ModelIo io{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    io.pc = take((size_t)n * 2 * sizeof(float));
+    io.po = take((size_t)n * 2 * sizeof(float));
+    io.w = take((size_t)n * sizeof(float));
+    io.H = take(9 * sizeof(float));
+    io.info = take(APAP_MODEL_INFO * sizeof(double));
+    io.total = off;
+    return io;
+}
+
+struct EmIo {
+    SpecIo spec;   // src, dst, descriptors, F, the initial mask
+    size_t H, info, seg, rm, om, sinfo, total;
+};
+EmIo em_io(int n, int steps) {
+    EmIo io{};
+    io.spec = spec_io(n, false);
+    size_t off = io.spec.total;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    io.H = take((size_t)steps * 9 * sizeof(float));
+    io.info = take((size_t)steps * APAP_MODEL_INFO * sizeof(double));
+    io.seg = take((size_t)steps * n * sizeof(double));
+    io.rm = take((size_t)steps * n * sizeof(float));
+    io.om = take((size_t)steps * n * sizeof(float));
+    io.sinfo = take((size_t)steps * APAP_SPECTRAL_INFO * sizeof(double));
+    io.total = off;
+    return io;
+}
+}  // namespace
+
+extern "C" {
+
+int apap_model_solve(apap_ctx *ctx, const float *pts_c, const float *pts_o, const float *weights, int n, const double *params,
+                     float *H_out, double *info_out, int device) {
+    const char *who = "apap_model_solve";
+    // the info block is NaN until the kernels have written it: an early return leaves no stale count or status behind
+    if (info_out) std::fill(info_out, info_out + APAP_MODEL_INFO, NAN);
+    if (H_out) std::fill(H_out, H_out + 9, NAN);
+    if (!pts_c || !pts_o || !weights || !params || !H_out || !info_out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    if (n < 1 || n > (1 << 26)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (need 1 .. 2^26 matches)", who, n);
+    PoolLock pl(ctx);
+    int dev;
+    int rc = select_device(device, &dev);
+    if (rc) return rc;
+    const ModelIo io = model_io(n);
+    const size_t work_bytes = apap_model_workspace_bytes(n);
+    void *d_io, *d_work;
+    if ((rc = slot_get(pl.pool, S_AUX, io.total, dev, &d_io))) return rc;
+    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
+    char *d = (char *)d_io;
+    APAP_HIP_TRY(hipMemcpyAsync(d + io.pc, pts_c, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + io.po, pts_o, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + io.w, weights, (size_t)n * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    rc = apap_model_solve_device(ctx, (const float *)(d + io.pc), (const float *)(d + io.po), (const float *)(d + io.w), n, params,
+                                 (float *)(d + io.H), (double *)(d + io.info), nullptr, d_work, work_bytes, nullptr);
+    if (rc) {
+        (void)hipStreamSynchronize(nullptr);
+        return rc;
+    }
+    APAP_HIP_TRY(hipMemcpyAsync(H_out, d + io.H, 9 * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(info_out, d + io.info, APAP_MODEL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    return model_status_code((int)info_out[APAP_MODEL_INFO_STATUS], who, 0);
+}
+
+int apap_spectral_em(apap_ctx *ctx, const float *src, const float *dst, const float *c_feats, const float *o_feats, int n,
+                     const double *F, const double *spec_params, const double *model_params, int em_steps, const float *mask_in,
+                     float *H_out, double *info_out, double *segment_out, float *ransac_mask_out, float *original_mask_out,
+                     double *spec_info_out, int device) {
+    const char *who = "apap_spectral_em";
+    if (info_out && em_steps >= 1 && em_steps <= 64) std::fill(info_out, info_out + (size_t)em_steps * APAP_MODEL_INFO, NAN);
+    if (H_out && em_steps >= 1 && em_steps <= 64) std::fill(H_out, H_out + (size_t)em_steps * 9, NAN);
+    if (!src || !dst || !c_feats || !o_feats || !F || !spec_params || !model_params || !mask_in || !H_out || !info_out ||
+        !segment_out || !ransac_mask_out || !original_mask_out || !spec_info_out)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    if (n < 1 || n > (1 << 26)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (need 1 .. 2^26 matches)", who, n);
+    if (em_steps < 1 || em_steps > 64) return apap::fail(APAP_ERR_INVALID_ARG, "%s: em_steps %d (1 .. 64)", who, em_steps);
+    PoolLock pl(ctx);
+    int dev;
+    int rc = select_device(device, &dev);
+    if (rc) return rc;
+    const EmIo io = em_io(n, em_steps);
+    const size_t work_bytes = apap_spectral_workspace_bytes(n) + apap_model_workspace_bytes(n);
+    void *d_io, *d_work;
+    if ((rc = slot_get(pl.pool, S_AUX, io.total, dev, &d_io))) return rc;
+    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
+    char *d = (char *)d_io;
+    if ((rc = spec_upload(d, io.spec, src, dst, c_feats, o_feats, n, F))) return rc;
+    APAP_HIP_TRY(hipMemcpyAsync(d + io.spec.mask, mask_in, (size_t)n * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    rc = apap::spectral_em_run(ctx, (const float *)(d + io.spec.src), (const float *)(d + io.spec.dst), (const float *)(d + io.spec.c),
+                                 (const float *)(d + io.spec.o), n, (const double *)(d + io.spec.F), spec_params, model_params,
+                                 em_steps, (const float *)(d + io.spec.mask), (float *)(d + io.H), (double *)(d + io.info),
+                                 (double *)(d + io.seg), (float *)(d + io.rm), (float *)(d + io.om), (double *)(d + io.sinfo),
+                                 nullptr, d_work, work_bytes, nullptr, 1);
+    if (rc) {
+        (void)hipStreamSynchronize(nullptr);
+        return rc;
+    }
+    const size_t k = (size_t)em_steps;
+    APAP_HIP_TRY(hipMemcpyAsync(H_out, d + io.H, k * 9 * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(info_out, d + io.info, k * APAP_MODEL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(segment_out, d + io.seg, k * n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(ransac_mask_out, d + io.rm, k * n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(original_mask_out, d + io.om, k * n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(spec_info_out, d + io.sinfo, k * APAP_SPECTRAL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    for (int r = 0; r < em_steps; ++r)
+        if ((rc = model_status_code((int)info_out[(size_t)r * APAP_MODEL_INFO + APAP_MODEL_INFO_STATUS], who, r))) return rc;
     return APAP_OK;
 }
 

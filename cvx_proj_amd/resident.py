@@ -221,3 +221,43 @@ def hip_spectral(src, dst, c_feats, o_feats, F, params, Hg=None, mask=None, stat
         None if mask is None or Hg is not None else mask.data_ptr(), seg.data_ptr(), rm.data_ptr(), om.data_ptr(), info.data_ptr(),
         None if status is None else status.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
     return seg, rm, om, info
+
+
+def model_workspace_bytes(n):
+    """Scratch of the M-step for ``n`` matches (``apap_model_workspace_bytes``)."""
+    return _native.lib().apap_model_workspace_bytes(n)
+
+
+def hip_spectral_em(src, dst, c_feats, o_feats, F, spec_params, model_params, em_steps, mask, status=None, ctx=None, work=None):
+    """``apap_spectral_em_device`` on the current stream of the tensors' device: ``em_steps`` rounds of calculate_M and the
+    M-step on resident data, no host synchronisation: every spectral restart cycle is enqueued (those after convergence return
+    at once but cost their launch), so this form is slower than the host-buffer ``spectral_method.spectral_em``, which stops
+    at convergence; the results are the same.  Inputs as hip_spectral, ``mask`` (n,) float32 the first round's initial
+    mask; ``spec_params`` / ``model_params``: host ``_native.spectral_params(...)`` / ``_native.model_params(...)``.  Returns
+    (H (k, 3, 3) float32, model info (k, 24), segment (k, n) float64, ransac_mask (k, n), original_mask (k, n), spectral
+    info (k, 6)) as device tensors, not synchronised.  ``status`` (int32, 1 element) collects every round's status bits."""
+    _needs_device(src, "hip_spectral_em")
+    dev, n, k = src.device, src.shape[0], int(em_steps)
+    for t, want in ((src, torch.float32), (dst, torch.float32), (c_feats, torch.float32), (o_feats, torch.float32),
+                    (F, torch.float64), (mask, torch.float32)):
+        if t.dtype != want or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"hip_spectral_em: inputs must be contiguous {want} tensors on {dev}")
+    if dst.shape != src.shape or c_feats.shape != (n, _native.SPECTRAL_DIM) or o_feats.shape != c_feats.shape or F.shape != (3, 3) \
+            or mask.shape != (n,):
+        raise ValueError("hip_spectral_em: shapes (n, 2), (n, 2), (n, 128), (n, 128), (3, 3), (n,) expected")
+    sp = np.ascontiguousarray(spec_params, dtype=np.float64)
+    mp = np.ascontiguousarray(model_params, dtype=np.float64)
+    H = torch.empty((k, 3, 3), dtype=torch.float32, device=dev)
+    info = torch.empty((k, _native.MODEL_INFO), dtype=torch.float64, device=dev)
+    seg = torch.empty((k, n), dtype=torch.float64, device=dev)
+    rm = torch.empty((k, n), dtype=torch.float32, device=dev)
+    om = torch.empty((k, n), dtype=torch.float32, device=dev)
+    sinfo = torch.empty((k, _native.SPECTRAL_INFO), dtype=torch.float64, device=dev)
+    work = _scratch(work, spectral_workspace_bytes(n) + model_workspace_bytes(n), dev)
+    dbl = ctypes.POINTER(ctypes.c_double)
+    _native.check(_native.lib().apap_spectral_em_device(
+        _native._h(ctx), src.data_ptr(), dst.data_ptr(), c_feats.data_ptr(), o_feats.data_ptr(), n, F.data_ptr(),
+        sp.ctypes.data_as(dbl), mp.ctypes.data_as(dbl), k, mask.data_ptr(), H.data_ptr(), info.data_ptr(), seg.data_ptr(),
+        rm.data_ptr(), om.data_ptr(), sinfo.data_ptr(), None if status is None else status.data_ptr(), work.data_ptr(),
+        work.numel(), _stream(dev)))
+    return H, info, seg, rm, om, sinfo

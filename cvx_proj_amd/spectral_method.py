@@ -9,6 +9,9 @@ runs), the part that needs neither OpenCV nor cvxpy: ``calculate_M`` (:66-133) a
 * ``recompute_matching``, ``match_RANSAC``, ``cv_to_array``, ``normalized_feature``: the reference's helpers.
   ``match_RANSAC`` uses THIS REPOSITORY's GPU RANSAC (``_native.find_homography_ransac``), not OpenCV's: sampler, adaptive
   stopping and refinement differ, so its mask is not cv.findHomography's (as in ``baseline_stitch_test``).
+* ``model_solve`` (:165-186): the M-step, model.py's LMSSolver / SDPSolver on the GPU (cvx_proj_amd/model.py).
+* ``spectral_em``: the EM loop of ``spectral_method()`` (:188-241) on arrays, every round on the device without a host
+  synchronisation (``apap_spectral_em``): calculate_M with Hg = the previous round's H_pred, then model_solve.
 * ``skew_symmetric_transform``, ``fundamental``, ``get_fundamental``: utils.py:162-186, host numpy.
 
 Keypoints and matches are duck-typed: anything with ``.pt`` and ``.queryIdx`` / ``.trainIdx`` (OpenCV's KeyPoint / DMatch
@@ -17,6 +20,7 @@ or simple stand-ins).  ``opts`` is any object with ``epi_weight``, ``affinity_ep
 """
 from __future__ import annotations
 
+import time
 import warnings
 from typing import NamedTuple
 
@@ -25,7 +29,8 @@ import numpy as np
 from . import _native
 
 __all__ = ["calculate_M", "spectral_weights", "SpectralResult", "recompute_matching", "match_RANSAC", "cv_to_array",
-           "normalized_feature", "skew_symmetric_transform", "fundamental", "get_fundamental"]
+           "normalized_feature", "model_solve", "spectral_em", "EMRound", "EMResult", "skew_symmetric_transform", "fundamental",
+           "get_fundamental"]
 
 
 class SpectralResult(NamedTuple):
@@ -155,6 +160,98 @@ def calculate_M(kpts_cp, feats_cp, kpts_op, feats_op, F, matches, opts, verbose=
             plt.tight_layout()
             plt.show()
     return res.segment, H, res.ransac_mask, res.original_mask
+
+
+# ------------------------------------------------------------------ M-step and EM loop (:165-241)
+def model_solve(kpts_cp, kpts_op, matches, weights, param=0.5, max_iter=8000, verbose=False, swap=True, lms=True, device=-1,
+                ctx=None):
+    """spectral_method.py:165-186: the matches with weight > 1e-3 (in order) into LMSSolver(max_iter, param) or
+    SDPSolver(max_iter, param, param).  Note the reference's defaults: lms=True with param=0.5 is the Huber loss, which
+    raises NotImplementedError here."""
+    from .model import LMSSolver, SDPSolver, solve_params
+    solver = LMSSolver(max_iter, param, device=device, ctx=ctx) if lms else SDPSolver(max_iter, param, param, device=device, ctx=ctx)
+    params = solver._params(swap)
+    params[3] = _native.MODEL_FLOOR
+    src, dst = cv_to_array(kpts_cp, kpts_op, matches)
+    w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+    if len(src) == 0 or not np.any(w.astype(np.float64) > _native.MODEL_FLOOR):
+        raise IndexError("too many indices for array: array is 1-dimensional, but 3 were indexed (no match selected)")
+    start = time.time()
+    if verbose:
+        solver._announce(int(np.count_nonzero(w.astype(np.float64) > _native.MODEL_FLOOR)))
+    H, solver.last = solve_params(params, src, dst, w, device=device, ctx=ctx)
+    if verbose:
+        print(f"Problem solved. Time consumption: {time.time() - start:.3f}")
+        print("The optimal value is", solver.last.objective)
+        print("Optimal solution:", H.ravel())
+    return H
+
+
+class EMRound(NamedTuple):
+    H_pred: np.ndarray          # (3, 3) float32: model_solve's result
+    spectral: SpectralResult    # the round's calculate_M (its H: Hg, or the first round's RANSAC homography)
+    model: object               # model.ModelResult of the round's M-step
+
+
+class EMResult(NamedTuple):
+    rounds: list                # EMRound per EM step
+    H_save: np.ndarray          # (3, 3) float64: inv(H_pred of the last round), normalised (:235-236)
+
+
+def _model_mode(lms, fluc, huber_param):
+    if lms:
+        if huber_param > 1e-2:
+            raise NotImplementedError("spectral_em with lms=True and huber_param > 1e-2 (the Huber loss) is not implemented on "
+                                      "the GPU: only the least-squares and SDP M-steps are")
+        return _native.model_params(_native.MODEL_LMS)
+    return _native.model_params(_native.MODEL_SDP, fluc, fluc)
+
+
+def spectral_em(src_pts, dst_pts, c_feats, o_feats, F, *, em_steps=2, lms=False, fluc=0.5, huber_param=-1.0, epi_weight=0.5,
+                affinity_eps=30.0, aff_thresh=0.5, em_radius=6.0, score_thresh=0.4, max_restarts=None, mask=None, swap=True,
+                device=-1, ctx=None):
+    """The EM loop of spectral_method() (:188-241) on arrays: ``em_steps`` rounds of calculate_M (Hg = the previous round's
+    H_pred) and model_solve(ransac_mask, param = huber_param if lms else fluc), all enqueued on the device at once.  The
+    first round's initial mask: ``mask``, else the GPU RANSAC of this repository (as spectral_weights; ``swap`` sets only the
+    direction of that RANSAC, as in match_RANSAC).  The M-step always inverts and normalises its solution (model_solve's
+    default swap=True, which spectral_method() uses).  Returns an EMResult.  Raises as model_solve (IndexError when a round selects no match, ValueError for a degenerate selection,
+    LinAlgError for a singular solution); warns as spectral_weights and the SDP solver."""
+    from .model import result_of, warn_no_convergence
+    mp = _model_mode(lms, fluc, huber_param)
+    src = np.ascontiguousarray(src_pts, dtype=np.float32)
+    dst = np.ascontiguousarray(dst_pts, dtype=np.float32)
+    sp = _native.spectral_params(epi_weight, affinity_eps, aff_thresh, em_radius, score_thresh,
+                                 0 if max_restarts is None else max_restarts)
+    H0 = None
+    if mask is None:
+        if src.ndim != 2 or len(src) == 0:
+            raise ValueError(f"no matches, or points not (n, 2): {src.shape}")
+        a, b = (dst, src) if swap else (src, dst)
+        H0, m = _native.find_homography_ransac(a, b, 5.0, device=device, ctx=ctx)
+        mask = m.astype(np.float32).ravel()
+    try:
+        out = _native.spectral_em(src, dst, c_feats, o_feats, F, sp, mp, em_steps, mask, device=device, ctx=ctx)
+    except _native.ApapValueError as e:
+        # the info blocks hold results only for rounds the kernels ran (NaN otherwise: an argument error)
+        out = getattr(e, "info", None)
+        info = out[1] if out is not None else np.empty((0, _native.MODEL_INFO))
+        status = info[:, _native.MODEL_INFO_STATUS]
+        bad = next((k for k in range(len(info)) if not np.isnan(status[k]) and int(status[k]) & _native.STATUS_MODEL_DEGENERATE),
+                   None)
+        if bad is not None and info[bad][_native.MODEL_INFO_COUNT] == 0:
+            raise IndexError(f"too many indices for array: array is 1-dimensional, but 3 were indexed (EM round {bad} "
+                             "selected no match)") from e
+        raise
+    H, info, seg, rm, om, sinfo = out
+    rounds = []
+    for k in range(em_steps):
+        res = _result(seg[k], rm[k], om[k], sinfo[k], H0 if k == 0 else H[k - 1])
+        m = result_of(info[k])
+        warn_no_convergence(m)
+        rounds.append(EMRound(H[k], res, m))
+    H_save = np.linalg.inv(H[-1]).astype(np.float64)
+    H_save /= H_save[-1, -1]
+    return EMResult(rounds, H_save)
 
 
 # ------------------------------------------------------------------ utils.py:162-186

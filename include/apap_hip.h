@@ -52,6 +52,10 @@ extern "C" {
 #define APAP_STATUS_INDEX 2      /* mesh edges do not cover the canvas (reference: IndexError)                 */
 #define APAP_STATUS_UNPREPARED 4 /* a gather on a warp workspace without lookup tables for this mesh / canvas */
 #define APAP_STATUS_NO_CONVERGENCE 8 /* the spectral eigen-solver hit its restart cap: the best Ritz vector is kept */
+/* Bits of the M-step (apap_model_solve*, apap_spectral_em*).  status_to_code above does not test them; the M-step's own entry
+ * points decode them (see there). */
+#define APAP_STATUS_MODEL_DEGENERATE 16     /* fewer than 4 selected matches, or a rank-deficient reduced system: H is NaN */
+#define APAP_STATUS_MODEL_NO_CONVERGENCE 32 /* the interior-point method hit its iteration cap: the best iterate is kept */
 
 /* Doubles per keypoint in the device point table (see apap_host_build_table). */
 #define APAP_TABLE_STRIDE 32
@@ -494,6 +498,81 @@ int apap_spectral_device(apap_ctx *ctx, const float *d_src, const float *d_dst, 
  * and for parity tests.  Same inputs as apap_spectral_weights; params' thresholds are not used. */
 int apap_spectral_affinity(apap_ctx *ctx, const float *src, const float *dst, const float *c_feats, const float *o_feats, int n,
                            const double *F, const double *params, double *M_out, int device);
+
+/* ------------------------------------------------- M-step and EM loop of the spectral method --- */
+/* model_solve of spectral_method.py:165-186 with model.py's solvers, in fp64, without cvxpy:
+ *   LMS  (LMSSolver, huber_param <= 1e-2):  min ||A h - rhs||^2                                   (model.py:29-41)
+ *   SDP  (SDPSolver(max_iter, du, dv)):     min r + t  s.t.  [[I_2n, P], [P^T, diag(r, r, t)]] >= 0,
+ *        P = [A1 h, A2 h, A h - rhs]                                                              (model.py:77-109)
+ * A, rhs (float32) and A1, A2 (float64) are built row by row on the device in the reference's dtypes and rounding from the
+ * selected matches (weight > the floor, in order).  A tall-skinny QR of K = [A | -rhs | A1's columns 0 3 6 | A2's 1 4 7]
+ * (2n x 15, fp64, fixed summation order) reduces the (2n+3)-sized LMI exactly to an 18 x 18 one in (h, r, t); the columns of
+ * h are equilibrated by powers of two.  LMS: back-substitution.  SDP: a primal-dual interior-point method (HKM direction,
+ * Mehrotra predictor-corrector, 10 x 10 Schur complement system) until tr(S Z) <= 1e-10 (r + t) or the iteration cap.
+ * The tail is model.py:50-56: h rounded to float32 with [2, 2] = 1; with swap, inverted (numpy.linalg.inv: fp64 LU, cast
+ * to float32) and divided by its [2, 2] in float32.
+ *   pts_c, pts_o    n x 2 float32 (kpts_cp[queryIdx].pt, kpts_op[trainIdx].pt)
+ *   weights         n float32
+ *   params          APAP_MODEL_PARAMS doubles, indexed by APAP_MODEL_* below
+ *   H_out           3 x 3 float32, row-major: what SDPSolver.solve / LMSSolver.solve returns
+ *   info_out        APAP_MODEL_INFO doubles, indexed by APAP_MODEL_INFO_* below
+ * Host-buffer call: H_out and info_out are set to NaN before anything else (a non-NULL pointer); an argument error returns
+ * APAP_ERR_INVALID_ARG with them so.  Once the kernels ran both hold their results and the call returns APAP_ERR_INVALID_ARG
+ * when APAP_STATUS_MODEL_DEGENERATE is set (H is NaN), APAP_ERR_SINGULAR when the inverse met a zero pivot (numpy:
+ * LinAlgError), APAP_OK otherwise, also when the iteration cap was hit (the status word is in
+ * info_out[APAP_MODEL_INFO_STATUS]).  n >= 1. */
+#define APAP_MODEL_LMS 0
+#define APAP_MODEL_SDP 1
+#define APAP_MODEL_MODE 0      /* APAP_MODEL_LMS or APAP_MODEL_SDP                                              */
+#define APAP_MODEL_DU 1        /* SDPSolver's du (model_solve: fluc)                                            */
+#define APAP_MODEL_DV 2        /* SDPSolver's dv (model_solve: fluc)                                            */
+#define APAP_MODEL_FLOOR 3     /* keep the matches with weight > floor (model_solve: 1e-3); -inf keeps them all  */
+#define APAP_MODEL_SWAP 4      /* 1: invert and normalise the solution (model.py:53-55)                          */
+#define APAP_MODEL_MAX_ITER 5  /* interior-point iteration cap; 0 = the default, 80                              */
+#define APAP_MODEL_PARAMS 6
+#define APAP_MODEL_INFO_OBJECTIVE 0 /* r + t (SDP) or ||A h - rhs||^2 (LMS)                                      */
+#define APAP_MODEL_INFO_R 1         /* SDP: r                                                                   */
+#define APAP_MODEL_INFO_T 2         /* SDP: t                                                                   */
+#define APAP_MODEL_INFO_GAP 3       /* SDP: tr(S Z) / (r + t) of the returned iterate (0 for LMS)                */
+#define APAP_MODEL_INFO_ITERS 4     /* SDP: interior-point iterations                                           */
+#define APAP_MODEL_INFO_STATUS 5    /* status word (APAP_STATUS_MODEL_*, APAP_STATUS_SINGULAR)                  */
+#define APAP_MODEL_INFO_COUNT 6     /* selected matches                                                          */
+#define APAP_MODEL_INFO_Z 7         /* SDP: 9 doubles, the dual 3 x 3 block (order u, v, q): the certificate      */
+#define APAP_MODEL_INFO_H 16        /* 8 doubles: h in fp64, before the float32 tail                             */
+#define APAP_MODEL_INFO 24
+int apap_model_solve(apap_ctx *ctx, const float *pts_c, const float *pts_o, const float *weights, int n, const double *params,
+                     float *H_out, double *info_out, int device);
+/* Scratch of the resident form for n matches: O(n / 240) 15 x 15 factors, 256-byte multiple. */
+size_t apap_model_workspace_bytes(int n);
+/* Resident form: every pointer but `params` (host) is a device pointer; d_work 256-byte aligned, points 8-byte aligned.
+ * Enqueues the reduction and the solve on `stream`.  d_H 9 floats, d_info APAP_MODEL_INFO doubles; d_status (may be NULL):
+ * the status bits are OR-ed into it.  An argument error returns at once and enqueues nothing. */
+int apap_model_solve_device(apap_ctx *ctx, const float *d_pts_c, const float *d_pts_o, const float *d_weights, int n,
+                            const double *params, float *d_H, double *d_info, int *d_status, void *d_work, size_t work_bytes,
+                            void *stream);
+/* The EM loop of spectral_method() (:188-241) on one pair: em_steps rounds of
+ *     calculate_M (apap_spectral_*, Hg = the previous round's H_pred; the first round takes mask_in)
+ *     model_solve(ransac_mask)  (weights floor 1e-3, swap; model_params' FLOOR and SWAP are overridden)
+ * on one stream (the resident form without any host synchronisation).  Outputs per round k (k = 0 .. em_steps-1): H_out[9 k], info_out[APAP_MODEL_INFO k],
+ * segment_out[n k], ransac_mask_out[n k], original_mask_out[n k], spec_info_out[APAP_SPECTRAL_INFO k].  mask_in: the first
+ * round's initial mask (what match_RANSAC returned), n float32.  Host-buffer call: with 1 <= em_steps <= 64, H_out and
+ * info_out are set to NaN before anything else; an argument error returns APAP_ERR_INVALID_ARG and writes nothing more.
+ * Once the kernels ran every output holds its round's results and the call returns the error of the first round whose
+ * M-step reported APAP_STATUS_MODEL_DEGENERATE or APAP_STATUS_SINGULAR (as apap_model_solve).  Like apap_spectral_weights it
+ * waits for each spectral restart cycle and stops at convergence (the resident form enqueues every cycle; same results). */
+int apap_spectral_em(apap_ctx *ctx, const float *src, const float *dst, const float *c_feats, const float *o_feats, int n,
+                     const double *F, const double *spec_params, const double *model_params, int em_steps, const float *mask_in,
+                     float *H_out, double *info_out, double *segment_out, float *ransac_mask_out, float *original_mask_out,
+                     double *spec_info_out, int device);
+/* Resident form of apap_spectral_em: device pointers but the two parameter blocks; d_work of at least
+ * apap_spectral_workspace_bytes(n) + apap_model_workspace_bytes(n) bytes, 256-byte aligned.  d_status (may be NULL) collects
+ * every round's status bits.  Enqueues every round, every spectral restart cycle included (those after convergence return at
+ * once but each costs its launch), and does not wait. */
+int apap_spectral_em_device(apap_ctx *ctx, const float *d_src, const float *d_dst, const float *d_c_feats, const float *d_o_feats,
+                            int n, const double *d_F, const double *spec_params, const double *model_params, int em_steps,
+                            const float *d_mask_in, float *d_H, double *d_info, double *d_segment, float *d_ransac_mask,
+                            float *d_original_mask, double *d_spec_info, int *d_status, void *d_work, size_t work_bytes,
+                            void *stream);
 
 #ifdef __cplusplus
 }
