@@ -169,6 +169,11 @@ SIGNATURES = {
                                    _f64p, _f32p, _f32p, _f64p, C.c_int]),
     "apap_spectral_em_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _f64p, _f64p, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _vp, C.c_size_t, _vp]),
+    "apap_spectral_em_batch_workspace_bytes": (C.c_size_t, [_i32p, C.c_int, _i32p, C.c_int]),
+    "apap_spectral_em_batch_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32p, C.c_int, _i32p, _f64p, _f64p, C.c_int,
+                                                C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "apap_spectral_em_batch": (C.c_int, [_vp, _f32p, _f32p, _f32p, _f32p, _f64p, _f32p, _i32p, C.c_int, _i32p, _f64p, _f64p,
+                                         C.c_int, C.c_int, _f32p, _f64p, _f64p, _f32p, _f32p, _f64p, _i32p, C.c_int]),
 }
 
 _lib = None
@@ -672,3 +677,79 @@ def spectral_em(src, dst, c_feats, o_feats, F, spec_params, model_params_, em_st
     out = (H, info, seg, rm, om, sinfo)
     _check_with_info(code, out)
     return out
+
+
+def em_batch_tables(pair_lengths, pair_of, spec_params, model_params_):
+    """The host tables of the batch entry points, checked: (pair_offset (P + 1,) int32, pair_of (B,) int32, spec_params
+    (B, 6) float64, model_params (B, 6) float64).  ``pair_lengths``: the number of matches of each pair."""
+    lengths = np.asarray(pair_lengths, dtype=np.int64).ravel()
+    if len(lengths) == 0 or np.any(lengths < 1):
+        raise ValueError("a batch needs at least one pair, and every pair at least one match")
+    off = np.zeros(len(lengths) + 1, np.int32)
+    off[1:] = np.cumsum(lengths)
+    po = np.asarray(pair_of)
+    if po.ndim != 1 or len(po) == 0 or not np.issubdtype(po.dtype, np.integer):
+        raise ValueError("pair_of must be a non-empty 1-D integer array")
+    if np.any(po < 0) or np.any(po >= len(lengths)):
+        raise ValueError(f"pair_of holds a pair index outside 0 .. {len(lengths) - 1}")
+    po = np.ascontiguousarray(po, dtype=np.int32)
+    sp = np.ascontiguousarray(spec_params, dtype=np.float64)
+    mp = np.ascontiguousarray(model_params_, dtype=np.float64)
+    if sp.shape != (len(po), SPECTRAL_PARAMS) or mp.shape != (len(po), MODEL_PARAMS):
+        raise ValueError(f"spectral / model parameter blocks must be ({len(po)}, {SPECTRAL_PARAMS}) and ({len(po)}, {MODEL_PARAMS}); "
+                         f"got {sp.shape} and {mp.shape}")
+    if np.any(sp[:, 5] != sp[0, 5]):
+        raise ValueError("max_restarts must be equal across the problems of a batch (the cap fixes how many cycles are enqueued)")
+    return off, po, sp, mp
+
+
+def em_batch_split(flat, lengths, em_steps):
+    """A per-match output of a batch call (problem-major, round-major inside a problem) as a list of (em_steps, n_b) views."""
+    out, at = [], 0
+    for n in lengths:
+        out.append(flat[at:at + em_steps * n].reshape(em_steps, n))
+        at += em_steps * n
+    return out
+
+
+def spectral_em_batch(src, dst, c_feats, o_feats, F, mask, pair_lengths, pair_of, spec_params, model_params_, em_steps, device=-1,
+                      ctx=None):
+    """``apap_spectral_em_batch``: B EM problems in lockstep.  src / dst (N, 2), c_feats / o_feats (N, 128), mask (N,): the
+    pairs concatenated, pair p of ``pair_lengths[p]`` matches; F (P, 3, 3); ``pair_of`` (B,): the pair of each problem;
+    ``spec_params`` (B, 6), ``model_params_`` (B, 6).  Returns (H (B, k, 3, 3) float32, model info (B, k, 24), segment, ransac_mask,
+    original_mask: lists of B arrays (k, n_b), spectral info (B, k, 6), status (B,) int32).  Every problem's outputs equal
+    ``spectral_em``'s for that problem alone, byte for byte.  A degenerate, singular or unconverged problem does not raise: its
+    bits are in ``status`` and in its info blocks."""
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    dst = np.ascontiguousarray(dst, dtype=np.float32)
+    c = np.ascontiguousarray(c_feats, dtype=np.float32)
+    o = np.ascontiguousarray(o_feats, dtype=np.float32)
+    F = np.ascontiguousarray(F, dtype=np.float64)
+    off, po, sp, mp = em_batch_tables(pair_lengths, pair_of, spec_params, model_params_)
+    N, P, B, k = int(off[-1]), len(off) - 1, len(po), int(em_steps)
+    if src.shape != (N, 2) or dst.shape != (N, 2):
+        raise ValueError(f"src/dst must both be ({N}, 2); got {src.shape} and {dst.shape}")
+    if c.shape != (N, SPECTRAL_DIM) or o.shape != (N, SPECTRAL_DIM):
+        raise ValueError(f"descriptors must be ({N}, {SPECTRAL_DIM}); got {c.shape} and {o.shape}")
+    if F.shape != (P, 3, 3):
+        raise ValueError(f"F must be ({P}, 3, 3); got {F.shape}")
+    mask = np.ascontiguousarray(mask, dtype=np.float32).ravel()
+    if mask.shape != (N,):
+        raise ValueError(f"mask must hold {N} values; got {mask.shape}")
+    if not 1 <= k <= 64:
+        raise ValueError(f"em_steps {k} (1 .. 64)")
+    lengths = [int(off[p + 1] - off[p]) for p in po]
+    M = sum(lengths)
+    H = np.full((B, k, 3, 3), np.nan, np.float32)
+    info = np.full((B, k, MODEL_INFO), np.nan)
+    seg = np.empty(k * M, np.float64)
+    rm = np.empty(k * M, np.float32)
+    om = np.empty(k * M, np.float32)
+    sinfo = np.empty((B, k, SPECTRAL_INFO), np.float64)
+    status = np.zeros(B, np.int32)
+    check(lib().apap_spectral_em_batch(_h(ctx), _ptr(src, C.c_float), _ptr(dst, C.c_float), _ptr(c, C.c_float), _ptr(o, C.c_float),
+                                       _ptr(F, C.c_double), _ptr(mask, C.c_float), _ptr(off, C.c_int), P, _ptr(po, C.c_int),
+                                       _ptr(sp, C.c_double), _ptr(mp, C.c_double), B, k, _ptr(H, C.c_float), _ptr(info, C.c_double),
+                                       _ptr(seg, C.c_double), _ptr(rm, C.c_float), _ptr(om, C.c_float), _ptr(sinfo, C.c_double),
+                                       _ptr(status, C.c_int), device))
+    return (H, info, em_batch_split(seg, lengths, k), em_batch_split(rm, lengths, k), em_batch_split(om, lengths, k), sinfo, status)

@@ -965,4 +965,67 @@ int apap_spectral_em(apap_ctx *ctx, const float *src, const float *dst, const fl
     return APAP_OK;
 }
 
+int apap_spectral_em_batch(apap_ctx *ctx, const float *src, const float *dst, const float *c_feats, const float *o_feats,
+                           const double *F, const float *mask_in, const int *pair_offset, int n_pairs, const int *pair_of,
+                           const double *spec_params, const double *model_params, int n_problems, int em_steps, float *H_out,
+                           double *info_out, double *segment_out, float *ransac_mask_out, float *original_mask_out,
+                           double *spec_info_out, int *status_out, int device) {
+    const char *who = "apap_spectral_em_batch";
+    if (!src || !dst || !c_feats || !o_feats || !F || !mask_in || !pair_offset || !pair_of || !spec_params || !model_params ||
+        !H_out || !info_out || !segment_out || !ransac_mask_out || !original_mask_out || !spec_info_out)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc = apap::spectral_em_batch_check(pair_offset, n_pairs, pair_of, spec_params, model_params, n_problems, em_steps, who);
+    if (rc) return rc;
+    PoolLock pl(ctx);
+    int dev;
+    if ((rc = select_device(device, &dev))) return rc;
+    const size_t N = (size_t)(pair_offset[n_pairs] - pair_offset[0]), B = (size_t)n_problems, k = (size_t)em_steps;
+    size_t M = 0;   // matches over the problems
+    for (int b = 0; b < n_problems; ++b) M += (size_t)(pair_offset[pair_of[b] + 1] - pair_offset[pair_of[b]]);
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    const size_t pts = N * 2 * sizeof(float), feats = N * APAP_SPECTRAL_DIM * sizeof(float);
+    const size_t o_src = take(pts), o_dst = take(pts), o_c = take(feats), o_o = take(feats), o_F = take((size_t)n_pairs * 9 * sizeof(double));
+    const size_t o_mask = take(N * sizeof(float)), o_H = take(B * k * 9 * sizeof(float)), o_info = take(B * k * APAP_MODEL_INFO * sizeof(double));
+    const size_t o_seg = take(k * M * sizeof(double)), o_rm = take(k * M * sizeof(float)), o_om = take(k * M * sizeof(float));
+    const size_t o_sinfo = take(B * k * APAP_SPECTRAL_INFO * sizeof(double)), o_status = take(B * sizeof(int));
+    const size_t work_bytes = apap_spectral_em_batch_workspace_bytes(pair_offset, n_pairs, pair_of, n_problems);
+    void *d_io, *d_work;
+    if ((rc = slot_get(pl.pool, S_AUX, off, dev, &d_io))) return rc;
+    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
+    char *d = (char *)d_io;
+    const size_t first = (size_t)pair_offset[0];   // the device arrays start at the first pair
+    std::vector<int> rel((size_t)n_pairs + 1);
+    for (int p = 0; p <= n_pairs; ++p) rel[p] = pair_offset[p] - pair_offset[0];
+    APAP_HIP_TRY(hipMemcpyAsync(d + o_src, src + first * 2, pts, hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + o_dst, dst + first * 2, pts, hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + o_c, c_feats + first * APAP_SPECTRAL_DIM, feats, hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + o_o, o_feats + first * APAP_SPECTRAL_DIM, feats, hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + o_F, F, (size_t)n_pairs * 9 * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + o_mask, mask_in + first, N * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemsetAsync(d + o_status, 0, B * sizeof(int), nullptr));
+    rc = apap::spectral_em_batch_run(ctx, (const float *)(d + o_src), (const float *)(d + o_dst), (const float *)(d + o_c),
+                                     (const float *)(d + o_o), (const double *)(d + o_F), (const float *)(d + o_mask), rel.data(),
+                                     n_pairs, pair_of, spec_params, model_params, n_problems, em_steps, (float *)(d + o_H),
+                                     (double *)(d + o_info), (double *)(d + o_seg), (float *)(d + o_rm), (float *)(d + o_om),
+                                     (double *)(d + o_sinfo), (int *)(d + o_status), d_work, work_bytes, nullptr, 1);
+    if (rc) {
+        (void)hipStreamSynchronize(nullptr);
+        return rc;
+    }
+    APAP_HIP_TRY(hipMemcpyAsync(H_out, d + o_H, B * k * 9 * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(info_out, d + o_info, B * k * APAP_MODEL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(segment_out, d + o_seg, k * M * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(ransac_mask_out, d + o_rm, k * M * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(original_mask_out, d + o_om, k * M * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(spec_info_out, d + o_sinfo, B * k * APAP_SPECTRAL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    if (status_out) APAP_HIP_TRY(hipMemcpyAsync(status_out, d + o_status, B * sizeof(int), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    return APAP_OK;   // a problem's status is its own: see status_out and the info blocks
+}
+
 }  // extern "C"

@@ -107,6 +107,16 @@ int spectral_em_run(apap_ctx *ctx, const float *d_src, const float *d_dst, const
                     const double *d_F, const double *spec_params, const double *model_params, int em_steps, const float *d_mask_in,
                     float *d_H, double *d_info, double *d_segment, float *d_ransac_mask, float *d_original_mask,
                     double *d_spec_info, int *d_status, void *d_work, size_t work_bytes, void *stream, int sync_each);
+// apap_spectral_em_batch_device (apap_em_batch.hip), with `sync_each` = 1 for the host-buffer entry point: it waits for every
+// restart cycle and stops a round's cycles once every problem of the batch reports convergence.
+int spectral_em_batch_run(apap_ctx *ctx, const float *d_src, const float *d_dst, const float *d_c_feats, const float *d_o_feats,
+                          const double *d_F, const float *d_mask_in, const int *pair_offset, int n_pairs, const int *pair_of,
+                          const double *spec_params, const double *model_params, int n_problems, int em_steps, float *d_H,
+                          double *d_info, double *d_segment, float *d_ransac_mask, float *d_original_mask, double *d_spec_info,
+                          int *d_status, void *d_work, size_t work_bytes, void *stream, int sync_each);
+// The argument checks of the batch entry points that need no device pointer.
+int spectral_em_batch_check(const int *pair_offset, int n_pairs, const int *pair_of, const double *spec_params,
+                            const double *model_params, int n_problems, int em_steps, const char *who);
 // Set-up and the dense M (n x n doubles) on `stream`.
 int spectral_affinity_run(const float *d_src, const float *d_dst, const float *d_c, const float *d_o, int n, const double *d_F,
                           const double *params, double *d_M, void *d_work, size_t work_bytes, void *stream);

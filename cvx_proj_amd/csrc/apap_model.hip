@@ -19,554 +19,23 @@
 
 #include "apap_internal.h"
 
+#include "apap_model_dev.h"
+
 namespace {
 
 inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
 
-constexpr int kW = 64;            // one wave per block
-constexpr int kC = 15;            // columns of K
-constexpr int kD = 18;            // the LMI's order
-constexpr int kDD = kD * kD;
-constexpr int kV = 10;            // unknowns of the SDP: h (8), r, t
-constexpr int kPair = 24;         // matches per Householder fold (48 rows in lanes 15..62)
-constexpr int kMinRounds = 10;    // at least 240 matches per block
-constexpr int kMaxBlocks = 1024;
-constexpr int kDefaultIters = 80;
-constexpr double kGapTol = 1e-10;   // tr(S Z) <= kGapTol (r + t)
-constexpr double kRankTol = 1e-12;  // |R_jj| of the equilibrated factor (unit-scale columns) below this: rank-deficient
-constexpr double kStep = 0.98;      // fraction of the step to the cone's boundary
-constexpr int kBisect = 14;         // bisection steps of the step length
-
-struct ModelLayout {
-    int n, per_block, nb;
-    size_t R, cnt, total;
-};
-
-ModelLayout model_layout(int n) {
-    ModelLayout L{};
-    L.n = n;
-    int rounds = (n + kPair * kMaxBlocks - 1) / (kPair * kMaxBlocks);
-    if (rounds < kMinRounds) rounds = kMinRounds;
-    L.per_block = rounds * kPair;
-    L.nb = (n + L.per_block - 1) / L.per_block;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) / 256 * 256;
-        return at;
-    };
-    L.R = take((size_t)L.nb * kC * kC * sizeof(double));
-    L.cnt = take((size_t)L.nb * sizeof(int));
-    L.total = off;
-    return L;
-}
-
-struct ModelScalars {
-    int mode, swap, use_floor, max_iter;
-    float du32, dv32;
-    double floor, du, dv;
-};
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = kW / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// Householder QR of the wave's 64 x 15 panel (one row per lane), in place: afterwards lanes 0..14 hold R (upper triangular,
-// diagonal of either sign) and the other lanes zeros.  Lanes 0..14 enter with an upper triangular R (or zeros).
-__device__ __forceinline__ void hh_panel(double (&a)[kC], int lane) {
-#pragma unroll
-    for (int j = 0; j < kC; ++j) {
-        const double x = a[j];
-        const double sig = wsum(lane > j ? x * x : 0.0);
-        const double x0 = __shfl(x, j);
-        if (sig == 0.0) continue;   // wave-uniform: the column is reduced already
-        const double mu = sqrt(x0 * x0 + sig);
-        const double v0 = x0 <= 0.0 ? x0 - mu : -sig / (x0 + mu);
-        const double tau = 2.0 * v0 * v0 / (sig + v0 * v0);
-        const double v = lane == j ? 1.0 : (lane > j ? x / v0 : 0.0);
-#pragma unroll
-        for (int k = j + 1; k < kC; ++k) {
-            const double d = wsum(v * a[k]);
-            a[k] -= tau * v * d;
-        }
-        a[j] = lane == j ? mu : (lane > j ? 0.0 : x);
-    }
-}
-
-// Row 2i + odd of K for match i (model.py:29-35, :77-93; every product rounded as numpy does, -ffp-contract=off):
-//   A      even [xc w, yc w, w, 0, 0, 0, (-xo xc) w, (-xo yc) w]   odd [0, 0, 0, xc w, yc w, w, (-yo xc) w, (-yo yc) w]  float32
-//   rhs    even xo w, odd yo w                                                                                          float32
-//   A1     cols 0 3 6: even (du32 w, 0, (-xo du) w), odd (0, du32 w, (-yo du) w)                                         float64
-//   A2     cols 1 4 7: even (dv32 w, 0, (-xo dv) w), odd (0, dv32 w, (-yo dv) w)                                         float64
-__device__ __forceinline__ void k_row(double (&a)[kC], float2 c, float2 o, float w, int odd, const ModelScalars &sc) {
-    const float p = odd ? o.y : o.x;   // xo or yo
-    const float np_ = -p;
-    const float r0 = (np_ * c.x) * w, r1 = (np_ * c.y) * w;
-    const double wd = (double)w;
-    const double diag_u = (double)sc.du32 * wd, diag_v = (double)sc.dv32 * wd;
-    const double lu = ((double)np_ * sc.du) * wd, lv = ((double)np_ * sc.dv) * wd;
-#pragma unroll
-    for (int k = 0; k < kC; ++k) a[k] = 0.0;
-    const int o3 = odd ? 3 : 0;
-    a[o3 + 0] = (double)(c.x * w);
-    a[o3 + 1] = (double)(c.y * w);
-    a[o3 + 2] = (double)(1.0f * w);
-    a[6] = (double)r0;
-    a[7] = (double)r1;
-    a[8] = -(double)(p * w);
-    a[9] = odd ? 0.0 : diag_u;
-    a[10] = odd ? diag_u : 0.0;
-    a[11] = lu;
-    a[12] = odd ? 0.0 : diag_v;
-    a[13] = odd ? diag_v : 0.0;
-    a[14] = lv;
-}
-
-// ---- M1 ------------------------------------------------------------------------------------------------------------------
+// The kernels of one problem: the bodies of apap_model_dev.h on this launch's blocks.
 __global__ __launch_bounds__(kW) void k_model_tsqr(const float2 *__restrict__ pc, const float2 *__restrict__ po,
                                                    const float *__restrict__ w, int n, int per_block, ModelScalars sc,
                                                    double *__restrict__ Rb, int *__restrict__ cnt) {
-    const int lane = threadIdx.x;
-    const int begin = blockIdx.x * per_block;
-    const int end = min(n, begin + per_block);
-    double a[kC];
-#pragma unroll
-    for (int k = 0; k < kC; ++k) a[k] = 0.0;
-    int count = 0;
-    for (int base = begin; base < end; base += kPair) {
-        const int r = lane - kC;
-        const int i = base + (r >> 1);
-        bool keep = false;
-        if (r >= 0 && r < 2 * kPair && i < end) {
-            const float wi = w[i];
-            keep = !sc.use_floor || (double)wi > sc.floor;   // numpy 1.x: float32 scalar vs Python float in float64
-            if (keep) k_row(a, pc[i], po[i], wi, r & 1, sc);
-        }
-        if (lane >= kC && !keep) {
-#pragma unroll
-            for (int k = 0; k < kC; ++k) a[k] = 0.0;
-        }
-        count += __popcll(__ballot(keep && (r & 1) == 0));
-        hh_panel(a, lane);
-    }
-    if (lane < kC) {
-        double *row = Rb + ((size_t)blockIdx.x * kC + lane) * kC;
-#pragma unroll
-        for (int k = 0; k < kC; ++k) row[k] = a[k];
-    }
-    if (lane == 0) cnt[blockIdx.x] = count;
-}
-
-// ---- M2: LDS helpers (one wave; every helper ends with a barrier) ---------------------------------------------------------
-struct Lds {
-    double F[kV + 1][kDD];   // F0 and the ten basis matrices of S(x) = F0 + sum x_i F_i
-    double S[kDD], Z[kDD], Si[kDD], T[kDD], W1[kDD], W2[kDD], dSa[kDD], dZa[kDD], C[kDD];
-    double R[kC * kC];
-    double M[kV * kV], Mc[kV * kV], x[kV], dx[kV], g[kV], rhs[kV], best_x[kV], best_z[9];
-    double d[kC];
-    int flag;
-};
-
-__device__ __forceinline__ void mm(double *C, const double *A, const double *B, int lane) {   // C = A B
-    for (int e = lane; e < kDD; e += kW) {
-        const int i = e / kD, j = e % kD;
-        double s = 0.0;
-        for (int k = 0; k < kD; ++k) s += A[i * kD + k] * B[k * kD + j];
-        C[e] = s;
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ double dot_dd(const double *A, const double *B, int lane) {   // sum A o B (wave-uniform)
-    double s = 0.0;
-    for (int e = lane; e < kDD; e += kW) s += A[e] * B[e];
-    return wsum(s);
-}
-
-__device__ __forceinline__ double dot_dt(const double *A, const double *B, int lane) {   // sum A o B^T
-    double s = 0.0;
-    for (int e = lane; e < kDD; e += kW) s += A[e] * B[(e % kD) * kD + e / kD];
-    return wsum(s);
-}
-
-// In-place Cholesky of the 18 x 18 A (lower triangle); false (wave-uniform) when A is not positive definite.
-__device__ bool chol18(double *A, int lane) {
-    for (int k = 0; k < kD; ++k) {
-        const double p = A[k * kD + k];
-        if (!(p > 0.0)) {
-            __syncthreads();
-            return false;
-        }
-        const double d = sqrt(p);
-        __syncthreads();
-        for (int i = k + 1 + lane; i < kD; i += kW) A[i * kD + k] /= d;
-        if (lane == 0) A[k * kD + k] = d;
-        __syncthreads();
-        const int m = kD - k - 1;
-        for (int e = lane; e < m * m; e += kW) {
-            const int i = k + 1 + e / m, j = k + 1 + e % m;
-            if (j <= i) A[i * kD + j] -= A[i * kD + k] * A[j * kD + k];
-        }
-        __syncthreads();
-    }
-    return true;
-}
-
-// The step length: 1 when A + dA / kStep is positive definite, else kStep x the largest feasible point of a kBisect-step
-// bisection of [0, 1 / kStep] (tests/model_spec.py: max_step).
-__device__ double max_step(const double *A, const double *dA, double *T, int lane) {
-    auto ok = [&](double a) {
-        for (int e = lane; e < kDD; e += kW) T[e] = A[e] + a * dA[e];
-        __syncthreads();
-        return chol18(T, lane);
-    };
-    double hi = 1.0 / kStep;
-    if (ok(hi)) return 1.0;
-    double lo = 0.0;
-    for (int b = 0; b < kBisect; ++b) {
-        const double mid = 0.5 * (lo + hi);
-        if (ok(mid)) lo = mid;
-        else hi = mid;
-    }
-    return kStep * lo;
-}
-
-// Si = S^-1 through the Cholesky factor in T (T = L L^T on entry): W2 = L^-1 by columns, Si = W2^T W2.
-__device__ void inverse_from_chol(const double *T, double *W2, double *Si, int lane) {
-    if (lane < kD) {
-        const int c = lane;
-        for (int i = 0; i < kD; ++i) {
-            double s = i == c ? 1.0 : 0.0;
-            for (int k = c; k < i; ++k) s -= T[i * kD + k] * W2[k * kD + c];
-            W2[i * kD + c] = i < c ? 0.0 : s / T[i * kD + i];
-        }
-    }
-    __syncthreads();
-    for (int e = lane; e < kDD; e += kW) {
-        const int a = e / kD, b = e % kD;
-        double s = 0.0;
-        for (int k = 0; k < kD; ++k) s += W2[k * kD + a] * W2[k * kD + b];
-        Si[e] = s;
-    }
-    __syncthreads();
-}
-
-// 10 x 10 Cholesky solve of M dx = rhs on lane 0 (M in L.M, overwritten); dx to L.dx.  false: M not positive definite.
-__device__ bool schur_solve(Lds &L, int lane) {
-    if (lane == 0) {
-        double *M = L.M;
-        bool good = true;
-        for (int k = 0; k < kV && good; ++k) {
-            double p = M[k * kV + k];
-            for (int j = 0; j < k; ++j) p -= M[k * kV + j] * M[k * kV + j];
-            if (!(p > 0.0)) good = false;
-            const double d = sqrt(p);
-            M[k * kV + k] = d;
-            for (int i = k + 1; i < kV; ++i) {
-                double s = M[i * kV + k];
-                for (int j = 0; j < k; ++j) s -= M[i * kV + j] * M[k * kV + j];
-                M[i * kV + k] = s / d;
-            }
-        }
-        if (good) {
-            double y[kV];
-            for (int i = 0; i < kV; ++i) {
-                double s = L.rhs[i];
-                for (int j = 0; j < i; ++j) s -= M[i * kV + j] * y[j];
-                y[i] = s / M[i * kV + i];
-            }
-            for (int i = kV - 1; i >= 0; --i) {
-                double s = y[i];
-                for (int j = i + 1; j < kV; ++j) s -= M[j * kV + i] * L.dx[j];
-                L.dx[i] = s / M[i * kV + i];
-            }
-        }
-        L.flag = good;
-    }
-    __syncthreads();
-    return L.flag != 0;
-}
-
-// dS = sum dx_i F_i;  dZ = sym(E - Z - Si dS Z), E = extra_si x Si - (C if with_c).  W1 = Si dS on return.
-__device__ void directions(Lds &L, double *dS, double *dZ, double extra_si, bool with_c, int lane) {
-    for (int e = lane; e < kDD; e += kW) {
-        double s = 0.0;
-        for (int i = 0; i < kV; ++i) s += L.dx[i] * L.F[i + 1][e];
-        dS[e] = s;
-    }
-    __syncthreads();
-    mm(L.W1, L.Si, dS, lane);
-    mm(L.W2, L.W1, L.Z, lane);
-    for (int e = lane; e < kDD; e += kW) {
-        const int a = e / kD, b = e % kD, et = b * kD + a;
-        const double v1 = extra_si * L.Si[e] - (with_c ? L.C[e] : 0.0) - L.Z[e] - L.W2[e];
-        const double v2 = extra_si * L.Si[et] - (with_c ? L.C[et] : 0.0) - L.Z[et] - L.W2[et];
-        dZ[e] = 0.5 * (v1 + v2);
-    }
-    __syncthreads();
-}
-
-// The interior-point method (tests/model_spec.py: ipm) on the equilibrated R in L.R, from h0 in L.x[0..7].  Leaves the
-// best iterate in L.best_x / L.best_z; returns (relative gap, iterations) through the references.
-__device__ void ipm(Lds &L, int lane, int max_iter, double &best_rel, int &iters) {
-    // the basis: F0 = [[I, R[:, 8] in column q]], F_{1+j} = R[:, j] in column q, plus A1 / A2's columns in u / v
-    for (int e = lane; e < (kV + 1) * kDD; e += kW) (&L.F[0][0])[e] = 0.0;
-    __syncthreads();
-    if (lane < kC) {
-        const int r = lane;
-        auto put = [&](int k, int col, double v) {
-            L.F[k][r * kD + kC + col] += v;
-            L.F[k][(kC + col) * kD + r] += v;
-        };
-        L.F[0][r * kD + r] = 1.0;
-        put(0, 2, L.R[r * kC + 8]);
-        for (int j = 0; j < 8; ++j) {
-            put(j + 1, 2, L.R[r * kC + j]);
-            if (j % 3 == 0) put(j + 1, 0, L.R[r * kC + 9 + j / 3]);
-            if (j % 3 == 1) put(j + 1, 1, L.R[r * kC + 12 + j / 3]);
-        }
-    }
-    if (lane == 0) {
-        L.F[9][15 * kD + 15] = L.F[9][16 * kD + 16] = 1.0;
-        L.F[10][17 * kD + 17] = 1.0;
-    }
-    __syncthreads();
-    // start: tau = 2 tr(G(h0)) + 1e-12, G = (R X)^T (R X); x = (h0, tau, tau), Z = diag(tau / 2 I_15, 1/2, 1/2, 1)
-    double g_uu = 0.0, g_vv = 0.0, g_qq = 0.0;
-    if (lane < kC) {
-        const int r = lane;
-        const double *Rr = L.R + r * kC;
-        double u = 0.0, v = 0.0, q = Rr[8];
-        for (int m = 0; m < 3; ++m) {
-            u += Rr[9 + m] * L.x[3 * m];
-            v += Rr[12 + m] * L.x[3 * m + 1];
-        }
-        for (int j = 0; j < 8; ++j) q += Rr[j] * L.x[j];
-        g_uu = u * u;
-        g_vv = v * v;
-        g_qq = q * q;
-    }
-    const double tau = 2.0 * (wsum(g_uu) + wsum(g_vv) + wsum(g_qq)) + 1e-12;
-    __syncthreads();
-    if (lane == 0) L.x[8] = L.x[9] = tau;
-    for (int e = lane; e < kDD; e += kW) {
-        const int a = e / kD, b = e % kD;
-        L.Z[e] = a != b ? 0.0 : a < kC ? 0.5 * tau : a < 17 ? 0.5 : 1.0;
-    }
-    __syncthreads();
-    best_rel = INFINITY;
-    iters = 0;
-    for (int it = 0;; ++it) {
-        for (int e = lane; e < kDD; e += kW) {
-            double s = L.F[0][e];
-            for (int i = 0; i < kV; ++i) s += L.x[i] * L.F[i + 1][e];
-            L.S[e] = s;
-        }
-        __syncthreads();
-        const double gap_abs = dot_dd(L.S, L.Z, lane);
-        const double obj = L.x[8] + L.x[9];
-        const double rel = gap_abs / fmax(obj, 1e-300);
-        if (rel < best_rel) {   // wave-uniform
-            best_rel = rel;
-            iters = it;
-            if (lane < kV) L.best_x[lane] = L.x[lane];
-            if (lane < 9) L.best_z[lane] = L.Z[(kC + lane / 3) * kD + kC + lane % 3];
-        }
-        iters = it;
-        if (rel <= kGapTol || it == max_iter) break;
-        const double mu = gap_abs / kD;
-        // S^-1
-        for (int e = lane; e < kDD; e += kW) L.T[e] = L.S[e];
-        __syncthreads();
-        if (!chol18(L.T, lane)) break;   // rounding pushed S out of the cone: keep the best iterate
-        inverse_from_chol(L.T, L.W2, L.Si, lane);
-        // Schur complement M_ij = tr(F_i S^-1 F_j Z) and g_i = tr(S^-1 F_i)
-        for (int j = 0; j < kV; ++j) {
-            mm(L.W1, L.Si, L.F[j + 1], lane);
-            mm(L.W2, L.W1, L.Z, lane);
-            for (int i = 0; i < kV; ++i) {
-                const double m = dot_dt(L.F[i + 1], L.W2, lane);
-                if (lane == 0) L.M[i * kV + j] = m;
-            }
-        }
-        for (int i = 0; i < kV; ++i) {
-            const double gi = dot_dd(L.Si, L.F[i + 1], lane);
-            if (lane == 0) {
-                L.g[i] = gi;
-                L.rhs[i] = i < 8 ? 0.0 : -1.0;   // predictor: -c
-            }
-        }
-        __syncthreads();
-        for (int e = lane; e < kV * kV; e += kW) L.Mc[e] = L.M[e];   // the corrector solves with M again
-        __syncthreads();
-        if (!schur_solve(L, lane)) break;
-        directions(L, L.dSa, L.dZa, 0.0, false, lane);
-        // C = S^-1 dSa dZa (W1 = S^-1 dSa)
-        mm(L.C, L.W1, L.dZa, lane);
-        const double ap = max_step(L.S, L.dSa, L.T, lane);
-        const double ad = max_step(L.Z, L.dZa, L.T, lane);
-        double s = 0.0;
-        for (int e = lane; e < kDD; e += kW) s += (L.S[e] + ap * L.dSa[e]) * (L.Z[e] + ad * L.dZa[e]);
-        const double mu_aff = wsum(s) / kD;
-        const double ratio = mu_aff / mu;
-        const double sig = fmin(1.0, ratio * ratio * ratio);
-        // corrector: M dx = sig mu g - c - tr(F_i C)
-        for (int e = lane; e < kV * kV; e += kW) L.M[e] = L.Mc[e];
-        for (int i = 0; i < kV; ++i) {
-            const double fc = dot_dt(L.F[i + 1], L.C, lane);
-            if (lane == 0) L.rhs[i] = sig * mu * L.g[i] - (i < 8 ? 0.0 : 1.0) - fc;
-        }
-        __syncthreads();
-        if (!schur_solve(L, lane)) break;
-        directions(L, L.dSa, L.dZa, sig * mu, true, lane);   // dS, dZ reuse the predictor's buffers
-        const double bp = max_step(L.S, L.dSa, L.T, lane);
-        const double bd = max_step(L.Z, L.dZa, L.T, lane);
-        if (lane < kV) L.x[lane] += bp * L.dx[lane];
-        for (int e = lane; e < kDD; e += kW) L.Z[e] += bd * L.dZa[e];
-        __syncthreads();
-    }
-}
-
-// ---- M2 ------------------------------------------------------------------------------------------------------------------
-// The power of two nearest x on a log scale: x = m 2^e, m in [1/2, 1) -> 2^e if m >= sqrt(1/2), else 2^(e-1); 1 for 0 / inf
-// / NaN (tests/model_spec.py: pow2_near).
-__device__ __forceinline__ double pow2_near(double x) {
-    if (!(x > 0.0) || isinf(x)) return 1.0;
-    int e;
-    const double m = frexp(x, &e);
-    return ldexp(1.0, m >= 0.70710678118654752440 ? e : e - 1);
+    model_tsqr_body(pc, po, w, n, per_block, sc, Rb, cnt, blockIdx.x);
 }
 
 __global__ __launch_bounds__(kW) void k_model_solve(const double *__restrict__ Rb, const int *__restrict__ cnt, int nb,
                                                     ModelScalars sc, float *__restrict__ H, double *__restrict__ info,
                                                     int *__restrict__ status) {
-    __shared__ Lds L;
-    const int lane = threadIdx.x;
-    // fold the block factors, three per pass, in block order
-    double a[kC];
-#pragma unroll
-    for (int k = 0; k < kC; ++k) a[k] = 0.0;
-    for (int base = 0; base < nb; base += 3) {
-        const int r = lane - kC;
-        const int b = base + r / kC;
-        const bool live = r >= 0 && r < 3 * kC && b < nb;
-        if (lane >= kC) {
-#pragma unroll
-            for (int k = 0; k < kC; ++k) a[k] = live ? Rb[((size_t)b * kC + r % kC) * kC + k] : 0.0;
-        }
-        hh_panel(a, lane);
-    }
-    if (lane < kC) {
-#pragma unroll
-        for (int k = 0; k < kC; ++k) L.R[lane * kC + k] = a[k];
-    }
-    int count = 0;
-    if (lane == 0)
-        for (int b = 0; b < nb; ++b) count += cnt[b];
-    count = __shfl(count, 0);
-    __syncthreads();
-    // signs (diagonal >= 0), column norms, power-of-two equilibration
-    if (lane < kC && L.R[lane * kC + lane] < 0.0)
-        for (int k = 0; k < kC; ++k) L.R[lane * kC + k] = -L.R[lane * kC + k];
-    __syncthreads();
-    if (lane < kC) {
-        double s = 0.0;
-        for (int r = 0; r < kC; ++r) s += L.R[r * kC + lane] * L.R[r * kC + lane];
-        L.d[lane] = sqrt(s);
-    }
-    __syncthreads();
-    double dsc = 1.0;   // this lane's column scale
-    if (lane < kC) {
-        const int c = lane;
-        const int hj = c < 8 ? c : c == 8 ? -1 : c < 12 ? 3 * (c - 9) : 3 * (c - 12) + 1;
-        dsc = hj < 0 ? 1.0 / pow2_near(L.d[8]) : 1.0 / pow2_near(L.d[hj]);
-    }
-    __syncthreads();
-    if (lane < kC) {
-        for (int r = 0; r < kC; ++r) L.R[r * kC + lane] *= dsc;
-        L.d[lane] = dsc;   // s_j for j < 8, 1 / sigma at 8
-    }
-    __syncthreads();
-    const double sigma = 1.0 / L.d[8];
-    bool degenerate = count < 4;
-    for (int j = 0; j < 8; ++j) degenerate = degenerate || !(fabs(L.R[j * kC + j]) > kRankTol);
-    int word = degenerate ? APAP_STATUS_MODEL_DEGENERATE : 0;
-    double hq[8];   // h'' (equilibrated)
-    double objective = NAN, r_out = NAN, t_out = NAN, gap = 0.0;
-    int iters = 0;
-    if (!degenerate) {
-        // LMS: R[0:8, 0:8] h'' = -R[0:8, 8]
-        for (int i = 7; i >= 0; --i) {
-            double s = -L.R[i * kC + 8];
-            for (int k = i + 1; k < 8; ++k) s -= L.R[i * kC + k] * hq[k];
-            hq[i] = s / L.R[i * kC + i];
-        }
-        objective = sigma * sigma * (L.R[8 * kC + 8] * L.R[8 * kC + 8]);
-        if (sc.mode == APAP_MODEL_SDP) {
-            if (lane < 8) L.x[lane] = hq[lane];
-            __syncthreads();
-            double rel;
-            ipm(L, lane, sc.max_iter, rel, iters);
-            __syncthreads();   // the loop may leave right after lanes 0..9 wrote best_x / best_z
-            for (int k = 0; k < 8; ++k) hq[k] = L.best_x[k];
-            r_out = sigma * sigma * L.best_x[8];
-            t_out = sigma * sigma * L.best_x[9];
-            objective = r_out + t_out;
-            gap = rel;
-            if (!(rel <= kGapTol)) word |= APAP_STATUS_MODEL_NO_CONVERGENCE;
-        }
-    }
-    if (lane != 0) return;
-    double h[8];
-    for (int k = 0; k < 8; ++k) h[k] = degenerate ? NAN : sigma * L.d[k] * hq[k];
-    // model.py:50-56: float32 solution, [2, 2] = 1; with swap numpy.linalg.inv (fp64 LU, cast back) and / [2, 2] in float32
-    float sol[9];
-    for (int k = 0; k < 8; ++k) sol[k] = (float)h[k];
-    sol[8] = 1.0f;
-    if (sc.swap && !degenerate) {
-        double m[9], r[9];
-        for (int k = 0; k < 9; ++k) m[k] = (double)sol[k];
-        if (!apap::inv3(m, r)) word |= APAP_STATUS_SINGULAR;
-        float q[9];
-        for (int k = 0; k < 9; ++k) q[k] = (float)r[k];
-        const float d = q[8];
-        for (int k = 0; k < 9; ++k) sol[k] = q[k] / d;
-    }
-    for (int k = 0; k < 9; ++k) H[k] = degenerate ? NAN : sol[k];
-    info[APAP_MODEL_INFO_OBJECTIVE] = objective;
-    info[APAP_MODEL_INFO_R] = r_out;
-    info[APAP_MODEL_INFO_T] = t_out;
-    info[APAP_MODEL_INFO_GAP] = gap;
-    info[APAP_MODEL_INFO_ITERS] = (double)iters;
-    info[APAP_MODEL_INFO_STATUS] = (double)word;
-    info[APAP_MODEL_INFO_COUNT] = (double)count;
-    for (int k = 0; k < 9; ++k)
-        info[APAP_MODEL_INFO_Z + k] = (sc.mode == APAP_MODEL_SDP && !degenerate) ? L.best_z[k] : NAN;
-    for (int k = 0; k < 8; ++k) info[APAP_MODEL_INFO_H + k] = h[k];
-    if (word && status) atomicOr(status, word);
-}
-
-int model_check_params(const double *params, ModelScalars *sc, const char *who) {
-    if (!params) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null params", who);
-    const double mode = params[APAP_MODEL_MODE], swap = params[APAP_MODEL_SWAP], it = params[APAP_MODEL_MAX_ITER];
-    if (mode != APAP_MODEL_LMS && mode != APAP_MODEL_SDP) return apap::fail(APAP_ERR_INVALID_ARG, "%s: mode %g (0 = LMS, 1 = SDP)", who, mode);
-    if (swap != 0.0 && swap != 1.0) return apap::fail(APAP_ERR_INVALID_ARG, "%s: swap %g (0 or 1)", who, swap);
-    if (!(it >= 0.0 && it <= 10000.0)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: max_iter %g out of range", who, it);
-    const double du = params[APAP_MODEL_DU], dv = params[APAP_MODEL_DV], fl = params[APAP_MODEL_FLOOR];
-    if (!std::isfinite(du) || !std::isfinite(dv)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: du / dv not finite", who);
-    if (std::isnan(fl)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: weight floor is NaN", who);
-    sc->mode = (int)mode;
-    sc->swap = (int)swap;
-    sc->max_iter = it == 0.0 ? kDefaultIters : (int)it;
-    sc->use_floor = fl != -INFINITY;
-    sc->floor = fl;
-    sc->du = du;
-    sc->dv = dv;
-    sc->du32 = (float)du;   // np.float32([[self.du, 0]]) (model.py:85)
-    sc->dv32 = (float)dv;
-    return APAP_OK;
+    model_solve_body(Rb, cnt, nb, sc, H, info, status);
 }
 
 int model_check_device_args(int n, const void *d_pc, const void *d_po, const void *d_w, const void *d_H, const void *d_info,

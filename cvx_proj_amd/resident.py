@@ -261,3 +261,53 @@ def hip_spectral_em(src, dst, c_feats, o_feats, F, spec_params, model_params, em
         rm.data_ptr(), om.data_ptr(), sinfo.data_ptr(), None if status is None else status.data_ptr(), work.data_ptr(),
         work.numel(), _stream(dev)))
     return H, info, seg, rm, om, sinfo
+
+
+def em_batch_workspace_bytes(pair_lengths, pair_of):
+    """Scratch of ``hip_spectral_em_batch``: linear in the sum over the problems of their pair's matches."""
+    off = np.zeros(len(pair_lengths) + 1, np.int32)
+    off[1:] = np.cumsum(pair_lengths)
+    po = np.ascontiguousarray(pair_of, dtype=np.int32)
+    ip = ctypes.POINTER(ctypes.c_int)
+    return _native.lib().apap_spectral_em_batch_workspace_bytes(off.ctypes.data_as(ip), len(off) - 1, po.ctypes.data_as(ip), len(po))
+
+
+def hip_spectral_em_batch(src, dst, c_feats, o_feats, F, mask, pair_lengths, pair_of, spec_params, model_params, em_steps,
+                          status=None, ctx=None, work=None):
+    """``apap_spectral_em_batch_device`` on the current stream of the tensors' device: B EM problems in lockstep on resident
+    data, no host synchronisation (every restart cycle is enqueued).  src / dst (N, 2), c_feats / o_feats (N, 128), mask (N,)
+    float32: the pairs concatenated, pair p of ``pair_lengths[p]`` matches; F (P, 3, 3) float64; ``pair_of`` (B,), ``spec_params``
+    (B, 6), ``model_params`` (B, 6): host arrays.  Returns (H (B, k, 3, 3) float32, model info (B, k, 24), segment, ransac_mask,
+    original_mask: flat tensors, problem b's (k, n_b) block at k x (the matches of the problems before b), spectral info
+    (B, k, 6), status (B,) int32) as device tensors, not synchronised.  ``status`` (int32, B elements, zeroed by the caller)
+    is used when given; each word collects its own problem's bits.  Same bytes as ``_native.spectral_em_batch``."""
+    _needs_device(src, "hip_spectral_em_batch")
+    dev, k = src.device, int(em_steps)
+    off, po, sp, mp = _native.em_batch_tables(pair_lengths, pair_of, spec_params, model_params)
+    N, P, B = int(off[-1]), len(off) - 1, len(po)
+    for t, want in ((src, torch.float32), (dst, torch.float32), (c_feats, torch.float32), (o_feats, torch.float32),
+                    (F, torch.float64), (mask, torch.float32)):
+        if t.dtype != want or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"hip_spectral_em_batch: inputs must be contiguous {want} tensors on {dev}")
+    if src.shape != (N, 2) or dst.shape != src.shape or c_feats.shape != (N, _native.SPECTRAL_DIM) or o_feats.shape != c_feats.shape \
+            or F.shape != (P, 3, 3) or mask.shape != (N,):
+        raise ValueError(f"hip_spectral_em_batch: shapes ({N}, 2), ({N}, 2), ({N}, 128), ({N}, 128), ({P}, 3, 3), ({N},) expected")
+    if status is None:
+        status = torch.zeros(B, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.shape != (B,) or status.device != dev or not status.is_contiguous():
+        raise ValueError(f"hip_spectral_em_batch: status must be a contiguous int32 tensor of {B} elements on {dev}")
+    M = int(sum(int(off[p + 1] - off[p]) for p in po))
+    H = torch.empty((B, k, 3, 3), dtype=torch.float32, device=dev)
+    info = torch.empty((B, k, _native.MODEL_INFO), dtype=torch.float64, device=dev)
+    seg = torch.empty(k * M, dtype=torch.float64, device=dev)
+    rm = torch.empty(k * M, dtype=torch.float32, device=dev)
+    om = torch.empty(k * M, dtype=torch.float32, device=dev)
+    sinfo = torch.empty((B, k, _native.SPECTRAL_INFO), dtype=torch.float64, device=dev)
+    work = _scratch(work, em_batch_workspace_bytes([int(off[p + 1] - off[p]) for p in range(P)], po), dev)
+    dbl, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+    _native.check(_native.lib().apap_spectral_em_batch_device(
+        _native._h(ctx), src.data_ptr(), dst.data_ptr(), c_feats.data_ptr(), o_feats.data_ptr(), F.data_ptr(), mask.data_ptr(),
+        off.ctypes.data_as(ip), P, po.ctypes.data_as(ip), sp.ctypes.data_as(dbl), mp.ctypes.data_as(dbl), B, k, H.data_ptr(),
+        info.data_ptr(), seg.data_ptr(), rm.data_ptr(), om.data_ptr(), sinfo.data_ptr(), status.data_ptr(), work.data_ptr(),
+        work.numel(), _stream(dev)))
+    return H, info, seg, rm, om, sinfo, status

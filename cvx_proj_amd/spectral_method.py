@@ -29,7 +29,7 @@ import numpy as np
 from . import _native
 
 __all__ = ["calculate_M", "spectral_weights", "SpectralResult", "recompute_matching", "match_RANSAC", "cv_to_array",
-           "normalized_feature", "model_solve", "spectral_em", "EMRound", "EMResult", "skew_symmetric_transform", "fundamental",
+           "normalized_feature", "model_solve", "spectral_em", "spectral_em_batch", "spectral_em_grid", "EMRound", "EMResult", "skew_symmetric_transform", "fundamental",
            "get_fundamental"]
 
 
@@ -252,6 +252,102 @@ def spectral_em(src_pts, dst_pts, c_feats, o_feats, F, *, em_steps=2, lms=False,
     H_save = np.linalg.inv(H[-1]).astype(np.float64)
     H_save /= H_save[-1, -1]
     return EMResult(rounds, H_save)
+
+
+_EM_OPTIONS = {"lms": False, "fluc": 0.5, "huber_param": -1.0, "epi_weight": 0.5, "affinity_eps": 30.0, "aff_thresh": 0.5,
+               "em_radius": 6.0, "score_thresh": 0.4, "max_restarts": None}
+
+
+def spectral_em_batch(pairs, problems, *, em_steps=2, swap=True, device=-1, ctx=None):
+    """Many EM problems in one call, advancing in lockstep on the device (``apap_spectral_em_batch``): the number of kernel
+    launches does not grow with the number of problems.  ``pairs``: a sequence of ``(src, dst, c_feats, o_feats, F, mask)``
+    (``mask`` None: the GPU RANSAC of this repository, once per pair, as spectral_em); ``problems``: a sequence of
+    ``(pair_index, options)``, the options being spectral_em's keywords ``lms``, ``fluc``, ``huber_param``, ``epi_weight``,
+    ``affinity_eps``, ``aff_thresh``, ``em_radius``, ``score_thresh`` and ``max_restarts`` (equal across the batch).  Returns
+    one EMResult per problem, each equal byte for byte to spectral_em's for that problem alone.
+
+    Unlike spectral_em this does not raise for a problem's status (a degenerate selection, a singular solution):
+    ``EMRound.model.status`` carries the bits, H_pred is NaN for a degenerate round, and ``H_save`` is all NaN when the last
+    H_pred is not finite.  The restart cap and the interior-point cap are warned about once per call, with the count of
+    affected problems."""
+    from .model import result_of
+    pairs, problems = list(pairs), list(problems)
+    if not pairs or not problems:
+        raise ValueError("spectral_em_batch needs at least one pair and one problem")
+    arrays, H0 = [], []
+    for i, pair in enumerate(pairs):
+        if len(pair) != 6:
+            raise ValueError(f"pair {i}: expected (src, dst, c_feats, o_feats, F, mask_or_None)")
+        src, dst, c, o, F, n = _native._spectral_inputs(*pair[:5])
+        mask, h0 = pair[5], None
+        if mask is None:
+            a, b = (dst, src) if swap else (src, dst)
+            h0, m = _native.find_homography_ransac(a, b, 5.0, device=device, ctx=ctx)
+            mask = m
+        mask = np.ascontiguousarray(mask, dtype=np.float32).ravel()
+        if mask.shape != (n,):
+            raise ValueError(f"pair {i}: mask must hold {n} values; got {mask.shape}")
+        arrays.append((src, dst, c, o, F, mask))
+        H0.append(h0)
+    pair_of, sp, mp = [], [], []
+    for b, (idx, options) in enumerate(problems):
+        if not isinstance(idx, (int, np.integer)) or not 0 <= idx < len(pairs):
+            raise ValueError(f"problem {b}: pair_index {idx!r} outside 0 .. {len(pairs) - 1}")
+        unknown = set(options) - set(_EM_OPTIONS)
+        if unknown:
+            raise TypeError(f"problem {b}: unknown option(s) {sorted(unknown)}")
+        opt = {**_EM_OPTIONS, **options}
+        mp.append(_model_mode(opt["lms"], opt["fluc"], opt["huber_param"]))
+        sp.append(_native.spectral_params(opt["epi_weight"], opt["affinity_eps"], opt["aff_thresh"], opt["em_radius"],
+                                          opt["score_thresh"], 0 if opt["max_restarts"] is None else opt["max_restarts"]))
+        pair_of.append(int(idx))
+    cat = [np.concatenate([a[i] for a in arrays]) for i in (0, 1, 2, 3)]
+    H, info, seg, rm, om, sinfo, status = _native.spectral_em_batch(
+        cat[0], cat[1], cat[2], cat[3], np.stack([a[4] for a in arrays]), np.concatenate([a[5] for a in arrays]),
+        [len(a[0]) for a in arrays], pair_of, np.stack(sp), np.stack(mp), em_steps, device=device, ctx=ctx)
+    results, capped, ipm_capped = [], 0, 0
+    for b, idx in enumerate(pair_of):
+        rounds = []
+        for k in range(em_steps):
+            si = sinfo[b, k]
+            res = SpectralResult(seg[b][k], rm[b][k], om[b][k], H0[idx] if k == 0 else H[b, k - 1], float(si[0]), float(si[1]),
+                                 int(si[2]), int(si[4]), float(si[5]), not int(si[3]) & _native.STATUS_NO_CONVERGENCE)
+            rounds.append(EMRound(H[b, k], res, result_of(info[b, k])))
+        capped += bool(status[b] & _native.STATUS_NO_CONVERGENCE)
+        ipm_capped += bool(status[b] & _native.STATUS_MODEL_NO_CONVERGENCE)
+        if np.all(np.isfinite(H[b, -1])):
+            H_save = np.linalg.inv(H[b, -1]).astype(np.float64)
+            H_save /= H_save[-1, -1]
+        else:
+            H_save = np.full((3, 3), np.nan)
+        results.append(EMResult(rounds, H_save))
+    if capped:
+        warnings.warn(f"spectral_em_batch: the eigen-solver hit its restart cap in {capped} of {len(problems)} problems; the best "
+                      "Ritz vector is used there", RuntimeWarning, stacklevel=2)
+    if ipm_capped:
+        warnings.warn(f"spectral_em_batch: the interior-point method hit its iteration cap in {ipm_capped} of {len(problems)} "
+                      "problems; the best iterate is returned there", RuntimeWarning, stacklevel=2)
+    return results
+
+
+_GRID_ORDER = ("affinity_eps", "aff_thresh", "epi_weight", "fluc")   # grid_search.sh's loops, outermost first
+
+
+def spectral_em_grid(pair, grid, **fixed):
+    """The parameter grid of the reference's ``grid_search.sh`` on one pair, as one batch: ``grid`` maps option names to value
+    lists; ``fixed``: the other options, and spectral_em_batch's ``em_steps`` / ``swap`` / ``device`` / ``ctx``.  Returns
+    ``(list of option dicts, list of EMResult)`` in the script's nesting order: ``affinity_eps`` outermost, then
+    ``aff_thresh``, ``epi_weight``, ``fluc`` (any other grid key varies faster, in the mapping's order)."""
+    import itertools
+    call = {k: fixed.pop(k) for k in ("em_steps", "swap", "device", "ctx") if k in fixed}
+    names = [k for k in _GRID_ORDER if k in grid] + [k for k in grid if k not in _GRID_ORDER]
+    clash = set(names) & set(fixed)
+    if clash:
+        raise TypeError(f"option(s) {sorted(clash)} both in the grid and fixed")
+    options = [{**fixed, **dict(zip(names, values))} for values in itertools.product(*(list(grid[k]) for k in names))]
+    if not options:
+        raise ValueError("empty grid")
+    return options, spectral_em_batch([pair], [(0, o) for o in options], **call)
 
 
 # ------------------------------------------------------------------ utils.py:162-186

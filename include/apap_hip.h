@@ -574,6 +574,42 @@ int apap_spectral_em_device(apap_ctx *ctx, const float *d_src, const float *d_ds
                             float *d_original_mask, double *d_spec_info, int *d_status, void *d_work, size_t work_bytes,
                             void *stream);
 
+/* The EM loop for a BATCH of independent problems on one stream: a problem is a pair, a set of spectral options and a set
+ * of model options.  The problems advance in lockstep; the number of kernel launches does not depend on n_problems (a batch
+ * whose pairs fall into several rows-per-block classes of the matrix-vector product takes one such launch per class, at most
+ * 4).  Every output of every problem equals, byte for byte, what apap_spectral_em_device returns for that problem alone.
+ *   src, dst, c_feats, o_feats, mask_in   the pairs concatenated: pair p holds matches pair_offset[p] .. pair_offset[p + 1] - 1
+ *   F                 n_pairs x 9
+ *   pair_offset       HOST, n_pairs + 1 entries, strictly increasing
+ *   pair_of           HOST, n_problems entries: the pair of each problem (the problems of one pair read the same arrays)
+ *   spec_params       HOST, n_problems x APAP_SPECTRAL_PARAMS; APAP_SPECTRAL_MAX_RESTARTS must be equal across the batch (the
+ *                     cap fixes how many cycles are enqueued)
+ *   model_params      HOST, n_problems x APAP_MODEL_PARAMS (FLOOR and SWAP overridden as in apap_spectral_em_device); LMS and
+ *                     SDP problems may be mixed
+ * Outputs are problem-major and round-major inside a problem: H[(b em_steps + k) 9], info[(b em_steps + k) APAP_MODEL_INFO],
+ * spec_info[(b em_steps + k) APAP_SPECTRAL_INFO]; the per-match outputs of problem b start at em_steps x (the matches of the
+ * problems before b), round k at + k n.  status: n_problems words (may be NULL), each collecting its own problem's bits; the
+ * device form ORs into them (zero them first), the host-buffer form writes them.  A degenerate, singular or unconverged
+ * problem sets its own status word and info blocks only, and the call still returns APAP_OK: the batch entry points do not
+ * turn a per-problem status into an error code.  Bad arguments (null pointers, counts below 1, pair_of out of range, offsets
+ * not increasing, em_steps outside 1 .. 64, bad per-problem parameters, a short or misaligned workspace) are refused before
+ * any device is touched.
+ * The device form enqueues every restart cycle and does not wait; the host-buffer form waits after each cycle and stops
+ * enqueuing a round's cycles once every problem reports convergence.  Both give the same bytes.  d_work: at least
+ * apap_spectral_em_batch_workspace_bytes(...) bytes (0 for invalid arguments), 256-byte aligned. */
+size_t apap_spectral_em_batch_workspace_bytes(const int *pair_offset, int n_pairs, const int *pair_of, int n_problems);
+int apap_spectral_em_batch_device(apap_ctx *ctx, const float *d_src, const float *d_dst, const float *d_c_feats,
+                                  const float *d_o_feats, const double *d_F, const float *d_mask_in, const int *pair_offset,
+                                  int n_pairs, const int *pair_of, const double *spec_params, const double *model_params,
+                                  int n_problems, int em_steps, float *d_H, double *d_info, double *d_segment, float *d_ransac_mask,
+                                  float *d_original_mask, double *d_spec_info, int *d_status, void *d_work, size_t work_bytes,
+                                  void *stream);
+int apap_spectral_em_batch(apap_ctx *ctx, const float *src, const float *dst, const float *c_feats, const float *o_feats,
+                           const double *F, const float *mask_in, const int *pair_offset, int n_pairs, const int *pair_of,
+                           const double *spec_params, const double *model_params, int n_problems, int em_steps, float *H_out,
+                           double *info_out, double *segment_out, float *ransac_mask_out, float *original_mask_out,
+                           double *spec_info_out, int *status_out, int device);
+
 #ifdef __cplusplus
 }
 #endif

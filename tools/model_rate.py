@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the M-step (cvx_proj_amd.model: SDPSolver / LMSSolver, host-buffer form) and the EM loop (spectral_em) on the GPU.
 
-    python tools/model_rate.py [--sizes 500 2000 5000] [--reps 5] [--em-n 2000]
+    python tools/model_rate.py [--sizes 500 2000 5000] [--reps 5] [--em-n 2000] [--batch B [B ...]]
 
 One JSON line per (solver, n): seconds per call (host clock around the synchronous call, after one warm-up call), the
 interior-point iterations and the relative gap reached; then one line per form of a two-round SDP EM loop at --em-n matches:
@@ -10,6 +10,11 @@ resident resident.hip_spectral_em (enqueues every cycle, then one synchronise), 
 it replaces (spectral_weights -> model_solve, twice).  Per-kernel times (k_model_tsqr, k_model_solve) come from running this
 tool under `rocprofv3 --kernel-trace`; dispatches come in this order: per n four SDP then four LMS solves, then four calls of
 each EM form (two rounds each) and of the chain.
+With --batch (default off) the tool prints, instead of the lines above, one JSON line per B: a grid of B parameter sets
+(two-round SDP EM loops; fluc and epi_weight vary) on the --em-n synthetic pair, timed three ways in this process after one
+warm-up each - the batched host-buffer call (spectral_method.spectral_em_batch), the batched resident call
+(resident.hip_spectral_em_batch, one synchronise) and a loop of B spectral_em calls -, the ratio loop / batch of the medians,
+and whether every problem's final H equals the loop's bit for bit.
 Inputs: seeded synthetic matches (a homography, 1 px noise, 20 % outliers, uniform weights in [0.1, 1))."""
 import argparse
 import json
@@ -44,11 +49,58 @@ def timed(fn, reps):
     return out, times
 
 
+def grid_options(B):
+    """B distinct parameter sets: fluc varies fastest over 9 values, epi_weight over the rest."""
+    return [dict(fluc=0.4 + 0.1 * (b % 9), epi_weight=0.25 + 0.05 * (b // 9)) for b in range(B)]
+
+
+def batch_line(B, a, torch):
+    import warnings
+
+    from cvx_proj_amd import _native
+    from cvx_proj_amd.spectral_method import spectral_em, spectral_em_batch
+    src, dst, c, o, F, mask = spectral_synth(a.em_n)
+    pair = (src, dst, c, o, F, mask)
+    options = grid_options(B)
+    problems = [(0, opt) for opt in options]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        got, t_batch = timed(lambda: spectral_em_batch([pair], problems, em_steps=2), a.reps)
+        want, t_loop = timed(lambda: [spectral_em(src, dst, c, o, F, em_steps=2, mask=mask, **opt) for opt in options], a.reps)
+    same = [g.rounds[-1].H_pred.tobytes() == w.rounds[-1].H_pred.tobytes() for g, w in zip(got, want)]
+    line = {"em_batch": B, "em_steps": 2, "solver": "sdp", "n": a.em_n, "reps": a.reps,
+            "batch_seconds_median": float(np.median(t_batch)), "batch_seconds_min": float(min(t_batch)),
+            "loop_seconds_median": float(np.median(t_loop)), "loop_seconds_min": float(min(t_loop)),
+            "loop_over_batch": float(np.median(t_loop) / np.median(t_batch)), "same_final_H": int(sum(same)),
+            "every_final_H_equal": bool(all(same)), "ipm_iterations_max": max(r.model.iterations for g in got for r in g.rounds),
+            "restarts_max": max(r.spectral.restarts for g in got for r in g.rounds)}
+    if torch is not None and torch.cuda.is_available():
+        from cvx_proj_amd import resident
+        dev = torch.device("cuda", 0)
+        t = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (src, dst, c, o, F[None], mask)]
+        sp = np.stack([_native.spectral_params(epi_weight=opt["epi_weight"]) for opt in options])
+        mp = np.stack([_native.model_params(_native.MODEL_SDP, opt["fluc"], opt["fluc"]) for opt in options])
+        work = torch.empty(resident.em_batch_workspace_bytes([a.em_n], [0] * B), dtype=torch.uint8, device=dev)
+        status = torch.zeros(B, dtype=torch.int32, device=dev)
+
+        def run():
+            out = resident.hip_spectral_em_batch(*t, [a.em_n], [0] * B, sp, mp, 2, status=status, work=work)
+            torch.cuda.synchronize()
+            return out
+        out, t_res = timed(run, a.reps)
+        H = out[0].cpu().numpy()
+        line.update({"resident_seconds_median": float(np.median(t_res)), "resident_seconds_min": float(min(t_res)),
+                     "resident_final_H_equal": bool(all(H[b, -1].tobytes() == want[b].rounds[-1].H_pred.tobytes() for b in range(B)))})
+    print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[500, 2000, 5000])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--em-n", type=int, default=2000)
+    ap.add_argument("--batch", type=int, nargs="+", default=None, metavar="B",
+                    help="time a grid of B parameter sets as one batched call against a loop of B spectral_em calls")
     a = ap.parse_args()
     try:
         import torch        # before the library: one HIP runtime in the process (cvx_proj_amd/_native.py)
@@ -59,6 +111,10 @@ def main():
     from cvx_proj_amd.spectral_method import spectral_em
     if _native.lib().apap_device_count() < 1:
         raise SystemExit("model_rate: no HIP device (this tool measures the GPU; it has no CPU mode)")
+    if a.batch:
+        for B in a.batch:
+            batch_line(B, a, torch)
+        return
     for n in a.sizes:
         pc, po, w = synth(n)
         for name, solver in (("sdp", SDPSolver(8000, 0.5, 0.5)), ("lms", LMSSolver(8000))):
