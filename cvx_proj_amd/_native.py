@@ -174,6 +174,11 @@ SIGNATURES = {
                                                 C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "apap_spectral_em_batch": (C.c_int, [_vp, _f32p, _f32p, _f32p, _f32p, _f64p, _f32p, _i32p, C.c_int, _i32p, _f64p, _f64p,
                                          C.c_int, C.c_int, _f32p, _f64p, _f64p, _f32p, _f32p, _f64p, _i32p, C.c_int]),
+    "apap_local_model_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "apap_local_model_solve_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, _f64p, _vp, _vp,
+                                                _vp, _vp, C.c_size_t, _vp]),
+    "apap_local_model_solve": (C.c_int, [_vp, _f32p, _f32p, _f32p, C.c_int, _f64p, C.c_int, C.c_double, C.c_double, _f64p, _f32p,
+                                         _f64p, _i32p, C.c_int]),
 }
 
 _lib = None
@@ -753,3 +758,48 @@ def spectral_em_batch(src, dst, c_feats, o_feats, F, mask, pair_lengths, pair_of
                                        _ptr(seg, C.c_double), _ptr(rm, C.c_float), _ptr(om, C.c_float), _ptr(sinfo, C.c_double),
                                        _ptr(status, C.c_int), device))
     return (H, info, em_batch_split(seg, lengths, k), em_batch_split(rm, lengths, k), em_batch_split(om, lengths, k), sinfo, status)
+
+
+# ---------------------------------------------------------------- robust moving DLT: the M-step's solve per mesh cell
+LOCAL_MODEL_CHUNK = 4096            # APAP_LOCAL_MODEL_CHUNK: cells whose scratch apap_local_model_workspace_bytes asks for
+LOCAL_MODEL_MAX_CELLS = 1 << 24     # APAP_LOCAL_MODEL_MAX_CELLS
+
+
+def local_model_inputs(pts_c, pts_o, vertices, params, match_weights):
+    """The host arrays of the robust moving DLT's entry points, checked: (pts_c, pts_o (n, 2) float32, vertices (..., 2)
+    float64, params (6,) float64, match_weights (n,) float32 or None)."""
+    pc = np.ascontiguousarray(pts_c, dtype=np.float32)
+    po = np.ascontiguousarray(pts_o, dtype=np.float32)
+    if pc.ndim != 2 or pc.shape[1] != 2 or po.shape != pc.shape:
+        raise ValueError(f"pts_c / pts_o must both be (n, 2); got {pc.shape} and {po.shape}")
+    v = np.ascontiguousarray(vertices, dtype=np.float64)
+    if v.ndim < 1 or v.shape[-1] != 2:
+        raise ValueError(f"vertices must be (..., 2); got {v.shape}")
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    if params.shape != (MODEL_PARAMS,):
+        raise ValueError(f"params must hold {MODEL_PARAMS} values")
+    mw = None
+    if match_weights is not None:
+        mw = np.ascontiguousarray(match_weights, dtype=np.float32).ravel()
+        if mw.shape != (pc.shape[0],):
+            raise ValueError(f"match_weights must hold {pc.shape[0]} values; got {mw.shape}")
+    return pc, po, v, params, mw
+
+
+def local_model_solve(pts_c, pts_o, vertices, gamma, sigma, params, match_weights=None, device=-1, ctx=None):
+    """``apap_local_model_solve``: the M-step's solve (``params``: ``model_params``) for every sample point of ``vertices``
+    (..., 2) float64, with the weight vector ``float32(local_weights(pts_c, vertex, gamma, sigma)) * match_weights`` - never
+    stored.  Returns (H (..., 3, 3) float32, info (..., 24) float64, status (...,) int32); every cell equals ``model_solve``
+    on its own weight vector, byte for byte.  A degenerate, singular or unconverged cell does not raise: its bits are in
+    ``status`` and in its info block, its H is NaN when degenerate.  ``match_weights``: (n,) float32, typically the last round's
+    ``ransac_mask`` of ``spectral_em``."""
+    pc, po, v, params, mw = local_model_inputs(pts_c, pts_o, vertices, params, match_weights)
+    lead, cells = v.shape[:-1], v.size // 2
+    H = np.full(lead + (3, 3), np.nan, np.float32)
+    info = np.full(lead + (MODEL_INFO,), np.nan)
+    status = np.zeros(lead, np.int32)
+    if cells:
+        check(lib().apap_local_model_solve(_h(ctx), _ptr(pc, C.c_float), _ptr(po, C.c_float), _ptr(mw, C.c_float), len(pc),
+                                           _ptr(v, C.c_double), cells, float(gamma), float(sigma), _ptr(params, C.c_double),
+                                           _ptr(H, C.c_float), _ptr(info, C.c_double), _ptr(status, C.c_int), device))
+    return H, info, status

@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import os
 import sys
+import warnings
 
 import numpy as np
 
@@ -198,6 +199,35 @@ class APAP:
         if return_weights and not (isinstance(return_weights, str) and return_weights == "eager"):      # any truthy value but "eager"
             W = LazyWeights(src_point, vertices, self.gamma, self.sigma, device=self.device, ctx=self.ctx)
         return H, W
+
+    def local_robust_homography(self, src_point, dst_point, vertices, match_weights=None, *, lms=False, fluc=0.5, swap=False,
+                                floor=1e-3, max_iter=0, return_info=False):
+        """Robust moving DLT: what the comment above the SVD of the reference's cell loop asks for (apap.py:155-157) - every
+        cell's plain weighted DLT replaced by the spectral method's M-step (``model.py``'s exact SDP with ``du = dv = fluc``,
+        or its least squares with ``lms=True``), in one call for the whole mesh.
+
+        Cell k solves on the weight vector ``float32(W_k) * match_weights``, ``W_k`` this instance's moving-DLT weights
+        (``gamma``, ``sigma``) of ``src_point`` for the cell's vertex; matches whose weight is at or below ``floor`` are
+        dropped (``None`` keeps all).  ``match_weights`` (n,) is typically the last round's ``ransac_mask`` of
+        ``spectral_method.spectral_em``: the spectral method's verdict on each match, folded into every cell.  Keypoints are
+        taken as float32.
+
+        Returns the ``(mesh_h, mesh_w, 3, 3)`` float32 grid, which :meth:`local_warp` accepts as it stands: with ``swap=False``
+        (default) a cell's H maps ``src_point -> dst_point`` like :meth:`local_homography`; ``swap=True`` gives model.py's
+        inverted, normalised form.  With ``return_info=True``: ``(H, info (mesh_h, mesh_w, 24) float64, status (mesh_h,
+        mesh_w) int32)``.  A cell with fewer than 4 selected matches or a rank-deficient system keeps a NaN H, an SDP cell that
+        hit ``max_iter`` (0 = 80) its best iterate; a ``RuntimeWarning`` names how many there were."""
+        params = _native.model_params(_native.MODEL_LMS if lms else _native.MODEL_SDP, fluc, fluc, floor=floor, swap=swap,
+                                      max_iter=max_iter)
+        H, info, status = _native.local_model_solve(src_point, dst_point, vertices, self.gamma, self.sigma, params,
+                                                    match_weights=match_weights, device=self.device, ctx=self.ctx)
+        degenerate = int(np.count_nonzero(status & (_native.STATUS_MODEL_DEGENERATE | _native.STATUS_SINGULAR)))
+        unconverged = int(np.count_nonzero(status & _native.STATUS_MODEL_NO_CONVERGENCE))
+        if degenerate or unconverged:
+            warnings.warn(f"local_robust_homography: {degenerate} of {status.size} cells degenerate (fewer than 4 selected matches, "
+                          f"a rank-deficient system or a singular solution; H is NaN where degenerate), {unconverged} "
+                          "unconverged (the interior-point iteration cap; the best iterate is kept)", RuntimeWarning, stacklevel=2)
+        return (H, info, status) if return_info else H
 
     # ---- hot loop 2 ------------------------------------------------------------------
     def local_warp(self, ori_img, local_homography, mesh, progress=False):

@@ -1028,4 +1028,56 @@ int apap_spectral_em_batch(apap_ctx *ctx, const float *src, const float *dst, co
     return APAP_OK;   // a problem's status is its own: see status_out and the info blocks
 }
 
+// ------------------------------------------------------------------ robust moving DLT (apap_local_model.hip)
+int apap_local_model_solve(apap_ctx *ctx, const float *pts_c, const float *pts_o, const float *match_weights, int n,
+                           const double *vertices, int cells, double gamma, double sigma, const double *params, float *H_out,
+                           double *info_out, int *status_out, int device) {
+    const char *who = "apap_local_model_solve";
+    if (cells >= 1 && cells <= APAP_LOCAL_MODEL_MAX_CELLS) {   // an early return leaves no stale result behind
+        if (H_out) std::fill(H_out, H_out + (size_t)cells * 9, NAN);
+        if (info_out) std::fill(info_out, info_out + (size_t)cells * APAP_MODEL_INFO, NAN);
+        if (status_out) std::fill(status_out, status_out + cells, 0);
+    }
+    if (!pts_c || !pts_o || !vertices || !params || !H_out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc = apap::local_model_check(n, cells, gamma, sigma, params, who);
+    if (rc) return rc;
+    PoolLock pl(ctx);
+    int dev;
+    if ((rc = select_device(device, &dev))) return rc;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    const size_t B = (size_t)cells, pts = (size_t)n * 2 * sizeof(float);
+    const size_t o_pc = take(pts), o_po = take(pts), o_mw = take(match_weights ? (size_t)n * sizeof(float) : 0);
+    const size_t o_H = take(B * 9 * sizeof(float)), o_info = take(info_out ? B * APAP_MODEL_INFO * sizeof(double) : 0);
+    const size_t o_status = take(B * sizeof(int));
+    const size_t work_bytes = apap_local_model_workspace_bytes(n, cells);
+    void *d_io, *d_vert, *d_work;
+    if ((rc = slot_get(pl.pool, S_AUX, off, dev, &d_io))) return rc;
+    if ((rc = slot_get(pl.pool, S_VERT, B * 2 * sizeof(double), dev, &d_vert))) return rc;
+    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
+    char *d = (char *)d_io;
+    APAP_HIP_TRY(hipMemcpyAsync(d + o_pc, pts_c, pts, hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + o_po, pts_o, pts, hipMemcpyHostToDevice, nullptr));
+    if (match_weights) APAP_HIP_TRY(hipMemcpyAsync(d + o_mw, match_weights, (size_t)n * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d_vert, vertices, B * 2 * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemsetAsync(d + o_status, 0, B * sizeof(int), nullptr));
+    rc = apap_local_model_solve_device(ctx, (const float *)(d + o_pc), (const float *)(d + o_po),
+                                       match_weights ? (const float *)(d + o_mw) : nullptr, n, (const double *)d_vert, cells, gamma,
+                                       sigma, params, (float *)(d + o_H), info_out ? (double *)(d + o_info) : nullptr,
+                                       (int *)(d + o_status), d_work, work_bytes, nullptr);
+    if (rc) {
+        (void)hipStreamSynchronize(nullptr);
+        return rc;
+    }
+    APAP_HIP_TRY(hipMemcpyAsync(H_out, d + o_H, B * 9 * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    if (info_out) APAP_HIP_TRY(hipMemcpyAsync(info_out, d + o_info, B * APAP_MODEL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    if (status_out) APAP_HIP_TRY(hipMemcpyAsync(status_out, d + o_status, B * sizeof(int), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    return APAP_OK;   // a cell's status is its own: see status_out and the info blocks
+}
+
 }  // extern "C"

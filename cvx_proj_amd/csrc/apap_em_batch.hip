@@ -88,8 +88,8 @@ __global__ __launch_bounds__(kFinishThreads) void k_spec_finish_b(const EmProb *
 __global__ __launch_bounds__(kW) void k_model_tsqr_b(const EmProb *__restrict__ tab, int round) {
     const EmProb &d = tab[blockIdx.y];
     if (blockIdx.x >= (unsigned)d.nb) return;
-    model_tsqr_body((const float2 *)d.src, (const float2 *)d.dst, d.ransac + (size_t)round * d.n, d.n, d.per_block, d.msc, d.Rb, d.cnt,
-                    blockIdx.x);
+    model_tsqr_body((const float2 *)d.src, (const float2 *)d.dst, LoadWeight{d.ransac + (size_t)round * d.n}, d.n, d.per_block, d.msc,
+                    d.Rb, d.cnt, blockIdx.x);
 }
 
 // One wave per problem; its 55 KB of LDS let two problems share a CU.

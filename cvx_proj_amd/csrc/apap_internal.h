@@ -117,6 +117,8 @@ int spectral_em_batch_run(apap_ctx *ctx, const float *d_src, const float *d_dst,
 // The argument checks of the batch entry points that need no device pointer.
 int spectral_em_batch_check(const int *pair_offset, int n_pairs, const int *pair_of, const double *spec_params,
                             const double *model_params, int n_problems, int em_steps, const char *who);
+// The argument checks of the robust moving DLT's entry points (apap_local_model.hip) that need no device pointer.
+int local_model_check(int n, int cells, double gamma, double sigma, const double *params, const char *who);
 // Set-up and the dense M (n x n doubles) on `stream`.
 int spectral_affinity_run(const float *d_src, const float *d_dst, const float *d_c, const float *d_o, int n, const double *d_F,
                           const double *params, double *d_M, void *d_work, size_t work_bytes, void *stream);

@@ -29,7 +29,7 @@ inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int
 __global__ __launch_bounds__(kW) void k_model_tsqr(const float2 *__restrict__ pc, const float2 *__restrict__ po,
                                                    const float *__restrict__ w, int n, int per_block, ModelScalars sc,
                                                    double *__restrict__ Rb, int *__restrict__ cnt) {
-    model_tsqr_body(pc, po, w, n, per_block, sc, Rb, cnt, blockIdx.x);
+    model_tsqr_body(pc, po, LoadWeight{w}, n, per_block, sc, Rb, cnt, blockIdx.x);
 }
 
 __global__ __launch_bounds__(kW) void k_model_solve(const double *__restrict__ Rb, const int *__restrict__ cnt, int nb,

@@ -113,9 +113,17 @@ __device__ __forceinline__ void k_row(double (&a)[kC], float2 c, float2 o, float
 }
 
 // ---- M1 ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void model_tsqr_body(const float2 *__restrict__ pc, const float2 *__restrict__ po,
-                                                   const float *__restrict__ w, int n, int per_block, ModelScalars sc,
-                                                   double *__restrict__ Rb, int *__restrict__ cnt, unsigned bx) {
+// Where a match's float32 weight comes from: `weight(i, pc[i])`.  LoadWeight reads the caller's vector; apap_local_model.hip
+// computes a cell's moving-DLT weight on the fly.  The body's arithmetic and summation order do not depend on the source.
+struct LoadWeight {
+    const float *__restrict__ w;
+    __device__ __forceinline__ float operator()(int i, float2) const { return w[i]; }
+};
+
+template <class Weight>
+__device__ __forceinline__ void model_tsqr_body(const float2 *__restrict__ pc, const float2 *__restrict__ po, const Weight weight,
+                                                   int n, int per_block, ModelScalars sc, double *__restrict__ Rb,
+                                                   int *__restrict__ cnt, unsigned bx) {
     const int lane = threadIdx.x;
     const int begin = bx * per_block;
     const int end = min(n, begin + per_block);
@@ -128,9 +136,10 @@ __device__ __forceinline__ void model_tsqr_body(const float2 *__restrict__ pc, c
         const int i = base + (r >> 1);
         bool keep = false;
         if (r >= 0 && r < 2 * kPair && i < end) {
-            const float wi = w[i];
+            const float2 c = pc[i];
+            const float wi = weight(i, c);
             keep = !sc.use_floor || (double)wi > sc.floor;   // numpy 1.x: float32 scalar vs Python float in float64
-            if (keep) k_row(a, pc[i], po[i], wi, r & 1, sc);
+            if (keep) k_row(a, c, po[i], wi, r & 1, sc);
         }
         if (lane >= kC && !keep) {
 #pragma unroll

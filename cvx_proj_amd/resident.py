@@ -311,3 +311,50 @@ def hip_spectral_em_batch(src, dst, c_feats, o_feats, F, mask, pair_lengths, pai
         info.data_ptr(), seg.data_ptr(), rm.data_ptr(), om.data_ptr(), sinfo.data_ptr(), status.data_ptr(), work.data_ptr(),
         work.numel(), _stream(dev)))
     return H, info, seg, rm, om, sinfo, status
+
+
+def local_model_workspace_bytes(n, cells):
+    """Scratch of ``hip_local_model_solve``: that of ``min(cells, _native.LOCAL_MODEL_CHUNK)`` cells of ``n`` matches."""
+    return _native.lib().apap_local_model_workspace_bytes(n, cells)
+
+
+def hip_local_model_solve(pts_c, pts_o, vertices, gamma, sigma, params, match_weights=None, status=None, ctx=None, work=None):
+    """``apap_local_model_solve_device`` on the current stream of the tensors' device: the robust moving DLT on resident
+    data.  pts_c / pts_o (n, 2) float32, vertices (..., 2) float64, match_weights (n,) float32 or None: contiguous device
+    tensors; ``params`` (6,): a host array (``_native.model_params``).  Returns (H (..., 3, 3) float32, info (..., 24) float64,
+    status (...,) int32) as device tensors, not synchronised.  ``status`` (int32, one element per cell, zeroed by the
+    caller) is used when given; each word collects its own cell's bits.  ``work`` (uint8) is used AS GIVEN: the cells are
+    processed in chunks of as many as it holds (at least one cell's scratch, ``local_model_workspace_bytes(n, 1)``); default
+    ``local_model_workspace_bytes(n, cells)``.  Same bytes as ``_native.local_model_solve`` whatever the chunking."""
+    _needs_device(pts_c, "hip_local_model_solve")
+    dev = pts_c.device
+    params = np.ascontiguousarray(params, dtype=np.float64)
+    if params.shape != (_native.MODEL_PARAMS,):
+        raise ValueError(f"hip_local_model_solve: params must hold {_native.MODEL_PARAMS} values")
+    tensors = [(pts_c, torch.float32), (pts_o, torch.float32), (vertices, torch.float64)]
+    if match_weights is not None:
+        tensors.append((match_weights, torch.float32))
+    for t, want in tensors:
+        if t.dtype != want or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"hip_local_model_solve: inputs must be contiguous {want} tensors on {dev}")
+    n = pts_c.shape[0]
+    if pts_c.shape != (n, 2) or pts_o.shape != pts_c.shape or vertices.dim() < 1 or vertices.shape[-1] != 2 \
+            or (match_weights is not None and match_weights.shape != (n,)):
+        raise ValueError(f"hip_local_model_solve: shapes ({n}, 2), ({n}, 2), (..., 2) and ({n},) expected")
+    lead = tuple(vertices.shape[:-1])
+    cells = vertices.numel() // 2
+    if status is None:
+        status = torch.zeros(lead, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.numel() != cells or status.device != dev or not status.is_contiguous():
+        raise ValueError(f"hip_local_model_solve: status must be a contiguous int32 tensor of {cells} elements on {dev}")
+    H = torch.empty(lead + (3, 3), dtype=torch.float32, device=dev)
+    info = torch.empty(lead + (_native.MODEL_INFO,), dtype=torch.float64, device=dev)
+    if cells == 0:
+        return H, info, status
+    if work is None:
+        work = torch.empty(local_model_workspace_bytes(n, cells), dtype=torch.uint8, device=dev)
+    _native.check(_native.lib().apap_local_model_solve_device(
+        _native._h(ctx), pts_c.data_ptr(), pts_o.data_ptr(), None if match_weights is None else match_weights.data_ptr(), n,
+        vertices.data_ptr(), cells, float(gamma), float(sigma), params.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), H.data_ptr(),
+        info.data_ptr(), status.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
+    return H, info, status

@@ -610,6 +610,44 @@ int apap_spectral_em_batch(apap_ctx *ctx, const float *src, const float *dst, co
                            double *info_out, double *segment_out, float *ransac_mask_out, float *original_mask_out,
                            double *spec_info_out, int *status_out, int device);
 
+/* ------------------------------------------------- robust moving DLT: the M-step's solve per mesh cell --- */
+/* What the comment above the SVD of the reference's cell loop asks for (apap.py:155-157): every cell's plain weighted DLT
+ * replaced by the M-step's robust solve (LMS or SDP, above), the cell's moving-DLT weights folded into the match weights.
+ * For cell k with vertex v_k:
+ *     W_k[i] = max(exp(-|v_k - pts_c[i]| / sigma^2), gamma)          float64: the weight of apap_local_weights_pts
+ *     w_k[i] = float32(W_k[i]) * match_weights[i]                    one float32 multiply; float32(W_k[i]) without match_weights
+ * and cell k's H (9 float32), info (APAP_MODEL_INFO doubles) and status word equal, byte for byte, what
+ * apap_model_solve_device(pts_c, pts_o, w_k, n, params) gives for that cell alone, whatever other cells are in the call.
+ * The cells x n weights are never stored.
+ *   pts_c, pts_o     n x 2 float32; distances are measured to pts_c.  With APAP_MODEL_SWAP 0 a cell's H maps pts_c -> pts_o
+ *                    (the direction of apap_local_homography's src -> dst)
+ *   match_weights    n float32, may be NULL (none): typically the last round's ransac_mask of apap_spectral_em
+ *   vertices         cells x 2 float64 (get_vertice)
+ *   params           HOST, APAP_MODEL_PARAMS doubles; MODE, DU, DV, FLOOR, SWAP and MAX_ITER are honoured as given
+ *   H                cells x 9 float32;  info (may be NULL) cells x APAP_MODEL_INFO doubles
+ *   status           cells words (may be NULL): each collects its own cell's bits.  The device form ORs into them (zero them
+ *                    first), the host-buffer form writes them
+ * A degenerate (fewer than 4 selected matches, or rank-deficient), singular or unconverged cell sets only its own status
+ * word, its NaN H and its info block; the call still returns APAP_OK.
+ * Refused before any device is touched: null pointers, n outside 1 .. 2^26, cells outside 1 .. APAP_LOCAL_MODEL_MAX_CELLS, a bad
+ * mode / swap / max_iter, du or dv negative or not finite, sigma not a finite number > 0, a NaN gamma, a short
+ * (APAP_ERR_WORKSPACE) or misaligned workspace.
+ * Workspace: one cell's scratch is O(n / 240) 15 x 15 factors (16.5 KB at n = 2000).  apap_local_model_workspace_bytes
+ * returns the scratch of min(cells, APAP_LOCAL_MODEL_CHUNK) cells (0 for invalid arguments; a 256-byte multiple).  The
+ * device form processes the cells in chunks of as many cells as the workspace it is GIVEN holds (at least one cell's scratch,
+ * else APAP_ERR_WORKSPACE; at most 65535 per chunk): two kernel launches per chunk, whatever the number of cells in it.
+ * Under APAP_OPT_PROFILE the reductions are counted in the APAP_PROF_ASSEMBLE slot and the solves in APAP_PROF_EIGEN.
+ * The host-buffer form sets H_out (and info_out) to NaN and status_out to 0 before anything else. */
+#define APAP_LOCAL_MODEL_CHUNK 4096
+#define APAP_LOCAL_MODEL_MAX_CELLS (1 << 24)
+size_t apap_local_model_workspace_bytes(int n, int cells);
+int apap_local_model_solve_device(apap_ctx *ctx, const float *d_pts_c, const float *d_pts_o, const float *d_match_weights, int n,
+                                  const double *d_vertices, int cells, double gamma, double sigma, const double *params,
+                                  float *d_H, double *d_info, int *d_status, void *d_work, size_t work_bytes, void *stream);
+int apap_local_model_solve(apap_ctx *ctx, const float *pts_c, const float *pts_o, const float *match_weights, int n,
+                           const double *vertices, int cells, double gamma, double sigma, const double *params, float *H_out,
+                           double *info_out, int *status_out, int device);
+
 #ifdef __cplusplus
 }
 #endif
