@@ -179,6 +179,13 @@ SIGNATURES = {
                                                 _vp, _vp, C.c_size_t, _vp]),
     "apap_local_model_solve": (C.c_int, [_vp, _f32p, _f32p, _f32p, C.c_int, _f64p, C.c_int, C.c_double, C.c_double, _f64p, _f32p,
                                          _f64p, _i32p, C.c_int]),
+    "apap_match_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "apap_match_descriptors": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, _i32p, _f32p, _i32p, _f32p, C.c_int]),
+    "apap_match_descriptors_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "apap_match_batch_workspace_bytes": (C.c_size_t, [_i32p, _i32p, C.c_int]),
+    "apap_match_descriptors_batch": (C.c_int, [_vp, _f32p, _f32p, _i32p, _i32p, C.c_int, _i32p, _f32p, _i32p, _f32p, C.c_int]),
+    "apap_match_descriptors_batch_device": (C.c_int, [_vp, _vp, _vp, _i32p, _i32p, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                                                      _vp]),
 }
 
 _lib = None
@@ -803,3 +810,78 @@ def local_model_solve(pts_c, pts_o, vertices, gamma, sigma, params, match_weight
                                            _ptr(v, C.c_double), cells, float(gamma), float(sigma), _ptr(params, C.c_double),
                                            _ptr(H, C.c_float), _ptr(info, C.c_double), _ptr(status, C.c_int), device))
     return H, info, status
+
+
+# ---------------------------------------------------------------- descriptor matching: exact nearest and second-nearest
+MATCH_DIM = 128                 # APAP_MATCH_DIM
+MATCH_QUERY_TILE = 64           # APAP_MATCH_QUERY_TILE: queries per block
+MATCH_TRAIN_CHUNK = 128         # APAP_MATCH_TRAIN_CHUNK: train rows per staged chunk
+MATCH_WANT_BLOCKS = 4096        # APAP_MATCH_WANT_BLOCKS: the train axis is split until a pair has about this many blocks
+MATCH_MAX_ROWS = 1 << 24        # queries / train rows of one pair
+MATCH_MAX_PAIRS = 65535
+
+
+def match_splits(nq, nt):
+    """Into how many splits the train axis of an (nq, nt) pair is cut, and of how many chunks each (the last may be shorter):
+    the rule of include/apap_hip.h.  No output depends on it; tests use it to place shapes at its edges."""
+    q_tiles = -(-int(nq) // MATCH_QUERY_TILE)
+    chunks = -(-int(nt) // MATCH_TRAIN_CHUNK)
+    per = -(-chunks // min(chunks, -(-MATCH_WANT_BLOCKS // q_tiles)))
+    return -(-chunks // per), per
+
+
+def as_descriptors(a, name="descriptors"):
+    """(n, 128) descriptors as a contiguous float32 array: uint8 (or any integer or float dtype) is converted."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != MATCH_DIM:
+        raise ValueError(f"{name} must be (n, {MATCH_DIM}); got {a.shape}")
+    return a
+
+
+def match_offsets(lengths, name):
+    """Row counts of the pairs -> int32 offsets (len + 1), checked as the library checks them."""
+    lengths = [int(x) for x in lengths]
+    if not 1 <= len(lengths) <= MATCH_MAX_PAIRS:
+        raise ValueError(f"{name}: {len(lengths)} pairs (1 .. {MATCH_MAX_PAIRS})")
+    if any(not 1 <= x <= MATCH_MAX_ROWS for x in lengths):
+        raise ValueError(f"{name}: a pair holds 1 .. 2^24 rows; got {lengths}")
+    if sum(lengths) > np.iinfo(np.int32).max:
+        raise ValueError(f"{name}: {sum(lengths)} rows in all exceed the int32 offsets")
+    off = np.zeros(len(lengths) + 1, np.int32)
+    off[1:] = np.cumsum(lengths)
+    return off
+
+
+def match_descriptors(q, t, second=True, device=-1, ctx=None):
+    """``apap_match_descriptors``: for every row of ``q`` (nq, 128) the nearest row of ``t`` (nt, 128) under the L2 distance,
+    exactly (float32 sum of squared differences; exact for integer descriptors in 0 .. 255), and with ``second`` the
+    runner-up.  uint8 or float descriptors are taken as float32.  Returns (idx (nq,) int32, dist (nq,) float32, idx2, dist2)
+    - the last two ``None`` without ``second``.  Ties go to the lowest index; a NaN distance is never selected; where nothing
+    can be selected (the runner-up of a single train row) the index is -1 and the distance +inf."""
+    q, t = as_descriptors(q, "q"), as_descriptors(t, "t")
+    if not 1 <= len(q) <= MATCH_MAX_ROWS or not 1 <= len(t) <= MATCH_MAX_ROWS:
+        raise ValueError(f"match_descriptors: {len(q)} queries, {len(t)} train rows (1 .. 2^24 each)")
+    idx, dist = np.empty(len(q), np.int32), np.empty(len(q), np.float32)
+    idx2, dist2 = (np.empty(len(q), np.int32), np.empty(len(q), np.float32)) if second else (None, None)
+    check(lib().apap_match_descriptors(_h(ctx), _ptr(q, C.c_float), len(q), _ptr(t, C.c_float), len(t), _ptr(idx, C.c_int),
+                                       _ptr(dist, C.c_float), _ptr(idx2, C.c_int), _ptr(dist2, C.c_float), device))
+    return idx, dist, idx2, dist2
+
+
+def match_descriptors_batch(q, t, q_lengths, t_lengths, second=True, device=-1, ctx=None):
+    """``apap_match_descriptors_batch``: many pairs in one call (two kernel launches, whatever their number).  ``q`` / ``t``:
+    the pairs' descriptors concatenated, pair p of ``q_lengths[p]`` queries and ``t_lengths[p]`` train rows.  Returns the four
+    arrays of ``match_descriptors`` laid out like ``q``; a pair's indices count from its own first train row, and its outputs
+    equal its own single call's byte for byte."""
+    q, t = as_descriptors(q, "q"), as_descriptors(t, "t")
+    if len(q_lengths) != len(t_lengths):
+        raise ValueError(f"match_descriptors_batch: {len(q_lengths)} query counts, {len(t_lengths)} train counts")
+    qo, to = match_offsets(q_lengths, "q_lengths"), match_offsets(t_lengths, "t_lengths")
+    if qo[-1] != len(q) or to[-1] != len(t):
+        raise ValueError(f"match_descriptors_batch: the counts sum to {qo[-1]} and {to[-1]} rows; got {len(q)} and {len(t)}")
+    idx, dist = np.empty(len(q), np.int32), np.empty(len(q), np.float32)
+    idx2, dist2 = (np.empty(len(q), np.int32), np.empty(len(q), np.float32)) if second else (None, None)
+    check(lib().apap_match_descriptors_batch(_h(ctx), _ptr(q, C.c_float), _ptr(t, C.c_float), _ptr(qo, C.c_int), _ptr(to, C.c_int),
+                                             len(qo) - 1, _ptr(idx, C.c_int), _ptr(dist, C.c_float), _ptr(idx2, C.c_int),
+                                             _ptr(dist2, C.c_float), device))
+    return idx, dist, idx2, dist2

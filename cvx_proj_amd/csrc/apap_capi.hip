@@ -1080,4 +1080,58 @@ int apap_local_model_solve(apap_ctx *ctx, const float *pts_c, const float *pts_o
     return APAP_OK;   // a cell's status is its own: see status_out and the info blocks
 }
 
+// ------------------------------------------------------------------ descriptor matching (apap_match.hip)
+int apap_match_descriptors_batch(apap_ctx *ctx, const float *q, const float *t, const int *q_offset, const int *t_offset,
+                                 int n_pairs, int *idx, float *dist, int *idx2, float *dist2, int device) {
+    const char *who = "apap_match_descriptors_batch";
+    if (!q || !t || !q_offset || !t_offset || !idx || !dist) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc = apap::match_check(q_offset, t_offset, n_pairs, who);
+    if (rc) return rc;
+    PoolLock pl(ctx);
+    int dev;
+    if ((rc = select_device(device, &dev))) return rc;
+    const size_t q0 = (size_t)q_offset[0], t0 = (size_t)t_offset[0];   // the device arrays start at the first pair
+    const size_t NQ = (size_t)q_offset[n_pairs] - q0, NT = (size_t)t_offset[n_pairs] - t0;
+    std::vector<int> qrel((size_t)n_pairs + 1), trel((size_t)n_pairs + 1);
+    for (int p = 0; p <= n_pairs; ++p) {
+        qrel[p] = q_offset[p] - q_offset[0];
+        trel[p] = t_offset[p] - t_offset[0];
+    }
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    const size_t row = APAP_MATCH_DIM * sizeof(float);
+    const size_t o_q = take(NQ * row), o_t = take(NT * row), o_idx = take(NQ * sizeof(int)), o_dist = take(NQ * sizeof(float));
+    const size_t o_idx2 = take(idx2 ? NQ * sizeof(int) : 0), o_dist2 = take(dist2 ? NQ * sizeof(float) : 0);
+    const size_t work_bytes = apap_match_batch_workspace_bytes(qrel.data(), trel.data(), n_pairs);
+    void *d_io, *d_work;
+    if ((rc = slot_get(pl.pool, S_AUX, off, dev, &d_io))) return rc;
+    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
+    char *d = (char *)d_io;
+    APAP_HIP_TRY(hipMemcpyAsync(d + o_q, q + q0 * APAP_MATCH_DIM, NQ * row, hipMemcpyHostToDevice, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(d + o_t, t + t0 * APAP_MATCH_DIM, NT * row, hipMemcpyHostToDevice, nullptr));
+    rc = apap_match_descriptors_batch_device(ctx, (const float *)(d + o_q), (const float *)(d + o_t), qrel.data(), trel.data(),
+                                             n_pairs, (int *)(d + o_idx), (float *)(d + o_dist), idx2 ? (int *)(d + o_idx2) : nullptr,
+                                             dist2 ? (float *)(d + o_dist2) : nullptr, d_work, work_bytes, nullptr);
+    if (rc) {
+        (void)hipStreamSynchronize(nullptr);
+        return rc;
+    }
+    APAP_HIP_TRY(hipMemcpyAsync(idx + q0, d + o_idx, NQ * sizeof(int), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(dist + q0, d + o_dist, NQ * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    if (idx2) APAP_HIP_TRY(hipMemcpyAsync(idx2 + q0, d + o_idx2, NQ * sizeof(int), hipMemcpyDeviceToHost, nullptr));
+    if (dist2) APAP_HIP_TRY(hipMemcpyAsync(dist2 + q0, d + o_dist2, NQ * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    return APAP_OK;
+}
+
+int apap_match_descriptors(apap_ctx *ctx, const float *q, int nq, const float *t, int nt, int *idx, float *dist, int *idx2,
+                           float *dist2, int device) {
+    const int qo[2] = {0, nq}, to[2] = {0, nt};
+    return apap_match_descriptors_batch(ctx, q, t, qo, to, 1, idx, dist, idx2, dist2, device);
+}
+
 }  // extern "C"

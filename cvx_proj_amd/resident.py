@@ -358,3 +358,53 @@ def hip_local_model_solve(pts_c, pts_o, vertices, gamma, sigma, params, match_we
         vertices.data_ptr(), cells, float(gamma), float(sigma), params.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), H.data_ptr(),
         info.data_ptr(), status.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
     return H, info, status
+
+
+def match_workspace_bytes(q_lengths, t_lengths=None):
+    """Scratch of ``hip_match_descriptors(q, t)`` as ``match_workspace_bytes(nq, nt)``, or of ``hip_match_descriptors_batch``
+    as ``match_workspace_bytes(q_lengths, t_lengths)`` with the pairs' row counts: 16 bytes per query and split of its pair's
+    train axis.  0 for invalid arguments."""
+    if np.ndim(q_lengths) == 0:
+        return _native.lib().apap_match_workspace_bytes(int(q_lengths), int(t_lengths))
+    qo, to = _native.match_offsets(q_lengths, "q_lengths"), _native.match_offsets(t_lengths, "t_lengths")
+    ip = ctypes.POINTER(ctypes.c_int)
+    return _native.lib().apap_match_batch_workspace_bytes(qo.ctypes.data_as(ip), to.ctypes.data_as(ip), min(len(qo), len(to)) - 1)
+
+
+def hip_match_descriptors_batch(q, t, q_lengths, t_lengths, second=True, ctx=None, work=None):
+    """``apap_match_descriptors_batch_device`` on the current stream of the tensors' device, no host synchronisation: many
+    pairs in two kernel launches.  q / t: contiguous float32 (N, 128) device tensors, the pairs concatenated, pair p of
+    ``q_lengths[p]`` queries and ``t_lengths[p]`` train rows (host lists).  Returns (idx int32, dist float32, idx2, dist2) laid
+    out like ``q`` (the last two ``None`` without ``second``), not synchronised; a pair's indices count from its own first
+    train row.  ``work`` (uint8) is used when it holds ``match_workspace_bytes(q_lengths, t_lengths)``.  Same bytes as
+    ``_native.match_descriptors_batch``, and per pair as ``hip_match_descriptors``.  What follows - gathering keypoints and
+    descriptors by ``idx`` into ``hip_spectral_em``'s inputs - is plain tensor indexing and stays with the caller."""
+    _needs_device(q, "hip_match_descriptors_batch")
+    dev = q.device
+    for x in (q, t):
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.device != dev or x.dim() != 2 or x.shape[1] != _native.MATCH_DIM:
+            raise ValueError(f"hip_match_descriptors_batch: descriptors must be contiguous float32 (n, {_native.MATCH_DIM}) tensors on {dev}")
+    if len(q_lengths) != len(t_lengths):
+        raise ValueError(f"hip_match_descriptors_batch: {len(q_lengths)} query counts, {len(t_lengths)} train counts")
+    qo, to = _native.match_offsets(q_lengths, "q_lengths"), _native.match_offsets(t_lengths, "t_lengths")
+    if qo[-1] != q.shape[0] or to[-1] != t.shape[0]:
+        raise ValueError(f"hip_match_descriptors_batch: the counts sum to {qo[-1]} and {to[-1]} rows; got {q.shape[0]} and {t.shape[0]}")
+    n = q.shape[0]
+    idx = torch.empty(n, dtype=torch.int32, device=dev)
+    dist = torch.empty(n, dtype=torch.float32, device=dev)
+    idx2 = torch.empty(n, dtype=torch.int32, device=dev) if second else None
+    dist2 = torch.empty(n, dtype=torch.float32, device=dev) if second else None
+    ip = ctypes.POINTER(ctypes.c_int)
+    work = _scratch(work, _native.lib().apap_match_batch_workspace_bytes(qo.ctypes.data_as(ip), to.ctypes.data_as(ip), len(qo) - 1), dev)
+    _native.check(_native.lib().apap_match_descriptors_batch_device(
+        _native._h(ctx), q.data_ptr(), t.data_ptr(), qo.ctypes.data_as(ip), to.ctypes.data_as(ip), len(qo) - 1, idx.data_ptr(),
+        dist.data_ptr(), None if idx2 is None else idx2.data_ptr(), None if dist2 is None else dist2.data_ptr(), work.data_ptr(),
+        work.numel(), _stream(dev)))
+    return idx, dist, idx2, dist2
+
+
+def hip_match_descriptors(q, t, second=True, ctx=None, work=None):
+    """``apap_match_descriptors_device``: the nearest and (with ``second``) second-nearest row of ``t`` (nt, 128) for every
+    row of ``q`` (nq, 128), exact L2; the batch of one pair (see ``hip_match_descriptors_batch``)."""
+    _needs_device(q, "hip_match_descriptors")
+    return hip_match_descriptors_batch(q, t, [q.shape[0]], [t.shape[0]], second=second, ctx=ctx, work=work)

@@ -648,6 +648,47 @@ int apap_local_model_solve(apap_ctx *ctx, const float *pts_c, const float *pts_o
                            const double *vertices, int cells, double gamma, double sigma, const double *params, float *H_out,
                            double *info_out, int *status_out, int device);
 
+/* ------------------------------------------------- descriptor matching: exact nearest and second-nearest, L2 --- */
+/* The exact answer that coarse_matching's cv.FlannBasedMatcher().match(feats_cp, feats_op) approximates (utils.py:142-151):
+ * for every query row i of q (nq x APAP_MATCH_DIM float32) the train row of t (nt x APAP_MATCH_DIM float32) at the smallest
+ *     d2(i, j) = sum_k (q[i, k] - t[j, k])^2      float32, difference form: a subtraction and an fmaf per term, k ascending
+ * and the runner-up.  For integer-valued descriptors in 0 .. 255 (OpenCV's SIFT) d2 <= 8 323 200 < 2^24 is exact.
+ *   idx     nq int32: the j of the smallest d2(i, j); among equal d2 the lowest j
+ *   dist    nq float32: the correctly rounded float32 square root of that float32 d2 (DMatch.distance)
+ *   idx2, dist2   the same over j != idx[i]; both may be NULL (nearest only)
+ * A d2 that is NaN or infinite is never selected.  Where no train row can be selected (and for the runner-up when nt = 1)
+ * the index is -1 and the distance +inf.  The outputs are a function of (q, t) alone: no floating-point atomics, the same
+ * bytes from every entry point below, whatever the launch geometry and whatever else is in a batch.
+ * Batch: the pairs are concatenated; pair p holds the query rows q_offset[p] .. q_offset[p + 1] - 1 and the train rows
+ * t_offset[p] .. t_offset[p + 1] - 1 (both HOST arrays of n_pairs + 1 strictly increasing entries; the device arrays are
+ * indexed by them as given, the host-buffer form reads and writes from q_offset[0] / t_offset[0] on).  The outputs are laid
+ * out like the queries; a pair's indices count from its own first train row.  Two kernel launches, whatever n_pairs; every
+ * pair's outputs equal, byte for byte, its own single call's (the single call is the batch of one).
+ * Refused before any device is touched: null required pointers, nq or nt (per pair) outside 1 .. 2^24, n_pairs outside
+ * 1 .. 65535, negative or not strictly increasing offsets, a short (APAP_ERR_WORKSPACE) or misaligned workspace (256 bytes;
+ * q and t 16 bytes).  Without a GPU the host-buffer forms return APAP_ERR_NO_DEVICE: there is no CPU fallback.
+ * The _device forms only enqueue on `stream` (an upload of n_pairs small descriptors and two kernels) and do not wait.
+ * d_work: at least apap_match_workspace_bytes(nq, nt) / apap_match_batch_workspace_bytes(...) bytes (0 for invalid arguments;
+ * a 256-byte multiple): one 16-byte partial per query and split of the train axis.
+ * The tiling (for tests and sizing; no output depends on it): a block takes APAP_MATCH_QUERY_TILE queries, the train rows go
+ * in chunks of APAP_MATCH_TRAIN_CHUNK, and the chunks are dealt to min(chunks, ceil(APAP_MATCH_WANT_BLOCKS / query tiles))
+ * splits of equal length (the last may be shorter). */
+#define APAP_MATCH_DIM 128            /* = APAP_SPECTRAL_DIM */
+#define APAP_MATCH_QUERY_TILE 64
+#define APAP_MATCH_TRAIN_CHUNK 128
+#define APAP_MATCH_WANT_BLOCKS 4096
+size_t apap_match_workspace_bytes(int nq, int nt);
+int apap_match_descriptors(apap_ctx *ctx, const float *q, int nq, const float *t, int nt, int *idx, float *dist, int *idx2,
+                           float *dist2, int device);
+int apap_match_descriptors_device(apap_ctx *ctx, const float *d_q, int nq, const float *d_t, int nt, int *d_idx, float *d_dist,
+                                  int *d_idx2, float *d_dist2, void *d_work, size_t work_bytes, void *stream);
+size_t apap_match_batch_workspace_bytes(const int *q_offset, const int *t_offset, int n_pairs);
+int apap_match_descriptors_batch(apap_ctx *ctx, const float *q, const float *t, const int *q_offset, const int *t_offset,
+                                 int n_pairs, int *idx, float *dist, int *idx2, float *dist2, int device);
+int apap_match_descriptors_batch_device(apap_ctx *ctx, const float *d_q, const float *d_t, const int *q_offset,
+                                        const int *t_offset, int n_pairs, int *d_idx, float *d_dist, int *d_idx2, float *d_dist2,
+                                        void *d_work, size_t work_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
