@@ -186,6 +186,14 @@ SIGNATURES = {
     "apap_match_descriptors_batch": (C.c_int, [_vp, _f32p, _f32p, _i32p, _i32p, C.c_int, _i32p, _f32p, _i32p, _f32p, C.c_int]),
     "apap_match_descriptors_batch_device": (C.c_int, [_vp, _vp, _vp, _i32p, _i32p, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
                                                       _vp]),
+    "apap_sift_window": (C.c_int, [_f32p]),
+    "apap_sift_taps": (C.c_int, [_f32p]),
+    "apap_sift_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "apap_sift_describe": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, _f32p, C.c_int]),
+    "apap_sift_describe_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "apap_sift_describe_batch": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, _f32p, _i32p, _f32p, C.c_int]),
+    "apap_sift_describe_batch_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, _vp, _i32p, _vp, _vp,
+                                                  C.c_size_t, _vp]),
 }
 
 _lib = None
@@ -885,3 +893,100 @@ def match_descriptors_batch(q, t, q_lengths, t_lengths, second=True, device=-1, 
                                              len(qo) - 1, _ptr(idx, C.c_int), _ptr(dist, C.c_float), _ptr(idx2, C.c_int),
                                              _ptr(dist2, C.c_float), device))
     return idx, dist, idx2, dist2
+
+
+# ---------------------------------------------------------------- descriptor extraction: SIFT at given keypoints
+SIFT_DIM = 128                  # APAP_SIFT_DIM
+SIFT_SAMPLES = 49               # APAP_SIFT_SAMPLES: the offsets |i|, |j| <= 3
+SIFT_TAPS = 13                  # APAP_SIFT_TAPS
+SIFT_PATCH = 21                 # APAP_SIFT_PATCH: the side of the grey patch one keypoint reads
+SIFT_WINDOW_COLS = 8            # APAP_SIFT_WINDOW_COLS
+SIFT_BLOCK_KEYPOINTS = 4        # APAP_SIFT_BLOCK_KEYPOINTS: keypoints per block (a wave each)
+SIFT_MIN_SIDE, SIFT_MAX_SIDE = 7, 32768
+SIFT_MAX_KEYPOINTS = 1 << 24    # per image
+SIFT_MAX_IMAGES = 65535
+
+
+def sift_window():
+    """``apap_sift_window`` (host only): the (49, 8) float32 table of the samples, rows in the order (i, j) ascending over
+    -3 .. 3: rbin, cbin, window weight, frac(rbin), frac(cbin), floor(rbin), floor(cbin), 0 - the kernel's own constants."""
+    out = np.empty((SIFT_SAMPLES, SIFT_WINDOW_COLS), np.float32)
+    check(lib().apap_sift_window(_ptr(out, C.c_float)))
+    return out
+
+
+def sift_taps():
+    """``apap_sift_taps`` (host only): the 13 float32 taps of the base image's Gaussian - the kernel's own constants."""
+    out = np.empty(SIFT_TAPS, np.float32)
+    check(lib().apap_sift_taps(_ptr(out, C.c_float)))
+    return out
+
+
+def as_sift_image(img, name="img"):
+    """A (h, w) grey or (h, w, 3) BGR uint8 image, contiguous; refuses every other dtype, shape or side outside 7 .. 32768.
+    Returns (array, channels)."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8:
+        raise ValueError(f"{name} must be uint8; got {img.dtype}")
+    if img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3)):
+        raise ValueError(f"{name} must be (h, w) grey or (h, w, 3) BGR; got {img.shape}")
+    if not all(SIFT_MIN_SIDE <= x <= SIFT_MAX_SIDE for x in img.shape[:2]):
+        raise ValueError(f"{name}: sides must be {SIFT_MIN_SIDE} .. {SIFT_MAX_SIDE}; got {img.shape[:2]}")
+    return np.ascontiguousarray(img), 1 if img.ndim == 2 else int(img.shape[2])
+
+
+def as_sift_points(pts, name="pts"):
+    """Keypoint coordinates (n, 2) as contiguous float32 (x, y): float64 and integers are cast first."""
+    pts = np.ascontiguousarray(pts, dtype=np.float32)
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise ValueError(f"{name} must be (n, 2); got {pts.shape}")
+    return pts
+
+
+def sift_offsets(lengths, name="lengths"):
+    """Keypoint counts of the images -> int32 offsets (len + 1), checked as the library checks them."""
+    lengths = [int(x) for x in lengths]
+    if not 1 <= len(lengths) <= SIFT_MAX_IMAGES:
+        raise ValueError(f"{name}: {len(lengths)} images (1 .. {SIFT_MAX_IMAGES})")
+    if any(not 1 <= x <= SIFT_MAX_KEYPOINTS for x in lengths):
+        raise ValueError(f"{name}: an image holds 1 .. 2^24 keypoints; got {lengths}")
+    if sum(lengths) > np.iinfo(np.int32).max:
+        raise ValueError(f"{name}: {sum(lengths)} keypoints in all exceed the int32 offsets")
+    off = np.zeros(len(lengths) + 1, np.int32)
+    off[1:] = np.cumsum(lengths)
+    return off
+
+
+def sift_describe_batch(imgs, pts, lengths, device=-1, ctx=None):
+    """``apap_sift_describe_batch``: the SIFT descriptors of OpenCV's ``KeyPoint(x, y, 1)`` at the given coordinates, many
+    images in one call (one kernel launch, whatever their number).  ``imgs``: a sequence of (h, w) grey or (h, w, 3) BGR uint8
+    arrays of any shapes; ``pts`` (N, 2): their keypoints (x, y) concatenated, image m of ``lengths[m]``.  Returns float32
+    (N, 128) with integer values 0 .. 255; an image's rows equal its own single call's byte for byte.  A keypoint with no
+    valid sample (on or beyond the border) gives zeros; a non-finite coordinate is refused."""
+    got = [as_sift_image(im, f"imgs[{m}]") for m, im in enumerate(imgs)]
+    pts = as_sift_points(pts)
+    if len(got) != len(lengths):
+        raise ValueError(f"sift_describe_batch: {len(got)} images, {len(lengths)} keypoint counts")
+    off = sift_offsets(lengths)
+    if off[-1] != len(pts):
+        raise ValueError(f"sift_describe_batch: the counts sum to {off[-1]} keypoints; got {len(pts)}")
+    ptrs = (C.c_void_p * len(got))(*[a.ctypes.data for a, _ in got])
+    hs, ws = np.array([a.shape[0] for a, _ in got], np.int32), np.array([a.shape[1] for a, _ in got], np.int32)
+    cs = np.array([c for _, c in got], np.int32)
+    out = np.empty((len(pts), SIFT_DIM), np.float32)
+    check(lib().apap_sift_describe_batch(_h(ctx), ptrs, _ptr(hs, C.c_int), _ptr(ws, C.c_int), _ptr(cs, C.c_int), len(got),
+                                         _ptr(pts, C.c_float), _ptr(off, C.c_int), _ptr(out, C.c_float), device))
+    return out
+
+
+def sift_describe(img, pts, device=-1, ctx=None):
+    """``apap_sift_describe``: float32 (n, 128) SIFT descriptors of ``KeyPoint(x, y, 1)`` at ``pts`` (n, 2) of one uint8 image
+    (see ``sift_describe_batch``; the single call is the batch of one)."""
+    img, ch = as_sift_image(img)
+    pts = as_sift_points(pts)
+    if not 1 <= len(pts) <= SIFT_MAX_KEYPOINTS:
+        raise ValueError(f"sift_describe: {len(pts)} keypoints (1 .. 2^24)")
+    out = np.empty((len(pts), SIFT_DIM), np.float32)
+    check(lib().apap_sift_describe(_h(ctx), _ptr(img, C.c_uint8), img.shape[0], img.shape[1], ch, _ptr(pts, C.c_float), len(pts),
+                                   _ptr(out, C.c_float), device))
+    return out

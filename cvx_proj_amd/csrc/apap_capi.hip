@@ -1134,4 +1134,62 @@ int apap_match_descriptors(apap_ctx *ctx, const float *q, int nq, const float *t
     return apap_match_descriptors_batch(ctx, q, t, qo, to, 1, idx, dist, idx2, dist2, device);
 }
 
+// ------------------------------------------------------------------ descriptor extraction (apap_sift.hip)
+int apap_sift_describe_batch(apap_ctx *ctx, const uint8_t *const *imgs, const int *heights, const int *widths, const int *channels,
+                             int n_images, const float *pts, const int *pt_offset, float *out, int device) {
+    const char *who = "apap_sift_describe_batch";
+    if (!imgs || !pts || !out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc = apap::sift_check(heights, widths, channels, n_images, pt_offset, who);
+    if (rc) return rc;
+    for (int m = 0; m < n_images; ++m)
+        if (!imgs[m]) return apap::fail(APAP_ERR_INVALID_ARG, "%s: image %d: null pointer", who, m);
+    const size_t k0 = (size_t)pt_offset[0], N = (size_t)pt_offset[n_images] - k0;   // the device arrays start at the first image
+    for (size_t k = 0; k < 2 * N; ++k)
+        if (!std::isfinite(pts[2 * k0 + k]))
+            return apap::fail(APAP_ERR_INVALID_ARG, "%s: keypoint %zu has a non-finite coordinate", who, k0 + k / 2);
+    PoolLock pl(ctx);
+    int dev;
+    if ((rc = select_device(device, &dev))) return rc;
+    std::vector<int> rel((size_t)n_images + 1);
+    for (int m = 0; m <= n_images; ++m) rel[m] = pt_offset[m] - pt_offset[0];
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    std::vector<size_t> o_img((size_t)n_images);
+    for (int m = 0; m < n_images; ++m) o_img[m] = take((size_t)heights[m] * widths[m] * channels[m]);
+    const size_t img_bytes = off;
+    off = 0;
+    const size_t o_pts = take(N * 2 * sizeof(float)), o_out = take(N * APAP_SIFT_DIM * sizeof(float));
+    const size_t work_bytes = apap_sift_workspace_bytes(n_images);
+    void *d_img, *d_io, *d_work;
+    if ((rc = slot_get(pl.pool, S_IMG, img_bytes, dev, &d_img))) return rc;
+    if ((rc = slot_get(pl.pool, S_AUX, off, dev, &d_io))) return rc;
+    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
+    char *d = (char *)d_io;
+    std::vector<const uint8_t *> d_imgs((size_t)n_images);
+    for (int m = 0; m < n_images; ++m) {
+        d_imgs[m] = (const uint8_t *)d_img + o_img[m];
+        APAP_HIP_TRY(hipMemcpyAsync((char *)d_img + o_img[m], imgs[m], (size_t)heights[m] * widths[m] * channels[m], hipMemcpyHostToDevice,
+                                    nullptr));
+    }
+    APAP_HIP_TRY(hipMemcpyAsync(d + o_pts, pts + 2 * k0, N * 2 * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    rc = apap_sift_describe_batch_device(ctx, d_imgs.data(), heights, widths, channels, n_images, (const float *)(d + o_pts), rel.data(),
+                                         (float *)(d + o_out), d_work, work_bytes, nullptr);
+    if (rc) {
+        (void)hipStreamSynchronize(nullptr);
+        return rc;
+    }
+    APAP_HIP_TRY(hipMemcpyAsync(out + k0 * APAP_SIFT_DIM, d + o_out, N * APAP_SIFT_DIM * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    return APAP_OK;
+}
+
+int apap_sift_describe(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, const float *pts, int n, float *out, int device) {
+    const int off[2] = {0, n};
+    return apap_sift_describe_batch(ctx, &img, &h, &w, &channels, 1, pts, off, out, device);
+}
+
 }  // extern "C"

@@ -121,6 +121,8 @@ int spectral_em_batch_check(const int *pair_offset, int n_pairs, const int *pair
 int local_model_check(int n, int cells, double gamma, double sigma, const double *params, const char *who);
 // The argument checks of the descriptor matcher's entry points (apap_match.hip) that need no device pointer.
 int match_check(const int *q_offset, const int *t_offset, int n_pairs, const char *who);
+// The argument checks of the descriptor extraction's entry points (apap_sift.hip) that need no device pointer.
+int sift_check(const int *heights, const int *widths, const int *channels, int n_images, const int *pt_offset, const char *who);
 // Set-up and the dense M (n x n doubles) on `stream`.
 int spectral_affinity_run(const float *d_src, const float *d_dst, const float *d_c, const float *d_o, int n, const double *d_F,
                           const double *params, double *d_M, void *d_work, size_t work_bytes, void *stream);

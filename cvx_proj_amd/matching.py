@@ -13,8 +13,9 @@ descriptor, the train descriptor at the smallest L2 distance.  ``apap_match_desc
 * ``matched_arrays``: ``(src_pts, dst_pts, c_feats, o_feats)``, what ``spectral_weights`` / ``spectral_em`` /
   ``spectral_em_batch`` take.
 
-SIFT extraction is not part of this package: descriptors are the caller's input.  ``DMatch`` and ``KeyPoint`` are the plain
-stand-ins for OpenCV's classes that the rest of the package duck-types.  Neither torch nor scipy is imported.  No CPU fallback.
+Descriptors are this module's input; ``cvx_proj_amd.features`` extracts them from images (SIFT at given keypoints) and hands
+on to it.  ``DMatch`` and ``KeyPoint`` are the plain stand-ins for OpenCV's classes that the rest of the package duck-types.
+Neither torch nor scipy is imported.  No CPU fallback.
 """
 from __future__ import annotations
 

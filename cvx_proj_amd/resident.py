@@ -408,3 +408,64 @@ def hip_match_descriptors(q, t, second=True, ctx=None, work=None):
     row of ``q`` (nq, 128), exact L2; the batch of one pair (see ``hip_match_descriptors_batch``)."""
     _needs_device(q, "hip_match_descriptors")
     return hip_match_descriptors_batch(q, t, [q.shape[0]], [t.shape[0]], second=second, ctx=ctx, work=work)
+
+
+def sift_workspace_bytes(n_images=1):
+    """Scratch of ``hip_sift_describe`` / ``hip_sift_describe_batch`` of ``n_images`` images: 32 bytes per image, a 256-byte
+    multiple.  0 for an invalid count."""
+    return _native.lib().apap_sift_workspace_bytes(int(n_images))
+
+
+def hip_sift_describe_batch(imgs, pts, lengths, ctx=None, work=None):
+    """``apap_sift_describe_batch_device`` on the current stream of the tensors' device, no host synchronisation: the SIFT
+    descriptors of ``KeyPoint(x, y, 1)`` at given coordinates, many images in one kernel launch.  ``imgs``: a sequence of
+    contiguous uint8 device tensors, (h, w) grey or (h, w, 3) BGR, of any shapes; ``pts``: contiguous float32 (N, 2) device
+    tensor, the images' keypoints (x, y) concatenated, image m of ``lengths[m]`` (a host list).  Returns float32 (N, 128), not
+    synchronised: what ``hip_match_descriptors`` takes.  A keypoint with no valid sample or a non-finite coordinate gives
+    zeros.  ``work`` (uint8) is used when it holds ``sift_workspace_bytes(len(imgs))``.  Same bytes as
+    ``_native.sift_describe_batch``, and per image as ``hip_sift_describe``."""
+    who = "hip_sift_describe_batch"
+    _needs_device(pts, who)
+    dev = pts.device
+    if pts.dtype != torch.float32 or not pts.is_contiguous() or pts.dim() != 2 or pts.shape[1] != 2:
+        raise ValueError(f"{who}: keypoints must be a contiguous float32 (n, 2) tensor")
+    imgs = list(imgs)
+    if len(imgs) != len(lengths):
+        raise ValueError(f"{who}: {len(imgs)} images, {len(lengths)} keypoint counts")
+    for m, im in enumerate(imgs):
+        if im.dtype != torch.uint8 or not im.is_contiguous() or im.device != dev or im.dim() not in (2, 3) or \
+                (im.dim() == 3 and im.shape[2] not in (1, 3)):
+            raise ValueError(f"{who}: imgs[{m}] must be a contiguous uint8 (h, w) or (h, w, 3) tensor on {dev}")
+        if not all(_native.SIFT_MIN_SIDE <= x <= _native.SIFT_MAX_SIDE for x in im.shape[:2]):
+            raise ValueError(f"{who}: imgs[{m}]: sides must be {_native.SIFT_MIN_SIDE} .. {_native.SIFT_MAX_SIDE}; got {tuple(im.shape[:2])}")
+    off = _native.sift_offsets(lengths)
+    if off[-1] != pts.shape[0]:
+        raise ValueError(f"{who}: the counts sum to {off[-1]} keypoints; got {pts.shape[0]}")
+    ip = ctypes.POINTER(ctypes.c_int)
+    ptrs = (ctypes.c_void_p * len(imgs))(*[im.data_ptr() for im in imgs])
+    hs, ws = np.array([im.shape[0] for im in imgs], np.int32), np.array([im.shape[1] for im in imgs], np.int32)
+    cs = np.array([1 if im.dim() == 2 else im.shape[2] for im in imgs], np.int32)
+    out = torch.empty((pts.shape[0], _native.SIFT_DIM), dtype=torch.float32, device=dev)
+    work = _scratch(work, sift_workspace_bytes(len(imgs)), dev)
+    _native.check(_native.lib().apap_sift_describe_batch_device(
+        _native._h(ctx), ptrs, hs.ctypes.data_as(ip), ws.ctypes.data_as(ip), cs.ctypes.data_as(ip), len(imgs), pts.data_ptr(),
+        off.ctypes.data_as(ip), out.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
+    return out
+
+
+def hip_sift_describe(img, pts, ctx=None, work=None):
+    """``apap_sift_describe_device``: float32 (n, 128) SIFT descriptors at ``pts`` (n, 2) of one uint8 device image; the batch
+    of one image (see ``hip_sift_describe_batch``)."""
+    _needs_device(pts, "hip_sift_describe")
+    return hip_sift_describe_batch([img], pts, [pts.shape[0]], ctx=ctx, work=work)
+
+
+def hip_describe_and_match(c_img, o_img, pts_c, pts_o, second=True, ctx=None):
+    """Both images described in one batched launch, then ``hip_match_descriptors`` of the centre image's descriptors against
+    the other's: three kernels on the current stream, nothing returns to the host in between.  Returns (idx, dist, idx2, dist2,
+    feats_c, feats_o): the matcher's four outputs (``idx2`` and ``dist2`` ``None`` without ``second``) and the float32 (n, 128)
+    descriptors, views of one tensor."""
+    _needs_device(pts_c, "hip_describe_and_match")
+    nc, no = pts_c.shape[0], pts_o.shape[0]
+    feats = hip_sift_describe_batch([c_img, o_img], torch.cat([pts_c, pts_o]), [nc, no], ctx=ctx)
+    return hip_match_descriptors(feats[:nc], feats[nc:], second=second, ctx=ctx) + (feats[:nc], feats[nc:])

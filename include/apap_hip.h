@@ -689,6 +689,55 @@ int apap_match_descriptors_batch_device(apap_ctx *ctx, const float *d_q, const f
                                         const int *t_offset, int n_pairs, int *d_idx, float *d_dist, int *d_idx2, float *d_dist2,
                                         void *d_work, size_t work_bytes, void *stream);
 
+/* ------------------------------------------------- descriptor extraction: SIFT at given keypoints --- */
+/* What coarse_matching asks of OpenCV before it matches (utils.py:142-151): cv.SIFT.create().compute(img, [cv.KeyPoint(x, y, 1)
+ * ...]), one 128-d descriptor per given keypoint (size 1, default angle, octave 0).  The definition - OpenCV 4.x's, restated
+ * without OpenCV - is in DESIGN.md "Descriptor extraction" and, operation by operation, in tests/sift_spec.py:
+ *   grey    (h, w) uint8 as it is; (h, w, 3) uint8 is BGR, grey = (3735 B + 19235 G + 9798 R + 16384) >> 15
+ *   base    the float32 grey image under a separable APAP_SIFT_TAPS-tap Gaussian, sigma = sqrt(1.6^2 - 0.5^2), reflect-101,
+ *           rows first; never materialised: a keypoint reads an APAP_SIFT_PATCH x APAP_SIFT_PATCH patch of the grey image
+ *   pt      (rint(x), rint(y)), round half to even; APAP_SIFT_SAMPLES samples at the offsets |i|, |j| <= 3, one counts if
+ *           0 < pt.y + i < h - 1 and 0 < pt.x + j < w - 1; gradient by central differences, magnitude x window weight,
+ *           orientation (the library's own atan2, <= 2e-6 rad) against 361 degrees, trilinear spread over 4 x 4 x 8 bins
+ *   out     clamp at 0.2 of the norm, scale to norm 512, round, saturate to 0 .. 255; float32 (n, APAP_SIFT_DIM): what SIFT
+ *           returns and what apap_match_descriptors takes.  A keypoint without a valid sample is 128 zeros, never NaN.
+ * Every operation is a single IEEE float32 operation in a fixed order (no fused multiply-add, no floating-point atomics): the
+ * outputs are a function of the image bytes and the float32 coordinates alone - the same bytes from every entry point below,
+ * whatever the launch geometry and whatever else is in a batch.
+ *   apap_sift_window   host only: the APAP_SIFT_SAMPLES x APAP_SIFT_WINDOW_COLS float32 table of the samples, rows in the order
+ *                      (i, j) ascending: rbin, cbin, window weight exp(-(c_rot^2 + r_rot^2) / 8), rbin - floor(rbin),
+ *                      cbin - floor(cbin), floor(rbin), floor(cbin), 0 - evaluated in float64 and rounded
+ *   apap_sift_taps     host only: the APAP_SIFT_TAPS float32 taps, likewise
+ * Batch: n_images images of their own shapes (HOST arrays heights, widths, channels and a HOST array of the image pointers -
+ * device pointers for the _device form); the keypoints (x, y) float32 concatenated, image m holds rows pt_offset[m] ..
+ * pt_offset[m + 1] - 1 (a HOST array of n_images + 1 strictly increasing entries; the device arrays are indexed by them as
+ * given, the host-buffer form reads and writes from pt_offset[0] on).  One small upload and one kernel launch, whatever
+ * n_images; every image's rows equal, byte for byte, its own single call's (the single call is the batch of one).
+ * Refused before any device is touched: null pointers, sides outside 7 .. 32768, channels other than 1 or 3, a count of
+ * keypoints (per image) outside 1 .. 2^24, n_images outside 1 .. 65535, negative or not strictly increasing offsets, a
+ * non-finite coordinate (host-buffer forms; the _device forms give such a keypoint 128 zeros), a short (APAP_ERR_WORKSPACE)
+ * or misaligned workspace (256 bytes).  Without a GPU the host-buffer forms return APAP_ERR_NO_DEVICE: there is no CPU fallback.
+ * The _device forms only enqueue on `stream` and do not wait.  d_work: at least apap_sift_workspace_bytes(n_images) bytes (0 for
+ * an invalid count; a 256-byte multiple): 32 bytes per image.  A block of 64 x APAP_SIFT_BLOCK_KEYPOINTS threads takes
+ * APAP_SIFT_BLOCK_KEYPOINTS consecutive keypoints of the concatenated list (for tests; no output depends on it). */
+#define APAP_SIFT_DIM 128             /* = APAP_MATCH_DIM */
+#define APAP_SIFT_SAMPLES 49
+#define APAP_SIFT_TAPS 13
+#define APAP_SIFT_PATCH 21
+#define APAP_SIFT_WINDOW_COLS 8
+#define APAP_SIFT_BLOCK_KEYPOINTS 4
+int apap_sift_window(float *out);
+int apap_sift_taps(float *out);
+size_t apap_sift_workspace_bytes(int n_images);
+int apap_sift_describe(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, const float *pts, int n, float *out, int device);
+int apap_sift_describe_device(apap_ctx *ctx, const uint8_t *d_img, int h, int w, int channels, const float *d_pts, int n, float *d_out,
+                              void *d_work, size_t work_bytes, void *stream);
+int apap_sift_describe_batch(apap_ctx *ctx, const uint8_t *const *imgs, const int *heights, const int *widths, const int *channels,
+                             int n_images, const float *pts, const int *pt_offset, float *out, int device);
+int apap_sift_describe_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs, const int *heights, const int *widths,
+                                    const int *channels, int n_images, const float *d_pts, const int *pt_offset, float *d_out,
+                                    void *d_work, size_t work_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
