@@ -82,6 +82,7 @@ _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
 _i32p = C.POINTER(C.c_int)
+_i64p = C.POINTER(C.c_longlong)
 _vp = C.c_void_p
 
 # name -> (restype, argtypes).  Must list every symbol include/apap_hip.h declares;
@@ -194,6 +195,14 @@ SIGNATURES = {
     "apap_sift_describe_batch": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, _f32p, _i32p, _f32p, C.c_int]),
     "apap_sift_describe_batch_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, _vp, _i32p, _vp, _vp,
                                                   C.c_size_t, _vp]),
+    "apap_corner_workspace_bytes": (C.c_size_t, [_i32p, _i32p, C.c_int, C.c_int]),
+    "apap_corner_detect": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _i64p, _i32p, C.c_int]),
+    "apap_corner_detect_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
+                                            C.c_size_t, _vp]),
+    "apap_corner_detect_batch": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p,
+                                           _i64p, _i32p, C.c_int]),
+    "apap_corner_detect_batch_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 
 _lib = None
@@ -990,3 +999,67 @@ def sift_describe(img, pts, device=-1, ctx=None):
     check(lib().apap_sift_describe(_h(ctx), _ptr(img, C.c_uint8), img.shape[0], img.shape[1], ch, _ptr(pts, C.c_float), len(pts),
                                    _ptr(out, C.c_float), device))
     return out
+
+
+# ---------------------------------------------------------------- corner detection: exact integer Harris corners
+CORNER_TILE_W, CORNER_TILE_H = 64, 32   # APAP_CORNER_TILE_W, APAP_CORNER_TILE_H
+CORNER_MAX_RADIUS = 16                  # APAP_CORNER_MAX_RADIUS
+CORNER_MAX_IMAGES = 65535
+
+
+def corner_bound(h, w, radius):
+    """``ceil(h / (radius + 1)) * ceil(w / (radius + 1))``: no image of that shape has more corners."""
+    s = int(radius) + 1
+    return -(-int(h) // s) * -(-int(w) // s)
+
+
+def corner_params(max_corners, radius, quality_permille, who="corner_detect"):
+    """The three parameters as ints, checked as the library checks them."""
+    max_corners, radius, quality_permille = int(max_corners), int(radius), int(quality_permille)
+    if max_corners < 1:
+        raise ValueError(f"{who}: max_corners must be >= 1; got {max_corners}")
+    if not 1 <= radius <= CORNER_MAX_RADIUS:
+        raise ValueError(f"{who}: radius must be 1 .. {CORNER_MAX_RADIUS}; got {radius}")
+    if not 0 <= quality_permille <= 1000:
+        raise ValueError(f"{who}: quality_permille must be 0 .. 1000; got {quality_permille}")
+    return max_corners, radius, quality_permille
+
+
+def corner_detect_batch(imgs, max_corners, radius=5, quality_permille=10, device=-1, ctx=None):
+    """``apap_corner_detect_batch``: exact integer Harris corners (include/apap_hip.h "corner detection") of many images in
+    one call (two kernel launches, whatever their number).  ``imgs``: a sequence of (h, w) grey or (h, w, 3) BGR uint8 arrays
+    of any shapes.  Returns a list of ``(pts, response)`` per image: float32 (n, 2) integer-valued (x, y) and int64 (n,), by
+    response descending then index ascending, ``n <= max_corners``; an image's outputs equal its own single call's byte for
+    byte.  ``max_corners`` beyond the largest image's bound on the corner count asks for no more rows than that bound."""
+    got = [as_sift_image(im, f"imgs[{m}]") for m, im in enumerate(imgs)]
+    if not 1 <= len(got) <= CORNER_MAX_IMAGES:
+        raise ValueError(f"corner_detect_batch: {len(got)} images (1 .. {CORNER_MAX_IMAGES})")
+    max_corners, radius, quality_permille = corner_params(max_corners, radius, quality_permille, "corner_detect_batch")
+    rows = min(max_corners, max(corner_bound(a.shape[0], a.shape[1], radius) for a, _ in got))
+    ptrs = (C.c_void_p * len(got))(*[a.ctypes.data for a, _ in got])
+    hs, ws = np.array([a.shape[0] for a, _ in got], np.int32), np.array([a.shape[1] for a, _ in got], np.int32)
+    cs = np.array([c for _, c in got], np.int32)
+    pts = np.empty((len(got), rows, 2), np.float32)
+    resp = np.empty((len(got), rows), np.int64)
+    count = np.empty(len(got), np.int32)
+    check(lib().apap_corner_detect_batch(_h(ctx), ptrs, _ptr(hs, C.c_int), _ptr(ws, C.c_int), _ptr(cs, C.c_int), len(got), rows, radius,
+                                         quality_permille, _ptr(pts, C.c_float), _ptr(resp, C.c_longlong), _ptr(count, C.c_int), device))
+    return [(pts[m, :count[m]].copy(), resp[m, :count[m]].copy()) for m in range(len(got))]
+
+
+def corner_detect(img, max_corners, radius=5, quality_permille=10, device=-1, ctx=None, full=False):
+    """``apap_corner_detect``: the exact integer Harris corners of one uint8 image, (h, w) grey or (h, w, 3) BGR: ``(pts,
+    response)`` trimmed to the count - float32 (n, 2) integer-valued (x, y), directly usable as keypoints of ``sift_describe``,
+    and int64 (n,) responses, by response descending then index ascending.  An image without corners gives two empty arrays.
+    With ``full``: ``(pts, response, count)`` as the library wrote them, all ``max_corners`` rows (zero from ``count`` on)."""
+    img, ch = as_sift_image(img)
+    max_corners, radius, quality_permille = corner_params(max_corners, radius, quality_permille)
+    rows = max_corners if full else min(max_corners, corner_bound(img.shape[0], img.shape[1], radius))
+    pts = np.empty((rows, 2), np.float32)
+    resp = np.empty(rows, np.int64)
+    count = C.c_int(-1)
+    check(lib().apap_corner_detect(_h(ctx), _ptr(img, C.c_uint8), img.shape[0], img.shape[1], ch, rows, radius, quality_permille,
+                                   _ptr(pts, C.c_float), _ptr(resp, C.c_longlong), C.byref(count), device))
+    if full:
+        return pts, resp, count.value
+    return pts[:count.value].copy(), resp[:count.value].copy()

@@ -1192,4 +1192,59 @@ int apap_sift_describe(apap_ctx *ctx, const uint8_t *img, int h, int w, int chan
     return apap_sift_describe_batch(ctx, &img, &h, &w, &channels, 1, pts, off, out, device);
 }
 
+// ------------------------------------------------------------------ corner detection (apap_corner.hip)
+int apap_corner_detect_batch(apap_ctx *ctx, const uint8_t *const *imgs, const int *heights, const int *widths, const int *channels,
+                             int n_images, int max_corners, int radius, int quality_permille, float *pts, long long *response,
+                             int *count, int device) {
+    const char *who = "apap_corner_detect_batch";
+    if (!imgs || !pts || !response || !count) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc = apap::corner_check(heights, widths, channels, n_images, max_corners, radius, quality_permille, who);
+    if (rc) return rc;
+    for (int m = 0; m < n_images; ++m)
+        if (!imgs[m]) return apap::fail(APAP_ERR_INVALID_ARG, "%s: image %d: null pointer", who, m);
+    PoolLock pl(ctx);
+    int dev;
+    if ((rc = select_device(device, &dev))) return rc;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    std::vector<size_t> o_img((size_t)n_images);
+    for (int m = 0; m < n_images; ++m) o_img[m] = take((size_t)heights[m] * widths[m] * channels[m]);
+    const size_t img_bytes = off;
+    off = 0;
+    const size_t rows = (size_t)n_images * (size_t)max_corners;
+    const size_t o_pts = take(rows * 2 * sizeof(float)), o_resp = take(rows * sizeof(long long)), o_count = take((size_t)n_images * sizeof(int));
+    const size_t work_bytes = apap_corner_workspace_bytes(heights, widths, n_images, radius);
+    void *d_img, *d_io, *d_work;
+    if ((rc = slot_get(pl.pool, S_IMG, img_bytes, dev, &d_img))) return rc;
+    if ((rc = slot_get(pl.pool, S_AUX, off, dev, &d_io))) return rc;
+    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
+    char *d = (char *)d_io;
+    std::vector<const uint8_t *> d_imgs((size_t)n_images);
+    for (int m = 0; m < n_images; ++m) {
+        d_imgs[m] = (const uint8_t *)d_img + o_img[m];
+        APAP_HIP_TRY(hipMemcpyAsync((char *)d_img + o_img[m], imgs[m], (size_t)heights[m] * widths[m] * channels[m], hipMemcpyHostToDevice,
+                                    nullptr));
+    }
+    rc = apap_corner_detect_batch_device(ctx, d_imgs.data(), heights, widths, channels, n_images, max_corners, radius, quality_permille,
+                                         (float *)(d + o_pts), (long long *)(d + o_resp), (int *)(d + o_count), d_work, work_bytes, nullptr);
+    if (rc) {
+        (void)hipStreamSynchronize(nullptr);
+        return rc;
+    }
+    APAP_HIP_TRY(hipMemcpyAsync(pts, d + o_pts, rows * 2 * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(response, d + o_resp, rows * sizeof(long long), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipMemcpyAsync(count, d + o_count, (size_t)n_images * sizeof(int), hipMemcpyDeviceToHost, nullptr));
+    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    return APAP_OK;
+}
+
+int apap_corner_detect(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, int max_corners, int radius,
+                       int quality_permille, float *pts, long long *response, int *count, int device) {
+    return apap_corner_detect_batch(ctx, &img, &h, &w, &channels, 1, max_corners, radius, quality_permille, pts, response, count, device);
+}
+
 }  // extern "C"

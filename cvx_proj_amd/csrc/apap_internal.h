@@ -123,6 +123,9 @@ int local_model_check(int n, int cells, double gamma, double sigma, const double
 int match_check(const int *q_offset, const int *t_offset, int n_pairs, const char *who);
 // The argument checks of the descriptor extraction's entry points (apap_sift.hip) that need no device pointer.
 int sift_check(const int *heights, const int *widths, const int *channels, int n_images, const int *pt_offset, const char *who);
+// The argument checks of the corner detector's entry points (apap_corner.hip) that need no device pointer.
+int corner_check(const int *heights, const int *widths, const int *channels, int n_images, int max_corners, int radius,
+                 int quality_permille, const char *who);
 // Set-up and the dense M (n x n doubles) on `stream`.
 int spectral_affinity_run(const float *d_src, const float *d_dst, const float *d_c, const float *d_o, int n, const double *d_F,
                           const double *params, double *d_M, void *d_work, size_t work_bytes, void *stream);

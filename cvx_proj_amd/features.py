@@ -10,6 +10,13 @@ The reference's ``coarse_matching`` (utils.py:142-151) starts from two images an
   images are described in one batched call.
 * ``matched_arrays``: ``(src_pts, dst_pts, c_feats, o_feats)``, what ``spectral_weights`` / ``spectral_em`` take.
 
+The keypoint coordinates need not come from outside: ``apap_corner_detect`` finds exact integer Harris corners (DESIGN.md
+"Corner detection"), which is all the descriptor can use - it rounds its coordinates and reads the base level only.
+
+* ``detect`` / ``detect_pair``: (n, 2) float32 corners, directly usable as ``raw_kpts``; the pair in one batched call.
+* ``detect_and_match``: ``coarse_matching``'s 5-tuple from the two images alone.
+* ``matched_arrays_from_images``: ``matched_arrays`` from the two images alone.
+
 Images are uint8, (h, w) grey or (h, w, 3) BGR (what ``cv.imread`` returns).  Neither torch nor scipy nor cv2 is imported.
 No CPU fallback.
 """
@@ -20,6 +27,7 @@ import numpy as np
 from . import _native, matching
 from .matching import KeyPoint
 
+# the descriptor stage's names, which tests/test_sift_host.py pins; the detection functions below are public all the same
 __all__ = ["compute", "describe_pair", "coarse_matching", "matched_arrays"]
 
 
@@ -55,3 +63,34 @@ def matched_arrays(c_img, o_img, raw_kpts_cp, raw_kpts_op, device=-1, ctx=None, 
     the arrays ``spectral_em`` takes."""
     feats_cp, feats_op = describe_pair(c_img, o_img, raw_kpts_cp, raw_kpts_op, device=device, ctx=ctx)
     return matching.matched_arrays(raw_kpts_cp, feats_cp, raw_kpts_op, feats_op, device=device, ctx=ctx, **match_kw)
+
+
+def _permille(quality):
+    return int(round(1000 * float(quality)))
+
+
+def detect(img, max_corners=2000, radius=5, quality=0.01, device=-1, ctx=None):
+    """The image's corners as (n, 2) float32 (x, y), integer-valued, strongest first: ``raw_kpts`` for ``compute`` and
+    ``coarse_matching``.  A corner is the strict maximum of the integer Harris response over its (2 radius + 1)^2 window and
+    reaches ``quality`` (rounded to a permille) of the strongest corner's response; at most ``max_corners`` are returned.  An
+    image without corners gives a (0, 2) array."""
+    return _native.corner_detect(img, max_corners, radius, _permille(quality), device=device, ctx=ctx)[0]
+
+
+def detect_pair(c_img, o_img, max_corners=2000, radius=5, quality=0.01, device=-1, ctx=None):
+    """The corners of both images in one batched call: (kpts_cp, kpts_op), each as ``detect`` returns it."""
+    (pc, _), (po, _) = _native.corner_detect_batch([c_img, o_img], max_corners, radius, _permille(quality), device=device, ctx=ctx)
+    return pc, po
+
+
+def detect_and_match(c_img, o_img, max_corners=2000, radius=5, quality=0.01, device=-1, ctx=None, **match_kw):
+    """``coarse_matching``'s 5-tuple ``(kpts_cp, feats_cp, kpts_op, feats_op, matches)`` from the two images alone: their
+    corners (``detect_pair``), the descriptors there, the matches."""
+    pc, po = detect_pair(c_img, o_img, max_corners, radius, quality, device=device, ctx=ctx)
+    return coarse_matching(c_img, o_img, pc, po, device=device, ctx=ctx, **match_kw)
+
+
+def matched_arrays_from_images(c_img, o_img, max_corners=2000, radius=5, quality=0.01, device=-1, ctx=None, **match_kw):
+    """``matched_arrays``'s ``(src_pts, dst_pts, c_feats, o_feats)`` from the two images alone: what ``spectral_em`` takes."""
+    pc, po = detect_pair(c_img, o_img, max_corners, radius, quality, device=device, ctx=ctx)
+    return matched_arrays(c_img, o_img, pc, po, device=device, ctx=ctx, **match_kw)

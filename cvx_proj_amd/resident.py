@@ -469,3 +469,74 @@ def hip_describe_and_match(c_img, o_img, pts_c, pts_o, second=True, ctx=None):
     nc, no = pts_c.shape[0], pts_o.shape[0]
     feats = hip_sift_describe_batch([c_img, o_img], torch.cat([pts_c, pts_o]), [nc, no], ctx=ctx)
     return hip_match_descriptors(feats[:nc], feats[nc:], second=second, ctx=ctx) + (feats[:nc], feats[nc:])
+
+
+def _corner_images(imgs, who):
+    """The checks of a sequence of uint8 device images and their shape tables."""
+    imgs = list(imgs)
+    if not imgs:
+        raise ValueError(f"{who}: no image")
+    _needs_device(imgs[0], who)
+    dev = imgs[0].device
+    for m, im in enumerate(imgs):
+        if im.dtype != torch.uint8 or not im.is_contiguous() or im.device != dev or im.dim() not in (2, 3) or \
+                (im.dim() == 3 and im.shape[2] not in (1, 3)):
+            raise ValueError(f"{who}: imgs[{m}] must be a contiguous uint8 (h, w) or (h, w, 3) tensor on {dev}")
+        if not all(_native.SIFT_MIN_SIDE <= x <= _native.SIFT_MAX_SIDE for x in im.shape[:2]):
+            raise ValueError(f"{who}: imgs[{m}]: sides must be {_native.SIFT_MIN_SIDE} .. {_native.SIFT_MAX_SIDE}; got {tuple(im.shape[:2])}")
+    hs, ws = np.array([im.shape[0] for im in imgs], np.int32), np.array([im.shape[1] for im in imgs], np.int32)
+    cs = np.array([1 if im.dim() == 2 else im.shape[2] for im in imgs], np.int32)
+    return imgs, dev, hs, ws, cs
+
+
+def corner_workspace_bytes(shapes, radius=5):
+    """Scratch of ``hip_corner_detect`` / ``hip_corner_detect_batch`` for images of ``shapes`` (a sequence of (h, w, ...)):
+    per image 64 bytes and twice 16 bytes per possible corner (the second time rounded up to a power of two); a 256-byte
+    multiple.  0 for invalid arguments."""
+    hs, ws = np.array([s[0] for s in shapes], np.int32), np.array([s[1] for s in shapes], np.int32)
+    ip = ctypes.POINTER(ctypes.c_int)
+    return _native.lib().apap_corner_workspace_bytes(hs.ctypes.data_as(ip), ws.ctypes.data_as(ip), len(hs), int(radius))
+
+
+def hip_corner_detect_batch(imgs, max_corners, radius=5, quality_permille=10, ctx=None, work=None):
+    """``apap_corner_detect_batch_device`` on the current stream of the tensors' device, no host synchronisation: the exact
+    integer Harris corners of many images in two kernel launches.  ``imgs``: a sequence of contiguous uint8 device tensors,
+    (h, w) grey or (h, w, 3) BGR, of any shapes.  Returns ``(pts, response, count)``, not synchronised: float32
+    (n_images, max_corners, 2) integer-valued (x, y), int64 (n_images, max_corners) and int32 (n_images,); rows from an image's
+    count on are zero.  ``work`` (uint8) is used when it holds ``corner_workspace_bytes(shapes, radius)``.  Same bytes as
+    ``_native.corner_detect_batch``, and per image as ``hip_corner_detect``."""
+    who = "hip_corner_detect_batch"
+    imgs, dev, hs, ws, cs = _corner_images(imgs, who)
+    max_corners, radius, quality_permille = _native.corner_params(max_corners, radius, quality_permille, who)
+    ip = ctypes.POINTER(ctypes.c_int)
+    ptrs = (ctypes.c_void_p * len(imgs))(*[im.data_ptr() for im in imgs])
+    pts = torch.empty((len(imgs), max_corners, 2), dtype=torch.float32, device=dev)
+    resp = torch.empty((len(imgs), max_corners), dtype=torch.int64, device=dev)
+    count = torch.empty(len(imgs), dtype=torch.int32, device=dev)
+    work = _scratch(work, _native.lib().apap_corner_workspace_bytes(hs.ctypes.data_as(ip), ws.ctypes.data_as(ip), len(imgs), radius), dev)
+    _native.check(_native.lib().apap_corner_detect_batch_device(
+        _native._h(ctx), ptrs, hs.ctypes.data_as(ip), ws.ctypes.data_as(ip), cs.ctypes.data_as(ip), len(imgs), max_corners, radius,
+        quality_permille, pts.data_ptr(), resp.data_ptr(), count.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
+    return pts, resp, count
+
+
+def hip_corner_detect(img, max_corners, radius=5, quality_permille=10, ctx=None, work=None):
+    """``apap_corner_detect_device``: ``(pts (max_corners, 2), response (max_corners,), count ())`` of one uint8 device image;
+    the batch of one image (see ``hip_corner_detect_batch``)."""
+    pts, resp, count = hip_corner_detect_batch([img], max_corners, radius, quality_permille, ctx=ctx, work=work)
+    return pts[0], resp[0], count[0]
+
+
+def hip_detect_describe_match(c_img, o_img, max_corners, radius=5, quality_permille=10, second=True, ctx=None):
+    """From two uint8 device images to matches: both images' corners in one batched call, their descriptors in one batched
+    call, then ``hip_match_descriptors`` of the centre image's descriptors against the other's.  Between detection and
+    description the two corner counts (8 bytes) are read back: the chain's only host synchronisation, needed because the
+    describe and match entry points take their lengths on the host.  Returns (idx, dist, idx2, dist2, feats_c, feats_o, pts_c,
+    pts_o): ``hip_describe_and_match``'s six outputs and the float32 (n, 2) corners.  An image without corners is refused
+    (``ValueError``): there is nothing to describe or match."""
+    pts, _, count = hip_corner_detect_batch([c_img, o_img], max_corners, radius, quality_permille, ctx=ctx)
+    nc, no = (int(x) for x in count.tolist())
+    if nc < 1 or no < 1:
+        raise ValueError(f"hip_detect_describe_match: {nc} and {no} corners; both images need at least one")
+    pts_c, pts_o = pts[0, :nc], pts[1, :no]
+    return hip_describe_and_match(c_img, o_img, pts_c, pts_o, second=second, ctx=ctx) + (pts_c, pts_o)

@@ -738,6 +738,52 @@ int apap_sift_describe_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs,
                                     const int *channels, int n_images, const float *d_pts, const int *pt_offset, float *d_out,
                                     void *d_work, size_t work_bytes, void *stream);
 
+/* ------------------------------------------------- corner detection: exact integer Harris corners --- */
+/* The keypoints that apap_sift_describe takes, from the image alone: integer pixel corners (the descriptor rounds its
+ * coordinates and reads the base level only, so nothing finer could be used).  Everything is integer arithmetic - no float,
+ * no rounding; the definition is in DESIGN.md "Corner detection" and, in numpy int64, in tests/corner_spec.py:
+ *   grey     (h, w) uint8 as it is; (h, w, 3) uint8 is BGR, grey = (3735 B + 19235 G + 9798 R + 16384) >> 15
+ *   Ix, Iy   3 x 3 Sobel with reflect-101 indices: Ix = (g[y-1,x+1] + 2 g[y,x+1] + g[y+1,x+1]) - (g[y-1,x-1] + 2 g[y,x-1] +
+ *            g[y+1,x-1]), Iy the same with rows and columns exchanged; -1020 .. 1020
+ *   a, b, c  the unnormalised 3 x 3 box sums of Ix^2, Ix Iy, Iy^2, reflect-101 on the indices of the product images; < 2^24
+ *   R        25 (a c - b^2) - (a + c)^2 in int64: 25 times Harris's det - k tr^2 at k = 0.04; |R| < 2.2e15
+ *   corner   R > 0 and (R, -index), index = y w + x, lexicographically greater than that of every other pixel of the
+ *            (2 radius + 1)^2 window inside the image: a plateau yields one corner, no two corners lie within `radius` of
+ *            each other in both axes, so an image holds at most ceil(h / (radius + 1)) ceil(w / (radius + 1)) of them
+ *   quality  with Rmax the largest corner response, a corner is kept if 1000 R >= quality_permille Rmax
+ *   order    R descending, then index ascending; the first max_corners are returned
+ *   pts      (max_corners, 2) float32 (x, y), integer-valued; response (max_corners) long long; *count int: rows from
+ *            *count on are zero.  An image without corners (flat, or straight edges only) gives *count = 0: not an error.
+ * The outputs are a function of the image bytes and (max_corners, radius, quality_permille) alone: the same bytes from every
+ * entry point below, whatever the tile geometry, the order in which atomics append candidates and whatever else is in a batch.
+ * Batch: n_images images of their own shapes (HOST arrays heights, widths, channels and a HOST array of the image pointers -
+ * device pointers for the _device form), one set of parameters; image m writes rows m max_corners .. (m + 1) max_corners - 1
+ * of pts and response, and count[m].  One small upload, one memset and two kernel launches, whatever n_images; every image's
+ * outputs equal, byte for byte, its own single call's (the single call is the batch of one).
+ * Refused before any device is touched: null pointers, sides outside 7 .. 32768, channels other than 1 or 3, radius outside
+ * 1 .. APAP_CORNER_MAX_RADIUS, quality_permille outside 0 .. 1000, max_corners < 1, n_images outside 1 .. 65535, a short
+ * (APAP_ERR_WORKSPACE) or misaligned workspace (256 bytes; pts and response 8).  Without a GPU the host-buffer forms return
+ * APAP_ERR_NO_DEVICE: there is no CPU fallback.
+ * The _device forms only enqueue on `stream` and do not wait.  d_work: at least apap_corner_workspace_bytes(...) bytes (0 for
+ * invalid arguments; a 256-byte multiple): 48 + 16 bytes per image, and 16 bytes per possible corner (the bound above) twice,
+ * the second time rounded up to a power of two.  A block takes a tile of APAP_CORNER_TILE_W x APAP_CORNER_TILE_H pixels (for
+ * tests; no output depends on it). */
+#define APAP_CORNER_TILE_W 64
+#define APAP_CORNER_TILE_H 32
+#define APAP_CORNER_MAX_RADIUS 16
+size_t apap_corner_workspace_bytes(const int *heights, const int *widths, int n_images, int radius);
+int apap_corner_detect(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, int max_corners, int radius,
+                       int quality_permille, float *pts, long long *response, int *count, int device);
+int apap_corner_detect_device(apap_ctx *ctx, const uint8_t *d_img, int h, int w, int channels, int max_corners, int radius,
+                              int quality_permille, float *d_pts, long long *d_response, int *d_count, void *d_work, size_t work_bytes,
+                              void *stream);
+int apap_corner_detect_batch(apap_ctx *ctx, const uint8_t *const *imgs, const int *heights, const int *widths, const int *channels,
+                             int n_images, int max_corners, int radius, int quality_permille, float *pts, long long *response,
+                             int *count, int device);
+int apap_corner_detect_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs, const int *heights, const int *widths,
+                                    const int *channels, int n_images, int max_corners, int radius, int quality_permille,
+                                    float *d_pts, long long *d_response, int *d_count, void *d_work, size_t work_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
