@@ -143,7 +143,9 @@ def max_step(A, dA):
 def ipm(R, h0):
     """Primal-dual path following (HKM direction, Mehrotra predictor-corrector) from the strictly feasible pair
     x = (h0, tau, tau), Z = diag(zeta I_15, 1/2, 1/2, 1).  R: the equilibrated factor.  Returns (x (10,), Z (18, 18), gap,
-    iterations, converged); gap = tr(S Z) / (r + t)."""
+    iterations, converged); gap = tr(S Z) / (r + t).  The kernel's guards: when rounding pushes S out of the cone, or the
+    Schur matrix is no longer positive definite (near-collinear points, at gaps just above GAP_TOL), the loop ends there and
+    the best iterate is returned with converged False."""
     F = lmi_basis(R)
     c = np.zeros(10)
     c[8:] = 1.0
@@ -165,12 +167,17 @@ def ipm(R, h0):
         if rel <= GAP_TOL or it == MAX_IT:
             break
         mu = gap_abs / 18.0
+        if not _chol_ok(S):
+            break
         Si = np.linalg.inv(S)
         B = [F[1 + i] @ Si for i in range(10)]           # F_i S^-1
         FZ = [F[1 + j] @ Z for j in range(10)]           # F_j Z
         Mx = np.array([[np.sum(B[i] * FZ[j].T) for j in range(10)] for i in range(10)])   # tr(F_i S^-1 F_j Z)
         g = np.array([np.trace(Si @ F[1 + i]) for i in range(10)])
-        L = np.linalg.cholesky(Mx)
+        try:
+            L = np.linalg.cholesky(Mx)
+        except np.linalg.LinAlgError:
+            break
 
         def solve(rhs):
             return np.linalg.solve(L.T, np.linalg.solve(L, rhs))

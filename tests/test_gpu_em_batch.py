@@ -162,6 +162,23 @@ def test_batch_of_one_equals_the_single_call(native_gpu, name):
     assert int(status[0]) == word
 
 
+def test_unequal_fluctuations_in_one_batch(native_gpu):
+    """du != dv and its exchange next to du = dv on one pair (blocks() passes one value for both): each problem equals its
+    own single call."""
+    native = native_gpu
+    pair, opts = load("spectral_n500")
+    sp = native.spectral_params(**opts)
+    sets = [(0.5, 0.5), (0.2, 1.25), (1.25, 0.2)]
+    problems = [(0, (sp, native.model_params(native.MODEL_SDP, du, dv))) for du, dv in sets]
+    got, status = batch(native, [pair], problems, 2)
+    for b, (du, dv) in enumerate(sets):
+        want, word, raised = single(native, pair, sp, problems[b][1][1], 2)
+        assert not raised
+        assert_same(got[b], want, (du, dv))
+        assert int(status[b]) == word, (du, dv)
+    assert got[1][0].tobytes() != got[2][0].tobytes()       # the exchange is another problem, and is routed as one
+
+
 GRID = {"affinity_eps": [20, 22.5, 25, 27.5], "aff_thresh": [0.6, 0.7, 0.8], "epi_weight": [0.25, 0.5, 0.75], "fluc": [0.8, 1.0, 1.25]}
 
 

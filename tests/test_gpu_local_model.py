@@ -126,6 +126,22 @@ def test_every_cell_equals_its_own_model_solve(native_gpu, n, solver, fluc, swap
         assert a.tobytes() == b.tobytes()     # inputs untouched
 
 
+@pytest.mark.parametrize("n", [240, 241, 720, 721])
+def test_unequal_fluctuations_at_the_block_edges(native_gpu, n):
+    """du != dv (params_of passes one value for both) with n on the 240-match block and on the three-block fold of M2."""
+    native = native_gpu
+    pc, po = pair(n)
+    v = np.stack(np.meshgrid(np.float64([320.37, 960.37]), np.float64([239.79, 719.79])), axis=-1)      # (2, 2, 2)
+    mw = match_weights("spectral", n)
+    params = native.model_params(native.MODEL_SDP, 0.2, 1.25, floor=1e-3, swap=True)
+    H, info, status = native.local_model_solve(pc, po, v, SMALL_GAMMA, SIGMA, params, match_weights=mw)
+    assert H.shape == (2, 2, 3, 3) and info.shape == (2, 2, native.MODEL_INFO) and status.shape == (2, 2)
+    w = cell_weights(native, pc, v, SMALL_GAMMA, SIGMA, mw)
+    for k in range(4):
+        i, j = divmod(k, 2)
+        assert_cell(native, (H[i, j], info[i, j], status[i, j]), single(native, pc, po, w[k], params), (n, k))
+
+
 def test_floor_off_keeps_every_match(native_gpu):
     """floor = None (-inf): zero-weight matches stay in as zero rows; the count is n in every cell."""
     native = native_gpu

@@ -86,6 +86,43 @@ def test_numpy_lms_is_least_squares():
     assert np.abs((h - ref) * cn).max() <= 1e-9 * np.abs(ref * cn).max()
 
 
+def test_guarded_ipm_on_near_collinear_points():
+    """The reference's own standing on the 72 near-collinear inputs of tests/test_gpu_model_edges.py: none is degenerate
+    (smallest equilibrated pivot far above the kernel's 1e-12), at most a third end above the 1e-10 gap (the Schur matrix
+    loses positive definiteness first; the guarded ipm keeps the best iterate), and every certificate holds to 1e-9."""
+    from test_gpu_model_edges import COLLINEAR, collinear_spec
+    gap, pivot, cert, rt = collinear_spec().T
+    late = int((gap > S.GAP_TOL).sum())
+    print(f"near-collinear family, guarded specification: {late} of {len(COLLINEAR)} above {S.GAP_TOL:g}, largest gap "
+          f"{gap.max():.3e}, smallest pivot {pivot.min():.3e}, largest (phi - psi) / phi {cert.max():.3e}, largest "
+          f"|r + t - phi| / phi {rt.max():.3e}")
+    assert len(COLLINEAR) == 72 and (pivot > 1e-12).all()
+    assert late <= 24
+    assert (cert <= 1e-9).all() and (cert >= -1e-12).all() and (rt <= 1e-9).all()
+
+
+@pytest.mark.parametrize("k", [1, 3, 6])
+def test_capped_ipm_keeps_the_duality_bound(k):
+    """The iteration cap on the specification: the capped iterate is primal feasible (r + t >= phi) and its reported gap
+    bounds the certificate, phi - psi <= gap (r + t), the conditions tests/test_gpu_model_edges.py puts on the engine."""
+    from test_gpu_model import synthetic
+    from test_gpu_model_edges import problem
+    pc, po, w = problem(400)
+    for a, b in zip((pc, po, w), synthetic("noisy", 400, 0)):
+        assert a.tobytes() == b.tobytes()       # the generator extends synthetic(): the same draws
+    old = S.MAX_IT
+    S.MAX_IT = k
+    try:
+        h, r, t, Z, gap, it = S.solve(pc, po, w, "sdp", 0.5, 0.5)
+    finally:
+        S.MAX_IT = old
+    ph, ps = S.phi(pc, po, w, h, 0.5, 0.5), S.psi(pc, po, w, Z, 0.5, 0.5)
+    print(f"max_iter={k}: gap={gap:.3e} (phi - psi) / phi={(ph - ps) / ph:.3e}")
+    assert it == k and gap > S.GAP_TOL
+    assert r + t >= ph * (1 - 1e-12)
+    assert ph - ps <= gap * (r + t) * (1 + 1e-6) + 1e-9 * ph
+
+
 # ---------------------------------------------------------------- the C ABI
 def header():
     return open(os.path.join(ROOT, "include", "apap_hip.h")).read()
