@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
+from spectral_spec import off_diagonal_f32, pairwise128
 
 NEW_SYMBOLS = ("apap_spectral_weights", "apap_spectral_workspace_bytes", "apap_spectral_device", "apap_spectral_affinity")
 
@@ -105,22 +106,6 @@ def test_argument_errors(native):
     assert rc == native.ERR_INVALID_ARG and "init_ransac" in native.last_error()
 
 
-def off_diagonal_f32(src, dst, affinity_eps):
-    """spectral_method.py:116-123 restated: every step float32, rounded separately, the diagonal set to 0."""
-    src = np.asarray(src, np.float32)
-    dst = np.asarray(dst, np.float32)
-    rcp = np.float32(1 / 2 / (affinity_eps ** 2))
-    ds = src[:, None, :] - src[None, :, :]
-    dd = dst[:, None, :] - dst[None, :, :]
-    s = ds[..., 0] * ds[..., 0] + ds[..., 1] * ds[..., 1]
-    d = dd[..., 0] * dd[..., 0] + dd[..., 1] * dd[..., 1]
-    t = s - d
-    off = np.maximum(np.float32(4.5) - (t * t) * rcp, np.float32(0))
-    np.fill_diagonal(off, 0)
-    assert off.dtype == np.float32
-    return off
-
-
 @pytest.mark.parametrize("path", fixtures_with_m(), ids=os.path.basename)
 def test_off_diagonal_restatement_matches_reference_bit_for_bit(path):
     g = np.load(path)
@@ -144,14 +129,6 @@ def test_fundamental_matches_utils_formula():
     F = fundamental(np.eye(3), np.eye(3), np.zeros(3, np.float32), np.float32([1, 0, 0]), K)
     x = np.array([100.0, 50.0, 1.0])
     assert abs(x @ F @ x) < 1e-12          # a pure x-translation: a point and itself lie on one epipolar line
-
-
-def pairwise128(a):
-    """numpy's float32 pairwise sum of 128 terms (8 accumulators) along the last axis, as the set-up kernel sums."""
-    r = a[..., :8].copy()
-    for i in range(8, 128, 8):
-        r = r + a[..., i:i + 8]
-    return ((r[..., 0] + r[..., 1]) + (r[..., 2] + r[..., 3])) + ((r[..., 4] + r[..., 5]) + (r[..., 6] + r[..., 7]))
 
 
 @pytest.mark.parametrize("path", fixtures_with_m(), ids=os.path.basename)
