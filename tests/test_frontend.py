@@ -281,34 +281,48 @@ def test_oracle_ransac_recovers_inliers_and_model():
     assert H is None and mask.sum() == 0
 
 
+def ransac_device(native, src, dst, thresh, K, seed, fill=0, work=None):
+    """One apap_ransac_device call on fresh outputs: ``dict(H, counts, result, mask, H_best, work)`` with the table of all K
+    hypotheses and their inlier counts read back from the workspace (``fill``: the byte a fresh workspace holds on entry)."""
+    import torch
+    dev = torch.device("cuda:0")
+    n = len(src)
+    d_src, d_dst = torch.from_numpy(src).to(dev), torch.from_numpy(dst).to(dev)
+    wb = native.lib().apap_ransac_workspace_bytes(n, K)
+    if work is None:
+        work = torch.full((wb,), fill, dtype=torch.uint8, device=dev)
+    Hb = torch.zeros(9, dtype=torch.float64, device=dev)
+    mask = torch.zeros(n, dtype=torch.uint8, device=dev)
+    res = torch.zeros(2, dtype=torch.int32, device=dev)
+    native.check(native.lib().apap_ransac_device(None, d_src.data_ptr(), d_dst.data_ptr(), n, thresh, K, ctypes.c_ulonglong(seed),
+                                                 Hb.data_ptr(), mask.data_ptr(), res.data_ptr(), work.data_ptr(), wb,
+                                                 ctypes.c_void_p(0)))
+    torch.cuda.synchronize()
+    raw = work.cpu().numpy()
+    return dict(H=raw[:K * 72].view(np.float64).reshape(K, 9), counts=raw[K * 72:K * 76].view(np.int32), result=res.cpu().tolist(),
+                mask=mask.cpu().numpy(), H_best=Hb.cpu().numpy(), work=work)
+
+
+def assert_ransac_equals_core(got, core):
+    """Sampler, minimal solver, inlier counts, winner and mask of ``ransac_device`` against F.ransac_core: bit for bit."""
+    H_all = got["H"]
+    assert np.array_equal(np.isnan(H_all), np.isnan(core["H"]))
+    same = np.nan_to_num(H_all) == np.nan_to_num(core["H"])
+    assert same.all(), f"{int((~same).sum())} of {same.size} hypothesis entries differ"
+    assert np.array_equal(got["counts"], core["counts"])
+    assert got["result"] == [core["best"], core["count"]]
+    assert np.array_equal(got["mask"], core["mask"])
+    assert np.array_equal(got["H_best"], core["H"][core["best"]], equal_nan=True)    # NaN only where the oracle's winner is NaN
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,outliers,seed", [(600, 0.3, 0), (2000, 0.5, 1), (8, 0.0, 2), (4, 0.0, 3), (57, 0.2, 4)])
 def test_ransac_device_half_is_bit_identical_to_the_oracle(native, n, outliers, seed):
     """Sampler, minimal solver, inlier counts, winner and mask: equal bit for bit."""
-    import torch
-    dev = torch.device("cuda:0")
     src, dst, _, _ = ransac_case(n, outliers, seed=seed)
     K = 512
     core = F.ransac_core(src, dst, 5.0, K, F.RANSAC_SEED)
-    d_src, d_dst = torch.from_numpy(src).to(dev), torch.from_numpy(dst).to(dev)
-    wb = native.lib().apap_ransac_workspace_bytes(n, K)
-    work = torch.zeros(wb, dtype=torch.uint8, device=dev)
-    Hb = torch.zeros(9, dtype=torch.float64, device=dev)
-    mask = torch.zeros(n, dtype=torch.uint8, device=dev)
-    res = torch.zeros(2, dtype=torch.int32, device=dev)
-    native.check(native.lib().apap_ransac_device(None, d_src.data_ptr(), d_dst.data_ptr(), n, 5.0, K, ctypes.c_ulonglong(F.RANSAC_SEED),
-                                                 Hb.data_ptr(), mask.data_ptr(), res.data_ptr(), work.data_ptr(), wb,
-                                                 ctypes.c_void_p(0)))
-    torch.cuda.synchronize()
-    H_all = work.cpu().numpy()[:K * 72].view(np.float64).reshape(K, 9)
-    counts = work.cpu().numpy()[K * 72:K * 76].view(np.int32)
-    assert np.array_equal(np.isnan(H_all), np.isnan(core["H"]))
-    same = np.nan_to_num(H_all) == np.nan_to_num(core["H"])
-    assert same.all(), f"{int((~same).sum())} of {same.size} hypothesis entries differ"
-    assert np.array_equal(counts, core["counts"])
-    assert res.cpu().tolist() == [core["best"], core["count"]]
-    assert np.array_equal(mask.cpu().numpy(), core["mask"])
-    assert np.array_equal(Hb.cpu().numpy(), core["H"][core["best"]])
+    assert_ransac_equals_core(ransac_device(native, src, dst, 5.0, K, F.RANSAC_SEED), core)
 
 
 @pytest.mark.gpu
