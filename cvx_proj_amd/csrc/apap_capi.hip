@@ -19,24 +19,12 @@ namespace {
 
 thread_local char g_err[512] = "";
 
-#define APAP_HIP_TRY(call)                                                              \
-    do {                                                                                \
-        const hipError_t e_ = (call);                                                   \
-        if (e_ != hipSuccess) return apap::fail(APAP_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
 using namespace apap;   // DevSlot, S_* slot names
 
 // The device buffers that host-buffer calls reuse live in the caller's context.  Calls made with
 // a NULL context share this one pool (a cache: no option or result depends on it) and are
 // serialised on its mutex - the reference is single-threaded, ctypes releases the GIL, so guard.
 apap_ctx g_shared;
-
-struct PoolLock {
-    apap_ctx *pool;
-    std::unique_lock<std::mutex> lock;
-    explicit PoolLock(apap_ctx *ctx) : pool(ctx ? ctx : &g_shared), lock(pool->mu) {}
-};
 
 int slot_get(apap_ctx *pool, int which, size_t bytes, int dev, void **out) {
     DevSlot &s = pool->slots[which];
@@ -49,7 +37,8 @@ int slot_get(apap_ctx *pool, int which, size_t bytes, int dev, void **out) {
     if (!s.ptr) {
         // +16: the warp gather reads one dword at a 3-byte pixel and may touch 1 byte
         // past the image; keep that inside the allocation for pooled buffers.
-        APAP_HIP_TRY(hipMalloc(&s.ptr, bytes + 16));
+        const hipError_t e = hipMalloc(&s.ptr, bytes + 16);
+        if (e != hipSuccess) return apap::hip_fail((int)e, "hipMalloc of a pooled buffer");
         s.cap = bytes;
         s.dev = dev;
     }
@@ -59,7 +48,7 @@ int slot_get(apap_ctx *pool, int which, size_t bytes, int dev, void **out) {
 
 int select_device(int device, int *chosen) {
     int count = 0;
-    const hipError_t e = hipGetDeviceCount(&count);
+    hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count < 1) {
         (void)hipGetLastError();
         return apap::fail(APAP_ERR_NO_DEVICE,
@@ -68,20 +57,123 @@ int select_device(int device, int *chosen) {
     }
     if (device >= count) return apap::fail(APAP_ERR_NO_DEVICE, "device %d requested, %d visible", device, count);
     if (device >= 0) {
-        APAP_HIP_TRY(hipSetDevice(device));
+        if ((e = hipSetDevice(device)) != hipSuccess) return apap::hip_fail((int)e, "hipSetDevice");
         *chosen = device;
     } else {
-        APAP_HIP_TRY(hipGetDevice(chosen));
+        if ((e = hipGetDevice(chosen)) != hipSuccess) return apap::hip_fail((int)e, "hipGetDevice");
     }
     return APAP_OK;
 }
 
-// Host-buffer calls enqueue copies from buffers they own (std::vector, stack arrays) on the null
-// stream; whatever way the function is left, the stream is drained before those buffers die.
-// Declare it AFTER the buffers it protects.
-struct SyncOnExit {
-    ~SyncOnExit() { (void)hipStreamSynchronize(nullptr); }
+// Bytes [at, at + bytes) of a pooled buffer.  The address is read from the slot when the part is used, so a part may
+// be taken before its slot is allocated.
+struct Part {
+    void *const *base;
+    size_t at, bytes;
+    template <class T>
+    T *as() const { return (T *)((char *)*base + at); }
+    Part first(size_t n) const { return Part{base, at, n}; }   // its leading n bytes
 };
+
+// The parts of one pooled buffer, each on a 256-byte boundary.  A part may be empty (an output the caller did not ask
+// for): it keeps its place in the order and takes no room.
+struct Layout {
+    int which;
+    void *const *base;
+    size_t total = 0;
+    Part take(size_t bytes) {
+        const Part p{base, total, bytes};
+        total += (bytes + 255) / 256 * 256;
+        return p;
+    }
+};
+
+// One synchronous host-buffer call.  It holds the pool's lock and the selected device, hands out the pooled slots and
+// enqueues copies on the null stream.  The first failure is kept: every later slot, copy and wait() does nothing and
+// rc() returns it, so a call checks rc() once before it launches and returns wait() at its end.
+// Whatever way the call is left, the stream is drained before the lock is released (the body of the destructor runs
+// before the members go): no copy into or out of host memory outlives the call, and the next holder of the pool finds
+// its buffers idle.  Host buffers of the call's own that a copy reads or writes (std::vector, stack variables) are
+// declared BEFORE the HostCall, so that they die after it.
+class HostCall {
+  public:
+    explicit HostCall(apap_ctx *ctx) : pool_(ctx ? ctx : &g_shared), lock_(pool_->mu) {}
+    ~HostCall() {
+        if (busy_) (void)hipStreamSynchronize(nullptr);
+    }
+    HostCall(const HostCall &) = delete;
+    HostCall &operator=(const HostCall &) = delete;
+
+    int select(int device) { return rc_ = select_device(device, &dev_); }
+    apap_ctx *pool() const { return pool_; }
+    int dev() const { return dev_; }
+    int rc() const { return rc_; }
+
+    Part slot(int which, size_t bytes) {
+        void *p;
+        if (!rc_) rc_ = slot_get(pool_, which, bytes, dev_, &p);
+        return Part{&pool_->slots[which].ptr, 0, bytes};
+    }
+    Layout layout(int which) const { return Layout{which, &pool_->slots[which].ptr}; }
+    void alloc(const Layout &l) { (void)slot(l.which, l.total); }
+
+    void up(const Part &to, const void *host) {
+        if (!rc_) check(hipMemcpyAsync(to.as<void>(), host, to.bytes, hipMemcpyHostToDevice, (hipStream_t)stream()), "host-buffer call: upload");
+    }
+    void down(void *host, const Part &from) {
+        if (!rc_) check(hipMemcpyAsync(host, from.as<void>(), from.bytes, hipMemcpyDeviceToHost, (hipStream_t)stream()), "host-buffer call: download");
+    }
+    void zero(const Part &p) {
+        if (!rc_) check(hipMemsetAsync(p.as<void>(), 0, p.bytes, (hipStream_t)stream()), "host-buffer call: zero fill");
+    }
+    // The stream of the call, for the "_device" entry points: the null stream.  Whoever asks for it enqueues on it, and
+    // the drain relies on the converse: nothing in a host-buffer call passes a literal nullptr as a stream, or enqueues
+    // on the null stream in any other way than through this object.
+    void *stream() {
+        busy_ = true;
+        return nullptr;
+    }
+    int wait() {
+        if (rc_) return rc_;
+        check(hipStreamSynchronize(nullptr), "host-buffer call: synchronize");
+        if (!rc_) busy_ = false;
+        return rc_;
+    }
+
+  private:
+    void check(hipError_t e, const char *what) {
+        if (e != hipSuccess) rc_ = apap::hip_fail((int)e, what);
+    }
+    apap_ctx *pool_;
+    std::unique_lock<std::mutex> lock_;
+    int dev_ = -1, rc_ = APAP_OK;
+    bool busy_ = false;   // something was enqueued on the null stream since the last completed wait()
+};
+
+// offset[0 .. count] relative to offset[0]: the device arrays of a batch start at its first pair or image
+std::vector<int> relative_offsets(const int *offset, int count) {
+    std::vector<int> rel((size_t)count + 1);
+    for (int p = 0; p <= count; ++p) rel[p] = offset[p] - offset[0];
+    return rel;
+}
+
+// The images of a batch side by side in S_IMG: their parts, the slot allocated ...
+std::vector<Part> image_parts(HostCall &call, const int *heights, const int *widths, const int *channels, int n_images) {
+    Layout lay = call.layout(S_IMG);
+    std::vector<Part> parts((size_t)n_images, Part{});
+    for (int m = 0; m < n_images; ++m) parts[m] = lay.take((size_t)heights[m] * widths[m] * channels[m]);
+    call.alloc(lay);
+    return parts;
+}
+// ... and one upload each; returns their device addresses.
+std::vector<const uint8_t *> upload_images(HostCall &call, const std::vector<Part> &parts, const uint8_t *const *imgs) {
+    std::vector<const uint8_t *> d_imgs(parts.size(), nullptr);
+    for (size_t m = 0; m < parts.size() && !call.rc(); ++m) {
+        d_imgs[m] = parts[m].as<const uint8_t>();
+        call.up(parts[m], imgs[m]);
+    }
+    return d_imgs;
+}
 
 int status_to_code(int status, const char *who) {
     if (status & APAP_STATUS_SINGULAR) return apap::fail(APAP_ERR_SINGULAR, "%s: Singular matrix", who);
@@ -120,27 +212,25 @@ int apap_device_count(void) {
 }
 
 // The weight tensor of `cells` cells, streamed through a bounded device buffer (it is 8 n bytes per cell):
-// d_table / d_vert are resident, W_out is the host destination.  1 GiB of device staging by default;
+// `table` / `vert` are resident, W_out is the host destination.  1 GiB of device staging by default;
 // APAP_OPT_WEIGHT_CHUNK_KB lets tests force several chunks.
-static int stream_weights(apap_ctx *ctx, apap_ctx *pool, int dev, const void *d_table, int n, const void *d_vert, int cells,
-                          double gamma, double sigma, double *W_out) {
+static int stream_weights(apap_ctx *ctx, HostCall &call, const Part &table, int n, const Part &vert, int cells, double gamma,
+                          double sigma, double *W_out) {
     const size_t max_bytes = (size_t)apap::opt(ctx, APAP_OPT_WEIGHT_CHUNK_KB) << 10;
     int chunk = (int)(max_bytes / ((size_t)n * sizeof(double)));
     if (chunk < 1) chunk = 1;
     if (chunk > cells) chunk = cells;
-    void *d_W;
-    int rc;
-    if ((rc = slot_get(pool, S_W, (size_t)chunk * n * sizeof(double), dev, &d_W))) return rc;
-    for (int c0 = 0; c0 < cells; c0 += chunk) {
+    const Part W = call.slot(S_W, (size_t)chunk * n * sizeof(double));
+    int rc = call.rc();
+    for (int c0 = 0; !rc && c0 < cells; c0 += chunk) {
         const int nc = cells - c0 < chunk ? cells - c0 : chunk;
-        rc = apap_weights_device(ctx, (const double *)d_table, n, (const double *)d_vert + (size_t)2 * c0, nc, gamma,
-                                 sigma, (double *)d_W, nullptr);
+        rc = apap_weights_device(ctx, table.as<const double>(), n, vert.as<const double>() + (size_t)2 * c0, nc, gamma, sigma,
+                                 W.as<double>(), call.stream());
         if (rc) return rc;
-        APAP_HIP_TRY(hipMemcpyAsync(W_out + (size_t)c0 * n, d_W, (size_t)nc * n * sizeof(double),
-                                    hipMemcpyDeviceToHost, nullptr));
-        APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+        call.down(W_out + (size_t)c0 * n, W.first((size_t)nc * n * sizeof(double)));
+        rc = call.wait();
     }
-    return APAP_OK;
+    return rc;
 }
 
 int apap_local_weights(apap_ctx *ctx, const float *src, int n, const double *vertices, int cells, double gamma,
@@ -152,23 +242,21 @@ int apap_local_weights_pts(apap_ctx *ctx, const void *src, int src_f64, int n, c
                            double sigma, double *W_out, int device) {
     if (!src || !vertices || !W_out) return apap::fail(APAP_ERR_INVALID_ARG, "apap_local_weights: null argument");
     if (n < 1 || cells < 1) return apap::fail(APAP_ERR_INVALID_ARG, "apap_local_weights: n=%d cells=%d", n, cells);
-    PoolLock pl(ctx);
-    int dev;
-    int rc = select_device(device, &dev);
+    std::vector<double> host_table;   // an upload reads it
+    HostCall call(ctx);
+    int rc = call.select(device);
     if (rc) return rc;
     // the weight kernel reads a keypoint's (x, y) from columns 30, 31 of its table row
-    std::vector<double> table((size_t)n * APAP_TABLE_STRIDE, 0.0);
+    host_table.assign((size_t)n * APAP_TABLE_STRIDE, 0.0);
     for (int k = 0; k < n; ++k) {
-        table[(size_t)k * APAP_TABLE_STRIDE + 30] = src_f64 ? ((const double *)src)[2 * k] : (double)((const float *)src)[2 * k];
-        table[(size_t)k * APAP_TABLE_STRIDE + 31] = src_f64 ? ((const double *)src)[2 * k + 1] : (double)((const float *)src)[2 * k + 1];
+        host_table[(size_t)k * APAP_TABLE_STRIDE + 30] = src_f64 ? ((const double *)src)[2 * k] : (double)((const float *)src)[2 * k];
+        host_table[(size_t)k * APAP_TABLE_STRIDE + 31] = src_f64 ? ((const double *)src)[2 * k + 1] : (double)((const float *)src)[2 * k + 1];
     }
-    const SyncOnExit drain;   // the async copy below reads `table`
-    void *d_table, *d_vert;
-    if ((rc = slot_get(pl.pool, S_TABLE, table.size() * sizeof(double), dev, &d_table))) return rc;
-    if ((rc = slot_get(pl.pool, S_VERT, (size_t)cells * 2 * sizeof(double), dev, &d_vert))) return rc;
-    APAP_HIP_TRY(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d_vert, vertices, (size_t)cells * 2 * sizeof(double), hipMemcpyHostToDevice, nullptr));
-    return stream_weights(ctx, pl.pool, dev, d_table, n, d_vert, cells, gamma, sigma, W_out);
+    const Part table = call.slot(S_TABLE, host_table.size() * sizeof(double));
+    const Part vert = call.slot(S_VERT, (size_t)cells * 2 * sizeof(double));
+    call.up(table, host_table.data());
+    call.up(vert, vertices);
+    return stream_weights(ctx, call, table, n, vert, cells, gamma, sigma, W_out);
 }
 
 int apap_local_homography(apap_ctx *ctx, const float *src, const float *dst, int n, const double *vertices,
@@ -184,9 +272,10 @@ int apap_local_homography_pts(apap_ctx *ctx, const void *src, int src_f64, const
     if (n < 2 || mesh_rows < 1 || mesh_cols < 1)
         return apap::fail(APAP_ERR_INVALID_ARG, "apap_local_homography: n=%d mesh=%dx%d", n, mesh_rows, mesh_cols);
     if ((long long)mesh_rows * mesh_cols > (1ll << 30)) return apap::fail(APAP_ERR_INVALID_ARG, "apap_local_homography: mesh too large");
-    PoolLock pl(ctx);
-    int dev;
-    int rc = select_device(device, &dev);
+    std::vector<double> host_table;   // uploads read these two
+    double host_denorm[APAP_DENORM_DOUBLES];
+    HostCall call(ctx);
+    int rc = call.select(device);
     if (rc) return rc;
 
     // once-per-pair set-up on the host (apap.py:132-145)
@@ -199,32 +288,28 @@ int apap_local_homography_pts(apap_ctx *ctx, const void *src, int src_f64, const
     if (rc) return rc;
     if ((rc = apap_host_dlt_rows_pts(cf1.data(), cf2.data(), n, src_f64 || dst_f64, aa.data()))) return rc;
     for (size_t i = 0; i < (size_t)2 * n; ++i) src64[i] = src_f64 ? ((const double *)src)[i] : (double)((const float *)src)[i];
-    std::vector<double> table((size_t)n * APAP_TABLE_STRIDE);
-    double denorm[APAP_DENORM_DOUBLES];
-    rc = apap::opt(ctx, APAP_OPT_MOMENTS) == 24 ? apap_host_build_table24(src64.data(), aa.data(), n, table.data())
-                                                : apap_host_build_table_rows(src64.data(), aa.data(), n, table.data());
+    host_table.resize((size_t)n * APAP_TABLE_STRIDE);
+    rc = apap::opt(ctx, APAP_OPT_MOMENTS) == 24 ? apap_host_build_table24(src64.data(), aa.data(), n, host_table.data())
+                                                : apap_host_build_table_rows(src64.data(), aa.data(), n, host_table.data());
     if (rc) return rc;
-    if ((rc = apap_host_build_denorm(iC2, C1, iN2, N1, denorm))) return rc;
-    const SyncOnExit drain;   // the async copies below read `table` and `denorm`
+    if ((rc = apap_host_build_denorm(iC2, C1, iN2, N1, host_denorm))) return rc;
 
     const int cells = mesh_rows * mesh_cols;
-    const size_t work_bytes = apap_solve_workspace_bytes(ctx, n, cells);
-    void *d_table, *d_vert, *d_denorm, *d_H, *d_work;
-    if ((rc = slot_get(pl.pool, S_TABLE, table.size() * sizeof(double), dev, &d_table))) return rc;
-    if ((rc = slot_get(pl.pool, S_VERT, (size_t)cells * 2 * sizeof(double), dev, &d_vert))) return rc;
-    if ((rc = slot_get(pl.pool, S_DENORM, sizeof(denorm), dev, &d_denorm))) return rc;
-    if ((rc = slot_get(pl.pool, S_H, (size_t)cells * 9 * sizeof(float), dev, &d_H))) return rc;
-    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-    APAP_HIP_TRY(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d_vert, vertices, (size_t)cells * 2 * sizeof(double), hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d_denorm, denorm, sizeof(denorm), hipMemcpyHostToDevice, nullptr));
-    rc = apap_solve_device(ctx, (const double *)d_table, n, (const double *)d_vert, cells, gamma, sigma,
-                           (const double *)d_denorm, (float *)d_H, d_work, work_bytes, nullptr);
+    const Part table = call.slot(S_TABLE, host_table.size() * sizeof(double));
+    const Part vert = call.slot(S_VERT, (size_t)cells * 2 * sizeof(double));
+    const Part denorm = call.slot(S_DENORM, sizeof(host_denorm));
+    const Part H = call.slot(S_H, (size_t)cells * 9 * sizeof(float));
+    const Part work = call.slot(S_WORK, apap_solve_workspace_bytes(ctx, n, cells));
+    call.up(table, host_table.data());
+    call.up(vert, vertices);
+    call.up(denorm, host_denorm);
+    if ((rc = call.rc())) return rc;
+    rc = apap_solve_device(ctx, table.as<const double>(), n, vert.as<const double>(), cells, gamma, sigma, denorm.as<const double>(),
+                           H.as<float>(), work.as<void>(), work.bytes, call.stream());
     if (rc) return rc;
-    APAP_HIP_TRY(hipMemcpyAsync(H_out, d_H, (size_t)cells * 9 * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    if (W_out && (rc = stream_weights(ctx, pl.pool, dev, d_table, n, d_vert, cells, gamma, sigma, W_out))) return rc;
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
-    return APAP_OK;
+    call.down(H_out, H);
+    if (W_out && (rc = stream_weights(ctx, call, table, n, vert, cells, gamma, sigma, W_out))) return rc;
+    return call.wait();
 }
 
 // ---- apap_local_warp / apap_local_stitch with PCIe overlapped ---------------------------------------
@@ -247,6 +332,13 @@ int apap_local_homography_pts(apap_ctx *ctx, const void *src, int src_f64, const
 // perspective denominator that changes sign inside a cell) wait for the whole image: the order of the
 // transfers changes, never the bytes of the canvas.
 namespace {
+
+// (the overlapped path has three streams of its own and keeps its own error returns and its own drain, DrainStreams)
+#define APAP_HIP_TRY(call)                                                              \
+    do {                                                                                \
+        const hipError_t e_ = (call);                                                   \
+        if (e_ != hipSuccess) return apap::fail(APAP_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
+    } while (0)
 
 struct PinGuard {       // hipHostRegister for the duration of a call
     void *p = nullptr;
@@ -487,69 +579,70 @@ static int warp_common(apap_ctx *ctx, const uint8_t *img, int img_h, int img_w, 
     if (!Hfwd || !mesh_w || !mesh_h) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
     if (mesh_rows < 1 || mesh_cols < 1 || n_w < 1 || n_h < 1 || final_w < 1 || final_h < 1)
         return apap::fail(APAP_ERR_INVALID_ARG, "%s: bad size", who);
-    PoolLock pl(ctx);
-    int dev;
-    int rc = select_device(device, &dev);
+    int status = 0;   // the last download writes it
+    HostCall call(ctx);
+    int rc = call.select(device);
     if (rc) return rc;
     if (!coords && h_bytes == sizeof(float) && apap::opt(ctx, APAP_OPT_OVERLAP_PCIE)) {
         bool done = false;
-        rc = warp_overlapped(ctx, pl.pool, dev, img, img_h, img_w, center, center_h, center_w, (const float *)Hfwd, mesh_rows,
-                             mesh_cols, mesh_w, n_w, mesh_h, n_h, final_w, final_h, off_x, off_y, out, (float *)Hinv_out, who, &done);
+        rc = warp_overlapped(ctx, call.pool(), call.dev(), img, img_h, img_w, center, center_h, center_w, (const float *)Hfwd,
+                             mesh_rows, mesh_cols, mesh_w, n_w, mesh_h, n_h, final_w, final_h, off_x, off_y, out, (float *)Hinv_out,
+                             who, &done);
         if (rc || done) return rc;
     }
     const int cells = mesh_rows * mesh_cols;
-    const size_t work_bytes = apap_warp_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h);
     const size_t pixels = (size_t)final_w * final_h;
-    void *d_H, *d_mw, *d_mh, *d_work, *d_status, *d_hinv = nullptr, *d_img = nullptr, *d_out = nullptr;
-    if ((rc = slot_get(pl.pool, S_H, (size_t)cells * 9 * h_bytes, dev, &d_H))) return rc;
-    if ((rc = slot_get(pl.pool, S_MESHW, (size_t)n_w * sizeof(double), dev, &d_mw))) return rc;
-    if ((rc = slot_get(pl.pool, S_MESHH, (size_t)n_h * sizeof(double), dev, &d_mh))) return rc;
-    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-    if ((rc = slot_get(pl.pool, S_STATUS, sizeof(int), dev, &d_status))) return rc;
-    if (Hinv_out && (rc = slot_get(pl.pool, S_HINV, (size_t)cells * 9 * h_bytes, dev, &d_hinv))) return rc;
-    const SyncOnExit drain;   // `status` below is a stack variable the last copy writes
-    APAP_HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int), nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d_H, Hfwd, (size_t)cells * 9 * h_bytes, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d_mw, mesh_w, (size_t)n_w * sizeof(double), hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d_mh, mesh_h, (size_t)n_h * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    const Part H = call.slot(S_H, (size_t)cells * 9 * h_bytes);
+    const Part mw = call.slot(S_MESHW, (size_t)n_w * sizeof(double));
+    const Part mh = call.slot(S_MESHH, (size_t)n_h * sizeof(double));
+    const Part work = call.slot(S_WORK, apap_warp_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h));
+    const Part d_status = call.slot(S_STATUS, sizeof(int));
+    const Part hinv = Hinv_out ? call.slot(S_HINV, H.bytes) : Part{};
+    void *d_hinv = Hinv_out ? hinv.as<void>() : nullptr;
+    call.zero(d_status);
+    call.up(H, Hfwd);
+    call.up(mw, mesh_w);
+    call.up(mh, mesh_h);
     if (coords) {
-        if ((rc = slot_get(pl.pool, S_OUT, pixels * 2 * sizeof(double), dev, &d_out))) return rc;
-        rc = apap_warp_coords_device(ctx, (const float *)d_H, mesh_rows, mesh_cols, (const double *)d_mw, n_w,
-                                     (const double *)d_mh, n_h, final_w, final_h, off_x, off_y, (double *)d_out,
-                                     d_work, work_bytes, (int *)d_status, nullptr);
+        const Part xy = call.slot(S_OUT, pixels * 2 * sizeof(double));
+        if ((rc = call.rc())) return rc;
+        rc = apap_warp_coords_device(ctx, H.as<const float>(), mesh_rows, mesh_cols, mw.as<const double>(), n_w,
+                                     mh.as<const double>(), n_h, final_w, final_h, off_x, off_y, xy.as<double>(), work.as<void>(),
+                                     work.bytes, d_status.as<int>(), call.stream());
         if (rc) return rc;
-        APAP_HIP_TRY(hipMemcpyAsync(coords, d_out, pixels * 2 * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+        call.down(coords, xy);
     } else {
-        const size_t img_bytes = (size_t)img_h * img_w * 3;
-        if ((rc = slot_get(pl.pool, S_IMG, img_bytes, dev, &d_img))) return rc;
-        if ((rc = slot_get(pl.pool, S_OUT, pixels * 3, dev, &d_out))) return rc;
-        APAP_HIP_TRY(hipMemcpyAsync(d_img, img, img_bytes, hipMemcpyHostToDevice, nullptr));
+        const Part d_img = call.slot(S_IMG, (size_t)img_h * img_w * 3);
+        const Part d_out = call.slot(S_OUT, pixels * 3);
+        call.up(d_img, img);
+        Part d_center{};
         if (center) {
-            void *d_center;
-            const size_t cbytes = (size_t)center_h * center_w * 3;
-            if ((rc = slot_get(pl.pool, S_AUX, cbytes, dev, &d_center))) return rc;
-            APAP_HIP_TRY(hipMemcpyAsync(d_center, center, cbytes, hipMemcpyHostToDevice, nullptr));
-            rc = apap_stitch_device(ctx, (const uint8_t *)d_img, img_h, img_w, (const uint8_t *)d_center, center_h, center_w,
-                                    (const float *)d_H, mesh_rows, mesh_cols, (const double *)d_mw, n_w,
-                                    (const double *)d_mh, n_h, final_w, final_h, off_x, off_y, (uint8_t *)d_out,
-                                    (float *)d_hinv, d_work, work_bytes, (int *)d_status, nullptr);
+            d_center = call.slot(S_AUX, (size_t)center_h * center_w * 3);
+            call.up(d_center, center);
+        }
+        if ((rc = call.rc())) return rc;
+        if (center) {
+            rc = apap_stitch_device(ctx, d_img.as<const uint8_t>(), img_h, img_w, d_center.as<const uint8_t>(), center_h, center_w,
+                                    H.as<const float>(), mesh_rows, mesh_cols, mw.as<const double>(), n_w, mh.as<const double>(),
+                                    n_h, final_w, final_h, off_x, off_y, d_out.as<uint8_t>(), (float *)d_hinv, work.as<void>(),
+                                    work.bytes, d_status.as<int>(), call.stream());
         } else if (h_bytes == sizeof(double)) {
-            rc = apap_warp_f64_device(ctx, (const uint8_t *)d_img, img_h, img_w, (const double *)d_H, mesh_rows, mesh_cols,
-                                      (const double *)d_mw, n_w, (const double *)d_mh, n_h, final_w, final_h, off_x, off_y,
-                                      (uint8_t *)d_out, (double *)d_hinv, d_work, work_bytes, (int *)d_status, nullptr);
+            rc = apap_warp_f64_device(ctx, d_img.as<const uint8_t>(), img_h, img_w, H.as<const double>(), mesh_rows, mesh_cols,
+                                      mw.as<const double>(), n_w, mh.as<const double>(), n_h, final_w, final_h, off_x, off_y,
+                                      d_out.as<uint8_t>(), (double *)d_hinv, work.as<void>(), work.bytes, d_status.as<int>(),
+                                      call.stream());
         } else {
-            rc = apap_warp_device(ctx, (const uint8_t *)d_img, img_h, img_w, (const float *)d_H, mesh_rows, mesh_cols,
-                                  (const double *)d_mw, n_w, (const double *)d_mh, n_h, final_w, final_h, off_x, off_y,
-                                  (uint8_t *)d_out, (float *)d_hinv, d_work, work_bytes, (int *)d_status, nullptr);
+            rc = apap_warp_device(ctx, d_img.as<const uint8_t>(), img_h, img_w, H.as<const float>(), mesh_rows, mesh_cols,
+                                  mw.as<const double>(), n_w, mh.as<const double>(), n_h, final_w, final_h, off_x, off_y,
+                                  d_out.as<uint8_t>(), (float *)d_hinv, work.as<void>(), work.bytes, d_status.as<int>(),
+                                  call.stream());
         }
         if (rc) return rc;
-        APAP_HIP_TRY(hipMemcpyAsync(out, d_out, pixels * 3, hipMemcpyDeviceToHost, nullptr));
-        if (Hinv_out)
-            APAP_HIP_TRY(hipMemcpyAsync(Hinv_out, d_hinv, (size_t)cells * 9 * h_bytes, hipMemcpyDeviceToHost, nullptr));
+        call.down(out, d_out);
+        if (Hinv_out) call.down(Hinv_out, hinv);
     }
-    int status = 0;
-    APAP_HIP_TRY(hipMemcpyAsync(&status, d_status, sizeof(int), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    call.down(&status, d_status);
+    if ((rc = call.wait())) return rc;
     return status_to_code(status, who);
 }
 
@@ -594,67 +687,58 @@ int apap_warp_coords(apap_ctx *ctx, const float *Hfwd, int mesh_rows, int mesh_c
 
 int apap_invert_normalize_flatten(apap_ctx *ctx, const float *H, int cells, double *out, int device) {
     if (!H || !out || cells < 1) return apap::fail(APAP_ERR_INVALID_ARG, "apap_invert_normalize_flatten: bad argument");
-    PoolLock pl(ctx);
-    int dev;
-    int rc = select_device(device, &dev);
+    int status = 0;   // the last download writes it
+    HostCall call(ctx);
+    int rc = call.select(device);
     if (rc) return rc;
-    void *d_H, *d_out, *d_status;
-    if ((rc = slot_get(pl.pool, S_H, (size_t)cells * 9 * sizeof(float), dev, &d_H))) return rc;
-    if ((rc = slot_get(pl.pool, S_AUX, (size_t)cells * 9 * sizeof(double), dev, &d_out))) return rc;
-    if ((rc = slot_get(pl.pool, S_STATUS, sizeof(int), dev, &d_status))) return rc;
-    int status = 0;
-    const SyncOnExit drain;
-    APAP_HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int), nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d_H, H, (size_t)cells * 9 * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    rc = apap_flatten_device(ctx, (const float *)d_H, cells, (double *)d_out, (int *)d_status, nullptr);
+    const Part d_H = call.slot(S_H, (size_t)cells * 9 * sizeof(float));
+    const Part d_out = call.slot(S_AUX, (size_t)cells * 9 * sizeof(double));
+    const Part d_status = call.slot(S_STATUS, sizeof(int));
+    call.zero(d_status);
+    call.up(d_H, H);
+    if ((rc = call.rc())) return rc;
+    rc = apap_flatten_device(ctx, d_H.as<const float>(), cells, d_out.as<double>(), d_status.as<int>(), call.stream());
     if (rc) return rc;
-    APAP_HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)cells * 9 * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(&status, d_status, sizeof(int), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    call.down(out, d_out);
+    call.down(&status, d_status);
+    if ((rc = call.wait())) return rc;
     return status_to_code(status, "apap_invert_normalize_flatten");
 }
 
 int apap_uniform_blend(apap_ctx *ctx, const uint8_t *img1, const uint8_t *img2, int h, int w, uint8_t *out,
                        int device) {
     if (!img1 || !img2 || !out || h < 1 || w < 1) return apap::fail(APAP_ERR_INVALID_ARG, "apap_uniform_blend: bad argument");
-    PoolLock pl(ctx);
-    int dev;
-    int rc = select_device(device, &dev);
+    HostCall call(ctx);
+    int rc = call.select(device);
     if (rc) return rc;
     const size_t bytes = (size_t)h * w * 3;
-    void *d_a, *d_b, *d_o;
-    if ((rc = slot_get(pl.pool, S_IMG, bytes, dev, &d_a))) return rc;
-    if ((rc = slot_get(pl.pool, S_AUX, bytes, dev, &d_b))) return rc;
-    if ((rc = slot_get(pl.pool, S_OUT, bytes, dev, &d_o))) return rc;
-    APAP_HIP_TRY(hipMemcpyAsync(d_a, img1, bytes, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d_b, img2, bytes, hipMemcpyHostToDevice, nullptr));
-    rc = apap_blend_device(ctx, (const uint8_t *)d_a, (const uint8_t *)d_b, h, w, (uint8_t *)d_o, nullptr);
+    const Part a = call.slot(S_IMG, bytes), b = call.slot(S_AUX, bytes), o = call.slot(S_OUT, bytes);
+    call.up(a, img1);
+    call.up(b, img2);
+    if ((rc = call.rc())) return rc;
+    rc = apap_blend_device(ctx, a.as<const uint8_t>(), b.as<const uint8_t>(), h, w, o.as<uint8_t>(), call.stream());
     if (rc) return rc;
-    APAP_HIP_TRY(hipMemcpyAsync(out, d_o, bytes, hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
-    return APAP_OK;
+    call.down(out, o);
+    return call.wait();
 }
 
 int apap_equalize_hist(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, uint8_t *out, int device) {
     if (!img || !out || h < 1 || w < 1 || channels < 1 || channels > 4)
         return apap::fail(APAP_ERR_INVALID_ARG, "apap_equalize_hist: bad argument");
-    PoolLock pl(ctx);
-    int dev;
-    int rc = select_device(device, &dev);
+    HostCall call(ctx);
+    int rc = call.select(device);
     if (rc) return rc;
     const size_t bytes = (size_t)h * w * channels;
-    const size_t work_bytes = apap_equalize_workspace_bytes(channels);
-    void *d_a, *d_o, *d_work;
-    if ((rc = slot_get(pl.pool, S_IMG, bytes, dev, &d_a))) return rc;
-    if ((rc = slot_get(pl.pool, S_OUT, bytes, dev, &d_o))) return rc;
-    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-    APAP_HIP_TRY(hipMemcpyAsync(d_a, img, bytes, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemsetAsync(d_work, 0, work_bytes, nullptr));  // the pooled buffer is shared: zero it per call
-    rc = apap_equalize_hist_device(ctx, (const uint8_t *)d_a, h, w, channels, (uint8_t *)d_o, d_work, work_bytes, nullptr);
+    const Part a = call.slot(S_IMG, bytes), o = call.slot(S_OUT, bytes);
+    const Part work = call.slot(S_WORK, apap_equalize_workspace_bytes(channels));
+    call.up(a, img);
+    call.zero(work);   // the device form wants it zero on entry, and the pool's S_WORK holds what any other call left: per call
+    if ((rc = call.rc())) return rc;
+    rc = apap_equalize_hist_device(ctx, a.as<const uint8_t>(), h, w, channels, o.as<uint8_t>(), work.as<void>(), work.bytes,
+                                   call.stream());
     if (rc) return rc;
-    APAP_HIP_TRY(hipMemcpyAsync(out, d_o, bytes, hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
-    return APAP_OK;
+    call.down(out, o);
+    return call.wait();
 }
 
 int apap_find_homography_ransac(apap_ctx *ctx, const float *src, const float *dst, int n, double thresh, int iterations,
@@ -665,27 +749,26 @@ int apap_find_homography_ransac(apap_ctx *ctx, const float *src, const float *ds
     if (n < 4) return apap::fail(APAP_ERR_INVALID_ARG, "apap_find_homography_ransac: n=%d, a homography needs 4 points", n);
     int result[2] = {0, 0};
     {
-        PoolLock pl(ctx);
-        int dev;
-        int rc = select_device(device, &dev);
+        // This scope ends the call, and so releases the pool, before the re-fit below: apap_local_homography takes the
+        // same pool's mutex, which is not recursive.
+        HostCall call(ctx);
+        int rc = call.select(device);
         if (rc) return rc;
         const size_t pt_bytes = (size_t)n * 2 * sizeof(float);
-        const size_t work_bytes = apap_ransac_workspace_bytes(n, iterations);
-        void *d_src, *d_dst, *d_work, *d_H, *d_mask, *d_result;
-        if ((rc = slot_get(pl.pool, S_IMG, pt_bytes, dev, &d_src))) return rc;
-        if ((rc = slot_get(pl.pool, S_AUX, pt_bytes, dev, &d_dst))) return rc;
-        if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-        if ((rc = slot_get(pl.pool, S_DENORM, 9 * sizeof(double), dev, &d_H))) return rc;
-        if ((rc = slot_get(pl.pool, S_OUT, (size_t)n, dev, &d_mask))) return rc;
-        if ((rc = slot_get(pl.pool, S_STATUS, 2 * sizeof(int), dev, &d_result))) return rc;
-        APAP_HIP_TRY(hipMemcpyAsync(d_src, src, pt_bytes, hipMemcpyHostToDevice, nullptr));
-        APAP_HIP_TRY(hipMemcpyAsync(d_dst, dst, pt_bytes, hipMemcpyHostToDevice, nullptr));
-        rc = apap_ransac_device(ctx, (const float *)d_src, (const float *)d_dst, n, thresh, iterations, seed, (double *)d_H,
-                                (uint8_t *)d_mask, (int *)d_result, d_work, work_bytes, nullptr);
+        const Part d_src = call.slot(S_IMG, pt_bytes), d_dst = call.slot(S_AUX, pt_bytes);
+        const Part work = call.slot(S_WORK, apap_ransac_workspace_bytes(n, iterations));
+        const Part d_H = call.slot(S_DENORM, 9 * sizeof(double));
+        const Part d_mask = call.slot(S_OUT, (size_t)n);
+        const Part d_result = call.slot(S_STATUS, sizeof(result));
+        call.up(d_src, src);
+        call.up(d_dst, dst);
+        if ((rc = call.rc())) return rc;
+        rc = apap_ransac_device(ctx, d_src.as<const float>(), d_dst.as<const float>(), n, thresh, iterations, seed, d_H.as<double>(),
+                                d_mask.as<uint8_t>(), d_result.as<int>(), work.as<void>(), work.bytes, call.stream());
         if (rc) return rc;
-        APAP_HIP_TRY(hipMemcpyAsync(mask_out, d_mask, (size_t)n, hipMemcpyDeviceToHost, nullptr));
-        APAP_HIP_TRY(hipMemcpyAsync(result, d_result, sizeof(result), hipMemcpyDeviceToHost, nullptr));
-        APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+        call.down(mask_out, d_mask);
+        call.down(result, d_result);
+        if ((rc = call.wait())) return rc;
     }
     *inliers_out = result[1];
     if (result[1] < 4) {  // cv.findHomography returns no model
@@ -717,42 +800,33 @@ int apap_find_homography_ransac(apap_ctx *ctx, const float *src, const float *ds
 // second one.
 namespace {
 struct SpecIo {
-    size_t src, dst, c, o, F, Hg, mask, seg, rm, om, info, M, total;
+    Part src, dst, c, o, F, Hg, mask, seg, rm, om, info, M;
 };
-SpecIo spec_io(int n, bool dense) {
-    SpecIo io{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) / 256 * 256;
-        return at;
-    };
+SpecIo spec_io(Layout &io, int n, bool dense) {
     const size_t pts = (size_t)n * 2 * sizeof(float), feats = (size_t)n * APAP_SPECTRAL_DIM * sizeof(float);
-    io.src = take(pts);
-    io.dst = take(pts);
-    io.c = take(feats);
-    io.o = take(feats);
-    io.F = take(9 * sizeof(double));
-    io.Hg = take(9 * sizeof(float));
-    io.mask = take((size_t)n * sizeof(float));
-    io.seg = take((size_t)n * sizeof(double));
-    io.rm = take((size_t)n * sizeof(float));
-    io.om = take((size_t)n * sizeof(float));
-    io.info = take(APAP_SPECTRAL_INFO * sizeof(double));
-    io.M = take(dense ? (size_t)n * n * sizeof(double) : 0);
-    io.total = off;
-    return io;
+    SpecIo p;
+    p.src = io.take(pts);
+    p.dst = io.take(pts);
+    p.c = io.take(feats);
+    p.o = io.take(feats);
+    p.F = io.take(9 * sizeof(double));
+    p.Hg = io.take(9 * sizeof(float));
+    p.mask = io.take((size_t)n * sizeof(float));
+    p.seg = io.take((size_t)n * sizeof(double));
+    p.rm = io.take((size_t)n * sizeof(float));
+    p.om = io.take((size_t)n * sizeof(float));
+    p.info = io.take(APAP_SPECTRAL_INFO * sizeof(double));
+    p.M = io.take(dense ? (size_t)n * n * sizeof(double) : 0);
+    return p;
 }
 
-int spec_upload(char *d, const SpecIo &io, const float *src, const float *dst, const float *c_feats, const float *o_feats, int n,
-                const double *F) {
-    const size_t pts = (size_t)n * 2 * sizeof(float), feats = (size_t)n * APAP_SPECTRAL_DIM * sizeof(float);
-    APAP_HIP_TRY(hipMemcpyAsync(d + io.src, src, pts, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + io.dst, dst, pts, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + io.c, c_feats, feats, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + io.o, o_feats, feats, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + io.F, F, 9 * sizeof(double), hipMemcpyHostToDevice, nullptr));
-    return APAP_OK;
+void spec_upload(HostCall &call, const SpecIo &p, const float *src, const float *dst, const float *c_feats, const float *o_feats,
+                 const double *F) {
+    call.up(p.src, src);
+    call.up(p.dst, dst);
+    call.up(p.c, c_feats);
+    call.up(p.o, o_feats);
+    call.up(p.F, F);
 }
 }  // namespace
 
@@ -767,34 +841,27 @@ int apap_spectral_weights(apap_ctx *ctx, const float *src, const float *dst, con
         return apap::fail(APAP_ERR_INVALID_ARG, "apap_spectral_weights: no initial mask (neither Hg nor a mask): the reference's "
                                                 "init_ransac=False path fails on `None *= float` (spectral_method.py:131)");
     if (n < 1 || n > (1 << 26)) return apap::fail(APAP_ERR_INVALID_ARG, "apap_spectral_weights: n=%d (need 1 .. 2^26 matches)", n);
-    PoolLock pl(ctx);
-    int dev;
-    int rc = select_device(device, &dev);
+    HostCall call(ctx);
+    int rc = call.select(device);
     if (rc) return rc;
-    const SpecIo io = spec_io(n, false);
-    const size_t work_bytes = apap_spectral_workspace_bytes(n);
-    void *d_io, *d_work;
-    if ((rc = slot_get(pl.pool, S_AUX, io.total, dev, &d_io))) return rc;
-    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-    char *d = (char *)d_io;
-    if ((rc = spec_upload(d, io, src, dst, c_feats, o_feats, n, F))) return rc;
-    if (Hg_or_null) APAP_HIP_TRY(hipMemcpyAsync(d + io.Hg, Hg_or_null, 9 * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    else APAP_HIP_TRY(hipMemcpyAsync(d + io.mask, mask_in_or_null, (size_t)n * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    rc = apap::spectral_run(ctx, (const float *)(d + io.src), (const float *)(d + io.dst), (const float *)(d + io.c),
-                            (const float *)(d + io.o), n, (const double *)(d + io.F), params,
-                            Hg_or_null ? (const float *)(d + io.Hg) : nullptr, Hg_or_null ? nullptr : (const float *)(d + io.mask),
-                            (double *)(d + io.seg), (float *)(d + io.rm), (float *)(d + io.om), (double *)(d + io.info), nullptr,
-                            d_work, work_bytes, nullptr, 1);
-    if (rc) {
-        (void)hipStreamSynchronize(nullptr);
-        return rc;
-    }
-    APAP_HIP_TRY(hipMemcpyAsync(segment_out, d + io.seg, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(ransac_mask_out, d + io.rm, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(original_mask_out, d + io.om, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(info_out, d + io.info, APAP_SPECTRAL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
-    return APAP_OK;
+    Layout io = call.layout(S_AUX);
+    const SpecIo p = spec_io(io, n, false);
+    call.alloc(io);
+    const Part work = call.slot(S_WORK, apap_spectral_workspace_bytes(n));
+    spec_upload(call, p, src, dst, c_feats, o_feats, F);
+    if (Hg_or_null) call.up(p.Hg, Hg_or_null);
+    else call.up(p.mask, mask_in_or_null);
+    if ((rc = call.rc())) return rc;
+    rc = apap::spectral_run(ctx, p.src.as<const float>(), p.dst.as<const float>(), p.c.as<const float>(), p.o.as<const float>(), n,
+                            p.F.as<const double>(), params, Hg_or_null ? p.Hg.as<const float>() : nullptr,
+                            Hg_or_null ? nullptr : p.mask.as<const float>(), p.seg.as<double>(), p.rm.as<float>(), p.om.as<float>(),
+                            p.info.as<double>(), nullptr, work.as<void>(), work.bytes, call.stream(), 1);
+    if (rc) return rc;
+    call.down(segment_out, p.seg);
+    call.down(ransac_mask_out, p.rm);
+    call.down(original_mask_out, p.om);
+    call.down(info_out, p.info);
+    return call.wait();
 }
 
 int apap_spectral_affinity(apap_ctx *ctx, const float *src, const float *dst, const float *c_feats, const float *o_feats, int n,
@@ -802,27 +869,20 @@ int apap_spectral_affinity(apap_ctx *ctx, const float *src, const float *dst, co
     if (!src || !dst || !c_feats || !o_feats || !F || !params || !M_out)
         return apap::fail(APAP_ERR_INVALID_ARG, "apap_spectral_affinity: null argument");
     if (n < 1 || n > 8192) return apap::fail(APAP_ERR_INVALID_ARG, "apap_spectral_affinity: n=%d (the dense M is for 1 .. 8192 matches)", n);
-    PoolLock pl(ctx);
-    int dev;
-    int rc = select_device(device, &dev);
+    HostCall call(ctx);
+    int rc = call.select(device);
     if (rc) return rc;
-    const SpecIo io = spec_io(n, true);
-    const size_t work_bytes = apap_spectral_workspace_bytes(n);
-    void *d_io, *d_work;
-    if ((rc = slot_get(pl.pool, S_AUX, io.total, dev, &d_io))) return rc;
-    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-    char *d = (char *)d_io;
-    if ((rc = spec_upload(d, io, src, dst, c_feats, o_feats, n, F))) return rc;
-    rc = apap::spectral_affinity_run((const float *)(d + io.src), (const float *)(d + io.dst), (const float *)(d + io.c),
-                                     (const float *)(d + io.o), n, (const double *)(d + io.F), params, (double *)(d + io.M), d_work,
-                                     work_bytes, nullptr);
-    if (rc) {
-        (void)hipStreamSynchronize(nullptr);
-        return rc;
-    }
-    APAP_HIP_TRY(hipMemcpyAsync(M_out, d + io.M, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
-    return APAP_OK;
+    Layout io = call.layout(S_AUX);
+    const SpecIo p = spec_io(io, n, true);
+    call.alloc(io);
+    const Part work = call.slot(S_WORK, apap_spectral_workspace_bytes(n));
+    spec_upload(call, p, src, dst, c_feats, o_feats, F);
+    if ((rc = call.rc())) return rc;
+    rc = apap::spectral_affinity_run(p.src.as<const float>(), p.dst.as<const float>(), p.c.as<const float>(), p.o.as<const float>(), n,
+                                     p.F.as<const double>(), params, p.M.as<double>(), work.as<void>(), work.bytes, call.stream());
+    if (rc) return rc;
+    call.down(M_out, p.M);
+    return call.wait();
 }
 
 }  // extern "C"
@@ -840,48 +900,6 @@ int model_status_code(int status, const char *who, int round) {
     return APAP_OK;
 }
 
-struct ModelIo {
-    size_t pc, po, w, H, info, total;
-};
-ModelIo model_io(int n) {
-    ModelIo io{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) / 256 * 256;
-        return at;
-    };
-    io.pc = take((size_t)n * 2 * sizeof(float));
-    io.po = take((size_t)n * 2 * sizeof(float));
-    io.w = take((size_t)n * sizeof(float));
-    io.H = take(9 * sizeof(float));
-    io.info = take(APAP_MODEL_INFO * sizeof(double));
-    io.total = off;
-    return io;
-}
-
-struct EmIo {
-    SpecIo spec;   // src, dst, descriptors, F, the initial mask
-    size_t H, info, seg, rm, om, sinfo, total;
-};
-EmIo em_io(int n, int steps) {
-    EmIo io{};
-    io.spec = spec_io(n, false);
-    size_t off = io.spec.total;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) / 256 * 256;
-        return at;
-    };
-    io.H = take((size_t)steps * 9 * sizeof(float));
-    io.info = take((size_t)steps * APAP_MODEL_INFO * sizeof(double));
-    io.seg = take((size_t)steps * n * sizeof(double));
-    io.rm = take((size_t)steps * n * sizeof(float));
-    io.om = take((size_t)steps * n * sizeof(float));
-    io.sinfo = take((size_t)steps * APAP_SPECTRAL_INFO * sizeof(double));
-    io.total = off;
-    return io;
-}
 }  // namespace
 
 extern "C" {
@@ -894,28 +912,24 @@ int apap_model_solve(apap_ctx *ctx, const float *pts_c, const float *pts_o, cons
     if (H_out) std::fill(H_out, H_out + 9, NAN);
     if (!pts_c || !pts_o || !weights || !params || !H_out || !info_out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
     if (n < 1 || n > (1 << 26)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (need 1 .. 2^26 matches)", who, n);
-    PoolLock pl(ctx);
-    int dev;
-    int rc = select_device(device, &dev);
+    HostCall call(ctx);
+    int rc = call.select(device);
     if (rc) return rc;
-    const ModelIo io = model_io(n);
-    const size_t work_bytes = apap_model_workspace_bytes(n);
-    void *d_io, *d_work;
-    if ((rc = slot_get(pl.pool, S_AUX, io.total, dev, &d_io))) return rc;
-    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-    char *d = (char *)d_io;
-    APAP_HIP_TRY(hipMemcpyAsync(d + io.pc, pts_c, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + io.po, pts_o, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + io.w, weights, (size_t)n * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    rc = apap_model_solve_device(ctx, (const float *)(d + io.pc), (const float *)(d + io.po), (const float *)(d + io.w), n, params,
-                                 (float *)(d + io.H), (double *)(d + io.info), nullptr, d_work, work_bytes, nullptr);
-    if (rc) {
-        (void)hipStreamSynchronize(nullptr);
-        return rc;
-    }
-    APAP_HIP_TRY(hipMemcpyAsync(H_out, d + io.H, 9 * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(info_out, d + io.info, APAP_MODEL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    Layout io = call.layout(S_AUX);
+    const Part pc = io.take((size_t)n * 2 * sizeof(float)), po = io.take((size_t)n * 2 * sizeof(float));
+    const Part w = io.take((size_t)n * sizeof(float)), H = io.take(9 * sizeof(float)), info = io.take(APAP_MODEL_INFO * sizeof(double));
+    call.alloc(io);
+    const Part work = call.slot(S_WORK, apap_model_workspace_bytes(n));
+    call.up(pc, pts_c);
+    call.up(po, pts_o);
+    call.up(w, weights);
+    if ((rc = call.rc())) return rc;
+    rc = apap_model_solve_device(ctx, pc.as<const float>(), po.as<const float>(), w.as<const float>(), n, params, H.as<float>(),
+                                 info.as<double>(), nullptr, work.as<void>(), work.bytes, call.stream());
+    if (rc) return rc;
+    call.down(H_out, H);
+    call.down(info_out, info);
+    if ((rc = call.wait())) return rc;
     return model_status_code((int)info_out[APAP_MODEL_INFO_STATUS], who, 0);
 }
 
@@ -931,35 +945,33 @@ int apap_spectral_em(apap_ctx *ctx, const float *src, const float *dst, const fl
         return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
     if (n < 1 || n > (1 << 26)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (need 1 .. 2^26 matches)", who, n);
     if (em_steps < 1 || em_steps > 64) return apap::fail(APAP_ERR_INVALID_ARG, "%s: em_steps %d (1 .. 64)", who, em_steps);
-    PoolLock pl(ctx);
-    int dev;
-    int rc = select_device(device, &dev);
+    HostCall call(ctx);
+    int rc = call.select(device);
     if (rc) return rc;
-    const EmIo io = em_io(n, em_steps);
-    const size_t work_bytes = apap_spectral_workspace_bytes(n) + apap_model_workspace_bytes(n);
-    void *d_io, *d_work;
-    if ((rc = slot_get(pl.pool, S_AUX, io.total, dev, &d_io))) return rc;
-    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-    char *d = (char *)d_io;
-    if ((rc = spec_upload(d, io.spec, src, dst, c_feats, o_feats, n, F))) return rc;
-    APAP_HIP_TRY(hipMemcpyAsync(d + io.spec.mask, mask_in, (size_t)n * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    rc = apap::spectral_em_run(ctx, (const float *)(d + io.spec.src), (const float *)(d + io.spec.dst), (const float *)(d + io.spec.c),
-                                 (const float *)(d + io.spec.o), n, (const double *)(d + io.spec.F), spec_params, model_params,
-                                 em_steps, (const float *)(d + io.spec.mask), (float *)(d + io.H), (double *)(d + io.info),
-                                 (double *)(d + io.seg), (float *)(d + io.rm), (float *)(d + io.om), (double *)(d + io.sinfo),
-                                 nullptr, d_work, work_bytes, nullptr, 1);
-    if (rc) {
-        (void)hipStreamSynchronize(nullptr);
-        return rc;
-    }
+    // the parts of one spectral call (its single-round outputs stay unused), then the per-round outputs
+    Layout io = call.layout(S_AUX);
+    const SpecIo p = spec_io(io, n, false);
     const size_t k = (size_t)em_steps;
-    APAP_HIP_TRY(hipMemcpyAsync(H_out, d + io.H, k * 9 * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(info_out, d + io.info, k * APAP_MODEL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(segment_out, d + io.seg, k * n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(ransac_mask_out, d + io.rm, k * n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(original_mask_out, d + io.om, k * n * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(spec_info_out, d + io.sinfo, k * APAP_SPECTRAL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
+    const Part H = io.take(k * 9 * sizeof(float)), info = io.take(k * APAP_MODEL_INFO * sizeof(double));
+    const Part seg = io.take(k * n * sizeof(double)), rm = io.take(k * n * sizeof(float)), om = io.take(k * n * sizeof(float));
+    const Part sinfo = io.take(k * APAP_SPECTRAL_INFO * sizeof(double));
+    call.alloc(io);
+    const Part work = call.slot(S_WORK, apap_spectral_workspace_bytes(n) + apap_model_workspace_bytes(n));
+    spec_upload(call, p, src, dst, c_feats, o_feats, F);
+    call.up(p.mask, mask_in);
+    if ((rc = call.rc())) return rc;
+    rc = apap::spectral_em_run(ctx, p.src.as<const float>(), p.dst.as<const float>(), p.c.as<const float>(), p.o.as<const float>(), n,
+                               p.F.as<const double>(), spec_params, model_params, em_steps, p.mask.as<const float>(), H.as<float>(),
+                               info.as<double>(), seg.as<double>(), rm.as<float>(), om.as<float>(), sinfo.as<double>(), nullptr,
+                               work.as<void>(), work.bytes, call.stream(), 1);
+    if (rc) return rc;
+    call.down(H_out, H);
+    call.down(info_out, info);
+    call.down(segment_out, seg);
+    call.down(ransac_mask_out, rm);
+    call.down(original_mask_out, om);
+    call.down(spec_info_out, sinfo);
+    if ((rc = call.wait())) return rc;
     for (int r = 0; r < em_steps; ++r)
         if ((rc = model_status_code((int)info_out[(size_t)r * APAP_MODEL_INFO + APAP_MODEL_INFO_STATUS], who, r))) return rc;
     return APAP_OK;
@@ -976,56 +988,44 @@ int apap_spectral_em_batch(apap_ctx *ctx, const float *src, const float *dst, co
         return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
     int rc = apap::spectral_em_batch_check(pair_offset, n_pairs, pair_of, spec_params, model_params, n_problems, em_steps, who);
     if (rc) return rc;
-    PoolLock pl(ctx);
-    int dev;
-    if ((rc = select_device(device, &dev))) return rc;
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
     const size_t N = (size_t)(pair_offset[n_pairs] - pair_offset[0]), B = (size_t)n_problems, k = (size_t)em_steps;
     size_t M = 0;   // matches over the problems
     for (int b = 0; b < n_problems; ++b) M += (size_t)(pair_offset[pair_of[b] + 1] - pair_offset[pair_of[b]]);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) / 256 * 256;
-        return at;
-    };
+    Layout io = call.layout(S_AUX);
     const size_t pts = N * 2 * sizeof(float), feats = N * APAP_SPECTRAL_DIM * sizeof(float);
-    const size_t o_src = take(pts), o_dst = take(pts), o_c = take(feats), o_o = take(feats), o_F = take((size_t)n_pairs * 9 * sizeof(double));
-    const size_t o_mask = take(N * sizeof(float)), o_H = take(B * k * 9 * sizeof(float)), o_info = take(B * k * APAP_MODEL_INFO * sizeof(double));
-    const size_t o_seg = take(k * M * sizeof(double)), o_rm = take(k * M * sizeof(float)), o_om = take(k * M * sizeof(float));
-    const size_t o_sinfo = take(B * k * APAP_SPECTRAL_INFO * sizeof(double)), o_status = take(B * sizeof(int));
-    const size_t work_bytes = apap_spectral_em_batch_workspace_bytes(pair_offset, n_pairs, pair_of, n_problems);
-    void *d_io, *d_work;
-    if ((rc = slot_get(pl.pool, S_AUX, off, dev, &d_io))) return rc;
-    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-    char *d = (char *)d_io;
+    const Part d_src = io.take(pts), d_dst = io.take(pts), d_c = io.take(feats), d_o = io.take(feats);
+    const Part d_F = io.take((size_t)n_pairs * 9 * sizeof(double)), d_mask = io.take(N * sizeof(float));
+    const Part H = io.take(B * k * 9 * sizeof(float)), info = io.take(B * k * APAP_MODEL_INFO * sizeof(double));
+    const Part seg = io.take(k * M * sizeof(double)), rm = io.take(k * M * sizeof(float)), om = io.take(k * M * sizeof(float));
+    const Part sinfo = io.take(B * k * APAP_SPECTRAL_INFO * sizeof(double)), status = io.take(B * sizeof(int));
+    call.alloc(io);
+    const Part work = call.slot(S_WORK, apap_spectral_em_batch_workspace_bytes(pair_offset, n_pairs, pair_of, n_problems));
     const size_t first = (size_t)pair_offset[0];   // the device arrays start at the first pair
-    std::vector<int> rel((size_t)n_pairs + 1);
-    for (int p = 0; p <= n_pairs; ++p) rel[p] = pair_offset[p] - pair_offset[0];
-    APAP_HIP_TRY(hipMemcpyAsync(d + o_src, src + first * 2, pts, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + o_dst, dst + first * 2, pts, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + o_c, c_feats + first * APAP_SPECTRAL_DIM, feats, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + o_o, o_feats + first * APAP_SPECTRAL_DIM, feats, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + o_F, F, (size_t)n_pairs * 9 * sizeof(double), hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + o_mask, mask_in + first, N * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemsetAsync(d + o_status, 0, B * sizeof(int), nullptr));
-    rc = apap::spectral_em_batch_run(ctx, (const float *)(d + o_src), (const float *)(d + o_dst), (const float *)(d + o_c),
-                                     (const float *)(d + o_o), (const double *)(d + o_F), (const float *)(d + o_mask), rel.data(),
-                                     n_pairs, pair_of, spec_params, model_params, n_problems, em_steps, (float *)(d + o_H),
-                                     (double *)(d + o_info), (double *)(d + o_seg), (float *)(d + o_rm), (float *)(d + o_om),
-                                     (double *)(d + o_sinfo), (int *)(d + o_status), d_work, work_bytes, nullptr, 1);
-    if (rc) {
-        (void)hipStreamSynchronize(nullptr);
-        return rc;
-    }
-    APAP_HIP_TRY(hipMemcpyAsync(H_out, d + o_H, B * k * 9 * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(info_out, d + o_info, B * k * APAP_MODEL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(segment_out, d + o_seg, k * M * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(ransac_mask_out, d + o_rm, k * M * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(original_mask_out, d + o_om, k * M * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(spec_info_out, d + o_sinfo, B * k * APAP_SPECTRAL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    if (status_out) APAP_HIP_TRY(hipMemcpyAsync(status_out, d + o_status, B * sizeof(int), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
-    return APAP_OK;   // a problem's status is its own: see status_out and the info blocks
+    const std::vector<int> rel = relative_offsets(pair_offset, n_pairs);
+    call.up(d_src, src + first * 2);
+    call.up(d_dst, dst + first * 2);
+    call.up(d_c, c_feats + first * APAP_SPECTRAL_DIM);
+    call.up(d_o, o_feats + first * APAP_SPECTRAL_DIM);
+    call.up(d_F, F);
+    call.up(d_mask, mask_in + first);
+    call.zero(status);
+    if ((rc = call.rc())) return rc;
+    rc = apap::spectral_em_batch_run(ctx, d_src.as<const float>(), d_dst.as<const float>(), d_c.as<const float>(),
+                                     d_o.as<const float>(), d_F.as<const double>(), d_mask.as<const float>(), rel.data(), n_pairs,
+                                     pair_of, spec_params, model_params, n_problems, em_steps, H.as<float>(), info.as<double>(),
+                                     seg.as<double>(), rm.as<float>(), om.as<float>(), sinfo.as<double>(), status.as<int>(),
+                                     work.as<void>(), work.bytes, call.stream(), 1);
+    if (rc) return rc;
+    call.down(H_out, H);
+    call.down(info_out, info);
+    call.down(segment_out, seg);
+    call.down(ransac_mask_out, rm);
+    call.down(original_mask_out, om);
+    call.down(spec_info_out, sinfo);
+    if (status_out) call.down(status_out, status);
+    return call.wait();   // a problem's status is its own: see status_out and the info blocks
 }
 
 // ------------------------------------------------------------------ robust moving DLT (apap_local_model.hip)
@@ -1041,43 +1041,31 @@ int apap_local_model_solve(apap_ctx *ctx, const float *pts_c, const float *pts_o
     if (!pts_c || !pts_o || !vertices || !params || !H_out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
     int rc = apap::local_model_check(n, cells, gamma, sigma, params, who);
     if (rc) return rc;
-    PoolLock pl(ctx);
-    int dev;
-    if ((rc = select_device(device, &dev))) return rc;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) / 256 * 256;
-        return at;
-    };
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    Layout io = call.layout(S_AUX);
     const size_t B = (size_t)cells, pts = (size_t)n * 2 * sizeof(float);
-    const size_t o_pc = take(pts), o_po = take(pts), o_mw = take(match_weights ? (size_t)n * sizeof(float) : 0);
-    const size_t o_H = take(B * 9 * sizeof(float)), o_info = take(info_out ? B * APAP_MODEL_INFO * sizeof(double) : 0);
-    const size_t o_status = take(B * sizeof(int));
-    const size_t work_bytes = apap_local_model_workspace_bytes(n, cells);
-    void *d_io, *d_vert, *d_work;
-    if ((rc = slot_get(pl.pool, S_AUX, off, dev, &d_io))) return rc;
-    if ((rc = slot_get(pl.pool, S_VERT, B * 2 * sizeof(double), dev, &d_vert))) return rc;
-    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-    char *d = (char *)d_io;
-    APAP_HIP_TRY(hipMemcpyAsync(d + o_pc, pts_c, pts, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + o_po, pts_o, pts, hipMemcpyHostToDevice, nullptr));
-    if (match_weights) APAP_HIP_TRY(hipMemcpyAsync(d + o_mw, match_weights, (size_t)n * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d_vert, vertices, B * 2 * sizeof(double), hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemsetAsync(d + o_status, 0, B * sizeof(int), nullptr));
-    rc = apap_local_model_solve_device(ctx, (const float *)(d + o_pc), (const float *)(d + o_po),
-                                       match_weights ? (const float *)(d + o_mw) : nullptr, n, (const double *)d_vert, cells, gamma,
-                                       sigma, params, (float *)(d + o_H), info_out ? (double *)(d + o_info) : nullptr,
-                                       (int *)(d + o_status), d_work, work_bytes, nullptr);
-    if (rc) {
-        (void)hipStreamSynchronize(nullptr);
-        return rc;
-    }
-    APAP_HIP_TRY(hipMemcpyAsync(H_out, d + o_H, B * 9 * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    if (info_out) APAP_HIP_TRY(hipMemcpyAsync(info_out, d + o_info, B * APAP_MODEL_INFO * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    if (status_out) APAP_HIP_TRY(hipMemcpyAsync(status_out, d + o_status, B * sizeof(int), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
-    return APAP_OK;   // a cell's status is its own: see status_out and the info blocks
+    const Part pc = io.take(pts), po = io.take(pts), mw = io.take(match_weights ? (size_t)n * sizeof(float) : 0);
+    const Part H = io.take(B * 9 * sizeof(float)), info = io.take(info_out ? B * APAP_MODEL_INFO * sizeof(double) : 0);
+    const Part status = io.take(B * sizeof(int));
+    call.alloc(io);
+    const Part vert = call.slot(S_VERT, B * 2 * sizeof(double));
+    const Part work = call.slot(S_WORK, apap_local_model_workspace_bytes(n, cells));
+    call.up(pc, pts_c);
+    call.up(po, pts_o);
+    if (match_weights) call.up(mw, match_weights);
+    call.up(vert, vertices);
+    call.zero(status);
+    if ((rc = call.rc())) return rc;
+    rc = apap_local_model_solve_device(ctx, pc.as<const float>(), po.as<const float>(), match_weights ? mw.as<const float>() : nullptr,
+                                       n, vert.as<const double>(), cells, gamma, sigma, params, H.as<float>(),
+                                       info_out ? info.as<double>() : nullptr, status.as<int>(), work.as<void>(), work.bytes,
+                                       call.stream());
+    if (rc) return rc;
+    call.down(H_out, H);
+    if (info_out) call.down(info_out, info);
+    if (status_out) call.down(status_out, status);
+    return call.wait();   // a cell's status is its own: see status_out and the info blocks
 }
 
 // ------------------------------------------------------------------ descriptor matching (apap_match.hip)
@@ -1087,45 +1075,29 @@ int apap_match_descriptors_batch(apap_ctx *ctx, const float *q, const float *t, 
     if (!q || !t || !q_offset || !t_offset || !idx || !dist) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
     int rc = apap::match_check(q_offset, t_offset, n_pairs, who);
     if (rc) return rc;
-    PoolLock pl(ctx);
-    int dev;
-    if ((rc = select_device(device, &dev))) return rc;
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
     const size_t q0 = (size_t)q_offset[0], t0 = (size_t)t_offset[0];   // the device arrays start at the first pair
     const size_t NQ = (size_t)q_offset[n_pairs] - q0, NT = (size_t)t_offset[n_pairs] - t0;
-    std::vector<int> qrel((size_t)n_pairs + 1), trel((size_t)n_pairs + 1);
-    for (int p = 0; p <= n_pairs; ++p) {
-        qrel[p] = q_offset[p] - q_offset[0];
-        trel[p] = t_offset[p] - t_offset[0];
-    }
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) / 256 * 256;
-        return at;
-    };
+    const std::vector<int> qrel = relative_offsets(q_offset, n_pairs), trel = relative_offsets(t_offset, n_pairs);
+    Layout io = call.layout(S_AUX);
     const size_t row = APAP_MATCH_DIM * sizeof(float);
-    const size_t o_q = take(NQ * row), o_t = take(NT * row), o_idx = take(NQ * sizeof(int)), o_dist = take(NQ * sizeof(float));
-    const size_t o_idx2 = take(idx2 ? NQ * sizeof(int) : 0), o_dist2 = take(dist2 ? NQ * sizeof(float) : 0);
-    const size_t work_bytes = apap_match_batch_workspace_bytes(qrel.data(), trel.data(), n_pairs);
-    void *d_io, *d_work;
-    if ((rc = slot_get(pl.pool, S_AUX, off, dev, &d_io))) return rc;
-    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-    char *d = (char *)d_io;
-    APAP_HIP_TRY(hipMemcpyAsync(d + o_q, q + q0 * APAP_MATCH_DIM, NQ * row, hipMemcpyHostToDevice, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(d + o_t, t + t0 * APAP_MATCH_DIM, NT * row, hipMemcpyHostToDevice, nullptr));
-    rc = apap_match_descriptors_batch_device(ctx, (const float *)(d + o_q), (const float *)(d + o_t), qrel.data(), trel.data(),
-                                             n_pairs, (int *)(d + o_idx), (float *)(d + o_dist), idx2 ? (int *)(d + o_idx2) : nullptr,
-                                             dist2 ? (float *)(d + o_dist2) : nullptr, d_work, work_bytes, nullptr);
-    if (rc) {
-        (void)hipStreamSynchronize(nullptr);
-        return rc;
-    }
-    APAP_HIP_TRY(hipMemcpyAsync(idx + q0, d + o_idx, NQ * sizeof(int), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(dist + q0, d + o_dist, NQ * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    if (idx2) APAP_HIP_TRY(hipMemcpyAsync(idx2 + q0, d + o_idx2, NQ * sizeof(int), hipMemcpyDeviceToHost, nullptr));
-    if (dist2) APAP_HIP_TRY(hipMemcpyAsync(dist2 + q0, d + o_dist2, NQ * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
-    return APAP_OK;
+    const Part d_q = io.take(NQ * row), d_t = io.take(NT * row), d_idx = io.take(NQ * sizeof(int)), d_dist = io.take(NQ * sizeof(float));
+    const Part d_idx2 = io.take(idx2 ? NQ * sizeof(int) : 0), d_dist2 = io.take(dist2 ? NQ * sizeof(float) : 0);
+    call.alloc(io);
+    const Part work = call.slot(S_WORK, apap_match_batch_workspace_bytes(qrel.data(), trel.data(), n_pairs));
+    call.up(d_q, q + q0 * APAP_MATCH_DIM);
+    call.up(d_t, t + t0 * APAP_MATCH_DIM);
+    if ((rc = call.rc())) return rc;
+    rc = apap_match_descriptors_batch_device(ctx, d_q.as<const float>(), d_t.as<const float>(), qrel.data(), trel.data(), n_pairs,
+                                             d_idx.as<int>(), d_dist.as<float>(), idx2 ? d_idx2.as<int>() : nullptr,
+                                             dist2 ? d_dist2.as<float>() : nullptr, work.as<void>(), work.bytes, call.stream());
+    if (rc) return rc;
+    call.down(idx + q0, d_idx);
+    call.down(dist + q0, d_dist);
+    if (idx2) call.down(idx2 + q0, d_idx2);
+    if (dist2) call.down(dist2 + q0, d_dist2);
+    return call.wait();
 }
 
 int apap_match_descriptors(apap_ctx *ctx, const float *q, int nq, const float *t, int nt, int *idx, float *dist, int *idx2,
@@ -1147,44 +1119,22 @@ int apap_sift_describe_batch(apap_ctx *ctx, const uint8_t *const *imgs, const in
     for (size_t k = 0; k < 2 * N; ++k)
         if (!std::isfinite(pts[2 * k0 + k]))
             return apap::fail(APAP_ERR_INVALID_ARG, "%s: keypoint %zu has a non-finite coordinate", who, k0 + k / 2);
-    PoolLock pl(ctx);
-    int dev;
-    if ((rc = select_device(device, &dev))) return rc;
-    std::vector<int> rel((size_t)n_images + 1);
-    for (int m = 0; m <= n_images; ++m) rel[m] = pt_offset[m] - pt_offset[0];
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) / 256 * 256;
-        return at;
-    };
-    std::vector<size_t> o_img((size_t)n_images);
-    for (int m = 0; m < n_images; ++m) o_img[m] = take((size_t)heights[m] * widths[m] * channels[m]);
-    const size_t img_bytes = off;
-    off = 0;
-    const size_t o_pts = take(N * 2 * sizeof(float)), o_out = take(N * APAP_SIFT_DIM * sizeof(float));
-    const size_t work_bytes = apap_sift_workspace_bytes(n_images);
-    void *d_img, *d_io, *d_work;
-    if ((rc = slot_get(pl.pool, S_IMG, img_bytes, dev, &d_img))) return rc;
-    if ((rc = slot_get(pl.pool, S_AUX, off, dev, &d_io))) return rc;
-    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-    char *d = (char *)d_io;
-    std::vector<const uint8_t *> d_imgs((size_t)n_images);
-    for (int m = 0; m < n_images; ++m) {
-        d_imgs[m] = (const uint8_t *)d_img + o_img[m];
-        APAP_HIP_TRY(hipMemcpyAsync((char *)d_img + o_img[m], imgs[m], (size_t)heights[m] * widths[m] * channels[m], hipMemcpyHostToDevice,
-                                    nullptr));
-    }
-    APAP_HIP_TRY(hipMemcpyAsync(d + o_pts, pts + 2 * k0, N * 2 * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    rc = apap_sift_describe_batch_device(ctx, d_imgs.data(), heights, widths, channels, n_images, (const float *)(d + o_pts), rel.data(),
-                                         (float *)(d + o_out), d_work, work_bytes, nullptr);
-    if (rc) {
-        (void)hipStreamSynchronize(nullptr);
-        return rc;
-    }
-    APAP_HIP_TRY(hipMemcpyAsync(out + k0 * APAP_SIFT_DIM, d + o_out, N * APAP_SIFT_DIM * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
-    return APAP_OK;
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    const std::vector<int> rel = relative_offsets(pt_offset, n_images);
+    const std::vector<Part> d_img = image_parts(call, heights, widths, channels, n_images);
+    Layout io = call.layout(S_AUX);
+    const Part d_pts = io.take(N * 2 * sizeof(float)), d_out = io.take(N * APAP_SIFT_DIM * sizeof(float));
+    call.alloc(io);
+    const Part work = call.slot(S_WORK, apap_sift_workspace_bytes(n_images));
+    const std::vector<const uint8_t *> d_imgs = upload_images(call, d_img, imgs);
+    call.up(d_pts, pts + 2 * k0);
+    if ((rc = call.rc())) return rc;
+    rc = apap_sift_describe_batch_device(ctx, d_imgs.data(), heights, widths, channels, n_images, d_pts.as<const float>(), rel.data(),
+                                         d_out.as<float>(), work.as<void>(), work.bytes, call.stream());
+    if (rc) return rc;
+    call.down(out + k0 * APAP_SIFT_DIM, d_out);
+    return call.wait();
 }
 
 int apap_sift_describe(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, const float *pts, int n, float *out, int device) {
@@ -1202,44 +1152,25 @@ int apap_corner_detect_batch(apap_ctx *ctx, const uint8_t *const *imgs, const in
     if (rc) return rc;
     for (int m = 0; m < n_images; ++m)
         if (!imgs[m]) return apap::fail(APAP_ERR_INVALID_ARG, "%s: image %d: null pointer", who, m);
-    PoolLock pl(ctx);
-    int dev;
-    if ((rc = select_device(device, &dev))) return rc;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) / 256 * 256;
-        return at;
-    };
-    std::vector<size_t> o_img((size_t)n_images);
-    for (int m = 0; m < n_images; ++m) o_img[m] = take((size_t)heights[m] * widths[m] * channels[m]);
-    const size_t img_bytes = off;
-    off = 0;
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
     const size_t rows = (size_t)n_images * (size_t)max_corners;
-    const size_t o_pts = take(rows * 2 * sizeof(float)), o_resp = take(rows * sizeof(long long)), o_count = take((size_t)n_images * sizeof(int));
-    const size_t work_bytes = apap_corner_workspace_bytes(heights, widths, n_images, radius);
-    void *d_img, *d_io, *d_work;
-    if ((rc = slot_get(pl.pool, S_IMG, img_bytes, dev, &d_img))) return rc;
-    if ((rc = slot_get(pl.pool, S_AUX, off, dev, &d_io))) return rc;
-    if ((rc = slot_get(pl.pool, S_WORK, work_bytes, dev, &d_work))) return rc;
-    char *d = (char *)d_io;
-    std::vector<const uint8_t *> d_imgs((size_t)n_images);
-    for (int m = 0; m < n_images; ++m) {
-        d_imgs[m] = (const uint8_t *)d_img + o_img[m];
-        APAP_HIP_TRY(hipMemcpyAsync((char *)d_img + o_img[m], imgs[m], (size_t)heights[m] * widths[m] * channels[m], hipMemcpyHostToDevice,
-                                    nullptr));
-    }
+    const std::vector<Part> d_img = image_parts(call, heights, widths, channels, n_images);
+    Layout io = call.layout(S_AUX);
+    const Part d_pts = io.take(rows * 2 * sizeof(float)), d_resp = io.take(rows * sizeof(long long));
+    const Part d_count = io.take((size_t)n_images * sizeof(int));
+    call.alloc(io);
+    const Part work = call.slot(S_WORK, apap_corner_workspace_bytes(heights, widths, n_images, radius));
+    const std::vector<const uint8_t *> d_imgs = upload_images(call, d_img, imgs);
+    if ((rc = call.rc())) return rc;
     rc = apap_corner_detect_batch_device(ctx, d_imgs.data(), heights, widths, channels, n_images, max_corners, radius, quality_permille,
-                                         (float *)(d + o_pts), (long long *)(d + o_resp), (int *)(d + o_count), d_work, work_bytes, nullptr);
-    if (rc) {
-        (void)hipStreamSynchronize(nullptr);
-        return rc;
-    }
-    APAP_HIP_TRY(hipMemcpyAsync(pts, d + o_pts, rows * 2 * sizeof(float), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(response, d + o_resp, rows * sizeof(long long), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipMemcpyAsync(count, d + o_count, (size_t)n_images * sizeof(int), hipMemcpyDeviceToHost, nullptr));
-    APAP_HIP_TRY(hipStreamSynchronize(nullptr));
-    return APAP_OK;
+                                         d_pts.as<float>(), d_resp.as<long long>(), d_count.as<int>(), work.as<void>(), work.bytes,
+                                         call.stream());
+    if (rc) return rc;
+    call.down(pts, d_pts);
+    call.down(response, d_resp);
+    call.down(count, d_count);
+    return call.wait();
 }
 
 int apap_corner_detect(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, int max_corners, int radius,
