@@ -203,6 +203,16 @@ SIGNATURES = {
                                            _i64p, _i32p, C.c_int]),
     "apap_corner_detect_batch_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "apap_image_warp_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _f64p, _i32p]),
+    "apap_image_warp_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "apap_image_warp": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, _f64p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.c_int, _u8p, C.c_int]),
+    "apap_image_warp_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _f64p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "apap_image_warp_batch": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, C.POINTER(C.c_void_p), _i32p, _i32p, _f64p, _i32p,
+                                        _i32p, _i32p, _i32p, _i32p, C.c_int, _u8p, _i64p, C.c_int]),
+    "apap_image_warp_batch_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, C.POINTER(C.c_void_p), _i32p, _i32p, _f64p,
+                                               _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int, _vp, _i64p, _vp, C.c_size_t, _vp, _vp]),
 }
 
 _lib = None
@@ -1063,3 +1073,114 @@ def corner_detect(img, max_corners, radius=5, quality_permille=10, device=-1, ct
     if full:
         return pts, resp, count.value
     return pts[:count.value].copy(), resp[:count.value].copy()
+
+
+# ---------------------------------------------------------------- global warp and blend: image_warping of utils.py:93-127
+IMAGE_WARP_MAX_SIDE = 32767         # APAP_IMAGE_WARP_MAX_SIDE
+IMAGE_WARP_MAX_PROBLEMS = 65535     # APAP_IMAGE_WARP_MAX_PROBLEMS
+
+
+def as_warp_image(img, name="img"):
+    """An (h, w, 3) uint8 picture, contiguous; every other dtype or shape is a ValueError (the reference's blend loop and
+    three-channel paste take nothing else)."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"{name} must be (h, w, 3) uint8; got {img.dtype} {img.shape}")
+    if not all(1 <= x <= IMAGE_WARP_MAX_SIDE for x in img.shape[:2]):
+        raise ValueError(f"{name}: sides must be 1 .. {IMAGE_WARP_MAX_SIDE}; got {img.shape[:2]}")
+    return np.ascontiguousarray(img)
+
+
+def as_homography(H, name="H"):
+    """A 3 x 3 homography in its own float dtype (float32 stays float32: the reference multiplies it as it is)."""
+    H = np.asarray(H)
+    if H.shape != (3, 3):
+        raise ValueError(f"{name} must be 3 x 3; got {H.shape}")
+    return H if H.dtype in (np.float32, np.float64) else H.astype(np.float64)
+
+
+def image_warp_bounds(h1, w1, h2, w2, H):
+    """``apap_image_warp_bounds`` (host only): (xmin, ymin, xmax, ymax) of utils.py:101-106 for an h1 x w1 base picture and an
+    h2 x w2 picture warped by ``H``.  A canvas with a side outside 1 .. 32767, or a non-finite corner, is a ValueError."""
+    H = np.ascontiguousarray(as_homography(H), dtype=np.float64)
+    out = np.empty(4, np.int32)
+    check(lib().apap_image_warp_bounds(int(h1), int(w1), int(h2), int(w2), _ptr(H, C.c_double), _ptr(out, C.c_int)))
+    return tuple(int(v) for v in out)
+
+
+def image_warp_geometry(h1, w1, h2, w2, H):
+    """What utils.py:99-114 derives from the shapes and ``H``: ``(M, canvas_w, canvas_h, off_x, off_y)`` with ``M`` the
+    reference's own ``Ht.dot(H)`` as contiguous float64 (the native layer never forms it: no BLAS summation order in the C
+    contract)."""
+    H = as_homography(H)
+    xmin, ymin, xmax, ymax = image_warp_bounds(h1, w1, h2, w2, H)
+    t = [-xmin, -ymin]
+    Ht = np.array([
+        [1, 0, t[0]],
+        [0, 1, t[1]],
+        [0, 0, 1]])
+    M = np.ascontiguousarray(Ht.dot(H), dtype=np.float64)
+    return M, xmax - xmin, ymax - ymin, t[0], t[1]
+
+
+def image_warp_tables(shapes_base, shapes_src, Ms, canvases, offsets, directs, out_offsets=None, who="image_warp_batch"):
+    """The host arrays of the batch entry points from per-problem lists: ``(n, base_h, base_w, src_h, src_w, M, canvas_w,
+    canvas_h, off_x, off_y, direct, out_offset, sizes)``; ``out_offsets`` default to the canvases packed back to back."""
+    n = len(Ms)
+    if not 1 <= n <= IMAGE_WARP_MAX_PROBLEMS:
+        raise ValueError(f"{who}: {n} problems (1 .. {IMAGE_WARP_MAX_PROBLEMS})")
+    if not all(len(x) == n for x in (shapes_base, shapes_src, canvases, offsets, directs)):
+        raise ValueError(f"{who}: the per-problem lists differ in length")
+    i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)      # noqa: E731
+    M = np.ascontiguousarray(np.stack([np.asarray(m, np.float64).reshape(3, 3) for m in Ms]), dtype=np.float64)
+    cw, ch = i32([c[0] for c in canvases]), i32([c[1] for c in canvases])
+    sizes = [int(h) * int(w) * 3 for w, h in canvases]
+    if out_offsets is None:
+        out_offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    off = np.ascontiguousarray(out_offsets, dtype=np.int64)
+    if off.shape != (n,):
+        raise ValueError(f"{who}: {n} problems, out_offsets of shape {off.shape}")
+    return (n, i32([s[0] for s in shapes_base]), i32([s[1] for s in shapes_base]), i32([s[0] for s in shapes_src]),
+            i32([s[1] for s in shapes_src]), M, cw, ch, i32([o[0] for o in offsets]), i32([o[1] for o in offsets]),
+            i32([1 if d else 0 for d in directs]), off, sizes)
+
+
+def image_warp_batch(bases, srcs, Ms, canvases, offsets, directs, out=None, out_offsets=None, device=-1, ctx=None):
+    """``apap_image_warp_batch``: many global warps and blends in one kernel launch.  Per problem: ``bases[p]`` and ``srcs[p]``
+    (h, w, 3) uint8 (problems may share pictures: the same array is uploaded once), ``Ms[p]`` 3 x 3 float64 (canvas <- source),
+    ``canvases[p]`` = (width, height), ``offsets[p]`` = (off_x, off_y) of the base picture, ``directs[p]`` the blend mode.
+    ``out``: a flat contiguous uint8 array receiving problem p's canvas at byte ``out_offsets[p]`` (default: a new array, the
+    canvases back to back).  Returns the list of canvases, views of ``out``; each equals its own single call's byte for byte."""
+    bases = [as_warp_image(b, f"bases[{p}]") for p, b in enumerate(bases)]
+    srcs = [as_warp_image(s, f"srcs[{p}]") for p, s in enumerate(srcs)]
+    n, bh, bw, sh, sw, M, cw, ch, ox, oy, direct, off, sizes = image_warp_tables(
+        [b.shape for b in bases], [s.shape for s in srcs], Ms, canvases, offsets, directs, out_offsets)
+    if (cw < 1).any() or (ch < 1).any() or (cw > IMAGE_WARP_MAX_SIDE).any() or (ch > IMAGE_WARP_MAX_SIDE).any():
+        raise ValueError(f"image_warp_batch: canvas sides must be 1 .. {IMAGE_WARP_MAX_SIDE}")
+    if (off < 0).any():
+        raise ValueError("image_warp_batch: negative output offset")
+    need = int(max(o + s for o, s in zip(off, sizes)))
+    if out is None:
+        out = np.empty(need, np.uint8)
+    if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.ndim != 1 or not out.flags.c_contiguous or out.size < need:
+        raise ValueError(f"image_warp_batch: out must be a flat contiguous uint8 array of at least {need} bytes")
+    vpp = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs])      # noqa: E731
+    ip = lambda a: _ptr(a, C.c_int)      # noqa: E731
+    check(lib().apap_image_warp_batch(_h(ctx), vpp(bases), ip(bh), ip(bw), vpp(srcs), ip(sh), ip(sw), _ptr(M, C.c_double), ip(cw), ip(ch),
+                                      ip(ox), ip(oy), ip(direct), n, _ptr(out, C.c_uint8), _ptr(off, C.c_longlong), device))
+    return [out[int(o):int(o) + s].reshape(int(h), int(w), 3) for o, s, w, h in zip(off, sizes, cw, ch)]
+
+
+def image_warp(base, src, M, canvas_w, canvas_h, off_x, off_y, direct_blend=True, device=-1, ctx=None):
+    """``apap_image_warp``: ``src`` warped by ``M`` (3 x 3 float64, canvas <- source) onto a canvas_h x canvas_w canvas, ``base``
+    pasted (``direct_blend``) or mean-blended at (off_x, off_y): (canvas_h, canvas_w, 3) uint8."""
+    base, src = as_warp_image(base, "base"), as_warp_image(src, "src")
+    M = np.ascontiguousarray(np.asarray(M, np.float64).reshape(3, 3))
+    canvas_w, canvas_h = int(canvas_w), int(canvas_h)
+    if not (1 <= canvas_w <= IMAGE_WARP_MAX_SIDE and 1 <= canvas_h <= IMAGE_WARP_MAX_SIDE):
+        raise ValueError(f"image_warp: canvas sides must be 1 .. {IMAGE_WARP_MAX_SIDE}; got {canvas_h} x {canvas_w}")
+    out = np.empty((canvas_h, canvas_w, 3), np.uint8)
+    check(lib().apap_image_warp(_h(ctx), _ptr(base, C.c_uint8), base.shape[0], base.shape[1], _ptr(src, C.c_uint8), src.shape[0],
+                                src.shape[1], _ptr(M, C.c_double), canvas_w, canvas_h, int(off_x), int(off_y), 1 if direct_blend else 0,
+                                _ptr(out, C.c_uint8), device))
+    return out

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <vector>
 
@@ -1176,6 +1177,67 @@ int apap_corner_detect_batch(apap_ctx *ctx, const uint8_t *const *imgs, const in
 int apap_corner_detect(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, int max_corners, int radius,
                        int quality_permille, float *pts, long long *response, int *count, int device) {
     return apap_corner_detect_batch(ctx, &img, &h, &w, &channels, 1, max_corners, radius, quality_permille, pts, response, count, device);
+}
+
+// ------------------------------------------------------------------ global warp and blend (apap_image_warp.hip)
+int apap_image_warp_batch(apap_ctx *ctx, const uint8_t *const *bases, const int *base_h, const int *base_w, const uint8_t *const *srcs,
+                          const int *src_h, const int *src_w, const double *M, const int *canvas_w, const int *canvas_h,
+                          const int *off_x, const int *off_y, const int *direct_blend, int n_problems, uint8_t *out,
+                          const long long *out_offset, int device) {
+    const char *who = "apap_image_warp_batch";
+    if (!bases || !srcs || !out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc = apap::image_warp_check(base_h, base_w, src_h, src_w, M, canvas_w, canvas_h, off_x, off_y, direct_blend, n_problems, out_offset, who);
+    if (rc) return rc;
+    for (int p = 0; p < n_problems; ++p)
+        if (!bases[p] || !srcs[p]) return apap::fail(APAP_ERR_INVALID_ARG, "%s: problem %d: null pointer", who, p);
+    // the distinct pictures of the batch (problems may share them: the reference's baseline / result pair), uploaded once each
+    struct Pic { const uint8_t *host; size_t bytes; };
+    std::vector<Pic> pics;
+    std::vector<int> base_pic((size_t)n_problems), src_pic((size_t)n_problems);
+    std::map<std::pair<const uint8_t *, size_t>, int> seen;
+    const auto pic_of = [&pics, &seen](const uint8_t *host, size_t bytes) {
+        const auto it = seen.emplace(std::make_pair(host, bytes), (int)pics.size());
+        if (it.second) pics.push_back(Pic{host, bytes});
+        return it.first->second;
+    };
+    long long lo = out_offset[0], hi = 0;   // the device canvases start at the lowest offset
+    for (int p = 0; p < n_problems; ++p) {
+        base_pic[p] = pic_of(bases[p], (size_t)base_h[p] * base_w[p] * 3);
+        src_pic[p] = pic_of(srcs[p], (size_t)src_h[p] * src_w[p] * 3);
+        lo = std::min(lo, out_offset[p]);
+        hi = std::max(hi, out_offset[p] + (long long)canvas_h[p] * canvas_w[p] * 3);
+    }
+    std::vector<long long> rel((size_t)n_problems);
+    for (int p = 0; p < n_problems; ++p) rel[p] = out_offset[p] - lo;
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    Layout imgs = call.layout(S_IMG);
+    std::vector<Part> d_pic(pics.size(), Part{});
+    for (size_t k = 0; k < pics.size(); ++k) d_pic[k] = imgs.take(pics[k].bytes);
+    call.alloc(imgs);
+    const Part d_out = call.slot(S_OUT, (size_t)(hi - lo));
+    const Part work = call.slot(S_WORK, apap_image_warp_workspace_bytes(n_problems));
+    for (size_t k = 0; k < pics.size(); ++k) call.up(d_pic[k], pics[k].host);
+    if ((rc = call.rc())) return rc;
+    std::vector<const uint8_t *> d_bases((size_t)n_problems), d_srcs((size_t)n_problems);
+    for (int p = 0; p < n_problems; ++p) {
+        d_bases[p] = d_pic[base_pic[p]].as<const uint8_t>();
+        d_srcs[p] = d_pic[src_pic[p]].as<const uint8_t>();
+    }
+    rc = apap_image_warp_batch_device(ctx, d_bases.data(), base_h, base_w, d_srcs.data(), src_h, src_w, M, canvas_w, canvas_h, off_x, off_y,
+                                      direct_blend, n_problems, d_out.as<uint8_t>(), rel.data(), work.as<void>(), work.bytes, nullptr,
+                                      call.stream());
+    if (rc) return rc;
+    for (int p = 0; p < n_problems; ++p)   // the bytes between the canvases are not the call's
+        call.down(out + out_offset[p], Part{d_out.base, (size_t)rel[p], (size_t)canvas_h[p] * canvas_w[p] * 3});
+    return call.wait();
+}
+
+int apap_image_warp(apap_ctx *ctx, const uint8_t *base, int h1, int w1, const uint8_t *src, int h2, int w2, const double *M,
+                    int canvas_w, int canvas_h, int off_x, int off_y, int direct_blend, uint8_t *out, int device) {
+    const long long at = 0;
+    return apap_image_warp_batch(ctx, &base, &h1, &w1, &src, &h2, &w2, M, &canvas_w, &canvas_h, &off_x, &off_y, &direct_blend, 1, out, &at,
+                                 device);
 }
 
 }  // extern "C"

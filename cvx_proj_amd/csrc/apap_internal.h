@@ -126,6 +126,10 @@ int sift_check(const int *heights, const int *widths, const int *channels, int n
 // The argument checks of the corner detector's entry points (apap_corner.hip) that need no device pointer.
 int corner_check(const int *heights, const int *widths, const int *channels, int n_images, int max_corners, int radius,
                  int quality_permille, const char *who);
+// The argument checks of the global warp's entry points (apap_image_warp.hip) that need no device pointer.
+int image_warp_check(const int *base_h, const int *base_w, const int *src_h, const int *src_w, const double *M, const int *canvas_w,
+                     const int *canvas_h, const int *off_x, const int *off_y, const int *direct_blend, int n_problems,
+                     const long long *out_offset, const char *who);
 // Set-up and the dense M (n x n doubles) on `stream`.
 int spectral_affinity_run(const float *d_src, const float *d_dst, const float *d_c, const float *d_o, int n, const double *d_F,
                           const double *params, double *d_M, void *d_work, size_t work_bytes, void *stream);

@@ -540,3 +540,74 @@ def hip_detect_describe_match(c_img, o_img, max_corners, radius=5, quality_permi
         raise ValueError(f"hip_detect_describe_match: {nc} and {no} corners; both images need at least one")
     pts_c, pts_o = pts[0, :nc], pts[1, :no]
     return hip_describe_and_match(c_img, o_img, pts_c, pts_o, second=second, ctx=ctx) + (pts_c, pts_o)
+
+
+def image_warp_workspace_bytes(n_problems=1):
+    """Scratch of ``hip_image_warp`` / ``hip_image_warp_batch`` of ``n_problems`` problems: 144 bytes per problem, a 256-byte
+    multiple, no contract on its contents.  0 for an invalid count."""
+    return _native.lib().apap_image_warp_workspace_bytes(int(n_problems))
+
+
+def _warp_picture(t, dev, who, name):
+    if t.dtype != torch.uint8 or not t.is_contiguous() or t.device != dev or t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError(f"{who}: {name} must be a contiguous uint8 (h, w, 3) tensor on {dev}")
+    if not all(1 <= x <= _native.IMAGE_WARP_MAX_SIDE for x in t.shape[:2]):
+        raise ValueError(f"{who}: {name}: sides must be 1 .. {_native.IMAGE_WARP_MAX_SIDE}; got {tuple(t.shape[:2])}")
+
+
+def hip_image_warp_batch(problems, out=None, out_offsets=None, status=None, ctx=None, work=None):
+    """``apap_image_warp_batch_device`` on the current stream of the tensors' device, no host synchronisation: the reference's
+    ``image_warping`` (utils.py:93-127) for a sequence of ``(img_base, img2warp, H, direct_blend)`` in one kernel launch.  The
+    pictures are contiguous uint8 (h, w, 3) device tensors (problems may share them), ``H`` a host 3 x 3 array: bounds, canvas
+    and ``Ht.dot(H)`` are host arithmetic on nine numbers.  ``out``: a flat uint8 device tensor receiving problem p's canvas
+    at byte ``out_offsets[p]`` (default: a new tensor, the canvases back to back).  ``status`` (an int32 tensor, may be None)
+    is passed on and never written.  ``work`` (uint8) is used when it holds ``image_warp_workspace_bytes(len(problems))``.
+    Returns the list of canvases, views of ``out``, not synchronised: the same bytes as ``utils.image_warping``."""
+    who = "hip_image_warp_batch"
+    problems = list(problems)
+    if not problems:
+        raise ValueError(f"{who}: no problems")
+    _needs_device(problems[0][0], who)
+    dev = problems[0][0].device
+    geo = []
+    for p, (base, src, H, _) in enumerate(problems):
+        _warp_picture(base, dev, who, f"problems[{p}]: img_base")
+        _warp_picture(src, dev, who, f"problems[{p}]: img2warp")
+        geo.append(_native.image_warp_geometry(base.shape[0], base.shape[1], src.shape[0], src.shape[1], H))
+    n, bh, bw, sh, sw, M, cw, ch, ox, oy, direct, off, sizes = _native.image_warp_tables(
+        [b.shape for b, _, _, _ in problems], [s.shape for _, s, _, _ in problems], [g[0] for g in geo], [(g[1], g[2]) for g in geo],
+        [(g[3], g[4]) for g in geo], [bool(d) for _, _, _, d in problems], out_offsets, who)
+    if (off < 0).any():
+        raise ValueError(f"{who}: negative output offset")
+    need = int(max(o + s for o, s in zip(off, sizes)))
+    if out is None:
+        out = torch.empty(need, dtype=torch.uint8, device=dev)
+    if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != dev or out.numel() < need:
+        raise ValueError(f"{who}: out must be a flat contiguous uint8 tensor of at least {need} bytes on {dev}")
+    work = _scratch(work, image_warp_workspace_bytes(n), dev)
+    ip, vpp = ctypes.POINTER(ctypes.c_int), ctypes.c_void_p * n
+    _native.check(_native.lib().apap_image_warp_batch_device(
+        _native._h(ctx), vpp(*[b.data_ptr() for b, _, _, _ in problems]), bh.ctypes.data_as(ip), bw.ctypes.data_as(ip),
+        vpp(*[s.data_ptr() for _, s, _, _ in problems]), sh.ctypes.data_as(ip), sw.ctypes.data_as(ip),
+        M.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cw.ctypes.data_as(ip), ch.ctypes.data_as(ip), ox.ctypes.data_as(ip),
+        oy.ctypes.data_as(ip), direct.ctypes.data_as(ip), n, out.data_ptr(), off.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
+        work.data_ptr(), work.numel(), status.data_ptr() if status is not None else None, _stream(dev)))
+    return [out[int(o):int(o) + s].view(int(h), int(w), 3) for o, s, w, h in zip(off, sizes, cw, ch)]
+
+
+def hip_image_warp(img_base, img2warp, H, direct_blend=True, status=None, ctx=None, work=None):
+    """``apap_image_warp_device``: ``utils.image_warping`` on device tensors, on the current stream, not synchronised.  Returns
+    the (canvas_h, canvas_w, 3) uint8 canvas (see ``hip_image_warp_batch``; the single call is the batch of one)."""
+    who = "hip_image_warp"
+    _needs_device(img_base, who)
+    dev = img_base.device
+    _warp_picture(img_base, dev, who, "img_base")
+    _warp_picture(img2warp, dev, who, "img2warp")
+    M, cw, ch, tx, ty = _native.image_warp_geometry(img_base.shape[0], img_base.shape[1], img2warp.shape[0], img2warp.shape[1], H)
+    out = torch.empty((ch, cw, 3), dtype=torch.uint8, device=dev)
+    work = _scratch(work, image_warp_workspace_bytes(1), dev)
+    _native.check(_native.lib().apap_image_warp_device(
+        _native._h(ctx), img_base.data_ptr(), img_base.shape[0], img_base.shape[1], img2warp.data_ptr(), img2warp.shape[0],
+        img2warp.shape[1], M.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cw, ch, tx, ty, 1 if direct_blend else 0, out.data_ptr(),
+        work.data_ptr(), work.numel(), status.data_ptr() if status is not None else None, _stream(dev)))
+    return out

@@ -12,6 +12,7 @@ runs), the part that needs neither OpenCV nor cvxpy: ``calculate_M`` (:66-133) a
 * ``model_solve`` (:165-186): the M-step, model.py's LMSSolver / SDPSolver on the GPU (cvx_proj_amd/model.py).
 * ``spectral_em``: the EM loop of ``spectral_method()`` (:188-241) on arrays, every round on the device without a host
   synchronisation (``apap_spectral_em``): calculate_M with Hg = the previous round's H_pred, then model_solve.
+* ``warp_results``: the two ``image_warping`` calls of the ``-s`` option (:227-229) as one batched kernel launch.
 * ``skew_symmetric_transform``, ``fundamental``, ``get_fundamental``: utils.py:162-186, host numpy.
 
 Keypoints and matches are duck-typed: anything with ``.pt`` and ``.queryIdx`` / ``.trainIdx`` (OpenCV's KeyPoint / DMatch
@@ -29,7 +30,7 @@ import numpy as np
 from . import _native
 
 __all__ = ["calculate_M", "spectral_weights", "SpectralResult", "recompute_matching", "match_RANSAC", "cv_to_array",
-           "normalized_feature", "model_solve", "spectral_em", "spectral_em_batch", "spectral_em_grid", "EMRound", "EMResult", "skew_symmetric_transform", "fundamental",
+           "normalized_feature", "model_solve", "spectral_em", "spectral_em_batch", "spectral_em_grid", "EMRound", "EMResult", "warp_results", "skew_symmetric_transform", "fundamental",
            "get_fundamental"]
 
 
@@ -252,6 +253,19 @@ def spectral_em(src_pts, dst_pts, c_feats, o_feats, F, *, em_steps=2, lms=False,
     H_save = np.linalg.inv(H[-1]).astype(np.float64)
     H_save /= H_save[-1, -1]
     return EMResult(rounds, H_save)
+
+
+def warp_results(center_img, other_img, H_baseline, H_pred, direct_blend=False, device=-1, ctx=None):
+    """spectral_method.py:227-229, the ``-s`` option: ``(warpped_baseline, warpped_result)`` =
+    ``(image_warping(center_img, other_img, H_baseline, False), image_warping(center_img, other_img, H_pred, False))`` as one
+    batched call - one kernel launch, the two pictures uploaded once.  ``H_baseline``: the first round's
+    ``SpectralResult.H`` (the RANSAC homography); ``H_pred``: ``em.rounds[-1].H_pred``."""
+    from .utils import image_warping_batch
+    if H_baseline is None or H_pred is None:
+        raise ValueError("warp_results needs both homographies (RANSAC found no model?)")
+    baseline, result = image_warping_batch([(center_img, other_img, H_baseline, direct_blend),
+                                            (center_img, other_img, H_pred, direct_blend)], device=device, ctx=ctx)
+    return baseline, result
 
 
 _EM_OPTIONS = {"lms": False, "fluc": 0.5, "huber_param": -1.0, "epi_weight": 0.5, "affinity_eps": 30.0, "aff_thresh": 0.5,

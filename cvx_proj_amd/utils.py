@@ -4,6 +4,8 @@ after the hot path (reference apap.py:17-18,236-238,245): image pre-processing, 
 
 * ``visualize_equalized_hist`` / ``equalize_hist``: per-channel ``cv.equalizeHist`` on the GPU
   (``apap_equalize_hist``, two HIP kernels).  No CPU fallback.
+* ``image_warping`` / ``image_warping_batch``: utils.py:93-127, the global-homography warp (OpenCV's fixed-point bilinear
+  ``cv.warpPerspective``, restated) and the paste or mean blend, one fused HIP kernel (``apap_image_warp``).  No CPU fallback.
 * ``get_features``: same indexing of ``keypoints.mat`` as utils.py:55-66.
 * images are read with Pillow and handed out in OpenCV's BGR channel order, because that is
   what ``cv.imread`` gives the reference.
@@ -20,7 +22,7 @@ import numpy as np
 from . import _native
 
 __all__ = ["get_base_path", "get_path", "imread", "equalize_hist", "visualize_equalized_hist", "get_no_scat_img",
-           "get_features", "save2mat"]
+           "get_features", "save2mat", "image_warping", "image_warping_batch"]
 
 DEFAULT_ROOT = "../diff_1/raw_data"     # utils.py:28
 
@@ -62,6 +64,30 @@ def visualize_equalized_hist(case_idx=1, img_idx=3, disp=False, root: str = DEFA
     if img is None:
         raise FileNotFoundError(path)
     return equalize_hist(img, device=device)
+
+
+def _warp_problem(img_base, img2warp, H, who):
+    base, src = _native.as_warp_image(img_base, f"{who}: img_base"), _native.as_warp_image(img2warp, f"{who}: img2warp")
+    return (base, src) + _native.image_warp_geometry(base.shape[0], base.shape[1], src.shape[0], src.shape[1], H)
+
+
+def image_warping(img_base, img2warp, H, direct_blend=True, device=-1, ctx=None):
+    """utils.py:93-127: ``img2warp`` warped by ``H`` onto the canvas that bounds it and ``img_base``; the base picture covers
+    it (``direct_blend``) or is mean-blended with it where the warped pixel is not black.  Both pictures (h, w, 3) uint8 -
+    anything else is a ValueError, as is an ``H`` whose canvas would have a side beyond 32767.  Returns the canvas.  The warp
+    is ``cv.warpPerspective``'s bilinear definition in exact integers (DESIGN.md "Global warp and blend")."""
+    base, src, M, cw, ch, tx, ty = _warp_problem(img_base, img2warp, H, "image_warping")
+    return _native.image_warp(base, src, M, cw, ch, tx, ty, direct_blend, device=device, ctx=ctx)
+
+
+def image_warping_batch(problems, device=-1, ctx=None):
+    """``image_warping`` for a sequence of ``(img_base, img2warp, H, direct_blend)`` in one kernel launch, whatever their
+    number and shapes; problems may share pictures (the same array is uploaded once).  Returns the list of canvases, each
+    equal to its own ``image_warping`` call's byte for byte."""
+    problems = list(problems)
+    got = [_warp_problem(b, s, H, f"image_warping_batch[{p}]") for p, (b, s, H, _) in enumerate(problems)]
+    return _native.image_warp_batch([g[0] for g in got], [g[1] for g in got], [g[2] for g in got], [(g[3], g[4]) for g in got],
+                                    [(g[5], g[6]) for g in got], [bool(d) for _, _, _, d in problems], device=device, ctx=ctx)
 
 
 def get_no_scat_img(case_idx, img_idx, center_id, root: str = DEFAULT_ROOT):

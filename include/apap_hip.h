@@ -784,6 +784,59 @@ int apap_corner_detect_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs,
                                     const int *channels, int n_images, int max_corners, int radius, int quality_permille,
                                     float *d_pts, long long *d_response, int *d_count, void *d_work, size_t work_bytes, void *stream);
 
+/* ------------------------------------------------- global warp and blend: image_warping of utils.py:93-127 --- */
+/* The output stage of spectral_method.py -s (:226-232): img2warp (h2 x w2 x 3 uint8) goes through one 3 x 3 homography onto
+ * a canvas that bounds it and img_base (h1 x w1 x 3 uint8), and the base picture is pasted or mean-blended onto it.  The
+ * definition - OpenCV 4.x's fixed-point INTER_LINEAR / BORDER_CONSTANT(0) warpPerspective in its exact-integer form, restated
+ * without OpenCV - is in DESIGN.md "Global warp and blend" and, in numpy int64 / float64, in tests/image_warp_spec.py:
+ *   bounds   apap_image_warp_bounds (host only, no device): the corners (0,0), (0,h2), (w2,h2), (w2,0) through H (9 doubles,
+ *            row-major) as cv.perspectiveTransform does - w = H6 x + H7 y + H8 in fp64, w = w ? 1 / w : 0, each coordinate
+ *            (Hk0 x + Hk1 y + Hk2) w rounded to float32 - joined with the base picture's corners; out = xmin, ymin, xmax, ymax
+ *            with min = trunc(float32(min - 0.5f)), max = trunc(float32(max + 0.5f)) (utils.py:105-106).  The canvas is
+ *            (xmax - xmin) x (ymax - ymin), the base picture sits at (-xmin, -ymin) and always fits.  A non-finite corner, one
+ *            beyond int32 or a canvas side outside 1 .. APAP_IMAGE_WARP_MAX_SIDE: APAP_ERR_INVALID_ARG
+ *   M        9 doubles, row-major: canvas <- source, the reference's Ht.dot(H) (utils.py:108-114), formed by the caller
+ *   warp     Minv = cofactors(M) / det3(M) in fp64 (cv::invert's closed form); per canvas pixel (x, y): X0 = Minv0 x + Minv1 y
+ *            + Minv2 (left to right, no fused multiply-add), Y0, W0 likewise; W = W0 ? 32 / W0 : 0; X = rint(min(max(X0 W,
+ *            -2^31), 2^31 - 1)) (half to even; a NaN takes -2^31), Y likewise; sx = clamp(X >> 5, -32768, 32767), ax = X & 31;
+ *            per channel out = ((32-ax)(32-ay) p00 + ax (32-ay) p01 + (32-ax) ay p10 + ax ay p11 + 512) >> 10 over the taps
+ *            src[sy, sx], src[sy, sx+1], src[sy+1, sx], src[sy+1, sx+1], a tap outside the source being 0
+ *   blend    direct_blend = 1: the base picture overwrites the canvas at (off_x, off_y).  0: inside that rectangle
+ *            out = (base + warped) >> 1 per channel where any channel of the warped pixel is non-zero, else base
+ *   out      canvas_h x canvas_w x 3 uint8, rows contiguous
+ * One fused kernel launch over the canvas: no intermediate canvas, no atomics.  The outputs are a function of the picture
+ * bytes, M and the geometry alone: the same bytes from every entry point below, whatever else is in a batch.
+ * Batch: n_problems problems in the same single launch, each with its own pictures (HOST arrays of pointers - device pointers
+ * for the _device form; problems may share pictures), shapes, M (n_problems x 9), canvas size, offsets and blend mode (HOST
+ * arrays); problem p writes its canvas at out + out_offset[p] bytes (a HOST array; the canvases must not overlap).  One small
+ * upload and one kernel launch, whatever n_problems; every problem's canvas equals, byte for byte, its own single call's
+ * (the single call is the batch of one).
+ * Refused before any device is touched: null pointers, picture or canvas sides outside 1 .. APAP_IMAGE_WARP_MAX_SIDE, a base
+ * picture that does not fit the canvas at the offsets (negative offsets included), direct_blend other than 0 or 1, a
+ * non-finite M, det3(M) = 0 or an inverse that is not finite, n_problems outside 1 .. APAP_IMAGE_WARP_MAX_PROBLEMS, negative
+ * or overlapping output offsets, a short (APAP_ERR_WORKSPACE) or misaligned workspace (256 bytes).  Without a GPU the
+ * host-buffer forms return APAP_ERR_NO_DEVICE: there is no CPU fallback.
+ * The _device forms only enqueue on `stream` and do not wait.  d_work: at least apap_image_warp_workspace_bytes(n_problems)
+ * bytes (0 for an invalid count; a 256-byte multiple): 144 bytes per problem, no contract on its contents.  d_status (may be
+ * NULL) is the status word of the other resident entry points; this kernel has no condition to report and never writes it. */
+#define APAP_IMAGE_WARP_MAX_SIDE 32767
+#define APAP_IMAGE_WARP_MAX_PROBLEMS 65535
+int apap_image_warp_bounds(int h1, int w1, int h2, int w2, const double *H, int *out);
+size_t apap_image_warp_workspace_bytes(int n_problems);
+int apap_image_warp(apap_ctx *ctx, const uint8_t *base, int h1, int w1, const uint8_t *src, int h2, int w2, const double *M,
+                    int canvas_w, int canvas_h, int off_x, int off_y, int direct_blend, uint8_t *out, int device);
+int apap_image_warp_device(apap_ctx *ctx, const uint8_t *d_base, int h1, int w1, const uint8_t *d_src, int h2, int w2, const double *M,
+                           int canvas_w, int canvas_h, int off_x, int off_y, int direct_blend, uint8_t *d_out, void *d_work,
+                           size_t work_bytes, int *d_status, void *stream);
+int apap_image_warp_batch(apap_ctx *ctx, const uint8_t *const *bases, const int *base_h, const int *base_w, const uint8_t *const *srcs,
+                          const int *src_h, const int *src_w, const double *M, const int *canvas_w, const int *canvas_h,
+                          const int *off_x, const int *off_y, const int *direct_blend, int n_problems, uint8_t *out,
+                          const long long *out_offset, int device);
+int apap_image_warp_batch_device(apap_ctx *ctx, const uint8_t *const *d_bases, const int *base_h, const int *base_w,
+                                 const uint8_t *const *d_srcs, const int *src_h, const int *src_w, const double *M, const int *canvas_w,
+                                 const int *canvas_h, const int *off_x, const int *off_y, const int *direct_blend, int n_problems,
+                                 uint8_t *d_out, const long long *out_offset, void *d_work, size_t work_bytes, int *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
