@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import sys
+from typing import NamedTuple
 
 import numpy as np
 
@@ -213,6 +214,15 @@ SIGNATURES = {
                                         _i32p, _i32p, _i32p, _i32p, C.c_int, _u8p, _i64p, C.c_int]),
     "apap_image_warp_batch_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, C.POINTER(C.c_void_p), _i32p, _i32p, _f64p,
                                                _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int, _vp, _i64p, _vp, C.c_size_t, _vp, _vp]),
+    "apap_panorama_bounds": (C.c_int, [C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, _i32p]),
+    "apap_panorama_workspace_bytes": (C.c_size_t, [_i32p, _i32p, _i32p, _i32p, C.c_int]),
+    "apap_panorama_mean_of": (C.c_uint, [C.c_uint, C.c_uint]),
+    "apap_panorama": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.POINTER(C.c_void_p), _i32p, _i32p, C.POINTER(C.c_void_p), _i32p, _i32p,
+                                C.POINTER(C.c_void_p), _i32p, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int, C.c_int,
+                                _u8p, _i32p, C.c_int]),
+    "apap_panorama_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_void_p), _i32p, _i32p, C.POINTER(C.c_void_p), _i32p,
+                                       _i32p, C.POINTER(C.c_void_p), _i32p, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, _i32p, _i32p,
+                                       C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp]),
 }
 
 _lib = None
@@ -1184,3 +1194,92 @@ def image_warp(base, src, M, canvas_w, canvas_h, off_x, off_y, direct_blend=True
                                 src.shape[1], _ptr(M, C.c_double), canvas_w, canvas_h, int(off_x), int(off_y), 1 if direct_blend else 0,
                                 _ptr(out, C.c_uint8), device))
     return out
+
+
+# ---------------------------------------------------------------- panorama: every view of a case on one canvas
+PANORAMA_MAX_LAYERS = 16            # APAP_PANORAMA_MAX_LAYERS
+PANORAMA_MEAN, PANORAMA_PASTE = 0, 1
+PANORAMA_MODES = {"mean": PANORAMA_MEAN, "paste": PANORAMA_PASTE}
+
+
+class PanoramaLayer(NamedTuple):
+    """One neighbour of a panorama: what ``APAP.local_warp`` takes for its pair.  ``img`` (h, w, 3) uint8, ``local_homography``
+    the forward grid (rows, cols, 3, 3) float32, ``mesh`` = (mesh_w, mesh_h) edges, ``final_size`` = (width, height) of the
+    pair canvas, ``offset`` = (x, y) of the centre picture on it."""
+    img: object
+    local_homography: object
+    mesh: object
+    final_size: object
+    offset: object
+
+
+def panorama_mode(blend, who="panorama"):
+    if blend not in PANORAMA_MODES:
+        raise ValueError(f"{who}: blend must be 'mean' or 'paste'; got {blend!r}")
+    return PANORAMA_MODES[blend]
+
+
+def panorama_geometry(layers, who="panorama"):
+    """The int32 tables (final_w, final_h, off_x, off_y) of ``layers`` (PanoramaLayer-like objects or 5-tuples)."""
+    layers = [l if isinstance(l, PanoramaLayer) else PanoramaLayer(*l) for l in layers]
+    if not 1 <= len(layers) <= PANORAMA_MAX_LAYERS:
+        raise ValueError(f"{who}: {len(layers)} layers (1 .. {PANORAMA_MAX_LAYERS})")
+    geo = np.array([[int(l.final_size[0]), int(l.final_size[1]), int(l.offset[0]), int(l.offset[1])] for l in layers], dtype=np.int64)
+    if np.abs(geo).max() >= 2 ** 31:
+        raise ValueError(f"{who}: canvas geometry beyond int32")
+    return layers, [np.ascontiguousarray(geo[:, k], dtype=np.int32) for k in range(4)]
+
+
+def panorama_bounds(center_shape, final_w, final_h, off_x, off_y):
+    """``apap_panorama_bounds`` (host only): (W, H, OX, OY) of the union canvas; ValueError when the centre does not fit a
+    pair canvas or the canvas has 2^31 pixels or more."""
+    arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in (final_w, final_h, off_x, off_y)]
+    out = np.zeros(4, np.int32)
+    check(lib().apap_panorama_bounds(int(center_shape[0]), int(center_shape[1]), *[_ptr(a, C.c_int) for a in arrs], int(arrs[0].size),
+                                     _ptr(out, C.c_int)))
+    return tuple(int(v) for v in out)
+
+
+def panorama_mean_of(total, count):
+    """``apap_panorama_mean_of``: the kernel's multiply-and-shift division on the host."""
+    return int(lib().apap_panorama_mean_of(int(total), int(count)))
+
+
+def panorama(center, layers, blend="mean", device=-1, ctx=None, return_status=False):
+    """``apap_panorama``: the centre picture and every layer (a :class:`PanoramaLayer` or a 5-tuple in its order) on one canvas.
+    Returns ``(canvas (H, W, 3) uint8, (W, H, OX, OY))`` - with ``return_status=True`` also the per-layer status words, and
+    then a status does not raise.  Neither the grids nor any other input is modified."""
+    who = "panorama"
+    mode = panorama_mode(blend, who)
+    layers, (fw, fh, ox, oy) = panorama_geometry(layers, who)
+    n = len(layers)
+    center = np.ascontiguousarray(center, dtype=np.uint8)
+    if center.ndim != 3 or center.shape[2] != 3:
+        raise ValueError(f"{who}: the centre must be (h, w, 3); got {center.shape}")
+    imgs, grids, mws, mhs = [], [], [], []
+    for k, l in enumerate(layers):
+        img = np.ascontiguousarray(l.img, dtype=np.uint8)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"{who}: layer {k}: the picture must be (h, w, 3); got {img.shape}")
+        H = as_f32(l.local_homography, (3, 3))
+        if H.ndim != 4:
+            raise ValueError(f"{who}: layer {k}: the grid must be (rows, cols, 3, 3); got {H.shape}")
+        imgs.append(img)
+        grids.append(H)
+        mws.append(np.ascontiguousarray(l.mesh[0], dtype=np.float64))
+        mhs.append(np.ascontiguousarray(l.mesh[1], dtype=np.float64))
+    i32 = lambda v: np.array(v, dtype=np.int32)      # noqa: E731
+    ih, iw = i32([a.shape[0] for a in imgs]), i32([a.shape[1] for a in imgs])
+    mr, mc = i32([a.shape[0] for a in grids]), i32([a.shape[1] for a in grids])
+    nw, nh = i32([a.size for a in mws]), i32([a.size for a in mhs])
+    W, Hc, OX, OY = panorama_bounds(center.shape, fw, fh, ox, oy)
+    out = np.empty((Hc, W, 3), np.uint8)
+    status = np.zeros(n, np.int32)
+    ip, vpp = (lambda a: _ptr(a, C.c_int)), (lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs]))
+    code = lib().apap_panorama(_h(ctx), _ptr(center, C.c_uint8), center.shape[0], center.shape[1], vpp(imgs), ip(ih), ip(iw), vpp(grids),
+                               ip(mr), ip(mc), vpp(mws), ip(nw), vpp(mhs), ip(nh), ip(fw), ip(fh), ip(ox), ip(oy), n, mode,
+                               _ptr(out, C.c_uint8), ip(status), device)
+    if return_status and code in (ERR_SINGULAR, ERR_INDEX):
+        return out, (W, Hc, OX, OY), status
+    check(code)
+    return (out, (W, Hc, OX, OY), status) if return_status else (out, (W, Hc, OX, OY))

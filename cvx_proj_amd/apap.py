@@ -14,7 +14,7 @@ the inputs come from ``--pair``)::
                                 [--data-root DIR | --pair pair.npz | --synth C1]
                                 [--config configs/case1.txt] [--out-prefix ../diff_1/results/]
                                 [--mesh-size 100] [--gamma 0.5] [--sigma 100] [--warp out.npy | --stitch out.npy]
-                                [--resident] [--timing]
+                                [--panorama pano.npy] [--resident] [--timing]
 
 The command goes through the host-buffer entry points of the C ABI (``apap_local_homography_pts``, ``apap_local_warp``,
 ``apap_invert_normalize_flatten``): no torch in the process - a pair is ~1 ms of GPU work, importing torch costs 2 s.
@@ -30,10 +30,11 @@ import warnings
 import numpy as np
 
 from . import _native
-from .apap_utils import final_size, get_mesh, get_vertice, uniform_blend  # noqa: F401  (re-exported like the reference)
+from ._native import PanoramaLayer
+from .apap_utils import final_size, get_mesh, get_vertice, panorama_size, uniform_blend  # noqa: F401  (re-exported like the reference)
 
-__all__ = ["APAP", "LazyWeights", "get_mesh", "get_vertice", "final_size", "uniform_blend", "save2mat", "run_pair",
-           "run_pair_by_calls", "main"]
+__all__ = ["APAP", "LazyWeights", "PanoramaLayer", "panorama", "panorama_layer", "panorama_size", "get_mesh", "get_vertice", "final_size",
+           "uniform_blend", "save2mat", "run_pair", "run_pair_by_calls", "main"]
 
 
 class LazyWeights:
@@ -261,6 +262,40 @@ class APAP:
         return out
 
 
+def panorama(center_img, layers, blend="mean", device=-1, ctx=None):
+    """Every view of a case on one canvas, in one fused pass on the GPU: ``center_img`` and each :class:`PanoramaLayer`
+    (the neighbour's picture, its grid from :meth:`APAP.local_homography`, its mesh, and the ``final_size`` / offsets of its
+    pair - what :meth:`APAP.local_warp` takes), warped through its own grid.  The reference stitches one pair at a time
+    (run_all.sh: views 1, 2, 4, 5 onto view 3) and never composes them; every piece of the composition is its own:
+    ``local_warp`` for a layer, ``final_size`` for its place, ``uniform_blend`` for the blend.
+
+    The canvas (:func:`panorama_size`) puts the centre at ``(OX, OY) = (max offset_x, max offset_y)``; layer k is
+    ``local_warp`` of its pair, byte for byte, at column ``OX - offset_x``, row ``OY - offset_y``.  ``blend="mean"``:
+    ``uniform_blend`` made symmetric in any number of pictures - per channel the truncated mean of the values with a non-zero
+    byte (one layer: :meth:`APAP.local_stitch`).  ``blend="paste"``: the centre inside its rectangle, black pixels included,
+    elsewhere the first layer with a non-zero byte (the rule of ``image_warping(direct_blend=True)``).
+
+    Returns ``(canvas (H, W, 3) uint8, (W, H, OX, OY))``.  The grids are not modified.  A singular cell raises
+    ``LinAlgError``, mesh edges that do not cover a pair canvas ``IndexError``, as ``local_warp`` of that layer would, with
+    the layer's index in the message."""
+    return _native.panorama(center_img, layers, blend=blend, device=device, ctx=ctx)
+
+
+def panorama_layer(src, dst, H_global, other_img, center_shape, mesh_size=100, gamma=0.5, sigma=100, device=-1, ctx=None):
+    """The :class:`PanoramaLayer` of one pair by the calls of the reference's ``__main__`` (apap.py:238-242): ``final_size``,
+    ``get_mesh``, ``get_vertice`` and ``local_homography`` of the keypoints ``src`` -> ``dst`` with the seed ``H_global``."""
+
+    class _S:
+        def __init__(self, shape):
+            self.shape = shape
+
+    fw, fh, ox, oy = (int(v) for v in final_size(_S(center_shape), _S(other_img.shape), H_global))
+    mesh = get_mesh((fw, fh), mesh_size + 1)
+    vertices = get_vertice((fw, fh), mesh_size, (ox, oy))
+    H, _ = APAP(gamma, sigma, [fw, fh], [ox, oy], device=device, ctx=ctx).local_homography(src, dst, vertices, return_weights=False)
+    return PanoramaLayer(other_img, H, mesh, (fw, fh), (ox, oy))
+
+
 # ------------------------------------------------------------------------------------
 # CLI: apap.py:220-265
 # ------------------------------------------------------------------------------------
@@ -356,6 +391,10 @@ def main(argv=None):
     ap.add_argument("--warp", help="also run local_warp and save the canvas to this .npy")
     ap.add_argument("--stitch", help="run the fused warp + blend with the centre image (the reference's "
                                      "commented-out tail, apap.py:258-262) and save the canvas to this .npy")
+    ap.add_argument("--panorama", help="stitch ALL the listed pictures of a case (--cases c --imgs i,j,...) onto its centre "
+                                       "picture in one fused pass and save the canvas to this .npy (several cases: the case "
+                                       "index goes before the extension)")
+    ap.add_argument("--panorama-blend", choices=("mean", "paste"), default="mean")
     ap.add_argument("--device", type=int, default=-1)
     ap.add_argument("--resident", action="store_true",
                     help="one resident pass per pair through cvx_proj_amd.pipeline (imports torch: ~2 s more start-up, ~0.3 ms less "
@@ -376,6 +415,11 @@ def main(argv=None):
     if not (a.pair or a.data_root or a.synth):
         ap.error("the reference's dataset (../diff_1) is not distributed: give --data-root, --pair or --synth")
     jobs = _parse_jobs(a, ap)
+    if a.panorama and (a.resident or a.warp or a.stitch):
+        ap.error("--panorama goes through the host-buffer entry points and writes one canvas per case: not with --resident, "
+                 "--warp or --stitch")
+    want_other, want_center = bool(a.warp or a.stitch or a.panorama), bool(a.stitch or a.panorama)
+    panoramas = {}      # case -> (centre picture, layers in the order of --imgs)
     stages = {"imports_ms": (time.perf_counter() - t_start) * 1e3}
 
     pipeline = None
@@ -397,8 +441,8 @@ def main(argv=None):
             z = np.load(a.pair)
             src, dst, Hg = z["src"], z["dst"], z["H"]
             other_shape, center_shape = tuple(z["other_shape"]), tuple(z["center_shape"])
-            other_img = z["other_img"] if ((a.warp or a.stitch) and "other_img" in z) else None
-            center_img = z["center_img"] if (a.stitch and "center_img" in z) else None
+            other_img = z["other_img"] if (want_other and "other_img" in z) else None
+            center_img = z["center_img"] if (want_center and "center_img" in z) else None
         elif a.data_root:
             from .baseline_stitch_test import CENTER_PIC_ID, visualize_feature_pairs
             from .utils import equalize_hist, get_no_scat_img, get_path, imread
@@ -417,9 +461,9 @@ def main(argv=None):
             src, dst, Hg = visualize_feature_pairs(None, None, case_idx=case_idx, pic_id=img_idx, swap=True,
                                                    root=a.data_root, device=a.device)
             other_img = center_img = None
-            if a.warp or a.stitch:      # the blend uses the haze-free pictures (apap.py:245,258-262)
+            if want_other:      # the blend uses the haze-free pictures (apap.py:245,258-262)
                 center_img, other_img = get_no_scat_img(case_idx, img_idx, CENTER_PIC_ID, root=a.data_root)
-                if not a.stitch:
+                if not want_center:
                     center_img = None
         else:
             from .synth import CONFIGS, synth_pair
@@ -428,11 +472,17 @@ def main(argv=None):
                 mesh_size = m
             # in a loop every (case, picture) is a pair of its own: the first one is the configuration's own seed
             seed += (case_idx - jobs[0][0]) * 16 + (img_idx - jobs[0][1])
-            p = synth_pair(w, h, n, mesh_size, seed, with_image=bool(a.warp or a.stitch))
+            p = synth_pair(w, h, n, mesh_size, seed, with_image=want_other)
             src, dst, Hg, other_shape, center_shape, other_img = p.src, p.dst, p.Hg, p.shape, p.shape, p.img
-            center_img = (np.random.default_rng(seed + 1).integers(0, 256, p.shape, dtype=np.uint8) if a.stitch else None)
+            center_img = (np.random.default_rng(seed + 1).integers(0, 256, p.shape, dtype=np.uint8) if want_center else None)
         t1 = time.perf_counter()
-        if pipeline is not None:
+        if a.panorama:
+            if other_img is None or center_img is None:
+                raise ValueError("--panorama needs the pictures of every pair (other_img and center_img)")
+            layer = panorama_layer(src, dst, Hg, other_img, center_shape, mesh_size, par["gamma"], par["sigma"], device=a.device)
+            flat, warped = _native.invert_normalize_flatten(layer.local_homography, device=a.device), None
+            panoramas.setdefault(case_idx, (center_img, []))[1].append(layer)   # a case's centre: its first pair's
+        elif pipeline is not None:
             flat, warped = run_pair(src, dst, Hg, other_shape, center_shape, mesh_size, par["gamma"], par["sigma"],
                                     other_img=other_img, center_img=center_img, device=a.device, pipeline=pipeline)
         else:
@@ -451,6 +501,16 @@ def main(argv=None):
             np.save(out, warped)
         stages["pairs"].append({"case": case_idx, "img": img_idx, "inputs_ms": (t1 - t0) * 1e3, "compute_ms": (t2 - t1) * 1e3,
                                 "save_ms": (time.perf_counter() - t2) * 1e3})
+    for case_idx, (center_img, layers) in panoramas.items():
+        t0 = time.perf_counter()
+        canvas, bounds = panorama(center_img, layers, blend=a.panorama_blend, device=a.device)
+        out = a.panorama
+        if len(panoramas) > 1:
+            root, ext = os.path.splitext(out)
+            out = f"{root}_case{case_idx}{ext}"
+        np.save(out, canvas)
+        stages.setdefault("panoramas", []).append({"case": case_idx, "layers": len(layers), "bounds": list(bounds),
+                                                   "ms": (time.perf_counter() - t0) * 1e3})
     stages["total_ms"] = (time.perf_counter() - t_start) * 1e3
     if a.timing:
         import json

@@ -1240,4 +1240,77 @@ int apap_image_warp(apap_ctx *ctx, const uint8_t *base, int h1, int w1, const ui
                                  device);
 }
 
+// ------------------------------------------------------------------ panorama (apap_panorama.hip)
+// `status` (may be NULL) receives the n_layers status words whatever the call returns once the kernels ran.
+int apap_panorama(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs, const int *img_h,
+                  const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols, const double *const *mesh_w,
+                  const int *n_w, const double *const *mesh_h, const int *n_h, const int *final_w, const int *final_h, const int *off_x,
+                  const int *off_y, int n_layers, int mode, uint8_t *out, int *status, int device) {
+    const char *who = "apap_panorama";
+    int b[4];
+    int rc = apap::panorama_check(center_h, center_w, img_h, img_w, mesh_rows, mesh_cols, n_w, n_h, final_w, final_h, off_x, off_y,
+                                  n_layers, mode, b, who);
+    if (rc) return rc;
+    if (!center || !imgs || !Hfwd || !mesh_w || !mesh_h || !out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    for (int k = 0; k < n_layers; ++k)
+        if (!imgs[k] || !Hfwd[k] || !mesh_w[k] || !mesh_h[k]) return apap::fail(APAP_ERR_INVALID_ARG, "%s: layer %d: null pointer", who, k);
+    // the distinct pictures (layers may share one), uploaded once each; picture 0 is the centre
+    struct Pic { const uint8_t *host; size_t bytes; };
+    std::vector<Pic> pics{Pic{center, (size_t)center_h * center_w * 3}};
+    std::vector<int> pic_of((size_t)n_layers);
+    std::map<std::pair<const uint8_t *, size_t>, int> seen;
+    for (int k = 0; k < n_layers; ++k) {
+        const size_t bytes = (size_t)img_h[k] * img_w[k] * 3;
+        const auto it = seen.emplace(std::make_pair(imgs[k], bytes), (int)pics.size());
+        if (it.second) pics.push_back(Pic{imgs[k], bytes});
+        pic_of[k] = it.first->second;
+    }
+    std::vector<int> st((size_t)n_layers, 0);       // before the HostCall: a download writes it
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    Layout l_img = call.layout(S_IMG), l_h = call.layout(S_H), l_mw = call.layout(S_MESHW), l_mh = call.layout(S_MESHH);
+    std::vector<Part> d_pic(pics.size(), Part{}), d_h((size_t)n_layers, Part{}), d_mw((size_t)n_layers, Part{}), d_mh((size_t)n_layers, Part{});
+    for (size_t k = 0; k < pics.size(); ++k) d_pic[k] = l_img.take(pics[k].bytes);
+    for (int k = 0; k < n_layers; ++k) {
+        d_h[k] = l_h.take((size_t)mesh_rows[k] * mesh_cols[k] * 9 * sizeof(float));
+        d_mw[k] = l_mw.take((size_t)n_w[k] * sizeof(double));
+        d_mh[k] = l_mh.take((size_t)n_h[k] * sizeof(double));
+    }
+    call.alloc(l_img); call.alloc(l_h); call.alloc(l_mw); call.alloc(l_mh);
+    const Part d_out = call.slot(S_OUT, (size_t)b[0] * b[1] * 3);
+    const Part d_status = call.slot(S_STATUS, (size_t)n_layers * sizeof(int));
+    const Part work = call.slot(S_WORK, apap_panorama_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h, n_layers));
+    for (size_t k = 0; k < pics.size(); ++k) call.up(d_pic[k], pics[k].host);
+    for (int k = 0; k < n_layers; ++k) {
+        call.up(d_h[k], Hfwd[k]);
+        call.up(d_mw[k], mesh_w[k]);
+        call.up(d_mh[k], mesh_h[k]);
+    }
+    call.zero(d_status);
+    if ((rc = call.rc())) return rc;
+    std::vector<const uint8_t *> p_img((size_t)n_layers);
+    std::vector<const float *> p_h((size_t)n_layers);
+    std::vector<const double *> p_mw((size_t)n_layers), p_mh((size_t)n_layers);
+    for (int k = 0; k < n_layers; ++k) {
+        p_img[k] = d_pic[pic_of[k]].as<const uint8_t>();
+        p_h[k] = d_h[k].as<const float>();
+        p_mw[k] = d_mw[k].as<const double>();
+        p_mh[k] = d_mh[k].as<const double>();
+    }
+    rc = apap_panorama_device(ctx, d_pic[0].as<const uint8_t>(), center_h, center_w, p_img.data(), img_h, img_w, p_h.data(), mesh_rows,
+                              mesh_cols, p_mw.data(), n_w, p_mh.data(), n_h, final_w, final_h, off_x, off_y, n_layers, mode,
+                              d_out.as<uint8_t>(), work.as<void>(), work.bytes, d_status.as<int>(), call.stream());
+    if (rc) return rc;
+    call.down(st.data(), d_status);
+    call.down(out, d_out);
+    if ((rc = call.wait())) return rc;
+    if (status) std::copy(st.begin(), st.end(), status);
+    for (int k = 0; k < n_layers; ++k) {
+        char layer[48];
+        snprintf(layer, sizeof(layer), "%s: layer %d", who, k);
+        if ((rc = status_to_code(st[k], layer))) return rc;
+    }
+    return APAP_OK;
+}
+
 }  // extern "C"

@@ -93,6 +93,22 @@ int warp_phase(apap_ctx *ctx, const uint8_t *d_img, int img_h, int img_w, const 
                int n_h, int final_w, int final_h, int off_x, int off_y, uint8_t *d_out_band, float *d_Hinv_out, void *d_work,
                size_t work_bytes, int *d_status, void *stream, int row_begin, int row_count, int phase, int **d_src_rows);
 
+// Where the set-up phases (kWarpSetup) leave the exact path's tables in a single-pair warp workspace, on the fast-table
+// path and on the linear-scan path alike: hinv_pad [cells][APAP_HINV_STRIDE] f64, the cells' inverses widened, and lut
+// [final_h + final_w] i32, canvas row -> cell row, then canvas column -> cell column (every entry a valid index, also where
+// the set-up reported APAP_STATUS_INDEX).  Launches nothing.
+struct WarpTables {
+    const double *hinv_pad;
+    const int *lut;
+};
+WarpTables warp_tables(void *d_work, int mesh_rows, int mesh_cols, int final_w, int final_h);
+
+// The argument checks of the panorama's entry points (apap_panorama.hip) that need no device pointer; fills bounds[4] =
+// W, H, OX, OY.
+int panorama_check(int center_h, int center_w, const int *img_h, const int *img_w, const int *mesh_rows, const int *mesh_cols,
+                   const int *n_w, const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y,
+                   int n_layers, int mode, int *bounds, const char *who);
+
 constexpr int kMoments = 30;       // distinct sums of A^T W^2 A
 
 // The spectral weights (apap_spectral.hip).  spectral_run is apap_spectral_device; with sync_each = 1 (the host-buffer

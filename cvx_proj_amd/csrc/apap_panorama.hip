@@ -1,0 +1,406 @@
+// Panorama: the centre picture and up to APAP_PANORAMA_MAX_LAYERS neighbours, each warped through its own local-homography
+// grid, on ONE canvas in one fused pass (DESIGN.md "Panorama"; the numpy definition is tests/panorama_spec.py).
+//
+// Geometry.  Layer k has what local_warp takes for one pair: a source picture, a forward grid, mesh edges, the pair canvas
+// (fw_k, fh_k) and the offsets (ox_k, oy_k) at which the centre sits on it.  The union canvas puts the centre at
+// (OX, OY) = (max ox_k, max oy_k) and is W = OX + max(fw_k - ox_k) wide, H = OY + max(fh_k - oy_k) high; pair canvas k
+// covers its columns [OX - ox_k, OX - ox_k + fw_k) and rows [OY - oy_k, OY - oy_k + fh_k).  The value of layer k at
+// canvas pixel (X, Y) is local_warp_k[Y - OY + oy_k, X - OX + ox_k] inside that rectangle and black outside it.  The
+// point the cell's inverse is applied to is (X - OX, Y - OY) for EVERY layer: a pixel's coordinates relative to the centre
+// do not depend on the pair canvas it is seen through.
+//
+// Set-up: per layer the warp's own set-up launch (apap::warp_phase with kWarpSetup) into that layer's slice of the
+// workspace; it leaves the cell inverses and the row / column -> cell tables (apap::warp_tables).
+//
+// k_panorama<mode>: K3's row-strip shape.  A lane owns 4 consecutive pixels of a canvas row, a wave a strip of kRows rows
+// of 256 pixels, a block kWaves strips below each other.  The layer descriptors travel BY VALUE in the kernel argument
+// (1 KB; no upload); the loop over layers is wave-uniform, a strip tests a layer's rectangle with scalar compares and
+// skips the layers it does not touch.  Per layer the lane looks up its four cell columns, the wave its rows' cell rows, and
+// the coordinates come from k_warp_rows' arithmetic (pixel_h, the float64 chain, the strict bounds test, the truncation):
+// the same device functions (apap_warp_dev.h), the same bits.  A layer's state (cell matrices, offsets, gathered pixels)
+// is dead before the next layer starts: the registers do not grow with the layer count.
+//   mean : per pixel the channel sums and the number of present values (any byte non-zero) in two registers
+//          (ch0 | ch2 << 16, ch1 | count << 16; at most 17 x 255 per sum); the quotient is one multiply and shift with
+//          ceil(2^18 / count) from a 18-entry LDS table (mean_recip / mean_div: exact for these ranges, checked exhaustively
+//          on the host through apap_panorama_mean_of).
+//   paste: inside the centre's rectangle the centre, unconditionally; outside it the first present layer.  A pixel that is
+//          decided is not computed again, and once a ballot shows a whole strip decided the wave leaves the layer loop - a
+//          strip wholly inside the centre's rectangle computes no coordinate at all.
+// The canvas is written once with 12-byte non-temporal stores (a row's tail byte by byte, never past the row).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+
+#include "apap_internal.h"
+#include "apap_warp_dev.h"
+
+namespace {
+
+inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
+
+constexpr int kMaxLayers = APAP_PANORAMA_MAX_LAYERS;
+constexpr int kRows = 4;            // canvas rows of a strip (one wave)
+constexpr int kWaves = 4;           // strips of a block
+constexpr int kStripCols = 256;     // 64 lanes x 4 pixels
+constexpr unsigned kMeanShift = 18;
+
+// floor(sum / count) for count = 1 .. 17 and sum <= 255 count as (sum * mean_recip(count)) >> 18: with m = ceil(2^18 / count)
+// the error m count - 2^18 is below count, and sum * 17 < 2^18, so the product's floor is the quotient's; count = 0 gives 0.
+__host__ __device__ inline unsigned mean_recip(unsigned count) { return count ? ((1u << kMeanShift) - 1u) / count + 1u : 0u; }
+__host__ __device__ inline unsigned mean_div(unsigned sum, unsigned recip) { return (sum * recip) >> kMeanShift; }
+
+struct PanoLayer {      // 64 bytes
+    const uint8_t *img;
+    const double *hinv_pad;     // [cells][APAP_HINV_STRIDE]
+    const int *lut;             // [fh] cell row of a pair-canvas row, then [fw] cell column of a pair-canvas column
+    int img_h, img_w, mesh_cols, fw, fh;
+    int dx, dy;                 // the union-canvas column / row of the pair canvas' first: OX - ox, OY - oy
+    unsigned last;              // bytes of the source - 4 (gather_px)
+    int pad[2];
+};
+static_assert(sizeof(PanoLayer) == 64, "the descriptor's size in the kernel argument");
+
+struct PanoArgs {
+    PanoLayer layer[kMaxLayers];
+    const uint8_t *center;
+    uint8_t *out;
+    int center_h, center_w, OX, OY, W, H, n_layers, col_blocks;
+    unsigned clast;             // bytes of the centre - 4
+    int pad;
+};
+static_assert(sizeof(PanoArgs) <= 4096, "kernel arguments");
+
+template <int kMode>
+__global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
+    __shared__ unsigned recip[32];
+    if (kMode == APAP_PANORAMA_MEAN) {
+        if (threadIdx.x < 32) recip[threadIdx.x] = threadIdx.x <= (unsigned)kMaxLayers + 1u ? mean_recip(threadIdx.x) : 0u;
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned row_block = blockIdx.x / (unsigned)A.col_blocks;
+    const int x_wave = (int)(blockIdx.x - row_block * (unsigned)A.col_blocks) * kStripCols;
+    const int j0 = x_wave + lane * 4;
+    const int y_first = ((int)row_block * kWaves + wave) * kRows;
+    const int y_end = min(y_first + kRows, A.H);
+    if (j0 >= A.W || y_first >= y_end) return;
+    const int npx = min(4, A.W - j0);
+    double xs[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) xs[k] = (double)(j0 + k - A.OX);
+
+    // the centre's pixels of the strip; bit 4 t + k of `live`: pixel k of row t is on the canvas
+    unsigned live = 0u;
+    unsigned und = 0u;                  // paste: live pixels no picture has decided yet
+    unsigned a0[kRows][4], a1[kRows][4];    // mean: ch0 | ch2 << 16 and ch1 | count << 16; paste: a0 = the pixel
+    {
+        const uint8_t *__restrict__ center = A.center;
+        unsigned co[kRows][4];
+#pragma unroll
+        for (int t = 0; t < kRows; ++t) {
+            const int ci = y_first + t - A.OY;
+            const bool row_on = y_first + t < y_end;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int cj = j0 + k - A.OX;
+                const bool on = row_on && k < npx;
+                const bool in = on && (unsigned)ci < (unsigned)A.center_h && (unsigned)cj < (unsigned)A.center_w;
+                live |= (unsigned)on << (4 * t + k);
+                und |= (unsigned)(on && !in) << (4 * t + k);
+                co[t][k] = in ? ((unsigned)ci * (unsigned)A.center_w + (unsigned)cj) * 3u : 0xffffffffu;
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < kRows; ++t) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned c = gather_px(center, co[t][k], A.clast);
+                if (kMode == APAP_PANORAMA_MEAN) {
+                    a0[t][k] = c & 0x00ff00ffu;
+                    a1[t][k] = ((c >> 8) & 0xffu) | ((unsigned)(c != 0u) << 16);
+                } else {
+                    a0[t][k] = c;
+                    a1[t][k] = 0u;
+                }
+            }
+        }
+    }
+
+    for (int l = 0; l < A.n_layers; ++l) {      // wave-uniform
+        if (kMode == APAP_PANORAMA_PASTE && __all(und == 0u)) break;
+        const PanoLayer &L = A.layer[l];
+        const int dx = L.dx, dy = L.dy, fw = L.fw, fh = L.fh;
+        // the strip against the pair canvas' rectangle: scalar compares
+        if (y_first >= dy + fh || y_end <= dy || x_wave >= dx + fw || x_wave + kStripCols <= dx) continue;
+        const int *__restrict__ lut = L.lut;
+        const double *__restrict__ hinv_pad = L.hinv_pad;
+        const uint8_t *__restrict__ img = L.img;
+        const int img_w = L.img_w, img_h = L.img_h, mesh_cols = L.mesh_cols;
+        int col[4];
+        unsigned want = 0u;             // bit 4 t + k: the pixel lies on the pair canvas (and, paste, is still undecided)
+        unsigned colin = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = j0 + k - dx;
+            colin |= (unsigned)((unsigned)j < (unsigned)fw) << k;
+            col[k] = lut[(unsigned)(fh + min(max(j, 0), fw - 1))];     // a pixel beside the pair canvas: any valid column
+        }
+        int rr[kRows];
+        unsigned todo = 0u;             // the strip's rows on the pair canvas
+#pragma unroll
+        for (int t = 0; t < kRows; ++t) {
+            const int i = y_first + t - dy;
+            const bool rowin = (unsigned)i < (unsigned)fh && y_first + t < y_end;
+            todo |= (unsigned)rowin << t;
+            want |= rowin ? colin << (4 * t) : 0u;
+            rr[t] = lut[(unsigned)min(max(i, 0), fh - 1)];
+        }
+#pragma unroll
+        for (int t = 0; t < kRows; ++t) rr[t] = __builtin_amdgcn_readfirstlane(rr[t]);
+        want &= kMode == APAP_PANORAMA_PASTE ? und : live;
+        unsigned off[kRows][4];
+#pragma unroll
+        for (int t = 0; t < kRows; ++t)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) off[t][k] = 0xffffffffu;
+        // One pass per cell row the strip touches, as in k_warp_rows: fetch that row's matrices, then do every strip row that
+        // lies in it.  All branches are wave-uniform.
+        while (todo != 0u) {
+            const int first = __builtin_ctz(todo);
+            int r = rr[0];
+#pragma unroll
+            for (int t = 1; t < kRows; ++t) r = (t == first) ? rr[t] : r;
+            const int base = r * mesh_cols;
+            const Hinv9 ha = load_hinv(hinv_pad, (unsigned)(base + col[0]));
+            const Hinv9 hb = load_hinv(hinv_pad, (unsigned)(base + col[3]));
+            PixelH q[4];
+            q[0] = pixel_h(ha, xs[0]);
+            q[3] = pixel_h(hb, xs[3]);
+#pragma unroll
+            for (int k = 1; k < 3; ++k) {
+                const bool is_a = col[k] == col[0];
+                Hinv9 hk = select_hinv(is_a, ha, hb);
+                if (!is_a && col[k] != col[3]) hk = load_hinv(hinv_pad, (unsigned)(base + col[k]));  // a third cell
+                q[k] = pixel_h(hk, xs[k]);
+            }
+#pragma unroll
+            for (int t = 0; t < kRows; ++t) {
+                if (!((todo >> t) & 1u) || rr[t] != r) continue;
+                todo &= ~(1u << t);
+                const double yd = (double)(y_first + t - A.OY);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    // k_warp_rows' sequence, operation for operation
+                    const double t0 = fma(q[k].h1, yd, q[k].p0) + q[k].h2;
+                    const double t1 = fma(q[k].h4, yd, q[k].p1) + q[k].h5;
+                    const double t2 = fma(q[k].h7, yd, q[k].p2) + q[k].h8;
+                    double rc = __builtin_amdgcn_rcp(t2);
+                    rc = fma(fma(-t2, rc, 1.0), rc, rc);
+                    const double q0 = t0 * rc, q1 = t1 * rc;
+                    const double tx = fma(fma(-t2, q0, t0), rc, q0);
+                    const double ty = fma(fma(-t2, q1, t1), rc, q1);
+                    const int ix = (int)tx, iy = (int)ty;
+                    const bool ok = (tx > 0.0) & (ty > 0.0) & (ix < img_w) & (iy < img_h) & (((want >> (4 * t + k)) & 1u) != 0u);
+                    off[t][k] = ok ? (__umul24((unsigned)iy, (unsigned)img_w) + (unsigned)ix) * 3u : 0xffffffffu;
+                }
+            }
+        }
+        const unsigned last = L.last;
+        unsigned px[kRows][4];
+#pragma unroll
+        for (int t = 0; t < kRows; ++t)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) px[t][k] = gather_px(img, off[t][k], last);
+#pragma unroll
+        for (int t = 0; t < kRows; ++t) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned v = px[t][k];
+                if (kMode == APAP_PANORAMA_MEAN) {
+                    a0[t][k] += v & 0x00ff00ffu;
+                    a1[t][k] += ((v >> 8) & 0xffu) | ((unsigned)(v != 0u) << 16);
+                } else {
+                    // off is the outside marker for every pixel that is decided: v != 0 only where the pixel is still open
+                    a0[t][k] = v != 0u ? v : a0[t][k];
+                    und &= ~((unsigned)(v != 0u) << (4 * t + k));
+                }
+            }
+        }
+    }
+
+#pragma unroll
+    for (int t = 0; t < kRows; ++t) {
+        const int y = y_first + t;
+        if (y >= y_end) break;  // wave-uniform
+        unsigned p[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (kMode == APAP_PANORAMA_MEAN) {
+                const unsigned m = recip[a1[t][k] >> 16] & 0x7ffffu;
+                p[k] = mean_div(a0[t][k] & 0xffffu, m) | (mean_div(a1[t][k] & 0xffffu, m) << 8) | (mean_div(a0[t][k] >> 16, m) << 16);
+            } else {
+                p[k] = a0[t][k];
+            }
+        }
+        uint8_t *o = A.out + ((size_t)y * (size_t)A.W + (size_t)j0) * 3u;
+        if (npx == 4) {
+            store12_stream(o, p[0] | (p[1] << 24), __builtin_amdgcn_perm(p[2], p[1], 0x05040201u),
+                           __builtin_amdgcn_perm(p[3], p[2], 0x06050402u));
+        } else {
+            for (int k = 0; k < npx; ++k) {
+                o[3 * k] = (uint8_t)(p[k] & 0xff);
+                o[3 * k + 1] = (uint8_t)((p[k] >> 8) & 0xff);
+                o[3 * k + 2] = (uint8_t)((p[k] >> 16) & 0xff);
+            }
+        }
+    }
+}
+
+size_t slice_bytes(int mesh_rows, int mesh_cols, int final_w, int final_h) {
+    return (apap_warp_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h) + 255) / 256 * 256;
+}
+
+// W, H, OX, OY of the union canvas from the pair canvases; refuses a centre that does not fit one of them (the check of
+// apap_stitch_device) and a canvas of 2^31 pixels or more
+int bounds_of(int center_h, int center_w, const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers,
+              int *out, const char *who) {
+    if (!final_w || !final_h || !off_x || !off_y || !out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    if (n_layers < 1 || n_layers > kMaxLayers) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n_layers = %d (1 .. %d)", who, n_layers, kMaxLayers);
+    if (center_h < 1 || center_w < 1) return apap::fail(APAP_ERR_INVALID_ARG, "%s: centre picture %d x %d", who, center_h, center_w);
+    long long OX = 0, OY = 0, right = 0, below = 0;
+    for (int k = 0; k < n_layers; ++k) {
+        if (final_w[k] < 1 || final_h[k] < 1)
+            return apap::fail(APAP_ERR_INVALID_ARG, "%s: layer %d: canvas %d x %d", who, k, final_w[k], final_h[k]);
+        if (off_x[k] < 0 || off_y[k] < 0 || (long long)off_y[k] + center_h > final_h[k] || (long long)off_x[k] + center_w > final_w[k])
+            return apap::fail(APAP_ERR_INVALID_ARG, "%s: layer %d: centre image %dx%d at (%d,%d) does not fit canvas %dx%d", who, k, center_w,
+                              center_h, off_x[k], off_y[k], final_w[k], final_h[k]);
+        OX = std::max(OX, (long long)off_x[k]);
+        OY = std::max(OY, (long long)off_y[k]);
+        right = std::max(right, (long long)final_w[k] - off_x[k]);
+        below = std::max(below, (long long)final_h[k] - off_y[k]);
+    }
+    const long long W = OX + right, H = OY + below;
+    if ((unsigned long long)W * (unsigned long long)H >= (1ull << 31))
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: canvas %lld x %lld: 2^31 pixels or more", who, W, H);
+    out[0] = (int)W; out[1] = (int)H; out[2] = (int)OX; out[3] = (int)OY;
+    return APAP_OK;
+}
+
+}  // namespace
+
+namespace apap {
+
+int panorama_check(int center_h, int center_w, const int *img_h, const int *img_w, const int *mesh_rows, const int *mesh_cols,
+                   const int *n_w, const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y,
+                   int n_layers, int mode, int *bounds, const char *who) {
+    if (!img_h || !img_w || !mesh_rows || !mesh_cols || !n_w || !n_h) return fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    if (mode != APAP_PANORAMA_MEAN && mode != APAP_PANORAMA_PASTE)
+        return fail(APAP_ERR_INVALID_ARG, "%s: mode = %d (APAP_PANORAMA_MEAN or APAP_PANORAMA_PASTE)", who, mode);
+    const int rc = bounds_of(center_h, center_w, final_w, final_h, off_x, off_y, n_layers, bounds, who);
+    if (rc) return rc;
+    // a picture: at least 2 pixels (the gather reads a dword), sides below 2^24 (24-bit multiplies), below 2 GiB (the sign
+    // bit of a byte offset marks a pixel outside it)
+    const auto picture = [](int h, int w) {
+        return h >= 1 && w >= 1 && (unsigned long long)h * w >= 2 && h < (1 << 24) && w < (1 << 24) &&
+               (unsigned long long)h * (unsigned long long)w * 3ull < (1ull << 31);
+    };
+    if (!picture(center_h, center_w))
+        return fail(APAP_ERR_INVALID_ARG, "%s: centre picture %d x %d (at least 2 pixels, sides below 2^24, below 2 GiB)", who, center_h, center_w);
+    for (int k = 0; k < n_layers; ++k) {
+        if (!picture(img_h[k], img_w[k]))
+            return fail(APAP_ERR_INVALID_ARG, "%s: layer %d: picture %d x %d (at least 2 pixels, sides below 2^24, below 2 GiB)", who, k,
+                        img_h[k], img_w[k]);
+        if (mesh_rows[k] < 1 || mesh_cols[k] < 1 || n_w[k] < 1 || n_h[k] < 1)
+            return fail(APAP_ERR_INVALID_ARG, "%s: layer %d: mesh %d x %d with %d / %d edges", who, k, mesh_rows[k], mesh_cols[k], n_w[k], n_h[k]);
+        if ((unsigned long long)mesh_rows[k] * (unsigned long long)mesh_cols[k] * APAP_HINV_STRIDE * sizeof(double) >= (1ull << 32))
+            return fail(APAP_ERR_INVALID_ARG, "%s: layer %d: mesh of 53 million cells or more", who, k);
+    }
+    return APAP_OK;
+}
+
+}  // namespace apap
+
+extern "C" {
+
+unsigned apap_panorama_mean_of(unsigned sum, unsigned count) { return mean_div(sum, mean_recip(count)); }
+
+int apap_panorama_bounds(int center_h, int center_w, const int *final_w, const int *final_h, const int *off_x, const int *off_y,
+                         int n_layers, int *out) {
+    return bounds_of(center_h, center_w, final_w, final_h, off_x, off_y, n_layers, out, "apap_panorama_bounds");
+}
+
+size_t apap_panorama_workspace_bytes(const int *mesh_rows, const int *mesh_cols, const int *final_w, const int *final_h, int n_layers) {
+    if (!mesh_rows || !mesh_cols || !final_w || !final_h || n_layers < 1 || n_layers > kMaxLayers) return 0;
+    size_t total = 0;
+    for (int k = 0; k < n_layers; ++k) {
+        const size_t b = slice_bytes(mesh_rows[k], mesh_cols[k], final_w[k], final_h[k]);
+        if (b == 0) return 0;
+        total += b;
+    }
+    return total;
+}
+
+int apap_panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                         const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows, const int *mesh_cols,
+                         const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h, const int *n_h,
+                         const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode,
+                         uint8_t *d_out, void *d_work, size_t work_bytes, int *d_status, void *stream) {
+    const char *who = "apap_panorama_device";
+    int b[4];
+    int rc = apap::panorama_check(center_h, center_w, img_h, img_w, mesh_rows, mesh_cols, n_w, n_h, final_w, final_h, off_x, off_y,
+                                  n_layers, mode, b, who);
+    if (rc) return rc;
+    if (!d_center || !d_imgs || !d_Hfwd || !d_mesh_w || !d_mesh_h || !d_out || !d_work || !d_status)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
+    for (int k = 0; k < n_layers; ++k)
+        if (!d_imgs[k] || !d_Hfwd[k] || !d_mesh_w[k] || !d_mesh_h[k])
+            return apap::fail(APAP_ERR_INVALID_ARG, "%s: layer %d: null device pointer", who, k);
+    const size_t need = apap_panorama_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h, n_layers);
+    if (work_bytes < need) return apap::fail(APAP_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, work_bytes, need);
+    if (((uintptr_t)d_work & 255) != 0) return apap::fail(APAP_ERR_INVALID_ARG, "%s: workspace must be 256-byte aligned", who);
+
+    PanoArgs A;
+    std::memset(&A, 0, sizeof(A));
+    char *w = (char *)d_work;
+    for (int k = 0; k < n_layers; ++k) {
+        const size_t slice = slice_bytes(mesh_rows[k], mesh_cols[k], final_w[k], final_h[k]);
+        // the warp's own set-up, unchanged: cell inverses and lookup tables of this pair into its slice
+        rc = apap::warp_phase(ctx, nullptr, 0, 0, nullptr, 0, 0, d_Hfwd[k], mesh_rows[k], mesh_cols[k], d_mesh_w[k], n_w[k], d_mesh_h[k],
+                              n_h[k], final_w[k], final_h[k], off_x[k], off_y[k], nullptr, nullptr, w, slice, d_status + k, stream, 0, 0,
+                              apap::kWarpSetup, nullptr);
+        if (rc) return rc;
+        const apap::WarpTables t = apap::warp_tables(w, mesh_rows[k], mesh_cols[k], final_w[k], final_h[k]);
+        PanoLayer &L = A.layer[k];
+        L.img = d_imgs[k];
+        L.hinv_pad = t.hinv_pad;
+        L.lut = t.lut;
+        L.img_h = img_h[k]; L.img_w = img_w[k]; L.mesh_cols = mesh_cols[k];
+        L.fw = final_w[k]; L.fh = final_h[k];
+        L.dx = b[2] - off_x[k]; L.dy = b[3] - off_y[k];
+        L.last = (unsigned)img_h[k] * (unsigned)img_w[k] * 3u - 4u;
+        w += slice;
+    }
+    A.center = d_center;
+    A.out = d_out;
+    A.center_h = center_h; A.center_w = center_w;
+    A.W = b[0]; A.H = b[1]; A.OX = b[2]; A.OY = b[3];
+    A.n_layers = n_layers;
+    A.col_blocks = (A.W + kStripCols - 1) / kStripCols;
+    A.clast = (unsigned)center_h * (unsigned)center_w * 3u - 4u;
+    const unsigned row_blocks = (unsigned)((A.H + kWaves * kRows - 1) / (kWaves * kRows));
+    const dim3 grid((unsigned)A.col_blocks * row_blocks);       // W H < 2^31: below 2^31 blocks
+    hipStream_t s = (hipStream_t)stream;
+    {
+        apap::ProfScope prof(ctx, APAP_PROF_WARP, s);
+        if (mode == APAP_PANORAMA_MEAN) hipLaunchKernelGGL(k_panorama<APAP_PANORAMA_MEAN>, grid, dim3(kWaves * 64), 0, s, A);
+        else hipLaunchKernelGGL(k_panorama<APAP_PANORAMA_PASTE>, grid, dim3(kWaves * 64), 0, s, A);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "apap_panorama_device launch");
+    return APAP_OK;
+}
+
+}  // extern "C"

@@ -77,3 +77,30 @@ def uniform_blend(img1, img2):
     total = img1.astype(np.float64) + img2.astype(np.float64)
     total *= np.where(both, 0.5, 1.0)[..., None]
     return total.astype(np.uint8)
+
+
+def panorama_size(center_shape, layers):
+    """Union canvas of a panorama: the centre picture and every layer's pair canvas on one canvas.
+
+    ``layers``: objects with ``final_size`` = (width, height) and ``offset`` = (x, y) as :func:`final_size` returns them for
+    the layer's pair (``apap.PanoramaLayer``), or ``(final_size, offset)`` pairs.  The centre sits at ``(OX, OY) = (max
+    offset_x, max offset_y)``; the canvas is ``W = OX + max(width - offset_x)`` wide and ``H = OY + max(height - offset_y)``
+    high, and layer k's pair canvas starts at its column ``OX - offset_x`` and row ``OY - offset_y``.  Returns
+    ``(W, H, OX, OY)``; ValueError when there are no layers, when the centre does not fit a pair canvas at its offsets (what
+    the paste of the reference's stitch raises) or when the canvas has 2^31 pixels or more.
+    """
+    geo = []
+    for l in layers:
+        size, off = (l.final_size, l.offset) if hasattr(l, "final_size") else l
+        geo.append((int(size[0]), int(size[1]), int(off[0]), int(off[1])))
+    if not geo:
+        raise ValueError("panorama_size: no layers")
+    ch, cw = int(center_shape[0]), int(center_shape[1])
+    for k, (fw, fh, ox, oy) in enumerate(geo):
+        if fw < 1 or fh < 1 or ox < 0 or oy < 0 or ox + cw > fw or oy + ch > fh:
+            raise ValueError(f"panorama_size: layer {k}: centre image {cw}x{ch} at ({ox},{oy}) does not fit canvas {fw}x{fh}")
+    OX, OY = max(g[2] for g in geo), max(g[3] for g in geo)
+    W, H = OX + max(g[0] - g[2] for g in geo), OY + max(g[1] - g[3] for g in geo)
+    if W * H >= 2 ** 31:
+        raise ValueError(f"panorama_size: canvas {W} x {H}: 2^31 pixels or more")
+    return W, H, OX, OY

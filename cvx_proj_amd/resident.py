@@ -611,3 +611,70 @@ def hip_image_warp(img_base, img2warp, H, direct_blend=True, status=None, ctx=No
         img2warp.shape[1], M.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cw, ch, tx, ty, 1 if direct_blend else 0, out.data_ptr(),
         work.data_ptr(), work.numel(), status.data_ptr() if status is not None else None, _stream(dev)))
     return out
+
+
+def panorama_workspace_bytes(layers):
+    """Scratch of ``hip_panorama`` for these layers (``PanoramaLayer``-like): every layer's warp workspace, a 256-byte
+    multiple each, no contract on its contents.  0 for invalid arguments."""
+    layers, (fw, fh, _, _) = _native.panorama_geometry(layers, "panorama_workspace_bytes")
+    ip = ctypes.POINTER(ctypes.c_int)
+    mr = np.array([l.local_homography.shape[0] for l in layers], dtype=np.int32)
+    mc = np.array([l.local_homography.shape[1] for l in layers], dtype=np.int32)
+    return _native.lib().apap_panorama_workspace_bytes(mr.ctypes.data_as(ip), mc.ctypes.data_as(ip), fw.ctypes.data_as(ip),
+                                                       fh.ctypes.data_as(ip), len(layers))
+
+
+def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, work=None):
+    """``apap_panorama_device`` on the current stream of the tensors' device, no host synchronisation: the centre picture and
+    every layer on one canvas in one fused pass (``apap.panorama`` on device tensors).  ``center`` (h, w, 3) uint8; a layer is
+    a ``PanoramaLayer`` (or a 5-tuple in its order) of device tensors - ``img`` (h, w, 3) uint8, ``local_homography`` (rows,
+    cols, 3, 3) float32, ``mesh`` = (mesh_w, mesh_h) float64 - with host ``final_size`` and ``offset``; layers may share
+    tensors.  ``out``: a contiguous (H, W, 3) uint8 tensor to write into; ``status``: an int32 tensor of at least one word per
+    layer, zeroed by the caller (default: a new one), into which layer k's set-up ORs its bits at [k]; ``work`` (uint8) is
+    used when it holds ``panorama_workspace_bytes(layers)``.  Returns ``(canvas, (W, H, OX, OY), status)``, not synchronised;
+    ``_native.raise_for_status(int(status[k]), ...)`` turns a word into the reference's exception.  The grids are not
+    modified."""
+    who = "hip_panorama"
+    _needs_device(center, who)
+    dev = center.device
+    mode = _native.panorama_mode(blend, who)
+    layers, (fw, fh, ox, oy) = _native.panorama_geometry(layers, who)
+    n = len(layers)
+
+    def tensor(t, dtype, name, k):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{who}: layer {k}: {name} must be a contiguous {dtype} tensor on {dev}")
+        return t
+
+    if center.dtype != torch.uint8 or not center.is_contiguous() or center.dim() != 3 or center.shape[2] != 3:
+        raise ValueError(f"{who}: the centre must be a contiguous uint8 (h, w, 3) tensor")
+    imgs, grids, mws, mhs = [], [], [], []
+    for k, l in enumerate(layers):
+        imgs.append(tensor(l.img, torch.uint8, "img", k))
+        grids.append(tensor(l.local_homography, torch.float32, "local_homography", k))
+        mws.append(tensor(l.mesh[0], torch.float64, "mesh_w", k))
+        mhs.append(tensor(l.mesh[1], torch.float64, "mesh_h", k))
+        if imgs[k].dim() != 3 or imgs[k].shape[2] != 3 or grids[k].dim() != 4 or tuple(grids[k].shape[2:]) != (3, 3):
+            raise ValueError(f"{who}: layer {k}: img must be (h, w, 3) and local_homography (rows, cols, 3, 3)")
+    W, H, OX, OY = _native.panorama_bounds(center.shape, fw, fh, ox, oy)
+    if out is None:
+        out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"{who}: out must be a contiguous uint8 tensor of shape {(H, W, 3)} on {dev}")
+    if status is None:
+        status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if status.dtype != torch.int32 or status.numel() < n or not status.is_contiguous() or status.device != dev:
+        raise ValueError(f"{who}: status must be a contiguous int32 tensor of at least {n} words on {dev}")
+    i32 = lambda v: np.array(v, dtype=np.int32)      # noqa: E731
+    ih, iw = i32([t.shape[0] for t in imgs]), i32([t.shape[1] for t in imgs])
+    mr, mc = i32([t.shape[0] for t in grids]), i32([t.shape[1] for t in grids])
+    nw, nh = i32([t.numel() for t in mws]), i32([t.numel() for t in mhs])
+    ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))      # noqa: E731
+    vpp = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])      # noqa: E731
+    need = _native.lib().apap_panorama_workspace_bytes(ip(mr), ip(mc), ip(fw), ip(fh), n)
+    work = _scratch(work, need, dev)
+    _native.check(_native.lib().apap_panorama_device(
+        _native._h(ctx), center.data_ptr(), center.shape[0], center.shape[1], vpp(imgs), ip(ih), ip(iw), vpp(grids), ip(mr), ip(mc),
+        vpp(mws), ip(nw), vpp(mhs), ip(nh), ip(fw), ip(fh), ip(ox), ip(oy), n, mode, out.data_ptr(), work.data_ptr(), work.numel(),
+        status.data_ptr(), _stream(dev)))
+    return out, (W, H, OX, OY), status

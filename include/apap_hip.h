@@ -837,6 +837,54 @@ int apap_image_warp_batch_device(apap_ctx *ctx, const uint8_t *const *d_bases, c
                                  const int *canvas_h, const int *off_x, const int *off_y, const int *direct_blend, int n_problems,
                                  uint8_t *d_out, const long long *out_offset, void *d_work, size_t work_bytes, int *d_status, void *stream);
 
+/* ------------------------------------------------- panorama: every view of a case on one canvas ------------------------ */
+/* The centre picture (center_h x center_w x 3 uint8) and n_layers = 1 .. APAP_PANORAMA_MAX_LAYERS neighbours on one canvas,
+ * in one fused pass (DESIGN.md "Panorama"; in numpy: tests/panorama_spec.py).  Layer k holds what apap_warp_device takes for
+ * one pair - its picture (img_h[k] x img_w[k] x 3), its forward grid (mesh_rows[k] x mesh_cols[k] x 3 x 3 float32), its mesh
+ * edges, its pair canvas (final_w[k], final_h[k]) and the offsets (off_x[k], off_y[k]) of the centre on it - and layers may
+ * differ in all of them.  All per-layer arguments are HOST arrays of n_layers entries; the pointer arrays hold host pointers
+ * in apap_panorama and device pointers in apap_panorama_device (layers may share a picture).
+ *   canvas   OX = max off_x, OY = max off_y, W = OX + max(final_w - off_x), H = OY + max(final_h - off_y):
+ *            apap_panorama_bounds (host only, no device) writes out = W, H, OX, OY
+ *   layer    at canvas pixel (X, Y), with j = X - OX + off_x[k], i = Y - OY + off_y[k]: the pixel [i, j] of apap_local_warp of
+ *            that layer where 0 <= j < final_w[k] and 0 <= i < final_h[k] - the same cell lookup, float64 chain, strict bounds
+ *            test and truncation -, (0, 0, 0) elsewhere.  The centre's value is its pixel (X - OX, Y - OY) inside its
+ *            rectangle, (0, 0, 0) outside
+ *   mean     APAP_PANORAMA_MEAN: a value is present when any of its bytes is non-zero; each channel of the output is
+ *            floor(sum of the present values / their number), 0 when none is present.  With one layer: apap_local_stitch
+ *   paste    APAP_PANORAMA_PASTE: inside the centre's rectangle the centre, black pixels included; outside it the first
+ *            present layer in the given order, or 0
+ *   out      H x W x 3 uint8, rows contiguous
+ *   status   d_status[n_layers] (zeroed by the caller): the set-up of layer k ORs APAP_STATUS_SINGULAR / APAP_STATUS_INDEX into
+ *            d_status[k].  apap_panorama returns APAP_ERR_SINGULAR / APAP_ERR_INDEX for the first layer that reports one, with
+ *            "layer k" in the message, and copies the n_layers words to its host array `status` (may be NULL) either way
+ * n_layers set-up launches (the warp's own, one per layer) and one launch over the canvas.  The grids are not modified.
+ * Refused before any device is touched (APAP_ERR_INVALID_ARG): null pointers, n_layers outside 1 .. APAP_PANORAMA_MAX_LAYERS,
+ * an unknown mode, a centre that does not fit a pair canvas at its offsets (negative offsets included), a canvas of 2^31
+ * pixels or more, a picture of fewer than 2 pixels, with a side of 2^24 or more or of 2 GiB or more, a mesh of 53 million
+ * cells or more; a short (APAP_ERR_WORKSPACE) or misaligned workspace (256 bytes).  Without a GPU apap_panorama returns
+ * APAP_ERR_NO_DEVICE: there is no CPU fallback.
+ * apap_panorama_device only enqueues on `stream` and does not wait.  d_work: at least apap_panorama_workspace_bytes(...)
+ * bytes (0 for invalid arguments; a 256-byte multiple), no contract on its contents.
+ * apap_panorama_mean_of: the kernel's division, floor(sum / count) for count = 1 .. 17 and sum <= 255 count by one multiply
+ * and shift (0 for count = 0), as a host function - so that it can be checked exhaustively without a device. */
+#define APAP_PANORAMA_MAX_LAYERS 16
+#define APAP_PANORAMA_MEAN 0
+#define APAP_PANORAMA_PASTE 1
+int apap_panorama_bounds(int center_h, int center_w, const int *final_w, const int *final_h, const int *off_x, const int *off_y,
+                         int n_layers, int *out);
+size_t apap_panorama_workspace_bytes(const int *mesh_rows, const int *mesh_cols, const int *final_w, const int *final_h, int n_layers);
+unsigned apap_panorama_mean_of(unsigned sum, unsigned count);
+int apap_panorama(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs, const int *img_h,
+                  const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols, const double *const *mesh_w,
+                  const int *n_w, const double *const *mesh_h, const int *n_h, const int *final_w, const int *final_h, const int *off_x,
+                  const int *off_y, int n_layers, int mode, uint8_t *out, int *status, int device);
+int apap_panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                         const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows, const int *mesh_cols,
+                         const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h, const int *n_h,
+                         const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode,
+                         uint8_t *d_out, void *d_work, size_t work_bytes, int *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
