@@ -1,6 +1,7 @@
 """Case set E of the global warp and blend: the inputs at the kernel's edges, shared by tests/test_gpu_image_warp.py (which
 runs them on the GPU) and tests/test_image_warp_host.py (which checks, without a GPU, that each input does exercise the
-edge it is named for).  A case is (name, img_base, img2warp, H); every canvas is under 200 x 200."""
+edge it is named for).  A case is (name, img_base, img2warp, H); every canvas is under 200 x 200.  Below it the sets at the
+tiling's edges, which set E does not reach: sweep(), tiling_cases(), many() and tiny_pair()."""
 import os
 
 import numpy as np
@@ -71,3 +72,107 @@ def geometry(base, src, H):
     """(M, canvas_w, canvas_h, off_x, off_y) by the specification."""
     xmin, ymin, xmax, ymax = S.bounds(base.shape[0], base.shape[1], src.shape[0], src.shape[1], H)
     return S.matrix(np.asarray(H), [-xmin, -ymin]), xmax - xmin, ymax - ymin, -xmin, -ymin
+
+
+# ---------------------------------------------------------------- the tiling sets: caller-chosen geometry, wide canvases, many problems
+# k_image_warp's tiling (csrc/apap_image_warp.hip): a lane owns GROUP consecutive pixels of a row, a block COLS_PER_BLOCK
+# columns of ROWS_PER_BLOCK rows; a problem takes col_blocks x row_tiles consecutive blocks of the launch.
+GROUP, COLS_PER_BLOCK, ROWS_PER_BLOCK = 4, 256, 4
+
+# A problem with caller-chosen geometry is (name, img_base, img2warp, M, (canvas_w, canvas_h), (off_x, off_y), direct): what
+# _native.image_warp_batch takes per problem.  Set E above never sets the geometry itself: its offsets are multiples of 4 but
+# for two cases, and its canvases one block wide.
+
+
+def expected(problem):
+    """The specification's canvas of a problem with caller-chosen geometry."""
+    _, base, src, M, canvas, off, direct = problem
+    return S.blend(S.warp_perspective(src, M, canvas), base, off, direct)
+
+
+def col_blocks(problem):
+    return (problem[4][0] + COLS_PER_BLOCK - 1) // COLS_PER_BLOCK
+
+
+def explicit(name, base, src, H, direct):
+    """A case of set E's form as a problem with the geometry the specification derives for it."""
+    M, cw, ch, ox, oy = geometry(base, src, H)
+    return (name, base, src, M, (cw, ch), (ox, oy), direct)
+
+
+SWEEP_CANVAS, SWEEP_OFF_Y, SWEEP_BASE_H = (23, 6), 2, 3
+
+
+def sweep():
+    """The base rectangle's left edge at every residue of a lane's group against its right edge at every residue: off_x in
+    0 .. 7, base_w in 1 .. 5, on one 23 x 6 canvas, each geometry in both blend modes with one base picture - 80 problems.  The
+    source (bytes 1 .. 255) covers the whole canvas through a fractional translation, so every warped pixel is non-zero: a lane
+    that skips taps it needs shows black."""
+    rng = np.random.default_rng(401)
+    src = _pic(rng, 9, 25, 1)
+    M = translation(-0.3, -0.4)
+    out = []
+    for off_x in range(8):
+        for base_w in range(1, 6):
+            base = _pic(rng, SWEEP_BASE_H, base_w)
+            for direct in (True, False):
+                out.append((f"sweep_x{off_x}_w{base_w}_{'direct' if direct else 'mean'}", base, src, M, SWEEP_CANVAS,
+                            (off_x, SWEEP_OFF_Y), direct))
+    return out
+
+
+def tiny_pair():
+    """Both pictures 1 x 1, (img_base, img2warp, H): the source is spread over a 3 x 3 canvas whose pixel (0, 0), where the
+    base lies, takes 812 / 1024 of it."""
+    rng = np.random.default_rng(11)
+    return _pic(rng, 1, 1, 1), _pic(rng, 1, 1, 64), np.array([[3.0, 0.0, 0.4], [0.0, 3.0, 0.3], [0.0, 0.0, 1.0]])
+
+
+WIDE_SHAPES = ((255, 3), (256, 4), (257, 5), (511, 4), (512, 3), (513, 5), (769, 4))
+SMALL_IN_WIDE = ("width_4k1", "src_1x1", "half_ties", "width_4", "rows_9", "base_1x1", "width_4k3")
+
+
+def tiling_cases():
+    """Canvases 255, 256, 257, 511, 512, 513 and 769 wide (1, 1, 2, 2, 2, 3, 4 blocks along a row) and 3, 4, 5 high, in both
+    modes, each followed by a small problem of set E, and the pair of 1 x 1 pictures in both modes: a block's index minus its
+    problem's first block has to be split by that problem's own col_blocks.  One source 7 x 780 of bytes 1 .. 255 serves the wide
+    problems, each through its own fractional translation; the 2-row base straddles column 256 (columns 250 .. 261; 243 ..
+    254 where the canvas ends before that), and on the 769 canvas columns 250 .. 519, so whole lanes and a whole block's
+    middle lie inside it."""
+    rng = np.random.default_rng(402)
+    src = _pic(rng, 7, 780, 1)
+    by_name = {c[0]: c for c in cases()}
+    out = []
+    for k, (cw, ch) in enumerate(WIDE_SHAPES):
+        base_w = 270 if cw == 769 else 12
+        off_x = min(250, cw - base_w)
+        base = _pic(rng, 2, base_w)
+        small = by_name[SMALL_IN_WIDE[k]]
+        for direct in (True, False):
+            out.append((f"wide_{cw}x{ch}_{'direct' if direct else 'mean'}", base, src, translation(-0.3 - k, -0.4), (cw, ch), (off_x, 1),
+                        direct))
+            out.append(explicit(f"{small[0]}_{'direct' if direct else 'mean'}", small[1], small[2], small[3], not direct))
+    base, tiny, H = tiny_pair()
+    for direct in (True, False):
+        out.append(explicit(f"both_1x1_{'direct' if direct else 'mean'}", base, tiny, H, direct))
+    return out
+
+
+MANY = 521
+
+
+def many():
+    """521 (a prime above 512) problems of set E's form, (img_base, img2warp, H, direct_blend), on canvases between 5 x 5 and
+    9 x 11: every problem has its own pictures, its own translation (drawn until the canvas has such a size) and its own mode,
+    so a block routed to a neighbouring problem writes other bytes.  The descriptor table is 75 KB and the bisection over the
+    first blocks ten levels deep."""
+    rng = np.random.default_rng(403)
+    out = []
+    while len(out) < MANY:
+        h1, w1, h2, w2 = (int(v) for v in rng.integers(1, 9, 4))
+        H = translation(*np.round(rng.uniform(-3.0, 3.0, 2), 3))
+        base, src, direct = _pic(rng, h1, w1), _pic(rng, h2, w2, 1), bool(rng.integers(0, 2))
+        _, cw, ch, _, _ = geometry(base, src, H)
+        if 5 <= cw <= 9 and 5 <= ch <= 11:
+            out.append((base, src, H, direct))
+    return out

@@ -124,18 +124,76 @@ def shared_source():
     return dict(center=center, layers=layers, geometries=[tuple(l.final_size) + tuple(l.offset) for l in layers], planted=[None, None])
 
 
+def plant_at(layer, Hg, point):
+    """``plant`` with the target given as a point (x, y) relative to the centre picture's first pixel - a canvas pixel less
+    (OX, OY) - which may lie outside the centre picture.  Returns the two source pixels (x, y)."""
+    h, w = layer.img.shape[:2]
+    p = np.linalg.inv(Hg) @ np.array([point[0], point[1], 1.0])
+    x, y = int(np.clip(p[0] / p[2], 2, w - 7)), int(np.clip(p[1] / p[2], 2, h - 3))
+    layer.img[y - 1:y + 2, x - 1:x + 2] = 0
+    layer.img[y - 1:y + 2, x + 3:x + 6] = (0, 0, 7)
+    return (x, y), (x + 4, y)
+
+
+def wide():
+    """Pair canvases against the 256-column strips of a 530 x 18 canvas: one begins in a strip's last column (dx = 255), one in
+    the next strip's first (256), one ends with a strip (right = 512), one a column later (513); one ends a row below a strip
+    of 4 rows (below = 17).  The placements are translations, by a fraction that keeps the pair canvases' first and last
+    columns inside the sources although every cell moves by a few tenths of a pixel."""
+    specs = [(30, 9, placement(-300.0, 0.0), 1, 2),
+             (20, 9, placement(-45.6, 0.0), 2, 2),
+             (20, 12, placement(-44.6, 2.0), 1, 3),
+             (30, 9, placement(182.4, 0.0), 2, 1),
+             (30, 9, placement(183.4, -3.0), 1, 1),
+             (30, 14, placement(200.4, 1.0), 3, 2)]
+    return build(530, (40, 9), specs)
+
+
+def exact():
+    """A canvas of exactly 256 x 16: one block, no partial strip, no row tail."""
+    return build(256, (200, 10), [(56, 16, placement(200.0, 0.0), 2, 2), (60, 9, placement(100.0, 1.0), 1, 3)])
+
+
+def black_outside():
+    """Two layers that overlap right of the centre picture; the FIRST has a black block and a block with one non-zero channel
+    in that overlap: paste falls through to the second layer on a value there, not on an absence."""
+    Hg0 = placement(25.0, 5.0, 0.02, 1e-5, -1e-5)
+    case = build(77, (30, 20), [(40, 30, Hg0, 2, 3), (40, 30, placement(35.0, -2.0, -0.01), 3, 2)])
+    case["planted"][0] = plant_at(case["layers"][0], Hg0, (45.0, 15.0))
+    return case
+
+
+def white17():
+    """sixteen() with every picture entirely 255: the packed sums hold 17 x 255 = 4335 where all are present."""
+    case = sixteen()
+    case["center"] = np.full_like(case["center"], 255)
+    case["layers"] = [l._replace(img=np.full_like(l.img, 255)) for l in case["layers"]]
+    return case
+
+
+def two_pixels():
+    """The smallest pictures: a centre of 2 x 1 pixels, sources of 2 x 1 and 1 x 2 pixels (width x height) magnified four
+    times, through meshes of 1 x 2 and 2 x 1 cells."""
+    specs = [(2, 1, np.array([[4.0, 0.0, 1.5], [0.0, 4.0, 0.5], [0.0, 0.0, 1.0]]), 1, 2),
+             (1, 2, np.array([[4.0, 0.0, -2.5], [0.0, 4.0, -3.5], [0.0, 0.0, 1.0]]), 2, 1)]
+    return build(2, (2, 1), specs)
+
+
 HOST_CASES = {"cross": cross, "strip259": lambda: strip_edges(259), "strip517": lambda: strip_edges(517), "sixteen": sixteen,
               "shared": shared_source}
+
+# the tiling's edges that HOST_CASES do not reach; tests/test_panorama_host.py shows that each reaches its own
+TILING_CASES = {"wide": wide, "exact": exact, "black_outside": black_outside, "white17": white17, "two_pixels": two_pixels}
 
 _cache = {}
 
 
 def get(name):
-    """The case ``name`` of HOST_CASES with ``oracle``: every layer's canvas by the oracle's ``local_warp`` (float32 inverses
+    """The case ``name`` of HOST_CASES or TILING_CASES with ``oracle``: every layer's canvas by the oracle's ``local_warp`` (float32 inverses
     of the cells, then the vectorised pixel loop).  Built once per session and shared: treat it as read-only."""
     if name not in _cache:
         from oracle import apap_oracle as O
-        case = HOST_CASES[name]()
+        case = (HOST_CASES.get(name) or TILING_CASES[name])()
         case["oracle"] = [O.local_warp_fast(l.img, O.invert_cells_f32(l.local_homography), l.mesh, l.final_size, l.offset)
                           for l in case["layers"]]
         _cache[name] = case

@@ -1,6 +1,8 @@
 """The global warp and blend on the GPU (apap_image_warp*, utils.image_warping, resident.hip_image_warp*) against the numpy
 specification of tests/image_warp_spec.py: the same bytes, at the kernel's edges (case set E of tests/image_warp_cases.py),
-in batches of any order, on device tensors, and on pooled buffers shared with other host-buffer calls."""
+in batches of any order, on device tensors, and on pooled buffers shared with other host-buffer calls; and at the tiling's
+edges (the sets sweep, tiling_cases and many of the same file): the base rectangle at every residue of a lane's group of 4,
+canvases of several blocks along a row inside a batch, 521 problems in one launch, both pictures 1 x 1."""
 import os
 
 import numpy as np
@@ -197,3 +199,119 @@ def test_medium_pair(native_gpu, direct):
     spec = S.image_warping(base, src, H, direct)
     assert 650 <= spec.shape[1] <= 750 and 450 <= spec.shape[0] <= 560, spec.shape
     same(utils.image_warping(base, src, H, direct), spec, f"medium direct={direct}")
+
+
+# ---------------------------------------------------------------- the tiling sets (caller-chosen geometry)
+def run_batch(native, problems, out=None, out_offsets=None):
+    return native.image_warp_batch([p[1] for p in problems], [p[2] for p in problems], [p[3] for p in problems], [p[4] for p in problems],
+                                   [p[5] for p in problems], [p[6] for p in problems], out=out, out_offsets=out_offsets)
+
+
+def run_single(native, p):
+    return native.image_warp(p[1], p[2], p[3], p[4][0], p[4][1], p[5][0], p[5][1], p[6])
+
+
+def frozen(canvases):
+    for c in canvases:
+        c.setflags(write=False)
+    return canvases
+
+
+@pytest.fixture(scope="module")
+def tiling():
+    """tiling_cases() and the specification's canvas of each, computed once."""
+    problems = E.tiling_cases()
+    return problems, frozen([E.expected(p) for p in problems])
+
+
+@pytest.fixture(scope="module")
+def many():
+    problems = E.many()
+    return problems, frozen([S.image_warping(*p) for p in problems])
+
+
+def test_base_rectangle_at_every_residue_of_a_lanes_group(native_gpu):
+    """sweep(): 80 problems in one launch, the base rectangle's two vertical edges at all 16 pairs of residues mod 4, base
+    pictures narrower than a lane's group strictly inside one, both modes; every eleventh also as its own single call."""
+    problems = E.sweep()
+    want_ = [E.expected(p) for p in problems]
+    got = run_batch(native_gpu, problems)
+    assert len(got) == len(problems) == 80
+    for p, canvas, w in zip(problems, got, want_):
+        same(canvas, w, f"sweep batch, {p[0]}")
+    for k in range(0, len(problems), 11):
+        same(run_single(native_gpu, problems[k]), want_[k], f"sweep single, {problems[k][0]}")
+
+
+def test_wide_canvases_inside_a_batch(native_gpu, tiling):
+    """tiling_cases(): 1, 2, 3 and 4 blocks along a row within one launch, behind problems that move the first block off 0, in
+    three orders; the canvases at odd gaps in a poisoned buffer, placed in another order than the problems."""
+    problems, want_ = tiling
+    n = len(problems)
+    rng = np.random.default_rng(9)
+    sizes = [w.size for w in want_]
+    for order in (list(range(n)), list(range(n))[::-1], [int(i) for i in rng.permutation(n)]):
+        place = rng.permutation(n)                       # the position of each problem's canvas in the buffer
+        offsets, at = [0] * n, 7
+        for j in np.argsort(place):
+            offsets[j] = at
+            at += sizes[order[j]] + (1, 3, 5, 7, 11)[j % 5]
+        out = np.full(at + 32, 0xA5, np.uint8)
+        got = run_batch(native_gpu, [problems[i] for i in order], out=out, out_offsets=offsets)
+        untouched = np.ones(out.size, bool)
+        for i, canvas, o in zip(order, got, offsets):
+            same(canvas, want_[i], f"order {order[:3]}..., {problems[i][0]} at offset {o}")
+            assert np.array_equal(out[o:o + sizes[i]], want_[i].ravel())
+            untouched[o:o + sizes[i]] = False
+        assert (out[untouched] == 0xA5).all() and untouched.sum() == out.size - sum(sizes)
+
+
+def test_each_wide_problem_equals_its_own_single_call(native_gpu, tiling):
+    for p, w in zip(*tiling):
+        same(run_single(native_gpu, p), w, f"single call, {p[0]}")
+
+
+def test_521_problems_in_one_launch(native_gpu, many):
+    """The host-buffer form and the resident form (a poisoned workspace of exactly the size asked for, canvases one poisoned
+    byte apart) on many(): the descriptor table is 75 KB, the bisection ten levels deep, every neighbour another problem."""
+    import torch
+    from cvx_proj_amd import resident, utils
+    problems, want_ = many
+    n = len(problems)
+    assert n == E.MANY == 521
+    got = utils.image_warping_batch(problems)
+    assert len(got) == n
+    for k, (canvas, w) in enumerate(zip(got, want_)):
+        same(canvas, w, f"host-buffer batch of {n}, problem {k}")
+    dev = torch.device("cuda")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    dprobs = [(up(b), up(s), H, d) for b, s, H, d in problems]
+    sizes = [w.size for w in want_]
+    offsets = [int(v) for v in np.cumsum([3] + [s + 1 for s in sizes])[:-1]]
+    need = resident.image_warp_workspace_bytes(n)
+    assert need == (n * 144 + 255) // 256 * 256
+    work = torch.full((need,), 0xFF, dtype=torch.uint8, device=dev)
+    out = torch.full((offsets[-1] + sizes[-1] + 9,), 0x5A, dtype=torch.uint8, device=dev)
+    views = resident.hip_image_warp_batch(dprobs, out=out, out_offsets=offsets, work=work)
+    torch.cuda.synchronize()
+    host = out.cpu().numpy()
+    untouched = np.ones(host.size, bool)
+    for k, (v, w, o, size) in enumerate(zip(views, want_, offsets, sizes)):
+        assert v.data_ptr() == out.data_ptr() + o
+        same(host[o:o + size].reshape(w.shape), w, f"resident batch of {n}, problem {k}")
+        untouched[o:o + size] = False
+    assert (host[untouched] == 0x5A).all() and untouched.sum() == 3 + (n - 1) + 9
+
+
+def test_both_pictures_1x1(native_gpu):
+    """Alone, in both modes, through the host-buffer and the resident single calls (in a batch: tiling_cases())."""
+    import torch
+    from cvx_proj_amd import resident, utils
+    base, src, H = E.tiny_pair()
+    assert base.shape == src.shape == (1, 1, 3)
+    dev = torch.device("cuda")
+    dbase, dsrc = torch.from_numpy(base).to(dev), torch.from_numpy(src).to(dev)
+    for direct in (True, False):
+        w = S.image_warping(base, src, H, direct)
+        same(utils.image_warping(base, src, H, direct), w, f"1 x 1 pair, direct={direct}")
+        same(resident.hip_image_warp(dbase, dsrc, H, direct).cpu().numpy(), w, f"1 x 1 pair, resident, direct={direct}")

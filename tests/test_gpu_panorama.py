@@ -58,6 +58,14 @@ def test_small_cases(native_gpu, name):
     check_case(native_gpu, E.get(name), name)
 
 
+@pytest.mark.parametrize("name", sorted(E.TILING_CASES))
+def test_tiling_cases(native_gpu, name):
+    """Pair canvases that begin and end at the 256-column strip boundaries of a 530-wide canvas, a canvas of exactly one
+    block, a black block of the first layer over a present second one outside the centre picture, 17 white pictures on one
+    pixel, pictures of two pixels: both modes (tests/test_panorama_host.py shows that each case reaches its edge)."""
+    check_case(native_gpu, E.get(name), name)
+
+
 def test_one_layer_at_c1_is_local_stitch(native_gpu):
     from cvx_proj_amd import apap
     case = E.single_c1()
@@ -176,6 +184,37 @@ def test_device_form_and_its_buffers(native_gpu):
     bad[0, 0] = 0
     _, _, status = resident.hip_panorama(center, layers[:3] + [layers[3]._replace(local_homography=bad)])
     assert status.tolist() == [0, 0, 0, native_gpu.STATUS_SINGULAR]
+
+
+@pytest.mark.parametrize("name", ["wide", "black_outside"])
+def test_device_form_on_tiling_cases(native_gpu, name):
+    """resident.hip_panorama into a guarded ``out`` with a workspace of 0xA5: the specification's bytes over the oracle's
+    layers, nothing written outside ``out``."""
+    import torch
+    from cvx_proj_amd import apap, resident
+    case = E.get(name)
+    dev = torch.device("cuda", 0)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    center = up(case["center"])
+    layers = [apap.PanoramaLayer(up(l.img), up(l.local_homography), (up(l.mesh[0]), up(l.mesh[1])), l.final_size, l.offset)
+              for l in case["layers"]]
+    n = len(layers)
+    W, H, OX, OY = S.panorama_size(case["center"].shape, case["geometries"])
+    need = resident.panorama_workspace_bytes(layers)
+    assert need > 0 and need % 256 == 0
+    guard = 4096
+    for mode in MODES:
+        buf = torch.full((guard + H * W * 3 + guard,), 0x5C, dtype=torch.uint8, device=dev)
+        out = buf[guard:guard + H * W * 3].view(H, W, 3)
+        work = torch.full((need + 512,), 0xA5, dtype=torch.uint8, device=dev)
+        status = torch.zeros(n + 2, dtype=torch.int32, device=dev)
+        got, bounds, _ = resident.hip_panorama(center, layers, blend=mode, out=out, status=status, work=work)
+        torch.cuda.synchronize(dev)
+        assert got.data_ptr() == out.data_ptr() and bounds == (W, H, OX, OY)
+        same(got.cpu().numpy(), S.compose(case["center"], case["oracle"], case["geometries"], mode), f"{name}, device form, {mode}")
+        assert bool((buf[:guard] == 0x5C).all()) and bool((buf[guard + H * W * 3:] == 0x5C).all()), "guard bytes around out"
+        assert bool((work[need:] == 0xA5).all()), "bytes past the workspace the call asked for"
+        assert status.tolist() == [0] * (n + 2)
 
 
 def test_command_line(native_gpu, tmp_path):

@@ -338,3 +338,110 @@ def test_edge_cases_exercise_the_edges_they_are_named_for():
     assert np.array_equal(geo["H_float32"][0], geo["H_float64"][0])
     for name in ("src_1x1", "src_1x2", "src_2x1"):
         assert S.image_warping(*cases[name], True).any(axis=-1).sum() > cases[name][0].shape[0] * cases[name][0].shape[1] - 40
+
+
+def test_sweep_reaches_every_residue_of_a_lanes_group():
+    """sweep(): what tests/test_gpu_image_warp.py needs of it, by the specification alone."""
+    import image_warp_cases as E
+    problems = E.sweep()
+    assert len(problems) == 80 and len({p[0] for p in problems}) == 80
+    pairs = set()
+    for direct_p, mean_p in zip(problems[0::2], problems[1::2]):
+        _, base, src, M, (cw, ch), (ox, oy), direct = direct_p
+        assert direct and not mean_p[6] and all(a is b for a, b in zip(direct_p[1:4], mean_p[1:4])) and direct_p[4:6] == mean_p[4:6]      # one problem, both modes
+        assert (cw, ch) == (23, 6) and oy == 2 and base.shape[0] == 3 and src.min() >= 1
+        w1 = base.shape[1]
+        pairs.add((ox % E.GROUP, (ox + w1) % E.GROUP))
+        warped = S.warp_perspective(src, M, (cw, ch))
+        # non-zero just left and right of the base rectangle, on its rows: a lane that skipped taps it needs shows black there
+        if ox > 0:
+            assert warped[oy:oy + 3, ox - 1].any(axis=-1).all()
+        assert ox + w1 < cw and warped[oy:oy + 3, ox + w1].any(axis=-1).all()
+        assert warped.any(axis=-1).all()
+        d, m = E.expected(direct_p), E.expected(mean_p)
+        assert np.array_equal(d[oy:oy + 3, ox:ox + w1], base) and not np.array_equal(d, m)
+        outside = np.ones((ch, cw), bool)
+        outside[oy:oy + 3, ox:ox + w1] = False
+        assert np.array_equal(d[outside], warped[outside]) and np.array_equal(m[outside], warped[outside])
+    assert pairs == {(a, b) for a in range(4) for b in range(4)}
+    # a base picture strictly inside one lane's group of four, and one that straddles a group's boundary at every odd residue
+    inside = [(p[5][0], p[1].shape[1]) for p in problems if p[5][0] % 4 >= 1 and p[5][0] % 4 + p[1].shape[1] <= 3]
+    assert (1, 1) in inside and (1, 2) in inside and (5, 2) in inside
+    assert {p[5][0] % 4 for p in problems if p[5][0] // 4 != (p[5][0] + p[1].shape[1] - 1) // 4} == {0, 1, 2, 3}
+    # the fractional translation: no tap weight is zero
+    X, Y = S.fixed_coords(problems[0][3], (23, 6))
+    assert (X & 31).all() and (Y & 31).all()
+
+
+def test_tiling_cases_reach_their_edges():
+    """tiling_cases(): col_blocks 1 .. 4 in one batch behind first blocks other than 0, widths on both sides of a block's 256
+    columns, warped and base pixels on both sides of columns 256 and 512."""
+    import image_warp_cases as E
+    problems = E.tiling_cases()
+    wide = [p for p in problems if p[0].startswith("wide_")]
+    assert {p[4] for p in wide} == set(E.WIDE_SHAPES) and len(wide) == 2 * len(E.WIDE_SHAPES)
+    assert sorted({p[4][0] for p in wide}) == [255, 256, 257, 511, 512, 513, 769] and {p[4][1] for p in wide} == {3, 4, 5}
+    assert {p[4][0] % E.COLS_PER_BLOCK for p in wide} == {255, 0, 1} and {p[4][0] % E.GROUP for p in wide} == {0, 1, 3}
+    assert {E.col_blocks(p) for p in wide} == {1, 2, 3, 4} and {p[4][1] % E.ROWS_PER_BLOCK for p in wide} == {0, 1, 3}
+    # interleaved: a wide problem never follows a wide one, neighbours differ in col_blocks somewhere, both modes of each
+    assert all(a[0].startswith("wide_") != b[0].startswith("wide_") for a, b in zip(problems[:28], problems[1:28]))
+    assert [E.col_blocks(p) for p in problems[:28:2]] == [1, 1, 1, 1, 2, 2, 2, 2, 2, 2, 3, 3, 4, 4]
+    assert all(E.col_blocks(p) == 1 for p in problems[1::2]) and {p[6] for p in wide} == {True, False}
+    assert len({id(p[2]) for p in wide}) == 1 and len({p[3][0, 2] for p in wide}) == len(E.WIDE_SHAPES)     # one source, 7 translations
+    for p in wide:
+        _, base, src, M, (cw, ch), (ox, oy), direct = p
+        assert src.min() >= 1 and oy == 1 and base.shape[0] == 2
+        warped = S.warp_perspective(src, M, (cw, ch))
+        for col in (255, 256, 257, 511, 512, 513):
+            if col < cw:
+                assert warped[:, col].any(axis=-1).all(), (p[0], col)
+        assert warped[:, cw - 1].any(axis=-1).all() and warped[:, 0].any(axis=-1).all()
+        w1 = base.shape[1]
+        if cw > 262:
+            assert ox == 250 and ox < 256 < ox + w1 - 1                      # the base rectangle straddles column 256
+        else:
+            assert ox + w1 == cw                                             # ... or ends with the canvas' last column
+        if cw == 769:
+            assert ox + w1 > 512 + E.GROUP and w1 > E.COLS_PER_BLOCK         # ... and column 512, a whole block's lanes inside it
+        got = E.expected(p)
+        assert np.array_equal(got[1:3, ox:ox + w1], base) == direct
+    # the small problems are set E's, with the specification's geometry; both 1 x 1 pictures close the batch
+    by_name = {c[0]: c for c in E.cases()}
+    for p in problems[1:28:2]:
+        name = p[0].rsplit("_", 1)[0]
+        assert name in E.SMALL_IN_WIDE and np.array_equal(E.expected(p), S.image_warping(*by_name[name][1:], p[6]))
+    assert [p[0] for p in problems[28:]] == ["both_1x1_direct", "both_1x1_mean"]
+    for p in problems[28:]:
+        assert p[1].shape == p[2].shape == (1, 1, 3) and np.array_equal(E.expected(p), S.image_warping(*E.tiny_pair(), p[6]))
+
+
+def test_tiny_pair_shows_both_pictures():
+    import image_warp_cases as E
+    base, src, H = E.tiny_pair()
+    M, cw, ch, ox, oy = E.geometry(base, src, H)
+    assert (cw, ch, ox, oy) == (3, 3, 0, 0)
+    warped = S.warp_perspective(src, M, (cw, ch))
+    assert warped.all() and np.array_equal(warped[0, 0], src[0, 0].astype(np.int64) * 812 + 512 >> 10)
+    d, m = S.image_warping(base, src, H, True), S.image_warping(base, src, H, False)
+    assert np.array_equal(d[0, 0], base[0, 0]) and np.array_equal(m[0, 0], (base[0, 0].astype(np.int64) + warped[0, 0]) >> 1)
+    assert not np.array_equal(d[0, 0], m[0, 0]) and not np.array_equal(m[0, 0], warped[0, 0])
+
+
+def test_many_problems_differ_from_their_neighbours(native):
+    import image_warp_cases as E
+    problems = E.many()
+    n = len(problems)
+    assert n == 521 and all(n % k for k in range(2, 23)) and n > 512
+    assert native.lib().apap_image_warp_workspace_bytes(n) == (n * 144 + 255) // 256 * 256 == 75264
+    geo = [E.geometry(b, s, H) for b, s, H, _ in problems]
+    assert all(5 <= g[1] <= 9 and 5 <= g[2] <= 11 for g in geo)
+    assert {g[1] for g in geo} == set(range(5, 10)) and {g[2] for g in geo} == set(range(5, 12))
+    assert len({(g[3], g[4]) for g in geo}) >= 9 and len({tuple(H[:2, 2]) for _, _, H, _ in problems}) == n
+    assert 200 < sum(d for _, _, _, d in problems) < 321
+    want = [S.image_warping(*p) for p in problems]
+    assert all(w.any() for w in want)
+    for a, b in zip(want, want[1:]):
+        assert a.shape != b.shape or not np.array_equal(a, b)
+    # the bisection's table: every problem is a handful of blocks, the first blocks all differ
+    blocks = [-(-g[1] // E.COLS_PER_BLOCK) * -(-g[2] // E.ROWS_PER_BLOCK) for g in geo]
+    assert set(blocks) == {2, 3} and len(set(np.cumsum(blocks))) == n

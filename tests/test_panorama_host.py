@@ -207,3 +207,125 @@ def test_paste_and_mean_differ_where_they_should():
     several = stack[1:].any(axis=-1).sum(axis=0) >= 2
     several[rect] = False
     assert several.any() and (paste[several] != mean[several]).any()
+
+
+# ---------------------------------------------------------------- TILING_CASES: the tiling's edges that HOST_CASES do not reach
+TILING = sorted(E.TILING_CASES)
+
+
+def edges_of(case):
+    center, geos = case["center"], case["geometries"]
+    W, H, OX, OY = S.panorama_size(center.shape, geos)
+    dx, dy = [OX - g[2] for g in geos], [OY - g[3] for g in geos]
+    return (W, H, OX, OY), dx, dy, [d + g[0] for d, g in zip(dx, geos)], [d + g[1] for d, g in zip(dy, geos)]
+
+
+@pytest.mark.parametrize("name", TILING)
+def test_tiling_cases_bounds_and_single_layers(native, name):
+    """What the HOST_CASES are held to: the C entry point's bounds are the specification's, and the specification with one
+    layer is the oracle's stitch."""
+    case = E.get(name)
+    geo = np.array(case["geometries"], dtype=np.int32)
+    want = S.panorama_size(case["center"].shape, case["geometries"])
+    assert native.panorama_bounds(case["center"].shape, geo[:, 0], geo[:, 1], geo[:, 2], geo[:, 3]) == want
+    for canvas, g, layer in zip(case["oracle"], case["geometries"], case["layers"]):
+        assert np.array_equal(S.compose(case["center"], [canvas], [g], "mean"), O.stitch(canvas, case["center"], layer.offset))
+
+
+def test_wide_reaches_the_strip_boundaries():
+    case = E.get("wide")
+    center, canvases, geos = case["center"], case["oracle"], case["geometries"]
+    (W, H, OX, OY), dx, dy, right, below = edges_of(case)
+    strips = range(-(-W // E.STRIP_COLS))
+    assert len(strips) == 3 and W % E.STRIP_COLS and W % E.GROUP and H % E.STRIP_ROWS
+    # a strip that ends at or before a pair canvas' first column: with equality for one layer, one column short for another
+    ends_before = {(s, k) for s in strips for k in range(len(geos)) if E.STRIP_COLS * (s + 1) <= dx[k]}
+    assert ends_before and any(E.STRIP_COLS * (s + 1) == dx[k] for s, k in ends_before)
+    begins_last = [k for k, d in enumerate(dx) if d % E.STRIP_COLS == E.STRIP_COLS - 1]
+    begins_first = [k for k, d in enumerate(dx) if d and d % E.STRIP_COLS == 0]
+    ends_with = [k for k, r in enumerate(right) if r % E.STRIP_COLS == 0 and r < W]
+    ends_after = [k for k, r in enumerate(right) if r % E.STRIP_COLS == 1 and r < W]
+    assert begins_last and begins_first and ends_with and ends_after
+    assert any(b % E.STRIP_ROWS == 1 and b < H for b in below)
+    # the pixels that a strip skipped by mistake would lose are there: the first column of the layers that begin at a strip
+    # boundary, the last column of those that end at or just after one (where no other picture is present in some row)
+    count = S.present_count(center, canvases, geos)
+    for k in begins_last + begins_first:
+        rows = canvases[k][:, 0].any(axis=-1)
+        assert rows.any() and (count[dy[k]:below[k], dx[k]][rows] == 1).any(), k
+    for k in ends_with + ends_after:
+        rows = canvases[k][:, -1].any(axis=-1)
+        assert rows.any() and (k in ends_with or (count[dy[k]:below[k], right[k] - 1][rows] == 1).any()), k
+    # ... and in paste: the first present layer there is that one
+    stack = S.placed(center, canvases, geos)
+    paste = S.compose(center, canvases, geos, "paste")
+    for k, col in [(k, dx[k]) for k in begins_last] + [(k, right[k] - 1) for k in ends_after]:
+        first = stack[1:k + 2, :, col].any(axis=-1).argmax(axis=0)
+        shows = stack[k + 1, :, col].any(axis=-1) & (first == k)
+        assert shows.any() and np.array_equal(paste[shows, col], stack[k + 1, shows, col]), k
+    # the layout: three sources on either side overlap each other and none the centre picture, so at most 3 are present
+    assert set(np.unique(count)) == {0, 1, 2, 3}
+
+
+def test_exact_has_no_partial_block():
+    case = E.get("exact")
+    (W, H, OX, OY), dx, dy, right, below = edges_of(case)
+    assert (W, H) == (256, 16) and W % E.STRIP_COLS == 0 and H % (E.STRIP_ROWS * E.WAVES_PER_BLOCK) == 0
+    assert len(case["layers"]) == 2 and case["oracle"][0][:, -1].any() and case["oracle"][0][-1].any()      # the last column and row
+    assert set(np.unique(S.present_count(case["center"], case["oracle"], case["geometries"]))) == {0, 1, 2}
+
+
+def test_black_outside_falls_through_on_a_value():
+    case = E.get("black_outside")
+    center, canvases, geos, (l0, l1) = case["center"], case["oracle"], case["geometries"], case["layers"]
+    (W, H, OX, OY), dx, dy, right, below = edges_of(case)
+    stack = S.placed(center, canvases, geos)
+    ids = np.zeros(l0.img.shape, np.uint8)
+    ys, xs = np.mgrid[:l0.img.shape[0], :l0.img.shape[1]]
+    ids[..., 0], ids[..., 1], ids[..., 2] = xs + 1, ys + 1, 1               # the source pixel of every pixel of layer 0's canvas
+    where = O.local_warp_fast(ids, O.invert_cells_f32(l0.local_homography), l0.mesh, l0.final_size, l0.offset)
+    where = S.placed(center, [where, np.zeros_like(canvases[1])], geos)[1]
+    (bx, by), (sx, sy) = case["planted"][0]
+    black = (where[..., 0] == bx + 1) & (where[..., 1] == by + 1) & (where[..., 2] == 1)
+    single = (where[..., 0] == sx + 1) & (where[..., 1] == sy + 1) & (where[..., 2] == 1)
+    assert black.any() and single.any()
+    outside = np.ones((H, W), bool)
+    outside[OY:OY + center.shape[0], OX:OX + center.shape[1]] = False
+    assert outside[black].all() and outside[single].all()
+    # layer 0 is black at the planted pixel, present two pixels away on every side, and layer 1 is present there
+    y, x = (int(v) for v in np.argwhere(black)[0])
+    assert not stack[1][black].any() and stack[2][black].any(axis=-1).all()
+    assert all(stack[1, y + a, x + b].any() for a, b in ((-3, 0), (3, 0), (0, -3), (-3, -3), (3, -3)))
+    paste, mean = S.compose(center, canvases, geos, "paste"), S.compose(center, canvases, geos, "mean")
+    assert np.array_equal(paste[black], stack[2][black])
+    # one non-zero channel is a value: layer 0 shows, and the mean of the two is something else
+    assert (stack[1][single] == (0, 0, 7)).all() and (paste[single] == (0, 0, 7)).all() and stack[2][single].any(axis=-1).all()
+    assert (mean[single] != paste[single]).any(axis=-1).all()
+    # everywhere else in the overlap paste shows layer 0
+    both = stack[1].any(axis=-1) & stack[2].any(axis=-1) & outside
+    assert both.sum() > 400 and np.array_equal(paste[both], stack[1][both])
+
+
+def test_white17_fills_the_accumulators():
+    case = E.get("white17")
+    center, canvases, geos = case["center"], case["oracle"], case["geometries"]
+    assert len(canvases) == 16 and center.min() == 255 and all(l.img.min() == 255 for l in case["layers"])
+    count = S.present_count(center, canvases, geos)
+    assert count.max() == 17 and (count == 17).sum() >= 2 and set(np.unique(count)) == set(range(18))
+    total = S.placed(center, canvases, geos).astype(np.int64).sum(axis=0)
+    assert total.max() == 17 * 255 == 4335
+    mean = S.compose(center, canvases, geos, "mean")
+    assert (mean[count > 0] == 255).all() and not mean[count == 0].any() and (count == 0).any()
+
+
+def test_two_pixels_are_both_seen():
+    case = E.get("two_pixels")
+    center, canvases, layers = case["center"], case["oracle"], case["layers"]
+    assert center.shape == (1, 2, 3) and [l.img.shape for l in layers] == [(1, 2, 3), (2, 1, 3)]
+    assert [l.local_homography.shape[:2] for l in layers] == [(1, 2), (2, 1)]
+    for canvas, l in zip(canvases, layers):
+        a, b = l.img.reshape(2, 3)
+        assert not np.array_equal(a, b)
+        flat = canvas.reshape(-1, 3)
+        assert (flat == a).all(axis=-1).sum() >= 6 and (flat == b).all(axis=-1).sum() >= 6       # each over several canvas pixels
+    assert set(np.unique(S.present_count(center, canvases, case["geometries"]))) == {0, 1, 2}
