@@ -223,7 +223,12 @@ SIGNATURES = {
     "apap_panorama_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_void_p), _i32p, _i32p, C.POINTER(C.c_void_p), _i32p,
                                        _i32p, C.POINTER(C.c_void_p), _i32p, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, _i32p, _i32p,
                                        C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "apap_panorama_ramp_weight": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "apap_panorama_ramp_quotients": (None, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.c_int, C.POINTER(C.c_uint)]),
 }
+# the ramp's entry points: the argument lists of apap_panorama / apap_panorama_device with `ramp` in place of `mode`
+SIGNATURES["apap_panorama_ramp"] = SIGNATURES["apap_panorama"]
+SIGNATURES["apap_panorama_ramp_device"] = SIGNATURES["apap_panorama_device"]
 
 _lib = None
 _torch_at_load = False      # was torch in the process when the library was loaded?  (cvx_proj_amd.resident refuses otherwise)
@@ -1200,6 +1205,7 @@ def image_warp(base, src, M, canvas_w, canvas_h, off_x, off_y, direct_blend=True
 PANORAMA_MAX_LAYERS = 16            # APAP_PANORAMA_MAX_LAYERS
 PANORAMA_MEAN, PANORAMA_PASTE = 0, 1
 PANORAMA_MODES = {"mean": PANORAMA_MEAN, "paste": PANORAMA_PASTE}
+PANORAMA_MAX_RAMP = 256             # APAP_PANORAMA_MAX_RAMP
 
 
 class PanoramaLayer(NamedTuple):
@@ -1215,8 +1221,19 @@ class PanoramaLayer(NamedTuple):
 
 def panorama_mode(blend, who="panorama"):
     if blend not in PANORAMA_MODES:
-        raise ValueError(f"{who}: blend must be 'mean' or 'paste'; got {blend!r}")
+        raise ValueError(f"{who}: blend must be 'mean', 'paste' or 'ramp'; got {blend!r}")
     return PANORAMA_MODES[blend]
+
+
+def panorama_entry(blend, ramp, who="panorama", device_form=False):
+    """The C entry point of ``blend`` and its mode argument: ``apap_panorama[_device]`` with the mode of 'mean' or 'paste' (``ramp``
+    is ignored), ``apap_panorama_ramp[_device]`` with the ramp width for 'ramp' - an integer 1 .. 256, or ValueError."""
+    suffix = "_device" if device_form else ""
+    if blend != "ramp":
+        return getattr(lib(), "apap_panorama" + suffix), panorama_mode(blend, who)
+    if isinstance(ramp, bool) or not isinstance(ramp, (int, np.integer)) or not 1 <= ramp <= PANORAMA_MAX_RAMP:
+        raise ValueError(f"{who}: ramp must be an integer 1 .. {PANORAMA_MAX_RAMP}; got {ramp!r}")
+    return getattr(lib(), "apap_panorama_ramp" + suffix), int(ramp)
 
 
 def panorama_geometry(layers, who="panorama"):
@@ -1245,12 +1262,29 @@ def panorama_mean_of(total, count):
     return int(lib().apap_panorama_mean_of(int(total), int(count)))
 
 
-def panorama(center, layers, blend="mean", device=-1, ctx=None, return_status=False):
-    """``apap_panorama``: the centre picture and every layer (a :class:`PanoramaLayer` or a 5-tuple in its order) on one canvas.
+def panorama_ramp_weight(x, y, w, h, ramp):
+    """``apap_panorama_ramp_weight`` (host only): the weight of pixel (x, y) of a w x h picture."""
+    return int(lib().apap_panorama_ramp_weight(int(x), int(y), int(w), int(h), int(ramp)))
+
+
+def panorama_ramp_quotients(total, wsum):
+    """``apap_panorama_ramp_quotients``: the ramp kernel's division on the host, element by element (uint32 arrays)."""
+    total = np.ascontiguousarray(total, dtype=np.uint32)
+    wsum = np.ascontiguousarray(wsum, dtype=np.uint32)
+    if total.shape != wsum.shape:
+        raise ValueError(f"panorama_ramp_quotients: {total.shape} sums and {wsum.shape} weight sums")
+    out = np.zeros(total.shape, np.uint32)
+    lib().apap_panorama_ramp_quotients(_ptr(total, C.c_uint), _ptr(wsum, C.c_uint), int(total.size), _ptr(out, C.c_uint))
+    return out
+
+
+def panorama(center, layers, blend="mean", device=-1, ctx=None, return_status=False, ramp=32):
+    """``apap_panorama`` (``blend`` 'mean' or 'paste') or ``apap_panorama_ramp`` ('ramp', with the ramp width ``ramp``, which the
+    other blends ignore): the centre picture and every layer (a :class:`PanoramaLayer` or a 5-tuple in its order) on one canvas.
     Returns ``(canvas (H, W, 3) uint8, (W, H, OX, OY))`` - with ``return_status=True`` also the per-layer status words, and
     then a status does not raise.  Neither the grids nor any other input is modified."""
     who = "panorama"
-    mode = panorama_mode(blend, who)
+    entry, mode = panorama_entry(blend, ramp, who)
     layers, (fw, fh, ox, oy) = panorama_geometry(layers, who)
     n = len(layers)
     center = np.ascontiguousarray(center, dtype=np.uint8)
@@ -1276,9 +1310,8 @@ def panorama(center, layers, blend="mean", device=-1, ctx=None, return_status=Fa
     out = np.empty((Hc, W, 3), np.uint8)
     status = np.zeros(n, np.int32)
     ip, vpp = (lambda a: _ptr(a, C.c_int)), (lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs]))
-    code = lib().apap_panorama(_h(ctx), _ptr(center, C.c_uint8), center.shape[0], center.shape[1], vpp(imgs), ip(ih), ip(iw), vpp(grids),
-                               ip(mr), ip(mc), vpp(mws), ip(nw), vpp(mhs), ip(nh), ip(fw), ip(fh), ip(ox), ip(oy), n, mode,
-                               _ptr(out, C.c_uint8), ip(status), device)
+    code = entry(_h(ctx), _ptr(center, C.c_uint8), center.shape[0], center.shape[1], vpp(imgs), ip(ih), ip(iw), vpp(grids), ip(mr), ip(mc),
+                 vpp(mws), ip(nw), vpp(mhs), ip(nh), ip(fw), ip(fh), ip(ox), ip(oy), n, mode, _ptr(out, C.c_uint8), ip(status), device)
     if return_status and code in (ERR_SINGULAR, ERR_INDEX):
         return out, (W, Hc, OX, OY), status
     check(code)

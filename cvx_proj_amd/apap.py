@@ -14,7 +14,8 @@ the inputs come from ``--pair``)::
                                 [--data-root DIR | --pair pair.npz | --synth C1]
                                 [--config configs/case1.txt] [--out-prefix ../diff_1/results/]
                                 [--mesh-size 100] [--gamma 0.5] [--sigma 100] [--warp out.npy | --stitch out.npy]
-                                [--panorama pano.npy] [--resident] [--timing]
+                                [--panorama pano.npy [--panorama-blend mean|paste|ramp] [--panorama-ramp 32]]
+                                [--resident] [--timing]
 
 The command goes through the host-buffer entry points of the C ABI (``apap_local_homography_pts``, ``apap_local_warp``,
 ``apap_invert_normalize_flatten``): no torch in the process - a pair is ~1 ms of GPU work, importing torch costs 2 s.
@@ -262,7 +263,7 @@ class APAP:
         return out
 
 
-def panorama(center_img, layers, blend="mean", device=-1, ctx=None):
+def panorama(center_img, layers, blend="mean", device=-1, ctx=None, ramp=32):
     """Every view of a case on one canvas, in one fused pass on the GPU: ``center_img`` and each :class:`PanoramaLayer`
     (the neighbour's picture, its grid from :meth:`APAP.local_homography`, its mesh, and the ``final_size`` / offsets of its
     pair - what :meth:`APAP.local_warp` takes), warped through its own grid.  The reference stitches one pair at a time
@@ -273,12 +274,15 @@ def panorama(center_img, layers, blend="mean", device=-1, ctx=None):
     ``local_warp`` of its pair, byte for byte, at column ``OX - offset_x``, row ``OY - offset_y``.  ``blend="mean"``:
     ``uniform_blend`` made symmetric in any number of pictures - per channel the truncated mean of the values with a non-zero
     byte (one layer: :meth:`APAP.local_stitch`).  ``blend="paste"``: the centre inside its rectangle, black pixels included,
-    elsewhere the first layer with a non-zero byte (the rule of ``image_warping(direct_blend=True)``).
+    elsewhere the first layer with a non-zero byte (the rule of ``image_warping(direct_blend=True)``).  ``blend="ramp"``: the
+    mean with a weight per sample, ``min(d, ramp)`` where ``d`` = 1, 2, ... is the distance of the *source* pixel from its
+    picture's border (for the centre the pixel itself), so that every picture fades out over ``ramp`` pixels instead of ending
+    in a step; ``ramp`` is an integer 1 .. 256 (1 is ``"mean"``), ignored by the other blends.
 
     Returns ``(canvas (H, W, 3) uint8, (W, H, OX, OY))``.  The grids are not modified.  A singular cell raises
     ``LinAlgError``, mesh edges that do not cover a pair canvas ``IndexError``, as ``local_warp`` of that layer would, with
     the layer's index in the message."""
-    return _native.panorama(center_img, layers, blend=blend, device=device, ctx=ctx)
+    return _native.panorama(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp)
 
 
 def panorama_layer(src, dst, H_global, other_img, center_shape, mesh_size=100, gamma=0.5, sigma=100, device=-1, ctx=None):
@@ -394,7 +398,9 @@ def main(argv=None):
     ap.add_argument("--panorama", help="stitch ALL the listed pictures of a case (--cases c --imgs i,j,...) onto its centre "
                                        "picture in one fused pass and save the canvas to this .npy (several cases: the case "
                                        "index goes before the extension)")
-    ap.add_argument("--panorama-blend", choices=("mean", "paste"), default="mean")
+    ap.add_argument("--panorama-blend", choices=("mean", "paste", "ramp"), default="mean")
+    ap.add_argument("--panorama-ramp", type=int, default=32, metavar="N",
+                    help="--panorama-blend ramp: a picture's weight grows over N pixels from its border (1 .. 256)")
     ap.add_argument("--device", type=int, default=-1)
     ap.add_argument("--resident", action="store_true",
                     help="one resident pass per pair through cvx_proj_amd.pipeline (imports torch: ~2 s more start-up, ~0.3 ms less "
@@ -503,7 +509,7 @@ def main(argv=None):
                                 "save_ms": (time.perf_counter() - t2) * 1e3})
     for case_idx, (center_img, layers) in panoramas.items():
         t0 = time.perf_counter()
-        canvas, bounds = panorama(center_img, layers, blend=a.panorama_blend, device=a.device)
+        canvas, bounds = panorama(center_img, layers, blend=a.panorama_blend, device=a.device, ramp=a.panorama_ramp)
         out = a.panorama
         if len(panoramas) > 1:
             root, ext = os.path.splitext(out)

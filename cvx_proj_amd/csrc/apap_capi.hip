@@ -1241,15 +1241,15 @@ int apap_image_warp(apap_ctx *ctx, const uint8_t *base, int h1, int w1, const ui
 }
 
 // ------------------------------------------------------------------ panorama (apap_panorama.hip)
-// `status` (may be NULL) receives the n_layers status words whatever the call returns once the kernels ran.
-int apap_panorama(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs, const int *img_h,
+// `status` (may be NULL) receives the n_layers status words whatever the call returns once the kernels ran.  `ramp` as in
+// apap::panorama_check: NULL for apap_panorama, the ramp width for apap_panorama_ramp.
+static int panorama_host(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs, const int *img_h,
                   const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols, const double *const *mesh_w,
                   const int *n_w, const double *const *mesh_h, const int *n_h, const int *final_w, const int *final_h, const int *off_x,
-                  const int *off_y, int n_layers, int mode, uint8_t *out, int *status, int device) {
-    const char *who = "apap_panorama";
+                  const int *off_y, int n_layers, int mode, const int *ramp, uint8_t *out, int *status, int device, const char *who) {
     int b[4];
     int rc = apap::panorama_check(center_h, center_w, img_h, img_w, mesh_rows, mesh_cols, n_w, n_h, final_w, final_h, off_x, off_y,
-                                  n_layers, mode, b, who);
+                                  n_layers, mode, ramp, b, who);
     if (rc) return rc;
     if (!center || !imgs || !Hfwd || !mesh_w || !mesh_h || !out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
     for (int k = 0; k < n_layers; ++k)
@@ -1297,9 +1297,9 @@ int apap_panorama(apap_ctx *ctx, const uint8_t *center, int center_h, int center
         p_mw[k] = d_mw[k].as<const double>();
         p_mh[k] = d_mh[k].as<const double>();
     }
-    rc = apap_panorama_device(ctx, d_pic[0].as<const uint8_t>(), center_h, center_w, p_img.data(), img_h, img_w, p_h.data(), mesh_rows,
-                              mesh_cols, p_mw.data(), n_w, p_mh.data(), n_h, final_w, final_h, off_x, off_y, n_layers, mode,
-                              d_out.as<uint8_t>(), work.as<void>(), work.bytes, d_status.as<int>(), call.stream());
+    rc = apap::panorama_device(ctx, d_pic[0].as<const uint8_t>(), center_h, center_w, p_img.data(), img_h, img_w, p_h.data(), mesh_rows,
+                               mesh_cols, p_mw.data(), n_w, p_mh.data(), n_h, final_w, final_h, off_x, off_y, n_layers, mode, ramp,
+                               d_out.as<uint8_t>(), work.as<void>(), work.bytes, d_status.as<int>(), call.stream(), who);
     if (rc) return rc;
     call.down(st.data(), d_status);
     call.down(out, d_out);
@@ -1311,6 +1311,23 @@ int apap_panorama(apap_ctx *ctx, const uint8_t *center, int center_h, int center
         if ((rc = status_to_code(st[k], layer))) return rc;
     }
     return APAP_OK;
+}
+
+int apap_panorama(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs, const int *img_h,
+                  const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols, const double *const *mesh_w,
+                  const int *n_w, const double *const *mesh_h, const int *n_h, const int *final_w, const int *final_h, const int *off_x,
+                  const int *off_y, int n_layers, int mode, uint8_t *out, int *status, int device) {
+    return panorama_host(ctx, center, center_h, center_w, imgs, img_h, img_w, Hfwd, mesh_rows, mesh_cols, mesh_w, n_w, mesh_h, n_h, final_w,
+                         final_h, off_x, off_y, n_layers, mode, nullptr, out, status, device, "apap_panorama");
+}
+
+int apap_panorama_ramp(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs, const int *img_h,
+                       const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols,
+                       const double *const *mesh_w, const int *n_w, const double *const *mesh_h, const int *n_h, const int *final_w,
+                       const int *final_h, const int *off_x, const int *off_y, int n_layers, int ramp, uint8_t *out, int *status,
+                       int device) {
+    return panorama_host(ctx, center, center_h, center_w, imgs, img_h, img_w, Hfwd, mesh_rows, mesh_cols, mesh_w, n_w, mesh_h, n_h, final_w,
+                         final_h, off_x, off_y, n_layers, APAP_PANORAMA_RAMP, &ramp, out, status, device, "apap_panorama_ramp");
 }
 
 }  // extern "C"

@@ -103,11 +103,21 @@ struct WarpTables {
 };
 WarpTables warp_tables(void *d_work, int mesh_rows, int mesh_cols, int final_w, int final_h);
 
+// The panorama's third blend, the edge ramp, has entry points of its own (apap_panorama_ramp*): as a mode it exists only
+// inside the library, and apap_panorama[_device] refuse it like any other unknown mode.
+#define APAP_PANORAMA_RAMP 2
 // The argument checks of the panorama's entry points (apap_panorama.hip) that need no device pointer; fills bounds[4] =
-// W, H, OX, OY.
+// W, H, OX, OY.  `ramp` is NULL for the entry points that take a mode (APAP_PANORAMA_MEAN or APAP_PANORAMA_PASTE) and
+// points to the ramp width, 1 .. APAP_PANORAMA_MAX_RAMP, for those that take one (`mode` is APAP_PANORAMA_RAMP then).
 int panorama_check(int center_h, int center_w, const int *img_h, const int *img_w, const int *mesh_rows, const int *mesh_cols,
                    const int *n_w, const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y,
-                   int n_layers, int mode, int *bounds, const char *who);
+                   int n_layers, int mode, const int *ramp, int *bounds, const char *who);
+// apap_panorama_device and apap_panorama_ramp_device: the set-up launches and k_panorama<mode>, with `who` in the messages.
+int panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs, const int *img_h,
+                    const int *img_w, const float *const *d_Hfwd, const int *mesh_rows, const int *mesh_cols,
+                    const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h, const int *n_h, const int *final_w,
+                    const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode, const int *ramp, uint8_t *d_out,
+                    void *d_work, size_t work_bytes, int *d_status, void *stream, const char *who);
 
 constexpr int kMoments = 30;       // distinct sums of A^T W^2 A
 

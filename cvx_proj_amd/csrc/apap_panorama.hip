@@ -26,6 +26,11 @@
 //   paste: inside the centre's rectangle the centre, unconditionally; outside it the first present layer.  A pixel that is
 //          decided is not computed again, and once a ballot shows a whole strip decided the wave leaves the layer loop - a
 //          strip wholly inside the centre's rectangle computes no coordinate at all.
+//   ramp : the mean with a weight per sample, min(distance of the SOURCE pixel from its picture's border, ramp), 1 .. ramp
+//          (ramp_weight; the centre's source pixel is (X - OX, Y - OY)).  Per pixel three registers of weight x value sums
+//          (below 2^21) and the weight sums of two neighbouring pixels in one (below 2^13 each, 16 bits apart); a layer's
+//          sixteen weights wait for its gathered pixels in registers.  The quotient is ramp_quotient, one IEEE float32
+//          division per channel - exact for these ranges, checked on the host through apap_panorama_ramp_quotients.
 // The canvas is written once with 12-byte non-temporal stores (a row's tail byte by byte, never past the row).
 #include <hip/hip_runtime.h>
 
@@ -51,6 +56,21 @@ constexpr unsigned kMeanShift = 18;
 __host__ __device__ inline unsigned mean_recip(unsigned count) { return count ? ((1u << kMeanShift) - 1u) / count + 1u : 0u; }
 __host__ __device__ inline unsigned mean_div(unsigned sum, unsigned recip) { return (sum * recip) >> kMeanShift; }
 
+// The weight of pixel (x, y) of a w x h picture: its distance from the border, counted from 1, at most ramp.
+__host__ __device__ inline int min_of(int a, int b) { return a < b ? a : b; }
+__host__ __device__ inline int ramp_weight(int x, int y, int w, int h, int ramp) {
+    return min_of(min_of(min_of(x + 1, w - x), min_of(y + 1, h - y)), ramp);
+}
+
+// floor(sum / wsum) for wsum = 1 .. 17 x 256 and sum <= 255 wsum (below 2^21): both convert to float32 exactly, and the
+// correctly rounded quotient truncates to the true one.  Where sum = k wsum the quotient is k, exactly.  Elsewhere the true
+// quotient lies at least 1 / wsum > 2^-13 below k + 1 and rounding moves it by less than 255 x 2^-24 < 2^-16; it does not
+// fall below k, which is a float32.  wsum = 0 gives 0.  Plain IEEE `/` on both sides (no reciprocal, no fast-math): the
+// same bits on the host and in the kernel.
+__host__ __device__ inline unsigned ramp_quotient(unsigned sum, unsigned wsum) {
+    return wsum ? (unsigned)((float)sum / (float)wsum) : 0u;
+}
+
 struct PanoLayer {      // 64 bytes
     const uint8_t *img;
     const double *hinv_pad;     // [cells][APAP_HINV_STRIDE]
@@ -68,7 +88,7 @@ struct PanoArgs {
     uint8_t *out;
     int center_h, center_w, OX, OY, W, H, n_layers, col_blocks;
     unsigned clast;             // bytes of the centre - 4
-    int pad;
+    int ramp;                   // ramp: the largest weight
 };
 static_assert(sizeof(PanoArgs) <= 4096, "kernel arguments");
 
@@ -96,6 +116,8 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
     unsigned live = 0u;
     unsigned und = 0u;                  // paste: live pixels no picture has decided yet
     unsigned a0[kRows][4], a1[kRows][4];    // mean: ch0 | ch2 << 16 and ch1 | count << 16; paste: a0 = the pixel
+    unsigned a2[kRows][4], aw[kRows][2];    // ramp: a0, a1, a2 = sums of weight x channel; aw = weight sums of pixels 2 k | 2 k + 1 << 16
+    const int ramp = A.ramp;
     {
         const uint8_t *__restrict__ center = A.center;
         unsigned co[kRows][4];
@@ -121,6 +143,13 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
                 if (kMode == APAP_PANORAMA_MEAN) {
                     a0[t][k] = c & 0x00ff00ffu;
                     a1[t][k] = ((c >> 8) & 0xffu) | ((unsigned)(c != 0u) << 16);
+                } else if (kMode == APAP_PANORAMA_RAMP) {
+                    // c != 0 only inside the centre's rectangle, where the weight is defined
+                    const unsigned wt = c != 0u ? (unsigned)ramp_weight(j0 + k - A.OX, y_first + t - A.OY, A.center_w, A.center_h, ramp) : 0u;
+                    a0[t][k] = __umul24(wt, c & 0xffu);
+                    a1[t][k] = __umul24(wt, (c >> 8) & 0xffu);
+                    a2[t][k] = __umul24(wt, c >> 16);
+                    aw[t][k >> 1] = (k & 1) ? aw[t][k >> 1] | (wt << 16) : wt;
                 } else {
                     a0[t][k] = c;
                     a1[t][k] = 0u;
@@ -166,6 +195,11 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
         for (int t = 0; t < kRows; ++t)
 #pragma unroll
             for (int k = 0; k < 4; ++k) off[t][k] = 0xffffffffu;
+        unsigned wgt[kRows][4];         // ramp: the weights of the layer's samples
+#pragma unroll
+        for (int t = 0; t < kRows; ++t)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) wgt[t][k] = 0u;
         // One pass per cell row the strip touches, as in k_warp_rows: fetch that row's matrices, then do every strip row that
         // lies in it.  All branches are wave-uniform.
         while (todo != 0u) {
@@ -205,6 +239,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
                     const int ix = (int)tx, iy = (int)ty;
                     const bool ok = (tx > 0.0) & (ty > 0.0) & (ix < img_w) & (iy < img_h) & (((want >> (4 * t + k)) & 1u) != 0u);
                     off[t][k] = ok ? (__umul24((unsigned)iy, (unsigned)img_w) + (unsigned)ix) * 3u : 0xffffffffu;
+                    if (kMode == APAP_PANORAMA_RAMP) wgt[t][k] = (unsigned)ramp_weight(ix, iy, img_w, img_h, ramp);  // used where ok
                 }
             }
         }
@@ -222,6 +257,13 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
                 if (kMode == APAP_PANORAMA_MEAN) {
                     a0[t][k] += v & 0x00ff00ffu;
                     a1[t][k] += ((v >> 8) & 0xffu) | ((unsigned)(v != 0u) << 16);
+                } else if (kMode == APAP_PANORAMA_RAMP) {
+                    // v != 0 only where the sample lies inside its picture: a black or outside sample weighs nothing
+                    const unsigned wt = v != 0u ? wgt[t][k] : 0u;
+                    a0[t][k] += __umul24(wt, v & 0xffu);
+                    a1[t][k] += __umul24(wt, (v >> 8) & 0xffu);
+                    a2[t][k] += __umul24(wt, v >> 16);
+                    aw[t][k >> 1] += wt << (16 * (k & 1));
                 } else {
                     // off is the outside marker for every pixel that is decided: v != 0 only where the pixel is still open
                     a0[t][k] = v != 0u ? v : a0[t][k];
@@ -241,6 +283,9 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
             if (kMode == APAP_PANORAMA_MEAN) {
                 const unsigned m = recip[a1[t][k] >> 16] & 0x7ffffu;
                 p[k] = mean_div(a0[t][k] & 0xffffu, m) | (mean_div(a1[t][k] & 0xffffu, m) << 8) | (mean_div(a0[t][k] >> 16, m) << 16);
+            } else if (kMode == APAP_PANORAMA_RAMP) {
+                const unsigned ws = (aw[t][k >> 1] >> (16 * (k & 1))) & 0xffffu;
+                p[k] = ramp_quotient(a0[t][k], ws) | (ramp_quotient(a1[t][k], ws) << 8) | (ramp_quotient(a2[t][k], ws) << 16);
             } else {
                 p[k] = a0[t][k];
             }
@@ -295,10 +340,14 @@ namespace apap {
 
 int panorama_check(int center_h, int center_w, const int *img_h, const int *img_w, const int *mesh_rows, const int *mesh_cols,
                    const int *n_w, const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y,
-                   int n_layers, int mode, int *bounds, const char *who) {
+                   int n_layers, int mode, const int *ramp, int *bounds, const char *who) {
     if (!img_h || !img_w || !mesh_rows || !mesh_cols || !n_w || !n_h) return fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
-    if (mode != APAP_PANORAMA_MEAN && mode != APAP_PANORAMA_PASTE)
+    if (ramp) {
+        if (*ramp < 1 || *ramp > APAP_PANORAMA_MAX_RAMP)
+            return fail(APAP_ERR_INVALID_ARG, "%s: ramp = %d (1 .. %d)", who, *ramp, APAP_PANORAMA_MAX_RAMP);
+    } else if (mode != APAP_PANORAMA_MEAN && mode != APAP_PANORAMA_PASTE) {
         return fail(APAP_ERR_INVALID_ARG, "%s: mode = %d (APAP_PANORAMA_MEAN or APAP_PANORAMA_PASTE)", who, mode);
+    }
     const int rc = bounds_of(center_h, center_w, final_w, final_h, off_x, off_y, n_layers, bounds, who);
     if (rc) return rc;
     // a picture: at least 2 pixels (the gather reads a dword), sides below 2^24 (24-bit multiplies), below 2 GiB (the sign
@@ -321,37 +370,14 @@ int panorama_check(int center_h, int center_w, const int *img_h, const int *img_
     return APAP_OK;
 }
 
-}  // namespace apap
-
-extern "C" {
-
-unsigned apap_panorama_mean_of(unsigned sum, unsigned count) { return mean_div(sum, mean_recip(count)); }
-
-int apap_panorama_bounds(int center_h, int center_w, const int *final_w, const int *final_h, const int *off_x, const int *off_y,
-                         int n_layers, int *out) {
-    return bounds_of(center_h, center_w, final_w, final_h, off_x, off_y, n_layers, out, "apap_panorama_bounds");
-}
-
-size_t apap_panorama_workspace_bytes(const int *mesh_rows, const int *mesh_cols, const int *final_w, const int *final_h, int n_layers) {
-    if (!mesh_rows || !mesh_cols || !final_w || !final_h || n_layers < 1 || n_layers > kMaxLayers) return 0;
-    size_t total = 0;
-    for (int k = 0; k < n_layers; ++k) {
-        const size_t b = slice_bytes(mesh_rows[k], mesh_cols[k], final_w[k], final_h[k]);
-        if (b == 0) return 0;
-        total += b;
-    }
-    return total;
-}
-
-int apap_panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
-                         const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows, const int *mesh_cols,
-                         const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h, const int *n_h,
-                         const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode,
-                         uint8_t *d_out, void *d_work, size_t work_bytes, int *d_status, void *stream) {
-    const char *who = "apap_panorama_device";
+int panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs, const int *img_h,
+                    const int *img_w, const float *const *d_Hfwd, const int *mesh_rows, const int *mesh_cols,
+                    const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h, const int *n_h, const int *final_w,
+                    const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode, const int *ramp, uint8_t *d_out,
+                    void *d_work, size_t work_bytes, int *d_status, void *stream, const char *who) {
     int b[4];
-    int rc = apap::panorama_check(center_h, center_w, img_h, img_w, mesh_rows, mesh_cols, n_w, n_h, final_w, final_h, off_x, off_y,
-                                  n_layers, mode, b, who);
+    int rc = panorama_check(center_h, center_w, img_h, img_w, mesh_rows, mesh_cols, n_w, n_h, final_w, final_h, off_x, off_y, n_layers,
+                            mode, ramp, b, who);
     if (rc) return rc;
     if (!d_center || !d_imgs || !d_Hfwd || !d_mesh_w || !d_mesh_h || !d_out || !d_work || !d_status)
         return apap::fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
@@ -390,17 +416,68 @@ int apap_panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, i
     A.n_layers = n_layers;
     A.col_blocks = (A.W + kStripCols - 1) / kStripCols;
     A.clast = (unsigned)center_h * (unsigned)center_w * 3u - 4u;
+    A.ramp = ramp ? *ramp : 0;
     const unsigned row_blocks = (unsigned)((A.H + kWaves * kRows - 1) / (kWaves * kRows));
     const dim3 grid((unsigned)A.col_blocks * row_blocks);       // W H < 2^31: below 2^31 blocks
     hipStream_t s = (hipStream_t)stream;
     {
         apap::ProfScope prof(ctx, APAP_PROF_WARP, s);
-        if (mode == APAP_PANORAMA_MEAN) hipLaunchKernelGGL(k_panorama<APAP_PANORAMA_MEAN>, grid, dim3(kWaves * 64), 0, s, A);
+        if (ramp) hipLaunchKernelGGL(k_panorama<APAP_PANORAMA_RAMP>, grid, dim3(kWaves * 64), 0, s, A);
+        else if (mode == APAP_PANORAMA_MEAN) hipLaunchKernelGGL(k_panorama<APAP_PANORAMA_MEAN>, grid, dim3(kWaves * 64), 0, s, A);
         else hipLaunchKernelGGL(k_panorama<APAP_PANORAMA_PASTE>, grid, dim3(kWaves * 64), 0, s, A);
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_panorama_device launch");
+    if (e != hipSuccess) return hip_fail(e, "k_panorama launch");
     return APAP_OK;
+}
+
+}  // namespace apap
+
+extern "C" {
+
+unsigned apap_panorama_mean_of(unsigned sum, unsigned count) { return mean_div(sum, mean_recip(count)); }
+
+int apap_panorama_ramp_weight(int x, int y, int w, int h, int ramp) { return ramp_weight(x, y, w, h, ramp); }
+
+void apap_panorama_ramp_quotients(const unsigned *sum, const unsigned *wsum, int n, unsigned *out) {
+    if (!sum || !wsum || !out) return;
+    for (int k = 0; k < n; ++k) out[k] = ramp_quotient(sum[k], wsum[k]);
+}
+
+int apap_panorama_bounds(int center_h, int center_w, const int *final_w, const int *final_h, const int *off_x, const int *off_y,
+                         int n_layers, int *out) {
+    return bounds_of(center_h, center_w, final_w, final_h, off_x, off_y, n_layers, out, "apap_panorama_bounds");
+}
+
+size_t apap_panorama_workspace_bytes(const int *mesh_rows, const int *mesh_cols, const int *final_w, const int *final_h, int n_layers) {
+    if (!mesh_rows || !mesh_cols || !final_w || !final_h || n_layers < 1 || n_layers > kMaxLayers) return 0;
+    size_t total = 0;
+    for (int k = 0; k < n_layers; ++k) {
+        const size_t b = slice_bytes(mesh_rows[k], mesh_cols[k], final_w[k], final_h[k]);
+        if (b == 0) return 0;
+        total += b;
+    }
+    return total;
+}
+
+int apap_panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                         const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows, const int *mesh_cols,
+                         const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h, const int *n_h,
+                         const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode,
+                         uint8_t *d_out, void *d_work, size_t work_bytes, int *d_status, void *stream) {
+    return apap::panorama_device(ctx, d_center, center_h, center_w, d_imgs, img_h, img_w, d_Hfwd, mesh_rows, mesh_cols, d_mesh_w, n_w,
+                                 d_mesh_h, n_h, final_w, final_h, off_x, off_y, n_layers, mode, nullptr, d_out, d_work, work_bytes,
+                                 d_status, stream, "apap_panorama_device");
+}
+
+int apap_panorama_ramp_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                              const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows,
+                              const int *mesh_cols, const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h,
+                              const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers,
+                              int ramp, uint8_t *d_out, void *d_work, size_t work_bytes, int *d_status, void *stream) {
+    return apap::panorama_device(ctx, d_center, center_h, center_w, d_imgs, img_h, img_w, d_Hfwd, mesh_rows, mesh_cols, d_mesh_w, n_w,
+                                 d_mesh_h, n_h, final_w, final_h, off_x, off_y, n_layers, APAP_PANORAMA_RAMP, &ramp, d_out, d_work,
+                                 work_bytes, d_status, stream, "apap_panorama_ramp_device");
 }
 
 }  // extern "C"

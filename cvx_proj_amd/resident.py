@@ -624,8 +624,9 @@ def panorama_workspace_bytes(layers):
                                                        fh.ctypes.data_as(ip), len(layers))
 
 
-def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, work=None):
-    """``apap_panorama_device`` on the current stream of the tensors' device, no host synchronisation: the centre picture and
+def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, work=None, ramp=32):
+    """``apap_panorama_device`` (``blend="ramp"``: ``apap_panorama_ramp_device`` with the ramp width ``ramp``, an integer 1 ..
+    256 that the other blends ignore) on the current stream of the tensors' device, no host synchronisation: the centre picture and
     every layer on one canvas in one fused pass (``apap.panorama`` on device tensors).  ``center`` (h, w, 3) uint8; a layer is
     a ``PanoramaLayer`` (or a 5-tuple in its order) of device tensors - ``img`` (h, w, 3) uint8, ``local_homography`` (rows,
     cols, 3, 3) float32, ``mesh`` = (mesh_w, mesh_h) float64 - with host ``final_size`` and ``offset``; layers may share
@@ -637,7 +638,7 @@ def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, 
     who = "hip_panorama"
     _needs_device(center, who)
     dev = center.device
-    mode = _native.panorama_mode(blend, who)
+    entry, mode = _native.panorama_entry(blend, ramp, who, device_form=True)
     layers, (fw, fh, ox, oy) = _native.panorama_geometry(layers, who)
     n = len(layers)
 
@@ -673,7 +674,7 @@ def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, 
     vpp = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])      # noqa: E731
     need = _native.lib().apap_panorama_workspace_bytes(ip(mr), ip(mc), ip(fw), ip(fh), n)
     work = _scratch(work, need, dev)
-    _native.check(_native.lib().apap_panorama_device(
+    _native.check(entry(
         _native._h(ctx), center.data_ptr(), center.shape[0], center.shape[1], vpp(imgs), ip(ih), ip(iw), vpp(grids), ip(mr), ip(mc),
         vpp(mws), ip(nw), vpp(mhs), ip(nh), ip(fw), ip(fh), ip(ox), ip(oy), n, mode, out.data_ptr(), work.data_ptr(), work.numel(),
         status.data_ptr(), _stream(dev)))

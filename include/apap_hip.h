@@ -884,6 +884,33 @@ int apap_panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, i
                          const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h, const int *n_h,
                          const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode,
                          uint8_t *d_out, void *d_work, size_t work_bytes, int *d_status, void *stream);
+/* The edge-ramp blend: the mean with a weight per sample, so that a picture fades out towards its own border instead of
+ * ending in a step (in numpy: tests/panorama_ramp_spec.py).  Canvas, layer value, bounds test, truncation and presence are
+ * the panorama's, unchanged; the argument lists are those of apap_panorama / apap_panorama_device with `ramp`, the ramp width
+ * 1 .. APAP_PANORAMA_MAX_RAMP, in place of `mode`; the workspace is apap_panorama_workspace_bytes(...).
+ *   weight   of the pixel (x, y) of an h x w picture: min(d, ramp) with d = min(x + 1, w - x, y + 1, h - y), at least 1
+ *            (apap_panorama_ramp_weight, host only).  For layer k (x, y) is the SOURCE pixel the sample is gathered from, the
+ *            truncated target coordinates; for the centre it is (X - OX, Y - OY).  A weight of the source, not a distance
+ *            transform of the warped footprint: that keeps the blend in the one pass
+ *   output   per channel floor(sum of weight x value / sum of weight) over the present samples, 0 where none is present; a
+ *            black source pixel is absent whatever its weight.  ramp = 1 is APAP_PANORAMA_MEAN byte for byte
+ * Refused like apap_panorama's arguments, before any device is touched: ramp outside 1 .. APAP_PANORAMA_MAX_RAMP.  The ramp is
+ * not a mode of apap_panorama[_device]: those keep refusing every mode but the two above.
+ * apap_panorama_ramp_quotients: the kernel's division, out[k] = floor(sum[k] / wsum[k]) for wsum = 1 .. 17 x 256 and
+ * sum <= 255 wsum by one IEEE float32 division (0 for wsum = 0), as a host function over n values. */
+#define APAP_PANORAMA_MAX_RAMP 256
+int apap_panorama_ramp_weight(int x, int y, int w, int h, int ramp);
+void apap_panorama_ramp_quotients(const unsigned *sum, const unsigned *wsum, int n, unsigned *out);
+int apap_panorama_ramp(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs, const int *img_h,
+                       const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols,
+                       const double *const *mesh_w, const int *n_w, const double *const *mesh_h, const int *n_h, const int *final_w,
+                       const int *final_h, const int *off_x, const int *off_y, int n_layers, int ramp, uint8_t *out, int *status,
+                       int device);
+int apap_panorama_ramp_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                              const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows,
+                              const int *mesh_cols, const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h,
+                              const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers,
+                              int ramp, uint8_t *d_out, void *d_work, size_t work_bytes, int *d_status, void *stream);
 
 #ifdef __cplusplus
 }

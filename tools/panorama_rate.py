@@ -7,14 +7,18 @@ in torch operations on the device.
 
 One JSON line per row, printed and APPENDED to --out.  Rows: a centre picture of configuration C3's size (3840 x 2160, mesh
 200 x 200) with K = 4 neighbours placed to its left, right, top and bottom, and the same at C1's size (768 x 768, mesh 20 x
-20), each in both blend modes.  Seeded pictures and grids (a global placement times I + 1e-3 x a smooth function of the cell),
+20), each in the blends ``mean`` and ``paste`` and in ``ramp`` at ramp width 64.  Seeded pictures and grids (a global placement times I + 1e-3 x a smooth function of the cell),
 resident on the device before the clock starts; outputs, workspaces and status words allocated beforehand.  The two forms
 alternate call by call in one process, every timed call between two events on its stream; median and minimum of --reps
 calls after --warmup.
 
 Beside each time: the algorithmic bytes - every source once, the centre once, the canvas once - over the fused call's time as
 a fraction of 8 TB/s, next to 0.43, what the fused per-pair warp + blend kernel is recorded at.  No time is a pass condition;
-the tool fails without a GPU, and when the SHA-256 of the panorama differs from the baseline's."""
+the tool fails without a GPU, and when the SHA-256 of the panorama differs from the baseline's.
+
+The chain has no ramp: a weight of the source pixel is lost once a layer is a finished canvas.  A ``ramp`` row therefore times
+three forms in the same alternation - the fused ramp, the fused ``mean`` and the ``mean`` chain - and reports the ramp over
+each of the two yardsticks; its check is that ramp width 1 gives the SHA-256 of the fused ``mean``."""
 import argparse
 import hashlib
 import json
@@ -28,6 +32,7 @@ sys.path.insert(0, ROOT)
 
 PEAK_BYTES_PER_SECOND = 8.0e12
 K3_FRACTION = 0.43
+RAMP = 64       # the ramp width of the `ramp` rows
 
 
 class _Shape:
@@ -123,26 +128,34 @@ def main():
                 base_out[OY:OY + ch, OX:OX + cw] = center
             return base_out
 
-        def fused(mode):
+        def fused(mode, ramp=RAMP):
             status.zero_()
-            return resident.hip_panorama(center, layers, blend=mode, out=out, status=status, work=work)[0]
+            return resident.hip_panorama(center, layers, blend=mode, out=out, status=status, work=work, ramp=ramp)[0]
 
-        for mode in ("mean", "paste"):
+        for mode in ("mean", "paste", "ramp"):
+            # a ramp row: the fused ramp beside the fused mean and the mean chain, its two yardsticks
+            forms = [(fused, mode), (chain, mode)] if mode != "ramp" else [(fused, "ramp"), (fused, "mean"), (chain, "mean")]
             for _ in range(a.warmup):
-                fused(mode)
-                chain(mode)
+                for fn, m in forms:
+                    fn(m)
             torch.cuda.synchronize(dev)
-            t_fused, t_chain = [], []
+            times = [[] for _ in forms]
             for _ in range(a.reps):
-                for fn, times in ((fused, t_fused), (chain, t_chain)):
+                for (fn, m), t in zip(forms, times):
                     e0, e1 = event_pair()
                     e0.record()
-                    fn(mode)
+                    fn(m)
                     e1.record()
                     e1.synchronize()
-                    times.append(e0.elapsed_time(e1) * 1e-3)
-            sha_f = hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()
-            sha_c = hashlib.sha256(base_out.cpu().numpy().tobytes()).hexdigest()
+                    t.append(e0.elapsed_time(e1) * 1e-3)
+            t_fused, t_chain = times[0], times[-1]
+            sha = lambda t: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()      # noqa: E731
+            if mode == "ramp":      # `out` holds the fused mean, the form that ran last into it
+                sha_c = sha(out)
+                sha_f = sha(fused("ramp", 1))
+                sha_ramp = sha(fused("ramp"))
+            else:
+                sha_f, sha_c = sha(out), sha(base_out)
             nbytes = 3.0 * (sum(l.img.shape[0] * l.img.shape[1] for l in layers) + ch * cw + Hc * W)
             med_f, med_c = float(np.median(t_fused)), float(np.median(t_chain))
             frac = nbytes / PEAK_BYTES_PER_SECOND / med_f
@@ -151,9 +164,14 @@ def main():
                     "chain_seconds_median": med_c, "chain_seconds_min": float(min(t_chain)), "ratio_chain_over_fused": med_c / med_f,
                     "algorithmic_bytes": nbytes, "fused_fraction_of_8TBps": frac, "fused_fraction_over_k_warp_fast_blend": frac / K3_FRACTION,
                     "status": status.tolist(), "sha256_fused": sha_f, "sha256_equal": sha_f == sha_c}
+            if mode == "ramp":
+                med_m = float(np.median(times[1]))
+                line.update({"row": f"{name}: {w}x{h}, mesh {mesh}, K = {K}, ramp {RAMP}", "mean_seconds_median": med_m,
+                             "mean_seconds_min": float(min(times[1])), "ratio_ramp_over_mean": med_f / med_m,
+                             "sha256_fused": sha_ramp, "sha256_ramp_1": sha_f, "sha256_equal": sha_f == sha_c})
             lines.append(line)
             if sha_f != sha_c:
-                failed.append(f"{line['row']}: the panorama and the chain differ")
+                failed.append(f"{line['row']}: " + ("ramp width 1 and the mean differ" if mode == "ramp" else "the panorama and the chain differ"))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as f:
         for line in lines:
