@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "apap_internal.h"
+#include "apap_warp_dev.h"      // APAP_STORE_PX4: the canvas store the local warp's kernels use
 
 namespace {
 
@@ -52,15 +53,6 @@ struct alignas(16) WarpProblem {   // one problem, in device memory
 static_assert(sizeof(WarpProblem) == 144, "the descriptor table's stride");
 
 size_t table_bytes(int n) { return ((size_t)n * sizeof(WarpProblem) + 255) / 256 * 256; }
-
-// 12 bytes to ANY byte address with the non-temporal hint (global_store_dwordx3 ... nt): the canvas is written once and
-// not read again by this kernel
-__device__ __forceinline__ void store12_stream(uint8_t *p, unsigned a, unsigned b, unsigned c) {
-    typedef unsigned Dwords3 __attribute__((ext_vector_type(3)));
-    typedef Dwords3 Dwords3AnyByte __attribute__((aligned(1)));
-    const Dwords3 v = {a, b, c};
-    __builtin_nontemporal_store(v, reinterpret_cast<Dwords3AnyByte *>(p));
-}
 
 // the 3 bytes at byte offset `off` of a picture of `total` bytes (off + 3 <= total), in the low 24 bits.  One unaligned dword
 // load; at the picture's last pixel the dword one byte earlier, shifted, so that no byte beyond the picture is touched.
@@ -156,16 +148,8 @@ __device__ __forceinline__ void warp_lane(const WarpProblem &P, int x0, int y) {
         const unsigned mean = (warped[k] & bpx[k]) + (((warped[k] ^ bpx[k]) & 0x00fefefeu) >> 1);
         px[k] = in[k] ? ((direct || warped[k] == 0u) ? bpx[k] : mean) : warped[k];
     }
-    uint8_t *o = P.out + ((size_t)y * (size_t)cw + (size_t)x0) * 3u;
-    if (x0 + kPxPerLane <= cw) {
-        store12_stream(o, px[0] | (px[1] << 24), (px[1] >> 8) | (px[2] << 16), (px[2] >> 16) | (px[3] << 8));
-    } else {
-        for (int k = 0; k < kPxPerLane && x0 + k < cw; ++k) {
-            o[3 * k] = (uint8_t)(px[k] & 0xff);
-            o[3 * k + 1] = (uint8_t)((px[k] >> 8) & 0xff);
-            o[3 * k + 2] = (uint8_t)((px[k] >> 16) & 0xff);
-        }
-    }
+    static_assert(kPxPerLane == 4, "APAP_STORE_PX4 stores a group of four");
+    APAP_STORE_PX4(P.out + ((size_t)y * (size_t)cw + (size_t)x0) * 3u, px, min(kPxPerLane, cw - x0));
 }
 
 __global__ __launch_bounds__(kThreads) void k_image_warp(const WarpProblem *__restrict__ tab, int n_problems) {

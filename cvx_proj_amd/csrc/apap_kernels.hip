@@ -1953,32 +1953,10 @@ __global__ __launch_bounds__(256) void k_warp(const uint8_t *__restrict__ img, i
     if (kBlend) {
         const unsigned clast = (unsigned)center_h * (unsigned)center_w * 3u - 4u;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int ci = ii[k] - off_y, cj = jj[k] - off_x;
-            const bool in = ci >= 0 && ci < center_h && cj >= 0 && cj < center_w;
-            const unsigned co = in ? ((unsigned)ci * (unsigned)center_w + (unsigned)cj) * 3u : 0u;
-            const unsigned cc = co < clast ? co : clast;
-            unsigned int c;
-            __builtin_memcpy(&c, center + cc, 4);
-            c = in ? ((c >> (8 * (co - cc))) & 0x00ffffffu) : 0u;
-            // uniform_blend: a pixel is "present" when its channel mean is > 0, i.e. any
-            // channel is non-zero; both present -> floor((a + b) / 2) per channel (float64
-            // sum * 0.5, astype(uint8)), otherwise a + b with one of them 0
-            const unsigned w = px[k];
-            const unsigned avg = (w & c) + (((w ^ c) & 0x00fefefeu) >> 1);
-            px[k] = (w != 0u && c != 0u) ? avg : (w | c);
-        }
+        for (int k = 0; k < 4; ++k)
+            px[k] = blend_center(px[k], center, ii[k] - off_y, jj[k] - off_x, center_h, center_w, clast);
     }
-    uint8_t *o = out + (size_t)g * 3;
-    if (g + 4u <= total) {
-        store12_stream(o, px[0] | (px[1] << 24), (px[1] >> 8) | (px[2] << 16), (px[2] >> 16) | (px[3] << 8));
-    } else {
-        for (unsigned k = 0; k < 4u && g + k < total; ++k) {
-            o[3 * k] = (uint8_t)(px[k] & 0xff);
-            o[3 * k + 1] = (uint8_t)((px[k] >> 8) & 0xff);
-            o[3 * k + 2] = (uint8_t)((px[k] >> 16) & 0xff);
-        }
-    }
+    APAP_STORE_PX4(out + (size_t)g * 3, px, (int)min(4u, total - g));
 }
 
 // K3, row-strip form.  Mesh cells are small (C3: ~20 x 11 pixels), so the flat-order kernel
@@ -2037,19 +2015,8 @@ __global__ __launch_bounds__(256) void k_warp_rows(const uint8_t *__restrict__ i
         int r = rr[0];
 #pragma unroll
         for (int t = 1; t < kRows; ++t) r = (t == first) ? rr[t] : r;
-        const int base = r * mesh_cols;
-        const Hinv9 ha = load_hinv(hinv_pad, (unsigned)(base + col[0]));
-        const Hinv9 hb = load_hinv(hinv_pad, (unsigned)(base + col[3]));
         PixelH q[4];
-        q[0] = pixel_h(ha, xs[0]);
-        q[3] = pixel_h(hb, xs[3]);
-#pragma unroll
-        for (int k = 1; k < 3; ++k) {
-            const bool is_a = col[k] == col[0];
-            Hinv9 hk = select_hinv(is_a, ha, hb);
-            if (!is_a && col[k] != col[3]) hk = load_hinv(hinv_pad, (unsigned)(base + col[k]));  // a third cell
-            q[k] = pixel_h(hk, xs[k]);
-        }
+        strip_cell_row(hinv_pad, r * mesh_cols, col, xs, q);
 #pragma unroll
         for (int t = 0; t < kRows; ++t) {
             if (rr[t] != r) continue;
@@ -2057,77 +2024,27 @@ __global__ __launch_bounds__(256) void k_warp_rows(const uint8_t *__restrict__ i
             const double yd = (double)(y_first + t - off_y);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                // (h0 x + h1 y) + h2 and so on: the order of the reference's matrix-vector product
-                const double t0 = fma(q[k].h1, yd, q[k].p0) + q[k].h2;
-                const double t1 = fma(q[k].h4, yd, q[k].p1) + q[k].h5;
-                const double t2 = fma(q[k].h7, yd, q[k].p2) + q[k].h8;
-                // shared reciprocal (one Newton step: ~2^-46) and a residual correction per
-                // quotient: the quotient's error before its final rounding is ~2^-92
-                double rc = __builtin_amdgcn_rcp(t2);
-                rc = fma(fma(-t2, rc, 1.0), rc, rc);
-                const double q0 = t0 * rc, q1 = t1 * rc;
-                const double tx = fma(fma(-t2, q0, t0), rc, q0);
-                const double ty = fma(fma(-t2, q1, t1), rc, q1);
-                // strict 0 < t < size, then truncation (apap.py:214-215).  For t > 0 the upper
-                // test is the same on the truncated integer (the conversion saturates, NaN
-                // fails t > 0).
-                const int ix = (int)tx, iy = (int)ty;
-                const bool ok = (tx > 0.0) & (ty > 0.0) & (ix < img_w) & (iy < img_h);  // no short-circuit branches
-                // a pixel outside the source is marked by the sign bit (the launcher sends
-                // sources of 2 GiB or more to the flat-order kernel)
-                off[t][k] = ok ? (__umul24((unsigned)iy, (unsigned)img_w) + (unsigned)ix) * 3u : 0xffffffffu;
+                int ix, iy;
+                const bool ok = strip_source(q[k], yd, img_w, img_h, ix, iy);
+                off[t][k] = strip_offset(ok, ix, iy, img_w);
             }
         }
     }
     unsigned int px[kRows][4];
 #pragma unroll
-    for (int t = 0; t < kRows; ++t) {
+    for (int t = 0; t < kRows; ++t)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            // the dword at the pixel's first byte; for the image's very last pixel the dword one
-            // byte earlier, shifted (v_alignbyte_b32), so that no byte beyond the image is touched
-            unsigned int v;
-            const unsigned o = off[t][k];
-            const unsigned oc = o < last ? o : last;
-            __builtin_memcpy(&v, img + oc, 4);
-            v = __builtin_amdgcn_alignbyte(0u, v, o - oc);
-            // v & 0xffffff & ~sign(o): v_bfe_i32 + v_bitop3_b32 (truth table a & b & ~c = 0x40)
-            px[t][k] = (unsigned)__builtin_amdgcn_bitop3_b32((int)v, 0x00ffffff, __builtin_amdgcn_sbfe((int)o, 31u, 1u), 0x40);
-        }
-    }
+        for (int k = 0; k < 4; ++k) px[t][k] = gather_px(img, off[t][k], last);
 #pragma unroll
     for (int t = 0; t < kRows; ++t) {
         const int y = y_first + t;
         if (y >= y_end) break;  // wave-uniform
         if (kBlend) {
-            const int ci = y - off_y;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int cj = j0 + k - off_x;
-                const bool in = ci >= 0 && ci < center_h && cj >= 0 && cj < center_w;
-                const unsigned co = in ? ((unsigned)ci * (unsigned)center_w + (unsigned)cj) * 3u : 0u;
-                const unsigned cc = co < clast ? co : clast;
-                unsigned int c;
-                __builtin_memcpy(&c, center + cc, 4);
-                c = in ? ((c >> (8 * (co - cc))) & 0x00ffffffu) : 0u;
-                const unsigned w = px[t][k];
-                const unsigned avg = (w & c) + (((w ^ c) & 0x00fefefeu) >> 1);
-                px[t][k] = (w != 0u && c != 0u) ? avg : (w | c);
-            }
+            for (int k = 0; k < 4; ++k)
+                px[t][k] = blend_center(px[t][k], center, y - off_y, j0 + k - off_x, center_h, center_w, clast);
         }
-        uint8_t *o = out + ((size_t)(y - row_begin) * (size_t)final_w) * 3 + (unsigned)j0 * 3u;
-        if (npx == 4) {
-            // 4 x 24 bits -> 3 dwords: one shift-or and two byte permutes (v_perm_b32 picks bytes 0-3 from its second
-            // operand, 4-7 from its first); rows start at any byte: an unaligned, non-temporal 12-byte store
-            store12_stream(o, px[t][0] | (px[t][1] << 24), __builtin_amdgcn_perm(px[t][2], px[t][1], 0x05040201u),
-                           __builtin_amdgcn_perm(px[t][3], px[t][2], 0x06050402u));
-        } else {
-            for (int k = 0; k < npx; ++k) {
-                o[3 * k] = (uint8_t)(px[t][k] & 0xff);
-                o[3 * k + 1] = (uint8_t)((px[t][k] >> 8) & 0xff);
-                o[3 * k + 2] = (uint8_t)((px[t][k] >> 16) & 0xff);
-            }
-        }
+        APAP_STORE_PX4(out + ((size_t)(y - row_begin) * (size_t)final_w) * 3 + (unsigned)j0 * 3u, px[t], npx);
     }
 }
 
@@ -2162,8 +2079,8 @@ __device__ __forceinline__ unsigned exact_offset(const double *__restrict__ hinv
     double tx, ty;
     target_of(hinv_pad, cell, (double)(j - off_x), (double)(i - off_y), tx, ty);
     const int ix = (int)tx, iy = (int)ty;
-    const bool ok = (tx > 0.0) & (ty > 0.0) & (ix < img_w) & (iy < img_h);   // as in k_warp_rows
-    return ok ? (__umul24((unsigned)iy, (unsigned)img_w) + (unsigned)ix) * 3u : 0xffffffffu;
+    const bool ok = (tx > 0.0) & (ty > 0.0) & (ix < img_w) & (iy < img_h);   // as in strip_source
+    return strip_offset(ok, ix, iy, img_w);
 }
 
 template <bool kBlend, int kRows>
@@ -2266,7 +2183,7 @@ __global__ __launch_bounds__(256) void k_warp_fast(const uint8_t *__restrict__ i
                 const int ix = n0x[k] + (fx >> kFastFracBits), iy = n0y[k] + (fy >> kFastFracBits);
                 const unsigned lo = min((unsigned)fx & 0xffffu, (unsigned)fy & 0xffffu);
                 const bool ok = ((unsigned)ix < (unsigned)img_w) & ((unsigned)iy < (unsigned)img_h);
-                off[t][k] = ok ? (__umul24((unsigned)iy, (unsigned)img_w) + (unsigned)ix) * 3u : 0xffffffffu;
+                off[t][k] = strip_offset(ok, ix, iy, img_w);
                 doubt[t][k] = __builtin_amdgcn_ballot_w64(lo < thr[k]);
             }
         }
@@ -2315,37 +2232,11 @@ __global__ __launch_bounds__(256) void k_warp_fast(const uint8_t *__restrict__ i
         const int y = y_first + t;
         if (y >= y_store_end) break;  // wave-uniform
         if (kBlend) {
-            const int ci = y - off_y;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int cj = j0 + k - off_x;
-                const bool in = ci >= 0 && ci < center_h && cj >= 0 && cj < center_w;
-                const unsigned co = in ? ((unsigned)ci * (unsigned)center_w + (unsigned)cj) * 3u : 0u;
-                const unsigned cc = co < clast ? co : clast;
-                unsigned int c;
-                __builtin_memcpy(&c, center + cc, 4);
-                c = in ? ((c >> (8 * (co - cc))) & 0x00ffffffu) : 0u;
-                const unsigned w = px[t][k];
-                const unsigned avg = (w & c) + (((w ^ c) & 0x00fefefeu) >> 1);
-                px[t][k] = (w != 0u && c != 0u) ? avg : (w | c);
-            }
+            for (int k = 0; k < 4; ++k)
+                px[t][k] = blend_center(px[t][k], center, y - off_y, j0 + k - off_x, center_h, center_w, clast);
         }
-        uint8_t *o = out + ((size_t)(y - row_begin) * (size_t)final_w) * 3 + (unsigned)j0 * 3u;
-        if (npx == 4) {
-            // 4 x 24 bits -> 3 dwords (v_perm_b32 picks bytes 0-3 from its second operand, 4-7 from its first), stored
-            // NON-TEMPORAL: the canvas is written once and never read back by this kernel - the bytes stream past the L2
-            // instead of waiting in it, dirty, for the write-back at the end of the kernel (tools/k3_policy.hip: of the
-            // eight sc0 / sc1 / nt combinations on the stores and the eight on the gathers, nt stores + plain loads is the
-            // fastest; K3 at C3 16.0 -> 15.1 us warm, 19.3 -> 17.5 us cold)
-            store12_stream(o, px[t][0] | (px[t][1] << 24), __builtin_amdgcn_perm(px[t][2], px[t][1], 0x05040201u),
-                           __builtin_amdgcn_perm(px[t][3], px[t][2], 0x06050402u));
-        } else {
-            for (int k = 0; k < npx; ++k) {
-                o[3 * k] = (uint8_t)(px[t][k] & 0xff);
-                o[3 * k + 1] = (uint8_t)((px[t][k] >> 8) & 0xff);
-                o[3 * k + 2] = (uint8_t)((px[t][k] >> 16) & 0xff);
-            }
-        }
+        APAP_STORE_PX4(out + ((size_t)(y - row_begin) * (size_t)final_w) * 3 + (unsigned)j0 * 3u, px[t], npx);
     }
 }
 
@@ -2849,15 +2740,11 @@ int warp_impl(apap_ctx *ctx, const WarpArgs &a) {
         const int rows = warp_kernel >= 8 ? 8 : warp_kernel >= 4 ? warp_kernel : 2;       // instantiated for 2, 4, 5, 6, 8
         constexpr int kWpb = 256 / 64;      // waves (= strips) per block
         const dim3 grid((unsigned)((final_w + 255) / 256), (unsigned)((row_count + kWpb * rows - 1) / (kWpb * rows)), batch);
-#define APAP_LAUNCH_FAST(R)                                                                                          \
-    if (d_center)                                                                                                    \
-        hipLaunchKernelGGL((k_warp_fast<true, R>), grid, dim3(256), 0, s, d_img, img_h, img_w, hinv_pad, mesh_rows, mesh_cols,  \
-                           lut, ww.frec, ww.fcol, ww.frow, final_w, final_h, off_x, off_y, d_out, d_center,           \
-                           center_h, center_w, row_begin, row_count, st, a.status);                                  \
-    else                                                                                                             \
-        hipLaunchKernelGGL((k_warp_fast<false, R>), grid, dim3(256), 0, s, d_img, img_h, img_w, hinv_pad, mesh_rows, mesh_cols, \
-                           lut, ww.frec, ww.fcol, ww.frow, final_w, final_h, off_x, off_y, d_out,                     \
-                           (const uint8_t *)nullptr, 0, 0, row_begin, row_count, st, a.status)
+        // one argument list for both blends: the kernels without the blend never read the centre's arguments
+#define APAP_LAUNCH_FAST(R)                                                                                            \
+    hipLaunchKernelGGL((d_center ? k_warp_fast<true, R> : k_warp_fast<false, R>), grid, dim3(256), 0, s, d_img, img_h, img_w, \
+                       hinv_pad, mesh_rows, mesh_cols, lut, ww.frec, ww.fcol, ww.frow, final_w, final_h, off_x, off_y, d_out, \
+                       d_center, center_h, center_w, row_begin, row_count, st, a.status)
         if (rows == 4) { APAP_LAUNCH_FAST(4); }
         else if (rows == 5) { APAP_LAUNCH_FAST(5); }
         else if (rows == 6) { APAP_LAUNCH_FAST(6); }
@@ -2868,15 +2755,10 @@ int warp_impl(apap_ctx *ctx, const WarpArgs &a) {
         ProfScope prof(ctx, APAP_PROF_WARP, s);
         const int rows = warp_kernel >= 8 ? 8 : warp_kernel >= 4 ? 4 : 2;  // rows per wave: instantiated for 2, 4, 8
         const dim3 grid((unsigned)((final_w + 255) / 256), (unsigned)((row_count + 4 * rows - 1) / (4 * rows)), batch);
-#define APAP_LAUNCH_ROWS(R)                                                                                          \
-    if (d_center)                                                                                                    \
-        hipLaunchKernelGGL((k_warp_rows<true, R>), grid, dim3(256), 0, s, d_img, img_h, img_w, hinv_pad, mesh_cols,  \
-                           lut, final_w, final_h, off_x, off_y, d_out, d_center, center_h, center_w, row_begin,      \
-                           row_count, st, mesh_rows, a.status);                                                      \
-    else                                                                                                             \
-        hipLaunchKernelGGL((k_warp_rows<false, R>), grid, dim3(256), 0, s, d_img, img_h, img_w, hinv_pad, mesh_cols, \
-                           lut, final_w, final_h, off_x, off_y, d_out, (const uint8_t *)nullptr, 0, 0, row_begin,    \
-                           row_count, st, mesh_rows, a.status)
+#define APAP_LAUNCH_ROWS(R)                                                                                            \
+    hipLaunchKernelGGL((d_center ? k_warp_rows<true, R> : k_warp_rows<false, R>), grid, dim3(256), 0, s, d_img, img_h, img_w, \
+                       hinv_pad, mesh_cols, lut, final_w, final_h, off_x, off_y, d_out, d_center, center_h, center_w,      \
+                       row_begin, row_count, st, mesh_rows, a.status)
         if (rows == 4) { APAP_LAUNCH_ROWS(4); }
         else if (rows == 8) { APAP_LAUNCH_ROWS(8); }
         else { APAP_LAUNCH_ROWS(2); }

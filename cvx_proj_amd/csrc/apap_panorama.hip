@@ -16,8 +16,8 @@
 // of 256 pixels, a block kWaves strips below each other.  The layer descriptors travel BY VALUE in the kernel argument
 // (1 KB; no upload); the loop over layers is wave-uniform, a strip tests a layer's rectangle with scalar compares and
 // skips the layers it does not touch.  Per layer the lane looks up its four cell columns, the wave its rows' cell rows, and
-// the coordinates come from k_warp_rows' arithmetic (pixel_h, the float64 chain, the strict bounds test, the truncation):
-// the same device functions (apap_warp_dev.h), the same bits.  A layer's state (cell matrices, offsets, gathered pixels)
+// the coordinates come from k_warp_rows' arithmetic (strip_cell_row, strip_source: the float64 chain, the strict bounds test, the
+// truncation): the same device functions (apap_warp_dev.h), the same bits.  A layer's state (cell matrices, offsets, gathered pixels)
 // is dead before the next layer starts: the registers do not grow with the layer count.
 //   mean : per pixel the channel sums and the number of present values (any byte non-zero) in two registers
 //          (ch0 | ch2 << 16, ch1 | count << 16; at most 17 x 255 per sum); the quotient is one multiply and shift with
@@ -207,19 +207,8 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
             int r = rr[0];
 #pragma unroll
             for (int t = 1; t < kRows; ++t) r = (t == first) ? rr[t] : r;
-            const int base = r * mesh_cols;
-            const Hinv9 ha = load_hinv(hinv_pad, (unsigned)(base + col[0]));
-            const Hinv9 hb = load_hinv(hinv_pad, (unsigned)(base + col[3]));
             PixelH q[4];
-            q[0] = pixel_h(ha, xs[0]);
-            q[3] = pixel_h(hb, xs[3]);
-#pragma unroll
-            for (int k = 1; k < 3; ++k) {
-                const bool is_a = col[k] == col[0];
-                Hinv9 hk = select_hinv(is_a, ha, hb);
-                if (!is_a && col[k] != col[3]) hk = load_hinv(hinv_pad, (unsigned)(base + col[k]));  // a third cell
-                q[k] = pixel_h(hk, xs[k]);
-            }
+            strip_cell_row(hinv_pad, r * mesh_cols, col, xs, q);
 #pragma unroll
             for (int t = 0; t < kRows; ++t) {
                 if (!((todo >> t) & 1u) || rr[t] != r) continue;
@@ -227,18 +216,9 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
                 const double yd = (double)(y_first + t - A.OY);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    // k_warp_rows' sequence, operation for operation
-                    const double t0 = fma(q[k].h1, yd, q[k].p0) + q[k].h2;
-                    const double t1 = fma(q[k].h4, yd, q[k].p1) + q[k].h5;
-                    const double t2 = fma(q[k].h7, yd, q[k].p2) + q[k].h8;
-                    double rc = __builtin_amdgcn_rcp(t2);
-                    rc = fma(fma(-t2, rc, 1.0), rc, rc);
-                    const double q0 = t0 * rc, q1 = t1 * rc;
-                    const double tx = fma(fma(-t2, q0, t0), rc, q0);
-                    const double ty = fma(fma(-t2, q1, t1), rc, q1);
-                    const int ix = (int)tx, iy = (int)ty;
-                    const bool ok = (tx > 0.0) & (ty > 0.0) & (ix < img_w) & (iy < img_h) & (((want >> (4 * t + k)) & 1u) != 0u);
-                    off[t][k] = ok ? (__umul24((unsigned)iy, (unsigned)img_w) + (unsigned)ix) * 3u : 0xffffffffu;
+                    int ix, iy;
+                    const bool ok = strip_source(q[k], yd, img_w, img_h, ix, iy) & (((want >> (4 * t + k)) & 1u) != 0u);
+                    off[t][k] = strip_offset(ok, ix, iy, img_w);
                     if (kMode == APAP_PANORAMA_RAMP) wgt[t][k] = (unsigned)ramp_weight(ix, iy, img_w, img_h, ramp);  // used where ok
                 }
             }
@@ -290,17 +270,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
                 p[k] = a0[t][k];
             }
         }
-        uint8_t *o = A.out + ((size_t)y * (size_t)A.W + (size_t)j0) * 3u;
-        if (npx == 4) {
-            store12_stream(o, p[0] | (p[1] << 24), __builtin_amdgcn_perm(p[2], p[1], 0x05040201u),
-                           __builtin_amdgcn_perm(p[3], p[2], 0x06050402u));
-        } else {
-            for (int k = 0; k < npx; ++k) {
-                o[3 * k] = (uint8_t)(p[k] & 0xff);
-                o[3 * k + 1] = (uint8_t)((p[k] >> 8) & 0xff);
-                o[3 * k + 2] = (uint8_t)((p[k] >> 16) & 0xff);
-            }
-        }
+        APAP_STORE_PX4(A.out + ((size_t)y * (size_t)A.W + (size_t)j0) * 3u, p, npx);
     }
 }
 

@@ -1,6 +1,18 @@
-// The device functions with which K3 turns a canvas pixel into a source pixel, shared by apap_kernels.hip (k_warp,
-// k_warp_rows, k_warp_fast) and apap_panorama.hip (k_panorama): one definition, hence the same bits wherever a pixel of
-// local_warp is computed.  Needs -ffp-contract=off like every kernel source: each fused multiply-add is written fma().
+// The per-pixel steps of the warp kernels, each defined ONCE: the same bits wherever a pixel of local_warp is computed, and one
+// place to change them.  Needs -ffp-contract=off like every kernel source: each fused multiply-add is written fma().
+//   matrices      load_hinv, select_hinv; target_from / target_of: the exact coordinate with TWO Newton steps, used per pixel by
+//                 k_warp, k_warp_coords and k_warp_fast's exact_offset (apap_kernels.hip)
+//   strips        pixel_h, strip_cell_row, strip_source, strip_offset: a cell row's matrices for a lane's four pixels and the
+//                 exact coordinate with ONE Newton step, used by k_warp_rows and k_panorama (strip_offset also by k_warp_fast)
+//   gather        gather_px: one source pixel from a byte offset or the outside marker (k_warp_rows, k_warp_fast, k_panorama)
+//   stitch        blend_center: centre paste + uniform_blend of one pixel (k_warp, k_warp_rows, k_warp_fast)
+//   store         store12_stream, APAP_STORE_PX4: four pixels as one 12-byte non-temporal store, or a partial group byte by byte
+//                 (every kernel above and k_image_warp, apap_image_warp.hip)
+// The two exact sequences stay apart; each is pinned by its own tests.  Their three sums are the same bits: fma(h, 1.0, s) is
+// the correctly rounded h + s, which is what `s + h` is.  Their quotients are NOT shown equal from the arithmetic: with one
+// Newton step the quotient's error before its final rounding is ~2^-92, with two it is smaller still, and the quotient of two
+// doubles can lie closer than that to the midpoint of two neighbouring doubles, where the two forms may round apart.  Either
+// form gives the oracle's coordinate wherever the tests compare them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,13 +22,40 @@
 
 namespace {
 
-// 12 bytes to ANY byte address with the non-temporal hint (global_store_dwordx3 ... nt)
+// 12 bytes to ANY byte address with the non-temporal hint (global_store_dwordx3 ... nt): a canvas is written once and never
+// read back by the kernel that writes it - the bytes stream past the L2 instead of waiting in it, dirty, for the write-back at
+// the end of the kernel (tools/k3_policy.hip: of the eight sc0 / sc1 / nt combinations on the stores and the eight on the
+// gathers, nt stores + plain loads is the fastest; K3 at C3 16.0 -> 15.1 us warm, 19.3 -> 17.5 us cold)
 __device__ __forceinline__ void store12_stream(uint8_t *p, unsigned a, unsigned b, unsigned c) {
     typedef unsigned Dwords3 __attribute__((ext_vector_type(3)));
     typedef Dwords3 Dwords3AnyByte __attribute__((aligned(1)));
     const Dwords3 v = {a, b, c};
     __builtin_nontemporal_store(v, reinterpret_cast<Dwords3AnyByte *>(p));
 }
+
+// The first `npx` (1 .. 4) of a lane's four 24-bit pixels p[0 .. 3] to `o`.  A whole group: 4 x 24 bits -> 3 dwords with one
+// shift-or and two byte permutes (v_perm_b32 picks bytes 0-3 from its second operand, 4-7 from its first); groups start at
+// any byte: an unaligned, non-temporal 12-byte store.  A partial group (the end of a row or of the canvas) byte by byte, never
+// past it.  A macro, not a function: as a function, even a forced-inline one, hipcc optimises the byte loop on its own before it
+// meets the strip's pixel array, and the strip kernels come out with another tail (80-130 instructions more per strip row, or
+// with a loop pragma against that, the 8-row k_warp_fast with its gathers in another order: 2 % slower at 32 C5 pairs per
+// launch, profiles/warp_shared_steps.txt).  Expanded in the kernel the strip kernels compile to the instructions they had
+// with the text written out in each.
+#define APAP_STORE_PX4(o_, p_, npx_)                                                                                     \
+    do {                                                                                                                 \
+        uint8_t *const apap_o = (o_);                                                                                    \
+        const int apap_n = (npx_);                                                                                       \
+        if (apap_n == 4) {                                                                                               \
+            store12_stream(apap_o, (p_)[0] | ((p_)[1] << 24), __builtin_amdgcn_perm((p_)[2], (p_)[1], 0x05040201u),      \
+                           __builtin_amdgcn_perm((p_)[3], (p_)[2], 0x06050402u));                                        \
+        } else {                                                                                                         \
+            for (int apap_k = 0; apap_k < apap_n; ++apap_k) {                                                            \
+                apap_o[3 * apap_k] = (uint8_t)((p_)[apap_k] & 0xff);                                                     \
+                apap_o[3 * apap_k + 1] = (uint8_t)(((p_)[apap_k] >> 8) & 0xff);                                          \
+                apap_o[3 * apap_k + 2] = (uint8_t)(((p_)[apap_k] >> 16) & 0xff);                                         \
+            }                                                                                                            \
+        }                                                                                                                \
+    } while (0)
 
 // target coordinate of canvas pixel (i, j) through the (already inverted) cell matrix:
 // float64 FMA chain in the order h0*x + h1*y + h2, then the two divisions by the third
@@ -77,6 +116,52 @@ __device__ __forceinline__ PixelH pixel_h(const Hinv9 &h, double x) {
     return q;
 }
 
+// The matrices of one cell row (its first cell is `base`) for a lane's four pixels, whose cell columns are col[] and whose
+// x are xs[]: the cells of the first and the last pixel; the two in between almost always sit in one of those (cell columns
+// are monotone along a row and cells are wider than 2 px), otherwise a third load.
+__device__ __forceinline__ void strip_cell_row(const double *__restrict__ hinv_pad, int base, const int (&col)[4],
+                                               const double (&xs)[4], PixelH (&q)[4]) {
+    const Hinv9 ha = load_hinv(hinv_pad, (unsigned)(base + col[0]));
+    const Hinv9 hb = load_hinv(hinv_pad, (unsigned)(base + col[3]));
+    q[0] = pixel_h(ha, xs[0]);
+    q[3] = pixel_h(hb, xs[3]);
+#pragma unroll
+    for (int k = 1; k < 3; ++k) {
+        const bool is_a = col[k] == col[0];
+        Hinv9 hk = select_hinv(is_a, ha, hb);
+        if (!is_a && col[k] != col[3]) hk = load_hinv(hinv_pad, (unsigned)(base + col[k]));  // a third cell
+        q[k] = pixel_h(hk, xs[k]);
+    }
+}
+
+// The exact source pixel (ix, iy) of a canvas pixel whose y relative to the centre is yd; false: outside the source (ix, iy
+// are then whatever the conversions gave).
+__device__ __forceinline__ bool strip_source(const PixelH &q, double yd, int img_w, int img_h, int &ix, int &iy) {
+    // (h0 x + h1 y) + h2 and so on: the order of the reference's matrix-vector product
+    const double t0 = fma(q.h1, yd, q.p0) + q.h2;
+    const double t1 = fma(q.h4, yd, q.p1) + q.h5;
+    const double t2 = fma(q.h7, yd, q.p2) + q.h8;
+    // shared reciprocal (one Newton step: ~2^-46) and a residual correction per
+    // quotient: the quotient's error before its final rounding is ~2^-92
+    double rc = __builtin_amdgcn_rcp(t2);
+    rc = fma(fma(-t2, rc, 1.0), rc, rc);
+    const double q0 = t0 * rc, q1 = t1 * rc;
+    const double tx = fma(fma(-t2, q0, t0), rc, q0);
+    const double ty = fma(fma(-t2, q1, t1), rc, q1);
+    // strict 0 < t < size, then truncation (apap.py:214-215).  For t > 0 the upper
+    // test is the same on the truncated integer (the conversion saturates, NaN
+    // fails t > 0).
+    ix = (int)tx;
+    iy = (int)ty;
+    return (tx > 0.0) & (ty > 0.0) & (ix < img_w) & (iy < img_h);  // no short-circuit branches
+}
+
+// The byte offset of source pixel (ix, iy), or the outside marker: a pixel outside the source is marked by the sign bit (the
+// launcher sends sources of 2 GiB or more to the flat-order kernel)
+__device__ __forceinline__ unsigned strip_offset(bool ok, int ix, int iy, int img_w) {
+    return ok ? (__umul24((unsigned)iy, (unsigned)img_w) + (unsigned)ix) * 3u : 0xffffffffu;
+}
+
 // the 3 bytes at byte offset `o` of the source as a 24-bit value; 0 for the "outside" marker 0xffffffff.
 // Reads the dword at the pixel's first byte; for the image's very last pixel the dword one byte earlier,
 // shifted (v_alignbyte_b32), so that no byte beyond the image is touched.
@@ -87,6 +172,24 @@ __device__ __forceinline__ unsigned gather_px(const uint8_t *__restrict__ img, u
     v = __builtin_amdgcn_alignbyte(0u, v, o - oc);
     // v & 0xffffff & ~sign(o): v_bfe_i32 + v_bitop3_b32 (truth table a & b & ~c = 0x40)
     return (unsigned)__builtin_amdgcn_bitop3_b32((int)v, 0x00ffffff, __builtin_amdgcn_sbfe((int)o, 31u, 1u), 0x40);
+}
+
+// The stitch of one canvas pixel: paste the centre picture's pixel (ci, cj) - nothing outside the picture - and uniform_blend
+// (apap_utils.py:75-88) it with the warped pixel `w`.  clast: bytes of the centre - 4; the centre's very last pixel is read
+// one byte earlier and shifted, as in gather_px.
+__device__ __forceinline__ unsigned blend_center(unsigned w, const uint8_t *__restrict__ center, int ci, int cj, int center_h,
+                                                 int center_w, unsigned clast) {
+    const bool in = ci >= 0 && ci < center_h && cj >= 0 && cj < center_w;
+    const unsigned co = in ? ((unsigned)ci * (unsigned)center_w + (unsigned)cj) * 3u : 0u;
+    const unsigned cc = co < clast ? co : clast;
+    unsigned int c;
+    __builtin_memcpy(&c, center + cc, 4);
+    c = in ? ((c >> (8 * (co - cc))) & 0x00ffffffu) : 0u;
+    // uniform_blend: a pixel is "present" when its channel mean is > 0, i.e. any
+    // channel is non-zero; both present -> floor((a + b) / 2) per channel (float64
+    // sum * 0.5, astype(uint8)), otherwise a + b with one of them 0
+    const unsigned avg = (w & c) + (((w ^ c) & 0x00fefefeu) >> 1);
+    return (w != 0u && c != 0u) ? avg : (w | c);
 }
 
 }  // namespace

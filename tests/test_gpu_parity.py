@@ -851,14 +851,54 @@ def test_batched_solve_equals_separate_solves(native):
         assert torch.equal(H2[k], Hk), k
 
 
+_NARROW = []
+
+
+def narrow_cases():
+    """Canvases 2, 5, 6 and 7 wide and 9 high under a 2 x 2 mesh: the last (for width 2 the only) group of a row holds 2, 1, 2
+    and 3 pixels, stored byte by byte, and the last strip is partial for strips of 2, 4, 5, 6 and 8 rows.  Each cell has its own
+    scale (a power of two) and translation (multiples of 1/8; no source coordinate is an integer), so the
+    float32 inverses are exact in any arithmetic and part of the canvas falls outside the 6 x 5 source.  The canvas's last pixel
+    samples the source's last pixel (the gather reads one byte earlier and shifts), and the centre picture ends on the
+    canvas's last pixel (the same guard for the centre).  Built once; the references are the oracle's."""
+    if _NARROW:
+        return _NARROW
+    ih, iw, fh, oy = 5, 6, 9, 4
+    for fw in (2, 5, 6, 7):
+        rng = np.random.default_rng(7000 + fw)
+        ox = fw // 2
+        img = rng.integers(1, 256, (ih, iw, 3), dtype=np.uint8)
+        center = rng.integers(0, 256, (fh - oy, fw - ox, 3), dtype=np.uint8)
+        center[rng.integers(0, 2, center.shape[:2]) == 0] = 0         # black centre pixels: the blend's other branch
+        mesh = (np.array([0.0, (fw + 1) // 2, fw]), np.array([0.0, 4.0, fh]))
+        H = np.zeros((2, 2, 3, 3), np.float32)
+        for r in range(2):
+            for c in range(2):
+                s = float(2.0 ** rng.integers(-1, 2))
+                # the cell's first canvas pixel samples a random point of the source, the others may leave it
+                x0, y0 = (0.0 if c == 0 else mesh[0][1]) - ox, (0.0 if r == 0 else mesh[1][1]) - oy
+                a = x0 - s * (float(rng.integers(0, 2 * iw)) * 0.5 + 0.25)
+                b = y0 - s * (float(rng.integers(0, 2 * ih)) * 0.5 + 0.25)
+                if r == 1 and c == 1:       # canvas pixel (fw - 1, fh - 1) -> source (iw - 0.25, ih - 0.25)
+                    a, b = (fw - 1 - ox) - s * (iw - 0.25), (fh - 1 - oy) - s * (ih - 0.25)
+                H[r, c] = [[s, 0.0, a], [0.0, s, b], [0.0, 0.0, 1.0]]
+        hinv = O.invert_cells_f32(H)
+        assert np.array_equal(hinv[..., 0, 0] * H[..., 0, 0], np.ones((2, 2), np.float32))    # exact inverses
+        warped = O.local_warp_fast(img, hinv, mesh, (fw, fh), (ox, oy))
+        assert np.array_equal(warped[-1, -1], img[-1, -1]) and (warped == 0).all(axis=-1).any() and (warped != 0).any(axis=-1).sum() > fw
+        _NARROW.append(dict(img=img, center=center, H=H, mesh=mesh, final=(fw, fh, ox, oy), hinv=hinv, warped=warped,
+                            stitched=O.stitch(warped, center, (ox, oy))))
+    return _NARROW
+
+
 @pytest.mark.parametrize("rows_per_wave,fast", [(0, 1), (2, 1), (4, 1), (5, 1), (6, 1), (8, 1), (2, 0), (4, 0), (8, 0)])
 def test_other_warp_kernel_forms_still_match(native, golden, rows_per_wave, fast):
     """The flat-order kernel (0) is the fallback for sources the strip kernels do not take (a side of
     2^24 pixels, 2 GiB); strips of 2 and 8 rows are the other instantiations; APAP_OPT_WARP_FAST = 0 is the
     strip kernel that runs the float64 sequence for every pixel (the default decides from a float32 estimate
     and falls back to float64 near integer boundaries).  Context options select them: same canvases, byte
-    for byte, as the default and as the reference's - tiny cases, every warp edge case, the fused stitch
-    and a full C2 canvas."""
+    for byte, as the default and as the reference's - tiny cases, every warp edge case, the fused stitch,
+    canvases whose rows end in a partial group of every size, and a full C2 canvas."""
     import hashlib
     ctx = native.Context(warp_rows=rows_per_wave, warp_fast=fast)
     for name in TINY:
@@ -874,6 +914,14 @@ def test_other_warp_kernel_forms_still_match(native, golden, rows_per_wave, fast
         fw, fh, ox, oy = (int(v) for v in e[f"geo{k}"])
         out, _ = native.local_warp(e[f"img{k}"], e[f"H{k}"].copy(), e[f"mesh_w{k}"], e[f"mesh_h{k}"], fw, fh, ox, oy, ctx=ctx)
         assert np.array_equal(out, e[f"warped{k}"]), k
+    # partial groups of 1, 2 and 3 pixels and a canvas narrower than a group, plain and stitched (narrow_cases)
+    for n in narrow_cases():
+        fw, fh, ox, oy = n["final"]
+        out, hinv = native.local_warp(n["img"], n["H"].copy(), n["mesh"][0], n["mesh"][1], fw, fh, ox, oy, ctx=ctx)
+        assert np.array_equal(hinv, n["hinv"]), fw
+        assert np.array_equal(out, n["warped"]), fw
+        st, _ = native.local_stitch(n["img"], n["center"], n["H"].copy(), n["mesh"][0], n["mesh"][1], fw, fh, ox, oy, ctx=ctx)
+        assert np.array_equal(st, n["stitched"]), fw
     g = golden("c2_ref")
     p = config_pair("C2")
     w, _ = native.local_warp(p.img, g["H_ref"], p.mesh[0], p.mesh[1], p.final_w, p.final_h, p.off_x, p.off_y, ctx=ctx)

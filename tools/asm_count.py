@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
-"""Static instruction mix of kernels in cvx_proj_amd/csrc/apap_kernels.gfx950.s (`make -C cvx_proj_amd/csrc asm`).
-   tools/asm_count.py k_warp_fastILb0ELi4 k_warp_rowsILb0ELi4"""
+"""Static instruction mix of kernels in a device assembly file of `make -C cvx_proj_amd/csrc asm`: by default
+   cvx_proj_amd/csrc/apap_kernels.gfx950.s, or the .s file given as the first argument.
+   tools/asm_count.py k_warp_fastILb0ELi4 k_warp_rowsILb0ELi4
+   tools/asm_count.py cvx_proj_amd/csrc/apap_panorama.gfx950.s k_panoramaILi0"""
 import sys
 from collections import Counter
 import os
-lines = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cvx_proj_amd/csrc/apap_kernels.gfx950.s")).read().split("\n")
-
+args = sys.argv[1:]
+path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cvx_proj_amd/csrc/apap_kernels.gfx950.s")
+if args and args[0].endswith(".s"):
+    path = args.pop(0)
+lines = open(path).read().split("\n")
 
 def func(name):
     start = [i for i, l in enumerate(lines) if l.startswith("_ZN") and name in l.split(":")[0] and ": " in l][0]
@@ -20,7 +25,7 @@ def func(name):
     return out
 
 
-for name in sys.argv[1:]:
+for name in args:
     c = Counter(func(name))
     tot = sum(c.values())
     grp = lambda pre: sum(n for k, n in c.items() if k.startswith(pre))  # noqa: E731
