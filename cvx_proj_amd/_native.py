@@ -364,6 +364,44 @@ def _vptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _ip(a):      # int * of an int32 array
+    return a.ctypes.data_as(_i32p)
+
+
+def _dp(a):      # double * of a float64 array
+    return a.ctypes.data_as(_f64p)
+
+
+def _addrs(addresses):
+    """A C array of the listed addresses (``ndarray.ctypes.data``, ``Tensor.data_ptr()``): a ``T *const *`` argument."""
+    return (C.c_void_p * len(addresses))(*addresses)
+
+
+def _i32(values):      # a new contiguous int32 array
+    return np.array(values, dtype=np.int32)
+
+
+def _offsets(lengths, name, one, many, rows, max_count, max_rows):
+    """Counts -> int32 offsets (len + 1), checked as the library checks them: 1 .. ``max_count`` counts (``many``, say "pairs"),
+    each (``one``: "a pair") of 1 .. ``max_rows`` ``rows``, a power of two, and their sum within int32."""
+    lengths = [int(x) for x in lengths]
+    if not 1 <= len(lengths) <= max_count:
+        raise ValueError(f"{name}: {len(lengths)} {many} (1 .. {max_count})")
+    if any(not 1 <= x <= max_rows for x in lengths):
+        raise ValueError(f"{name}: {one} holds 1 .. 2^{max_rows.bit_length() - 1} {rows}; got {lengths}")
+    if sum(lengths) > np.iinfo(np.int32).max:
+        raise ValueError(f"{name}: {sum(lengths)} {rows} in all exceed the int32 offsets")
+    off = np.zeros(len(lengths) + 1, np.int32)
+    off[1:] = np.cumsum(lengths)
+    return off
+
+
+def _image_table(got):
+    """``(array, channels)`` per image -> the batch entry points' (addresses, heights, widths, channels)."""
+    return (_addrs([a.ctypes.data for a, _ in got]), _i32([a.shape[0] for a, _ in got]), _i32([a.shape[1] for a, _ in got]),
+            _i32([c for _, c in got]))
+
+
 # ------------------------------------------------------------------ host-only helpers
 def host_prepare(src, dst):
     """C restatement of the set-up in apap.py:132-140,165-166, in the dtype of each keypoint set.  Returns a dict: N1 N2 C1 C2
@@ -882,16 +920,7 @@ def as_descriptors(a, name="descriptors"):
 
 def match_offsets(lengths, name):
     """Row counts of the pairs -> int32 offsets (len + 1), checked as the library checks them."""
-    lengths = [int(x) for x in lengths]
-    if not 1 <= len(lengths) <= MATCH_MAX_PAIRS:
-        raise ValueError(f"{name}: {len(lengths)} pairs (1 .. {MATCH_MAX_PAIRS})")
-    if any(not 1 <= x <= MATCH_MAX_ROWS for x in lengths):
-        raise ValueError(f"{name}: a pair holds 1 .. 2^24 rows; got {lengths}")
-    if sum(lengths) > np.iinfo(np.int32).max:
-        raise ValueError(f"{name}: {sum(lengths)} rows in all exceed the int32 offsets")
-    off = np.zeros(len(lengths) + 1, np.int32)
-    off[1:] = np.cumsum(lengths)
-    return off
+    return _offsets(lengths, name, "a pair", "pairs", "rows", MATCH_MAX_PAIRS, MATCH_MAX_ROWS)
 
 
 def match_descriptors(q, t, second=True, device=-1, ctx=None):
@@ -979,16 +1008,7 @@ def as_sift_points(pts, name="pts"):
 
 def sift_offsets(lengths, name="lengths"):
     """Keypoint counts of the images -> int32 offsets (len + 1), checked as the library checks them."""
-    lengths = [int(x) for x in lengths]
-    if not 1 <= len(lengths) <= SIFT_MAX_IMAGES:
-        raise ValueError(f"{name}: {len(lengths)} images (1 .. {SIFT_MAX_IMAGES})")
-    if any(not 1 <= x <= SIFT_MAX_KEYPOINTS for x in lengths):
-        raise ValueError(f"{name}: an image holds 1 .. 2^24 keypoints; got {lengths}")
-    if sum(lengths) > np.iinfo(np.int32).max:
-        raise ValueError(f"{name}: {sum(lengths)} keypoints in all exceed the int32 offsets")
-    off = np.zeros(len(lengths) + 1, np.int32)
-    off[1:] = np.cumsum(lengths)
-    return off
+    return _offsets(lengths, name, "an image", "images", "keypoints", SIFT_MAX_IMAGES, SIFT_MAX_KEYPOINTS)
 
 
 def sift_describe_batch(imgs, pts, lengths, device=-1, ctx=None):
@@ -1004,12 +1024,10 @@ def sift_describe_batch(imgs, pts, lengths, device=-1, ctx=None):
     off = sift_offsets(lengths)
     if off[-1] != len(pts):
         raise ValueError(f"sift_describe_batch: the counts sum to {off[-1]} keypoints; got {len(pts)}")
-    ptrs = (C.c_void_p * len(got))(*[a.ctypes.data for a, _ in got])
-    hs, ws = np.array([a.shape[0] for a, _ in got], np.int32), np.array([a.shape[1] for a, _ in got], np.int32)
-    cs = np.array([c for _, c in got], np.int32)
+    ptrs, hs, ws, cs = _image_table(got)
     out = np.empty((len(pts), SIFT_DIM), np.float32)
-    check(lib().apap_sift_describe_batch(_h(ctx), ptrs, _ptr(hs, C.c_int), _ptr(ws, C.c_int), _ptr(cs, C.c_int), len(got),
-                                         _ptr(pts, C.c_float), _ptr(off, C.c_int), _ptr(out, C.c_float), device))
+    check(lib().apap_sift_describe_batch(_h(ctx), ptrs, _ip(hs), _ip(ws), _ip(cs), len(got), _ptr(pts, C.c_float), _ip(off),
+                                         _ptr(out, C.c_float), device))
     return out
 
 
@@ -1061,14 +1079,12 @@ def corner_detect_batch(imgs, max_corners, radius=5, quality_permille=10, device
         raise ValueError(f"corner_detect_batch: {len(got)} images (1 .. {CORNER_MAX_IMAGES})")
     max_corners, radius, quality_permille = corner_params(max_corners, radius, quality_permille, "corner_detect_batch")
     rows = min(max_corners, max(corner_bound(a.shape[0], a.shape[1], radius) for a, _ in got))
-    ptrs = (C.c_void_p * len(got))(*[a.ctypes.data for a, _ in got])
-    hs, ws = np.array([a.shape[0] for a, _ in got], np.int32), np.array([a.shape[1] for a, _ in got], np.int32)
-    cs = np.array([c for _, c in got], np.int32)
+    ptrs, hs, ws, cs = _image_table(got)
     pts = np.empty((len(got), rows, 2), np.float32)
     resp = np.empty((len(got), rows), np.int64)
     count = np.empty(len(got), np.int32)
-    check(lib().apap_corner_detect_batch(_h(ctx), ptrs, _ptr(hs, C.c_int), _ptr(ws, C.c_int), _ptr(cs, C.c_int), len(got), rows, radius,
-                                         quality_permille, _ptr(pts, C.c_float), _ptr(resp, C.c_longlong), _ptr(count, C.c_int), device))
+    check(lib().apap_corner_detect_batch(_h(ctx), ptrs, _ip(hs), _ip(ws), _ip(cs), len(got), rows, radius, quality_permille,
+                                         _ptr(pts, C.c_float), _ptr(resp, C.c_longlong), _ip(count), device))
     return [(pts[m, :count[m]].copy(), resp[m, :count[m]].copy()) for m in range(len(got))]
 
 
@@ -1146,18 +1162,17 @@ def image_warp_tables(shapes_base, shapes_src, Ms, canvases, offsets, directs, o
         raise ValueError(f"{who}: {n} problems (1 .. {IMAGE_WARP_MAX_PROBLEMS})")
     if not all(len(x) == n for x in (shapes_base, shapes_src, canvases, offsets, directs)):
         raise ValueError(f"{who}: the per-problem lists differ in length")
-    i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)      # noqa: E731
     M = np.ascontiguousarray(np.stack([np.asarray(m, np.float64).reshape(3, 3) for m in Ms]), dtype=np.float64)
-    cw, ch = i32([c[0] for c in canvases]), i32([c[1] for c in canvases])
+    cw, ch = _i32([c[0] for c in canvases]), _i32([c[1] for c in canvases])
     sizes = [int(h) * int(w) * 3 for w, h in canvases]
     if out_offsets is None:
         out_offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]])
     off = np.ascontiguousarray(out_offsets, dtype=np.int64)
     if off.shape != (n,):
         raise ValueError(f"{who}: {n} problems, out_offsets of shape {off.shape}")
-    return (n, i32([s[0] for s in shapes_base]), i32([s[1] for s in shapes_base]), i32([s[0] for s in shapes_src]),
-            i32([s[1] for s in shapes_src]), M, cw, ch, i32([o[0] for o in offsets]), i32([o[1] for o in offsets]),
-            i32([1 if d else 0 for d in directs]), off, sizes)
+    return (n, _i32([s[0] for s in shapes_base]), _i32([s[1] for s in shapes_base]), _i32([s[0] for s in shapes_src]),
+            _i32([s[1] for s in shapes_src]), M, cw, ch, _i32([o[0] for o in offsets]), _i32([o[1] for o in offsets]),
+            _i32([1 if d else 0 for d in directs]), off, sizes)
 
 
 def image_warp_batch(bases, srcs, Ms, canvases, offsets, directs, out=None, out_offsets=None, device=-1, ctx=None):
@@ -1179,10 +1194,9 @@ def image_warp_batch(bases, srcs, Ms, canvases, offsets, directs, out=None, out_
         out = np.empty(need, np.uint8)
     if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.ndim != 1 or not out.flags.c_contiguous or out.size < need:
         raise ValueError(f"image_warp_batch: out must be a flat contiguous uint8 array of at least {need} bytes")
-    vpp = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs])      # noqa: E731
-    ip = lambda a: _ptr(a, C.c_int)      # noqa: E731
-    check(lib().apap_image_warp_batch(_h(ctx), vpp(bases), ip(bh), ip(bw), vpp(srcs), ip(sh), ip(sw), _ptr(M, C.c_double), ip(cw), ip(ch),
-                                      ip(ox), ip(oy), ip(direct), n, _ptr(out, C.c_uint8), _ptr(off, C.c_longlong), device))
+    check(lib().apap_image_warp_batch(_h(ctx), _addrs([a.ctypes.data for a in bases]), _ip(bh), _ip(bw),
+                                      _addrs([a.ctypes.data for a in srcs]), _ip(sh), _ip(sw), _dp(M), _ip(cw), _ip(ch), _ip(ox), _ip(oy),
+                                      _ip(direct), n, _ptr(out, C.c_uint8), _ptr(off, C.c_longlong), device))
     return [out[int(o):int(o) + s].reshape(int(h), int(w), 3) for o, s, w, h in zip(off, sizes, cw, ch)]
 
 
@@ -1302,16 +1316,15 @@ def panorama(center, layers, blend="mean", device=-1, ctx=None, return_status=Fa
         grids.append(H)
         mws.append(np.ascontiguousarray(l.mesh[0], dtype=np.float64))
         mhs.append(np.ascontiguousarray(l.mesh[1], dtype=np.float64))
-    i32 = lambda v: np.array(v, dtype=np.int32)      # noqa: E731
-    ih, iw = i32([a.shape[0] for a in imgs]), i32([a.shape[1] for a in imgs])
-    mr, mc = i32([a.shape[0] for a in grids]), i32([a.shape[1] for a in grids])
-    nw, nh = i32([a.size for a in mws]), i32([a.size for a in mhs])
+    ih, iw = _i32([a.shape[0] for a in imgs]), _i32([a.shape[1] for a in imgs])
+    mr, mc = _i32([a.shape[0] for a in grids]), _i32([a.shape[1] for a in grids])
+    nw, nh = _i32([a.size for a in mws]), _i32([a.size for a in mhs])
     W, Hc, OX, OY = panorama_bounds(center.shape, fw, fh, ox, oy)
     out = np.empty((Hc, W, 3), np.uint8)
     status = np.zeros(n, np.int32)
-    ip, vpp = (lambda a: _ptr(a, C.c_int)), (lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs]))
-    code = entry(_h(ctx), _ptr(center, C.c_uint8), center.shape[0], center.shape[1], vpp(imgs), ip(ih), ip(iw), vpp(grids), ip(mr), ip(mc),
-                 vpp(mws), ip(nw), vpp(mhs), ip(nh), ip(fw), ip(fh), ip(ox), ip(oy), n, mode, _ptr(out, C.c_uint8), ip(status), device)
+    p = [_addrs([a.ctypes.data for a in arrs]) for arrs in (imgs, grids, mws, mhs)]
+    code = entry(_h(ctx), _ptr(center, C.c_uint8), center.shape[0], center.shape[1], p[0], _ip(ih), _ip(iw), p[1], _ip(mr), _ip(mc),
+                 p[2], _ip(nw), p[3], _ip(nh), _ip(fw), _ip(fh), _ip(ox), _ip(oy), n, mode, _ptr(out, C.c_uint8), _ip(status), device)
     if return_status and code in (ERR_SINGULAR, ERR_INDEX):
         return out, (W, Hc, OX, OY), status
     check(code)

@@ -84,7 +84,7 @@ struct Layout {
     size_t total = 0;
     Part take(size_t bytes) {
         const Part p{base, total, bytes};
-        total += (bytes + 255) / 256 * 256;
+        total += up256(bytes);
         return p;
     }
 };
@@ -175,6 +175,27 @@ std::vector<const uint8_t *> upload_images(HostCall &call, const std::vector<Par
     }
     return d_imgs;
 }
+
+// The distinct host pictures of a call, uploaded once each: problems and layers may share a picture (the reference's
+// baseline / result pair), told by its address and size.  Declared before the HostCall, like every host vector of a call.
+struct Pictures {
+    struct Pic { const uint8_t *host; size_t bytes; Part dev; };
+    std::vector<Pic> pics;   // in the order of their first add(): the order of their parts and uploads
+    std::map<std::pair<const uint8_t *, size_t>, int> seen;
+    // The index of the picture.  `shared` false: a picture of its own, whatever was added before or comes after.
+    int add(const uint8_t *host, size_t bytes, bool shared = true) {
+        const int next = (int)pics.size();
+        if (shared) {
+            const auto it = seen.emplace(std::make_pair(host, bytes), next);
+            if (!it.second) return it.first->second;
+        }
+        pics.push_back(Pic{host, bytes, Part{}});
+        return next;
+    }
+    void take(Layout &lay) { for (Pic &p : pics) p.dev = lay.take(p.bytes); }
+    void upload(HostCall &call) const { for (const Pic &p : pics) call.up(p.dev, p.host); }
+    const uint8_t *dev(int k) const { return pics[k].dev.as<const uint8_t>(); }
+};
 
 int status_to_code(int status, const char *who) {
     if (status & APAP_STATUS_SINGULAR) return apap::fail(APAP_ERR_SINGULAR, "%s: Singular matrix", who);
@@ -1190,20 +1211,12 @@ int apap_image_warp_batch(apap_ctx *ctx, const uint8_t *const *bases, const int 
     if (rc) return rc;
     for (int p = 0; p < n_problems; ++p)
         if (!bases[p] || !srcs[p]) return apap::fail(APAP_ERR_INVALID_ARG, "%s: problem %d: null pointer", who, p);
-    // the distinct pictures of the batch (problems may share them: the reference's baseline / result pair), uploaded once each
-    struct Pic { const uint8_t *host; size_t bytes; };
-    std::vector<Pic> pics;
+    Pictures pics;   // of the batch
     std::vector<int> base_pic((size_t)n_problems), src_pic((size_t)n_problems);
-    std::map<std::pair<const uint8_t *, size_t>, int> seen;
-    const auto pic_of = [&pics, &seen](const uint8_t *host, size_t bytes) {
-        const auto it = seen.emplace(std::make_pair(host, bytes), (int)pics.size());
-        if (it.second) pics.push_back(Pic{host, bytes});
-        return it.first->second;
-    };
     long long lo = out_offset[0], hi = 0;   // the device canvases start at the lowest offset
     for (int p = 0; p < n_problems; ++p) {
-        base_pic[p] = pic_of(bases[p], (size_t)base_h[p] * base_w[p] * 3);
-        src_pic[p] = pic_of(srcs[p], (size_t)src_h[p] * src_w[p] * 3);
+        base_pic[p] = pics.add(bases[p], (size_t)base_h[p] * base_w[p] * 3);
+        src_pic[p] = pics.add(srcs[p], (size_t)src_h[p] * src_w[p] * 3);
         lo = std::min(lo, out_offset[p]);
         hi = std::max(hi, out_offset[p] + (long long)canvas_h[p] * canvas_w[p] * 3);
     }
@@ -1212,17 +1225,16 @@ int apap_image_warp_batch(apap_ctx *ctx, const uint8_t *const *bases, const int 
     HostCall call(ctx);
     if ((rc = call.select(device))) return rc;
     Layout imgs = call.layout(S_IMG);
-    std::vector<Part> d_pic(pics.size(), Part{});
-    for (size_t k = 0; k < pics.size(); ++k) d_pic[k] = imgs.take(pics[k].bytes);
+    pics.take(imgs);
     call.alloc(imgs);
     const Part d_out = call.slot(S_OUT, (size_t)(hi - lo));
     const Part work = call.slot(S_WORK, apap_image_warp_workspace_bytes(n_problems));
-    for (size_t k = 0; k < pics.size(); ++k) call.up(d_pic[k], pics[k].host);
+    pics.upload(call);
     if ((rc = call.rc())) return rc;
     std::vector<const uint8_t *> d_bases((size_t)n_problems), d_srcs((size_t)n_problems);
     for (int p = 0; p < n_problems; ++p) {
-        d_bases[p] = d_pic[base_pic[p]].as<const uint8_t>();
-        d_srcs[p] = d_pic[src_pic[p]].as<const uint8_t>();
+        d_bases[p] = pics.dev(base_pic[p]);
+        d_srcs[p] = pics.dev(src_pic[p]);
     }
     rc = apap_image_warp_batch_device(ctx, d_bases.data(), base_h, base_w, d_srcs.data(), src_h, src_w, M, canvas_w, canvas_h, off_x, off_y,
                                       direct_blend, n_problems, d_out.as<uint8_t>(), rel.data(), work.as<void>(), work.bytes, nullptr,
@@ -1254,23 +1266,17 @@ static int panorama_host(apap_ctx *ctx, const uint8_t *center, int center_h, int
     if (!center || !imgs || !Hfwd || !mesh_w || !mesh_h || !out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
     for (int k = 0; k < n_layers; ++k)
         if (!imgs[k] || !Hfwd[k] || !mesh_w[k] || !mesh_h[k]) return apap::fail(APAP_ERR_INVALID_ARG, "%s: layer %d: null pointer", who, k);
-    // the distinct pictures (layers may share one), uploaded once each; picture 0 is the centre
-    struct Pic { const uint8_t *host; size_t bytes; };
-    std::vector<Pic> pics{Pic{center, (size_t)center_h * center_w * 3}};
+    // picture 0 is the centre, on its own: only the layers share pictures, among themselves
+    Pictures pics;
+    pics.add(center, (size_t)center_h * center_w * 3, false);
     std::vector<int> pic_of((size_t)n_layers);
-    std::map<std::pair<const uint8_t *, size_t>, int> seen;
-    for (int k = 0; k < n_layers; ++k) {
-        const size_t bytes = (size_t)img_h[k] * img_w[k] * 3;
-        const auto it = seen.emplace(std::make_pair(imgs[k], bytes), (int)pics.size());
-        if (it.second) pics.push_back(Pic{imgs[k], bytes});
-        pic_of[k] = it.first->second;
-    }
+    for (int k = 0; k < n_layers; ++k) pic_of[k] = pics.add(imgs[k], (size_t)img_h[k] * img_w[k] * 3);
     std::vector<int> st((size_t)n_layers, 0);       // before the HostCall: a download writes it
     HostCall call(ctx);
     if ((rc = call.select(device))) return rc;
     Layout l_img = call.layout(S_IMG), l_h = call.layout(S_H), l_mw = call.layout(S_MESHW), l_mh = call.layout(S_MESHH);
-    std::vector<Part> d_pic(pics.size(), Part{}), d_h((size_t)n_layers, Part{}), d_mw((size_t)n_layers, Part{}), d_mh((size_t)n_layers, Part{});
-    for (size_t k = 0; k < pics.size(); ++k) d_pic[k] = l_img.take(pics[k].bytes);
+    std::vector<Part> d_h((size_t)n_layers, Part{}), d_mw((size_t)n_layers, Part{}), d_mh((size_t)n_layers, Part{});
+    pics.take(l_img);
     for (int k = 0; k < n_layers; ++k) {
         d_h[k] = l_h.take((size_t)mesh_rows[k] * mesh_cols[k] * 9 * sizeof(float));
         d_mw[k] = l_mw.take((size_t)n_w[k] * sizeof(double));
@@ -1280,7 +1286,7 @@ static int panorama_host(apap_ctx *ctx, const uint8_t *center, int center_h, int
     const Part d_out = call.slot(S_OUT, (size_t)b[0] * b[1] * 3);
     const Part d_status = call.slot(S_STATUS, (size_t)n_layers * sizeof(int));
     const Part work = call.slot(S_WORK, apap_panorama_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h, n_layers));
-    for (size_t k = 0; k < pics.size(); ++k) call.up(d_pic[k], pics[k].host);
+    pics.upload(call);
     for (int k = 0; k < n_layers; ++k) {
         call.up(d_h[k], Hfwd[k]);
         call.up(d_mw[k], mesh_w[k]);
@@ -1292,12 +1298,12 @@ static int panorama_host(apap_ctx *ctx, const uint8_t *center, int center_h, int
     std::vector<const float *> p_h((size_t)n_layers);
     std::vector<const double *> p_mw((size_t)n_layers), p_mh((size_t)n_layers);
     for (int k = 0; k < n_layers; ++k) {
-        p_img[k] = d_pic[pic_of[k]].as<const uint8_t>();
+        p_img[k] = pics.dev(pic_of[k]);
         p_h[k] = d_h[k].as<const float>();
         p_mw[k] = d_mw[k].as<const double>();
         p_mh[k] = d_mh[k].as<const double>();
     }
-    rc = apap::panorama_device(ctx, d_pic[0].as<const uint8_t>(), center_h, center_w, p_img.data(), img_h, img_w, p_h.data(), mesh_rows,
+    rc = apap::panorama_device(ctx, pics.dev(0), center_h, center_w, p_img.data(), img_h, img_w, p_h.data(), mesh_rows,
                                mesh_cols, p_mw.data(), n_w, p_mh.data(), n_h, final_w, final_h, off_x, off_y, n_layers, mode, ramp,
                                d_out.as<uint8_t>(), work.as<void>(), work.bytes, d_status.as<int>(), call.stream(), who);
     if (rc) return rc;

@@ -1,6 +1,6 @@
 // Harris corners in exact integer arithmetic: the keypoints that apap_sift_describe takes, from the image alone.  The contract
 // is in include/apap_hip.h and DESIGN.md "Corner detection", and, in numpy int64, in tests/corner_spec.py:
-//   grey   uint8 as it is, or BGR -> (3735 B + 19235 G + 9798 R + 16384) >> 15 (the descriptor's formula)
+//   grey   uint8 as it is, or BGR -> (3735 B + 19235 G + 9798 R + 16384) >> 15: apap::grey_at, which the descriptor reads too
 //   Ix, Iy 3 x 3 Sobel, reflect-101 on the grey image's indices: -1020 .. 1020
 //   a b c  unnormalised 3 x 3 box sums of Ix^2, Ix Iy, Iy^2, reflect-101 on the product images' indices: < 2^24
 //   R      25 (a c - b^2) - (a + c)^2 in int64: 25 times Harris's det - 0.04 tr^2
@@ -30,18 +30,19 @@
 #include <cstdint>
 #include <vector>
 
+#include "apap_image_dev.h"
 #include "apap_internal.h"
 
 namespace {
+
+using apap::grey_at, apap::reflect, apap::up256;
 
 inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
 
 constexpr int kTW = APAP_CORNER_TILE_W, kTH = APAP_CORNER_TILE_H;
 constexpr int kThreads = 256;
-constexpr int kMinSide = 7, kMaxSide = 32768;
 constexpr int kMaxRadius = APAP_CORNER_MAX_RADIUS;
 constexpr int kSmallRadius = 5;          // the kernel instance with the smaller LDS footprint serves radius <= 5
-constexpr int kMaxImages = 65535;
 constexpr int kSelThreads = 1024;
 constexpr int kLdsSort = 2048;           // candidates sorted in LDS (32 KB)
 static_assert(kTW == 64 && kTH == 32 && kMaxRadius == 16, "the tile kernel's LDS budget is for these");
@@ -77,14 +78,6 @@ inline size_t pow2ceil(size_t n) {
     while (p < n) p <<= 1;
     return p;
 }
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-
-// reflect-101, once, then clamped: positions more than one pixel outside the image are staged but never used
-__device__ __forceinline__ int reflect(int i, int n) {
-    if (i < 0) i = -i;
-    if (i > n - 1) i = 2 * (n - 1) - i;
-    return min(max(i, 0), n - 1);
-}
 
 template <int RMAX>
 __global__ __launch_bounds__(kThreads) void k_corner_tile(const CornerImage *__restrict__ tab, CornerCount *__restrict__ cnt, int r) {
@@ -119,10 +112,7 @@ __global__ __launch_bounds__(kThreads) void k_corner_tile(const CornerImage *__r
     for (int at = tid; at < GW * GH; at += kThreads) {
         const int ly = at / GW, lx = at - ly * GW;
         const int y = reflect(y0 - r - 2 + ly, I.h), x = reflect(x0 - r - 2 + lx, I.w);
-        const uint8_t *p = I.img + ((size_t)y * I.w + x) * I.c;
-        int g = p[0];
-        if (I.c == 3) g = (3735 * g + 19235 * (int)p[1] + 9798 * (int)p[2] + 16384) >> 15;
-        s_g[at] = (uint8_t)g;
+        s_g[at] = (uint8_t)grey_at(I.img, y, x, I.w, I.c);
     }
     __syncthreads();
 
@@ -342,12 +332,11 @@ Layout layout(const int *heights, const int *widths, int n_images, int radius) {
 
 int shapes_check(const int *heights, const int *widths, int n_images, int radius, const char *who) {
     if (!heights || !widths) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null heights / widths", who);
-    if (n_images < 1 || n_images > kMaxImages) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n_images = %d (1 .. %d)", who, n_images, kMaxImages);
+    if (n_images < 1 || n_images > apap::kMaxImages)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: n_images = %d (1 .. %d)", who, n_images, apap::kMaxImages);
     if (radius < 1 || radius > kMaxRadius) return apap::fail(APAP_ERR_INVALID_ARG, "%s: radius = %d (1 .. %d)", who, radius, kMaxRadius);
     for (int m = 0; m < n_images; ++m)
-        if (heights[m] < kMinSide || heights[m] > kMaxSide || widths[m] < kMinSide || widths[m] > kMaxSide)
-            return apap::fail(APAP_ERR_INVALID_ARG, "%s: image %d is %d x %d (sides %d .. %d)", who, m, heights[m], widths[m], kMinSide,
-                              kMaxSide);
+        if (int rc = apap::image_sides_check(m, heights[m], widths[m], who)) return rc;
     return APAP_OK;
 }
 
@@ -362,8 +351,7 @@ int corner_check(const int *heights, const int *widths, const int *channels, int
     int rc = shapes_check(heights, widths, n_images, radius, who);
     if (rc) return rc;
     for (int m = 0; m < n_images; ++m)
-        if (channels[m] != 1 && channels[m] != 3)
-            return apap::fail(APAP_ERR_INVALID_ARG, "%s: image %d has %d channels (1 = grey or 3 = BGR)", who, m, channels[m]);
+        if ((rc = apap::image_channels_check(m, channels[m], who))) return rc;
     if (max_corners < 1) return apap::fail(APAP_ERR_INVALID_ARG, "%s: max_corners = %d (>= 1)", who, max_corners);
     if (quality_permille < 0 || quality_permille > 1000)
         return apap::fail(APAP_ERR_INVALID_ARG, "%s: quality_permille = %d (0 .. 1000)", who, quality_permille);

@@ -52,7 +52,7 @@ struct alignas(16) WarpProblem {   // one problem, in device memory
 };
 static_assert(sizeof(WarpProblem) == 144, "the descriptor table's stride");
 
-size_t table_bytes(int n) { return ((size_t)n * sizeof(WarpProblem) + 255) / 256 * 256; }
+size_t table_bytes(int n) { return apap::up256((size_t)n * sizeof(WarpProblem)); }
 
 // the 3 bytes at byte offset `off` of a picture of `total` bytes (off + 3 <= total), in the low 24 bits.  One unaligned dword
 // load; at the picture's last pixel the dword one byte earlier, shifted, so that no byte beyond the picture is touched.

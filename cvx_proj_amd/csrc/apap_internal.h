@@ -147,6 +147,24 @@ int spectral_em_batch_check(const int *pair_offset, int n_pairs, const int *pair
 int local_model_check(int n, int cells, double gamma, double sigma, const double *params, const char *who);
 // The argument checks of the descriptor matcher's entry points (apap_match.hip) that need no device pointer.
 int match_check(const int *q_offset, const int *t_offset, int n_pairs, const char *who);
+// `bytes` rounded up to the 256-byte boundary on which every part of a workspace or pooled buffer starts.
+inline size_t up256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// The images of the feature front end (corner detection, descriptor extraction): their sides and their number in one call.
+// 7: every reflect-101 index that a valid descriptor sample reads reflects once (apap_image_dev.h).  (kImage...: named apart
+// from the global warp's own kMaxSide, 32767, which apap_image_warp.hip uses inside this namespace.)
+constexpr int kImageMinSide = 7, kImageMaxSide = 32768, kMaxImages = 65535;
+// Their per-image checks, one image a call so that each caller keeps its own order: corner_check looks at every image's
+// sides and then at every image's channels, sift_check at image after image.
+inline int image_sides_check(int m, int h, int w, const char *who) {
+    if (h < kImageMinSide || h > kImageMaxSide || w < kImageMinSide || w > kImageMaxSide)
+        return fail(APAP_ERR_INVALID_ARG, "%s: image %d is %d x %d (sides %d .. %d)", who, m, h, w, kImageMinSide, kImageMaxSide);
+    return APAP_OK;
+}
+inline int image_channels_check(int m, int c, const char *who) {
+    if (c != 1 && c != 3) return fail(APAP_ERR_INVALID_ARG, "%s: image %d has %d channels (1 = grey or 3 = BGR)", who, m, c);
+    return APAP_OK;
+}
 // The argument checks of the descriptor extraction's entry points (apap_sift.hip) that need no device pointer.
 int sift_check(const int *heights, const int *widths, const int *channels, int n_images, const int *pt_offset, const char *who);
 // The argument checks of the corner detector's entry points (apap_corner.hip) that need no device pointer.

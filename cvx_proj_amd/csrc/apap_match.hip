@@ -228,11 +228,11 @@ MatchPlan plan_match(int nq, int nt) {
     const int want = std::min(n_chunks, (APAP_MATCH_WANT_BLOCKS + p.q_tiles - 1) / p.q_tiles);
     p.cps = (n_chunks + want - 1) / want;
     p.splits = (n_chunks + p.cps - 1) / p.cps;
-    p.part_bytes = ((size_t)p.splits * nq * sizeof(MatchPart) + 255) / 256 * 256;
+    p.part_bytes = apap::up256((size_t)p.splits * nq * sizeof(MatchPart));
     return p;
 }
 
-size_t table_bytes(int n_pairs) { return ((size_t)n_pairs * sizeof(MatchPair) + 255) / 256 * 256; }
+size_t table_bytes(int n_pairs) { return apap::up256((size_t)n_pairs * sizeof(MatchPair)); }
 
 }  // namespace
 

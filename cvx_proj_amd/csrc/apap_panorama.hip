@@ -275,7 +275,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
 }
 
 size_t slice_bytes(int mesh_rows, int mesh_cols, int final_w, int final_h) {
-    return (apap_warp_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h) + 255) / 256 * 256;
+    return apap::up256(apap_warp_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h));
 }
 
 // W, H, OX, OY of the union canvas from the pair canvases; refuses a centre that does not fit one of them (the check of

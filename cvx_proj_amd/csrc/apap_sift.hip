@@ -28,9 +28,12 @@
 #include <cstdint>
 #include <vector>
 
+#include "apap_image_dev.h"
 #include "apap_internal.h"
 
 namespace {
+
+using apap::grey_at, apap::reflect;
 
 inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
 
@@ -42,9 +45,7 @@ constexpr int kBase = kPatch - (kTaps - 1);        // 9: the base-image patch
 constexpr int kPerBlock = APAP_SIFT_BLOCK_KEYPOINTS;
 constexpr int kThreads = 64 * kPerBlock;
 constexpr int kWinCols = APAP_SIFT_WINDOW_COLS;
-constexpr int kMinSide = 7, kMaxSide = 32768;      // 7: every reflect-101 index that a valid sample reads reflects once
 constexpr int kMaxRows = 1 << 24;
-constexpr int kMaxImages = 65535;
 static_assert(kDim == 128 && kSamples == 49 && kTaps == 13 && kPatch == 21 && kBase == 9 && kPerBlock == 4, "the lane mapping below is for these");
 
 struct SiftConst {   // the constants of the kernel, a kernel argument: made on the host in float64, rounded to float32
@@ -133,14 +134,6 @@ __device__ __forceinline__ float atan2_deg(float y, float x) {
     return deg;
 }
 
-// reflect-101, once, then clamped: a valid sample reads indices -6 .. n + 5 only, which reflect once into 0 .. n - 1 for
-// n >= 7; the clamp keeps what an invalid sample would read (and never uses) inside the image
-__device__ __forceinline__ int reflect(int i, int n) {
-    if (i < 0) i = -i;
-    if (i > n - 1) i = 2 * (n - 1) - i;
-    return min(max(i, 0), n - 1);
-}
-
 __device__ __forceinline__ float tree_sum(float a, float b) {   // bins (l, l + 64), then lanes l ^ 32, ^ 16 .. ^ 1
     float s = a + b;
 #pragma unroll
@@ -191,10 +184,7 @@ __global__ __launch_bounds__(kThreads) void k_sift_describe(const SiftImage *__r
         for (int at = lane; at < kPatch * kPatch; at += 64) {
             const int pr = at / kPatch, pc = at - pr * kPatch;
             const int y = reflect(py - 10 + pr, I.h), x = reflect(px - 10 + pc, I.w);
-            const uint8_t *p = I.img + ((size_t)y * I.w + x) * I.c;
-            int g = p[0];
-            if (I.c == 3) g = (3735 * g + 19235 * (int)p[1] + 9798 * (int)p[2] + 16384) >> 15;
-            patch[at] = (float)g;
+            patch[at] = (float)grey_at(I.img, y, x, I.w, I.c);
         }
     }
     __syncthreads();
@@ -270,7 +260,7 @@ __global__ __launch_bounds__(kThreads) void k_sift_describe(const SiftImage *__r
     o[lane + 64] = fminf(fmaxf(rintf(h[1] * scale), 0.f), 255.f);
 }
 
-size_t table_bytes(int n_images) { return ((size_t)n_images * sizeof(SiftImage) + 255) / 256 * 256; }
+size_t table_bytes(int n_images) { return apap::up256((size_t)n_images * sizeof(SiftImage)); }
 
 }  // namespace
 
@@ -279,15 +269,12 @@ namespace apap {
 // The argument checks of the descriptor extraction's entry points that need no device pointer.
 int sift_check(const int *heights, const int *widths, const int *channels, int n_images, const int *pt_offset, const char *who) {
     if (!heights || !widths || !channels || !pt_offset) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null heights / widths / channels / pt_offset", who);
-    if (n_images < 1 || n_images > kMaxImages)
-        return apap::fail(APAP_ERR_INVALID_ARG, "%s: n_images = %d (1 .. %d)", who, n_images, kMaxImages);
+    if (n_images < 1 || n_images > apap::kMaxImages)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: n_images = %d (1 .. %d)", who, n_images, apap::kMaxImages);
     if (pt_offset[0] < 0) return apap::fail(APAP_ERR_INVALID_ARG, "%s: pt_offset[0] = %d: negative", who, pt_offset[0]);
     for (int m = 0; m < n_images; ++m) {
-        if (heights[m] < kMinSide || heights[m] > kMaxSide || widths[m] < kMinSide || widths[m] > kMaxSide)
-            return apap::fail(APAP_ERR_INVALID_ARG, "%s: image %d is %d x %d (sides %d .. %d)", who, m, heights[m], widths[m], kMinSide,
-                              kMaxSide);
-        if (channels[m] != 1 && channels[m] != 3)
-            return apap::fail(APAP_ERR_INVALID_ARG, "%s: image %d has %d channels (1 = grey or 3 = BGR)", who, m, channels[m]);
+        if (int rc = apap::image_sides_check(m, heights[m], widths[m], who)) return rc;
+        if (int rc = apap::image_channels_check(m, channels[m], who)) return rc;
         const long long n = (long long)pt_offset[m + 1] - pt_offset[m];
         if (n < 1 || n > kMaxRows)
             return apap::fail(APAP_ERR_INVALID_ARG, "%s: image %d: %lld keypoints (offsets must increase strictly, an image holds "
@@ -316,7 +303,7 @@ int apap_sift_taps(float *out) {
     return APAP_OK;
 }
 
-size_t apap_sift_workspace_bytes(int n_images) { return n_images < 1 || n_images > kMaxImages ? 0 : table_bytes(n_images); }
+size_t apap_sift_workspace_bytes(int n_images) { return n_images < 1 || n_images > apap::kMaxImages ? 0 : table_bytes(n_images); }
 
 int apap_sift_describe_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs, const int *heights, const int *widths,
                                     const int *channels, int n_images, const float *d_pts, const int *pt_offset, float *d_out,

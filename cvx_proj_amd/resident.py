@@ -9,6 +9,7 @@ import ctypes
 import numpy as np
 
 from . import _native
+from ._native import _addrs, _dp, _i32, _ip
 
 if _native._lib is not None and not _native._torch_at_load:
     raise _native.ApapError(_native.ERR_HIP, "cvx_proj_amd's library was loaded before torch was imported: torch cannot see the GPU "
@@ -39,6 +40,24 @@ def _stream(dev):
 def _needs_device(t, who):
     if not t.is_cuda:
         raise _native.ApapError(_native.ERR_NO_DEVICE, f"{who} needs CUDA/HIP tensors; there is no CPU fallback")
+
+
+def _contiguous(tensors, dev, who):
+    """Every ``(tensor, dtype)`` of ``tensors`` must be a contiguous tensor of that dtype on ``dev``."""
+    for t, want in tensors:
+        if t.dtype != want or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{who}: inputs must be contiguous {want} tensors on {dev}")
+
+
+def _status(status, shape, dev, who, flat=False):
+    """``status`` checked - contiguous int32 on ``dev``, of ``shape`` or, with ``flat``, of as many elements - or a new zeroed one."""
+    if status is None:
+        return torch.zeros(shape, dtype=torch.int32, device=dev)
+    n = int(np.prod(shape))
+    if status.dtype != torch.int32 or (status.numel() != n if flat else status.shape != shape) or status.device != dev \
+            or not status.is_contiguous():
+        raise ValueError(f"{who}: status must be a contiguous int32 tensor of {n} elements on {dev}")
+    return status
 
 
 def _solve(tables, denorms, vertices, gamma, sigma, batch, ctx=None, out=None, work=None):
@@ -203,10 +222,8 @@ def hip_spectral(src, dst, c_feats, o_feats, F, params, Hg=None, mask=None, stat
     element) receives STATUS_NO_CONVERGENCE when the restart cap is hit (also in info[3])."""
     _needs_device(src, "hip_spectral")
     dev, n = src.device, src.shape[0]
-    for t, want in ((src, torch.float32), (dst, torch.float32), (c_feats, torch.float32), (o_feats, torch.float32),
-                    (F, torch.float64)):
-        if t.dtype != want or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"hip_spectral: inputs must be contiguous {want} tensors on {dev}")
+    _contiguous(((src, torch.float32), (dst, torch.float32), (c_feats, torch.float32), (o_feats, torch.float32), (F, torch.float64)),
+                dev, "hip_spectral")
     if dst.shape != src.shape or c_feats.shape != (n, _native.SPECTRAL_DIM) or o_feats.shape != c_feats.shape or F.shape != (3, 3):
         raise ValueError("hip_spectral: shapes (n, 2), (n, 2), (n, 128), (n, 128), (3, 3) expected")
     params = np.ascontiguousarray(params, dtype=np.float64)
@@ -217,7 +234,7 @@ def hip_spectral(src, dst, c_feats, o_feats, F, params, Hg=None, mask=None, stat
     work = _scratch(work, spectral_workspace_bytes(n), dev)
     _native.check(_native.lib().apap_spectral_device(
         _native._h(ctx), src.data_ptr(), dst.data_ptr(), c_feats.data_ptr(), o_feats.data_ptr(), n, F.data_ptr(),
-        params.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), None if Hg is None else Hg.data_ptr(),
+        _dp(params), None if Hg is None else Hg.data_ptr(),
         None if mask is None or Hg is not None else mask.data_ptr(), seg.data_ptr(), rm.data_ptr(), om.data_ptr(), info.data_ptr(),
         None if status is None else status.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
     return seg, rm, om, info
@@ -238,10 +255,8 @@ def hip_spectral_em(src, dst, c_feats, o_feats, F, spec_params, model_params, em
     info (k, 6)) as device tensors, not synchronised.  ``status`` (int32, 1 element) collects every round's status bits."""
     _needs_device(src, "hip_spectral_em")
     dev, n, k = src.device, src.shape[0], int(em_steps)
-    for t, want in ((src, torch.float32), (dst, torch.float32), (c_feats, torch.float32), (o_feats, torch.float32),
-                    (F, torch.float64), (mask, torch.float32)):
-        if t.dtype != want or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"hip_spectral_em: inputs must be contiguous {want} tensors on {dev}")
+    _contiguous(((src, torch.float32), (dst, torch.float32), (c_feats, torch.float32), (o_feats, torch.float32), (F, torch.float64),
+                 (mask, torch.float32)), dev, "hip_spectral_em")
     if dst.shape != src.shape or c_feats.shape != (n, _native.SPECTRAL_DIM) or o_feats.shape != c_feats.shape or F.shape != (3, 3) \
             or mask.shape != (n,):
         raise ValueError("hip_spectral_em: shapes (n, 2), (n, 2), (n, 128), (n, 128), (3, 3), (n,) expected")
@@ -254,10 +269,9 @@ def hip_spectral_em(src, dst, c_feats, o_feats, F, spec_params, model_params, em
     om = torch.empty((k, n), dtype=torch.float32, device=dev)
     sinfo = torch.empty((k, _native.SPECTRAL_INFO), dtype=torch.float64, device=dev)
     work = _scratch(work, spectral_workspace_bytes(n) + model_workspace_bytes(n), dev)
-    dbl = ctypes.POINTER(ctypes.c_double)
     _native.check(_native.lib().apap_spectral_em_device(
         _native._h(ctx), src.data_ptr(), dst.data_ptr(), c_feats.data_ptr(), o_feats.data_ptr(), n, F.data_ptr(),
-        sp.ctypes.data_as(dbl), mp.ctypes.data_as(dbl), k, mask.data_ptr(), H.data_ptr(), info.data_ptr(), seg.data_ptr(),
+        _dp(sp), _dp(mp), k, mask.data_ptr(), H.data_ptr(), info.data_ptr(), seg.data_ptr(),
         rm.data_ptr(), om.data_ptr(), sinfo.data_ptr(), None if status is None else status.data_ptr(), work.data_ptr(),
         work.numel(), _stream(dev)))
     return H, info, seg, rm, om, sinfo
@@ -268,8 +282,7 @@ def em_batch_workspace_bytes(pair_lengths, pair_of):
     off = np.zeros(len(pair_lengths) + 1, np.int32)
     off[1:] = np.cumsum(pair_lengths)
     po = np.ascontiguousarray(pair_of, dtype=np.int32)
-    ip = ctypes.POINTER(ctypes.c_int)
-    return _native.lib().apap_spectral_em_batch_workspace_bytes(off.ctypes.data_as(ip), len(off) - 1, po.ctypes.data_as(ip), len(po))
+    return _native.lib().apap_spectral_em_batch_workspace_bytes(_ip(off), len(off) - 1, _ip(po), len(po))
 
 
 def hip_spectral_em_batch(src, dst, c_feats, o_feats, F, mask, pair_lengths, pair_of, spec_params, model_params, em_steps,
@@ -285,17 +298,12 @@ def hip_spectral_em_batch(src, dst, c_feats, o_feats, F, mask, pair_lengths, pai
     dev, k = src.device, int(em_steps)
     off, po, sp, mp = _native.em_batch_tables(pair_lengths, pair_of, spec_params, model_params)
     N, P, B = int(off[-1]), len(off) - 1, len(po)
-    for t, want in ((src, torch.float32), (dst, torch.float32), (c_feats, torch.float32), (o_feats, torch.float32),
-                    (F, torch.float64), (mask, torch.float32)):
-        if t.dtype != want or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"hip_spectral_em_batch: inputs must be contiguous {want} tensors on {dev}")
+    _contiguous(((src, torch.float32), (dst, torch.float32), (c_feats, torch.float32), (o_feats, torch.float32), (F, torch.float64),
+                 (mask, torch.float32)), dev, "hip_spectral_em_batch")
     if src.shape != (N, 2) or dst.shape != src.shape or c_feats.shape != (N, _native.SPECTRAL_DIM) or o_feats.shape != c_feats.shape \
             or F.shape != (P, 3, 3) or mask.shape != (N,):
         raise ValueError(f"hip_spectral_em_batch: shapes ({N}, 2), ({N}, 2), ({N}, 128), ({N}, 128), ({P}, 3, 3), ({N},) expected")
-    if status is None:
-        status = torch.zeros(B, dtype=torch.int32, device=dev)
-    elif status.dtype != torch.int32 or status.shape != (B,) or status.device != dev or not status.is_contiguous():
-        raise ValueError(f"hip_spectral_em_batch: status must be a contiguous int32 tensor of {B} elements on {dev}")
+    status = _status(status, (B,), dev, "hip_spectral_em_batch")
     M = int(sum(int(off[p + 1] - off[p]) for p in po))
     H = torch.empty((B, k, 3, 3), dtype=torch.float32, device=dev)
     info = torch.empty((B, k, _native.MODEL_INFO), dtype=torch.float64, device=dev)
@@ -304,10 +312,9 @@ def hip_spectral_em_batch(src, dst, c_feats, o_feats, F, mask, pair_lengths, pai
     om = torch.empty(k * M, dtype=torch.float32, device=dev)
     sinfo = torch.empty((B, k, _native.SPECTRAL_INFO), dtype=torch.float64, device=dev)
     work = _scratch(work, em_batch_workspace_bytes([int(off[p + 1] - off[p]) for p in range(P)], po), dev)
-    dbl, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
     _native.check(_native.lib().apap_spectral_em_batch_device(
         _native._h(ctx), src.data_ptr(), dst.data_ptr(), c_feats.data_ptr(), o_feats.data_ptr(), F.data_ptr(), mask.data_ptr(),
-        off.ctypes.data_as(ip), P, po.ctypes.data_as(ip), sp.ctypes.data_as(dbl), mp.ctypes.data_as(dbl), B, k, H.data_ptr(),
+        _ip(off), P, _ip(po), _dp(sp), _dp(mp), B, k, H.data_ptr(),
         info.data_ptr(), seg.data_ptr(), rm.data_ptr(), om.data_ptr(), sinfo.data_ptr(), status.data_ptr(), work.data_ptr(),
         work.numel(), _stream(dev)))
     return H, info, seg, rm, om, sinfo, status
@@ -334,19 +341,14 @@ def hip_local_model_solve(pts_c, pts_o, vertices, gamma, sigma, params, match_we
     tensors = [(pts_c, torch.float32), (pts_o, torch.float32), (vertices, torch.float64)]
     if match_weights is not None:
         tensors.append((match_weights, torch.float32))
-    for t, want in tensors:
-        if t.dtype != want or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"hip_local_model_solve: inputs must be contiguous {want} tensors on {dev}")
+    _contiguous(tensors, dev, "hip_local_model_solve")
     n = pts_c.shape[0]
     if pts_c.shape != (n, 2) or pts_o.shape != pts_c.shape or vertices.dim() < 1 or vertices.shape[-1] != 2 \
             or (match_weights is not None and match_weights.shape != (n,)):
         raise ValueError(f"hip_local_model_solve: shapes ({n}, 2), ({n}, 2), (..., 2) and ({n},) expected")
     lead = tuple(vertices.shape[:-1])
     cells = vertices.numel() // 2
-    if status is None:
-        status = torch.zeros(lead, dtype=torch.int32, device=dev)
-    elif status.dtype != torch.int32 or status.numel() != cells or status.device != dev or not status.is_contiguous():
-        raise ValueError(f"hip_local_model_solve: status must be a contiguous int32 tensor of {cells} elements on {dev}")
+    status = _status(status, lead, dev, "hip_local_model_solve", flat=True)
     H = torch.empty(lead + (3, 3), dtype=torch.float32, device=dev)
     info = torch.empty(lead + (_native.MODEL_INFO,), dtype=torch.float64, device=dev)
     if cells == 0:
@@ -355,7 +357,7 @@ def hip_local_model_solve(pts_c, pts_o, vertices, gamma, sigma, params, match_we
         work = torch.empty(local_model_workspace_bytes(n, cells), dtype=torch.uint8, device=dev)
     _native.check(_native.lib().apap_local_model_solve_device(
         _native._h(ctx), pts_c.data_ptr(), pts_o.data_ptr(), None if match_weights is None else match_weights.data_ptr(), n,
-        vertices.data_ptr(), cells, float(gamma), float(sigma), params.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), H.data_ptr(),
+        vertices.data_ptr(), cells, float(gamma), float(sigma), _dp(params), H.data_ptr(),
         info.data_ptr(), status.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
     return H, info, status
 
@@ -367,8 +369,7 @@ def match_workspace_bytes(q_lengths, t_lengths=None):
     if np.ndim(q_lengths) == 0:
         return _native.lib().apap_match_workspace_bytes(int(q_lengths), int(t_lengths))
     qo, to = _native.match_offsets(q_lengths, "q_lengths"), _native.match_offsets(t_lengths, "t_lengths")
-    ip = ctypes.POINTER(ctypes.c_int)
-    return _native.lib().apap_match_batch_workspace_bytes(qo.ctypes.data_as(ip), to.ctypes.data_as(ip), min(len(qo), len(to)) - 1)
+    return _native.lib().apap_match_batch_workspace_bytes(_ip(qo), _ip(to), min(len(qo), len(to)) - 1)
 
 
 def hip_match_descriptors_batch(q, t, q_lengths, t_lengths, second=True, ctx=None, work=None):
@@ -394,10 +395,10 @@ def hip_match_descriptors_batch(q, t, q_lengths, t_lengths, second=True, ctx=Non
     dist = torch.empty(n, dtype=torch.float32, device=dev)
     idx2 = torch.empty(n, dtype=torch.int32, device=dev) if second else None
     dist2 = torch.empty(n, dtype=torch.float32, device=dev) if second else None
-    ip = ctypes.POINTER(ctypes.c_int)
-    work = _scratch(work, _native.lib().apap_match_batch_workspace_bytes(qo.ctypes.data_as(ip), to.ctypes.data_as(ip), len(qo) - 1), dev)
+    p_qo, p_to = _ip(qo), _ip(to)
+    work = _scratch(work, _native.lib().apap_match_batch_workspace_bytes(p_qo, p_to, len(qo) - 1), dev)
     _native.check(_native.lib().apap_match_descriptors_batch_device(
-        _native._h(ctx), q.data_ptr(), t.data_ptr(), qo.ctypes.data_as(ip), to.ctypes.data_as(ip), len(qo) - 1, idx.data_ptr(),
+        _native._h(ctx), q.data_ptr(), t.data_ptr(), p_qo, p_to, len(qo) - 1, idx.data_ptr(),
         dist.data_ptr(), None if idx2 is None else idx2.data_ptr(), None if dist2 is None else dist2.data_ptr(), work.data_ptr(),
         work.numel(), _stream(dev)))
     return idx, dist, idx2, dist2
@@ -408,6 +409,19 @@ def hip_match_descriptors(q, t, second=True, ctx=None, work=None):
     row of ``q`` (nq, 128), exact L2; the batch of one pair (see ``hip_match_descriptors_batch``)."""
     _needs_device(q, "hip_match_descriptors")
     return hip_match_descriptors_batch(q, t, [q.shape[0]], [t.shape[0]], second=second, ctx=ctx, work=work)
+
+
+def _image_table(imgs, dev, who):
+    """The checks of a list of uint8 images on ``dev``, (h, w) grey or (h, w, 3) BGR - what ``_native.as_sift_image`` asks of a
+    host array, with its side limits - and the batch entry points' (addresses, heights, widths, channels)."""
+    for m, im in enumerate(imgs):
+        if im.dtype != torch.uint8 or not im.is_contiguous() or im.device != dev or im.dim() not in (2, 3) or \
+                (im.dim() == 3 and im.shape[2] not in (1, 3)):
+            raise ValueError(f"{who}: imgs[{m}] must be a contiguous uint8 (h, w) or (h, w, 3) tensor on {dev}")
+        if not all(_native.SIFT_MIN_SIDE <= x <= _native.SIFT_MAX_SIDE for x in im.shape[:2]):
+            raise ValueError(f"{who}: imgs[{m}]: sides must be {_native.SIFT_MIN_SIDE} .. {_native.SIFT_MAX_SIDE}; got {tuple(im.shape[:2])}")
+    return (_addrs([im.data_ptr() for im in imgs]), _i32([im.shape[0] for im in imgs]), _i32([im.shape[1] for im in imgs]),
+            _i32([1 if im.dim() == 2 else im.shape[2] for im in imgs]))
 
 
 def sift_workspace_bytes(n_images=1):
@@ -432,24 +446,15 @@ def hip_sift_describe_batch(imgs, pts, lengths, ctx=None, work=None):
     imgs = list(imgs)
     if len(imgs) != len(lengths):
         raise ValueError(f"{who}: {len(imgs)} images, {len(lengths)} keypoint counts")
-    for m, im in enumerate(imgs):
-        if im.dtype != torch.uint8 or not im.is_contiguous() or im.device != dev or im.dim() not in (2, 3) or \
-                (im.dim() == 3 and im.shape[2] not in (1, 3)):
-            raise ValueError(f"{who}: imgs[{m}] must be a contiguous uint8 (h, w) or (h, w, 3) tensor on {dev}")
-        if not all(_native.SIFT_MIN_SIDE <= x <= _native.SIFT_MAX_SIDE for x in im.shape[:2]):
-            raise ValueError(f"{who}: imgs[{m}]: sides must be {_native.SIFT_MIN_SIDE} .. {_native.SIFT_MAX_SIDE}; got {tuple(im.shape[:2])}")
+    ptrs, hs, ws, cs = _image_table(imgs, dev, who)
     off = _native.sift_offsets(lengths)
     if off[-1] != pts.shape[0]:
         raise ValueError(f"{who}: the counts sum to {off[-1]} keypoints; got {pts.shape[0]}")
-    ip = ctypes.POINTER(ctypes.c_int)
-    ptrs = (ctypes.c_void_p * len(imgs))(*[im.data_ptr() for im in imgs])
-    hs, ws = np.array([im.shape[0] for im in imgs], np.int32), np.array([im.shape[1] for im in imgs], np.int32)
-    cs = np.array([1 if im.dim() == 2 else im.shape[2] for im in imgs], np.int32)
     out = torch.empty((pts.shape[0], _native.SIFT_DIM), dtype=torch.float32, device=dev)
     work = _scratch(work, sift_workspace_bytes(len(imgs)), dev)
     _native.check(_native.lib().apap_sift_describe_batch_device(
-        _native._h(ctx), ptrs, hs.ctypes.data_as(ip), ws.ctypes.data_as(ip), cs.ctypes.data_as(ip), len(imgs), pts.data_ptr(),
-        off.ctypes.data_as(ip), out.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
+        _native._h(ctx), ptrs, _ip(hs), _ip(ws), _ip(cs), len(imgs), pts.data_ptr(), _ip(off), out.data_ptr(), work.data_ptr(), work.numel(),
+        _stream(dev)))
     return out
 
 
@@ -471,31 +476,12 @@ def hip_describe_and_match(c_img, o_img, pts_c, pts_o, second=True, ctx=None):
     return hip_match_descriptors(feats[:nc], feats[nc:], second=second, ctx=ctx) + (feats[:nc], feats[nc:])
 
 
-def _corner_images(imgs, who):
-    """The checks of a sequence of uint8 device images and their shape tables."""
-    imgs = list(imgs)
-    if not imgs:
-        raise ValueError(f"{who}: no image")
-    _needs_device(imgs[0], who)
-    dev = imgs[0].device
-    for m, im in enumerate(imgs):
-        if im.dtype != torch.uint8 or not im.is_contiguous() or im.device != dev or im.dim() not in (2, 3) or \
-                (im.dim() == 3 and im.shape[2] not in (1, 3)):
-            raise ValueError(f"{who}: imgs[{m}] must be a contiguous uint8 (h, w) or (h, w, 3) tensor on {dev}")
-        if not all(_native.SIFT_MIN_SIDE <= x <= _native.SIFT_MAX_SIDE for x in im.shape[:2]):
-            raise ValueError(f"{who}: imgs[{m}]: sides must be {_native.SIFT_MIN_SIDE} .. {_native.SIFT_MAX_SIDE}; got {tuple(im.shape[:2])}")
-    hs, ws = np.array([im.shape[0] for im in imgs], np.int32), np.array([im.shape[1] for im in imgs], np.int32)
-    cs = np.array([1 if im.dim() == 2 else im.shape[2] for im in imgs], np.int32)
-    return imgs, dev, hs, ws, cs
-
-
 def corner_workspace_bytes(shapes, radius=5):
     """Scratch of ``hip_corner_detect`` / ``hip_corner_detect_batch`` for images of ``shapes`` (a sequence of (h, w, ...)):
     per image 64 bytes and twice 16 bytes per possible corner (the second time rounded up to a power of two); a 256-byte
     multiple.  0 for invalid arguments."""
-    hs, ws = np.array([s[0] for s in shapes], np.int32), np.array([s[1] for s in shapes], np.int32)
-    ip = ctypes.POINTER(ctypes.c_int)
-    return _native.lib().apap_corner_workspace_bytes(hs.ctypes.data_as(ip), ws.ctypes.data_as(ip), len(hs), int(radius))
+    hs, ws = _i32([s[0] for s in shapes]), _i32([s[1] for s in shapes])
+    return _native.lib().apap_corner_workspace_bytes(_ip(hs), _ip(ws), len(hs), int(radius))
 
 
 def hip_corner_detect_batch(imgs, max_corners, radius=5, quality_permille=10, ctx=None, work=None):
@@ -506,16 +492,20 @@ def hip_corner_detect_batch(imgs, max_corners, radius=5, quality_permille=10, ct
     count on are zero.  ``work`` (uint8) is used when it holds ``corner_workspace_bytes(shapes, radius)``.  Same bytes as
     ``_native.corner_detect_batch``, and per image as ``hip_corner_detect``."""
     who = "hip_corner_detect_batch"
-    imgs, dev, hs, ws, cs = _corner_images(imgs, who)
+    imgs = list(imgs)
+    if not imgs:
+        raise ValueError(f"{who}: no image")
+    _needs_device(imgs[0], who)
+    dev = imgs[0].device
+    ptrs, hs, ws, cs = _image_table(imgs, dev, who)
     max_corners, radius, quality_permille = _native.corner_params(max_corners, radius, quality_permille, who)
-    ip = ctypes.POINTER(ctypes.c_int)
-    ptrs = (ctypes.c_void_p * len(imgs))(*[im.data_ptr() for im in imgs])
     pts = torch.empty((len(imgs), max_corners, 2), dtype=torch.float32, device=dev)
     resp = torch.empty((len(imgs), max_corners), dtype=torch.int64, device=dev)
     count = torch.empty(len(imgs), dtype=torch.int32, device=dev)
-    work = _scratch(work, _native.lib().apap_corner_workspace_bytes(hs.ctypes.data_as(ip), ws.ctypes.data_as(ip), len(imgs), radius), dev)
+    p_hs, p_ws = _ip(hs), _ip(ws)
+    work = _scratch(work, _native.lib().apap_corner_workspace_bytes(p_hs, p_ws, len(imgs), radius), dev)
     _native.check(_native.lib().apap_corner_detect_batch_device(
-        _native._h(ctx), ptrs, hs.ctypes.data_as(ip), ws.ctypes.data_as(ip), cs.ctypes.data_as(ip), len(imgs), max_corners, radius,
+        _native._h(ctx), ptrs, p_hs, p_ws, _ip(cs), len(imgs), max_corners, radius,
         quality_permille, pts.data_ptr(), resp.data_ptr(), count.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
     return pts, resp, count
 
@@ -585,13 +575,11 @@ def hip_image_warp_batch(problems, out=None, out_offsets=None, status=None, ctx=
     if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != dev or out.numel() < need:
         raise ValueError(f"{who}: out must be a flat contiguous uint8 tensor of at least {need} bytes on {dev}")
     work = _scratch(work, image_warp_workspace_bytes(n), dev)
-    ip, vpp = ctypes.POINTER(ctypes.c_int), ctypes.c_void_p * n
     _native.check(_native.lib().apap_image_warp_batch_device(
-        _native._h(ctx), vpp(*[b.data_ptr() for b, _, _, _ in problems]), bh.ctypes.data_as(ip), bw.ctypes.data_as(ip),
-        vpp(*[s.data_ptr() for _, s, _, _ in problems]), sh.ctypes.data_as(ip), sw.ctypes.data_as(ip),
-        M.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cw.ctypes.data_as(ip), ch.ctypes.data_as(ip), ox.ctypes.data_as(ip),
-        oy.ctypes.data_as(ip), direct.ctypes.data_as(ip), n, out.data_ptr(), off.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
-        work.data_ptr(), work.numel(), status.data_ptr() if status is not None else None, _stream(dev)))
+        _native._h(ctx), _addrs([b.data_ptr() for b, _, _, _ in problems]), _ip(bh), _ip(bw),
+        _addrs([s.data_ptr() for _, s, _, _ in problems]), _ip(sh), _ip(sw), _dp(M), _ip(cw), _ip(ch), _ip(ox), _ip(oy), _ip(direct), n,
+        out.data_ptr(), _native._ptr(off, ctypes.c_longlong), work.data_ptr(), work.numel(),
+        status.data_ptr() if status is not None else None, _stream(dev)))
     return [out[int(o):int(o) + s].view(int(h), int(w), 3) for o, s, w, h in zip(off, sizes, cw, ch)]
 
 
@@ -608,7 +596,7 @@ def hip_image_warp(img_base, img2warp, H, direct_blend=True, status=None, ctx=No
     work = _scratch(work, image_warp_workspace_bytes(1), dev)
     _native.check(_native.lib().apap_image_warp_device(
         _native._h(ctx), img_base.data_ptr(), img_base.shape[0], img_base.shape[1], img2warp.data_ptr(), img2warp.shape[0],
-        img2warp.shape[1], M.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cw, ch, tx, ty, 1 if direct_blend else 0, out.data_ptr(),
+        img2warp.shape[1], _dp(M), cw, ch, tx, ty, 1 if direct_blend else 0, out.data_ptr(),
         work.data_ptr(), work.numel(), status.data_ptr() if status is not None else None, _stream(dev)))
     return out
 
@@ -617,11 +605,9 @@ def panorama_workspace_bytes(layers):
     """Scratch of ``hip_panorama`` for these layers (``PanoramaLayer``-like): every layer's warp workspace, a 256-byte
     multiple each, no contract on its contents.  0 for invalid arguments."""
     layers, (fw, fh, _, _) = _native.panorama_geometry(layers, "panorama_workspace_bytes")
-    ip = ctypes.POINTER(ctypes.c_int)
-    mr = np.array([l.local_homography.shape[0] for l in layers], dtype=np.int32)
-    mc = np.array([l.local_homography.shape[1] for l in layers], dtype=np.int32)
-    return _native.lib().apap_panorama_workspace_bytes(mr.ctypes.data_as(ip), mc.ctypes.data_as(ip), fw.ctypes.data_as(ip),
-                                                       fh.ctypes.data_as(ip), len(layers))
+    mr = _i32([l.local_homography.shape[0] for l in layers])
+    mc = _i32([l.local_homography.shape[1] for l in layers])
+    return _native.lib().apap_panorama_workspace_bytes(_ip(mr), _ip(mc), _ip(fw), _ip(fh), len(layers))
 
 
 def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, work=None, ramp=32):
@@ -666,16 +652,14 @@ def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, 
         status = torch.zeros(n, dtype=torch.int32, device=dev)
     if status.dtype != torch.int32 or status.numel() < n or not status.is_contiguous() or status.device != dev:
         raise ValueError(f"{who}: status must be a contiguous int32 tensor of at least {n} words on {dev}")
-    i32 = lambda v: np.array(v, dtype=np.int32)      # noqa: E731
-    ih, iw = i32([t.shape[0] for t in imgs]), i32([t.shape[1] for t in imgs])
-    mr, mc = i32([t.shape[0] for t in grids]), i32([t.shape[1] for t in grids])
-    nw, nh = i32([t.numel() for t in mws]), i32([t.numel() for t in mhs])
-    ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))      # noqa: E731
-    vpp = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])      # noqa: E731
-    need = _native.lib().apap_panorama_workspace_bytes(ip(mr), ip(mc), ip(fw), ip(fh), n)
-    work = _scratch(work, need, dev)
+    ih, iw = _i32([t.shape[0] for t in imgs]), _i32([t.shape[1] for t in imgs])
+    mr, mc = _i32([t.shape[0] for t in grids]), _i32([t.shape[1] for t in grids])
+    nw, nh = _i32([t.numel() for t in mws]), _i32([t.numel() for t in mhs])
+    table = [_addrs([t.data_ptr() for t in ts]) for ts in (imgs, grids, mws, mhs)]
+    p_mr, p_mc, p_fw, p_fh = _ip(mr), _ip(mc), _ip(fw), _ip(fh)
+    work = _scratch(work, _native.lib().apap_panorama_workspace_bytes(p_mr, p_mc, p_fw, p_fh, n), dev)
     _native.check(entry(
-        _native._h(ctx), center.data_ptr(), center.shape[0], center.shape[1], vpp(imgs), ip(ih), ip(iw), vpp(grids), ip(mr), ip(mc),
-        vpp(mws), ip(nw), vpp(mhs), ip(nh), ip(fw), ip(fh), ip(ox), ip(oy), n, mode, out.data_ptr(), work.data_ptr(), work.numel(),
+        _native._h(ctx), center.data_ptr(), center.shape[0], center.shape[1], table[0], _ip(ih), _ip(iw), table[1], p_mr, p_mc,
+        table[2], _ip(nw), table[3], _ip(nh), p_fw, p_fh, _ip(ox), _ip(oy), n, mode, out.data_ptr(), work.data_ptr(), work.numel(),
         status.data_ptr(), _stream(dev)))
     return out, (W, H, OX, OY), status

@@ -75,6 +75,29 @@ def test_bytes_equal_the_specification(native_gpu, big, n):
         same_bytes(native_gpu.sift_describe(S.grey(img), pts[:n]), want[:n], "grey")
 
 
+@pytest.mark.parametrize("shape", [(7, 7, 3), (37, 53, 3)], ids=str)
+def test_bgr_equals_its_grey(native_gpu, spec, shape):
+    """test_gpu_corner.py::test_bgr_equals_its_grey for the descriptor: the kernels of both read an image through the same
+    apap::grey_at.  Keypoints on the four corners, the four edge midpoints and the centre; at 7 x 7, the smallest image, every
+    one of them reads reflected indices on all four sides."""
+    import torch
+    from cvx_proj_amd import resident
+    h, w = shape[:2]
+    img = np.random.default_rng(h * w).integers(0, 256, shape).astype(np.uint8)
+    g = S.grey(img)
+    assert g.shape == (h, w) and g.dtype == np.uint8
+    pts = np.float32([[x, y] for y in (0, h // 2, h - 1) for x in (0, w // 2, w - 1)])
+    a, b = native_gpu.sift_describe(img, pts), native_gpu.sift_describe(g, pts)
+    same_bytes(a, b, "BGR against grey")
+    same_bytes(b, spec(g, pts), "against the specification")
+    assert a.shape == (9, 128) and a.any(axis=1).all()
+    dev = torch.device("cuda", 0)
+    d_pts = torch.from_numpy(pts).to(dev)
+    da, db = (resident.hip_sift_describe(torch.from_numpy(x).to(dev), d_pts).cpu().numpy() for x in (img, g))
+    same_bytes(da, db, "resident: BGR against grey")
+    same_bytes(da, a, "resident against host buffers")
+
+
 def test_zero_descriptors(native_gpu):
     img = scene(40, 50)
     far = np.float32([[-3, 5], [5, -3], [52, 5], [5, 42], [1e6, 1e6], [-1e30, 3], [3, 3e38], [-3.4, 5]])
