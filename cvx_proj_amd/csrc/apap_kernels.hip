@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "apap_internal.h"
@@ -35,29 +36,10 @@ struct BatchStride {
     long long table, vertices, moments, denorm, H;
 };
 
-// sqrt_pos, exp_nonpos and cell_weight (the weight of one keypoint for one cell) live in apap_weight_dev.h.
-
-// w^2 for K1, where the weight itself is not an output: 31 fp64 instructions instead of
-// 37.  max(exp(-t), gamma)^2 = max(exp(-2t), gamma^2); the squared distance is one
-// multiply-add chain that carries the 1e-300 guard; sqrt keeps one residual correction
-// (error < 1 ulp instead of correctly rounded).  Each change moves w^2 by at most a few
-// ulp of float64 (1e-16 relative) - eight orders below what the float32 H can see; the
-// weight tensor that callers can ask for still comes from cell_weight().
-//   inv_sigma2 = 2 / sigma^2,  gamma2 = gamma > 0 ? gamma * gamma : 0
-__device__ __forceinline__ double cell_weight_sq(double vx, double vy, double sx, double sy,
-                                                 double inv_sigma2, double gamma2) {
-    const double dx = vx - sx;
-    const double dy = vy - sy;
-    const double x = fma(dx, dx, fma(dy, dy, 1e-300));
-    const double y = __builtin_amdgcn_rsq(x);
-    double g = x * y;
-    const double h = y * 0.5;
-    const double r = fma(-h, g, 0.5);
-    g = fma(g, r, g);
-    const double d = fma(-g, g, x);
-    g = fma(d, h, g);  // h keeps the seed's ~2^-23 error: invisible in a ~2^-45 g correction
-    return fmax(exp_nonpos(-(g * inv_sigma2)), gamma2);
-}
+// The weight tensor that callers can ask for comes from cell_weight() (apap_weight_dev.h, with sqrt_pos and exp_nonpos).  K1
+// needs w^2 only and never returns it: its chains below (cell_weight_sq_tab in float64, cell_weight_sq_f32) evaluate
+// max(exp(-t), gamma)^2 as max(exp(-2t), gamma^2) with a cheaper square root and a table-driven exp, a few ulp of float64
+// from cell_weight()^2 - eight orders below what the float32 H can see.
 
 // Table-driven exp for the MFMA variant, argument pre-scaled: the caller passes
 // yu = u * 512 log2(e) >= 0 and gets exp(-u) = 2^(-yu / 512).  With -floor(yu) = 512 m + j
@@ -272,6 +254,163 @@ __device__ __forceinline__ bool table_is_24(const double *__restrict__ table) {
 }
 
 // --------------------------------------------------------------------------------
+// The steps that K1's forms share (k_assemble_valu, k_assemble_mfma, k_assemble_mfma4, the fused k_solve_small), defined once:
+// the block's share of the launch, the exp table's way into LDS, the staging of a 64-keypoint chunk into swizzled LDS rows, the
+// weight chain, the 16x16x4 step, the D-register layouts of the two MFMA forms (profiles/solve_shared_steps.txt: the compiled code).
+// --------------------------------------------------------------------------------
+typedef double double4_t __attribute__((ext_vector_type(4)));
+// Keypoints per LDS buffer (16 KiB).  32 / 48 / 64 measured the same (196-200 us at C3): the
+// kernel is bound by the fp64 pipe, not by barriers or occupancy (VGPR + AGPR = 102 -> 4 waves
+// per SIMD; forcing <= 96 registers for 5-6 waves per SIMD changed nothing either).
+constexpr int kChunk = 64;
+static_assert(kChunk % 16 == 0 && kChunk % 4 == 0, "chunk must split evenly over 256 threads and 4-keypoint steps");
+
+// The block's share of a batched launch: blockIdx.z's pair (`table` and `vertices` move to it; the outputs differ per kernel
+// and stay with them) and keypoint split `split` of `pts_per_split` keypoints each: [p_begin, p_end), nchunks chunks.
+struct K1Block {
+    int p_begin, p_end, nchunks;
+    __device__ __forceinline__ K1Block(const double *__restrict__ &table, const double *__restrict__ &vertices,
+                                       const BatchStride &bs, int n, int split, int pts_per_split) {
+        table += (long long)blockIdx.z * bs.table;
+        vertices += (long long)blockIdx.z * bs.vertices;
+        p_begin = min(n, split * pts_per_split);
+        p_end = min(n, p_begin + pts_per_split);
+        nchunks = (p_end - p_begin + kChunk - 1) / kChunk;
+    }
+};
+
+// The sample point of `cell`; the lanes of a tile's overhang repeat the last cell's (their sums are never stored).
+__device__ __forceinline__ double2 cell_vertex(const double *__restrict__ vertices, int cell, int cells) {
+    const int cc = min(cell, cells - 1);
+    return make_double2(vertices[2 * cc], vertices[2 * cc + 1]);
+}
+
+// The exp table's way into LDS (visible after the block's next barrier), in two flavours.  Direct: one pass, the block waits
+// for the table before it goes on.  Register-staged: fetched first, published AFTER the first chunk's loads have been issued:
+// `s_exp2[j] = kExp2Tab[j]` at the top made the block wait out one global-memory latency before it even asked for its
+// keypoints (two latencies in a row; it shows on small meshes).
+template <int kThreads>
+__device__ __forceinline__ void exp_table_copy(double *s_exp2, int tid) {
+    for (int j = tid; j < kExpN; j += kThreads) s_exp2[j] = kExp2Tab[j];
+}
+template <int kThreads>
+struct ExpTableStage {
+    static_assert(kExpN % kThreads == 0 || kThreads % kExpN == 0, "exp table vs block size");
+    static constexpr int kPerThread = (kExpN + kThreads - 1) / kThreads;
+    double v[kPerThread];
+    __device__ __forceinline__ void fetch(int tid) {
+#pragma unroll
+        for (int i = 0; i < kPerThread; ++i) v[i] = kExp2Tab[(tid + i * kThreads) & (kExpN - 1)];
+    }
+    __device__ __forceinline__ void publish(double *s_exp2, int tid) const {
+#pragma unroll
+        for (int i = 0; i < kPerThread; ++i) s_exp2[(tid + i * kThreads) & (kExpN - 1)] = v[i];
+    }
+};
+
+// Byte offset of table entry (row r, column c) in an LDS chunk: 256-B rows; odd rows swap
+// their 128-B halves so that the two keypoint rows a 32-lane ds_read_b64 covers (lanes
+// 0-15 -> row r, 16-31 -> row r+1) fall on disjoint halves of the 64 banks.
+__host__ __device__ constexpr int lds_off(int r, int c) { return r * 256 + ((c ^ ((r & 1) << 4)) << 3); }
+// The same swizzle for the staging's 16-byte pieces (slot = columns 2 slot, 2 slot + 1), tied to lds_off by the assertion.  Not
+// lds_off(r, 2 * slot): from that form the compiler folds a thread's four pieces into one address and four immediates, 8-9
+// instructions out of every chunk loop - a tuning change, to be measured on its own.  (A macro: see APAP_CHUNK_STORE.)
+#define APAP_LDS_PIECE_OFF(r, slot) ((r) * 256 + ((slot) ^ (((r) & 1) << 3)) * 16)
+constexpr bool lds_swizzles_agree() {
+    for (int r = 0; r < 2; ++r)
+        for (int slot = 0; slot < 16; ++slot)
+            if (APAP_LDS_PIECE_OFF(r, slot) != lds_off(r, 2 * slot) || APAP_LDS_PIECE_OFF(r, slot) + 8 != lds_off(r, 2 * slot + 1))
+                return false;
+    return true;
+}
+static_assert(lds_swizzles_agree(), "a staged piece lands where lds_off looks for its two columns, for both row parities");
+
+// Staging of a chunk: thread t of kThreads moves the 16-byte pieces t, t + kThreads, ... of the chunk's 1024;
+// piece q = (row q >> 4, 16-byte slot q & 15 = columns 2 (q & 15) and the next).  chunk_load fetches table rows
+// first_row .. first_row + 63 into registers (rows from end_row on are zero: zero rows add nothing whatever their weight) and
+// APAP_CHUNK_STORE writes them to the chunk buffer `buf`, so that the loads can fly while the previous chunk is worked on.
+template <int kThreads>
+using ChunkStage = double2[kChunk * 16 / kThreads];
+template <int kThreads>
+__device__ __forceinline__ void chunk_load(ChunkStage<kThreads> &stage, const double *__restrict__ table, int tid, int first_row,
+                                           int end_row) {
+#pragma unroll
+    for (int i = 0; i < kChunk * 16 / kThreads; ++i) {
+        const int q = tid + kThreads * i;
+        const int p = first_row + (q >> 4);
+        stage[i] = (p < end_row) ? *reinterpret_cast<const double2 *>(table + (size_t)p * APAP_TABLE_STRIDE + 2 * (q & 15))
+                                 : make_double2(0.0, 0.0);
+    }
+}
+// chunk_store is a macro: as a function - __forceinline__ or not, the buffer passed as a pointer, as an array or as (ring, index) -
+// it changed the address arithmetic of the stores inside the chunk loops of the nine MFMA kernels (2-3 instructions fewer, and
+// in k_assemble_mfma<4, false, false> another interleaving of the weight chains); expanded in place the loops are the ones the
+// kernels had when each spelt the staging out.  `buf` is the chunk buffer as the array it is (lds[b]).
+#define APAP_CHUNK_STORE(kThreads, buf, stage, tid)                                          \
+    do {                                                                                     \
+        _Pragma("unroll") for (int i_ = 0; i_ < kChunk * 16 / (kThreads); ++i_) {            \
+            const int q_ = (tid) + (kThreads) * i_;                                          \
+            const int r_ = q_ >> 4, slot_ = q_ & 15;                                         \
+            *reinterpret_cast<double2 *>(&(buf)[APAP_LDS_PIECE_OFF(r_, slot_)]) = (stage)[i_]; \
+        }                                                                                    \
+    } while (0)
+
+// w^2 of one cell (sample point v) for the keypoint whose coordinates sit at an LDS address: the float64 chain reads (x, y)
+// from columns 30, 31 of the keypoint's row, the float32 chain (kW32, 24-sum tables only) a float2 from column 29.
+//   inv_sigma2 = 2 / sigma^2, gamma2 = k1_gamma2(gamma, kW32)
+template <bool kW32>
+struct CellWeight {
+    static constexpr int kXyColumn = kW32 ? 29 : 30;
+    using Xy = std::conditional_t<kW32, float2, double2>;
+    double vx, vy, scaled_inv_sigma2, gamma2;
+    float vxf, vyf, neg_scale_f, gamma2f;
+    const double *exp2;     // the exp table in LDS
+    __device__ __forceinline__ void set(double2 v, double inv_sigma2, double gamma2_, const double *s_exp2) {
+        vx = v.x, vy = v.y;
+        scaled_inv_sigma2 = inv_sigma2 * kExpScale;
+        gamma2 = gamma2_;
+        vxf = (float)vx, vyf = (float)vy;
+        neg_scale_f = (float)(inv_sigma2 * -0x1.71547652b82fep+0), gamma2f = (float)gamma2;
+        exp2 = s_exp2;
+    }
+    static __device__ __forceinline__ Xy read(const unsigned char *at) { return *reinterpret_cast<const Xy *>(at); }
+    __device__ __forceinline__ double sq(Xy s) const {
+        if constexpr (kW32) return cell_weight_sq_f32(vxf, vyf, s, neg_scale_f, gamma2f);
+        else return cell_weight_sq_tab(vx, vy, s.x, s.y, scaled_inv_sigma2, gamma2, exp2);
+    }
+    __device__ __forceinline__ double sq(const unsigned char *at) const { return sq(read(at)); }
+};
+
+// The sums of 16 cells over the 32 (kM24: 24) table columns, and one step = 4 keypoints of them: the table entries b0 (columns
+// 0..15) and b1 from LDS, then two v_mfma_f64_16x16x4_f64 (acc0, acc1), or for 24 sums one and TWO v_mfma_f64_4x4x4_4b_f64
+// (columns 16..19 in acc_a and, 32 bytes on, 20..23 in acc_b), all fed by the same w^2 register.
+template <bool kM24>
+struct Sums16 {
+    double4_t acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+    double acc_a = 0.0, acc_b = 0.0;
+    __device__ __forceinline__ void step(double w2, const unsigned char *at0, const unsigned char *at1) {
+        const double b0 = *reinterpret_cast<const double *>(at0);
+        const double b1 = *reinterpret_cast<const double *>(at1);
+        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(w2, b0, acc0, 0, 0, 0);
+        if constexpr (kM24) {
+            acc_a = __builtin_amdgcn_mfma_f64_4x4x4f64(w2, b1, acc_a, 0, 0, 0);
+            acc_b = __builtin_amdgcn_mfma_f64_4x4x4f64(w2, *reinterpret_cast<const double *>(at1 + 32), acc_b, 0, 0, 0);
+        } else {
+            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(w2, b1, acc1, 0, 0, 0);
+        }
+    }
+};
+
+// D layout of v_mfma_f64_16x16x4_f64: register i of lane l is D[row = (l >> 4) + 4 i][col = l & 15],
+// row = cell within the wave's 16, col = moment index (acc0: 0..15, acc1: 16..31).
+__device__ __forceinline__ int d16_cell(int lane, int i) { return (lane >> 4) + 4 * i; }
+__device__ __forceinline__ int d16_column(int lane) { return lane & 15; }
+// D[b][i][j] of v_mfma_f64_4x4x4_4b_f64 sits in lane 16 i + 4 b + j: cell 4 b + i of the 16-cell group, column j of the
+// instruction's four (tools/mfma4_layout.hip).
+__device__ __forceinline__ int d4_cell(int lane) { return 4 * ((lane >> 2) & 3) + (lane >> 4); }
+__device__ __forceinline__ int d4_column(int lane) { return lane & 3; }
+
+// --------------------------------------------------------------------------------
 // K1 (VALU variant): lanes = cells, one wave per 64-cell tile and keypoint split (grid.y).
 // Per keypoint the 32 table doubles are wave-uniform: they arrive through the scalar
 // cache into SGPRs and feed v_fma_f64 as the scalar operand, so the vector unit only
@@ -283,8 +422,10 @@ __global__ __launch_bounds__(256) void k_assemble_valu(const double *__restrict_
                                                        int pts_per_split, double *__restrict__ moments,
                                                        BatchStride bs) {
     __shared__ double s_exp2[kExpN];
-    for (int j = threadIdx.x; j < kExpN; j += 256) s_exp2[j] = kExp2Tab[j];
+    exp_table_copy<256>(s_exp2, threadIdx.x);
     __syncthreads();
+    // The block's share, expanded in place: through K1Block the keypoint loop addresses the table row with immediates where it has
+    // adds (12 scalar instructions fewer per keypoint; 156.7 against 158.5 us at C3) - a speed change, not that refactor's to make.
     table += (long long)blockIdx.z * bs.table;
     vertices += (long long)blockIdx.z * bs.vertices;
     moments += (long long)blockIdx.z * bs.moments;
@@ -294,9 +435,8 @@ __global__ __launch_bounds__(256) void k_assemble_valu(const double *__restrict_
     // table row fetched through the scalar cache by one wave is a hit for the other three
     const int cell = (blockIdx.x * 4 + wave) * kWave + lane;
     if (cell - lane >= cells_pad) return;  // wave-uniform; no barrier below
-    const int cc = min(cell, cells - 1);
-    const double vx = vertices[2 * cc];
-    const double vy = vertices[2 * cc + 1];
+    const double2 v = cell_vertex(vertices, cell, cells);
+    const double vx = v.x, vy = v.y;
     const int p0 = min(n, (int)blockIdx.y * pts_per_split);
     const int p1 = min(n, p0 + pts_per_split);
     const double scaled_inv_sigma2 = inv_sigma2 * kExpScale;
@@ -346,18 +486,6 @@ __global__ __launch_bounds__(256) void k_assemble_valu(const double *__restrict_
 // A block is 4 waves = 64 cells sharing each 64-keypoint LDS chunk (16 KiB, double
 // buffered, register-staged so the next chunk's global loads fly during the MFMAs).
 // --------------------------------------------------------------------------------
-typedef double double4_t __attribute__((ext_vector_type(4)));
-// Keypoints per LDS buffer (16 KiB).  32 / 48 / 64 measured the same (196-200 us at C3): the
-// kernel is bound by the fp64 pipe, not by barriers or occupancy (VGPR + AGPR = 102 -> 4 waves
-// per SIMD; forcing <= 96 registers for 5-6 waves per SIMD changed nothing either).
-constexpr int kChunk = 64;
-static_assert(kChunk % 16 == 0 && kChunk % 4 == 0, "chunk must split evenly over 256 threads and 4-keypoint steps");
-
-// Byte offset of table entry (row r, column c) in an LDS chunk: 256-B rows; odd rows swap
-// their 128-B halves so that the two keypoint rows a 32-lane ds_read_b64 covers (lanes
-// 0-15 -> row r, 16-31 -> row r+1) fall on disjoint halves of the 64 banks.
-__device__ __forceinline__ int lds_off(int r, int c) { return r * 256 + ((c ^ ((r & 1) << 4)) << 3); }
-
 //
 // kM24 (APAP_OPT_MOMENTS = 24, opt-in): the table holds the 24 sums of the exact products (SURVEY.md section 8a:
 // A^T W^2 A = [[S0, 0, Sx], [0, S0, Sy], [Sx, Sy, Sr]], 6 unique entries each) in columns 0..23; per step ONE
@@ -371,87 +499,31 @@ __global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__r
                                                        int cells_pad, double gamma2, double inv_sigma2,
                                                        int pts_per_split, double *__restrict__ moments,
                                                        BatchStride bs) {
+    constexpr int kThreads = kWaves * 64;
     __shared__ __attribute__((aligned(16))) unsigned char lds[2][kChunk * 256];
-    table += (long long)blockIdx.z * bs.table;
-    vertices += (long long)blockIdx.z * bs.vertices;
+    const K1Block blk(table, vertices, bs, n, (int)blockIdx.y, pts_per_split);
     moments += (long long)blockIdx.z * bs.moments;
     __shared__ double s_exp2[kExpN];
-    // The exp table goes through registers and is written to LDS AFTER the first chunk's loads have been
-    // issued: `s_exp2[j] = kExp2Tab[j]` up here made the block wait out one global-memory latency before
-    // it even asked for its keypoints (two latencies in a row; it shows on small meshes).
-    static_assert(kExpN % (kWaves * 64) == 0 || (kWaves * 64) % kExpN == 0, "exp table vs block size");
-    constexpr int kExpPerThread = (kExpN + kWaves * 64 - 1) / (kWaves * 64);
-    double exp_stage[kExpPerThread];
-#pragma unroll
-    for (int i = 0; i < kExpPerThread; ++i) exp_stage[i] = kExp2Tab[(threadIdx.x + i * kWaves * 64) & (kExpN - 1)];
-    const double scaled_inv_sigma2 = inv_sigma2 * kExpScale;
     const int tid = threadIdx.x;
+    ExpTableStage<kThreads> exp_stage;      // register-staged (see there)
+    exp_stage.fetch(tid);
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int kgrp = lane >> 4;  // which of the step's 4 keypoints this lane weighs
     const int col = lane & 15;   // cell within the wave's 16 (A operand) / table column (B operand)
     const int cell = blockIdx.x * (16 * kWaves) + wave * 16 + col;
-    const int cc = min(cell, cells - 1);
-    const double vx = vertices[2 * cc];
-    const double vy = vertices[2 * cc + 1];
-    const float vxf = (float)vx, vyf = (float)vy;
-    const float neg_scale_f = (float)(inv_sigma2 * -0x1.71547652b82fep+0), gamma2f = (float)gamma2;
-    const int p_begin = min(n, (int)blockIdx.y * pts_per_split);
-    const int p_end = min(n, p_begin + pts_per_split);
-    const int nchunks = (p_end - p_begin + kChunk - 1) / kChunk;
+    CellWeight<kW32> weight;
+    weight.set(cell_vertex(vertices, cell, cells), inv_sigma2, gamma2, s_exp2);
+    const int p_begin = blk.p_begin, p_end = blk.p_end, nchunks = blk.nchunks;
 
-    // staging: thread t moves 16-byte pieces t, t+256, t+512, t+768 of a chunk;
-    // piece q = (row q >> 4, 16-byte slot q & 15)
-    constexpr int kThreads = kWaves * 64;
-    constexpr int kPieces = kChunk * 16 / kThreads;  // 16-byte pieces of a chunk per thread
-    double2 stage[kPieces];
-    auto load_chunk = [&](int c) {
-#pragma unroll
-        for (int i = 0; i < kPieces; ++i) {
-            const int q = tid + kThreads * i;
-            const int p = p_begin + c * kChunk + (q >> 4);
-            stage[i] = (p < p_end) ? *reinterpret_cast<const double2 *>(table + (size_t)p * APAP_TABLE_STRIDE + 2 * (q & 15))
-                                   : make_double2(0.0, 0.0);  // zero rows add nothing whatever their weight
-        }
-    };
-    auto store_chunk = [&](int b) {
-#pragma unroll
-        for (int i = 0; i < kPieces; ++i) {
-            const int q = tid + kThreads * i;
-            const int r = q >> 4;
-            const int slot = (q & 15) ^ ((r & 1) << 3);
-            *reinterpret_cast<double2 *>(&lds[b][r * 256 + slot * 16]) = stage[i];
-        }
-    };
-
-    const int off_xy = kW32 ? lds_off(kgrp, 29) : lds_off(kgrp, 30), off_b0 = lds_off(kgrp, col);
+    ChunkStage<kThreads> stage;
+    const int off_xy = lds_off(kgrp, CellWeight<kW32>::kXyColumn), off_b0 = lds_off(kgrp, col);
     // second operand: columns 16..31 (30 sums), or columns 16 + (lane & 3) and, 32 bytes on, 20 + (lane & 3) (24 sums)
     const int off_b1 = lds_off(kgrp, 16 + (kM24 ? (lane & 3) : col));
-    double4_t acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-    double acc_a = 0.0, acc_b = 0.0;
-    auto weight = [&](const unsigned char *at) -> double {
-        if constexpr (kW32) {
-            return cell_weight_sq_f32(vxf, vyf, *reinterpret_cast<const float2 *>(at), neg_scale_f, gamma2f);
-        } else {
-            const double2 xy = *reinterpret_cast<const double2 *>(at);
-            return cell_weight_sq_tab(vx, vy, xy.x, xy.y, scaled_inv_sigma2, gamma2, s_exp2);
-        }
-    };
-    auto accumulate = [&](double w2, const unsigned char *at0, const unsigned char *at1) {
-        const double b0 = *reinterpret_cast<const double *>(at0);
-        const double b1 = *reinterpret_cast<const double *>(at1);
-        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(w2, b0, acc0, 0, 0, 0);
-        if constexpr (kM24) {
-            acc_a = __builtin_amdgcn_mfma_f64_4x4x4f64(w2, b1, acc_a, 0, 0, 0);
-            acc_b = __builtin_amdgcn_mfma_f64_4x4x4f64(w2, *reinterpret_cast<const double *>(at1 + 32), acc_b, 0, 0, 0);
-        } else {
-            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(w2, b1, acc1, 0, 0, 0);
-        }
-    };
-    if (nchunks > 0) load_chunk(0);
-#pragma unroll
-    for (int i = 0; i < kExpPerThread; ++i) s_exp2[(tid + i * kThreads) & (kExpN - 1)] = exp_stage[i];  // visible after the barrier
-    if (nchunks > 0) store_chunk(0);
+    Sums16<kM24> sums;
+    if (nchunks > 0) chunk_load<kThreads>(stage, table, tid, p_begin, p_end);
+    exp_stage.publish(s_exp2, tid);  // visible after the barrier
+    if (nchunks > 0) APAP_CHUNK_STORE(kThreads, lds[0], stage, tid);
     __syncthreads();
     // Drain the prologue's loads (vertex, first chunk) here: otherwise the compiler's wait
     // for the vertex registers lands inside the step loop as vmcnt(0) and also waits for
@@ -466,7 +538,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__r
     // chunk, two 68 KB blocks per CU.  profiles/r06_k1_compiler.txt.)
     const int nfull = (p_end - p_begin) / kChunk;
     for (int c = 0; c < nfull; ++c) {
-        if (c + 1 < nchunks) load_chunk(c + 1);
+        if (c + 1 < nchunks) chunk_load<kThreads>(stage, table, tid, p_begin + (c + 1) * kChunk, p_end);
         const unsigned char *buf = lds[c & 1];
         // The weights of g steps first, then their 2 g MFMAs back to back: g times fewer MFMA <-> VALU
         // transitions (~10 issue cycles each, profiles/r02_coexec.txt) and g independent weight chains
@@ -478,43 +550,40 @@ __global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__r
         for (int s0 = 0; s0 < kChunk / 4; s0 += 8) {
             double w2[8];
 #pragma unroll
-            for (int g = 0; g < 8; ++g) w2[g] = weight(buf + off_xy + 1024 * (s0 + g));
+            for (int g = 0; g < 8; ++g) w2[g] = weight.sq(buf + off_xy + 1024 * (s0 + g));
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int g = 0; g < 8; ++g) accumulate(w2[g], buf + off_b0 + 1024 * (s0 + g), buf + off_b1 + 1024 * (s0 + g));
+            for (int g = 0; g < 8; ++g) sums.step(w2[g], buf + off_b0 + 1024 * (s0 + g), buf + off_b1 + 1024 * (s0 + g));
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (c + 1 < nchunks) store_chunk((c + 1) & 1);
+        if (c + 1 < nchunks) APAP_CHUNK_STORE(kThreads, lds[(c + 1) & 1], stage, tid);
         __syncthreads();
     }
     if (nfull < nchunks) {      // the partial last chunk (staged and published by the loop's last pass, or by the prologue)
         const unsigned char *buf = lds[nfull & 1];
         const int steps_here = (p_end - p_begin - nfull * kChunk + 3) >> 2;
         for (int s1 = 0; s1 < steps_here; ++s1)
-            accumulate(weight(buf + off_xy + 1024 * s1), buf + off_b0 + 1024 * s1, buf + off_b1 + 1024 * s1);
+            sums.step(weight.sq(buf + off_xy + 1024 * s1), buf + off_b0 + 1024 * s1, buf + off_b1 + 1024 * s1);
     }
 
-    // D layout of v_mfma_f64_16x16x4_f64: register i of lane l is D[row = (l >> 4) + 4 i][col = l & 15],
-    // row = cell within the wave's 16, col = moment index (acc0: 0..15, acc1: 16..31).
     constexpr int kSums = kM24 ? 24 : kMoments;
     double *slab = moments + (size_t)blockIdx.y * kSums * cells_pad;
-    const int cell_base = blockIdx.x * (16 * kWaves) + wave * 16 + kgrp;
+    const int cell_base = blockIdx.x * (16 * kWaves) + wave * 16;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int ci = cell_base + 4 * i;
+    for (int i = 0; i < 4; ++i) {       // the 16x16x4 D registers (d16_cell, d16_column)
+        const int ci = cell_base + d16_cell(lane, i);
         if (ci < cells_pad) {  // an 8-wave block may overhang the padded cell count
             // (plain stores: non-temporal ones were measured - K1 150.0 -> 148.7 us, but the 128-byte pieces of a moment row no
             // longer merge in the L2 and WRITE_SIZE grows from 18.8 to 34.1 MB per launch, profiles/r05_solve_experiments.txt)
-            slab[(size_t)col * cells_pad + ci] = acc0[i];
-            if (!kM24 && col < kMoments - 16) slab[(size_t)(16 + col) * cells_pad + ci] = acc1[i];
+            slab[(size_t)d16_column(lane) * cells_pad + ci] = sums.acc0[i];
+            if (!kM24 && d16_column(lane) < kMoments - 16) slab[(size_t)(16 + d16_column(lane)) * cells_pad + ci] = sums.acc1[i];
         }
     }
-    if constexpr (kM24) {
-        // D[b][i][j] of v_mfma_f64_4x4x4_4b_f64 sits in lane 16 i + 4 b + j: cell 4 b + i of the wave's 16, column 16 + j / 20 + j
-        const int ci = blockIdx.x * (16 * kWaves) + wave * 16 + 4 * ((lane >> 2) & 3) + (lane >> 4);
+    if constexpr (kM24) {       // the 4x4x4_4b D registers (d4_cell, d4_column): columns 16 + j and 20 + j
+        const int ci = cell_base + d4_cell(lane);
         if (ci < cells_pad) {
-            slab[(size_t)(16 + (lane & 3)) * cells_pad + ci] = acc_a;
-            slab[(size_t)(20 + (lane & 3)) * cells_pad + ci] = acc_b;
+            slab[(size_t)(16 + d4_column(lane)) * cells_pad + ci] = sums.acc_a;
+            slab[(size_t)(20 + d4_column(lane)) * cells_pad + ci] = sums.acc_b;
         }
     }
 }
@@ -542,55 +611,23 @@ __global__ __launch_bounds__(256) void k_assemble_mfma4(const double *__restrict
                                                         int pts_per_split, double *__restrict__ moments,
                                                         BatchStride bs) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2][kChunk * 256];
-    table += (long long)blockIdx.z * bs.table;
-    vertices += (long long)blockIdx.z * bs.vertices;
+    const K1Block blk(table, vertices, bs, n, (int)blockIdx.y, pts_per_split);
     moments += (long long)blockIdx.z * bs.moments;
     __shared__ double s_exp2[kExpN];
-    for (int j = threadIdx.x; j < kExpN; j += 256) s_exp2[j] = kExp2Tab[j];  // visible after the first barrier
-    const double scaled_inv_sigma2 = inv_sigma2 * kExpScale;
+    exp_table_copy<256>(s_exp2, threadIdx.x);  // direct; visible after the first barrier
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int kgrp = lane >> 4;  // which of the step's 4 keypoints this lane weighs / reads B for
     const int col = lane & 15;   // cell within a 16-cell group (A operand)
     const int cell0 = (blockIdx.x * 4 + wave) * (16 * kGroups);
-    double vx[kGroups], vy[kGroups];
-    float vxf[kGroups], vyf[kGroups];
+    CellWeight<kW32> weight[kGroups];
 #pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
-        const int cc = min(cell0 + 16 * g + col, cells - 1);
-        vx[g] = vertices[2 * cc];
-        vy[g] = vertices[2 * cc + 1];
-        vxf[g] = (float)vx[g];
-        vyf[g] = (float)vy[g];
-    }
-    const float neg_scale_f = (float)(inv_sigma2 * -0x1.71547652b82fep+0), gamma2f = (float)gamma2;
-    const int p_begin = min(n, (int)blockIdx.y * pts_per_split);
-    const int p_end = min(n, p_begin + pts_per_split);
-    const int nchunks = (p_end - p_begin + kChunk - 1) / kChunk;
+    for (int g = 0; g < kGroups; ++g) weight[g].set(cell_vertex(vertices, cell0 + 16 * g + col, cells), inv_sigma2, gamma2, s_exp2);
+    const int p_begin = blk.p_begin, p_end = blk.p_end, nchunks = blk.nchunks;
 
-    constexpr int kPieces = kChunk * 16 / 256;  // 16-byte pieces of a chunk per thread
-    double2 stage[kPieces];
-    auto load_chunk = [&](int c) {
-#pragma unroll
-        for (int i = 0; i < kPieces; ++i) {
-            const int q = tid + 256 * i;
-            const int p = p_begin + c * kChunk + (q >> 4);
-            stage[i] = (p < p_end) ? *reinterpret_cast<const double2 *>(table + (size_t)p * APAP_TABLE_STRIDE + 2 * (q & 15))
-                                   : make_double2(0.0, 0.0);
-        }
-    };
-    auto store_chunk = [&](int b) {
-#pragma unroll
-        for (int i = 0; i < kPieces; ++i) {
-            const int q = tid + 256 * i;
-            const int r = q >> 4;
-            const int slot = (q & 15) ^ ((r & 1) << 3);
-            *reinterpret_cast<double2 *>(&lds[b][r * 256 + slot * 16]) = stage[i];
-        }
-    };
-
-    const int off_xy = kW32 ? lds_off(kgrp, 29) : lds_off(kgrp, 30);
+    ChunkStage<256> stage;
+    const int off_xy = lds_off(kgrp, CellWeight<kW32>::kXyColumn);
     // column 4 m + j of row kgrp: the swizzle only flips bit 4 of the column, so two per-lane bases
     // (columns 0-15 and 16-31) plus the immediate 32 (m & 3)
     const int off_lo = lds_off(kgrp, lane & 3), off_hi = lds_off(kgrp, 16 + (lane & 3));
@@ -600,13 +637,13 @@ __global__ __launch_bounds__(256) void k_assemble_mfma4(const double *__restrict
 #pragma unroll
         for (int m = 0; m < kQuads; ++m) acc[g][m] = 0.0;
     if (nchunks > 0) {
-        load_chunk(0);
-        store_chunk(0);
+        chunk_load<256>(stage, table, tid, p_begin, p_end);
+        APAP_CHUNK_STORE(256, lds[0], stage, tid);
     }
     __syncthreads();
     __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0): see k_assemble_mfma
     for (int c = 0; c < nchunks; ++c) {
-        if (c + 1 < nchunks) load_chunk(c + 1);
+        if (c + 1 < nchunks) chunk_load<256>(stage, table, tid, p_begin + (c + 1) * kChunk, p_end);
         const unsigned char *buf = lds[c & 1];
 #pragma unroll
         for (int s = 0; s < kChunk / 4; ++s) {
@@ -615,30 +652,23 @@ __global__ __launch_bounds__(256) void k_assemble_mfma4(const double *__restrict
             for (int m = 0; m < kQuads; ++m)
                 bv[m] = *reinterpret_cast<const double *>(buf + (m < 4 ? off_lo : off_hi) + 32 * (m & 3) + 1024 * s);
             double w2[kGroups];
-            if constexpr (kW32) {
-                const float2 xyf = *reinterpret_cast<const float2 *>(buf + off_xy + 1024 * s);
+            const auto xy = CellWeight<kW32>::read(buf + off_xy + 1024 * s);    // one read for the wave's groups
 #pragma unroll
-                for (int g = 0; g < kGroups; ++g) w2[g] = cell_weight_sq_f32(vxf[g], vyf[g], xyf, neg_scale_f, gamma2f);
-            } else {
-                const double2 xy = *reinterpret_cast<const double2 *>(buf + off_xy + 1024 * s);
-#pragma unroll
-                for (int g = 0; g < kGroups; ++g)
-                    w2[g] = cell_weight_sq_tab(vx[g], vy[g], xy.x, xy.y, scaled_inv_sigma2, gamma2, s_exp2);
-            }
+            for (int g = 0; g < kGroups; ++g) w2[g] = weight[g].sq(xy);
 #pragma unroll
             for (int m = 0; m < kQuads; ++m)
 #pragma unroll
                 for (int g = 0; g < kGroups; ++g)
                     acc[g][m] = __builtin_amdgcn_mfma_f64_4x4x4f64(w2[g], bv[m], acc[g][m], 0, 0, 0);
         }
-        if (c + 1 < nchunks) store_chunk((c + 1) & 1);
+        if (c + 1 < nchunks) APAP_CHUNK_STORE(256, lds[(c + 1) & 1], stage, tid);
         __syncthreads();
     }
-    // D[b][i][j] sits in lane 16 i + 4 b + j: cell 4 b + i of the group, table column 4 m + j
+    // the 4x4x4_4b D registers (d4_cell, d4_column): table column 4 m + j
     constexpr int kSums = kQuads == 6 ? 24 : kMoments;
     double *slab = moments + (size_t)blockIdx.y * kSums * cells_pad;
-    const int dcell = 4 * ((lane >> 2) & 3) + (lane >> 4);
-    const int dj = lane & 3;
+    const int dcell = d4_cell(lane);
+    const int dj = d4_column(lane);
 #pragma unroll
     for (int g = 0; g < kGroups; ++g) {
         const int ci = cell0 + 16 * g + dcell;
@@ -1215,9 +1245,33 @@ __device__ __forceinline__ void eigen_denorm_cell(const double (&m)[kMoments], c
     }
 }
 
+// The 30 entries the tail works on from the 24 sums S0, Sx, Sy, Sr of K1's 24-sum form (6 each, upper triangle of a 3 x 3 by
+// rows): S0 and Sr as they are, Sx and Sy written out as full 3 x 3 blocks.
+__device__ __forceinline__ void moments_from_24(const double (&t)[24], double (&m)[kMoments]) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        m[j] = t[j];
+        m[24 + j] = t[18 + j];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int u = i <= j ? i * (5 - i) / 2 + j : j * (5 - j) / 2 + i;   // (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
+            m[6 + 3 * i + j] = t[6 + u];
+            m[15 + 3 * i + j] = t[12 + u];
+        }
+}
+
+// The caller's table has the other layout than the kernel reads (table_is_24): nothing computed from it is an answer, and
+// the cell's homography is NaN.
+__device__ __forceinline__ void refuse_table_layout(float *out) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) out[k] = __builtin_nanf("");
+}
+
 // K2.  kUseInverseIteration = false is the pure-Jacobi kernel (APAP_EIGEN_JACOBI).
-// kM24: the slabs hold the 24 sums S0, Sx, Sy, Sr (6 each, upper triangle of a 3 x 3 by rows) of K1's 24-sum form; the 30
-// entries the tail works on are those with Sx and Sy written out as full 3 x 3 blocks.
+// kM24: the slabs hold the 24 sums of K1's 24-sum form (moments_from_24).
 template <bool kUseInverseIteration, bool kM24>
 __global__ __launch_bounds__(64) void k_eigen_denorm(const double *__restrict__ moments, int splits,
                                                      int cells, int cells_pad,
@@ -1246,19 +1300,7 @@ __global__ __launch_bounds__(64) void k_eigen_denorm(const double *__restrict__ 
     }
     double m[kMoments];
     if constexpr (kM24) {
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            m[j] = t[j];
-            m[24 + j] = t[18 + j];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int u = i <= j ? i * (5 - i) / 2 + j : j * (5 - j) / 2 + i;   // (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
-                m[6 + 3 * i + j] = t[6 + u];
-                m[15 + 3 * i + j] = t[12 + u];
-            }
+        moments_from_24(t, m);
     } else {
 #pragma unroll
         for (int j = 0; j < kMoments; ++j) m[j] = t[j];
@@ -1266,10 +1308,7 @@ __global__ __launch_bounds__(64) void k_eigen_denorm(const double *__restrict__ 
     float *out = cell < cells ? H + (size_t)cell * 9 : nullptr;
     eigen_denorm_cell<kUseInverseIteration>(m, denorm, pick_rank, careful, table, n, vertices[2 * cc], vertices[2 * cc + 1],
                                             gamma, inv_sigma, out, we, (int)blockIdx.z, cell, edges, kM24, trace_floor);
-    if (!layout_ok && out) {      // the caller's table has the other layout (wave-uniform): nothing computed from it is an answer
-#pragma unroll
-        for (int k = 0; k < 9; ++k) out[k] = __builtin_nanf("");
-    }
+    if (!layout_ok && out) refuse_table_layout(out);      // (wave-uniform)
 }
 
 // --------------------------------------------------------------------------------
@@ -1296,61 +1335,38 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(const double *__r
     constexpr int kRing = 4;
     __shared__ __attribute__((aligned(16))) unsigned char lds[kRing][kChunk * 256];
     __shared__ double s_exp2[kExpN];
-    table += (long long)blockIdx.z * bs.table;
-    vertices += (long long)blockIdx.z * bs.vertices;
+    const K1Block blk(table, vertices, bs, n, 0, n);   // every keypoint: no grid-level split here
     denorm += (long long)blockIdx.z * bs.denorm;
     H += (long long)blockIdx.z * bs.H;
     const int tid = threadIdx.x;
-    constexpr int kExpPerThread = kExpN / kSmallThreads;
-    double exp_stage[kExpPerThread];   // to LDS after the first round's loads are issued
-#pragma unroll
-    for (int i = 0; i < kExpPerThread; ++i) exp_stage[i] = kExp2Tab[tid + i * kSmallThreads];
+    ExpTableStage<kSmallThreads> exp_stage;   // register-staged: to LDS after the first round's loads are issued
+    exp_stage.fetch(tid);
     // the four de-normalisation matrices too: the tail would otherwise wait for them (cold scalar loads) at its very end
     __shared__ double s_denorm[APAP_DENORM_DOUBLES];
     const double den_stage = denorm[min(tid, APAP_DENORM_DOUBLES - 1)];
-    static_assert(kExpN % kSmallThreads == 0, "exp table entries per thread");
-    const double gamma2 = k1_gamma2(gamma, false);
-    const double scaled_inv_sigma2 = 2.0 * inv_sigma * kExpScale;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kgrp = lane >> 4, col = lane & 15;
     const int cell = blockIdx.x * 16 + col;
-    const int cc = min(cell, cells - 1);
-    const double vx = vertices[2 * cc], vy = vertices[2 * cc + 1];
-    const int nchunks = (n + kChunk - 1) / kChunk;
+    const double2 v = cell_vertex(vertices, cell, cells);
+    CellWeight<false> weight;
+    weight.set(v, 2.0 * inv_sigma, k1_gamma2(gamma, false), s_exp2);
+    const int nchunks = blk.nchunks;
     const int nrounds = (nchunks + kRing - 1) / kRing;
 
-    constexpr int kPieces = kChunk * 16 / kSmallThreads;
-    double2 stage[kRing][kPieces];
+    ChunkStage<kSmallThreads> stage[kRing];
     auto load_round = [&](int r) {
 #pragma unroll
-        for (int b = 0; b < kRing; ++b) {
-#pragma unroll
-            for (int i = 0; i < kPieces; ++i) {
-                const int q = tid + kSmallThreads * i;
-                const int p = (r * kRing + b) * kChunk + (q >> 4);
-                stage[b][i] = (p < n) ? *reinterpret_cast<const double2 *>(table + (size_t)p * APAP_TABLE_STRIDE + 2 * (q & 15))
-                                      : make_double2(0.0, 0.0);  // zero rows add nothing whatever their weight
-            }
-        }
+        for (int b = 0; b < kRing; ++b) chunk_load<kSmallThreads>(stage[b], table, tid, (r * kRing + b) * kChunk, n);
     };
     auto store_round = [&]() {
 #pragma unroll
-        for (int b = 0; b < kRing; ++b) {
-#pragma unroll
-            for (int i = 0; i < kPieces; ++i) {
-                const int q = tid + kSmallThreads * i;
-                const int r = q >> 4;
-                const int slot = (q & 15) ^ ((r & 1) << 3);
-                *reinterpret_cast<double2 *>(&lds[b][r * 256 + slot * 16]) = stage[b][i];
-            }
-        }
+        for (int b = 0; b < kRing; ++b) APAP_CHUNK_STORE(kSmallThreads, lds[b], stage[b], tid);
     };
-    const int off_xy = lds_off(kgrp, 30), off_b0 = lds_off(kgrp, col), off_b1 = lds_off(kgrp, 16 + col);
-    double4_t acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+    const int off_xy = lds_off(kgrp, CellWeight<false>::kXyColumn), off_b0 = lds_off(kgrp, col), off_b1 = lds_off(kgrp, 16 + col);
+    Sums16<false> sums;
     load_round(0);
-#pragma unroll
-    for (int i = 0; i < kExpPerThread; ++i) s_exp2[tid + i * kSmallThreads] = exp_stage[i];
+    exp_stage.publish(s_exp2, tid);
     if (tid < APAP_DENORM_DOUBLES) s_denorm[tid] = den_stage;
     store_round();
     __syncthreads();
@@ -1362,31 +1378,19 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(const double *__r
             // only the steps that hold keypoints (see k_assemble_mfma): C1's 150 keypoints are 2 chunks and 6 steps
             const int steps_here = min(kChunk / 4, (n - (r * kRing + b) * kChunk + 3) >> 2);
             if (steps_here < kChunk / 4) {
-                for (int i = 0; wave + kSmallWaves * i < steps_here; ++i) {
-                    const double2 xy = *reinterpret_cast<const double2 *>(buf + off_xy + 1024 * kSmallWaves * i);
-                    const double b0 = *reinterpret_cast<const double *>(buf + off_b0 + 1024 * kSmallWaves * i);
-                    const double b1 = *reinterpret_cast<const double *>(buf + off_b1 + 1024 * kSmallWaves * i);
-                    const double w2s = cell_weight_sq_tab(vx, vy, xy.x, xy.y, scaled_inv_sigma2, gamma2, s_exp2);
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(w2s, b0, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(w2s, b1, acc1, 0, 0, 0);
-                }
+                for (int i = 0; wave + kSmallWaves * i < steps_here; ++i)
+                    sums.step(weight.sq(buf + off_xy + 1024 * kSmallWaves * i), buf + off_b0 + 1024 * kSmallWaves * i,
+                              buf + off_b1 + 1024 * kSmallWaves * i);
                 continue;
             }
             constexpr int kMine = kChunk / 4 / kSmallWaves;
             double w2[kMine];  // this wave's steps: wave, wave + kSmallWaves, ...; weights first (see k_assemble_mfma)
 #pragma unroll
-            for (int i = 0; i < kMine; ++i) {
-                const double2 xy = *reinterpret_cast<const double2 *>(buf + off_xy + 1024 * kSmallWaves * i);
-                w2[i] = cell_weight_sq_tab(vx, vy, xy.x, xy.y, scaled_inv_sigma2, gamma2, s_exp2);
-            }
+            for (int i = 0; i < kMine; ++i) w2[i] = weight.sq(buf + off_xy + 1024 * kSmallWaves * i);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < kMine; ++i) {
-                const double b0 = *reinterpret_cast<const double *>(buf + off_b0 + 1024 * kSmallWaves * i);
-                const double b1 = *reinterpret_cast<const double *>(buf + off_b1 + 1024 * kSmallWaves * i);
-                acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(w2[i], b0, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(w2[i], b1, acc1, 0, 0, 0);
-            }
+            for (int i = 0; i < kMine; ++i)
+                sums.step(w2[i], buf + off_b0 + 1024 * kSmallWaves * i, buf + off_b1 + 1024 * kSmallWaves * i);
             __builtin_amdgcn_sched_barrier(0);
         }
         __syncthreads();                                    // every wave is done reading the ring
@@ -1399,16 +1403,15 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(const double *__r
     // to 33 doubles so that both "32 moments of a cell" and "one moment of 16 cells" are conflict-free (with 32, the
     // tail's 16 lanes read 256 B apart: one bank, 16 turns per read).  All threads add the waves' partial sums (in
     // wave order: the same sums whoever adds them); the tail only picks up its cell's 30 totals.
-    // D layout: register i of lane l is D[row = (l >> 4) + 4 i][col = l & 15] = (cell, moment)
     constexpr int kRow = 33;
     double *part = reinterpret_cast<double *>(&lds[0][0]);
     double *tot = part + kSmallWaves * 16 * kRow;
     static_assert((kSmallWaves + 1) * 16 * kRow * sizeof(double) <= sizeof(lds), "reduction buffers fit the chunk ring");
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int ci = kgrp + 4 * i;
-        part[(wave * 16 + ci) * kRow + col] = acc0[i];
-        part[(wave * 16 + ci) * kRow + 16 + col] = acc1[i];
+    for (int i = 0; i < 4; ++i) {       // the 16x16x4 D registers (d16_cell, d16_column) = (cell, moment)
+        const int ci = d16_cell(lane, i);
+        part[(wave * 16 + ci) * kRow + d16_column(lane)] = sums.acc0[i];
+        part[(wave * 16 + ci) * kRow + 16 + d16_column(lane)] = sums.acc1[i];
     }
     __syncthreads();
 #pragma unroll
@@ -1425,12 +1428,10 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(const double *__r
 #pragma unroll
     for (int j = 0; j < kMoments; ++j) m[j] = tot[lane * kRow + j];
     const CellEdges edges = warp_emit_prefetch(we, cell < cells ? cell : -1);
-    eigen_denorm_cell<kUseInverseIteration>(m, s_denorm, pick_rank, careful, table, n, vx, vy, gamma, inv_sigma,
-                                            cell < cells ? H + (size_t)cell * 9 : nullptr, we, (int)blockIdx.z, cell, edges);
-    if (table_is_24(table) && cell < cells) {   // a 24-sum table: this kernel reads the 30-sum layout
-#pragma unroll
-        for (int k = 0; k < 9; ++k) H[(size_t)cell * 9 + k] = __builtin_nanf("");
-    }
+    float *out = cell < cells ? H + (size_t)cell * 9 : nullptr;
+    eigen_denorm_cell<kUseInverseIteration>(m, s_denorm, pick_rank, careful, table, n, v.x, v.y, gamma, inv_sigma, out, we,
+                                            (int)blockIdx.z, cell, edges);
+    if (table_is_24(table) && out) refuse_table_layout(out);   // a 24-sum table: this kernel reads the 30-sum layout
 }
 
 // --------------------------------------------------------------------------------
@@ -2487,37 +2488,35 @@ static int solve_batch_impl(apap_ctx *ctx, const double *d_tables, int n, const 
     }
     {
         ProfScope prof(ctx, APAP_PROF_ASSEMBLE, s);
-        const dim3 grid(p.cell_tiles, p.splits, batch);
-        // 4 waves (64 cells) per block measured best: 2 -> 224 us, 4 -> 201 us, 8 -> 227 us at C3
-#define APAP_K1_ARGS d_tables, n, d_vertices, cells, p.cells_pad, gamma2, inv_sigma2, p.pts_per_split, moments, bs
-        const dim3 grid2((p.cell_tiles + 1) / 2, p.splits, batch);   // two 64-cell tiles per block
-        if (p.variant == APAP_VARIANT_MFMA) {
-            if (!m24) hipLaunchKernelGGL((k_assemble_mfma<4, false, false>), grid, dim3(256), 0, s, APAP_K1_ARGS);
-            else if (!w32) hipLaunchKernelGGL((k_assemble_mfma<4, true, false>), grid, dim3(256), 0, s, APAP_K1_ARGS);
-            else hipLaunchKernelGGL((k_assemble_mfma<4, true, true>), grid, dim3(256), 0, s, APAP_K1_ARGS);
-        } else if (p.variant == APAP_VARIANT_MFMA4) {
-            if (!m24) hipLaunchKernelGGL((k_assemble_mfma4<1, 8, false>), grid, dim3(256), 0, s, APAP_K1_ARGS);
-            else if (!w32) hipLaunchKernelGGL((k_assemble_mfma4<1, 6, false>), grid, dim3(256), 0, s, APAP_K1_ARGS);
-            else hipLaunchKernelGGL((k_assemble_mfma4<1, 6, true>), grid, dim3(256), 0, s, APAP_K1_ARGS);
-        } else if (p.variant == APAP_VARIANT_MFMA4X2) {
-            if (!m24) hipLaunchKernelGGL((k_assemble_mfma4<2, 8, false>), grid2, dim3(256), 0, s, APAP_K1_ARGS);
-            else if (!w32) hipLaunchKernelGGL((k_assemble_mfma4<2, 6, false>), grid2, dim3(256), 0, s, APAP_K1_ARGS);
-            else hipLaunchKernelGGL((k_assemble_mfma4<2, 6, true>), grid2, dim3(256), 0, s, APAP_K1_ARGS);
-        } else {
-            hipLaunchKernelGGL(k_assemble_valu, dim3((p.cell_tiles + 3) / 4, p.splits, batch), dim3(256), 0, s, APAP_K1_ARGS);
-        }
-#undef APAP_K1_ARGS
+        // K1's forms by (variant, table and weight chain), and how many 64-cell tiles a block of each takes
+        // (k_assemble_mfma: 4 waves (64 cells) per block measured best: 2 -> 224 us, 4 -> 201 us, 8 -> 227 us at C3).
+        using K1 = void (*)(const double *, int, const double *, int, int, double, double, int, double *, BatchStride);
+        static const struct {
+            K1 form[3];         // 30 sums / 24 sums / 24 sums with float32 weights
+            int tiles;
+        } k1[] = {
+            {{k_assemble_valu, nullptr, nullptr}, 4},      // one tile per wave; no 24-sum form (refused above)
+            {{k_assemble_mfma<4, false, false>, k_assemble_mfma<4, true, false>, k_assemble_mfma<4, true, true>}, 1},
+            {{k_assemble_mfma4<1, 8, false>, k_assemble_mfma4<1, 6, false>, k_assemble_mfma4<1, 6, true>}, 1},
+            {{k_assemble_mfma4<2, 8, false>, k_assemble_mfma4<2, 6, false>, k_assemble_mfma4<2, 6, true>}, 2},
+        };
+        static_assert(APAP_VARIANT_MFMA == APAP_VARIANT_VALU + 1 && APAP_VARIANT_MFMA4 == APAP_VARIANT_VALU + 2 &&
+                      APAP_VARIANT_MFMA4X2 == APAP_VARIANT_VALU + 3, "k1[] is indexed by the variant");
+        const auto &k = k1[p.variant >= APAP_VARIANT_MFMA && p.variant <= APAP_VARIANT_MFMA4X2 ? p.variant - APAP_VARIANT_VALU : 0];
+        const dim3 grid((p.cell_tiles + k.tiles - 1) / k.tiles, p.splits, batch);
+        hipLaunchKernelGGL(k.form[!m24 ? 0 : !w32 ? 1 : 2], grid, dim3(256), 0, s, d_tables, n, d_vertices, cells, p.cells_pad, gamma2,
+                           inv_sigma2, p.pts_per_split, moments, bs);
     }
     {
         ProfScope prof(ctx, APAP_PROF_EIGEN, s);
         const dim3 grid(p.cell_tiles, 1, batch);
-#define APAP_K2_ARGS moments, p.splits, cells, p.cells_pad, d_denorms, pick_rank, d_H, bs, d_tables, n, d_vertices, gamma, inv_sigma, careful, trace_floor, we
+        using K2 = void (*)(const double *, int, int, int, const double *, int, float *, BatchStride, const double *, int, const double *,
+                            double, double, int, double, const WarpEmit);
+        static const K2 k2[2][2] = {{k_eigen_denorm<true, false>, k_eigen_denorm<true, true>},       // [Jacobi][24 sums]
+                                    {k_eigen_denorm<false, false>, k_eigen_denorm<false, true>}};
         const bool jacobi = apap::opt(ctx, APAP_OPT_EIGEN_SOLVER) == APAP_EIGEN_JACOBI;
-        if (jacobi && m24) hipLaunchKernelGGL((k_eigen_denorm<false, true>), grid, dim3(64), 0, s, APAP_K2_ARGS);
-        else if (jacobi) hipLaunchKernelGGL((k_eigen_denorm<false, false>), grid, dim3(64), 0, s, APAP_K2_ARGS);
-        else if (m24) hipLaunchKernelGGL((k_eigen_denorm<true, true>), grid, dim3(64), 0, s, APAP_K2_ARGS);
-        else hipLaunchKernelGGL((k_eigen_denorm<true, false>), grid, dim3(64), 0, s, APAP_K2_ARGS);
-#undef APAP_K2_ARGS
+        hipLaunchKernelGGL(k2[jacobi][m24], grid, dim3(64), 0, s, moments, p.splits, cells, p.cells_pad, d_denorms, pick_rank, d_H, bs,
+                           d_tables, n, d_vertices, gamma, inv_sigma, careful, trace_floor, we);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "apap_solve_device launch");
