@@ -399,7 +399,50 @@ struct Sums16 {
             acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(w2, b1, acc1, 0, 0, 0);
         }
     }
+    // The same step with the table entries in hand (b1b: the entry 32 bytes after b1, read by the 24-sum form only): for a wave
+    // that carries two 16-cell groups and reads each step's entries once for both.
+    __device__ __forceinline__ void step(double w2, double b0, double b1, double b1b) {
+        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(w2, b0, acc0, 0, 0, 0);
+        if constexpr (kM24) {
+            acc_a = __builtin_amdgcn_mfma_f64_4x4x4f64(w2, b1, acc_a, 0, 0, 0);
+            acc_b = __builtin_amdgcn_mfma_f64_4x4x4f64(w2, b1b, acc_b, 0, 0, 0);
+        } else {
+            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(w2, b1, acc1, 0, 0, 0);
+        }
+    }
 };
+
+// Paired launch of k_assemble_mfma (plan_pairs on the host): a 1-D grid in which the first `pairs` blocks own TWO tiles
+// (2 j, 2 j + 1) of one keypoint split and the rest one tile each, so that a launch of more (tile, split) units than the chip
+// holds blocks, but fewer than twice as many, is resident from its start.  Paired block i is pair i / splits of split
+// i % splits (the pairs are spread evenly over the splits); the single blocks follow split by split, each split's unpaired
+// tiles in order.  pairs = 0: the 3-D grid (blockIdx.x = tile, .y = split, .z = pair of a batch).
+// Why the FIRST ids: block i goes to XCD i % 8, and every run of 256 consecutive ids lands on 256 different CUs (recorded
+// per block from HW_REG_HW_ID / HW_REG_XCC_ID, profiles/k1_paired_tiles.txt), so up to 256 paired blocks sit on different CUs
+// (more of them spread evenly, layer by layer); and a SIMD issues from its oldest wave first, so the paired wave runs ahead and the three
+// single waves fill its gaps.  With the pairs on the LAST ids the launch is slower than unpaired (150 against 147.5 us at C3).
+struct K1Pairs {
+    int pairs, splits, tiles;
+};
+__host__ __device__ inline void k1_unit(const K1Pairs &pp, int i, int &tile, int &split, bool &paired) {
+    const int base = pp.pairs / pp.splits, rem = pp.pairs % pp.splits;  // splits 0 .. rem - 1 hold base + 1 pairs, the others base
+    paired = i < pp.pairs;
+    if (paired) {
+        split = i % pp.splits;
+        tile = 2 * (i / pp.splits);
+        return;
+    }
+    int k = i - pp.pairs;
+    const int n1 = pp.tiles - 2 * (base + 1), n0 = pp.tiles - 2 * base;  // single tiles of a split with base + 1 / base pairs
+    if (k < rem * n1) {
+        split = k / n1;
+        tile = 2 * (base + 1) + k % n1;
+    } else {
+        k -= rem * n1;
+        split = rem + k / n0;
+        tile = 2 * base + k % n0;
+    }
+}
 
 // D layout of v_mfma_f64_16x16x4_f64: register i of lane l is D[row = (l >> 4) + 4 i][col = l & 15],
 // row = cell within the wave's 16, col = moment index (acc0: 0..15, acc1: 16..31).
@@ -493,17 +536,23 @@ __global__ __launch_bounds__(256) void k_assemble_valu(const double *__restrict_
 // the same w^2 register: the two instruction forms share the lane -> (cell, keypoint) mapping of the A operand
 // (k_assemble_mfma4 below has the small form's layout).  Not bit-identical to the reference (its products are rounded to
 // float32, apap.py:103-119): one float32 ulp in a few per cent of the grid's entries.  kW32: weights by cell_weight_sq_f32.
-template <int kWaves, bool kM24, bool kW32>
-__global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__restrict__ table, int n,
-                                                       const double *__restrict__ vertices, int cells,
-                                                       int cells_pad, double gamma2, double inv_sigma2,
-                                                       int pts_per_split, double *__restrict__ moments,
-                                                       BatchStride bs) {
+// The body for a block that owns kGroups tiles (1, or 2 in a paired launch: tiles `tile` and `tile + 1`) of one keypoint
+// split: every wave carries kGroups 16-cell groups, each with its own vertex and sums, through the same staged chunks.  With
+// two groups a step's (x, y) and table entries are read from LDS once for both, and a group of steps is 4 steps x 2 groups (the
+// same 8 weight chains and 16 MFMAs between two transitions as the 8 steps of one group).  Per accumulator the MFMAs and their
+// operands come in keypoint order whatever kGroups is, and cells are independent: a cell's sums do not depend on the body
+// that computed them.
+// kLevel (the blocks of a paired launch, single-tile ones included): a wave's issue priority falls as it gets on - 3, 2, 1, 0 over
+// the quarters of its whole chunks.  A SIMD issues from its oldest wave first, so without it the four waves of a SIMD end one
+// after the other, 23-25 us apart at C3, and the last runs alone for 20 us at 56 % of what the SIMD can do; with it the waves
+// that are behind get the issue slots, all four stay within a quarter of each other and the SIMD is full almost to the end
+// (C3, paired: 144.4 -> 139.6 us; all blocks end between 91 and 135 us).  It needs every block resident from the start: on the
+// plain grid, where a second round starts late, it costs 1.2 us (148.7 against 147.5), so that grid's body has none of it.
+template <int kWaves, bool kM24, bool kW32, int kGroups, bool kLevel>
+__device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 256], double *s_exp2, const double *__restrict__ table,
+                                              const double *__restrict__ vertices, int cells, int cells_pad, double gamma2,
+                                              double inv_sigma2, double *__restrict__ slab, int tile, const K1Block &blk) {
     constexpr int kThreads = kWaves * 64;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2][kChunk * 256];
-    const K1Block blk(table, vertices, bs, n, (int)blockIdx.y, pts_per_split);
-    moments += (long long)blockIdx.z * bs.moments;
-    __shared__ double s_exp2[kExpN];
     const int tid = threadIdx.x;
     ExpTableStage<kThreads> exp_stage;      // register-staged (see there)
     exp_stage.fetch(tid);
@@ -511,16 +560,25 @@ __global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__r
     const int wave = tid >> 6;
     const int kgrp = lane >> 4;  // which of the step's 4 keypoints this lane weighs
     const int col = lane & 15;   // cell within the wave's 16 (A operand) / table column (B operand)
-    const int cell = blockIdx.x * (16 * kWaves) + wave * 16 + col;
-    CellWeight<kW32> weight;
-    weight.set(cell_vertex(vertices, cell, cells), inv_sigma2, gamma2, s_exp2);
+    CellWeight<kW32> weight[kGroups];
+#pragma unroll
+    for (int t = 0; t < kGroups; ++t)
+        weight[t].set(cell_vertex(vertices, (tile + t) * (16 * kWaves) + wave * 16 + col, cells), inv_sigma2, gamma2, s_exp2);
     const int p_begin = blk.p_begin, p_end = blk.p_end, nchunks = blk.nchunks;
 
     ChunkStage<kThreads> stage;
     const int off_xy = lds_off(kgrp, CellWeight<kW32>::kXyColumn), off_b0 = lds_off(kgrp, col);
     // second operand: columns 16..31 (30 sums), or columns 16 + (lane & 3) and, 32 bytes on, 20 + (lane & 3) (24 sums)
     const int off_b1 = lds_off(kgrp, 16 + (kM24 ? (lane & 3) : col));
-    Sums16<kM24> sums;
+    Sums16<kM24> sums[kGroups];
+    // one step of two groups: the table entries once, then each group's MFMAs
+    auto step2 = [&](const double (&w2)[kGroups], const unsigned char *at0, const unsigned char *at1) {
+        const double b0 = *reinterpret_cast<const double *>(at0);
+        const double b1 = *reinterpret_cast<const double *>(at1);
+        const double b1b = kM24 ? *reinterpret_cast<const double *>(at1 + 32) : 0.0;
+#pragma unroll
+        for (int t = 0; t < kGroups; ++t) sums[t].step(w2[t], b0, b1, b1b);
+    };
     if (nchunks > 0) chunk_load<kThreads>(stage, table, tid, p_begin, p_end);
     exp_stage.publish(s_exp2, tid);  // visible after the barrier
     if (nchunks > 0) APAP_CHUNK_STORE(kThreads, lds[0], stage, tid);
@@ -538,6 +596,12 @@ __global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__r
     // chunk, two 68 KB blocks per CU.  profiles/r06_k1_compiler.txt.)
     const int nfull = (p_end - p_begin) / kChunk;
     for (int c = 0; c < nfull; ++c) {
+        if constexpr (kLevel) {
+            if (4 * c < nfull) __builtin_amdgcn_s_setprio(3);           // the level is an immediate of the instruction
+            else if (4 * c < 2 * nfull) __builtin_amdgcn_s_setprio(2);
+            else if (4 * c < 3 * nfull) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+        }
         if (c + 1 < nchunks) chunk_load<kThreads>(stage, table, tid, p_begin + (c + 1) * kChunk, p_end);
         const unsigned char *buf = lds[c & 1];
         // The weights of g steps first, then their 2 g MFMAs back to back: g times fewer MFMA <-> VALU
@@ -546,15 +610,34 @@ __global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__r
         // A/B at C3 on one box (tools/ab_build.sh): g = 1: 169.5-170.7 us, 2: 165.5-166.3, 4: 165.5-166.1,
         // 8: 163.8-164.1, 16: 163.9-164.2.  (s_setprio 1 / 3 around the MFMA group: +-1 %; a 128-keypoint
         // chunk: +4 %; profiles/r02_k1_variants.txt.)
+        if constexpr (kGroups == 1) {
 #pragma unroll
-        for (int s0 = 0; s0 < kChunk / 4; s0 += 8) {
-            double w2[8];
+            for (int s0 = 0; s0 < kChunk / 4; s0 += 8) {
+                double w2[8];
 #pragma unroll
-            for (int g = 0; g < 8; ++g) w2[g] = weight.sq(buf + off_xy + 1024 * (s0 + g));
-            __builtin_amdgcn_sched_barrier(0);
+                for (int g = 0; g < 8; ++g) w2[g] = weight[0].sq(buf + off_xy + 1024 * (s0 + g));
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int g = 0; g < 8; ++g) sums.step(w2[g], buf + off_b0 + 1024 * (s0 + g), buf + off_b1 + 1024 * (s0 + g));
-            __builtin_amdgcn_sched_barrier(0);
+                for (int g = 0; g < 8; ++g) sums[0].step(w2[g], buf + off_b0 + 1024 * (s0 + g), buf + off_b1 + 1024 * (s0 + g));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            // (float32 weights: 2 steps x 2 groups, which keeps that form within the 96 registers of its five waves per SIMD)
+            constexpr int kSteps = kW32 ? 2 : 4;
+#pragma unroll
+            for (int s0 = 0; s0 < kChunk / 4; s0 += kSteps) {
+                double w2[kSteps][kGroups];
+#pragma unroll
+                for (int g = 0; g < kSteps; ++g) {
+                    const auto xy = CellWeight<kW32>::read(buf + off_xy + 1024 * (s0 + g));
+#pragma unroll
+                    for (int t = 0; t < kGroups; ++t) w2[g][t] = weight[t].sq(xy);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int g = 0; g < kSteps; ++g) step2(w2[g], buf + off_b0 + 1024 * (s0 + g), buf + off_b1 + 1024 * (s0 + g));
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
         if (c + 1 < nchunks) APAP_CHUNK_STORE(kThreads, lds[(c + 1) & 1], stage, tid);
         __syncthreads();
@@ -562,30 +645,62 @@ __global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__r
     if (nfull < nchunks) {      // the partial last chunk (staged and published by the loop's last pass, or by the prologue)
         const unsigned char *buf = lds[nfull & 1];
         const int steps_here = (p_end - p_begin - nfull * kChunk + 3) >> 2;
-        for (int s1 = 0; s1 < steps_here; ++s1)
-            sums.step(weight.sq(buf + off_xy + 1024 * s1), buf + off_b0 + 1024 * s1, buf + off_b1 + 1024 * s1);
+        for (int s1 = 0; s1 < steps_here; ++s1) {
+            if constexpr (kGroups == 1) {
+                sums[0].step(weight[0].sq(buf + off_xy + 1024 * s1), buf + off_b0 + 1024 * s1, buf + off_b1 + 1024 * s1);
+            } else {
+                const auto xy = CellWeight<kW32>::read(buf + off_xy + 1024 * s1);
+                double w2[kGroups];
+#pragma unroll
+                for (int t = 0; t < kGroups; ++t) w2[t] = weight[t].sq(xy);
+                step2(w2, buf + off_b0 + 1024 * s1, buf + off_b1 + 1024 * s1);
+            }
+        }
     }
 
-    constexpr int kSums = kM24 ? 24 : kMoments;
-    double *slab = moments + (size_t)blockIdx.y * kSums * cells_pad;
-    const int cell_base = blockIdx.x * (16 * kWaves) + wave * 16;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {       // the 16x16x4 D registers (d16_cell, d16_column)
-        const int ci = cell_base + d16_cell(lane, i);
-        if (ci < cells_pad) {  // an 8-wave block may overhang the padded cell count
-            // (plain stores: non-temporal ones were measured - K1 150.0 -> 148.7 us, but the 128-byte pieces of a moment row no
-            // longer merge in the L2 and WRITE_SIZE grows from 18.8 to 34.1 MB per launch, profiles/r05_solve_experiments.txt)
-            slab[(size_t)d16_column(lane) * cells_pad + ci] = sums.acc0[i];
-            if (!kM24 && d16_column(lane) < kMoments - 16) slab[(size_t)(16 + d16_column(lane)) * cells_pad + ci] = sums.acc1[i];
+    for (int t = 0; t < kGroups; ++t) {
+        const int cell_base = (tile + t) * (16 * kWaves) + wave * 16;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {       // the 16x16x4 D registers (d16_cell, d16_column)
+            const int ci = cell_base + d16_cell(lane, i);
+            if (ci < cells_pad) {  // an 8-wave block may overhang the padded cell count
+                // (plain stores: non-temporal ones were measured - K1 150.0 -> 148.7 us, but the 128-byte pieces of a moment row no
+                // longer merge in the L2 and WRITE_SIZE grows from 18.8 to 34.1 MB per launch, profiles/r05_solve_experiments.txt)
+                slab[(size_t)d16_column(lane) * cells_pad + ci] = sums[t].acc0[i];
+                if (!kM24 && d16_column(lane) < kMoments - 16) slab[(size_t)(16 + d16_column(lane)) * cells_pad + ci] = sums[t].acc1[i];
+            }
+        }
+        if constexpr (kM24) {       // the 4x4x4_4b D registers (d4_cell, d4_column): columns 16 + j and 20 + j
+            const int ci = cell_base + d4_cell(lane);
+            if (ci < cells_pad) {
+                slab[(size_t)(16 + d4_column(lane)) * cells_pad + ci] = sums[t].acc_a;
+                slab[(size_t)(20 + d4_column(lane)) * cells_pad + ci] = sums[t].acc_b;
+            }
         }
     }
-    if constexpr (kM24) {       // the 4x4x4_4b D registers (d4_cell, d4_column): columns 16 + j and 20 + j
-        const int ci = cell_base + d4_cell(lane);
-        if (ci < cells_pad) {
-            slab[(size_t)(16 + d4_column(lane)) * cells_pad + ci] = sums.acc_a;
-            slab[(size_t)(20 + d4_column(lane)) * cells_pad + ci] = sums.acc_b;
-        }
-    }
+}
+
+template <int kWaves, bool kM24, bool kW32>
+__global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__restrict__ table, int n,
+                                                       const double *__restrict__ vertices, int cells,
+                                                       int cells_pad, double gamma2, double inv_sigma2,
+                                                       int pts_per_split, double *__restrict__ moments,
+                                                       BatchStride bs, K1Pairs pp) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2][kChunk * 256];
+    __shared__ double s_exp2[kExpN];
+    int tile = blockIdx.x, split = blockIdx.y;
+    bool paired = false;
+    if (pp.pairs > 0) k1_unit(pp, (int)blockIdx.x, tile, split, paired);    // block-uniform
+    const K1Block blk(table, vertices, bs, n, split, pts_per_split);
+    constexpr int kSums = kM24 ? 24 : kMoments;
+    double *slab = moments + (long long)blockIdx.z * bs.moments + (size_t)split * kSums * cells_pad;
+    if (paired)
+        k1_mfma_tiles<kWaves, kM24, kW32, 2, true>(lds, s_exp2, table, vertices, cells, cells_pad, gamma2, inv_sigma2, slab, tile, blk);
+    else if (pp.pairs > 0)
+        k1_mfma_tiles<kWaves, kM24, kW32, 1, true>(lds, s_exp2, table, vertices, cells, cells_pad, gamma2, inv_sigma2, slab, tile, blk);
+    else        // the plain grid: the loop as it has always been
+        k1_mfma_tiles<kWaves, kM24, kW32, 1, false>(lds, s_exp2, table, vertices, cells, cells_pad, gamma2, inv_sigma2, slab, tile, blk);
 }
 
 // --------------------------------------------------------------------------------
@@ -2336,7 +2451,9 @@ SolvePlan plan_solve(int n, int cells, int variant, int batch, int want_waves, i
     p.cell_tiles = (cells + kWave - 1) / kWave;  // both variants: 64 cells per 4-wave block
     p.cells_pad = p.cell_tiles * kWave;
     // Fill the chip (256 CUs x 4 SIMDs): aim at >= 4 waves per SIMD (also evens out the
-    // blocks-per-CU imbalance: 2500 waves leave SIMDs with 2 or 3, 5000 with 4 or 5).  Small meshes split
+    // blocks-per-CU imbalance: 2500 waves leave SIMDs with 2 or 3).  5000 waves are more than the 4096 that k_assemble_mfma keeps
+    // resident (4 per SIMD): the launcher pairs tiles in the blocks that would otherwise start when the first 1024 end
+    // (plan_pairs; the splits chosen here never depend on it).  Small meshes split
     // the keypoint list over grid.y; each split writes its own moment slab and K2 adds
     // the slabs in a fixed order.  A split is at least one LDS chunk of keypoints and a whole
     // number of chunks (a partial chunk costs as much as a full one in the MFMA kernel).
@@ -2355,6 +2472,17 @@ SolvePlan plan_solve(int n, int cells, int variant, int batch, int want_waves, i
     p.pts_per_split = pps;
     p.moment_bytes = (size_t)p.splits * (moments == 24 ? 24 : kMoments) * p.cells_pad * sizeof(double);
     return p;
+}
+
+// The paired launch of k_assemble_mfma (K1Pairs): how many blocks take two tiles when `slots` blocks are resident at once.
+// Only a single pair whose J = tiles x splits units are more than the slots and fewer than twice as many is paired: J - slots
+// pairs make the launch exactly `slots` blocks (fewer pairs where a split has an odd tile left over).  The splits and the
+// slab layout are plan_solve's and never depend on this.
+int plan_pairs(int cell_tiles, int splits, int batch, int slots) {
+    const long long units = (long long)cell_tiles * splits;
+    if (batch != 1 || slots < 1 || units <= slots || units >= 2ll * slots) return 0;
+    const long long room = (long long)splits * (cell_tiles / 2);
+    return (int)(units - slots < room ? units - slots : room);
 }
 
 }  // namespace apap
@@ -2390,7 +2518,8 @@ int apap_ctx_set_option(apap_ctx *ctx, int option, int value) {
         case APAP_OPT_WARP_ROWS: ok = value == 0 || value == 1 || value == 2 || value == 4 || value == 5 || value == 6 || value == 8; break;
         case APAP_OPT_WEIGHT_CHUNK_KB: ok = value >= 1; break;
         case APAP_OPT_FUSED_MAX_CELLS:
-        case APAP_OPT_PLAN_CELLS: ok = value >= 0; break;
+        case APAP_OPT_PLAN_CELLS:
+        case APAP_OPT_PLAN_SLOTS: ok = value >= 0; break;
         case APAP_OPT_WARP_FAST:
         case APAP_OPT_OVERLAP_PCIE:
         case APAP_OPT_WEIGHTS_F32: ok = value == 0 || value == 1; break;
@@ -2496,16 +2625,50 @@ static int solve_batch_impl(apap_ctx *ctx, const double *d_tables, int n, const 
             int tiles;
         } k1[] = {
             {{k_assemble_valu, nullptr, nullptr}, 4},      // one tile per wave; no 24-sum form (refused above)
-            {{k_assemble_mfma<4, false, false>, k_assemble_mfma<4, true, false>, k_assemble_mfma<4, true, true>}, 1},
+            {{nullptr, nullptr, nullptr}, 1},              // k_assemble_mfma: k1_mfma below (it takes the pairing too)
             {{k_assemble_mfma4<1, 8, false>, k_assemble_mfma4<1, 6, false>, k_assemble_mfma4<1, 6, true>}, 1},
             {{k_assemble_mfma4<2, 8, false>, k_assemble_mfma4<2, 6, false>, k_assemble_mfma4<2, 6, true>}, 2},
         };
+        using K1Mfma = void (*)(const double *, int, const double *, int, int, double, double, int, double *, BatchStride, K1Pairs);
+        static const K1Mfma k1_mfma[3] = {k_assemble_mfma<4, false, false>, k_assemble_mfma<4, true, false>, k_assemble_mfma<4, true, true>};
         static_assert(APAP_VARIANT_MFMA == APAP_VARIANT_VALU + 1 && APAP_VARIANT_MFMA4 == APAP_VARIANT_VALU + 2 &&
                       APAP_VARIANT_MFMA4X2 == APAP_VARIANT_VALU + 3, "k1[] is indexed by the variant");
-        const auto &k = k1[p.variant >= APAP_VARIANT_MFMA && p.variant <= APAP_VARIANT_MFMA4X2 ? p.variant - APAP_VARIANT_VALU : 0];
-        const dim3 grid((p.cell_tiles + k.tiles - 1) / k.tiles, p.splits, batch);
-        hipLaunchKernelGGL(k.form[!m24 ? 0 : !w32 ? 1 : 2], grid, dim3(256), 0, s, d_tables, n, d_vertices, cells, p.cells_pad, gamma2,
-                           inv_sigma2, p.pts_per_split, moments, bs);
+        const int form = !m24 ? 0 : !w32 ? 1 : 2;
+        if (p.variant == APAP_VARIANT_MFMA) {
+            // A single pair whose (tile, split) units are more than the chip holds blocks of this form, and fewer than twice as
+            // many, goes out as exactly that many blocks, some of them with two tiles (plan_pairs): every block is resident from
+            // the start.  The slots: APAP_OPT_PLAN_SLOTS, or what the device says, asked once per context, device and form.
+            int slots = apap::opt(ctx, APAP_OPT_PLAN_SLOTS);
+            if (slots == 0 && batch == 1) {
+                int dev = 0;
+                hipError_t e = hipGetDevice(&dev);
+                if (e != hipSuccess) return hip_fail(e, "apap_solve_device (hipGetDevice)");
+                if (!ctx || ctx->k1_slots_dev != dev || ctx->k1_slots[form] == 0) {
+                    int per_cu = 0, cus = 0;
+                    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(k1_mfma[form]), 256, 0);
+                    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+                    if (e != hipSuccess) return hip_fail(e, "apap_solve_device (resident blocks of K1)");
+                    slots = per_cu * cus;
+                    if (ctx) {
+                        if (ctx->k1_slots_dev != dev) ctx->k1_slots[0] = ctx->k1_slots[1] = ctx->k1_slots[2] = 0;
+                        ctx->k1_slots_dev = dev;
+                        ctx->k1_slots[form] = slots;
+                    }
+                } else {
+                    slots = ctx->k1_slots[form];
+                }
+            }
+            const int pairs = apap::plan_pairs(p.cell_tiles, p.splits, batch, slots);
+            const K1Pairs pp{pairs, p.splits, p.cell_tiles};
+            const dim3 grid = pairs > 0 ? dim3(p.cell_tiles * p.splits - pairs, 1, 1) : dim3(p.cell_tiles, p.splits, batch);
+            hipLaunchKernelGGL(k1_mfma[form], grid, dim3(256), 0, s, d_tables, n, d_vertices, cells, p.cells_pad, gamma2, inv_sigma2,
+                               p.pts_per_split, moments, bs, pp);
+        } else {
+            const auto &k = k1[p.variant > APAP_VARIANT_MFMA && p.variant <= APAP_VARIANT_MFMA4X2 ? p.variant - APAP_VARIANT_VALU : 0];
+            const dim3 grid((p.cell_tiles + k.tiles - 1) / k.tiles, p.splits, batch);
+            hipLaunchKernelGGL(k.form[form], grid, dim3(256), 0, s, d_tables, n, d_vertices, cells, p.cells_pad, gamma2,
+                               inv_sigma2, p.pts_per_split, moments, bs);
+        }
     }
     {
         ProfScope prof(ctx, APAP_PROF_EIGEN, s);

@@ -168,7 +168,15 @@ typedef struct apap_ctx apap_ctx;
                                       with gamma^2 flooring every weight (BASELINE's gamma = 0.5, sigma = 100: |x| <= 2) that
                                       is the class of MOMENTS = 24 alone (one float32 ulp here and there).  gamma >= 1 makes
                                       every weight gamma: this chain then clamps at 1 (gamma^2 overflows float32 at 1.8e19)  */
-#define APAP_OPT_COUNT 13
+#define APAP_OPT_PLAN_SLOTS 13      /* 0 (default): the blocks of K1's 16x16x4 kernel that the device keeps resident at once are
+                                      asked of the device (once per context).  A single pair (batch = 1) whose J = tiles x
+                                      splits blocks are more than these S slots and fewer than 2 S is launched as S blocks, J - S
+                                      of them carrying TWO 64-cell tiles of one keypoint split, so that none waits for a second
+                                      round.  s > 0: plan that pairing as for s resident slots (a large s switches it off).
+                                      It moves K1's block-to-tile mapping (and, in a paired launch, the issue priority of its
+                                      waves) and nothing else: splits, workspace size, the
+                                      moment slabs and the grids are the same bits for every value                        */
+#define APAP_OPT_COUNT 14
 apap_ctx *apap_ctx_create(void);
 void apap_ctx_destroy(apap_ctx *ctx); /* frees the pooled device buffers and pending events; NULL is a no-op */
 int apap_ctx_set_option(apap_ctx *ctx, int option, int value);
