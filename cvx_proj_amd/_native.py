@@ -30,7 +30,9 @@ EIGEN_AUTO, EIGEN_JACOBI, EIGEN_INVERSE_ITERATION = 0, 1, 2
 # options of a context (include/apap_hip.h)
 OPT_SOLVER_VARIANT, OPT_EIGEN_SOLVER, OPT_CAREFUL, OPT_PROFILE, OPT_WANT_WAVES, OPT_WARP_ROWS, OPT_WEIGHT_CHUNK_KB, \
     OPT_FUSED_MAX_CELLS, OPT_WARP_FAST, OPT_OVERLAP_PCIE, OPT_PLAN_CELLS, OPT_MOMENTS, OPT_WEIGHTS_F32, \
-    OPT_PLAN_SLOTS = range(14)
+    OPT_PLAN_SLOTS, OPT_WARP_SAMPLING = range(15)
+SAMPLING_NEAREST, SAMPLING_BILINEAR = 0, 1      # values of OPT_WARP_SAMPLING
+SAMPLINGS = {"nearest": SAMPLING_NEAREST, "bilinear": SAMPLING_BILINEAR}
 
 
 class ApapError(RuntimeError):
@@ -292,7 +294,7 @@ class Context:
               "want_waves": OPT_WANT_WAVES, "warp_rows": OPT_WARP_ROWS, "weight_chunk_kb": OPT_WEIGHT_CHUNK_KB,
               "fused_max_cells": OPT_FUSED_MAX_CELLS, "warp_fast": OPT_WARP_FAST, "overlap_pcie": OPT_OVERLAP_PCIE,
               "plan_cells": OPT_PLAN_CELLS, "moments": OPT_MOMENTS, "weights_f32": OPT_WEIGHTS_F32,
-              "plan_slots": OPT_PLAN_SLOTS}
+              "plan_slots": OPT_PLAN_SLOTS, "warp_sampling": OPT_WARP_SAMPLING}
 
     def set(self, name, value):
         check(lib().apap_ctx_set_option(self._h, self._NAMES[name], int(value)))
@@ -335,6 +337,44 @@ def _h(ctx):
 
 def last_error():
     return lib().apap_last_error().decode("utf-8", "replace")
+
+
+def sampling_value(sampling, who="local_warp"):
+    """The ``OPT_WARP_SAMPLING`` value of a ``sampling=`` keyword: ``None`` (whatever the context says) -> ``None``,
+    ``"nearest"`` / ``"bilinear"`` -> 0 / 1, anything else a ValueError - raised before any device is touched."""
+    if sampling is None:
+        return None
+    if not isinstance(sampling, str) or sampling not in SAMPLINGS:
+        raise ValueError(f"{who}: sampling must be None, 'nearest' or 'bilinear'; got {sampling!r}")
+    return SAMPLINGS[sampling]
+
+
+class sampling_scope:
+    """``with sampling_scope(ctx, sampling, who) as c:`` - the context to pass to the native call.  ``sampling=None``: ``ctx``
+    itself, untouched.  A string: ``ctx`` (a fresh context when ``ctx`` is None) with ``OPT_WARP_SAMPLING`` set for the body
+    and put back to what it was found at on the way out."""
+
+    def __init__(self, ctx, sampling, who="local_warp"):
+        self._value = sampling_value(sampling, who)
+        self._ctx, self._own, self._before = ctx, None, None
+
+    def __enter__(self):
+        if self._value is None:
+            return self._ctx
+        if self._ctx is None:
+            self._own = self._ctx = Context()
+        before = C.c_int(0)
+        check(lib().apap_ctx_get_option(_h(self._ctx), OPT_WARP_SAMPLING, C.byref(before)))
+        self._before = before.value
+        check(lib().apap_ctx_set_option(_h(self._ctx), OPT_WARP_SAMPLING, self._value))
+        return self._ctx
+
+    def __exit__(self, *exc):
+        if self._before is not None:
+            lib().apap_ctx_set_option(_h(self._ctx), OPT_WARP_SAMPLING, self._before)
+        if self._own is not None:
+            self._own.close()
+        return False
 
 
 def _ptr(a, ctype):
@@ -516,9 +556,16 @@ def local_weights(src, points, gamma, sigma, device=-1, ctx=None):
     return W
 
 
-def local_warp(img, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, want_inverse=True, device=-1, ctx=None, out=None):
+def local_warp(img, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, want_inverse=True, device=-1, ctx=None, out=None,
+               sampling=None):
     """``out``: the caller's own (final_h, final_w, 3) uint8 canvas (e.g. page-locked memory, which the library then neither
-    registers nor stages) instead of a fresh array."""
+    registers nor stages) instead of a fresh array.  ``sampling``: ``None`` (the context's ``warp_sampling``), ``"nearest"`` or
+    ``"bilinear"`` for this call only."""
+    with sampling_scope(ctx, sampling, "local_warp") as ctx:
+        return _local_warp(img, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, want_inverse, device, ctx, out)
+
+
+def _local_warp(img, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, want_inverse, device, ctx, out):
     img = np.ascontiguousarray(img, dtype=np.uint8)
     img_h, img_w, ch = img.shape
     if ch != 3:
@@ -552,8 +599,14 @@ def local_warp(img, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, want_inve
     return out, Hinv
 
 
-def local_stitch(img, center, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, want_inverse=False, device=-1, ctx=None):
-    """Fused local_warp + paste of ``center`` at the offsets + uniform_blend."""
+def local_stitch(img, center, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, want_inverse=False, device=-1, ctx=None,
+                 sampling=None):
+    """Fused local_warp + paste of ``center`` at the offsets + uniform_blend.  ``sampling``: as in :func:`local_warp`."""
+    with sampling_scope(ctx, sampling, "local_stitch") as ctx:
+        return _local_stitch(img, center, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, want_inverse, device, ctx)
+
+
+def _local_stitch(img, center, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, want_inverse, device, ctx):
     img = np.ascontiguousarray(img, dtype=np.uint8)
     center = np.ascontiguousarray(center, dtype=np.uint8)
     if img.ndim != 3 or img.shape[2] != 3 or center.ndim != 3 or center.shape[2] != 3:
@@ -1294,7 +1347,14 @@ def panorama_ramp_quotients(total, wsum):
     return out
 
 
-def panorama(center, layers, blend="mean", device=-1, ctx=None, return_status=False, ramp=32):
+def panorama(center, layers, blend="mean", device=-1, ctx=None, return_status=False, ramp=32, sampling=None):
+    """See :func:`_panorama`; ``sampling``: ``None`` (the context's ``warp_sampling``), ``"nearest"`` or ``"bilinear"`` for this
+    call only - every layer is then sampled that way."""
+    with sampling_scope(ctx, sampling, "panorama") as ctx:
+        return _panorama(center, layers, blend, device, ctx, return_status, ramp)
+
+
+def _panorama(center, layers, blend, device, ctx, return_status, ramp):
     """``apap_panorama`` (``blend`` 'mean' or 'paste') or ``apap_panorama_ramp`` ('ramp', with the ramp width ``ramp``, which the
     other blends ignore): the centre picture and every layer (a :class:`PanoramaLayer` or a 5-tuple in its order) on one canvas.
     Returns ``(canvas (H, W, 3) uint8, (W, H, OX, OY))`` - with ``return_status=True`` also the per-layer status words, and

@@ -232,38 +232,43 @@ class APAP:
         return (H, info, status) if return_info else H
 
     # ---- hot loop 2 ------------------------------------------------------------------
-    def local_warp(self, ori_img, local_homography, mesh, progress=False):
-        """Backward warp of ``ori_img`` onto the canvas.  Reference apap.py:186-217.
+    def local_warp(self, ori_img, local_homography, mesh, progress=False, sampling=None):
+        """Backward warp of ``ori_img`` onto the canvas.  Reference apap.py:186-217.  ``sampling``: ``None`` (the context's
+        ``warp_sampling``; by default the reference's truncation), ``"nearest"`` or ``"bilinear"`` (the same footprint, each
+        pixel reconstructed at its source coordinate from four neighbours) for this call only.
 
         Like the reference, the per-cell inverses are written back INTO
         ``local_homography`` (apap.py:201-203) when it is a writable float32 array.
         ``progress`` is accepted for signature compatibility; one kernel launch has no
         rows to report."""
+        _native.sampling_value(sampling, "APAP.local_warp")
         mesh_w, mesh_h = mesh
         ori_h, ori_w, _ = ori_img.shape
         mesh_n, pt_size, _, _ = local_homography.shape
         print("Inverse solving started.")        # the reference prints these two lines (apap.py:200,204);
         warped, hinv = _native.local_warp(ori_img, local_homography, mesh_w, mesh_h, self.final_width,
                                           self.final_height, self.offset_x, self.offset_y,
-                                          want_inverse=True, device=self.device, ctx=self.ctx)
+                                          want_inverse=True, device=self.device, ctx=self.ctx, sampling=sampling)
         print("Inverse solving completed.")      # here the inverses come from the same native call as the warp
         if isinstance(local_homography, np.ndarray) and local_homography.flags.writeable:
             local_homography[...] = hinv
         return warped
 
 
-    def local_stitch(self, ori_img, center_img, local_homography, mesh):
+    def local_stitch(self, ori_img, center_img, local_homography, mesh, sampling=None):
         """The blend the reference's ``__main__`` keeps commented out (apap.py:258-262) as
         one fused pass: ``uniform_blend(local_warp(ori_img, H, mesh), paste(center_img))``
         with the centre image pasted at ``(offset_x, offset_y)``.  Does not mutate
-        ``local_homography``."""
+        ``local_homography``.  ``sampling``: as in :meth:`local_warp`."""
+        _native.sampling_value(sampling, "APAP.local_stitch")
         mesh_w, mesh_h = mesh
         out, _ = _native.local_stitch(ori_img, center_img, local_homography, mesh_w, mesh_h, self.final_width,
-                                      self.final_height, self.offset_x, self.offset_y, device=self.device, ctx=self.ctx)
+                                      self.final_height, self.offset_x, self.offset_y, device=self.device, ctx=self.ctx,
+                                      sampling=sampling)
         return out
 
 
-def panorama(center_img, layers, blend="mean", device=-1, ctx=None, ramp=32):
+def panorama(center_img, layers, blend="mean", device=-1, ctx=None, ramp=32, sampling=None):
     """Every view of a case on one canvas, in one fused pass on the GPU: ``center_img`` and each :class:`PanoramaLayer`
     (the neighbour's picture, its grid from :meth:`APAP.local_homography`, its mesh, and the ``final_size`` / offsets of its
     pair - what :meth:`APAP.local_warp` takes), warped through its own grid.  The reference stitches one pair at a time
@@ -281,8 +286,12 @@ def panorama(center_img, layers, blend="mean", device=-1, ctx=None, ramp=32):
 
     Returns ``(canvas (H, W, 3) uint8, (W, H, OX, OY))``.  The grids are not modified.  A singular cell raises
     ``LinAlgError``, mesh edges that do not cover a pair canvas ``IndexError``, as ``local_warp`` of that layer would, with
-    the layer's index in the message."""
-    return _native.panorama(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp)
+    the layer's index in the message.
+
+    ``sampling``: ``None`` (the context's ``warp_sampling``; by default truncation), ``"nearest"`` or ``"bilinear"``: how every
+    layer is sampled.  The footprints, the presence counts and the ramp's weights (taken at ``(int(tx), int(ty))``) do not
+    depend on it."""
+    return _native.panorama(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp, sampling=sampling)
 
 
 def panorama_layer(src, dst, H_global, other_img, center_shape, mesh_size=100, gamma=0.5, sigma=100, device=-1, ctx=None):
@@ -324,23 +333,24 @@ def read_config(path):
 
 
 def run_pair(src, dst, H_global, other_shape, center_shape, mesh_size=100, gamma=0.5, sigma=100,
-             other_img=None, center_img=None, device=-1, pipeline=None):
+             other_img=None, center_img=None, device=-1, pipeline=None, sampling=None):
     """Body of the reference's ``__main__`` between loading and saving
     (apap.py:238-264).  Returns ``(H_flat (m*m, 9) float64, canvas or None)``; the canvas
     is the warped other image, or - when ``center_img`` is given - the blended stitch
     of apap.py:258-262.  One resident pass (:class:`cvx_proj_amd.pipeline.Pipeline`): the H grid never
-    leaves HBM between the solve, the output stage and the warp."""
+    leaves HBM between the solve, the output stage and the warp.  ``sampling``: as in :meth:`APAP.local_warp`."""
+    _native.sampling_value(sampling, "run_pair")
     from .pipeline import Pipeline
     pipe = pipeline if pipeline is not None else Pipeline(device=device)
     return pipe.run_pair(src, dst, H_global, other_shape, center_shape, mesh_size, gamma, sigma,
-                         other_img=other_img, center_img=center_img)
+                         other_img=other_img, center_img=center_img, sampling=sampling)
 
 
 def run_pair_by_calls(src, dst, H_global, other_shape, center_shape, mesh_size=100, gamma=0.5, sigma=100,
-                      other_img=None, center_img=None, device=-1):
+                      other_img=None, center_img=None, device=-1, sampling=None):
     """The same through the mirror class, call by call, as the reference's ``__main__`` is written: numpy in and
     out of every stage (the H grid crosses PCIe three times).  Kept as the yardstick of :func:`run_pair`."""
-
+    _native.sampling_value(sampling, "run_pair_by_calls")
     class _S:
         def __init__(self, shape):
             self.shape = shape
@@ -351,9 +361,9 @@ def run_pair_by_calls(src, dst, H_global, other_shape, center_shape, mesh_size=1
     eng = APAP(gamma, sigma, [fw, fh], [ox, oy], device=device)
     H, _ = eng.local_homography(src, dst, vertices, return_weights=False)
     if other_img is not None and center_img is not None:
-        warped = eng.local_stitch(other_img, center_img, H, mesh)
+        warped = eng.local_stitch(other_img, center_img, H, mesh, sampling=sampling)
     else:
-        warped = eng.local_warp(other_img, H.copy(), mesh) if other_img is not None else None
+        warped = eng.local_warp(other_img, H.copy(), mesh, sampling=sampling) if other_img is not None else None
     flat = _native.invert_normalize_flatten(H, device=device)   # apap.py:250-264
     return flat, warped
 
@@ -401,6 +411,9 @@ def main(argv=None):
     ap.add_argument("--panorama-blend", choices=("mean", "paste", "ramp"), default="mean")
     ap.add_argument("--panorama-ramp", type=int, default=32, metavar="N",
                     help="--panorama-blend ramp: a picture's weight grows over N pixels from its border (1 .. 256)")
+    ap.add_argument("--sampling", choices=("nearest", "bilinear"), default=None,
+                    help="how --warp, --stitch and --panorama sample the source pictures: nearest = the reference's truncation "
+                         "(default), bilinear = four neighbours with 5 fractional bits, the same footprint")
     ap.add_argument("--device", type=int, default=-1)
     ap.add_argument("--resident", action="store_true",
                     help="one resident pass per pair through cvx_proj_amd.pipeline (imports torch: ~2 s more start-up, ~0.3 ms less "
@@ -490,10 +503,11 @@ def main(argv=None):
             panoramas.setdefault(case_idx, (center_img, []))[1].append(layer)   # a case's centre: its first pair's
         elif pipeline is not None:
             flat, warped = run_pair(src, dst, Hg, other_shape, center_shape, mesh_size, par["gamma"], par["sigma"],
-                                    other_img=other_img, center_img=center_img, device=a.device, pipeline=pipeline)
+                                    other_img=other_img, center_img=center_img, device=a.device, pipeline=pipeline,
+                                    sampling=a.sampling)
         else:
             flat, warped = run_pair_by_calls(src, dst, Hg, other_shape, center_shape, mesh_size, par["gamma"], par["sigma"],
-                                             other_img=other_img, center_img=center_img, device=a.device)
+                                             other_img=other_img, center_img=center_img, device=a.device, sampling=a.sampling)
         t2 = time.perf_counter()
         print(f"local_homography shape: {(mesh_size, mesh_size, 3, 3)}")
         out_dir = f"{a.out_prefix}case{case_idx}"
@@ -509,7 +523,8 @@ def main(argv=None):
                                 "save_ms": (time.perf_counter() - t2) * 1e3})
     for case_idx, (center_img, layers) in panoramas.items():
         t0 = time.perf_counter()
-        canvas, bounds = panorama(center_img, layers, blend=a.panorama_blend, device=a.device, ramp=a.panorama_ramp)
+        canvas, bounds = panorama(center_img, layers, blend=a.panorama_blend, device=a.device, ramp=a.panorama_ramp,
+                                  sampling=a.sampling)
         out = a.panorama
         if len(panoramas) > 1:
             root, ext = os.path.splitext(out)

@@ -605,7 +605,10 @@ static int warp_common(apap_ctx *ctx, const uint8_t *img, int img_h, int img_w, 
     HostCall call(ctx);
     int rc = call.select(device);
     if (rc) return rc;
-    if (!coords && h_bytes == sizeof(float) && apap::opt(ctx, APAP_OPT_OVERLAP_PCIE)) {
+    // (the overlapped path schedules its upload bands from src_rows, which bounds the TRUNCATED source row only: under bilinear
+    // sampling the plain path)
+    if (!coords && h_bytes == sizeof(float) && apap::opt(ctx, APAP_OPT_OVERLAP_PCIE) &&
+        apap::opt(ctx, APAP_OPT_WARP_SAMPLING) == APAP_SAMPLING_NEAREST) {
         bool done = false;
         rc = warp_overlapped(ctx, call.pool(), call.dev(), img, img_h, img_w, center, center_h, center_w, (const float *)Hfwd,
                              mesh_rows, mesh_cols, mesh_w, n_w, mesh_h, n_h, final_w, final_h, off_x, off_y, out, (float *)Hinv_out,

@@ -27,7 +27,7 @@ enum { S_TABLE, S_VERT, S_DENORM, S_H, S_WORK, S_W, S_IMG, S_OUT, S_MESHW, S_MES
 // The context of include/apap_hip.h: options, profiling events, device-buffer pool.  Nothing else
 // in the library is mutable after load.
 struct apap_ctx {
-    int opt[APAP_OPT_COUNT] = {APAP_VARIANT_AUTO, APAP_EIGEN_AUTO, 1, 0, 4096, 1, 1 << 20, 4096, 1, 0, 0, 30, 0, 0};
+    int opt[APAP_OPT_COUNT] = {APAP_VARIANT_AUTO, APAP_EIGEN_AUTO, 1, 0, 4096, 1, 1 << 20, 4096, 1, 0, 0, 30, 0, 0, APAP_SAMPLING_NEAREST};
     std::vector<apap::ProfSpan> spans;
     apap::DevSlot slots[apap::S_COUNT];
     std::mutex mu;   // serialises the host-buffer entry points that share this context's pool
@@ -107,6 +107,22 @@ struct WarpTables {
     const int *lut;
 };
 WarpTables warp_tables(void *d_work, int mesh_rows, int mesh_cols, int final_w, int final_h);
+
+// The gather of a warp under APAP_SAMPLING_BILINEAR (apap_warp_bilinear.hip): what warp_impl hands its kernel once the set-up
+// has run - the sizes it has checked, the exact path's tables, the pairs' strides (bytes; hinv in doubles).  Travels by value
+// in the kernel argument.  center = NULL: no stitch.
+struct WarpGather {
+    const uint8_t *img;
+    const uint8_t *center;
+    uint8_t *out;               // row `row_begin` of pair 0's canvas
+    const double *hinv_pad;
+    const int *lut;
+    int *status;
+    long long img_stride, center_stride, out_stride, hinv_stride;
+    int img_h, img_w, center_h, center_w, mesh_rows, mesh_cols, final_w, final_h, off_x, off_y, row_begin, row_count;
+};
+// k_warp_bilinear over rows [row_begin, row_begin + row_count) of `batch` canvases on `stream` (under the APAP_PROF_WARP slot).
+int warp_bilinear_launch(apap_ctx *ctx, const WarpGather &g, int batch, void *stream);
 
 // The panorama's third blend, the edge ramp, has entry points of its own (apap_panorama_ramp*): as a mode it exists only
 // inside the library, and apap_panorama[_device] refuse it like any other unknown mode.

@@ -1595,19 +1595,11 @@ __global__ __launch_bounds__(256) void k_invert_cells(const T *__restrict__ H, i
 // never built - or were built for another mesh / canvas size - would index the per-cell tables with garbage.  The word behind
 // the lut carries a stamp of the sizes the tables were built for; every gather kernel compares it (one scalar load, issued with
 // its first table loads) before it uses a table VALUE as an index, and leaves with bit 2 of the status word otherwise.
-__host__ __device__ __forceinline__ int warp_stamp(int mesh_rows, int mesh_cols, int final_w, int final_h) {
-    return (int)(((unsigned)mesh_rows * 0x9E3779B1u) ^ ((unsigned)mesh_cols * 0x85EBCA77u) ^ ((unsigned)final_w * 0xC2B2AE3Du) ^
-                 ((unsigned)final_h * 0x27D4EB2Fu)) | 1;
-}
+// (warp_stamp and warp_tables_ready: apap_warp_dev.h, shared with the bilinear strip kernel's source)
 // the same in 16 bits, never 0: carried by every row entry of the fast tables (frow[i].x = cell row | stamp16 << 16), so that
 // the strip kernel learns it from a load it makes anyway
 __host__ __device__ __forceinline__ unsigned warp_stamp16(int mesh_rows, int mesh_cols, int final_w, int final_h) {
     return (((unsigned)warp_stamp(mesh_rows, mesh_cols, final_w, final_h) >> 12) & 0xffffu) | 1u;
-}
-__device__ __forceinline__ bool warp_tables_ready(int have, int mesh_rows, int mesh_cols, int final_w, int final_h, int *status) {
-    if (__builtin_expect(have == warp_stamp(mesh_rows, mesh_cols, final_w, final_h), 1)) return true;
-    if ((threadIdx.x & 63) == 0) atomicOr(status, APAP_STATUS_UNPREPARED);
-    return false;
 }
 
 __global__ __launch_bounds__(256) void k_cell_lut(const double *__restrict__ mesh_w, int n_w,
@@ -2524,6 +2516,7 @@ int apap_ctx_set_option(apap_ctx *ctx, int option, int value) {
         case APAP_OPT_OVERLAP_PCIE:
         case APAP_OPT_WEIGHTS_F32: ok = value == 0 || value == 1; break;
         case APAP_OPT_MOMENTS: ok = value == 30 || value == 24; break;
+        case APAP_OPT_WARP_SAMPLING: ok = value == APAP_SAMPLING_NEAREST || value == APAP_SAMPLING_BILINEAR; break;
         default: return apap::fail(APAP_ERR_INVALID_ARG, "apap_ctx_set_option: unknown option %d", option);
     }
     if (!ok) return apap::fail(APAP_ERR_INVALID_ARG, "apap_ctx_set_option: value %d is not valid for option %d", value, option);
@@ -2875,6 +2868,17 @@ int warp_impl(apap_ctx *ctx, const WarpArgs &a) {
     const WarpStrides st{a.img_stride, a.out_stride, a.center_stride, ww.hinv_stride, ww.frec_stride};
     const size_t total = (size_t)final_w * row_count;
     const size_t threads = (total + 3) / 4;
+    // APAP_OPT_WARP_SAMPLING: bilinear sampling has one kernel for every source and canvas admitted above (apap_warp_bilinear.hip);
+    // APAP_OPT_WARP_ROWS and APAP_OPT_WARP_FAST do not apply to it (the float32 estimate's doubt window is built around integer
+    // boundaries, not 1/32 boundaries).
+    if (apap::opt(ctx, APAP_OPT_WARP_SAMPLING) == APAP_SAMPLING_BILINEAR) {
+        apap::WarpGather g;
+        g.img = d_img; g.center = d_center; g.out = d_out; g.hinv_pad = hinv_pad; g.lut = lut; g.status = a.status;
+        g.img_stride = st.img; g.center_stride = st.center; g.out_stride = st.out; g.hinv_stride = st.hinv;
+        g.img_h = img_h; g.img_w = img_w; g.center_h = center_h; g.center_w = center_w; g.mesh_rows = mesh_rows; g.mesh_cols = mesh_cols;
+        g.final_w = final_w; g.final_h = final_h; g.off_x = off_x; g.off_y = off_y; g.row_begin = row_begin; g.row_count = row_count;
+        return apap::warp_bilinear_launch(ctx, g, (int)batch, a.stream);
+    }
     // APAP_OPT_WARP_ROWS: 0 = flat-order kernel, 2 / 4 / 5 / 6 / 8 = row strips of that many rows per wave, 1 (default) =
     // chosen from the size of the launch.  A strip pays its table trips and its cell records once, so taller strips are
     // cheaper per pixel - but a launch needs a few generations of waves before that shows: measured on the final kernel

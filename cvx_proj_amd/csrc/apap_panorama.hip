@@ -92,7 +92,7 @@ struct PanoArgs {
 };
 static_assert(sizeof(PanoArgs) <= 4096, "kernel arguments");
 
-template <int kMode>
+template <int kMode, int kSampling>
 __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
     __shared__ unsigned recip[32];
     if (kMode == APAP_PANORAMA_MEAN) {
@@ -190,6 +190,64 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
 #pragma unroll
         for (int t = 0; t < kRows; ++t) rr[t] = __builtin_amdgcn_readfirstlane(rr[t]);
         want &= kMode == APAP_PANORAMA_PASTE ? und : live;
+        if (kSampling == APAP_SAMPLING_BILINEAR) {
+            // The same passes over the cell rows; a sample keeps its first tap's offset and, in one register, its weights, its
+            // presence and (ramp) its weight in the blend, which is still that of source pixel (int(tx), int(ty)).  A sample
+            // that is absent, undecided or off the pair canvas keeps the taps of pixel (0, 0) and counts as black.  Then row by
+            // row: sixteen taps in flight, four blends, four pixels into the accumulators.
+            unsigned boff[kRows][4], bfr[kRows][4];
+#pragma unroll
+            for (int t = 0; t < kRows; ++t)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) boff[t][k] = bfr[t][k] = 0u;
+            while (todo != 0u) {
+                const int first = __builtin_ctz(todo);
+                int r = rr[0];
+#pragma unroll
+                for (int t = 1; t < kRows; ++t) r = (t == first) ? rr[t] : r;
+                PixelH q[4];
+                strip_cell_row(hinv_pad, r * mesh_cols, col, xs, q);
+#pragma unroll
+                for (int t = 0; t < kRows; ++t) {
+                    if (!((todo >> t) & 1u) || rr[t] != r) continue;
+                    todo &= ~(1u << t);
+                    const double yd = (double)(y_first + t - A.OY);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        int ix, iy;
+                        double tx, ty;
+                        const bool ok = strip_source_xy(q[k], yd, img_w, img_h, ix, iy, tx, ty) & (((want >> (4 * t + k)) & 1u) != 0u);
+                        bilinear_taps(ok, tx, ty, img_w, img_h, boff[t][k], bfr[t][k]);
+                        if (kMode == APAP_PANORAMA_RAMP) bfr[t][k] |= (ok ? (unsigned)ramp_weight(ix, iy, img_w, img_h, ramp) : 0u) << 16;
+                    }
+                }
+            }
+            const unsigned last = L.last, row_bytes = (unsigned)img_w * 3u;
+#pragma unroll
+            for (int t = 0; t < kRows; ++t) {
+                unsigned tap[4][4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) gather_taps(img, boff[t][k], bfr[t][k], row_bytes, last, tap[k]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const unsigned v = bilinear_blend(tap[k], bfr[t][k]);
+                    if (kMode == APAP_PANORAMA_MEAN) {
+                        a0[t][k] += v & 0x00ff00ffu;
+                        a1[t][k] += ((v >> 8) & 0xffu) | ((unsigned)(v != 0u) << 16);
+                    } else if (kMode == APAP_PANORAMA_RAMP) {
+                        const unsigned wt = v != 0u ? bfr[t][k] >> 16 : 0u;
+                        a0[t][k] += __umul24(wt, v & 0xffu);
+                        a1[t][k] += __umul24(wt, (v >> 8) & 0xffu);
+                        a2[t][k] += __umul24(wt, v >> 16);
+                        aw[t][k >> 1] += wt << (16 * (k & 1));
+                    } else {
+                        a0[t][k] = v != 0u ? v : a0[t][k];
+                        und &= ~((unsigned)(v != 0u) << (4 * t + k));
+                    }
+                }
+            }
+            continue;
+        }
         unsigned off[kRows][4];
 #pragma unroll
         for (int t = 0; t < kRows; ++t)
@@ -392,9 +450,16 @@ int panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int ce
     hipStream_t s = (hipStream_t)stream;
     {
         apap::ProfScope prof(ctx, APAP_PROF_WARP, s);
-        if (ramp) hipLaunchKernelGGL(k_panorama<APAP_PANORAMA_RAMP>, grid, dim3(kWaves * 64), 0, s, A);
-        else if (mode == APAP_PANORAMA_MEAN) hipLaunchKernelGGL(k_panorama<APAP_PANORAMA_MEAN>, grid, dim3(kWaves * 64), 0, s, A);
-        else hipLaunchKernelGGL(k_panorama<APAP_PANORAMA_PASTE>, grid, dim3(kWaves * 64), 0, s, A);
+        // APAP_OPT_WARP_SAMPLING: the option the pair warps read (the set-up phases above do not depend on it)
+#define APAP_LAUNCH_PANORAMA(S)                                                                                                   \
+    do {                                                                                                                          \
+        if (ramp) hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_RAMP, S>), grid, dim3(kWaves * 64), 0, s, A);                      \
+        else if (mode == APAP_PANORAMA_MEAN) hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_MEAN, S>), grid, dim3(kWaves * 64), 0, s, A); \
+        else hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_PASTE, S>), grid, dim3(kWaves * 64), 0, s, A);                          \
+    } while (0)
+        if (apap::opt(ctx, APAP_OPT_WARP_SAMPLING) == APAP_SAMPLING_BILINEAR) APAP_LAUNCH_PANORAMA(APAP_SAMPLING_BILINEAR);
+        else APAP_LAUNCH_PANORAMA(APAP_SAMPLING_NEAREST);
+#undef APAP_LAUNCH_PANORAMA
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "k_panorama launch");

@@ -5,7 +5,11 @@
 //   strips        pixel_h, strip_cell_row, strip_source, strip_offset: a cell row's matrices for a lane's four pixels and the
 //                 exact coordinate with ONE Newton step, used by k_warp_rows and k_panorama (strip_offset also by k_warp_fast)
 //   gather        gather_px: one source pixel from a byte offset or the outside marker (k_warp_rows, k_warp_fast, k_panorama)
+//   bilinear      strip_source_xy (strip_source with the coordinate handed back), fixed_coord, bilinear_taps, gather_tap(s),
+//                 bilinear_blend: APAP_SAMPLING_BILINEAR's per-pixel steps (k_warp_bilinear, apap_warp_bilinear.hip, and
+//                 k_panorama's bilinear forms)
 //   stitch        blend_center: centre paste + uniform_blend of one pixel (k_warp, k_warp_rows, k_warp_fast)
+//   tables        warp_stamp, warp_tables_ready: the stamp of a workspace's lookup tables (every gather kernel)
 //   store         store12_stream, APAP_STORE_PX4: four pixels as one 12-byte non-temporal store, or a partial group byte by byte
 //                 (every kernel above and k_image_warp, apap_image_warp.hip)
 // The two exact sequences stay apart; each is pinned by its own tests.  Their three sums are the same bits: fma(h, 1.0, s) is
@@ -56,6 +60,18 @@ __device__ __forceinline__ void store12_stream(uint8_t *p, unsigned a, unsigned 
             }                                                                                                            \
         }                                                                                                                \
     } while (0)
+
+// The stamp of the sizes a warp workspace's lookup tables were built for (the word behind the lut; apap_kernels.hip describes
+// it at warp_stamp16), and the test every gather kernel makes before it uses a table value as an index.
+__host__ __device__ __forceinline__ int warp_stamp(int mesh_rows, int mesh_cols, int final_w, int final_h) {
+    return (int)(((unsigned)mesh_rows * 0x9E3779B1u) ^ ((unsigned)mesh_cols * 0x85EBCA77u) ^ ((unsigned)final_w * 0xC2B2AE3Du) ^
+                 ((unsigned)final_h * 0x27D4EB2Fu)) | 1;
+}
+__device__ __forceinline__ bool warp_tables_ready(int have, int mesh_rows, int mesh_cols, int final_w, int final_h, int *status) {
+    if (__builtin_expect(have == warp_stamp(mesh_rows, mesh_cols, final_w, final_h), 1)) return true;
+    if ((threadIdx.x & 63) == 0) atomicOr(status, APAP_STATUS_UNPREPARED);
+    return false;
+}
 
 // target coordinate of canvas pixel (i, j) through the (already inverted) cell matrix:
 // float64 FMA chain in the order h0*x + h1*y + h2, then the two divisions by the third
@@ -172,6 +188,89 @@ __device__ __forceinline__ unsigned gather_px(const uint8_t *__restrict__ img, u
     v = __builtin_amdgcn_alignbyte(0u, v, o - oc);
     // v & 0xffffff & ~sign(o): v_bfe_i32 + v_bitop3_b32 (truth table a & b & ~c = 0x40)
     return (unsigned)__builtin_amdgcn_bitop3_b32((int)v, 0x00ffffff, __builtin_amdgcn_sbfe((int)o, 31u, 1u), 0x40);
+}
+
+// ---- bilinear sampling (APAP_OPT_WARP_SAMPLING = APAP_SAMPLING_BILINEAR; the numpy definition is tests/warp_bilinear_spec.py),
+// used by k_warp_bilinear (apap_warp_bilinear.hip) and k_panorama's bilinear forms --------------------------------------------
+
+// strip_source's sibling: the same sequence, the same bits, and the coordinate itself.
+__device__ __forceinline__ bool strip_source_xy(const PixelH &q, double yd, int img_w, int img_h, int &ix, int &iy, double &tx,
+                                                double &ty) {
+    const double t0 = fma(q.h1, yd, q.p0) + q.h2;
+    const double t1 = fma(q.h4, yd, q.p1) + q.h5;
+    const double t2 = fma(q.h7, yd, q.p2) + q.h8;
+    double rc = __builtin_amdgcn_rcp(t2);
+    rc = fma(fma(-t2, rc, 1.0), rc, rc);
+    const double q0 = t0 * rc, q1 = t1 * rc;
+    tx = fma(fma(-t2, q0, t0), rc, q0);
+    ty = fma(fma(-t2, q1, t1), rc, q1);
+    ix = (int)tx;
+    iy = (int)ty;
+    return (tx > 0.0) & (ty > 0.0) & (ix < img_w) & (iy < img_h);
+}
+
+// X = rint(32 t) for 0 <= t < 2^31, split into the tap index X >> 5 and the weight X & 31.  One FMA: 32 t is exact, and the sum
+// with 1.5 x 2^52 lies in [2^52, 2^53), where doubles are the integers - the FMA's single rounding (to nearest, ties to even;
+// the constant is even) IS rint, and the sum's low mantissa bits are X: its low word holds X mod 2^32, bits 0 .. 18 of its high
+// word X >> 32 (X < 2^36 for any side a source of under 4 GiB can have).  Any other t (an absent pixel) gives some pair of
+// numbers.
+__device__ __forceinline__ void fixed_coord(double t, unsigned &s, unsigned &a) {
+    const double d = fma(32.0, t, 6755399441055744.0);
+    const unsigned lo = (unsigned)__double2loint(d), hi = (unsigned)__double2hiint(d);
+    s = __builtin_amdgcn_alignbit(hi, lo, 5u);
+    a = lo & 31u;
+}
+
+// A sample's four taps in one register pair.  off: the byte offset of tap (y0, x0) = (min(sy, h - 1), min(sx, w - 1)) - all 32
+// bits are offset, a source may have up to 4 GiB - 1 bytes, so presence is held apart, in `fr`.  fr: ax | ay << 5 | (x1 > x0) << 10
+// | (y1 > y0) << 11 | present << 12 (bits 16 and up are the caller's); tap (y0, x1) is 3 bytes on when x1 > x0, and row y1 is
+// 3 w bytes on when y1 > y0: the border is replicated.  An absent pixel gets the taps of pixel (0, 0) - addresses that are
+// valid and shared, as the outside marker's are in gather_px - and its value is never used.
+__device__ __forceinline__ void bilinear_taps(bool ok, double tx, double ty, int img_w, int img_h, unsigned &off, unsigned &fr) {
+    unsigned sx, ax, sy, ay;
+    fixed_coord(tx, sx, ax);
+    fixed_coord(ty, sy, ay);
+    sx = ok ? sx : 0u;
+    sy = ok ? sy : 0u;
+    const unsigned x0 = min(sx, (unsigned)img_w - 1u), y0 = min(sy, (unsigned)img_h - 1u);
+    const unsigned stepx = (unsigned)(x0 + 1u < (unsigned)img_w), stepy = (unsigned)(y0 + 1u < (unsigned)img_h);
+    off = (y0 * (unsigned)img_w + x0) * 3u;
+    fr = ax | (ay << 5) | (stepx << 10) | (stepy << 11) | ((unsigned)ok << 12);
+}
+
+// the dword that holds the 3 bytes at byte offset `o` of the source in its low 24 bits (the top byte is whatever follows).
+// For the image's very last pixel the dword one byte earlier, shifted, as in gather_px: no byte beyond the image is touched.
+__device__ __forceinline__ unsigned gather_tap(const uint8_t *__restrict__ img, unsigned o, unsigned last) {
+    unsigned int v;
+    const unsigned oc = o < last ? o : last;
+    __builtin_memcpy(&v, img + oc, 4);
+    return __builtin_amdgcn_alignbyte(0u, v, o - oc);
+}
+
+// the four taps of (off, fr) in the order p00, p01, p10, p11; row_bytes = 3 w
+__device__ __forceinline__ void gather_taps(const uint8_t *__restrict__ img, unsigned off, unsigned fr, unsigned row_bytes,
+                                            unsigned last, unsigned (&p)[4]) {
+    const unsigned dx = (fr & (1u << 10)) ? 3u : 0u, dy = (fr & (1u << 11)) ? row_bytes : 0u;
+    p[0] = gather_tap(img, off, last);
+    p[1] = gather_tap(img, off + dx, last);
+    p[2] = gather_tap(img, off + dy, last);
+    p[3] = gather_tap(img, off + dy + dx, last);
+}
+
+// ((32 - ax)(32 - ay) p00 + ax (32 - ay) p01 + (32 - ax) ay p10 + ax ay p11 + 512) >> 10 per channel as a 24-bit pixel; 0 for an
+// absent sample.  Rows first, channels 0 and 2 side by side in one register (a row's sum is at most 32 x 255 < 2^13), then the
+// columns channel by channel (at most 1024 x 255 + 512 < 2^18): integer sums, so the order does not matter.
+__device__ __forceinline__ unsigned bilinear_blend(const unsigned (&p)[4], unsigned fr) {
+    const unsigned ax = fr & 31u, ay = (fr >> 5) & 31u, bx = 32u - ax, by = 32u - ay;
+    const unsigned t02 = __umul24(bx, p[0] & 0x00ff00ffu) + __umul24(ax, p[1] & 0x00ff00ffu);
+    const unsigned t1 = __umul24(bx, (p[0] >> 8) & 0xffu) + __umul24(ax, (p[1] >> 8) & 0xffu);
+    const unsigned b02 = __umul24(bx, p[2] & 0x00ff00ffu) + __umul24(ax, p[3] & 0x00ff00ffu);
+    const unsigned b1 = __umul24(bx, (p[2] >> 8) & 0xffu) + __umul24(ax, (p[3] >> 8) & 0xffu);
+    const unsigned c0 = (__umul24(by, t02 & 0xffffu) + __umul24(ay, b02 & 0xffffu) + 512u) >> 10;
+    const unsigned c1 = (__umul24(by, t1) + __umul24(ay, b1) + 512u) >> 10;
+    const unsigned c2 = (__umul24(by, t02 >> 16) + __umul24(ay, b02 >> 16) + 512u) >> 10;
+    const unsigned v = c0 | (c1 << 8) | (c2 << 16);
+    return (fr & (1u << 12)) ? v : 0u;
 }
 
 // The stitch of one canvas pixel: paste the centre picture's pixel (ci, cj) - nothing outside the picture - and uniform_blend

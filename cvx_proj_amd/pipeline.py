@@ -141,7 +141,7 @@ class Pipeline:
         return plan
 
     def run_pair(self, src, dst, H_global, other_shape, center_shape, mesh_size=100, gamma=0.5, sigma=100,
-                 other_img=None, center_img=None, want_grid=False, canvas_out=None):
+                 other_img=None, center_img=None, want_grid=False, canvas_out=None, sampling=None):
         """Body of the reference's ``__main__`` between loading and saving (apap.py:238-264): returns
         ``(H_flat (m*m, 9) float64, canvas or None)`` (and the float32 H grid with ``want_grid``); the canvas is
         the warped other image or, with ``center_img``, the blended stitch of apap.py:258-262.
@@ -156,8 +156,10 @@ class Pipeline:
         The solve's tail leaves every cell warp ready, so the warp is the gather kernel alone on tables whose geometry half
         (and the mesh's vertices) were built when this canvas geometry was first seen; the canvas download is the one copy
         left on the critical path (0.5 ms of the 1.04).  ``self.trace = True`` records HIP events at the stage boundaries
-        (``self.device_marks``)."""
+        (``self.device_marks``).  ``sampling``: ``None`` (the context's ``warp_sampling``), ``"nearest"`` or ``"bilinear"``: how
+        the canvas is sampled in this pass."""
         import time
+        _native.sampling_value(sampling, "Pipeline.run_pair")
         from .resident import hip_solve, hip_warp_batch, solve_workspace_bytes, warp_workspace_bytes
         torch = self.torch
         t0 = time.perf_counter()
@@ -254,14 +256,14 @@ class Pipeline:
                         d_cen = self._up("center", np.ascontiguousarray(center_img, dtype=np.uint8), torch.uint8)
                 d_out = self._get("canvas", (fh, fw, 3), torch.uint8)
                 if plan is not None:
-                    plan.gather(d_img, out=d_out.view(1, fh, fw, 3), centers=d_cen)
+                    plan.gather(d_img, out=d_out.view(1, fh, fw, 3), centers=d_cen, sampling=sampling)
                     mark("warp done")
                 else:
                     d_mw = self._up("mesh_w", mesh[0], torch.float64)
                     d_mh = self._up("mesh_h", mesh[1], torch.float64)
                     d_ww = self._get("warp_work", (warp_workspace_bytes((rows, cols), fw, fh),), torch.uint8)
                     hip_warp_batch(d_img, d_H.view(1, cells, 9), d_mw, d_mh, fw, fh, ox, oy, (rows, cols), out=d_out.view(1, fh, fw, 3),
-                                   centers=d_cen, ctx=self.ctx, work=d_ww, status=d_status)
+                                   centers=d_cen, ctx=self.ctx, work=d_ww, status=d_status, sampling=sampling)
             # the status word follows the last kernel into page-locked memory: read after the final synchronisation, no copy of its own
             if getattr(self, "_status_host", None) is None:
                 self._status_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)

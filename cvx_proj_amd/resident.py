@@ -113,22 +113,25 @@ def hip_solve_batch(tables, denorms, vertices, gamma, sigma, ctx=None):
 
 
 def hip_warp_rows(img, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, row_begin, row_count, out_band, shape, ctx=None,
-                  work=None, status=None):
+                  work=None, status=None, sampling=None):
     """Default ``warp_fn`` of :mod:`cvx_proj_amd.dist`: warps canvas rows ``[row_begin, row_begin + row_count)`` of one pair into
-    ``out_band``.  ``work`` / ``status`` are reused when given."""
+    ``out_band``.  ``work`` / ``status`` are reused when given.  ``sampling``: as in :func:`hip_warp_batch`."""
+    _native.sampling_value(sampling, "hip_warp_rows")
     _needs_device(img, "hip_warp_rows")
     return hip_warp_batch(img, H.view(1, -1, 9), mesh_w, mesh_h, final_w, final_h, off_x, off_y, shape, out=out_band, ctx=ctx,
-                          work=work, status=status, rows=(row_begin, row_count))[1]
+                          work=work, status=status, rows=(row_begin, row_count), sampling=sampling)[1]
 
 
 def hip_warp_batch(imgs, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, shape, out=None, centers=None, ctx=None,
-                   work=None, status=None, phases=_native.WARP_ALL, rows=None, hinv_out=None):
+                   work=None, status=None, phases=_native.WARP_ALL, rows=None, hinv_out=None, sampling=None):
     """Backward warp of a BATCH of independent pairs in one set of launches (``apap_warp_batch_device``, grid.z = pair):
     ``imgs`` (B, h, w, 3) uint8 - or (h, w, 3): one image for every pair -, ``H`` (B, cells, 9) float32 (what
     ``hip_solve_batch`` returns), one set of edges, canvas size and offsets for all -> canvases (B, final_h, final_w, 3).
     ``centers`` (B, ch, cw, 3) or (ch, cw, 3): the fused stitch (warp + paste + uniform_blend).  ``phases``: which of
     geometry tables / per-cell set-up / gather run on ``work`` (a caller that keeps ``work`` runs the geometry once).
-    ``rows`` = (row_begin, row_count): a band of every canvas; ``out`` is then (B, row_count, final_w, 3)."""
+    ``rows`` = (row_begin, row_count): a band of every canvas; ``out`` is then (B, row_count, final_w, 3).  ``sampling``:
+    ``None`` (the context's ``warp_sampling``), ``"nearest"`` or ``"bilinear"`` for this call only."""
+    _native.sampling_value(sampling, "hip_warp_batch")
     _needs_device(H, "hip_warp_batch")
     batch, dev = H.shape[0], H.device
     if out is None:
@@ -136,8 +139,9 @@ def hip_warp_batch(imgs, H, mesh_w, mesh_h, final_w, final_h, off_x, off_y, shap
     work = _scratch(work, warp_workspace_bytes(shape, final_w, final_h, batch), dev)
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _warp(ctx, phases, shape, mesh_w, mesh_h, final_w, final_h, off_x, off_y, batch, work, status, imgs=imgs, H=H, out=out,
-          centers=centers, rows=rows, hinv_out=hinv_out)
+    with _native.sampling_scope(ctx, sampling, "hip_warp_batch") as ctx:
+        _warp(ctx, phases, shape, mesh_w, mesh_h, final_w, final_h, off_x, off_y, batch, work, status, imgs=imgs, H=H, out=out,
+              centers=centers, rows=rows, hinv_out=hinv_out)
     return out, status
 
 
@@ -173,10 +177,10 @@ class WarpPlan:
         """``status`` as an int (synchronises)."""
         return int(self.status.cpu()[0])
 
-    def _phase(self, phases, **kw):
+    def _phase(self, phases, ctx=None, **kw):
         fw, fh, ox, oy = self.geo
-        _warp(self.ctx, phases, (self.rows, self.cols), self.mesh_w, self.mesh_h, fw, fh, ox, oy, self.batch, self.work,
-              self.status, **kw)
+        _warp(self.ctx if ctx is None else ctx, phases, (self.rows, self.cols), self.mesh_w, self.mesh_h, fw, fh, ox, oy, self.batch,
+              self.work, self.status, **kw)
 
     def solve(self, tables, denorms, vertices, gamma, sigma, out=None, work=None):
         """``tables`` (B, n, 32) or (n, 32), ``denorms`` (B, 36) or (36,), ``vertices`` (cells, 2) -> H (B * cells, 9) float32, and
@@ -200,12 +204,15 @@ class WarpPlan:
         """Per-cell set-up from a grid that was not solved into this plan (``H`` (B * cells, 9) float32)."""
         self._phase(_native.WARP_CELLS, H=H, hinv_out=hinv_out)
 
-    def gather(self, imgs, out=None, centers=None, rows=None):
-        """K3: ``imgs`` (B, h, w, 3) or (h, w, 3) -> canvases (B, rows, final_w, 3)."""
+    def gather(self, imgs, out=None, centers=None, rows=None, sampling=None):
+        """K3: ``imgs`` (B, h, w, 3) or (h, w, 3) -> canvases (B, rows, final_w, 3).  ``sampling``: ``None`` (the plan's context's
+        ``warp_sampling``), ``"nearest"`` or ``"bilinear"`` for this gather only; the set-up phases do not depend on it."""
+        _native.sampling_value(sampling, "WarpPlan.gather")
         fw, fh, _, _ = self.geo
         if out is None:
             out = torch.empty((self.batch, fh if rows is None else rows[1], fw, 3), dtype=torch.uint8, device=self.dev)
-        self._phase(_native.WARP_GATHER, imgs=imgs, out=out, centers=centers, rows=rows)
+        with _native.sampling_scope(self.ctx, sampling, "WarpPlan.gather") as ctx:
+            self._phase(_native.WARP_GATHER, ctx=ctx, imgs=imgs, out=out, centers=centers, rows=rows)
         return out
 
 
@@ -610,7 +617,7 @@ def panorama_workspace_bytes(layers):
     return _native.lib().apap_panorama_workspace_bytes(_ip(mr), _ip(mc), _ip(fw), _ip(fh), len(layers))
 
 
-def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, work=None, ramp=32):
+def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, work=None, ramp=32, sampling=None):
     """``apap_panorama_device`` (``blend="ramp"``: ``apap_panorama_ramp_device`` with the ramp width ``ramp``, an integer 1 ..
     256 that the other blends ignore) on the current stream of the tensors' device, no host synchronisation: the centre picture and
     every layer on one canvas in one fused pass (``apap.panorama`` on device tensors).  ``center`` (h, w, 3) uint8; a layer is
@@ -620,8 +627,9 @@ def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, 
     layer, zeroed by the caller (default: a new one), into which layer k's set-up ORs its bits at [k]; ``work`` (uint8) is
     used when it holds ``panorama_workspace_bytes(layers)``.  Returns ``(canvas, (W, H, OX, OY), status)``, not synchronised;
     ``_native.raise_for_status(int(status[k]), ...)`` turns a word into the reference's exception.  The grids are not
-    modified."""
+    modified.  ``sampling``: ``None`` (the context's ``warp_sampling``), ``"nearest"`` or ``"bilinear"`` for this call only."""
     who = "hip_panorama"
+    _native.sampling_value(sampling, who)
     _needs_device(center, who)
     dev = center.device
     entry, mode = _native.panorama_entry(blend, ramp, who, device_form=True)
@@ -658,8 +666,9 @@ def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, 
     table = [_addrs([t.data_ptr() for t in ts]) for ts in (imgs, grids, mws, mhs)]
     p_mr, p_mc, p_fw, p_fh = _ip(mr), _ip(mc), _ip(fw), _ip(fh)
     work = _scratch(work, _native.lib().apap_panorama_workspace_bytes(p_mr, p_mc, p_fw, p_fh, n), dev)
-    _native.check(entry(
-        _native._h(ctx), center.data_ptr(), center.shape[0], center.shape[1], table[0], _ip(ih), _ip(iw), table[1], p_mr, p_mc,
-        table[2], _ip(nw), table[3], _ip(nh), p_fw, p_fh, _ip(ox), _ip(oy), n, mode, out.data_ptr(), work.data_ptr(), work.numel(),
-        status.data_ptr(), _stream(dev)))
+    with _native.sampling_scope(ctx, sampling, who) as ctx:
+        _native.check(entry(
+            _native._h(ctx), center.data_ptr(), center.shape[0], center.shape[1], table[0], _ip(ih), _ip(iw), table[1], p_mr, p_mc,
+            table[2], _ip(nw), table[3], _ip(nh), p_fw, p_fh, _ip(ox), _ip(oy), n, mode, out.data_ptr(), work.data_ptr(),
+            work.numel(), status.data_ptr(), _stream(dev)))
     return out, (W, H, OX, OY), status

@@ -39,6 +39,18 @@ int main(int argc, char **argv) {
     for (size_t i = 0; i < (size_t)W * Hh * 3; ++i) img[i] = (unsigned char)(lcg(&seed) & 0xff);
     rc = apap_local_warp(NULL, img, Hh, W, H, ROWS, COLS, mesh_w, COLS + 1, mesh_h, ROWS + 1, fw, fh, ox, oy, out, NULL, -1);
     if (rc) { fprintf(stderr, "local_warp: %s\n", apap_last_error()); return 1; }
+    { /* an option lives in a context: the same warp sampled bilinearly (the default, and the NULL context's, is truncation) */
+        apap_ctx *ctx = apap_ctx_create();
+        rc = ctx ? apap_ctx_set_option(ctx, APAP_OPT_WARP_SAMPLING, APAP_SAMPLING_BILINEAR) : 1;
+        unsigned char *smooth = malloc((size_t)fw * fh * 3);
+        if (!rc) rc = apap_local_warp(ctx, img, Hh, W, H, ROWS, COLS, mesh_w, COLS + 1, mesh_h, ROWS + 1, fw, fh, ox, oy, smooth, NULL, -1);
+        if (rc) { fprintf(stderr, "bilinear local_warp: %s\n", apap_last_error()); return 1; }
+        unsigned long long bs = 0;
+        for (size_t i = 0; i < (size_t)fw * fh * 3; ++i) bs += smooth[i];
+        printf("bilinear_pixel_sum %llu\n", bs);
+        free(smooth);
+        apap_ctx_destroy(ctx);
+    }
     double *flat = malloc(sizeof(double) * ROWS * COLS * 9);
     rc = apap_invert_normalize_flatten(NULL, H, ROWS * COLS, flat, -1);
     if (rc) { fprintf(stderr, "flatten: %s\n", apap_last_error()); return 1; }

@@ -176,7 +176,18 @@ typedef struct apap_ctx apap_ctx;
                                       It moves K1's block-to-tile mapping (and, in a paired launch, the issue priority of its
                                       waves) and nothing else: splits, workspace size, the
                                       moment slabs and the grids are the same bits for every value                        */
-#define APAP_OPT_COUNT 14
+#define APAP_OPT_WARP_SAMPLING 14   /* APAP_SAMPLING_NEAREST (0, default): a canvas pixel is source pixel (int(tx), int(ty)), the
+                                      reference's truncation (apap.py:211-215).  APAP_SAMPLING_BILINEAR (1): the same float64
+                                      coordinate, the same footprint (a pixel is present iff the truncating warp has one there),
+                                      sampled from its four neighbours with 5 fractional bits - X = rint(32 tx), taps at
+                                      X >> 5 and X >> 5 + 1 clamped to the picture (the border is replicated),
+                                      (sum of weight x tap + 512) >> 10 per channel.  Honoured by every warp, stitch, band, batch
+                                      and plan entry point and by the panorama.  APAP_OPT_WARP_ROWS and APAP_OPT_WARP_FAST are
+                                      ignored under bilinear sampling (one all-float64 strip kernel), and so is
+                                      APAP_OPT_OVERLAP_PCIE (the host-buffer warp takes the plain path)                        */
+#define APAP_SAMPLING_NEAREST 0
+#define APAP_SAMPLING_BILINEAR 1
+#define APAP_OPT_COUNT 15
 apap_ctx *apap_ctx_create(void);
 void apap_ctx_destroy(apap_ctx *ctx); /* frees the pooled device buffers and pending events; NULL is a no-op */
 int apap_ctx_set_option(apap_ctx *ctx, int option, int value);
