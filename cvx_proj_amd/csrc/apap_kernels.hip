@@ -446,12 +446,75 @@ __host__ __device__ inline void k1_unit(const K1Pairs &pp, int i, int &tile, int
 
 // D layout of v_mfma_f64_16x16x4_f64: register i of lane l is D[row = (l >> 4) + 4 i][col = l & 15],
 // row = cell within the wave's 16, col = moment index (acc0: 0..15, acc1: 16..31).
-__device__ __forceinline__ int d16_cell(int lane, int i) { return (lane >> 4) + 4 * i; }
-__device__ __forceinline__ int d16_column(int lane) { return lane & 15; }
+__host__ __device__ constexpr int d16_cell(int lane, int i) { return (lane >> 4) + 4 * i; }
+__host__ __device__ constexpr int d16_column(int lane) { return lane & 15; }
 // D[b][i][j] of v_mfma_f64_4x4x4_4b_f64 sits in lane 16 i + 4 b + j: cell 4 b + i of the 16-cell group, column j of the
 // instruction's four (tools/mfma4_layout.hip).
-__device__ __forceinline__ int d4_cell(int lane) { return 4 * ((lane >> 2) & 3) + (lane >> 4); }
-__device__ __forceinline__ int d4_column(int lane) { return lane & 3; }
+__host__ __device__ constexpr int d4_cell(int lane) { return 4 * ((lane >> 2) & 3) + (lane >> 4); }
+__host__ __device__ constexpr int d4_column(int lane) { return lane & 3; }
+
+// How a 16-cell group's sums leave k_assemble_mfma: in the slab ([column][cells_pad]) they are one whole, 128-byte-aligned
+// line per column, so the wave turns its D registers round in LDS - a stage of [column][16 cells], rows kLinePitch bytes apart,
+// written from the D layouts above - and reads it back in the line layout: store j of lane l carries the 16 bytes of cells
+// line_cell(l), line_cell(l) + 1 of column line_column(l, j), so that eight lanes make a line and one store instruction
+// writes eight whole lines (columns 8 j .. 8 j + 7; those from kSums on are not stored: column 30 of a split is column 0 of
+// the next).  The pitch of 144 bytes: the 32 lanes of a ds_write_b64 (16 columns x 2 neighbouring cells: 16-byte pieces 9
+// apart, modulo 16 a permutation) fall on 64 different banks, the 4x4x4 layout's (4 columns x 4 blocks x 2 cells) two to a
+// bank at most, and so do the 16 lanes of a ds_read_b128 (two rows of 8 pieces, 9 apart: the last piece of one row meets the
+// first of the next).
+constexpr int kLinePitch = 144;
+constexpr int kLineStageBytes = 32 * kLinePitch;    // per wave: 32 columns (the 30-sum form stages the keypoint's x, y sums too)
+__host__ __device__ constexpr int line_stage_off(int column, int cell) { return column * kLinePitch + cell * 8; }
+__host__ __device__ constexpr int line_column(int lane, int j) { return 8 * j + (lane >> 3); }
+__host__ __device__ constexpr int line_cell(int lane) { return 2 * (lane & 7); }
+__host__ __device__ constexpr int line_stores(int sums) { return (sums + 7) / 8; }
+// Every (column, cell) the D layouts hold is staged exactly once, and every (column < sums, cell < 16) - and nothing else - is
+// stored exactly once, from 16-byte-aligned stage offsets that never cross a row.
+template <int kSums>
+constexpr bool line_layout_covers() {
+    static_assert(kSums == 30 || kSums == 24, "the two tables");
+    int staged[32][16] = {}, stored[32][16] = {};
+    for (int lane = 0; lane < 64; ++lane) {
+        for (int i = 0; i < 4; ++i) {
+            ++staged[d16_column(lane)][d16_cell(lane, i)];
+            if (kSums == 30) ++staged[16 + d16_column(lane)][d16_cell(lane, i)];
+        }
+        if (kSums == 24) {
+            ++staged[16 + d4_column(lane)][d4_cell(lane)];
+            ++staged[20 + d4_column(lane)][d4_cell(lane)];
+        }
+        for (int j = 0; j < line_stores(kSums); ++j) {
+            const int c = line_column(lane, j);
+            if (c >= 32 || line_cell(lane) + 1 >= 16 || line_stage_off(c, line_cell(lane)) % 16 != 0 ||
+                line_stage_off(c, line_cell(lane) + 1) != line_stage_off(c, line_cell(lane)) + 8)
+                return false;
+            if (c < kSums) ++stored[c][line_cell(lane)], ++stored[c][line_cell(lane) + 1];
+        }
+    }
+    for (int c = 0; c < 32; ++c)
+        for (int cell = 0; cell < 16; ++cell)
+            if (staged[c][cell] != (c < (kSums == 30 ? 32 : 24)) || stored[c][cell] != (c < kSums)) return false;
+    return true;
+}
+static_assert(line_layout_covers<30>() && line_layout_covers<24>(),
+              "the line layout stores every sum of a 16-cell group once, columns from kSums on never, from what the D layouts staged");
+static_assert(kLinePitch % 16 == 0 && 16 * 8 <= kLinePitch && 4 * kLineStageBytes <= 2 * kChunk * 256,
+              "16-byte reads of whole rows; four waves' stages fit the two chunk buffers");
+
+// The slab's stores, 16 bytes of a whole line each, write-through (sc1): the line goes to memory while the kernel runs
+// instead of sitting dirty in the L2 until the boundary to K2, which then waits for 19 MB of write-back.  Measured at C3 on
+// one box with the whole-line epilogue, four alternating passes (profiles/solve_slab_stores.txt), H/s of the headline and
+// K1 + K2 by events:   straight from the D layout (before)  2.729-2.737e8   141.0 + 12.8 us
+//                       plain stores                         2.740-2.749e8   140.2 + 12.4 us
+//                       non-temporal (__builtin_nontemporal_store)  2.744-2.750e8   139.1 + 12.8 us
+//                       write-through                        2.770-2.786e8   138.9 + 12.5 us
+// WRITE_SIZE of the launch is the same for all of them (whole lines: nothing is left to merge in the L2).  K2 follows in a
+// launch of its own on the same stream: nothing is handed over inside a launch, no result depends on the policy.
+typedef double double2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void slab_store_line(double *p, double2_t v) {
+    // (s_nop 1: the store reads its data registers after it has been issued)
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
 
 // --------------------------------------------------------------------------------
 // K1 (VALU variant): lanes = cells, one wave per 64-cell tile and keypoint split (grid.y).
@@ -656,26 +719,46 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
                 step2(w2, buf + off_b0 + 1024 * s1, buf + off_b1 + 1024 * s1);
             }
         }
+        __syncthreads();    // the chunk buffers become the stages below: no wave may still be reading the partial chunk
     }
 
+    // The sums leave in whole lines (line_column, line_cell): each wave turns a group's D registers round in a stage of its
+    // own inside the chunk buffers, which are free now (the barrier that ends the last whole chunk, or the one above), and the
+    // second group of a paired block follows the first through the same stage.  Within the wave the stage's writes and reads
+    // are ordered by the wavefront fences alone: LDS takes a wave's instructions in order.
+    static_assert(kWaves * kLineStageBytes <= (int)sizeof(lds), "a stage per wave");
+    constexpr int kSums = kM24 ? 24 : kMoments;
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);    // (scalar: the stage and the lines' base cost no vector register)
+    unsigned char *stage_lds = &lds[0][0] + wave_u * kLineStageBytes;
 #pragma unroll
     for (int t = 0; t < kGroups; ++t) {
-        const int cell_base = (tile + t) * (16 * kWaves) + wave * 16;
+        const int cell_base = (tile + t) * (16 * kWaves) + wave_u * 16;
+        if (t > 0) {    // the first group's reads before the second's writes
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {       // the 16x16x4 D registers (d16_cell, d16_column)
-            const int ci = cell_base + d16_cell(lane, i);
-            if (ci < cells_pad) {  // an 8-wave block may overhang the padded cell count
-                // (plain stores: non-temporal ones were measured - K1 150.0 -> 148.7 us, but the 128-byte pieces of a moment row no
-                // longer merge in the L2 and WRITE_SIZE grows from 18.8 to 34.1 MB per launch, profiles/r05_solve_experiments.txt)
-                slab[(size_t)d16_column(lane) * cells_pad + ci] = sums[t].acc0[i];
-                if (!kM24 && d16_column(lane) < kMoments - 16) slab[(size_t)(16 + d16_column(lane)) * cells_pad + ci] = sums[t].acc1[i];
-            }
+            *reinterpret_cast<double *>(stage_lds + line_stage_off(d16_column(lane), d16_cell(lane, i))) = sums[t].acc0[i];
+            if constexpr (!kM24)
+                *reinterpret_cast<double *>(stage_lds + line_stage_off(16 + d16_column(lane), d16_cell(lane, i))) = sums[t].acc1[i];
         }
-        if constexpr (kM24) {       // the 4x4x4_4b D registers (d4_cell, d4_column): columns 16 + j and 20 + j
-            const int ci = cell_base + d4_cell(lane);
-            if (ci < cells_pad) {
-                slab[(size_t)(16 + d4_column(lane)) * cells_pad + ci] = sums[t].acc_a;
-                slab[(size_t)(20 + d4_column(lane)) * cells_pad + ci] = sums[t].acc_b;
+        if constexpr (kM24) {               // the 4x4x4_4b D registers (d4_cell, d4_column): columns 16 + j and 20 + j
+            *reinterpret_cast<double *>(stage_lds + line_stage_off(16 + d4_column(lane), d4_cell(lane))) = sums[t].acc_a;
+            *reinterpret_cast<double *>(stage_lds + line_stage_off(20 + d4_column(lane), d4_cell(lane))) = sums[t].acc_b;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (cell_base < cells_pad) {        // a group is inside the padded cell count or outside it as a whole (cells_pad % 16 == 0)
+#pragma unroll
+            for (int j = 0; j < line_stores(kSums); ++j) {
+                const int c = line_column(lane, j);
+                const double2_t v = *reinterpret_cast<const double2_t *>(stage_lds + line_stage_off(c, line_cell(lane)));
+                // (write-through: see slab_store_line.  Non-temporal stores from the D layout, 32-byte pieces of a line per
+                // instruction, once grew WRITE_SIZE from 18.8 to 34.1 MB, profiles/r05_solve_experiments.txt; whole lines do not.)
+                if (c < kSums) slab_store_line(slab + (size_t)c * cells_pad + cell_base + line_cell(lane), v);
             }
         }
     }
@@ -2628,6 +2711,11 @@ static int solve_batch_impl(apap_ctx *ctx, const double *d_tables, int n, const 
                       APAP_VARIANT_MFMA4X2 == APAP_VARIANT_VALU + 3, "k1[] is indexed by the variant");
         const int form = !m24 ? 0 : !w32 ? 1 : 2;
         if (p.variant == APAP_VARIANT_MFMA) {
+            // k_assemble_mfma stores whole 128-byte lines of the slab, 16 bytes per lane: every column of every split and pair
+            // must start on a line (cells_pad % 64 == 0 makes every stride a multiple of 512 bytes).
+            if ((uintptr_t)d_work % 256 != 0 || p.cells_pad % 64 != 0)
+                return apap::fail(APAP_ERR_INVALID_ARG, "apap_solve_device: the workspace must be 256-byte aligned (%p, cells_pad %d)",
+                                  d_work, p.cells_pad);
             // A single pair whose (tile, split) units are more than the chip holds blocks of this form, and fewer than twice as
             // many, goes out as exactly that many blocks, some of them with two tiles (plan_pairs): every block is resident from
             // the start.  The slots: APAP_OPT_PLAN_SLOTS, or what the device says, asked once per context, device and form.

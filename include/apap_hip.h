@@ -327,7 +327,8 @@ size_t apap_solve_workspace_bytes(apap_ctx *ctx, int n, int cells);
  *   d_vertices cells x 2 doubles
  *   d_denorm   APAP_DENORM_DOUBLES doubles     (apap_host_build_denorm)
  *   d_H        cells x 9 floats (output)
- *   d_work     scratch of apap_solve_workspace_bytes(ctx, n, cells) bytes */
+ *   d_work     scratch of apap_solve_workspace_bytes(ctx, n, cells) bytes, 256-byte aligned (as hipMalloc returns it; the
+ *              MFMA variant writes it in whole 128-byte lines and refuses another address with APAP_ERR_INVALID_ARG) */
 int apap_solve_device(apap_ctx *ctx, const double *d_table, int n, const double *d_vertices, int cells,
                       double gamma, double sigma, const double *d_denorm, float *d_H, void *d_work,
                       size_t work_bytes, void *stream);
