@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "apap_internal.h"
+#include "apap_row_term.h"
 #include "apap_warp_dev.h"
 #include "apap_weight_dev.h"
 
@@ -201,17 +202,27 @@ __device__ __forceinline__ double exp_neg_scaled(double yu, const double *tab /*
 // w^2 for the MFMA variant; `scaled_inv_sigma2` = kExpScale * 2 / sigma^2.  The square root is
 // the rsq seed (~2^-23) times a cubic correction: with g = x y and e = 1 - g y,
 // sqrt(x) = g (1 - e)^(-1/2) = g + g e (1/2 + 3/8 e) + O(e^3) -- 5 slots, error < 1 ulp.
-__device__ __forceinline__ double cell_weight_sq_tab(double vx, double vy, double sx, double sy,
-                                                     double scaled_inv_sigma2, double gamma2, const double *tab) {
-    const double dx = vx - sx;
-    const double dy = vy - sy;
-    const double x = fma(dx, dx, fma(dy, dy, 1e-300));
+// Two entries, one chain from x = fma(dx, dx, row term) on (cell_weight_sq_of): cell_weight_sq_tab forms the distance's row
+// term fma(dy, dy, 1e-300), dy = vy - sy, itself; cell_weight_sq_row takes it from its caller (k_assemble_mfma reads it from a
+// side table where a block shares it, apap_row_term.h).
+__device__ __forceinline__ double cell_weight_sq_of(double x, double scaled_inv_sigma2, double gamma2, const double *tab) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y;
     const double e = fma(-g, y, 1.0);
     const double c = fma(e, 0.375, 0.5);
     g = fma(g * e, c, g);
     return fmax(exp_neg_scaled(g * scaled_inv_sigma2, tab), gamma2);
+}
+__device__ __forceinline__ double cell_weight_sq_tab(double vx, double vy, double sx, double sy,
+                                                     double scaled_inv_sigma2, double gamma2, const double *tab) {
+    const double dx = vx - sx;
+    const double dy = vy - sy;
+    return cell_weight_sq_of(fma(dx, dx, fma(dy, dy, 1e-300)), scaled_inv_sigma2, gamma2, tab);
+}
+__device__ __forceinline__ double cell_weight_sq_row(double vx, double sx, double row_term,
+                                                     double scaled_inv_sigma2, double gamma2, const double *tab) {
+    const double dx = vx - sx;
+    return cell_weight_sq_of(fma(dx, dx, row_term), scaled_inv_sigma2, gamma2, tab);
 }
 
 // w^2 in float32 for the opt-in tolerance tier (APAP_OPT_WEIGHTS_F32 with APAP_OPT_MOMENTS = 24): v_sqrt_f32 and
@@ -379,6 +390,11 @@ struct CellWeight {
         else return cell_weight_sq_tab(vx, vy, s.x, s.y, scaled_inv_sigma2, gamma2, exp2);
     }
     __device__ __forceinline__ double sq(const unsigned char *at) const { return sq(read(at)); }
+    // The float64 chain with the row term in hand (a block that shares it): the keypoint's x alone, column 30, and the term.
+    // (The float32 chain has no such entry: k1_mfma_tiles never shares the term there.)
+    __device__ __forceinline__ double sq_row(double sx, double row_term) const {
+        return cell_weight_sq_row(vx, sx, row_term, scaled_inv_sigma2, gamma2, exp2);
+    }
 };
 
 // The sums of 16 cells over the 32 (kM24: 24) table columns, and one step = 4 keypoints of them: the table entries b0 (columns
@@ -611,10 +627,21 @@ __global__ __launch_bounds__(256) void k_assemble_valu(const double *__restrict_
 // that are behind get the issue slots, all four stay within a quarter of each other and the SIMD is full almost to the end
 // (C3, paired: 144.4 -> 139.6 us; all blocks end between 91 and 135 us).  It needs every block resident from the start: on the
 // plain grid, where a second round starts late, it costs 1.2 us (148.7 against 147.5), so that grid's body has none of it.
+// The shared row term (float64 weights; apap_row_term.h): the chain's x = fma(dx, dx, fma(dy, dy, 1e-300)), dy = vy - sy, holds a
+// term that depends on the keypoint and the cell's vy alone, and the cells of a block lie on one or two mesh rows.  A block whose
+// cells hold at most two vy bit patterns (A, its first cell's, and B, the first other in cell order; decided per block in the
+// prologue, on bits, by a vote every wave takes over all the block's cells) has threads 0 .. 127 compute the term once per
+// (keypoint of the chunk, A or B) into s_row[2][kChunk][2] where the chunk is staged - the keypoint's y straight from the
+// table, 0.0 beyond the split's end like the zero rows - and every lane reads the keypoint's x (column 30) and its term: the
+// same two operations on the same operands, 2 of the chain's 24 vector instructions fewer per step, one ds_read_b64 more per
+// group.  Any other block (arbitrary vertices, a mesh narrower than a tile, a pair of tiles on three rows) runs the loop as it
+// was, with the same instruction counts.  The float32-weight form never shares.  tests/test_gpu_k1_row_term.py solves every
+// problem in both ways and compares the workspaces byte for byte; profiles/k1_row_term.txt has the measurements.
 template <int kWaves, bool kM24, bool kW32, int kGroups, bool kLevel>
-__device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 256], double *s_exp2, const double *__restrict__ table,
-                                              const double *__restrict__ vertices, int cells, int cells_pad, double gamma2,
-                                              double inv_sigma2, double *__restrict__ slab, int tile, const K1Block &blk) {
+__device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 256], double *s_exp2, double (&s_row)[2][kChunk][2],
+                                              const double *__restrict__ table, const double *__restrict__ vertices, int cells,
+                                              int cells_pad, double gamma2, double inv_sigma2, double *__restrict__ slab, int tile,
+                                              const K1Block &blk) {
     constexpr int kThreads = kWaves * 64;
     const int tid = threadIdx.x;
     ExpTableStage<kThreads> exp_stage;      // register-staged (see there)
@@ -628,6 +655,58 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
     for (int t = 0; t < kGroups; ++t)
         weight[t].set(cell_vertex(vertices, (tile + t) * (16 * kWaves) + wave * 16 + col, cells), inv_sigma2, gamma2, s_exp2);
     const int p_begin = blk.p_begin, p_end = blk.p_end, nchunks = blk.nchunks;
+
+    // Does the block share the row term?  A: the vy of its first cell; B: the first vy in cell order that is not A (through
+    // cell_vertex's clamp, over both tiles of a paired block) - on a mesh the last cell's, and a block whose rows go A, B, A
+    // shares too.  Every wave looks at all the block's cells, one or two a lane, and votes among its own lanes: the same cells
+    // in every wave, so the answer is block-uniform without a barrier or a word of LDS.  Bit patterns only.
+    constexpr bool kCanShare = !kW32;
+    bool share = false;
+    double row_v = 0.0;         // the value this wave writes terms for (wave 0: A, wave 1: B; the others write none)
+    bool row_owner = false;
+    int off_row[kGroups];       // this lane's constant part of its term's address, per group (row_read_off)
+    if constexpr (kCanShare) {
+        static_assert(kWaves == 4 && kThreads >= apap::kRowOwners && kChunk == apap::kRowChunk, "the side table's owners");
+        const int first = tile * (16 * kWaves);
+        auto uniform_bits = [](double v) {
+            const long long b = __double_as_longlong(v);
+            return (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
+                               (unsigned)__builtin_amdgcn_readfirstlane((int)b));
+        };
+        const long long a_bits = uniform_bits(cell_vertex(vertices, first, cells).y);
+        long long seen[kGroups];    // the vy of cell first + 64 t + lane
+#pragma unroll
+        for (int t = 0; t < kGroups; ++t) seen[t] = __double_as_longlong(cell_vertex(vertices, first + 64 * t + lane, cells).y);
+        long long b_bits = a_bits;  // apap::row_second_value: the first in cell order that is not A
+#pragma unroll
+        for (int t = kGroups - 1; t >= 0; --t) {
+            const unsigned long long other = __ballot(seen[t] != a_bits);
+            const int l = other ? __builtin_ctzll(other) : 0;
+            const long long there = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(seen[t] >> 32), l) << 32) |
+                                                (unsigned)__builtin_amdgcn_readlane((int)seen[t], l));
+            b_bits = other ? there : b_bits;
+        }
+        bool mine = true;
+#pragma unroll
+        for (int t = 0; t < kGroups; ++t) mine = mine && apap::row_is_shared(seen[t], a_bits, b_bits);
+        share = __all(mine);
+        const int wave_r = __builtin_amdgcn_readfirstlane(wave);
+        row_owner = wave_r < apap::kRowOwners / 64;
+        row_v = __longlong_as_double(apap::row_owner_value(wave_r * 64) == 0 ? a_bits : b_bits);
+#pragma unroll
+        for (int t = 0; t < kGroups; ++t)
+            off_row[t] = apap::row_read_off(0, 0, kgrp, apap::row_value(__double_as_longlong(weight[t].vy), a_bits));
+    }
+    // The side table's producer (threads 0 .. 127 of a sharing block): the keypoint's y straight from the table, 0.0 for the
+    // rows from p_end on (what the chunk's zero rows hold), then the chain's own two operations on the chain's own operands.
+    auto row_fetch = [&](int first_row) {
+        const int p = first_row + apap::row_owner_keypoint(tid);
+        return p < p_end ? table[(size_t)p * APAP_TABLE_STRIDE + 31] : 0.0;
+    };
+    auto row_publish = [&](int buffer, double sy) {
+        const double dy = row_v - sy;
+        s_row[buffer][apap::row_owner_keypoint(tid)][apap::row_owner_value(tid)] = fma(dy, dy, 1e-300);
+    };
 
     ChunkStage<kThreads> stage;
     const int off_xy = lds_off(kgrp, CellWeight<kW32>::kXyColumn), off_b0 = lds_off(kgrp, col);
@@ -643,8 +722,17 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
         for (int t = 0; t < kGroups; ++t) sums[t].step(w2[t], b0, b1, b1b);
     };
     if (nchunks > 0) chunk_load<kThreads>(stage, table, tid, p_begin, p_end);
+    // The first chunk's terms, whether the block shares them or not: asked for only once the vote is in, the keypoints' y
+    // would cost every block a second memory latency in a row before its first barrier.
+    double row_y0 = 0.0;
+    if constexpr (kCanShare) {
+        if (row_owner && nchunks > 0) row_y0 = row_fetch(p_begin);
+    }
     exp_stage.publish(s_exp2, tid);  // visible after the barrier
     if (nchunks > 0) APAP_CHUNK_STORE(kThreads, lds[0], stage, tid);
+    if constexpr (kCanShare) {
+        if (row_owner && nchunks > 0) row_publish(0, row_y0);
+    }
     __syncthreads();
     // Drain the prologue's loads (vertex, first chunk) here: otherwise the compiler's wait
     // for the vertex registers lands inside the step loop as vmcnt(0) and also waits for
@@ -657,69 +745,119 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
     // (Also round 6, not kept: ONE block of 8 waves running both keypoint splits of its 64 cells and adding them through LDS
     // before it stores one slab - bit-identical, K2 8.4 -> 7.2 us, but K1 147.5 -> 173 us: eight waves on one barrier per
     // chunk, two 68 KB blocks per CU.  profiles/r06_k1_compiler.txt.)
+    // The loops exist twice: kRow = false is the loop as it has always been (every lane forms the row term itself), kRow = true
+    // the one of a block that shares it - the keypoint's x and the lane's term from LDS, x = fma(dx, dx, term), and the terms
+    // of chunk c + 1 written where chunk c + 1 is staged.
     const int nfull = (p_end - p_begin) / kChunk;
-    for (int c = 0; c < nfull; ++c) {
-        if constexpr (kLevel) {
-            if (4 * c < nfull) __builtin_amdgcn_s_setprio(3);           // the level is an immediate of the instruction
-            else if (4 * c < 2 * nfull) __builtin_amdgcn_s_setprio(2);
-            else if (4 * c < 3 * nfull) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-        }
-        if (c + 1 < nchunks) chunk_load<kThreads>(stage, table, tid, p_begin + (c + 1) * kChunk, p_end);
-        const unsigned char *buf = lds[c & 1];
-        // The weights of g steps first, then their 2 g MFMAs back to back: g times fewer MFMA <-> VALU
-        // transitions (~10 issue cycles each, profiles/r02_coexec.txt) and g independent weight chains
-        // for the scheduler.  Same MFMAs in the same order per accumulator: bit-identical sums.
-        // A/B at C3 on one box (tools/ab_build.sh): g = 1: 169.5-170.7 us, 2: 165.5-166.3, 4: 165.5-166.1,
-        // 8: 163.8-164.1, 16: 163.9-164.2.  (s_setprio 1 / 3 around the MFMA group: +-1 %; a 128-keypoint
-        // chunk: +4 %; profiles/r02_k1_variants.txt.)
-        if constexpr (kGroups == 1) {
-#pragma unroll
-            for (int s0 = 0; s0 < kChunk / 4; s0 += 8) {
-                double w2[8];
-#pragma unroll
-                for (int g = 0; g < 8; ++g) w2[g] = weight[0].sq(buf + off_xy + 1024 * (s0 + g));
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int g = 0; g < 8; ++g) sums[0].step(w2[g], buf + off_b0 + 1024 * (s0 + g), buf + off_b1 + 1024 * (s0 + g));
-                __builtin_amdgcn_sched_barrier(0);
+    auto chunks = [&](auto row_tag) {
+        constexpr bool kRow = decltype(row_tag)::value;
+        // w^2 of group t for the keypoint of step s: the weight chain's two entries
+        auto w2_row = [&](int t, double sx, const unsigned char *rbuf, int s) {
+            return weight[t].sq_row(sx, *reinterpret_cast<const double *>(rbuf + off_row[t] + apap::kRowStepBytes * s));
+        };
+        for (int c = 0; c < nfull; ++c) {
+            if constexpr (kLevel) {
+                if (4 * c < nfull) __builtin_amdgcn_s_setprio(3);           // the level is an immediate of the instruction
+                else if (4 * c < 2 * nfull) __builtin_amdgcn_s_setprio(2);
+                else if (4 * c < 3 * nfull) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
             }
-        } else {
-            // (float32 weights: 2 steps x 2 groups, which keeps that form within the 96 registers of its five waves per SIMD)
-            constexpr int kSteps = kW32 ? 2 : 4;
-#pragma unroll
-            for (int s0 = 0; s0 < kChunk / 4; s0 += kSteps) {
-                double w2[kSteps][kGroups];
-#pragma unroll
-                for (int g = 0; g < kSteps; ++g) {
-                    const auto xy = CellWeight<kW32>::read(buf + off_xy + 1024 * (s0 + g));
-#pragma unroll
-                    for (int t = 0; t < kGroups; ++t) w2[g][t] = weight[t].sq(xy);
+            // (the next chunk's registers belong to this pass: loaded and stored under the same condition.  As one variable with
+            // the prologue's, shared by the two forms of the loop, the first chunk's 16 registers stayed live through the loops.)
+            ChunkStage<kThreads> next;
+            double row_y = 0.0;
+            if (c + 1 < nchunks) {
+                chunk_load<kThreads>(next, table, tid, p_begin + (c + 1) * kChunk, p_end);
+                if constexpr (kRow) {
+                    if (row_owner) row_y = row_fetch(p_begin + (c + 1) * kChunk);
                 }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int g = 0; g < kSteps; ++g) step2(w2[g], buf + off_b0 + 1024 * (s0 + g), buf + off_b1 + 1024 * (s0 + g));
-                __builtin_amdgcn_sched_barrier(0);
             }
-        }
-        if (c + 1 < nchunks) APAP_CHUNK_STORE(kThreads, lds[(c + 1) & 1], stage, tid);
-        __syncthreads();
-    }
-    if (nfull < nchunks) {      // the partial last chunk (staged and published by the loop's last pass, or by the prologue)
-        const unsigned char *buf = lds[nfull & 1];
-        const int steps_here = (p_end - p_begin - nfull * kChunk + 3) >> 2;
-        for (int s1 = 0; s1 < steps_here; ++s1) {
+            const unsigned char *buf = lds[c & 1];
+            const unsigned char *rbuf = reinterpret_cast<const unsigned char *>(s_row[c & 1]);
+            // The weights of g steps first, then their 2 g MFMAs back to back: g times fewer MFMA <-> VALU
+            // transitions (~10 issue cycles each, profiles/r02_coexec.txt) and g independent weight chains
+            // for the scheduler.  Same MFMAs in the same order per accumulator: bit-identical sums.
+            // A/B at C3 on one box (tools/ab_build.sh): g = 1: 169.5-170.7 us, 2: 165.5-166.3, 4: 165.5-166.1,
+            // 8: 163.8-164.1, 16: 163.9-164.2.  (s_setprio 1 / 3 around the MFMA group: +-1 %; a 128-keypoint
+            // chunk: +4 %; profiles/r02_k1_variants.txt.)
             if constexpr (kGroups == 1) {
-                sums[0].step(weight[0].sq(buf + off_xy + 1024 * s1), buf + off_b0 + 1024 * s1, buf + off_b1 + 1024 * s1);
-            } else {
-                const auto xy = CellWeight<kW32>::read(buf + off_xy + 1024 * s1);
-                double w2[kGroups];
 #pragma unroll
-                for (int t = 0; t < kGroups; ++t) w2[t] = weight[t].sq(xy);
-                step2(w2, buf + off_b0 + 1024 * s1, buf + off_b1 + 1024 * s1);
+                for (int s0 = 0; s0 < kChunk / 4; s0 += 8) {
+                    double w2[8];
+#pragma unroll
+                    for (int g = 0; g < 8; ++g) {
+                        if constexpr (kRow) w2[g] = w2_row(0, *reinterpret_cast<const double *>(buf + off_xy + 1024 * (s0 + g)), rbuf, s0 + g);
+                        else w2[g] = weight[0].sq(buf + off_xy + 1024 * (s0 + g));
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int g = 0; g < 8; ++g) sums[0].step(w2[g], buf + off_b0 + 1024 * (s0 + g), buf + off_b1 + 1024 * (s0 + g));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            } else {
+                // (float32 weights: 2 steps x 2 groups, which keeps that form within the 96 registers of its five waves per SIMD)
+                constexpr int kSteps = kW32 ? 2 : 4;
+#pragma unroll
+                for (int s0 = 0; s0 < kChunk / 4; s0 += kSteps) {
+                    double w2[kSteps][kGroups];
+#pragma unroll
+                    for (int g = 0; g < kSteps; ++g) {
+                        if constexpr (kRow) {       // the keypoint's x once for both groups, each group its own term
+                            const double sx = *reinterpret_cast<const double *>(buf + off_xy + 1024 * (s0 + g));
+#pragma unroll
+                            for (int t = 0; t < kGroups; ++t) w2[g][t] = w2_row(t, sx, rbuf, s0 + g);
+                        } else {
+                            const auto xy = CellWeight<kW32>::read(buf + off_xy + 1024 * (s0 + g));
+#pragma unroll
+                            for (int t = 0; t < kGroups; ++t) w2[g][t] = weight[t].sq(xy);
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int g = 0; g < kSteps; ++g) step2(w2[g], buf + off_b0 + 1024 * (s0 + g), buf + off_b1 + 1024 * (s0 + g));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
+            if (c + 1 < nchunks) {
+                APAP_CHUNK_STORE(kThreads, lds[(c + 1) & 1], next, tid);
+                if constexpr (kRow) {
+                    if (row_owner) row_publish((c + 1) & 1, row_y);
+                }
+            }
+            __syncthreads();
         }
-        __syncthreads();    // the chunk buffers become the stages below: no wave may still be reading the partial chunk
+        if (nfull < nchunks) {      // the partial last chunk (staged and published by the loop's last pass, or by the prologue)
+            const unsigned char *buf = lds[nfull & 1];
+            const unsigned char *rbuf = reinterpret_cast<const unsigned char *>(s_row[nfull & 1]);
+            const int steps_here = (p_end - p_begin - nfull * kChunk + 3) >> 2;
+            for (int s1 = 0; s1 < steps_here; ++s1) {
+                if constexpr (kGroups == 1) {
+                    double w2;
+                    if constexpr (kRow) w2 = w2_row(0, *reinterpret_cast<const double *>(buf + off_xy + 1024 * s1), rbuf, s1);
+                    else w2 = weight[0].sq(buf + off_xy + 1024 * s1);
+                    sums[0].step(w2, buf + off_b0 + 1024 * s1, buf + off_b1 + 1024 * s1);
+                } else {
+                    double w2[kGroups];
+                    if constexpr (kRow) {
+                        const double sx = *reinterpret_cast<const double *>(buf + off_xy + 1024 * s1);
+#pragma unroll
+                        for (int t = 0; t < kGroups; ++t) w2[t] = w2_row(t, sx, rbuf, s1);
+                    } else {
+                        const auto xy = CellWeight<kW32>::read(buf + off_xy + 1024 * s1);
+#pragma unroll
+                        for (int t = 0; t < kGroups; ++t) w2[t] = weight[t].sq(xy);
+                    }
+                    step2(w2, buf + off_b0 + 1024 * s1, buf + off_b1 + 1024 * s1);
+                }
+            }
+            __syncthreads();    // the chunk buffers become the stages below: no wave may still be reading the partial chunk
+        }
+    };
+    if constexpr (kCanShare) {
+        if (share) chunks(std::true_type{});
+        else chunks(std::false_type{});
+    } else {
+        chunks(std::false_type{});
     }
 
     // The sums leave in whole lines (line_column, line_cell): each wave turns a group's D registers round in a stage of its
@@ -772,6 +910,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__r
                                                        BatchStride bs, K1Pairs pp) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2][kChunk * 256];
     __shared__ double s_exp2[kExpN];
+    __shared__ __attribute__((aligned(16))) double s_row[2][kChunk][2];     // the shared row terms (apap_row_term.h)
     int tile = blockIdx.x, split = blockIdx.y;
     bool paired = false;
     if (pp.pairs > 0) k1_unit(pp, (int)blockIdx.x, tile, split, paired);    // block-uniform
@@ -779,11 +918,11 @@ __global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__r
     constexpr int kSums = kM24 ? 24 : kMoments;
     double *slab = moments + (long long)blockIdx.z * bs.moments + (size_t)split * kSums * cells_pad;
     if (paired)
-        k1_mfma_tiles<kWaves, kM24, kW32, 2, true>(lds, s_exp2, table, vertices, cells, cells_pad, gamma2, inv_sigma2, slab, tile, blk);
+        k1_mfma_tiles<kWaves, kM24, kW32, 2, true>(lds, s_exp2, s_row, table, vertices, cells, cells_pad, gamma2, inv_sigma2, slab, tile, blk);
     else if (pp.pairs > 0)
-        k1_mfma_tiles<kWaves, kM24, kW32, 1, true>(lds, s_exp2, table, vertices, cells, cells_pad, gamma2, inv_sigma2, slab, tile, blk);
+        k1_mfma_tiles<kWaves, kM24, kW32, 1, true>(lds, s_exp2, s_row, table, vertices, cells, cells_pad, gamma2, inv_sigma2, slab, tile, blk);
     else        // the plain grid: the loop as it has always been
-        k1_mfma_tiles<kWaves, kM24, kW32, 1, false>(lds, s_exp2, table, vertices, cells, cells_pad, gamma2, inv_sigma2, slab, tile, blk);
+        k1_mfma_tiles<kWaves, kM24, kW32, 1, false>(lds, s_exp2, s_row, table, vertices, cells, cells_pad, gamma2, inv_sigma2, slab, tile, blk);
 }
 
 // --------------------------------------------------------------------------------

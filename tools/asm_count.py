@@ -13,7 +13,14 @@
    steady state.  The steady state is taken from the code itself: every backward branch whose body holds an MFMA (the VALU
    K1 has none: v_rsq_f64, the head of its weight chain) closes a loop; inside the outermost such body the sequence runs
    from the first instruction of a weight chain (v_rsq_f64, v_sqrt_f32) or MFMA to the last s_barrier (the one that closes
-   the chunk loop), or to the closing branch where the loop has no barrier.  Prefetch loads at the loop's top are outside it."""
+   the chunk loop), or to the closing branch where the loop has no barrier.  Prefetch loads at the loop's top are outside it.
+
+   Loop table: every loop of a kernel that holds an MFMA, in file order, one line each.
+   tools/asm_count.py --loops [file.s] k_assemble_mfmaILi4ELb0ELb0E
+   Instructions from the loop's label to its backward branch, and of its largest basic block (the unrolled steps), with the
+   MFMAs, LDS reads and float64 adds and fused multiply-adds inside.  k_assemble_mfma with float64 weights has twelve: per body
+   (plain grid, levelled, paired) the chunk loop and the partial-chunk loop of a block that forms the row term in every lane,
+   then the two of a block that shares it (2 v_add_f64 and 1 FMA fewer per weight chain, one ds_read_b64 more per group)."""
 import os
 import re
 import sys
@@ -56,6 +63,32 @@ def steady(ins, lab):
     head = next(k for k in range(lo, hi + 1) if ops[k].startswith(("v_rsq_f64", "v_sqrt_f32", "v_mfma")))
     bars = [k for k in range(head, hi + 1) if ops[k] == "s_barrier"]
     return ops[head:(bars[-1] if bars else hi) + 1]
+
+
+def loops(path, names):
+    lab = {}
+    for name, ins in kernels(path, lab).items():
+        if names and not any(n in name for n in names):
+            continue
+        ops = [i.split()[0] for i in ins]
+        starts = sorted(set(lab[name].values()))
+        found = []
+        for k, i in enumerate(ins):
+            if ops[k].startswith(("s_cbranch", "s_branch")) and lab[name].get(i.split()[-1], k + 1) <= k:
+                t = lab[name][i.split()[-1]]
+                if any(o.startswith("v_mfma") for o in ops[t:k]):
+                    found.append((t, k))
+        found = [f for f in found if not any(g != f and f[0] <= g[0] and g[1] <= f[1] for g in found)]     # innermost
+        print(f"{name}: {len(ins)} instructions, {len(found)} loops with MFMAs")
+        for t, k in found:
+            cuts = [t] + [b for b in starts if t < b <= k] + [k + 1]
+            big = max(zip(cuts, cuts[1:]), key=lambda ab: ab[1] - ab[0])
+            body = ops[big[0]:big[1]]
+            c = Counter(ops[t:k + 1])
+            grp = lambda pre: sum(n for o, n in c.items() if o.startswith(pre))  # noqa: E731
+            print(f"    {k + 1 - t:5d} instructions ({len(body)} in the largest block): v_mfma {grp('v_mfma')}, ds_read {grp('ds_read')}, "
+                  f"v_add_f64 {grp('v_add_f64')}, FMA f64 {grp(('v_fma_f64', 'v_fmac_f64'))}, VALU {grp('v_') - grp('v_mfma')}, "
+                  f"s_barrier {c['s_barrier']}")
 
 
 def compare(path_a, path_b, names):
@@ -110,6 +143,10 @@ if __name__ == "__main__":
     args = sys.argv[1:]
     if args and args[0] == "--compare":
         compare(args[1], args[2], args[3:])
+    elif args and args[0] == "--loops":
+        args.pop(0)
+        default = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cvx_proj_amd/csrc/apap_kernels.gfx950.s")
+        loops(args.pop(0) if args and args[0].endswith(".s") else default, args)
     else:
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cvx_proj_amd/csrc/apap_kernels.gfx950.s")
         if args and args[0].endswith(".s"):
