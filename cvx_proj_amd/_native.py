@@ -232,6 +232,22 @@ SIGNATURES = {
 # the ramp's entry points: the argument lists of apap_panorama / apap_panorama_device with `ramp` in place of `mode`
 SIGNATURES["apap_panorama_ramp"] = SIGNATURES["apap_panorama"]
 SIGNATURES["apap_panorama_ramp_device"] = SIGNATURES["apap_panorama_device"]
+# gain compensation: the geometry arguments of apap_panorama (up to n_layers) / apap_panorama_device, then each entry point's own
+_u64p = C.POINTER(C.c_ulonglong)
+_PANO_GEOMETRY = SIGNATURES["apap_panorama"][1][:19]
+_PANO_GEOMETRY_DEVICE = SIGNATURES["apap_panorama_device"][1][:19]
+SIGNATURES.update({
+    "apap_panorama_gain_solve": (C.c_int, [_u64p, _u64p, C.c_int, C.c_double, C.c_double, _f64p, _i32p, _i32p]),
+    "apap_panorama_gain_apply": (C.c_int, [_u8p, C.c_int, C.c_int, _u8p]),
+    "apap_panorama_gain_stats": (C.c_int, _PANO_GEOMETRY + [C.c_int, _u64p, _u64p, _i32p, C.c_int]),
+    "apap_panorama_gain_stats_device": (C.c_int, _PANO_GEOMETRY_DEVICE + [C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "apap_panorama_gain": (C.c_int, _PANO_GEOMETRY + [C.c_int, C.c_int, _i32p, _u8p, _i32p, C.c_int]),
+    "apap_panorama_gain_device": (C.c_int, _PANO_GEOMETRY_DEVICE + [C.c_int, C.c_int, _i32p, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "apap_panorama_auto_gain": (C.c_int, _PANO_GEOMETRY + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _u8p, _u64p, _u64p, _f64p,
+                                                           _i32p, _i32p, _i32p, C.c_int]),
+    "apap_panorama_auto_gain_device": (C.c_int, _PANO_GEOMETRY_DEVICE + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp,
+                                                                         _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+})
 
 _lib = None
 _torch_at_load = False      # was torch in the process when the library was loaded?  (cvx_proj_amd.resident refuses otherwise)
@@ -1347,20 +1363,61 @@ def panorama_ramp_quotients(total, wsum):
     return out
 
 
-def panorama(center, layers, blend="mean", device=-1, ctx=None, return_status=False, ramp=32, sampling=None):
-    """See :func:`_panorama`; ``sampling``: ``None`` (the context's ``warp_sampling``), ``"nearest"`` or ``"bilinear"`` for this
-    call only - every layer is then sampled that way."""
-    with sampling_scope(ctx, sampling, "panorama") as ctx:
-        return _panorama(center, layers, blend, device, ctx, return_status, ramp)
+PANORAMA_RAMP = 2                    # APAP_PANORAMA_RAMP: a mode of the gain entry points only
+PANORAMA_GAIN_MAX_STEP = 64         # APAP_PANORAMA_GAIN_MAX_STEP
+PANORAMA_GAIN_MIN_Q, PANORAMA_GAIN_MAX_Q = 1024, 16383
 
 
-def _panorama(center, layers, blend, device, ctx, return_status, ramp):
-    """``apap_panorama`` (``blend`` 'mean' or 'paste') or ``apap_panorama_ramp`` ('ramp', with the ramp width ``ramp``, which the
-    other blends ignore): the centre picture and every layer (a :class:`PanoramaLayer` or a 5-tuple in its order) on one canvas.
-    Returns ``(canvas (H, W, 3) uint8, (W, H, OX, OY))`` - with ``return_status=True`` also the per-layer status words, and
-    then a status does not raise.  Neither the grids nor any other input is modified."""
-    who = "panorama"
-    entry, mode = panorama_entry(blend, ramp, who)
+class PanoramaGains(NamedTuple):
+    """Gain compensation of a panorama's K + 1 views (the centre first): ``gains`` float64, ``q = clamp(rint(4096 gains), 1024,
+    16383)`` int32, and the overlap statistics ``N``, ``S`` (K + 1, K + 1) uint64 they were fitted to."""
+    gains: object
+    q: object
+    N: object
+    S: object
+
+
+def panorama_gain_mode(blend, ramp, who="panorama"):
+    """(mode, ramp) of the gain entry points, which take the ramp as a mode."""
+    if blend != "ramp":
+        return panorama_mode(blend, who), 0
+    panorama_entry(blend, ramp, who)
+    return PANORAMA_RAMP, int(ramp)
+
+
+def panorama_gain_q(gain_q, n_views, who="panorama"):
+    """``gain_q`` as the int32 array of ``n_views`` values the library takes (it checks their range)."""
+    q = np.asarray(gain_q)
+    if q.shape != (n_views,) or q.dtype.kind not in "iu":
+        raise ValueError(f"{who}: gain_q must be {n_views} integers (the centre, then every layer); got {gain_q!r}")
+    if (q < -2 ** 31).any() or (q >= 2 ** 31).any():
+        raise ValueError(f"{who}: gain_q beyond int32")
+    return np.ascontiguousarray(q, dtype=np.int32)
+
+
+def panorama_gain_apply(values, q):
+    """``apap_panorama_gain_apply`` (host only): ``min(255, (c q + 2048) >> 12)`` of every byte of ``values``."""
+    values = np.ascontiguousarray(values, dtype=np.uint8)
+    out = np.empty_like(values)
+    check(lib().apap_panorama_gain_apply(_ptr(values, C.c_uint8), int(values.size), int(q), _ptr(out, C.c_uint8)))
+    return out
+
+
+def panorama_gain_solve(N, S, sigma_n=10.0, sigma_g=0.1):
+    """``apap_panorama_gain_solve`` (host only): ``(g float64, q int32, flag)`` of the (V, V) uint64 overlap statistics - the
+    bits the device solve of the resident chain gives."""
+    N, S = np.ascontiguousarray(N, dtype=np.uint64), np.ascontiguousarray(S, dtype=np.uint64)
+    if N.ndim != 2 or N.shape[0] != N.shape[1] or S.shape != N.shape:
+        raise ValueError(f"panorama_gain_solve: N and S must be (V, V); got {N.shape} and {S.shape}")
+    v = N.shape[0]
+    g, q, flag = np.zeros(v, np.float64), np.zeros(v, np.int32), np.zeros(1, np.int32)
+    check(lib().apap_panorama_gain_solve(_ptr(N, C.c_ulonglong), _ptr(S, C.c_ulonglong), v, float(sigma_n), float(sigma_g),
+                                         _ptr(g, C.c_double), _ip(q), _ip(flag)))
+    return g, q, int(flag[0])
+
+
+def _panorama_inputs(center, layers, who):
+    """The host arrays of a panorama call and its leading C arguments after the context: (args, keep-alive, n, bounds)."""
     layers, (fw, fh, ox, oy) = panorama_geometry(layers, who)
     n = len(layers)
     center = np.ascontiguousarray(center, dtype=np.uint8)
@@ -1381,12 +1438,76 @@ def _panorama(center, layers, blend, device, ctx, return_status, ramp):
     ih, iw = _i32([a.shape[0] for a in imgs]), _i32([a.shape[1] for a in imgs])
     mr, mc = _i32([a.shape[0] for a in grids]), _i32([a.shape[1] for a in grids])
     nw, nh = _i32([a.size for a in mws]), _i32([a.size for a in mhs])
-    W, Hc, OX, OY = panorama_bounds(center.shape, fw, fh, ox, oy)
+    bounds = panorama_bounds(center.shape, fw, fh, ox, oy)
+    p = [_addrs([a.ctypes.data for a in arrs]) for arrs in (imgs, grids, mws, mhs)]
+    args = [_ptr(center, C.c_uint8), center.shape[0], center.shape[1], p[0], _ip(ih), _ip(iw), p[1], _ip(mr), _ip(mc),
+            p[2], _ip(nw), p[3], _ip(nh), _ip(fw), _ip(fh), _ip(ox), _ip(oy), n]
+    return args, (center, imgs, grids, mws, mhs, ih, iw, mr, mc, nw, nh, fw, fh, ox, oy, p), n, bounds
+
+
+def _gain_step(step, who):
+    if isinstance(step, bool) or not isinstance(step, (int, np.integer)):
+        raise ValueError(f"{who}: the lattice step must be an integer 1 .. {PANORAMA_GAIN_MAX_STEP}; got {step!r}")
+    return int(step)
+
+
+def panorama_gain_stats(center, layers, step=4, device=-1, ctx=None, sampling=None):
+    """``apap_panorama_gain_stats``: ``(N, S)``, the (K + 1, K + 1) uint64 overlap statistics of the centre and the layers over
+    the canvas pixels with ``X % step == 0 and Y % step == 0``."""
+    who = "panorama_gain_stats"
+    step = _gain_step(step, who)
+    with sampling_scope(ctx, sampling, who) as ctx:
+        args, keep, n, _ = _panorama_inputs(center, layers, who)
+        N, S = np.zeros((n + 1, n + 1), np.uint64), np.zeros((n + 1, n + 1), np.uint64)
+        status = np.zeros(n, np.int32)
+        check(lib().apap_panorama_gain_stats(_h(ctx), *args, step, _ptr(N, C.c_ulonglong), _ptr(S, C.c_ulonglong), _ip(status), device))
+    return N, S
+
+
+def panorama(center, layers, blend="mean", device=-1, ctx=None, return_status=False, ramp=32, sampling=None, gain_q=None):
+    """See :func:`_panorama`; ``sampling``: ``None`` (the context's ``warp_sampling``), ``"nearest"`` or ``"bilinear"`` for this
+    call only - every layer is then sampled that way.  ``gain_q``: ``None``, or K + 1 integers 1024 .. 16383 (4096 = 1.0), the
+    gain of the centre and of every layer (``apap_panorama_gain``)."""
+    with sampling_scope(ctx, sampling, "panorama") as ctx:
+        return _panorama(center, layers, blend, device, ctx, return_status, ramp, gain_q)
+
+
+def panorama_auto_gain(center, layers, blend="mean", device=-1, ctx=None, ramp=32, sampling=None, step=4, sigma_n=10.0, sigma_g=0.1):
+    """``apap_panorama_auto_gain``: the statistics, the solve and the gained blend in one call.  Returns ``(canvas, (W, H, OX,
+    OY), PanoramaGains)``."""
+    who = "panorama"
+    step = _gain_step(step, who)
+    mode, width = panorama_gain_mode(blend, ramp, who)
+    with sampling_scope(ctx, sampling, who) as ctx:
+        args, keep, n, (W, Hc, OX, OY) = _panorama_inputs(center, layers, who)
+        out = np.empty((Hc, W, 3), np.uint8)
+        N, S = np.zeros((n + 1, n + 1), np.uint64), np.zeros((n + 1, n + 1), np.uint64)
+        g, q, flag, status = np.zeros(n + 1, np.float64), np.zeros(n + 1, np.int32), np.zeros(1, np.int32), np.zeros(n, np.int32)
+        check(lib().apap_panorama_auto_gain(_h(ctx), *args, mode, width, step, float(sigma_n), float(sigma_g), _ptr(out, C.c_uint8),
+                                            _ptr(N, C.c_ulonglong), _ptr(S, C.c_ulonglong), _ptr(g, C.c_double), _ip(q), _ip(flag),
+                                            _ip(status), device))
+    return out, (W, Hc, OX, OY), PanoramaGains(g, q, N, S)
+
+
+def _panorama(center, layers, blend, device, ctx, return_status, ramp, gain_q=None):
+    """``apap_panorama`` (``blend`` 'mean' or 'paste') or ``apap_panorama_ramp`` ('ramp', with the ramp width ``ramp``, which the
+    other blends ignore): the centre picture and every layer (a :class:`PanoramaLayer` or a 5-tuple in its order) on one canvas.
+    Returns ``(canvas (H, W, 3) uint8, (W, H, OX, OY))`` - with ``return_status=True`` also the per-layer status words, and
+    then a status does not raise.  Neither the grids nor any other input is modified."""
+    who = "panorama"
+    if gain_q is None:
+        entry, mode = panorama_entry(blend, ramp, who)
+        tail = [mode]
+    else:
+        entry = lib().apap_panorama_gain
+        tail = list(panorama_gain_mode(blend, ramp, who))
+    args, keep, n, (W, Hc, OX, OY) = _panorama_inputs(center, layers, who)
+    if gain_q is not None:
+        q = panorama_gain_q(gain_q, n + 1, who)
+        tail.append(_ip(q))
     out = np.empty((Hc, W, 3), np.uint8)
     status = np.zeros(n, np.int32)
-    p = [_addrs([a.ctypes.data for a in arrs]) for arrs in (imgs, grids, mws, mhs)]
-    code = entry(_h(ctx), _ptr(center, C.c_uint8), center.shape[0], center.shape[1], p[0], _ip(ih), _ip(iw), p[1], _ip(mr), _ip(mc),
-                 p[2], _ip(nw), p[3], _ip(nh), _ip(fw), _ip(fh), _ip(ox), _ip(oy), n, mode, _ptr(out, C.c_uint8), _ip(status), device)
+    code = entry(_h(ctx), *args, *tail, _ptr(out, C.c_uint8), _ip(status), device)
     if return_status and code in (ERR_SINGULAR, ERR_INDEX):
         return out, (W, Hc, OX, OY), status
     check(code)

@@ -14,7 +14,8 @@ the inputs come from ``--pair``)::
                                 [--data-root DIR | --pair pair.npz | --synth C1]
                                 [--config configs/case1.txt] [--out-prefix ../diff_1/results/]
                                 [--mesh-size 100] [--gamma 0.5] [--sigma 100] [--warp out.npy | --stitch out.npy]
-                                [--panorama pano.npy [--panorama-blend mean|paste|ramp] [--panorama-ramp 32]]
+                                [--panorama pano.npy [--panorama-blend mean|paste|ramp] [--panorama-ramp 32]
+                                 [--panorama-gain none|auto] [--panorama-gain-step 4]]
                                 [--resident] [--timing]
 
 The command goes through the host-buffer entry points of the C ABI (``apap_local_homography_pts``, ``apap_local_warp``,
@@ -31,10 +32,10 @@ import warnings
 import numpy as np
 
 from . import _native
-from ._native import PanoramaLayer
+from ._native import PanoramaGains, PanoramaLayer
 from .apap_utils import final_size, get_mesh, get_vertice, panorama_size, uniform_blend  # noqa: F401  (re-exported like the reference)
 
-__all__ = ["APAP", "LazyWeights", "PanoramaLayer", "panorama", "panorama_layer", "panorama_size", "get_mesh", "get_vertice", "final_size",
+__all__ = ["APAP", "LazyWeights", "PanoramaGains", "PanoramaLayer", "panorama", "panorama_gains", "panorama_layer", "panorama_size", "get_mesh", "get_vertice", "final_size",
            "uniform_blend", "save2mat", "run_pair", "run_pair_by_calls", "main"]
 
 
@@ -268,7 +269,7 @@ class APAP:
         return out
 
 
-def panorama(center_img, layers, blend="mean", device=-1, ctx=None, ramp=32, sampling=None):
+def panorama(center_img, layers, blend="mean", device=-1, ctx=None, ramp=32, sampling=None, gain=None, gain_step=4):
     """Every view of a case on one canvas, in one fused pass on the GPU: ``center_img`` and each :class:`PanoramaLayer`
     (the neighbour's picture, its grid from :meth:`APAP.local_homography`, its mesh, and the ``final_size`` / offsets of its
     pair - what :meth:`APAP.local_warp` takes), warped through its own grid.  The reference stitches one pair at a time
@@ -290,8 +291,32 @@ def panorama(center_img, layers, blend="mean", device=-1, ctx=None, ramp=32, sam
 
     ``sampling``: ``None`` (the context's ``warp_sampling``; by default truncation), ``"nearest"`` or ``"bilinear"``: how every
     layer is sampled.  The footprints, the presence counts and the ramp's weights (taken at ``(int(tx), int(ty))``) do not
-    depend on it."""
-    return _native.panorama(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp, sampling=sampling)
+    depend on it.
+
+    ``gain``: ``None`` (no gain: the call above, byte for byte), ``"auto"`` - exposure gain compensation: one gain per view,
+    fitted to the views' overlaps on every ``gain_step``-th canvas row and column (:func:`panorama_gains`) and applied to
+    every sample inside the same fused pass -, or a sequence of K + 1 integers ``q`` (the centre first; 4096 = 1.0, 1024 ..
+    16383), under which a channel ``c`` becomes ``min(255, (c q + 2048) >> 12)``.  Which samples are present, the ramp's
+    weights and paste's choice of layer do not depend on the gains."""
+    if gain is None:
+        return _native.panorama(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp, sampling=sampling)
+    if isinstance(gain, str):
+        if gain != "auto":
+            raise ValueError(f"panorama: gain must be None, 'auto' or K + 1 integers; got {gain!r}")
+        return _native.panorama_auto_gain(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp, sampling=sampling,
+                                          step=gain_step)[:2]
+    return _native.panorama(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp, sampling=sampling, gain_q=gain)
+
+
+def panorama_gains(center_img, layers, step=4, sigma_n=10.0, sigma_g=0.1, sampling=None, device=-1, ctx=None):
+    """Exposure gain compensation (Brown & Lowe, IJCV 2007, section 6) of the views of :func:`panorama`: over the canvas pixels
+    with ``X % step == 0 and Y % step == 0`` the GPU counts, for every pair of views, the pixels at which both are present
+    (``N``) and sums each view's ``r + g + b`` over them (``S``); the gains minimise ``1/2 sum N_ab [(g_a m_ab - g_b m_ba)^2 /
+    sigma_n^2 + (1 - g_a)^2 / sigma_g^2]`` with ``m_ab = S_ab / (3 N_ab)``.  Returns :class:`PanoramaGains` ``(gains, q, N,
+    S)``; ``q`` is what ``panorama(..., gain=q)`` takes, and ``panorama(..., gain="auto", gain_step=step)`` is that call."""
+    N, S = _native.panorama_gain_stats(center_img, layers, step=step, device=device, ctx=ctx, sampling=sampling)
+    g, q, _ = _native.panorama_gain_solve(N, S, sigma_n, sigma_g)
+    return PanoramaGains(g, q, N, S)
 
 
 def panorama_layer(src, dst, H_global, other_img, center_shape, mesh_size=100, gamma=0.5, sigma=100, device=-1, ctx=None):
@@ -411,6 +436,10 @@ def main(argv=None):
     ap.add_argument("--panorama-blend", choices=("mean", "paste", "ramp"), default="mean")
     ap.add_argument("--panorama-ramp", type=int, default=32, metavar="N",
                     help="--panorama-blend ramp: a picture's weight grows over N pixels from its border (1 .. 256)")
+    ap.add_argument("--panorama-gain", choices=("none", "auto"), default="none",
+                    help="auto: exposure gain compensation, one gain per picture fitted to the pictures' overlaps")
+    ap.add_argument("--panorama-gain-step", type=int, default=4, metavar="N",
+                    help="--panorama-gain auto: the overlaps are measured on every N-th canvas row and column (1 .. 64)")
     ap.add_argument("--sampling", choices=("nearest", "bilinear"), default=None,
                     help="how --warp, --stitch and --panorama sample the source pictures: nearest = the reference's truncation "
                          "(default), bilinear = four neighbours with 5 fractional bits, the same footprint")
@@ -524,7 +553,8 @@ def main(argv=None):
     for case_idx, (center_img, layers) in panoramas.items():
         t0 = time.perf_counter()
         canvas, bounds = panorama(center_img, layers, blend=a.panorama_blend, device=a.device, ramp=a.panorama_ramp,
-                                  sampling=a.sampling)
+                                  sampling=a.sampling, gain=None if a.panorama_gain == "none" else a.panorama_gain,
+                                  gain_step=a.panorama_gain_step)
         out = a.panorama
         if len(panoramas) > 1:
             root, ext = os.path.splitext(out)

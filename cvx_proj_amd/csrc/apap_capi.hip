@@ -1257,16 +1257,38 @@ int apap_image_warp(apap_ctx *ctx, const uint8_t *base, int h1, int w1, const ui
 
 // ------------------------------------------------------------------ panorama (apap_panorama.hip)
 // `status` (may be NULL) receives the n_layers status words whatever the call returns once the kernels ran.  `ramp` as in
-// apap::panorama_check: NULL for apap_panorama, the ramp width for apap_panorama_ramp.
+// apap::panorama_check: NULL for apap_panorama, the ramp width for apap_panorama_ramp.  `gain` (NULL: the plain blend): what the
+// gain entry points ask for - the blend under gain_q (kPanoGain), the statistics alone (kPanoStats, no `out`), or statistics,
+// the solve on the host and the blend under its gains (kPanoAuto: two passes, each with the layers' set-up).
+struct HostGain {
+    int what;
+    const int *gain_q;
+    int step;
+    double sigma_n, sigma_g;
+    unsigned long long *N, *S;
+    double *g;
+    int *q, *flag;
+};
 static int panorama_host(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs, const int *img_h,
                   const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols, const double *const *mesh_w,
                   const int *n_w, const double *const *mesh_h, const int *n_h, const int *final_w, const int *final_h, const int *off_x,
-                  const int *off_y, int n_layers, int mode, const int *ramp, uint8_t *out, int *status, int device, const char *who) {
+                  const int *off_y, int n_layers, int mode, const int *ramp, uint8_t *out, int *status, int device, const char *who,
+                  const HostGain *gain = nullptr) {
     int b[4];
     int rc = apap::panorama_check(center_h, center_w, img_h, img_w, mesh_rows, mesh_cols, n_w, n_h, final_w, final_h, off_x, off_y,
                                   n_layers, mode, ramp, b, who);
     if (rc) return rc;
-    if (!center || !imgs || !Hfwd || !mesh_w || !mesh_h || !out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    const int what = gain ? gain->what : apap::kPanoPlain;
+    const bool stats = what == apap::kPanoStats || what == apap::kPanoAuto, blend = what != apap::kPanoStats;
+    if (gain) {
+        const bool solve = what == apap::kPanoAuto;
+        if ((rc = apap::panorama_gain_check(n_layers + 1, stats ? &gain->step : nullptr, what == apap::kPanoGain ? gain->gain_q : nullptr,
+                                            solve ? &gain->sigma_n : nullptr, solve ? &gain->sigma_g : nullptr, who)))
+            return rc;
+        if ((what == apap::kPanoGain && !gain->gain_q) || (stats && (!gain->N || !gain->S)) || (solve && (!gain->g || !gain->q || !gain->flag)))
+            return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    }
+    if (!center || !imgs || !Hfwd || !mesh_w || !mesh_h || (blend && !out)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
     for (int k = 0; k < n_layers; ++k)
         if (!imgs[k] || !Hfwd[k] || !mesh_w[k] || !mesh_h[k]) return apap::fail(APAP_ERR_INVALID_ARG, "%s: layer %d: null pointer", who, k);
     // picture 0 is the centre, on its own: only the layers share pictures, among themselves
@@ -1286,9 +1308,13 @@ static int panorama_host(apap_ctx *ctx, const uint8_t *center, int center_h, int
         d_mh[k] = l_mh.take((size_t)n_h[k] * sizeof(double));
     }
     call.alloc(l_img); call.alloc(l_h); call.alloc(l_mw); call.alloc(l_mh);
-    const Part d_out = call.slot(S_OUT, (size_t)b[0] * b[1] * 3);
+    const Part d_out = blend ? call.slot(S_OUT, (size_t)b[0] * b[1] * 3) : Part{};
     const Part d_status = call.slot(S_STATUS, (size_t)n_layers * sizeof(int));
     const Part work = call.slot(S_WORK, apap_panorama_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h, n_layers));
+    const size_t table_bytes = (size_t)(n_layers + 1) * (n_layers + 1) * sizeof(unsigned long long);
+    Layout l_tab = call.layout(S_AUX);
+    const Part d_N = l_tab.take(stats ? table_bytes : 0), d_S = l_tab.take(stats ? table_bytes : 0);
+    if (stats) call.alloc(l_tab);
     pics.upload(call);
     for (int k = 0; k < n_layers; ++k) {
         call.up(d_h[k], Hfwd[k]);
@@ -1306,12 +1332,29 @@ static int panorama_host(apap_ctx *ctx, const uint8_t *center, int center_h, int
         p_mw[k] = d_mw[k].as<const double>();
         p_mh[k] = d_mh[k].as<const double>();
     }
-    rc = apap::panorama_device(ctx, pics.dev(0), center_h, center_w, p_img.data(), img_h, img_w, p_h.data(), mesh_rows,
-                               mesh_cols, p_mw.data(), n_w, p_mh.data(), n_h, final_w, final_h, off_x, off_y, n_layers, mode, ramp,
-                               d_out.as<uint8_t>(), work.as<void>(), work.bytes, d_status.as<int>(), call.stream(), who);
-    if (rc) return rc;
+    const apap::PanoGeometry G{pics.dev(0), center_h, center_w, p_img.data(), img_h, img_w, p_h.data(), mesh_rows, mesh_cols, p_mw.data(),
+                               n_w, p_mh.data(), n_h, final_w, final_h, off_x, off_y, n_layers};
+    apap::PanoJob J;
+    J.mode = mode; J.ramp = ramp;
+    if (stats) {
+        J.what = apap::kPanoStats;
+        J.step = gain->step; J.d_N = d_N.as<unsigned long long>(); J.d_S = d_S.as<unsigned long long>();
+        if ((rc = apap::panorama_run(ctx, G, J, work.as<void>(), work.bytes, d_status.as<int>(), call.stream(), who))) return rc;
+        call.down(gain->N, d_N);
+        call.down(gain->S, d_S);
+        if (blend) {    // the solve on the host, between the two passes
+            if ((rc = call.wait())) return rc;
+            *gain->flag = apap::panorama_gain_solve_host(gain->N, gain->S, n_layers + 1, gain->sigma_n, gain->sigma_g, gain->g, gain->q);
+        }
+    }
+    if (blend) {
+        J.what = gain ? apap::kPanoGain : apap::kPanoPlain;
+        J.gain_q = !gain ? nullptr : what == apap::kPanoAuto ? gain->q : gain->gain_q;
+        J.d_out = d_out.as<uint8_t>();
+        if ((rc = apap::panorama_run(ctx, G, J, work.as<void>(), work.bytes, d_status.as<int>(), call.stream(), who))) return rc;
+        call.down(out, d_out);
+    }
     call.down(st.data(), d_status);
-    call.down(out, d_out);
     if ((rc = call.wait())) return rc;
     if (status) std::copy(st.begin(), st.end(), status);
     for (int k = 0; k < n_layers; ++k) {
@@ -1337,6 +1380,39 @@ int apap_panorama_ramp(apap_ctx *ctx, const uint8_t *center, int center_h, int c
                        int device) {
     return panorama_host(ctx, center, center_h, center_w, imgs, img_h, img_w, Hfwd, mesh_rows, mesh_cols, mesh_w, n_w, mesh_h, n_h, final_w,
                          final_h, off_x, off_y, n_layers, APAP_PANORAMA_RAMP, &ramp, out, status, device, "apap_panorama_ramp");
+}
+
+int apap_panorama_gain_stats(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs,
+                             const int *img_h, const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols,
+                             const double *const *mesh_w, const int *n_w, const double *const *mesh_h, const int *n_h,
+                             const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers, int step,
+                             unsigned long long *N, unsigned long long *S, int *status, int device) {
+    const HostGain g{apap::kPanoStats, nullptr, step, 0.0, 0.0, N, S, nullptr, nullptr, nullptr};
+    return panorama_host(ctx, center, center_h, center_w, imgs, img_h, img_w, Hfwd, mesh_rows, mesh_cols, mesh_w, n_w, mesh_h, n_h, final_w,
+                         final_h, off_x, off_y, n_layers, APAP_PANORAMA_MEAN, nullptr, nullptr, status, device, "apap_panorama_gain_stats", &g);
+}
+
+int apap_panorama_gain(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs, const int *img_h,
+                       const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols,
+                       const double *const *mesh_w, const int *n_w, const double *const *mesh_h, const int *n_h, const int *final_w,
+                       const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode, int ramp, const int *gain_q,
+                       uint8_t *out, int *status, int device) {
+    const HostGain g{apap::kPanoGain, gain_q, 1, 0.0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return panorama_host(ctx, center, center_h, center_w, imgs, img_h, img_w, Hfwd, mesh_rows, mesh_cols, mesh_w, n_w, mesh_h, n_h, final_w,
+                         final_h, off_x, off_y, n_layers, mode, mode == APAP_PANORAMA_RAMP ? &ramp : nullptr, out, status, device,
+                         "apap_panorama_gain", &g);
+}
+
+int apap_panorama_auto_gain(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs,
+                            const int *img_h, const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols,
+                            const double *const *mesh_w, const int *n_w, const double *const *mesh_h, const int *n_h,
+                            const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode, int ramp,
+                            int step, double sigma_n, double sigma_g, uint8_t *out, unsigned long long *N, unsigned long long *S,
+                            double *g, int *q, int *flag, int *status, int device) {
+    const HostGain hg{apap::kPanoAuto, nullptr, step, sigma_n, sigma_g, N, S, g, q, flag};
+    return panorama_host(ctx, center, center_h, center_w, imgs, img_h, img_w, Hfwd, mesh_rows, mesh_cols, mesh_w, n_w, mesh_h, n_h, final_w,
+                         final_h, off_x, off_y, n_layers, mode, mode == APAP_PANORAMA_RAMP ? &ramp : nullptr, out, status, device,
+                         "apap_panorama_auto_gain", &hg);
 }
 
 }  // extern "C"

@@ -124,9 +124,8 @@ struct WarpGather {
 // k_warp_bilinear over rows [row_begin, row_begin + row_count) of `batch` canvases on `stream` (under the APAP_PROF_WARP slot).
 int warp_bilinear_launch(apap_ctx *ctx, const WarpGather &g, int batch, void *stream);
 
-// The panorama's third blend, the edge ramp, has entry points of its own (apap_panorama_ramp*): as a mode it exists only
-// inside the library, and apap_panorama[_device] refuse it like any other unknown mode.
-#define APAP_PANORAMA_RAMP 2
+// The panorama's third blend, the edge ramp, has entry points of its own (apap_panorama_ramp*): apap_panorama[_device] refuse
+// APAP_PANORAMA_RAMP like any other unknown mode; only the gain entry points take it as a mode.
 // The argument checks of the panorama's entry points (apap_panorama.hip) that need no device pointer; fills bounds[4] =
 // W, H, OX, OY.  `ramp` is NULL for the entry points that take a mode (APAP_PANORAMA_MEAN or APAP_PANORAMA_PASTE) and
 // points to the ramp width, 1 .. APAP_PANORAMA_MAX_RAMP, for those that take one (`mode` is APAP_PANORAMA_RAMP then).
@@ -139,6 +138,45 @@ int panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int ce
                     const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h, const int *n_h, const int *final_w,
                     const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode, const int *ramp, uint8_t *d_out,
                     void *d_work, size_t work_bytes, int *d_status, void *stream, const char *who);
+
+// Gain compensation (apap_panorama.hip, DESIGN.md "Panorama, gain compensation").  The per-layer arguments of the device
+// entry points as one value, and what a call is to do with them.
+struct PanoGeometry {
+    const uint8_t *d_center;
+    int center_h, center_w;
+    const uint8_t *const *d_imgs;
+    const int *img_h, *img_w;
+    const float *const *d_Hfwd;
+    const int *mesh_rows, *mesh_cols;
+    const double *const *d_mesh_w;
+    const int *n_w;
+    const double *const *d_mesh_h;
+    const int *n_h, *final_w, *final_h, *off_x, *off_y;
+    int n_layers;
+};
+enum { kPanoPlain = 0, kPanoGain, kPanoStats, kPanoAuto };   // the blend; the blend under gain_q; the statistics; statistics, device solve, blend
+struct PanoJob {
+    int what = kPanoPlain;
+    int mode = APAP_PANORAMA_MEAN;
+    const int *ramp = nullptr;      // as in panorama_check
+    uint8_t *d_out = nullptr;
+    const int *gain_q = nullptr;    // kPanoGain: n_layers + 1 HOST ints
+    int step = 1;                   // kPanoStats, kPanoAuto
+    unsigned long long *d_N = nullptr, *d_S = nullptr;
+    double sigma_n = 10.0, sigma_g = 0.1;   // kPanoAuto
+    double *d_g = nullptr;
+    int *d_q = nullptr, *d_flag = nullptr;
+};
+// Every check (panorama_check, then panorama_gain_check, then the device pointers and the workspace), the set-up launches and
+// the job's kernels on `stream`; does not wait.
+int panorama_run(apap_ctx *ctx, const PanoGeometry &G, const PanoJob &J, void *d_work, size_t work_bytes, int *d_status, void *stream,
+                 const char *who);
+// The gain arguments that need no device: n_views 2 .. 17 and, where the pointer is set, step 1 .. 64, every q 1024 .. 16383,
+// sigmas finite and positive.
+int panorama_gain_check(int n_views, const int *step, const int *gain_q, const double *sigma_n, const double *sigma_g, const char *who);
+// The shared solve on the host: g and q of n_views views; returns the flag.
+int panorama_gain_solve_host(const unsigned long long *N, const unsigned long long *S, int n_views, double sigma_n, double sigma_g,
+                             double *g, int *q);
 
 constexpr int kMoments = 30;       // distinct sums of A^T W^2 A
 

@@ -92,8 +92,41 @@ struct PanoArgs {
 };
 static_assert(sizeof(PanoArgs) <= 4096, "kernel arguments");
 
-template <int kMode, int kSampling>
-__global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
+// ---- gain compensation (DESIGN.md "Panorama, gain compensation"; the numpy definition is tests/panorama_gain_spec.py) ----
+constexpr int kViews = kMaxLayers + 1;      // view 0 is the centre, view k layer k - 1
+
+// One channel of a sample under the 4.12 fixed-point gain q = 1024 .. 16383: round to nearest, clamp at 255.  q = 4096 is
+// the identity, and 0 stays 0 at every q (2048 >> 12): a sample outside its picture stays black.
+__host__ __device__ inline unsigned gain_channel(unsigned c, unsigned q) {
+    const unsigned v = (c * q + 2048u) >> 12;
+    return v < 255u ? v : 255u;
+}
+__host__ __device__ inline unsigned gain_px(unsigned v, unsigned q) {
+    return gain_channel(v & 0xffu, q) | (gain_channel((v >> 8) & 0xffu, q) << 8) | (gain_channel(v >> 16, q) << 16);
+}
+
+// The arguments of the gained forms: the panorama's, and the gains by value or, where d_gain is set (the resident chain,
+// whose solve runs on the device), in device memory.
+struct PanoGainArgs {
+    PanoArgs A;
+    const int *d_gain;
+    int gain_q[kViews];
+};
+static_assert(sizeof(PanoGainArgs) <= 4096, "kernel arguments");
+template <bool kGain> struct ArgsOf { typedef PanoArgs type; };
+template <> struct ArgsOf<true> { typedef PanoGainArgs type; };
+__device__ __forceinline__ const PanoArgs &pano_args(const PanoArgs &a) { return a; }
+__device__ __forceinline__ const PanoArgs &pano_args(const PanoGainArgs &g) { return g.A; }
+__device__ __forceinline__ unsigned gain_of(const PanoArgs &, int) { return 4096u; }
+__device__ __forceinline__ unsigned gain_of(const PanoGainArgs &g, int view) {
+    return (unsigned)(g.d_gain ? g.d_gain[view] : g.gain_q[view]);
+}
+
+// kGain: every sample is scaled by its view's gain (gain_px) AFTER its presence, its ramp weight and paste's choice have
+// been decided on the ungained bytes.  Without it the code is the ungained kernel's, instruction for instruction.
+template <int kMode, int kSampling, bool kGain>
+__global__ __launch_bounds__(kWaves * 64) void k_panorama(const typename ArgsOf<kGain>::type P) {
+    const PanoArgs &A = pano_args(P);
     __shared__ unsigned recip[32];
     if (kMode == APAP_PANORAMA_MEAN) {
         if (threadIdx.x < 32) recip[threadIdx.x] = threadIdx.x <= (unsigned)kMaxLayers + 1u ? mean_recip(threadIdx.x) : 0u;
@@ -120,6 +153,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
     const int ramp = A.ramp;
     {
         const uint8_t *__restrict__ center = A.center;
+        const unsigned gain_c = gain_of(P, 0);
         unsigned co[kRows][4];
 #pragma unroll
         for (int t = 0; t < kRows; ++t) {
@@ -140,18 +174,19 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const unsigned c = gather_px(center, co[t][k], A.clast);
+                const unsigned cg = kGain ? gain_px(c, gain_c) : c;
                 if (kMode == APAP_PANORAMA_MEAN) {
-                    a0[t][k] = c & 0x00ff00ffu;
-                    a1[t][k] = ((c >> 8) & 0xffu) | ((unsigned)(c != 0u) << 16);
+                    a0[t][k] = cg & 0x00ff00ffu;
+                    a1[t][k] = ((cg >> 8) & 0xffu) | ((unsigned)(c != 0u) << 16);
                 } else if (kMode == APAP_PANORAMA_RAMP) {
                     // c != 0 only inside the centre's rectangle, where the weight is defined
                     const unsigned wt = c != 0u ? (unsigned)ramp_weight(j0 + k - A.OX, y_first + t - A.OY, A.center_w, A.center_h, ramp) : 0u;
-                    a0[t][k] = __umul24(wt, c & 0xffu);
-                    a1[t][k] = __umul24(wt, (c >> 8) & 0xffu);
-                    a2[t][k] = __umul24(wt, c >> 16);
+                    a0[t][k] = __umul24(wt, cg & 0xffu);
+                    a1[t][k] = __umul24(wt, (cg >> 8) & 0xffu);
+                    a2[t][k] = __umul24(wt, cg >> 16);
                     aw[t][k >> 1] = (k & 1) ? aw[t][k >> 1] | (wt << 16) : wt;
                 } else {
-                    a0[t][k] = c;
+                    a0[t][k] = cg;
                     a1[t][k] = 0u;
                 }
             }
@@ -168,6 +203,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
         const double *__restrict__ hinv_pad = L.hinv_pad;
         const uint8_t *__restrict__ img = L.img;
         const int img_w = L.img_w, img_h = L.img_h, mesh_cols = L.mesh_cols;
+        const unsigned gain_l = gain_of(P, l + 1);
         int col[4];
         unsigned want = 0u;             // bit 4 t + k: the pixel lies on the pair canvas (and, paste, is still undecided)
         unsigned colin = 0u;
@@ -231,17 +267,18 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const unsigned v = bilinear_blend(tap[k], bfr[t][k]);
+                    const unsigned vg = kGain ? gain_px(v, gain_l) : v;
                     if (kMode == APAP_PANORAMA_MEAN) {
-                        a0[t][k] += v & 0x00ff00ffu;
-                        a1[t][k] += ((v >> 8) & 0xffu) | ((unsigned)(v != 0u) << 16);
+                        a0[t][k] += vg & 0x00ff00ffu;
+                        a1[t][k] += ((vg >> 8) & 0xffu) | ((unsigned)(v != 0u) << 16);
                     } else if (kMode == APAP_PANORAMA_RAMP) {
                         const unsigned wt = v != 0u ? bfr[t][k] >> 16 : 0u;
-                        a0[t][k] += __umul24(wt, v & 0xffu);
-                        a1[t][k] += __umul24(wt, (v >> 8) & 0xffu);
-                        a2[t][k] += __umul24(wt, v >> 16);
+                        a0[t][k] += __umul24(wt, vg & 0xffu);
+                        a1[t][k] += __umul24(wt, (vg >> 8) & 0xffu);
+                        a2[t][k] += __umul24(wt, vg >> 16);
                         aw[t][k >> 1] += wt << (16 * (k & 1));
                     } else {
-                        a0[t][k] = v != 0u ? v : a0[t][k];
+                        a0[t][k] = v != 0u ? vg : a0[t][k];
                         und &= ~((unsigned)(v != 0u) << (4 * t + k));
                     }
                 }
@@ -292,19 +329,20 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const unsigned v = px[t][k];
+                const unsigned vg = kGain ? gain_px(v, gain_l) : v;
                 if (kMode == APAP_PANORAMA_MEAN) {
-                    a0[t][k] += v & 0x00ff00ffu;
-                    a1[t][k] += ((v >> 8) & 0xffu) | ((unsigned)(v != 0u) << 16);
+                    a0[t][k] += vg & 0x00ff00ffu;
+                    a1[t][k] += ((vg >> 8) & 0xffu) | ((unsigned)(v != 0u) << 16);
                 } else if (kMode == APAP_PANORAMA_RAMP) {
                     // v != 0 only where the sample lies inside its picture: a black or outside sample weighs nothing
                     const unsigned wt = v != 0u ? wgt[t][k] : 0u;
-                    a0[t][k] += __umul24(wt, v & 0xffu);
-                    a1[t][k] += __umul24(wt, (v >> 8) & 0xffu);
-                    a2[t][k] += __umul24(wt, v >> 16);
+                    a0[t][k] += __umul24(wt, vg & 0xffu);
+                    a1[t][k] += __umul24(wt, (vg >> 8) & 0xffu);
+                    a2[t][k] += __umul24(wt, vg >> 16);
                     aw[t][k >> 1] += wt << (16 * (k & 1));
                 } else {
                     // off is the outside marker for every pixel that is decided: v != 0 only where the pixel is still open
-                    a0[t][k] = v != 0u ? v : a0[t][k];
+                    a0[t][k] = v != 0u ? vg : a0[t][k];
                     und &= ~((unsigned)(v != 0u) << (4 * t + k));
                 }
             }
@@ -330,6 +368,253 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const PanoArgs A) {
         }
         APAP_STORE_PX4(A.out + ((size_t)y * (size_t)A.W + (size_t)j0) * 3u, p, npx);
     }
+}
+
+// ---- overlap statistics -------------------------------------------------------------------------------------------------
+// k_panorama_stats: N[a][b], the number of lattice pixels (X % step == 0 and Y % step == 0) at which views a and b are both
+// present, and S[a][b], the sum of I_a = r + g + b of view a's sample over them.  One pass over the lattice.  A lane owns 4
+// consecutive lattice columns of one lattice row, a wave 256 of them, a block kStatWaves lattice rows; a block takes strips
+// blockIdx.x, blockIdx.x + gridDim.x, ...  Per pixel the panorama's own layer loop - the rectangle test with scalar compares,
+// strip_cell_row / strip_source[_xy] / gather_px or the bilinear taps with the same arguments, hence the same bits - leaves a
+// presence mask in a register and the intensities of the lane's four pixels, 16 bits each, in the lane's own 8 bytes of LDS
+// per view (a register array indexed by the layer would go to scratch).  Then, for every pair of views some lane of the wave
+// saw (a wave-uniform loop over the OR of the masks), the lanes' counts and sums are added across the wave, and lane 0 adds
+// them to the block's table in LDS with integer atomics.  At its end the block adds every touched entry to the table in
+// memory with one 64-bit integer atomic each.  Integers throughout: the result does not depend on the grid or on any order.
+// The block's table holds 32-bit words: the launcher gives a block at most 2048 strips, 2^21 pixels, and 765 x 2^21 < 2^31.
+constexpr int kStatWaves = 4;
+
+struct StatsArgs {
+    PanoArgs A;
+    unsigned long long *N, *S;      // [V][V] each, V = n_layers + 1
+    int step, LW, LH;               // the lattice: LW x LH pixels
+    unsigned col_strips, n_strips;  // strips of 256 lattice columns in a row; blocks' strips in all
+};
+static_assert(sizeof(StatsArgs) <= 4096, "kernel arguments");
+
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += (unsigned)__shfl_xor((int)v, d, 64);
+    return v;
+}
+
+__device__ __forceinline__ unsigned intensity(unsigned v) { return (v & 0xffu) + ((v >> 8) & 0xffu) + (v >> 16); }
+
+template <int kSampling>
+__global__ __launch_bounds__(kStatWaves * 64) void k_panorama_stats(const StatsArgs P) {
+    const PanoArgs &A = P.A;
+    __shared__ uint2 inten[kViews][kStatWaves * 64];    // [view][thread]: I of the thread's four pixels, 16 bits each
+    __shared__ unsigned tn[kViews * kViews], ts[kViews * kViews];
+    for (int i = threadIdx.x; i < kViews * kViews; i += kStatWaves * 64) tn[i] = ts[i] = 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int V = A.n_layers + 1;
+    const int step = P.step;
+    for (unsigned strip = blockIdx.x; strip < P.n_strips; strip += gridDim.x) {    // block-uniform
+        const unsigned row_block = strip / P.col_strips;
+        const int lx_wave = (int)(strip - row_block * P.col_strips) * 256;
+        const int ly = (int)row_block * kStatWaves + wave;
+        if (ly >= P.LH) continue;       // wave-uniform; nothing below waits for another wave
+        const int Y = ly * step;
+        // the wave's canvas columns [x_first, x_last]: lattice columns lx_wave .. lx_wave + 255, as far as the lattice goes
+        const int x_first = lx_wave * step, x_last = (min(lx_wave + 255, P.LW - 1)) * step;
+        int X[4];
+        double xs[4];
+        unsigned live = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int lx = lx_wave + lane * 4 + k;
+            const bool on = lx < P.LW;
+            live |= (unsigned)on << k;
+            X[k] = on ? lx * step : 0;      // a lane past the lattice: a valid column whose sample is not wanted
+            xs[k] = (double)(X[k] - A.OX);
+        }
+        unsigned m[4];                      // bit v: view v is present at pixel k
+        {
+            const int ci = Y - A.OY;
+            unsigned iv[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int cj = X[k] - A.OX;
+                const bool in = ((live >> k) & 1u) && (unsigned)ci < (unsigned)A.center_h && (unsigned)cj < (unsigned)A.center_w;
+                const unsigned co = in ? ((unsigned)ci * (unsigned)A.center_w + (unsigned)cj) * 3u : 0xffffffffu;
+                const unsigned c = gather_px(A.center, co, A.clast);
+                m[k] = (unsigned)(c != 0u);
+                iv[k] = intensity(c);
+            }
+            inten[0][threadIdx.x] = make_uint2(iv[0] | (iv[1] << 16), iv[2] | (iv[3] << 16));
+        }
+        const double yd = (double)(Y - A.OY);
+        for (int l = 0; l < A.n_layers; ++l) {      // wave-uniform
+            const PanoLayer &L = A.layer[l];
+            const int dx = L.dx, dy = L.dy, fw = L.fw, fh = L.fh;
+            if (Y < dy || Y >= dy + fh || x_first >= dx + fw || x_last < dx) continue;
+            const int *__restrict__ lut = L.lut;
+            const double *__restrict__ hinv_pad = L.hinv_pad;
+            const uint8_t *__restrict__ img = L.img;
+            const int img_w = L.img_w, img_h = L.img_h;
+            int col[4];
+            unsigned want = 0u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = X[k] - dx;
+                want |= (unsigned)((unsigned)j < (unsigned)fw) << k;
+                col[k] = lut[(unsigned)(fh + min(max(j, 0), fw - 1))];
+            }
+            want &= live;
+            const int r = __builtin_amdgcn_readfirstlane(lut[(unsigned)(Y - dy)]);
+            PixelH q[4];
+            strip_cell_row(hinv_pad, r * L.mesh_cols, col, xs, q);
+            const unsigned last = L.last;
+            unsigned v[4];
+            if (kSampling == APAP_SAMPLING_BILINEAR) {
+                unsigned boff[4], bfr[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    int ix, iy;
+                    double tx, ty;
+                    const bool ok = strip_source_xy(q[k], yd, img_w, img_h, ix, iy, tx, ty) & (((want >> k) & 1u) != 0u);
+                    bilinear_taps(ok, tx, ty, img_w, img_h, boff[k], bfr[k]);
+                }
+                unsigned tap[4][4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) gather_taps(img, boff[k], bfr[k], (unsigned)img_w * 3u, last, tap[k]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = bilinear_blend(tap[k], bfr[k]);
+            } else {
+                unsigned off[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    int ix, iy;
+                    const bool ok = strip_source(q[k], yd, img_w, img_h, ix, iy) & (((want >> k) & 1u) != 0u);
+                    off[k] = strip_offset(ok, ix, iy, img_w);
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = gather_px(img, off[k], last);
+            }
+            unsigned iv[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                m[k] |= (unsigned)(v[k] != 0u) << (l + 1);
+                iv[k] = intensity(v[k]);
+            }
+            inten[l + 1][threadIdx.x] = make_uint2(iv[0] | (iv[1] << 16), iv[2] | (iv[3] << 16));
+        }
+
+        // the pairs: a view the wave skipped left no bit in any mask, and what its LDS words hold is never selected
+        const unsigned mine = m[0] | m[1] | m[2] | m[3];
+        unsigned seen = 0u;
+        for (int v = 0; v < V; ++v) seen |= __any((int)((mine >> v) & 1u)) ? 1u << v : 0u;
+        seen = __builtin_amdgcn_readfirstlane(seen);
+        for (unsigned ua = seen; ua != 0u; ua &= ua - 1u) {
+            const int a = __builtin_ctz(ua);
+            const uint2 pa = inten[a][threadIdx.x];
+            const unsigned ia[4] = {pa.x & 0xffffu, pa.x >> 16, pa.y & 0xffffu, pa.y >> 16};
+            for (unsigned ub = ua; ub != 0u; ub &= ub - 1u) {      // b = a, then every later view
+                const int b = __builtin_ctz(ub);
+                unsigned both = 0u;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) both |= ((m[k] >> a) & (m[k] >> b) & 1u) << k;
+                if (!__any((int)both)) continue;
+                const uint2 pb = inten[b][threadIdx.x];
+                const unsigned ib[4] = {pb.x & 0xffffu, pb.x >> 16, pb.y & 0xffffu, pb.y >> 16};
+                unsigned x = 0u, y = 0u;    // x: count << 20 | sum of I_a (a wave: at most 256 and 256 x 765 < 2^18); y: sum of I_b
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const bool on = ((both >> k) & 1u) != 0u;
+                    x += on ? (1u << 20) + ia[k] : 0u;
+                    y += on ? ib[k] : 0u;
+                }
+                x = wave_sum(x);
+                y = wave_sum(y);
+                if (lane == 0) {
+                    atomicAdd(&tn[a * kViews + b], x >> 20);
+                    atomicAdd(&ts[a * kViews + b], x & 0xfffffu);
+                    if (b != a) {
+                        atomicAdd(&tn[b * kViews + a], x >> 20);
+                        atomicAdd(&ts[b * kViews + a], y);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < V * V; i += kStatWaves * 64) {
+        const int a = i / V, b = i - a * V;
+        const unsigned n = tn[a * kViews + b], s = ts[a * kViews + b];
+        if (n != 0u) atomicAdd(&P.N[i], (unsigned long long)n);
+        if (s != 0u) atomicAdd(&P.S[i], (unsigned long long)s);
+    }
+}
+
+// ---- the gains ----------------------------------------------------------------------------------------------------------
+// The normal equations of Brown & Lowe's gain compensation over n views and their solution by Cholesky, float64, in ONE
+// written-out order of + - * / sqrt (the build has -ffp-contract=off: nothing is fused), so that host and device give the
+// same bits; tests/panorama_gain_spec.py spells the same order in Python floats.  N, S: [n][n]; L: n x kViews doubles of
+// scratch (row stride kViews); g: n doubles, q: n ints.  Returns 1, with every gain 1, when a pivot is not positive and
+// finite or a gain is not finite - which valid statistics cannot cause -, else 0.
+__host__ __device__ inline int gain_solve(const unsigned long long *N, const unsigned long long *S, int n, double sigma_n,
+                                          double sigma_g, double *L, double *g, int *q) {
+    const double big = 1.7976931348623157e308;
+    const double inv_n2 = 1.0 / (sigma_n * sigma_n), inv_g2 = 1.0 / (sigma_g * sigma_g);
+    for (int c = 0; c < n; ++c) {
+        double acc = 0.0, rhs = 0.0;
+        for (int b = 0; b < n; ++b) {
+            L[c * kViews + b] = 0.0;
+            if (b == c || N[c * n + b] == 0ull) continue;
+            const double nf = (double)N[c * n + b];
+            const double d3 = 3.0 * nf;
+            const double mcb = (double)S[c * n + b] / d3, mbc = (double)S[b * n + c] / d3;
+            acc = acc + nf * ((2.0 * (mcb * mcb)) * inv_n2 + inv_g2);
+            rhs = rhs + nf * inv_g2;
+            L[c * kViews + b] = -((((2.0 * nf) * mcb) * mbc) * inv_n2);
+        }
+        const bool overlaps = acc > 0.0;
+        L[c * kViews + c] = overlaps ? acc : 1.0;       // a view that overlaps nothing: gain 1
+        g[c] = overlaps ? rhs : 1.0;
+    }
+    int bad = 0;
+    for (int j = 0; j < n && !bad; ++j) {       // the lower triangle, row by row, in place
+        for (int k = 0; k < j; ++k) {
+            double s = L[j * kViews + k];
+            for (int p = 0; p < k; ++p) s = s - L[j * kViews + p] * L[k * kViews + p];
+            L[j * kViews + k] = s / L[k * kViews + k];
+        }
+        double d = L[j * kViews + j];
+        for (int p = 0; p < j; ++p) d = d - L[j * kViews + p] * L[j * kViews + p];
+        if (!(d > 0.0) || d > big) bad = 1;
+        else L[j * kViews + j] = sqrt(d);
+    }
+    if (!bad) {
+        for (int j = 0; j < n; ++j) {
+            double s = g[j];
+            for (int p = 0; p < j; ++p) s = s - L[j * kViews + p] * g[p];
+            g[j] = s / L[j * kViews + j];
+        }
+        for (int j = n - 1; j >= 0; --j) {
+            double s = g[j];
+            for (int p = j + 1; p < n; ++p) s = s - L[p * kViews + j] * g[p];
+            g[j] = s / L[j * kViews + j];
+        }
+        for (int j = 0; j < n; ++j)
+            if (!(g[j] >= -big && g[j] <= big)) bad = 1;
+    }
+    for (int j = 0; j < n; ++j) {
+        if (bad) g[j] = 1.0;
+        double t = rint(4096.0 * g[j]);     // half to even
+        t = t >= 1024.0 ? t : 1024.0;
+        t = t <= 16383.0 ? t : 16383.0;
+        q[j] = (int)t;
+    }
+    return bad;
+}
+
+// One lane runs gain_solve on the table in device memory: the resident chain does not wait for the host.
+__global__ __launch_bounds__(64) void k_panorama_gain_solve(const unsigned long long *N, const unsigned long long *S, int n,
+                                                            double sigma_n, double sigma_g, double *g, int *q, int *flag) {
+    __shared__ double L[kViews * kViews];
+    if (threadIdx.x == 0) *flag = gain_solve(N, S, n, sigma_n, sigma_g, L, g, q);
 }
 
 size_t slice_bytes(int mesh_rows, int mesh_cols, int final_w, int final_h) {
@@ -398,72 +683,178 @@ int panorama_check(int center_h, int center_w, const int *img_h, const int *img_
     return APAP_OK;
 }
 
-int panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs, const int *img_h,
-                    const int *img_w, const float *const *d_Hfwd, const int *mesh_rows, const int *mesh_cols,
-                    const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h, const int *n_h, const int *final_w,
-                    const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode, const int *ramp, uint8_t *d_out,
-                    void *d_work, size_t work_bytes, int *d_status, void *stream, const char *who) {
-    int b[4];
-    int rc = panorama_check(center_h, center_w, img_h, img_w, mesh_rows, mesh_cols, n_w, n_h, final_w, final_h, off_x, off_y, n_layers,
-                            mode, ramp, b, who);
-    if (rc) return rc;
-    if (!d_center || !d_imgs || !d_Hfwd || !d_mesh_w || !d_mesh_h || !d_out || !d_work || !d_status)
+// The checks of the device forms that follow panorama_check, the warp's own set-up of every layer into its slice of the
+// workspace, and the kernel arguments all three kernels share (`out` is left NULL).
+static int panorama_prepare(apap_ctx *ctx, const PanoGeometry &G, const int *b, void *d_work, size_t work_bytes, int *d_status,
+                            void *stream, const char *who, PanoArgs &A) {
+    const int n_layers = G.n_layers;
+    if (!G.d_center || !G.d_imgs || !G.d_Hfwd || !G.d_mesh_w || !G.d_mesh_h || !d_work || !d_status)
         return apap::fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
     for (int k = 0; k < n_layers; ++k)
-        if (!d_imgs[k] || !d_Hfwd[k] || !d_mesh_w[k] || !d_mesh_h[k])
+        if (!G.d_imgs[k] || !G.d_Hfwd[k] || !G.d_mesh_w[k] || !G.d_mesh_h[k])
             return apap::fail(APAP_ERR_INVALID_ARG, "%s: layer %d: null device pointer", who, k);
-    const size_t need = apap_panorama_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h, n_layers);
+    const size_t need = apap_panorama_workspace_bytes(G.mesh_rows, G.mesh_cols, G.final_w, G.final_h, n_layers);
     if (work_bytes < need) return apap::fail(APAP_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, work_bytes, need);
     if (((uintptr_t)d_work & 255) != 0) return apap::fail(APAP_ERR_INVALID_ARG, "%s: workspace must be 256-byte aligned", who);
 
-    PanoArgs A;
     std::memset(&A, 0, sizeof(A));
     char *w = (char *)d_work;
     for (int k = 0; k < n_layers; ++k) {
-        const size_t slice = slice_bytes(mesh_rows[k], mesh_cols[k], final_w[k], final_h[k]);
+        const size_t slice = slice_bytes(G.mesh_rows[k], G.mesh_cols[k], G.final_w[k], G.final_h[k]);
         // the warp's own set-up, unchanged: cell inverses and lookup tables of this pair into its slice
-        rc = apap::warp_phase(ctx, nullptr, 0, 0, nullptr, 0, 0, d_Hfwd[k], mesh_rows[k], mesh_cols[k], d_mesh_w[k], n_w[k], d_mesh_h[k],
-                              n_h[k], final_w[k], final_h[k], off_x[k], off_y[k], nullptr, nullptr, w, slice, d_status + k, stream, 0, 0,
-                              apap::kWarpSetup, nullptr);
+        const int rc = apap::warp_phase(ctx, nullptr, 0, 0, nullptr, 0, 0, G.d_Hfwd[k], G.mesh_rows[k], G.mesh_cols[k], G.d_mesh_w[k],
+                                        G.n_w[k], G.d_mesh_h[k], G.n_h[k], G.final_w[k], G.final_h[k], G.off_x[k], G.off_y[k], nullptr,
+                                        nullptr, w, slice, d_status + k, stream, 0, 0, apap::kWarpSetup, nullptr);
         if (rc) return rc;
-        const apap::WarpTables t = apap::warp_tables(w, mesh_rows[k], mesh_cols[k], final_w[k], final_h[k]);
+        const apap::WarpTables t = apap::warp_tables(w, G.mesh_rows[k], G.mesh_cols[k], G.final_w[k], G.final_h[k]);
         PanoLayer &L = A.layer[k];
-        L.img = d_imgs[k];
+        L.img = G.d_imgs[k];
         L.hinv_pad = t.hinv_pad;
         L.lut = t.lut;
-        L.img_h = img_h[k]; L.img_w = img_w[k]; L.mesh_cols = mesh_cols[k];
-        L.fw = final_w[k]; L.fh = final_h[k];
-        L.dx = b[2] - off_x[k]; L.dy = b[3] - off_y[k];
-        L.last = (unsigned)img_h[k] * (unsigned)img_w[k] * 3u - 4u;
+        L.img_h = G.img_h[k]; L.img_w = G.img_w[k]; L.mesh_cols = G.mesh_cols[k];
+        L.fw = G.final_w[k]; L.fh = G.final_h[k];
+        L.dx = b[2] - G.off_x[k]; L.dy = b[3] - G.off_y[k];
+        L.last = (unsigned)G.img_h[k] * (unsigned)G.img_w[k] * 3u - 4u;
         w += slice;
     }
-    A.center = d_center;
-    A.out = d_out;
-    A.center_h = center_h; A.center_w = center_w;
+    A.center = G.d_center;
+    A.center_h = G.center_h; A.center_w = G.center_w;
     A.W = b[0]; A.H = b[1]; A.OX = b[2]; A.OY = b[3];
     A.n_layers = n_layers;
     A.col_blocks = (A.W + kStripCols - 1) / kStripCols;
-    A.clast = (unsigned)center_h * (unsigned)center_w * 3u - 4u;
+    A.clast = (unsigned)G.center_h * (unsigned)G.center_w * 3u - 4u;
+    return APAP_OK;
+}
+
+// k_panorama over the canvas.  gain_q (host, n_layers + 1 values) or d_gain (device) selects the gained forms.
+static int panorama_launch(apap_ctx *ctx, PanoArgs &A, int mode, const int *ramp, const int *gain_q, const int *d_gain, uint8_t *d_out,
+                           void *stream) {
+    A.out = d_out;
     A.ramp = ramp ? *ramp : 0;
     const unsigned row_blocks = (unsigned)((A.H + kWaves * kRows - 1) / (kWaves * kRows));
     const dim3 grid((unsigned)A.col_blocks * row_blocks);       // W H < 2^31: below 2^31 blocks
     hipStream_t s = (hipStream_t)stream;
+    const bool bilinear = apap::opt(ctx, APAP_OPT_WARP_SAMPLING) == APAP_SAMPLING_BILINEAR;
     {
         apap::ProfScope prof(ctx, APAP_PROF_WARP, s);
         // APAP_OPT_WARP_SAMPLING: the option the pair warps read (the set-up phases above do not depend on it)
-#define APAP_LAUNCH_PANORAMA(S)                                                                                                   \
+#define APAP_LAUNCH_PANORAMA(S, GAIN, ARGS)                                                                                       \
     do {                                                                                                                          \
-        if (ramp) hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_RAMP, S>), grid, dim3(kWaves * 64), 0, s, A);                      \
-        else if (mode == APAP_PANORAMA_MEAN) hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_MEAN, S>), grid, dim3(kWaves * 64), 0, s, A); \
-        else hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_PASTE, S>), grid, dim3(kWaves * 64), 0, s, A);                          \
+        if (ramp) hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_RAMP, S, GAIN>), grid, dim3(kWaves * 64), 0, s, ARGS);             \
+        else if (mode == APAP_PANORAMA_MEAN) hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_MEAN, S, GAIN>), grid, dim3(kWaves * 64), 0, s, ARGS); \
+        else hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_PASTE, S, GAIN>), grid, dim3(kWaves * 64), 0, s, ARGS);                 \
     } while (0)
-        if (apap::opt(ctx, APAP_OPT_WARP_SAMPLING) == APAP_SAMPLING_BILINEAR) APAP_LAUNCH_PANORAMA(APAP_SAMPLING_BILINEAR);
-        else APAP_LAUNCH_PANORAMA(APAP_SAMPLING_NEAREST);
+        if (gain_q || d_gain) {
+            PanoGainArgs GA;
+            std::memset(&GA, 0, sizeof(GA));
+            GA.A = A;
+            GA.d_gain = d_gain;
+            for (int v = 0; v < kViews; ++v) GA.gain_q[v] = gain_q && v <= A.n_layers ? gain_q[v] : 4096;
+            if (bilinear) APAP_LAUNCH_PANORAMA(APAP_SAMPLING_BILINEAR, true, GA);
+            else APAP_LAUNCH_PANORAMA(APAP_SAMPLING_NEAREST, true, GA);
+        } else if (bilinear) {
+            APAP_LAUNCH_PANORAMA(APAP_SAMPLING_BILINEAR, false, A);
+        } else {
+            APAP_LAUNCH_PANORAMA(APAP_SAMPLING_NEAREST, false, A);
+        }
 #undef APAP_LAUNCH_PANORAMA
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "k_panorama launch");
     return APAP_OK;
+}
+
+// The tables zeroed on the stream, then k_panorama_stats over the lattice.
+static int stats_launch(apap_ctx *ctx, const PanoArgs &A, int step, unsigned long long *d_N, unsigned long long *d_S, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bytes = (size_t)(A.n_layers + 1) * (A.n_layers + 1) * sizeof(unsigned long long);
+    hipError_t e = hipMemsetAsync(d_N, 0, bytes, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_S, 0, bytes, s);
+    if (e != hipSuccess) return hip_fail(e, "panorama statistics: zero fill");
+    StatsArgs P;
+    std::memset(&P, 0, sizeof(P));
+    P.A = A;
+    P.N = d_N; P.S = d_S;
+    P.step = step;
+    P.LW = (A.W - 1) / step + 1;
+    P.LH = (A.H - 1) / step + 1;
+    P.col_strips = (unsigned)((P.LW + 255) / 256);
+    P.n_strips = P.col_strips * (unsigned)((P.LH + kStatWaves - 1) / kStatWaves);      // LW LH < 2^31: fits
+    // 4096 blocks, block x with the strips x, x + 4096, ... - or more blocks, so that none takes more than 2048 strips: 2^21
+    // pixels at most, and a sum of the block's 32-bit table at most 765 times that, below 2^31.
+    const dim3 grid(std::max(std::min(P.n_strips, 4096u), (P.n_strips + 2047u) / 2048u));
+    {
+        apap::ProfScope prof(ctx, APAP_PROF_WARP, s);
+        if (apap::opt(ctx, APAP_OPT_WARP_SAMPLING) == APAP_SAMPLING_BILINEAR)
+            hipLaunchKernelGGL((k_panorama_stats<APAP_SAMPLING_BILINEAR>), grid, dim3(kStatWaves * 64), 0, s, P);
+        else
+            hipLaunchKernelGGL((k_panorama_stats<APAP_SAMPLING_NEAREST>), grid, dim3(kStatWaves * 64), 0, s, P);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "k_panorama_stats launch");
+    return APAP_OK;
+}
+
+int panorama_gain_check(int n_views, const int *step, const int *gain_q, const double *sigma_n, const double *sigma_g, const char *who) {
+    if (n_views < 2 || n_views > kViews) return fail(APAP_ERR_INVALID_ARG, "%s: n_views = %d (2 .. %d)", who, n_views, kViews);
+    if (step && (*step < 1 || *step > APAP_PANORAMA_GAIN_MAX_STEP))
+        return fail(APAP_ERR_INVALID_ARG, "%s: step = %d (1 .. %d)", who, *step, APAP_PANORAMA_GAIN_MAX_STEP);
+    if (gain_q)
+        for (int v = 0; v < n_views; ++v)
+            if (gain_q[v] < APAP_PANORAMA_GAIN_MIN_Q || gain_q[v] > APAP_PANORAMA_GAIN_MAX_Q)
+                return fail(APAP_ERR_INVALID_ARG, "%s: gain_q[%d] = %d (%d .. %d)", who, v, gain_q[v], APAP_PANORAMA_GAIN_MIN_Q,
+                            APAP_PANORAMA_GAIN_MAX_Q);
+    const double big = 1.7976931348623157e308;
+    if (sigma_n && !(*sigma_n > 0.0 && *sigma_n <= big)) return fail(APAP_ERR_INVALID_ARG, "%s: sigma_n must be finite and positive", who);
+    if (sigma_g && !(*sigma_g > 0.0 && *sigma_g <= big)) return fail(APAP_ERR_INVALID_ARG, "%s: sigma_g must be finite and positive", who);
+    return APAP_OK;
+}
+
+int panorama_run(apap_ctx *ctx, const PanoGeometry &G, const PanoJob &J, void *d_work, size_t work_bytes, int *d_status, void *stream,
+                 const char *who) {
+    int b[4];
+    int rc = panorama_check(G.center_h, G.center_w, G.img_h, G.img_w, G.mesh_rows, G.mesh_cols, G.n_w, G.n_h, G.final_w, G.final_h, G.off_x,
+                            G.off_y, G.n_layers, J.mode, J.ramp, b, who);
+    if (rc) return rc;
+    const bool stats = J.what == kPanoStats || J.what == kPanoAuto;
+    if (J.what != kPanoPlain &&
+        (rc = panorama_gain_check(G.n_layers + 1, stats ? &J.step : nullptr, J.what == kPanoGain ? J.gain_q : nullptr,
+                                  J.what == kPanoAuto ? &J.sigma_n : nullptr, J.what == kPanoAuto ? &J.sigma_g : nullptr, who)))
+        return rc;
+    if (J.what == kPanoGain && !J.gain_q) return fail(APAP_ERR_INVALID_ARG, "%s: null gain_q", who);
+    if (stats && (!J.d_N || !J.d_S)) return fail(APAP_ERR_INVALID_ARG, "%s: null statistics table", who);
+    if (J.what == kPanoAuto && (!J.d_g || !J.d_q || !J.d_flag)) return fail(APAP_ERR_INVALID_ARG, "%s: null gain output", who);
+    if (J.what != kPanoStats && !J.d_out) return fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
+    PanoArgs A;
+    if ((rc = panorama_prepare(ctx, G, b, d_work, work_bytes, d_status, stream, who, A))) return rc;
+    if (stats && (rc = stats_launch(ctx, A, J.step, J.d_N, J.d_S, stream))) return rc;
+    if (J.what == kPanoStats) return APAP_OK;
+    if (J.what == kPanoAuto) {
+        hipLaunchKernelGGL(k_panorama_gain_solve, dim3(1), dim3(64), 0, (hipStream_t)stream, J.d_N, J.d_S, G.n_layers + 1, J.sigma_n,
+                           J.sigma_g, J.d_g, J.d_q, J.d_flag);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "k_panorama_gain_solve launch");
+    }
+    return panorama_launch(ctx, A, J.mode, J.ramp, J.what == kPanoGain ? J.gain_q : nullptr, J.what == kPanoAuto ? J.d_q : nullptr, J.d_out,
+                           stream);
+}
+
+int panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs, const int *img_h,
+                    const int *img_w, const float *const *d_Hfwd, const int *mesh_rows, const int *mesh_cols,
+                    const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h, const int *n_h, const int *final_w,
+                    const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode, const int *ramp, uint8_t *d_out,
+                    void *d_work, size_t work_bytes, int *d_status, void *stream, const char *who) {
+    const PanoGeometry G{d_center, center_h, center_w, d_imgs, img_h, img_w, d_Hfwd, mesh_rows, mesh_cols, d_mesh_w, n_w, d_mesh_h, n_h,
+                         final_w, final_h, off_x, off_y, n_layers};
+    PanoJob J;
+    J.mode = mode; J.ramp = ramp; J.d_out = d_out;
+    return panorama_run(ctx, G, J, d_work, work_bytes, d_status, stream, who);
+}
+
+int panorama_gain_solve_host(const unsigned long long *N, const unsigned long long *S, int n_views, double sigma_n, double sigma_g,
+                             double *g, int *q) {
+    double L[kViews * kViews];
+    return gain_solve(N, S, n_views, sigma_n, sigma_g, L, g, q);
 }
 
 }  // namespace apap
@@ -477,6 +868,68 @@ int apap_panorama_ramp_weight(int x, int y, int w, int h, int ramp) { return ram
 void apap_panorama_ramp_quotients(const unsigned *sum, const unsigned *wsum, int n, unsigned *out) {
     if (!sum || !wsum || !out) return;
     for (int k = 0; k < n; ++k) out[k] = ramp_quotient(sum[k], wsum[k]);
+}
+
+int apap_panorama_gain_solve(const unsigned long long *N, const unsigned long long *S, int n_views, double sigma_n, double sigma_g,
+                             double *g_out, int *q_out, int *flag_out) {
+    const char *who = "apap_panorama_gain_solve";
+    if (!N || !S || !g_out || !q_out || !flag_out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    const int rc = apap::panorama_gain_check(n_views, nullptr, nullptr, &sigma_n, &sigma_g, who);
+    if (rc) return rc;
+    *flag_out = apap::panorama_gain_solve_host(N, S, n_views, sigma_n, sigma_g, g_out, q_out);
+    return APAP_OK;
+}
+
+int apap_panorama_gain_apply(const uint8_t *values, int n, int q, uint8_t *out) {
+    const char *who = "apap_panorama_gain_apply";
+    if (!values || !out || n < 0) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument or negative n", who);
+    if (q < APAP_PANORAMA_GAIN_MIN_Q || q > APAP_PANORAMA_GAIN_MAX_Q)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: q = %d (%d .. %d)", who, q, APAP_PANORAMA_GAIN_MIN_Q, APAP_PANORAMA_GAIN_MAX_Q);
+    for (int k = 0; k < n; ++k) out[k] = (uint8_t)gain_channel(values[k], (unsigned)q);
+    return APAP_OK;
+}
+
+int apap_panorama_gain_stats_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                                    const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows,
+                                    const int *mesh_cols, const double *const *d_mesh_w, const int *n_w,
+                                    const double *const *d_mesh_h, const int *n_h, const int *final_w, const int *final_h,
+                                    const int *off_x, const int *off_y, int n_layers, int step, unsigned long long *d_N,
+                                    unsigned long long *d_S, void *d_work, size_t work_bytes, int *d_status, void *stream) {
+    const apap::PanoGeometry G{d_center, center_h, center_w, d_imgs, img_h, img_w, d_Hfwd, mesh_rows, mesh_cols, d_mesh_w, n_w, d_mesh_h,
+                               n_h, final_w, final_h, off_x, off_y, n_layers};
+    apap::PanoJob J;
+    J.what = apap::kPanoStats; J.step = step; J.d_N = d_N; J.d_S = d_S;
+    return apap::panorama_run(ctx, G, J, d_work, work_bytes, d_status, stream, "apap_panorama_gain_stats_device");
+}
+
+int apap_panorama_gain_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                              const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows,
+                              const int *mesh_cols, const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h,
+                              const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers,
+                              int mode, int ramp, const int *gain_q, uint8_t *d_out, void *d_work, size_t work_bytes, int *d_status,
+                              void *stream) {
+    const apap::PanoGeometry G{d_center, center_h, center_w, d_imgs, img_h, img_w, d_Hfwd, mesh_rows, mesh_cols, d_mesh_w, n_w, d_mesh_h,
+                               n_h, final_w, final_h, off_x, off_y, n_layers};
+    apap::PanoJob J;
+    J.what = apap::kPanoGain; J.mode = mode; J.ramp = mode == APAP_PANORAMA_RAMP ? &ramp : nullptr;
+    J.gain_q = gain_q; J.d_out = d_out;
+    return apap::panorama_run(ctx, G, J, d_work, work_bytes, d_status, stream, "apap_panorama_gain_device");
+}
+
+int apap_panorama_auto_gain_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                                   const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows,
+                                   const int *mesh_cols, const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h,
+                                   const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y,
+                                   int n_layers, int mode, int ramp, int step, double sigma_n, double sigma_g, uint8_t *d_out,
+                                   unsigned long long *d_N, unsigned long long *d_S, double *d_g, int *d_q, int *d_flag, void *d_work,
+                                   size_t work_bytes, int *d_status, void *stream) {
+    const apap::PanoGeometry G{d_center, center_h, center_w, d_imgs, img_h, img_w, d_Hfwd, mesh_rows, mesh_cols, d_mesh_w, n_w, d_mesh_h,
+                               n_h, final_w, final_h, off_x, off_y, n_layers};
+    apap::PanoJob J;
+    J.what = apap::kPanoAuto; J.mode = mode; J.ramp = mode == APAP_PANORAMA_RAMP ? &ramp : nullptr;
+    J.step = step; J.sigma_n = sigma_n; J.sigma_g = sigma_g;
+    J.d_out = d_out; J.d_N = d_N; J.d_S = d_S; J.d_g = d_g; J.d_q = d_q; J.d_flag = d_flag;
+    return apap::panorama_run(ctx, G, J, d_work, work_bytes, d_status, stream, "apap_panorama_auto_gain_device");
 }
 
 int apap_panorama_bounds(int center_h, int center_w, const int *final_w, const int *final_h, const int *off_x, const int *off_y,

@@ -617,7 +617,8 @@ def panorama_workspace_bytes(layers):
     return _native.lib().apap_panorama_workspace_bytes(_ip(mr), _ip(mc), _ip(fw), _ip(fh), len(layers))
 
 
-def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, work=None, ramp=32, sampling=None):
+def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, work=None, ramp=32, sampling=None, gain=None,
+                 gain_step=4, sigma_n=10.0, sigma_g=0.1, return_gains=False):
     """``apap_panorama_device`` (``blend="ramp"``: ``apap_panorama_ramp_device`` with the ramp width ``ramp``, an integer 1 ..
     256 that the other blends ignore) on the current stream of the tensors' device, no host synchronisation: the centre picture and
     every layer on one canvas in one fused pass (``apap.panorama`` on device tensors).  ``center`` (h, w, 3) uint8; a layer is
@@ -627,14 +628,36 @@ def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, 
     layer, zeroed by the caller (default: a new one), into which layer k's set-up ORs its bits at [k]; ``work`` (uint8) is
     used when it holds ``panorama_workspace_bytes(layers)``.  Returns ``(canvas, (W, H, OX, OY), status)``, not synchronised;
     ``_native.raise_for_status(int(status[k]), ...)`` turns a word into the reference's exception.  The grids are not
-    modified.  ``sampling``: ``None`` (the context's ``warp_sampling``), ``"nearest"`` or ``"bilinear"`` for this call only."""
+    modified.  ``sampling``: ``None`` (the context's ``warp_sampling``), ``"nearest"`` or ``"bilinear"`` for this call only.
+
+    ``gain``: ``None`` (the call above), K + 1 host integers ``q`` (``apap_panorama_gain_device``), or ``"auto"``
+    (``apap_panorama_auto_gain_device``): the overlap statistics on every ``gain_step``-th canvas row and column, the solve
+    on the device and the gained blend, one after the other on the stream - nothing waits for the host.  With
+    ``return_gains=True`` and ``"auto"`` a fourth value follows: ``_native.PanoramaGains`` of device tensors (``gains``
+    float64, ``q`` int32, ``N``, ``S`` int64 holding the uint64 statistics), not synchronised."""
     who = "hip_panorama"
     _native.sampling_value(sampling, who)
     _needs_device(center, who)
     dev = center.device
-    entry, mode = _native.panorama_entry(blend, ramp, who, device_form=True)
+    auto = isinstance(gain, str)
+    if auto and gain != "auto":
+        raise ValueError(f"{who}: gain must be None, 'auto' or K + 1 integers; got {gain!r}")
+    if return_gains and not auto:
+        raise ValueError(f"{who}: return_gains goes with gain='auto'")
+    if gain is None:
+        entry, mode = _native.panorama_entry(blend, ramp, who, device_form=True)
+        tail = [mode]
+    else:
+        tail = list(_native.panorama_gain_mode(blend, ramp, who))
+        entry = _native.lib().apap_panorama_auto_gain_device if auto else _native.lib().apap_panorama_gain_device
     layers, (fw, fh, ox, oy) = _native.panorama_geometry(layers, who)
     n = len(layers)
+    gains = None
+    if auto:
+        tail += [_native._gain_step(gain_step, who), float(sigma_n), float(sigma_g)]
+    elif gain is not None:
+        q_host = _native.panorama_gain_q(gain, n + 1, who)
+        tail.append(_ip(q_host))
 
     def tensor(t, dtype, name, k):
         if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
@@ -666,9 +689,64 @@ def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, 
     table = [_addrs([t.data_ptr() for t in ts]) for ts in (imgs, grids, mws, mhs)]
     p_mr, p_mc, p_fw, p_fh = _ip(mr), _ip(mc), _ip(fw), _ip(fh)
     work = _scratch(work, _native.lib().apap_panorama_workspace_bytes(p_mr, p_mc, p_fw, p_fh, n), dev)
+    after = []
+    if auto:
+        gains = _native.PanoramaGains(torch.empty(n + 1, dtype=torch.float64, device=dev), torch.empty(n + 1, dtype=torch.int32, device=dev),
+                                      torch.empty((n + 1, n + 1), dtype=torch.int64, device=dev),
+                                      torch.empty((n + 1, n + 1), dtype=torch.int64, device=dev))
+        flag = torch.empty(1, dtype=torch.int32, device=dev)
+        after = [gains.N.data_ptr(), gains.S.data_ptr(), gains.gains.data_ptr(), gains.q.data_ptr(), flag.data_ptr()]
     with _native.sampling_scope(ctx, sampling, who) as ctx:
         _native.check(entry(
             _native._h(ctx), center.data_ptr(), center.shape[0], center.shape[1], table[0], _ip(ih), _ip(iw), table[1], p_mr, p_mc,
-            table[2], _ip(nw), table[3], _ip(nh), p_fw, p_fh, _ip(ox), _ip(oy), n, mode, out.data_ptr(), work.data_ptr(),
+            table[2], _ip(nw), table[3], _ip(nh), p_fw, p_fh, _ip(ox), _ip(oy), n, *tail, out.data_ptr(), *after, work.data_ptr(),
             work.numel(), status.data_ptr(), _stream(dev)))
-    return out, (W, H, OX, OY), status
+    return (out, (W, H, OX, OY), status, gains) if return_gains else (out, (W, H, OX, OY), status)
+
+
+def hip_panorama_gain_stats(center, layers, step=4, N=None, S=None, status=None, ctx=None, work=None, sampling=None):
+    """``apap_panorama_gain_stats_device`` on the current stream, not synchronised: the overlap statistics of the centre and
+    the layers (as in :func:`hip_panorama`) over the canvas pixels with ``X % step == 0 and Y % step == 0``.  ``N``, ``S``:
+    contiguous (K + 1, K + 1) int64 tensors to write into (the uint64 counts and sums; the call zeroes them itself; default:
+    new ones); ``work`` as in :func:`hip_panorama`.  Returns ``(N, S, status)``."""
+    who = "hip_panorama_gain_stats"
+    _native.sampling_value(sampling, who)
+    _needs_device(center, who)
+    dev = center.device
+    step = _native._gain_step(step, who)
+    layers, (fw, fh, ox, oy) = _native.panorama_geometry(layers, who)
+    n = len(layers)
+    if center.dtype != torch.uint8 or not center.is_contiguous() or center.dim() != 3 or center.shape[2] != 3:
+        raise ValueError(f"{who}: the centre must be a contiguous uint8 (h, w, 3) tensor")
+    for k, l in enumerate(layers):
+        for t, dtype, name in ((l.img, torch.uint8, "img"), (l.local_homography, torch.float32, "local_homography"),
+                               (l.mesh[0], torch.float64, "mesh_w"), (l.mesh[1], torch.float64, "mesh_h")):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{who}: layer {k}: {name} must be a contiguous {dtype} tensor on {dev}")
+        if l.img.dim() != 3 or l.img.shape[2] != 3 or l.local_homography.dim() != 4 or tuple(l.local_homography.shape[2:]) != (3, 3):
+            raise ValueError(f"{who}: layer {k}: img must be (h, w, 3) and local_homography (rows, cols, 3, 3)")
+    _native.panorama_bounds(center.shape, fw, fh, ox, oy)
+    tables = []
+    for t, name in ((N, "N"), (S, "S")):
+        if t is None:
+            t = torch.empty((n + 1, n + 1), dtype=torch.int64, device=dev)
+        if t.dtype != torch.int64 or tuple(t.shape) != (n + 1, n + 1) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{who}: {name} must be a contiguous int64 tensor of shape {(n + 1, n + 1)} on {dev}")
+        tables.append(t)
+    if status is None:
+        status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if status.dtype != torch.int32 or status.numel() < n or not status.is_contiguous() or status.device != dev:
+        raise ValueError(f"{who}: status must be a contiguous int32 tensor of at least {n} words on {dev}")
+    ih, iw = _i32([l.img.shape[0] for l in layers]), _i32([l.img.shape[1] for l in layers])
+    mr, mc = _i32([l.local_homography.shape[0] for l in layers]), _i32([l.local_homography.shape[1] for l in layers])
+    nw, nh = _i32([l.mesh[0].numel() for l in layers]), _i32([l.mesh[1].numel() for l in layers])
+    table = [_addrs([t.data_ptr() for t in ts]) for ts in ([l.img for l in layers], [l.local_homography for l in layers],
+                                                           [l.mesh[0] for l in layers], [l.mesh[1] for l in layers])]
+    p_mr, p_mc, p_fw, p_fh = _ip(mr), _ip(mc), _ip(fw), _ip(fh)
+    work = _scratch(work, _native.lib().apap_panorama_workspace_bytes(p_mr, p_mc, p_fw, p_fh, n), dev)
+    with _native.sampling_scope(ctx, sampling, who) as ctx:
+        _native.check(_native.lib().apap_panorama_gain_stats_device(
+            _native._h(ctx), center.data_ptr(), center.shape[0], center.shape[1], table[0], _ip(ih), _ip(iw), table[1], p_mr, p_mc,
+            table[2], _ip(nw), table[3], _ip(nh), p_fw, p_fh, _ip(ox), _ip(oy), n, step, tables[0].data_ptr(), tables[1].data_ptr(),
+            work.data_ptr(), work.numel(), status.data_ptr(), _stream(dev)))
+    return tables[0], tables[1], status

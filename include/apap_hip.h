@@ -931,6 +931,73 @@ int apap_panorama_ramp_device(apap_ctx *ctx, const uint8_t *d_center, int center
                               const int *mesh_cols, const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h,
                               const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers,
                               int ramp, uint8_t *d_out, void *d_work, size_t work_bytes, int *d_status, void *stream);
+/* Exposure gain compensation: one multiplicative gain per view, fitted to the views' overlaps (Brown & Lowe, IJCV 2007,
+ * section 6), applied inside the fused pass (DESIGN.md "Panorama, gain compensation"; in numpy: tests/panorama_gain_spec.py).
+ * View 0 is the centre, view k = 1 .. n_layers layer k - 1.  A view's sample at a canvas pixel, and whether it is present, are
+ * the panorama's under the context's APAP_OPT_WARP_SAMPLING; I = r + g + b of the sample.
+ *   statistics  over the canvas pixels with X % step == 0 and Y % step == 0 (step 1 .. APAP_PANORAMA_GAIN_MAX_STEP):
+ *               N[a][b] the number of them at which a and b are both present, S[a][b] the sum of I_a over those; both
+ *               (n_layers + 1)^2 uint64, row-major, the diagonal a view by itself.  Exact integers; the call zeroes the tables
+ *   gains       the minimiser of 1/2 sum_{a != b} N_ab [(g_a m_ab - g_b m_ba)^2 / sigma_n^2 + (1 - g_a)^2 / sigma_g^2] with
+ *               m_ab = S_ab / (3 N_ab) (the paper's sigma_n = 10, sigma_g = 0.1), by Cholesky in float64 in one fixed order
+ *               of + - * / sqrt: the same bits from apap_panorama_gain_solve on the host and from the device.  A view that
+ *               overlaps nothing has gain 1.  q = clamp(rint(4096 g), APAP_PANORAMA_GAIN_MIN_Q, APAP_PANORAMA_GAIN_MAX_Q).
+ *               flag = 1 and every gain 1 if a pivot or a gain is not positive / finite (valid statistics cannot cause it)
+ *   application a channel c of a sample of view v becomes min(255, (c q_v + 2048) >> 12) (apap_panorama_gain_apply, host
+ *               only, over n bytes).  Presence, the ramp weight and paste's first present layer are decided on the UNGAINED
+ *               sample; mean, paste and ramp then take the gained value.  q = 4096 everywhere is the ungained canvas
+ * apap_panorama_gain[_device]: apap_panorama[_device]'s arguments with mode = APAP_PANORAMA_MEAN, APAP_PANORAMA_PASTE or
+ * APAP_PANORAMA_RAMP, `ramp` (read for APAP_PANORAMA_RAMP only) and gain_q, n_layers + 1 HOST ints.
+ * apap_panorama_gain_stats[_device]: the geometry arguments and `step`; N, S host arrays / d_N, d_S device arrays.
+ * apap_panorama_auto_gain_device: statistics, the solve on the device and the gained blend, all enqueued on `stream`, no
+ * wait; d_N, d_S, d_g (n_layers + 1 doubles), d_q (n_layers + 1 ints) and d_flag (one int) are written for the caller.
+ * apap_panorama_auto_gain: the same on host buffers (N, S, g, q, flag receive the results; the solve runs on the host
+ * between the two passes).  All device forms use the workspace of apap_panorama_workspace_bytes and nothing more.
+ * Refused before any device is touched (APAP_ERR_INVALID_ARG): whatever apap_panorama refuses, step outside 1 .. 64, a q
+ * outside 1024 .. 16383, sigmas that are not finite and positive, n_views outside 2 .. 17.  Without a GPU the compute entry
+ * points return APAP_ERR_NO_DEVICE; apap_panorama_gain_solve and apap_panorama_gain_apply touch no device. */
+#define APAP_PANORAMA_RAMP 2
+#define APAP_PANORAMA_GAIN_MAX_STEP 64
+#define APAP_PANORAMA_GAIN_MIN_Q 1024
+#define APAP_PANORAMA_GAIN_MAX_Q 16383
+int apap_panorama_gain_solve(const unsigned long long *N, const unsigned long long *S, int n_views, double sigma_n, double sigma_g,
+                             double *g_out, int *q_out, int *flag_out);
+int apap_panorama_gain_apply(const uint8_t *values, int n, int q, uint8_t *out);
+int apap_panorama_gain_stats(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs,
+                             const int *img_h, const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols,
+                             const double *const *mesh_w, const int *n_w, const double *const *mesh_h, const int *n_h,
+                             const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers, int step,
+                             unsigned long long *N, unsigned long long *S, int *status, int device);
+int apap_panorama_gain_stats_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                                    const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows,
+                                    const int *mesh_cols, const double *const *d_mesh_w, const int *n_w,
+                                    const double *const *d_mesh_h, const int *n_h, const int *final_w, const int *final_h,
+                                    const int *off_x, const int *off_y, int n_layers, int step, unsigned long long *d_N,
+                                    unsigned long long *d_S, void *d_work, size_t work_bytes, int *d_status, void *stream);
+int apap_panorama_gain(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs, const int *img_h,
+                       const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols,
+                       const double *const *mesh_w, const int *n_w, const double *const *mesh_h, const int *n_h, const int *final_w,
+                       const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode, int ramp, const int *gain_q,
+                       uint8_t *out, int *status, int device);
+int apap_panorama_gain_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                              const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows,
+                              const int *mesh_cols, const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h,
+                              const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers,
+                              int mode, int ramp, const int *gain_q, uint8_t *d_out, void *d_work, size_t work_bytes, int *d_status,
+                              void *stream);
+int apap_panorama_auto_gain(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs,
+                            const int *img_h, const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols,
+                            const double *const *mesh_w, const int *n_w, const double *const *mesh_h, const int *n_h,
+                            const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers, int mode, int ramp,
+                            int step, double sigma_n, double sigma_g, uint8_t *out, unsigned long long *N, unsigned long long *S,
+                            double *g, int *q, int *flag, int *status, int device);
+int apap_panorama_auto_gain_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                                   const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows,
+                                   const int *mesh_cols, const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h,
+                                   const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y,
+                                   int n_layers, int mode, int ramp, int step, double sigma_n, double sigma_g, uint8_t *d_out,
+                                   unsigned long long *d_N, unsigned long long *d_S, double *d_g, int *d_q, int *d_flag, void *d_work,
+                                   size_t work_bytes, int *d_status, void *stream);
 
 #ifdef __cplusplus
 }
