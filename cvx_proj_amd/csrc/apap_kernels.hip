@@ -325,7 +325,8 @@ struct ExpTableStage {
 __host__ __device__ constexpr int lds_off(int r, int c) { return r * 256 + ((c ^ ((r & 1) << 4)) << 3); }
 // The same swizzle for the staging's 16-byte pieces (slot = columns 2 slot, 2 slot + 1), tied to lds_off by the assertion.  Not
 // lds_off(r, 2 * slot): from that form the compiler folds a thread's four pieces into one address and four immediates, 8-9
-// instructions out of every chunk loop - a tuning change, to be measured on its own.  (A macro: see APAP_CHUNK_STORE.)
+// instructions out of every chunk loop - which k_assemble_mfma's staging now spells out itself (ChunkWindow below); the other
+// kernels keep the loops they had.  (A macro: see APAP_CHUNK_STORE.)
 #define APAP_LDS_PIECE_OFF(r, slot) ((r) * 256 + ((slot) ^ (((r) & 1) << 3)) * 16)
 constexpr bool lds_swizzles_agree() {
     for (int r = 0; r < 2; ++r)
@@ -365,6 +366,54 @@ __device__ __forceinline__ void chunk_load(ChunkStage<kThreads> &stage, const do
             *reinterpret_cast<double2 *>(&(buf)[APAP_LDS_PIECE_OFF(r_, slot_)]) = (stage)[i_]; \
         }                                                                                    \
     } while (0)
+
+// k_assemble_mfma's staging: the same pieces into the same LDS image through a raw buffer resource whose range check makes the
+// zero rows, so that the chunk loop holds no compare, no exec mask, no zero fill and no 64-bit address of the staging's.
+// The resource is a WINDOW on one chunk - base = the chunk's first row, num_records = the bytes of its rows below end_row,
+// 0 .. 16384 - rebuilt by scalar instructions at every chunk from block-uniform values.  Everything the range check must see
+// sits in the lane's offset, a per-thread constant below 16384, and a split of any length has a valid 32-bit num_records (no
+// second loader for splits of 2^23 rows and more).  The other form, one resource per split with the chunk's offset in the
+// instruction's scalar offset, was not built: LLVM documents that operand of its raw buffer intrinsics as excluded from bounds
+// checking, in which case the rows behind the split's end - the next split's, the next pair's - come back as they are.  A probe
+// on an MI355X (profiles/k1_staging_levels.txt section 0) shows this chip does refuse a load whose scalar offset is past
+// num_records, so that form would be right here too, at 5 scalar instructions and 3 registers less per pass; not measured.
+// The pieces of a thread are 16 rows = 4096 bytes apart, past the instruction's 12-bit immediate: their lane offsets are loop
+// invariants.
+// Word 3 = 0x00020000: DATA_FORMAT 32 bit, every other field 0 (raw, no swizzle, no add-tid) - the word the compiler's own
+// buffer lowering uses on gfx9 (gfx90a/gfx942/gfx950 share the descriptor layout).
+constexpr int kBufferWord3 = 0x00020000;
+constexpr int kTableRowBytes = APAP_TABLE_STRIDE * 8;
+static_assert(kTableRowBytes == 256, "an LDS row is a table row");
+struct ChunkWindow {
+    __amdgpu_buffer_rsrc_t rsrc;
+    // rows first_row .. first_row + 63 of `table`, those from end_row on out of range (first_row <= end_row, block-uniform:
+    // every caller stages a chunk of the split, or an empty split's none.  One s_min: clamped from below as well, the
+    // compiler forms a v_med3_i32 and wraps every load in a loop over the resource's values)
+    __device__ __forceinline__ ChunkWindow(const double *__restrict__ table, int first_row, int end_row) {
+        const int rows = min(kChunk, end_row - first_row);
+        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(table) + (size_t)first_row * APAP_TABLE_STRIDE, 0,
+                                                 rows * kTableRowBytes, kBufferWord3);
+    }
+    __device__ __forceinline__ double2 load16(int lane_off) const {
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off, 0, 0);
+        return make_double2(__longlong_as_double(((long long)v[1] << 32) | v[0]), __longlong_as_double(((long long)v[3] << 32) | v[2]));
+    }
+    __device__ __forceinline__ double load8(int lane_off) const {
+        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, lane_off, 0, 0);
+        return __longlong_as_double(((long long)v[1] << 32) | v[0]);
+    }
+};
+// Piece i of thread t (q = t + kThreads i): row (t >> 4) + 16 i (kThreads = 256), the same slot and the same row parity, so
+// one table offset and one LDS offset per thread and i * 4096 on both.
+constexpr bool lds_pieces_are_4096_apart() {
+    for (int t = 0; t < 256; ++t)
+        for (int i = 0; i < 4; ++i)
+            if (APAP_LDS_PIECE_OFF((t + 256 * i) >> 4, (t + 256 * i) & 15) != APAP_LDS_PIECE_OFF(t >> 4, t & 15) + 4096 * i) return false;
+    return true;
+}
+static_assert(lds_pieces_are_4096_apart(), "a thread's four pieces: one LDS address and four immediates");
 
 // w^2 of one cell (sample point v) for the keypoint whose coordinates sit at an LDS address: the float64 chain reads (x, y)
 // from columns 30, 31 of the keypoint's row, the float32 chain (kW32, 24-sum tables only) a float2 from column 29.
@@ -697,12 +746,24 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
         for (int t = 0; t < kGroups; ++t)
             off_row[t] = apap::row_read_off(0, 0, kgrp, apap::row_value(__double_as_longlong(weight[t].vy), a_bits));
     }
-    // The side table's producer (threads 0 .. 127 of a sharing block): the keypoint's y straight from the table, 0.0 for the
-    // rows from p_end on (what the chunk's zero rows hold), then the chain's own two operations on the chain's own operands.
-    auto row_fetch = [&](int first_row) {
-        const int p = first_row + apap::row_owner_keypoint(tid);
-        return p < p_end ? table[(size_t)p * APAP_TABLE_STRIDE + 31] : 0.0;
+    // The staging's per-thread constants (ChunkWindow): the byte offset of the thread's first piece in a chunk of the table
+    // and in its LDS image, and where a row term's owner finds its keypoint's y (column 31).
+    static_assert(kThreads == 256, "four pieces a thread, 16 rows apart");
+    const int piece_src = (tid >> 4) * kTableRowBytes + (tid & 15) * 16;
+    const int piece_dst = APAP_LDS_PIECE_OFF(tid >> 4, tid & 15);
+    const int row_src = apap::row_owner_keypoint(tid) * kTableRowBytes + 31 * 8;
+    auto window_load = [&](ChunkStage<kThreads> &to, const ChunkWindow &win) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) to[i] = win.load16(piece_src + 4096 * i);
     };
+    auto window_store = [&](unsigned char *buf, const ChunkStage<kThreads> &from) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<double2 *>(buf + piece_dst + 4096 * i) = from[i];
+    };
+    // The side table's producer (threads 0 .. 127 of a sharing block): the keypoint's y straight from the table, 0.0 for the
+    // rows from p_end on (what the chunk's zero rows hold: out of the window's range), then the chain's own two operations on
+    // the chain's own operands.
+    auto row_fetch = [&](const ChunkWindow &win) { return win.load8(row_src); };
     auto row_publish = [&](int buffer, double sy) {
         const double dy = row_v - sy;
         s_row[buffer][apap::row_owner_keypoint(tid)][apap::row_owner_value(tid)] = fma(dy, dy, 1e-300);
@@ -721,15 +782,16 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
 #pragma unroll
         for (int t = 0; t < kGroups; ++t) sums[t].step(w2[t], b0, b1, b1b);
     };
-    if (nchunks > 0) chunk_load<kThreads>(stage, table, tid, p_begin, p_end);
+    const ChunkWindow first_window(table, p_begin, p_end);      // (an empty split: no record, every load is zero)
+    if (nchunks > 0) window_load(stage, first_window);
     // The first chunk's terms, whether the block shares them or not: asked for only once the vote is in, the keypoints' y
     // would cost every block a second memory latency in a row before its first barrier.
     double row_y0 = 0.0;
     if constexpr (kCanShare) {
-        if (row_owner && nchunks > 0) row_y0 = row_fetch(p_begin);
+        if (row_owner && nchunks > 0) row_y0 = row_fetch(first_window);
     }
     exp_stage.publish(s_exp2, tid);  // visible after the barrier
-    if (nchunks > 0) APAP_CHUNK_STORE(kThreads, lds[0], stage, tid);
+    if (nchunks > 0) window_store(lds[0], stage);
     if constexpr (kCanShare) {
         if (row_owner && nchunks > 0) row_publish(0, row_y0);
     }
@@ -762,14 +824,22 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
                 else if (4 * c < 3 * nfull) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(0);
             }
-            // (the next chunk's registers belong to this pass: loaded and stored under the same condition.  As one variable with
-            // the prologue's, shared by the two forms of the loop, the first chunk's 16 registers stayed live through the loops.)
+            // (the next chunk's registers belong to this pass.  As one variable with the prologue's, shared by the two forms of
+            // the loop, the first chunk's 16 registers stayed live through the loops.)
+            // Staged in EVERY pass, with no condition on c + 1 < nchunks: the last whole chunk of a split that has no partial one
+            // gets a window of no rows (no memory is touched) and stores 16 KiB of zeros into the free buffer before the
+            // barrier.  With the loads and the stores each under that condition the compiler's wait counter saw a path that
+            // loads and does not store, and in the loops of a sharing block it put s_waitcnt vmcnt(0) right behind the loads,
+            // at the TOP of the pass: every wave waited out the memory latency of its prefetch before its first step.  Now the
+            // waits (vmcnt 3, 2, 1, 0) stand in front of the four LDS stores at the end of the pass in all six chunk loops.
             ChunkStage<kThreads> next;
             double row_y = 0.0;
-            if (c + 1 < nchunks) {
-                chunk_load<kThreads>(next, table, tid, p_begin + (c + 1) * kChunk, p_end);
+            {
+                const int next_row = p_begin + (c + 1) * kChunk;
+                const ChunkWindow window(table, next_row, c + 1 < nchunks ? p_end : next_row);
+                window_load(next, window);
                 if constexpr (kRow) {
-                    if (row_owner) row_y = row_fetch(p_begin + (c + 1) * kChunk);
+                    if (row_owner) row_y = row_fetch(window);
                 }
             }
             const unsigned char *buf = lds[c & 1];
@@ -818,11 +888,9 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            if (c + 1 < nchunks) {
-                APAP_CHUNK_STORE(kThreads, lds[(c + 1) & 1], next, tid);
-                if constexpr (kRow) {
-                    if (row_owner) row_publish((c + 1) & 1, row_y);
-                }
+            window_store(lds[(c + 1) & 1], next);
+            if constexpr (kRow) {
+                if (row_owner) row_publish((c + 1) & 1, row_y);
             }
             __syncthreads();
         }
