@@ -248,6 +248,14 @@ SIGNATURES.update({
     "apap_panorama_auto_gain_device": (C.c_int, _PANO_GEOMETRY_DEVICE + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp,
                                                                          _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
 })
+# the two-band blend: the geometry arguments, then ramp, band, gain_q (host ints or NULL) and the ramp entry points' tails
+SIGNATURES.update({
+    "apap_box_blur": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, _u8p, C.c_int]),
+    "apap_box_blur_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "apap_panorama_band_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int, C.c_int]),
+    "apap_panorama_band": (C.c_int, _PANO_GEOMETRY + [C.c_int, C.c_int, _i32p, _u8p, _i32p, C.c_int]),
+    "apap_panorama_band_device": (C.c_int, _PANO_GEOMETRY_DEVICE + [C.c_int, C.c_int, _i32p, _vp, _vp, C.c_size_t, _vp, _vp]),
+})
 
 _lib = None
 _torch_at_load = False      # was torch in the process when the library was loaded?  (cvx_proj_amd.resident refuses otherwise)
@@ -1306,7 +1314,7 @@ class PanoramaLayer(NamedTuple):
 
 def panorama_mode(blend, who="panorama"):
     if blend not in PANORAMA_MODES:
-        raise ValueError(f"{who}: blend must be 'mean', 'paste' or 'ramp'; got {blend!r}")
+        raise ValueError(f"{who}: blend must be 'mean', 'paste', 'ramp' or 'band'; got {blend!r}")
     return PANORAMA_MODES[blend]
 
 
@@ -1464,12 +1472,36 @@ def panorama_gain_stats(center, layers, step=4, device=-1, ctx=None, sampling=No
     return N, S
 
 
-def panorama(center, layers, blend="mean", device=-1, ctx=None, return_status=False, ramp=32, sampling=None, gain_q=None):
+PANORAMA_BAND = 3                   # APAP_PANORAMA_BAND: the two-band blend's kernel mode; no entry point takes it as a mode
+PANORAMA_MAX_BAND = 32              # APAP_PANORAMA_MAX_BAND
+
+
+def panorama_band_radius(band, who="panorama"):
+    """``band`` of the two-band blend as an int 0 .. 32, or ValueError."""
+    if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or not 0 <= band <= PANORAMA_MAX_BAND:
+        raise ValueError(f"{who}: band must be an integer 0 .. {PANORAMA_MAX_BAND}; got {band!r}")
+    return int(band)
+
+
+def box_blur(img, radius, device=-1, ctx=None):
+    """``apap_box_blur``: the low-pass picture of the two-band blend, ``(T + (n^2 >> 1)) // n^2`` with ``n = 2 radius + 1`` and T
+    the sum over the n x n window with the border replicated; ``img`` (h, w, 3) uint8, ``radius`` 0 .. 32."""
+    radius = panorama_band_radius(radius, "box_blur")
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"box_blur: the picture must be (h, w, 3); got {img.shape}")
+    out = np.empty_like(img)
+    check(lib().apap_box_blur(_h(ctx), _ptr(img, C.c_uint8), img.shape[0], img.shape[1], radius, _ptr(out, C.c_uint8), device))
+    return out
+
+
+def panorama(center, layers, blend="mean", device=-1, ctx=None, return_status=False, ramp=32, sampling=None, gain_q=None, band=8):
     """See :func:`_panorama`; ``sampling``: ``None`` (the context's ``warp_sampling``), ``"nearest"`` or ``"bilinear"`` for this
     call only - every layer is then sampled that way.  ``gain_q``: ``None``, or K + 1 integers 1024 .. 16383 (4096 = 1.0), the
-    gain of the centre and of every layer (``apap_panorama_gain``)."""
+    gain of the centre and of every layer (``apap_panorama_gain``; ``apap_panorama_band`` takes them itself).  ``band``: the
+    radius 0 .. 32 of the low-pass pictures of ``blend="band"``; every other blend ignores it."""
     with sampling_scope(ctx, sampling, "panorama") as ctx:
-        return _panorama(center, layers, blend, device, ctx, return_status, ramp, gain_q)
+        return _panorama(center, layers, blend, device, ctx, return_status, ramp, gain_q, band)
 
 
 def panorama_auto_gain(center, layers, blend="mean", device=-1, ctx=None, ramp=32, sampling=None, step=4, sigma_n=10.0, sigma_g=0.1):
@@ -1489,13 +1521,18 @@ def panorama_auto_gain(center, layers, blend="mean", device=-1, ctx=None, ramp=3
     return out, (W, Hc, OX, OY), PanoramaGains(g, q, N, S)
 
 
-def _panorama(center, layers, blend, device, ctx, return_status, ramp, gain_q=None):
-    """``apap_panorama`` (``blend`` 'mean' or 'paste') or ``apap_panorama_ramp`` ('ramp', with the ramp width ``ramp``, which the
-    other blends ignore): the centre picture and every layer (a :class:`PanoramaLayer` or a 5-tuple in its order) on one canvas.
+def _panorama(center, layers, blend, device, ctx, return_status, ramp, gain_q=None, band=8):
+    """``apap_panorama`` (``blend`` 'mean' or 'paste'), ``apap_panorama_ramp`` ('ramp', with the ramp width ``ramp``, which 'mean'
+    and 'paste' ignore) or ``apap_panorama_band`` ('band', with ``ramp`` and the radius ``band``): the centre picture and every
+    layer (a :class:`PanoramaLayer` or a 5-tuple in its order) on one canvas.
     Returns ``(canvas (H, W, 3) uint8, (W, H, OX, OY))`` - with ``return_status=True`` also the per-layer status words, and
     then a status does not raise.  Neither the grids nor any other input is modified."""
     who = "panorama"
-    if gain_q is None:
+    if blend == "band":
+        panorama_entry("ramp", ramp, who)
+        entry = lib().apap_panorama_band
+        tail = [int(ramp), panorama_band_radius(band, who)]
+    elif gain_q is None:
         entry, mode = panorama_entry(blend, ramp, who)
         tail = [mode]
     else:
@@ -1505,6 +1542,8 @@ def _panorama(center, layers, blend, device, ctx, return_status, ramp, gain_q=No
     if gain_q is not None:
         q = panorama_gain_q(gain_q, n + 1, who)
         tail.append(_ip(q))
+    elif blend == "band":
+        tail.append(None)       # apap_panorama_band takes NULL for no gains
     out = np.empty((Hc, W, 3), np.uint8)
     status = np.zeros(n, np.int32)
     code = entry(_h(ctx), *args, *tail, _ptr(out, C.c_uint8), _ip(status), device)

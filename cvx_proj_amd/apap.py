@@ -14,7 +14,7 @@ the inputs come from ``--pair``)::
                                 [--data-root DIR | --pair pair.npz | --synth C1]
                                 [--config configs/case1.txt] [--out-prefix ../diff_1/results/]
                                 [--mesh-size 100] [--gamma 0.5] [--sigma 100] [--warp out.npy | --stitch out.npy]
-                                [--panorama pano.npy [--panorama-blend mean|paste|ramp] [--panorama-ramp 32]
+                                [--panorama pano.npy [--panorama-blend mean|paste|ramp|band] [--panorama-ramp 32] [--panorama-band 8]
                                  [--panorama-gain none|auto] [--panorama-gain-step 4]]
                                 [--resident] [--timing]
 
@@ -269,7 +269,7 @@ class APAP:
         return out
 
 
-def panorama(center_img, layers, blend="mean", device=-1, ctx=None, ramp=32, sampling=None, gain=None, gain_step=4):
+def panorama(center_img, layers, blend="mean", device=-1, ctx=None, ramp=32, sampling=None, gain=None, gain_step=4, band=8):
     """Every view of a case on one canvas, in one fused pass on the GPU: ``center_img`` and each :class:`PanoramaLayer`
     (the neighbour's picture, its grid from :meth:`APAP.local_homography`, its mesh, and the ``final_size`` / offsets of its
     pair - what :meth:`APAP.local_warp` takes), warped through its own grid.  The reference stitches one pair at a time
@@ -283,7 +283,7 @@ def panorama(center_img, layers, blend="mean", device=-1, ctx=None, ramp=32, sam
     elsewhere the first layer with a non-zero byte (the rule of ``image_warping(direct_blend=True)``).  ``blend="ramp"``: the
     mean with a weight per sample, ``min(d, ramp)`` where ``d`` = 1, 2, ... is the distance of the *source* pixel from its
     picture's border (for the centre the pixel itself), so that every picture fades out over ``ramp`` pixels instead of ending
-    in a step; ``ramp`` is an integer 1 .. 256 (1 is ``"mean"``), ignored by the other blends.
+    in a step; ``ramp`` is an integer 1 .. 256 (1 is ``"mean"``), ignored by ``"mean"`` and ``"paste"``.
 
     Returns ``(canvas (H, W, 3) uint8, (W, H, OX, OY))``.  The grids are not modified.  A singular cell raises
     ``LinAlgError``, mesh edges that do not cover a pair canvas ``IndexError``, as ``local_warp`` of that layer would, with
@@ -297,15 +297,29 @@ def panorama(center_img, layers, blend="mean", device=-1, ctx=None, ramp=32, sam
     fitted to the views' overlaps on every ``gain_step``-th canvas row and column (:func:`panorama_gains`) and applied to
     every sample inside the same fused pass -, or a sequence of K + 1 integers ``q`` (the centre first; 4096 = 1.0, 1024 ..
     16383), under which a channel ``c`` becomes ``min(255, (c q + 2048) >> 12)``.  Which samples are present, the ramp's
-    weights and paste's choice of layer do not depend on the gains."""
+    weights and paste's choice of layer do not depend on the gains.
+
+    ``blend="band"``: the two-band blend (Brown & Lowe, IJCV 2007, section 7, with two bands).  Every picture has a low-pass
+    picture, its box blur of radius ``band`` (an integer 0 .. 32) in source space, border replicated.  The low band is
+    ramp-blended (``ramp`` as above); the detail, sample minus low-pass sample, is taken from ONE view, the present one whose
+    source pixel is furthest from its border (the centre first, then the layers in order, on ties), and added, clipped to 0 ..
+    255.  Seams fade as under ``"ramp"``, and fine detail is never averaged, so misregistration cannot double it.  ``band=0``
+    is ``"ramp"`` byte for byte; every other blend ignores ``band``.  With ``gain="auto"`` the gains are fitted as above
+    (:func:`panorama_gains`) and the blend then runs under them: two calls."""
+    if blend == "band":
+        _native.panorama_entry("ramp", ramp, "panorama")
+        _native.panorama_band_radius(band, "panorama")      # before the library is entered
     if gain is None:
-        return _native.panorama(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp, sampling=sampling)
+        return _native.panorama(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp, sampling=sampling, band=band)
     if isinstance(gain, str):
         if gain != "auto":
             raise ValueError(f"panorama: gain must be None, 'auto' or K + 1 integers; got {gain!r}")
-        return _native.panorama_auto_gain(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp, sampling=sampling,
-                                          step=gain_step)[:2]
-    return _native.panorama(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp, sampling=sampling, gain_q=gain)
+        if blend == "band":
+            gain = panorama_gains(center_img, layers, step=gain_step, sampling=sampling, device=device, ctx=ctx).q
+        else:
+            return _native.panorama_auto_gain(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp, sampling=sampling,
+                                              step=gain_step)[:2]
+    return _native.panorama(center_img, layers, blend=blend, device=device, ctx=ctx, ramp=ramp, sampling=sampling, gain_q=gain, band=band)
 
 
 def panorama_gains(center_img, layers, step=4, sigma_n=10.0, sigma_g=0.1, sampling=None, device=-1, ctx=None):
@@ -433,9 +447,12 @@ def main(argv=None):
     ap.add_argument("--panorama", help="stitch ALL the listed pictures of a case (--cases c --imgs i,j,...) onto its centre "
                                        "picture in one fused pass and save the canvas to this .npy (several cases: the case "
                                        "index goes before the extension)")
-    ap.add_argument("--panorama-blend", choices=("mean", "paste", "ramp"), default="mean")
+    ap.add_argument("--panorama-blend", choices=("mean", "paste", "ramp", "band"), default="mean")
     ap.add_argument("--panorama-ramp", type=int, default=32, metavar="N",
-                    help="--panorama-blend ramp: a picture's weight grows over N pixels from its border (1 .. 256)")
+                    help="--panorama-blend ramp or band: a picture's weight grows over N pixels from its border (1 .. 256)")
+    ap.add_argument("--panorama-band", type=int, default=8, metavar="N",
+                    help="--panorama-blend band: the radius of the low-pass pictures' box blur (0 .. 32); the detail above it "
+                         "comes from one picture only")
     ap.add_argument("--panorama-gain", choices=("none", "auto"), default="none",
                     help="auto: exposure gain compensation, one gain per picture fitted to the pictures' overlaps")
     ap.add_argument("--panorama-gain-step", type=int, default=4, metavar="N",
@@ -554,7 +571,7 @@ def main(argv=None):
         t0 = time.perf_counter()
         canvas, bounds = panorama(center_img, layers, blend=a.panorama_blend, device=a.device, ramp=a.panorama_ramp,
                                   sampling=a.sampling, gain=None if a.panorama_gain == "none" else a.panorama_gain,
-                                  gain_step=a.panorama_gain_step)
+                                  gain_step=a.panorama_gain_step, band=a.panorama_band)
         out = a.panorama
         if len(panoramas) > 1:
             root, ext = os.path.splitext(out)

@@ -1259,7 +1259,8 @@ int apap_image_warp(apap_ctx *ctx, const uint8_t *base, int h1, int w1, const ui
 // `status` (may be NULL) receives the n_layers status words whatever the call returns once the kernels ran.  `ramp` as in
 // apap::panorama_check: NULL for apap_panorama, the ramp width for apap_panorama_ramp.  `gain` (NULL: the plain blend): what the
 // gain entry points ask for - the blend under gain_q (kPanoGain), the statistics alone (kPanoStats, no `out`), or statistics,
-// the solve on the host and the blend under its gains (kPanoAuto: two passes, each with the layers' set-up).
+// the solve on the host and the blend under its gains (kPanoAuto: two passes, each with the layers' set-up).  `band` (NULL for
+// every other blend): the two-band blend's radius; its workspace holds the views' low-pass pictures too.
 struct HostGain {
     int what;
     const int *gain_q;
@@ -1273,9 +1274,11 @@ static int panorama_host(apap_ctx *ctx, const uint8_t *center, int center_h, int
                   const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols, const double *const *mesh_w,
                   const int *n_w, const double *const *mesh_h, const int *n_h, const int *final_w, const int *final_h, const int *off_x,
                   const int *off_y, int n_layers, int mode, const int *ramp, uint8_t *out, int *status, int device, const char *who,
-                  const HostGain *gain = nullptr) {
+                  const HostGain *gain = nullptr, const int *band = nullptr) {
     int b[4];
-    int rc = apap::panorama_check(center_h, center_w, img_h, img_w, mesh_rows, mesh_cols, n_w, n_h, final_w, final_h, off_x, off_y,
+    int rc = band ? apap::panorama_band_check(*band, who) : APAP_OK;
+    if (rc) return rc;
+    rc = apap::panorama_check(center_h, center_w, img_h, img_w, mesh_rows, mesh_cols, n_w, n_h, final_w, final_h, off_x, off_y,
                                   n_layers, mode, ramp, b, who);
     if (rc) return rc;
     const int what = gain ? gain->what : apap::kPanoPlain;
@@ -1310,7 +1313,9 @@ static int panorama_host(apap_ctx *ctx, const uint8_t *center, int center_h, int
     call.alloc(l_img); call.alloc(l_h); call.alloc(l_mw); call.alloc(l_mh);
     const Part d_out = blend ? call.slot(S_OUT, (size_t)b[0] * b[1] * 3) : Part{};
     const Part d_status = call.slot(S_STATUS, (size_t)n_layers * sizeof(int));
-    const Part work = call.slot(S_WORK, apap_panorama_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h, n_layers));
+    const Part work = call.slot(S_WORK, band ? apap_panorama_band_workspace_bytes(center_h, center_w, img_h, img_w, mesh_rows, mesh_cols, final_w,
+                                                                                  final_h, n_layers, *band)
+                                             : apap_panorama_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h, n_layers));
     const size_t table_bytes = (size_t)(n_layers + 1) * (n_layers + 1) * sizeof(unsigned long long);
     Layout l_tab = call.layout(S_AUX);
     const Part d_N = l_tab.take(stats ? table_bytes : 0), d_S = l_tab.take(stats ? table_bytes : 0);
@@ -1335,7 +1340,7 @@ static int panorama_host(apap_ctx *ctx, const uint8_t *center, int center_h, int
     const apap::PanoGeometry G{pics.dev(0), center_h, center_w, p_img.data(), img_h, img_w, p_h.data(), mesh_rows, mesh_cols, p_mw.data(),
                                n_w, p_mh.data(), n_h, final_w, final_h, off_x, off_y, n_layers};
     apap::PanoJob J;
-    J.mode = mode; J.ramp = ramp;
+    J.mode = mode; J.ramp = ramp; J.band = band;
     if (stats) {
         J.what = apap::kPanoStats;
         J.step = gain->step; J.d_N = d_N.as<unsigned long long>(); J.d_S = d_S.as<unsigned long long>();
@@ -1413,6 +1418,33 @@ int apap_panorama_auto_gain(apap_ctx *ctx, const uint8_t *center, int center_h, 
     return panorama_host(ctx, center, center_h, center_w, imgs, img_h, img_w, Hfwd, mesh_rows, mesh_cols, mesh_w, n_w, mesh_h, n_h, final_w,
                          final_h, off_x, off_y, n_layers, mode, mode == APAP_PANORAMA_RAMP ? &ramp : nullptr, out, status, device,
                          "apap_panorama_auto_gain", &hg);
+}
+
+int apap_panorama_band(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs, const int *img_h,
+                       const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols,
+                       const double *const *mesh_w, const int *n_w, const double *const *mesh_h, const int *n_h, const int *final_w,
+                       const int *final_h, const int *off_x, const int *off_y, int n_layers, int ramp, int band, const int *gain_q,
+                       uint8_t *out, int *status, int device) {
+    const HostGain g{apap::kPanoGain, gain_q, 1, 0.0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return panorama_host(ctx, center, center_h, center_w, imgs, img_h, img_w, Hfwd, mesh_rows, mesh_cols, mesh_w, n_w, mesh_h, n_h, final_w,
+                         final_h, off_x, off_y, n_layers, APAP_PANORAMA_BAND, &ramp, out, status, device, "apap_panorama_band",
+                         gain_q ? &g : nullptr, &band);
+}
+
+int apap_box_blur(apap_ctx *ctx, const uint8_t *img, int h, int w, int radius, uint8_t *out, int device) {
+    const char *who = "apap_box_blur";
+    int rc = apap::box_blur_check(h, w, radius, who);
+    if (rc) return rc;
+    if (!img || !out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    const size_t bytes = (size_t)h * w * 3;
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    const Part d_img = call.slot(S_IMG, bytes), d_out = call.slot(S_OUT, bytes);
+    call.up(d_img, img);
+    if ((rc = call.rc())) return rc;
+    if ((rc = apap_box_blur_device(ctx, d_img.as<const uint8_t>(), h, w, radius, d_out.as<uint8_t>(), call.stream()))) return rc;
+    call.down(out, d_out);
+    return call.wait();
 }
 
 }  // extern "C"

@@ -159,6 +159,7 @@ struct PanoJob {
     int what = kPanoPlain;
     int mode = APAP_PANORAMA_MEAN;
     const int *ramp = nullptr;      // as in panorama_check
+    const int *band = nullptr;      // the two-band blend (mode APAP_PANORAMA_BAND, `ramp` set; kPanoPlain or kPanoGain): the blur's radius
     uint8_t *d_out = nullptr;
     const int *gain_q = nullptr;    // kPanoGain: n_layers + 1 HOST ints
     int step = 1;                   // kPanoStats, kPanoAuto
@@ -171,6 +172,10 @@ struct PanoJob {
 // the job's kernels on `stream`; does not wait.
 int panorama_run(apap_ctx *ctx, const PanoGeometry &G, const PanoJob &J, void *d_work, size_t work_bytes, int *d_status, void *stream,
                  const char *who);
+// The two-band blend's radius, 0 .. APAP_PANORAMA_MAX_BAND: the first check of its entry points, before panorama_check.
+int panorama_band_check(int band, const char *who);
+// apap_box_blur[_device]'s arguments that need no device: the radius, then a picture of at least 1 pixel and below 2 GiB.
+int box_blur_check(int h, int w, int radius, const char *who);
 // The gain arguments that need no device: n_views 2 .. 17 and, where the pointer is set, step 1 .. 64, every q 1024 .. 16383,
 // sigmas finite and positive.
 int panorama_gain_check(int n_views, const int *step, const int *gain_q, const double *sigma_n, const double *sigma_g, const char *who);

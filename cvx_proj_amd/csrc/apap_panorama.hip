@@ -31,7 +31,21 @@
 //          (below 2^21) and the weight sums of two neighbouring pixels in one (below 2^13 each, 16 bits apart); a layer's
 //          sixteen weights wait for its gathered pixels in registers.  The quotient is ramp_quotient, one IEEE float32
 //          division per channel - exact for these ranges, checked on the host through apap_panorama_ramp_quotients.
+//   band : the two-band blend (DESIGN.md "Panorama, two-band blend"; in numpy: tests/panorama_band_spec.py).  Every view has a
+//          low-pass picture B_v, its box blur of radius `band` in SOURCE space (k_box_blur below, once per picture, border
+//          replicated; band = 0: B_v = I_v) - not a blur of the warped canvas, for the reason the ramp weighs source pixels:
+//          the blend stays in this one pass and needs no canvas-sized intermediate.  A view's sample c_v and the sample b_v of
+//          B_v at the same place (the same pixel, or the same four taps and weights) are gathered together; presence is
+//          decided on c_v.  The low band is the ramp blend of the b_v: L = floor(sum w_v b'_v / sum w_v), w_v = min(D_v, ramp)
+//          with D_v the uncapped border distance of the source pixel.  The detail c'_s - b'_s comes from ONE view, the present
+//          one with the largest D_v (the lowest index on ties), so fine detail is never averaged: out = clip(L + c'_s - b'_s,
+//          0, 255).  Per pixel the ramp's three sums, one register with the weight sum (low 16 bits) and the best D so far
+//          (14 bits, from bit 16), and one with the best view's detail, 9 bits a channel, biased by 255.  A strip of this
+//          mode has kBandRows rows: the second gather's pixels live next to the first's.
 // The canvas is written once with 12-byte non-temporal stores (a row's tail byte by byte, never past the row).
+//
+// k_box_blur: B = (T + (n^2 >> 1)) / n^2, n = 2 r + 1, T the sum of the picture over the n x n window with the border
+// replicated; every view of a call in one launch (descriptors by value).  See the kernel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,6 +61,8 @@ inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int
 
 constexpr int kMaxLayers = APAP_PANORAMA_MAX_LAYERS;
 constexpr int kRows = 4;            // canvas rows of a strip (one wave)
+constexpr int kBandRows = 2;        // ... of the two-band blend, which holds two gathers' pixels at a time
+constexpr int strip_rows(int mode) { return mode == APAP_PANORAMA_BAND ? kBandRows : kRows; }
 constexpr int kWaves = 4;           // strips of a block
 constexpr int kStripCols = 256;     // 64 lanes x 4 pixels
 constexpr unsigned kMeanShift = 18;
@@ -78,7 +94,7 @@ struct PanoLayer {      // 64 bytes
     int img_h, img_w, mesh_cols, fw, fh;
     int dx, dy;                 // the union-canvas column / row of the pair canvas' first: OX - ox, OY - oy
     unsigned last;              // bytes of the source - 4 (gather_px)
-    int pad[2];
+    const uint8_t *blur;        // band: the picture's low-pass picture, the same layout (img itself at band = 0)
 };
 static_assert(sizeof(PanoLayer) == 64, "the descriptor's size in the kernel argument");
 
@@ -88,9 +104,38 @@ struct PanoArgs {
     uint8_t *out;
     int center_h, center_w, OX, OY, W, H, n_layers, col_blocks;
     unsigned clast;             // bytes of the centre - 4
-    int ramp;                   // ramp: the largest weight
+    int ramp;                   // ramp, band: the largest weight
+    const uint8_t *center_blur; // band: the centre's low-pass picture
 };
 static_assert(sizeof(PanoArgs) <= 4096, "kernel arguments");
+
+// ---- the two-band blend's per-pixel steps ----
+// The uncapped distance of pixel (x, y) of a w x h picture from its border, counted from 1: below 2^14 for a picture of
+// less than 2 GiB.
+__host__ __device__ inline int border_distance(int x, int y, int w, int h) { return min_of(min_of(x + 1, w - x), min_of(y + 1, h - y)); }
+constexpr unsigned kNoDetail = 255u | (255u << 9) | (255u << 18);      // c' = b' in every channel
+// c' - b' + 255 per channel, 9 bits each
+__device__ __forceinline__ unsigned band_detail(unsigned cg, unsigned bg) {
+    return ((cg & 0xffu) + 255u - (bg & 0xffu)) | ((((cg >> 8) & 0xffu) + 255u - ((bg >> 8) & 0xffu)) << 9) |
+           (((cg >> 16) + 255u - (bg >> 16)) << 18);
+}
+// One present view's sample into a pixel's state: D is its source pixel's border distance, 0 for an absent view, which then
+// weighs nothing and never beats the best so far.  wd: weight sum (at most 17 x 256) | best D << 16.
+__device__ __forceinline__ void band_take(unsigned cg, unsigned bg, unsigned D, unsigned ramp, unsigned &s0, unsigned &s1, unsigned &s2,
+                                          unsigned &wd, unsigned &det) {
+    const unsigned wt = min(D, ramp);
+    s0 += __umul24(wt, bg & 0xffu);
+    s1 += __umul24(wt, (bg >> 8) & 0xffu);
+    s2 += __umul24(wt, bg >> 16);
+    const bool better = (D << 16) > (wd & 0xffff0000u);     // strictly: the lowest index wins a tie
+    det = better ? band_detail(cg, bg) : det;
+    wd = (better ? (wd & 0xffffu) | (D << 16) : wd) + wt;
+}
+// clip(L + c' - b', 0, 255) of one channel
+__device__ __forceinline__ unsigned band_channel(unsigned low, unsigned biased) {
+    const int v = (int)low + (int)biased - 255;
+    return (unsigned)min(max(v, 0), 255);
+}
 
 // ---- gain compensation (DESIGN.md "Panorama, gain compensation"; the numpy definition is tests/panorama_gain_spec.py) ----
 constexpr int kViews = kMaxLayers + 1;      // view 0 is the centre, view k layer k - 1
@@ -127,6 +172,7 @@ __device__ __forceinline__ unsigned gain_of(const PanoGainArgs &g, int view) {
 template <int kMode, int kSampling, bool kGain>
 __global__ __launch_bounds__(kWaves * 64) void k_panorama(const typename ArgsOf<kGain>::type P) {
     const PanoArgs &A = pano_args(P);
+    constexpr int kRows = strip_rows(kMode);
     __shared__ unsigned recip[32];
     if (kMode == APAP_PANORAMA_MEAN) {
         if (threadIdx.x < 32) recip[threadIdx.x] = threadIdx.x <= (unsigned)kMaxLayers + 1u ? mean_recip(threadIdx.x) : 0u;
@@ -150,6 +196,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const typename ArgsOf<
     unsigned und = 0u;                  // paste: live pixels no picture has decided yet
     unsigned a0[kRows][4], a1[kRows][4];    // mean: ch0 | ch2 << 16 and ch1 | count << 16; paste: a0 = the pixel
     unsigned a2[kRows][4], aw[kRows][2];    // ramp: a0, a1, a2 = sums of weight x channel; aw = weight sums of pixels 2 k | 2 k + 1 << 16
+    unsigned ad[kRows][4], det[kRows][4];   // band: a0, a1, a2 = sums of weight x low band; ad = weight sum | best D << 16; det = the best view's detail
     const int ramp = A.ramp;
     {
         const uint8_t *__restrict__ center = A.center;
@@ -185,6 +232,12 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const typename ArgsOf<
                     a1[t][k] = __umul24(wt, (cg >> 8) & 0xffu);
                     a2[t][k] = __umul24(wt, cg >> 16);
                     aw[t][k >> 1] = (k & 1) ? aw[t][k >> 1] | (wt << 16) : wt;
+                } else if (kMode == APAP_PANORAMA_BAND) {
+                    const unsigned b = gather_px(A.center_blur, co[t][k], A.clast);
+                    const unsigned D = c != 0u ? (unsigned)border_distance(j0 + k - A.OX, y_first + t - A.OY, A.center_w, A.center_h) : 0u;
+                    a0[t][k] = a1[t][k] = a2[t][k] = ad[t][k] = 0u;
+                    det[t][k] = kNoDetail;
+                    band_take(cg, kGain ? gain_px(b, gain_c) : b, D, (unsigned)ramp, a0[t][k], a1[t][k], a2[t][k], ad[t][k], det[t][k]);
                 } else {
                     a0[t][k] = cg;
                     a1[t][k] = 0u;
@@ -202,6 +255,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const typename ArgsOf<
         const int *__restrict__ lut = L.lut;
         const double *__restrict__ hinv_pad = L.hinv_pad;
         const uint8_t *__restrict__ img = L.img;
+        const uint8_t *__restrict__ blur = L.blur;      // band only
         const int img_w = L.img_w, img_h = L.img_h, mesh_cols = L.mesh_cols;
         const unsigned gain_l = gain_of(P, l + 1);
         int col[4];
@@ -255,6 +309,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const typename ArgsOf<
                         const bool ok = strip_source_xy(q[k], yd, img_w, img_h, ix, iy, tx, ty) & (((want >> (4 * t + k)) & 1u) != 0u);
                         bilinear_taps(ok, tx, ty, img_w, img_h, boff[t][k], bfr[t][k]);
                         if (kMode == APAP_PANORAMA_RAMP) bfr[t][k] |= (ok ? (unsigned)ramp_weight(ix, iy, img_w, img_h, ramp) : 0u) << 16;
+                        if (kMode == APAP_PANORAMA_BAND) bfr[t][k] |= (ok ? (unsigned)border_distance(ix, iy, img_w, img_h) : 0u) << 16;
                     }
                 }
             }
@@ -264,11 +319,22 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const typename ArgsOf<
                 unsigned tap[4][4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) gather_taps(img, boff[t][k], bfr[t][k], row_bytes, last, tap[k]);
+                unsigned low[4];        // band: the low-pass picture through the same taps and weights
+                if (kMode == APAP_PANORAMA_BAND) {
+                    unsigned btap[4][4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) gather_taps(blur, boff[t][k], bfr[t][k], row_bytes, last, btap[k]);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) low[k] = bilinear_blend(btap[k], bfr[t][k]);
+                }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const unsigned v = bilinear_blend(tap[k], bfr[t][k]);
                     const unsigned vg = kGain ? gain_px(v, gain_l) : v;
-                    if (kMode == APAP_PANORAMA_MEAN) {
+                    if (kMode == APAP_PANORAMA_BAND) {
+                        const unsigned D = v != 0u ? bfr[t][k] >> 16 : 0u;
+                        band_take(vg, kGain ? gain_px(low[k], gain_l) : low[k], D, (unsigned)ramp, a0[t][k], a1[t][k], a2[t][k], ad[t][k], det[t][k]);
+                    } else if (kMode == APAP_PANORAMA_MEAN) {
                         a0[t][k] += vg & 0x00ff00ffu;
                         a1[t][k] += ((vg >> 8) & 0xffu) | ((unsigned)(v != 0u) << 16);
                     } else if (kMode == APAP_PANORAMA_RAMP) {
@@ -315,6 +381,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const typename ArgsOf<
                     const bool ok = strip_source(q[k], yd, img_w, img_h, ix, iy) & (((want >> (4 * t + k)) & 1u) != 0u);
                     off[t][k] = strip_offset(ok, ix, iy, img_w);
                     if (kMode == APAP_PANORAMA_RAMP) wgt[t][k] = (unsigned)ramp_weight(ix, iy, img_w, img_h, ramp);  // used where ok
+                    if (kMode == APAP_PANORAMA_BAND) wgt[t][k] = (unsigned)border_distance(ix, iy, img_w, img_h);    // D, used where ok
                 }
             }
         }
@@ -324,13 +391,24 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const typename ArgsOf<
         for (int t = 0; t < kRows; ++t)
 #pragma unroll
             for (int k = 0; k < 4; ++k) px[t][k] = gather_px(img, off[t][k], last);
+        unsigned bpx[kRows][4];         // band: the low-pass picture at the same offsets
+        if (kMode == APAP_PANORAMA_BAND) {
+#pragma unroll
+            for (int t = 0; t < kRows; ++t)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) bpx[t][k] = gather_px(blur, off[t][k], last);
+        }
 #pragma unroll
         for (int t = 0; t < kRows; ++t) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const unsigned v = px[t][k];
                 const unsigned vg = kGain ? gain_px(v, gain_l) : v;
-                if (kMode == APAP_PANORAMA_MEAN) {
+                if (kMode == APAP_PANORAMA_BAND) {
+                    // v != 0 only where the sample lies inside its picture, where wgt is its distance
+                    const unsigned D = v != 0u ? wgt[t][k] : 0u;
+                    band_take(vg, kGain ? gain_px(bpx[t][k], gain_l) : bpx[t][k], D, (unsigned)ramp, a0[t][k], a1[t][k], a2[t][k], ad[t][k], det[t][k]);
+                } else if (kMode == APAP_PANORAMA_MEAN) {
                     a0[t][k] += vg & 0x00ff00ffu;
                     a1[t][k] += ((vg >> 8) & 0xffu) | ((unsigned)(v != 0u) << 16);
                 } else if (kMode == APAP_PANORAMA_RAMP) {
@@ -362,11 +440,154 @@ __global__ __launch_bounds__(kWaves * 64) void k_panorama(const typename ArgsOf<
             } else if (kMode == APAP_PANORAMA_RAMP) {
                 const unsigned ws = (aw[t][k >> 1] >> (16 * (k & 1))) & 0xffffu;
                 p[k] = ramp_quotient(a0[t][k], ws) | (ramp_quotient(a1[t][k], ws) << 8) | (ramp_quotient(a2[t][k], ws) << 16);
+            } else if (kMode == APAP_PANORAMA_BAND) {
+                const unsigned ws = ad[t][k] & 0xffffu, d = det[t][k];
+                p[k] = band_channel(ramp_quotient(a0[t][k], ws), d & 0x1ffu) | (band_channel(ramp_quotient(a1[t][k], ws), (d >> 9) & 0x1ffu) << 8) |
+                       (band_channel(ramp_quotient(a2[t][k], ws), d >> 18) << 16);
             } else {
                 p[k] = a0[t][k];
             }
         }
         APAP_STORE_PX4(A.out + ((size_t)y * (size_t)A.W + (size_t)j0) * 3u, p, npx);
+    }
+}
+
+// ---- the low-pass pictures of the two-band blend ----------------------------------------------------------------------------
+// k_box_blur: B = (T + (n^2 >> 1)) / n^2 with n = 2 r + 1 and T[y][x][c] the sum of I[clamp(y + dy)][clamp(x + dx)][c] over
+// |dx|, |dy| <= r, for every picture of a call in ONE launch: the descriptors travel by value, a block finds its picture by
+// comparing its index with the pictures' first blocks (scalar compares).  A block owns a tile of kBlurCols x th pixels
+// (th = 32 rows up to r = 16, 16 rows above: the tile with its halo and the row sums fill at most 60 KB of LDS) and goes
+// through four phases, a barrier after each:
+//   load   the tile's rows with their halo, (th + 2 r) rows of (kBlurCols + 2 r) pixels, into LDS as bytes.  A row of the
+//          picture is 3 w bytes and starts at any alignment: the row's span is read as the ALIGNED dwords that cover it; a
+//          dword that is not wholly inside the picture (only the picture's first and last can be) byte by byte, the bytes
+//          inside it only.  A row above or below the picture is the clamped row, read again; the columns beside the picture
+//          are then filled from the row's first / last pixel in LDS.  Every byte of the LDS tile is written.
+//   rows   16-bit sums over n pixels along x (at most 255 x 65), as running sums over runs of kBlurRun outputs.
+//   cols   32-bit sums of n row sums along y, as running sums over runs of kBlurRun rows, then the division: T + (n^2 >> 1)
+//          is below 2^21 and n^2 <= 4225, ramp_quotient's ranges (checked exhaustively on the host through
+//          apap_panorama_ramp_quotients).  The bytes go to LDS, over the dead input tile.
+//   store  the tile's rows as aligned dwords; a dword that is not wholly inside the tile's span of the row byte by byte, the
+//          bytes inside it only - a neighbouring tile owns the others.  Plain stores: the canvas pass reads them next.
+// Integers throughout: the result depends neither on the tile nor on any order.
+constexpr int kBlurCols = 64, kBlurThreads = 256, kBlurRun = 8;
+constexpr int kBlurOutBytes = kBlurCols * 3;
+
+struct BlurView {       // 32 bytes
+    const uint8_t *img;
+    uint8_t *out;
+    int h, w;
+    unsigned first, tiles_x;    // the picture's first block; tiles in a row of tiles
+};
+struct BlurArgs {
+    BlurView view[kViews];
+    int n_views, r, th;
+};
+static_assert(sizeof(BlurArgs) <= 4096, "kernel arguments");
+
+__host__ __device__ inline int blur_tile_rows(int r) { return r <= 16 ? 32 : 16; }
+__host__ __device__ inline int blur_in_stride(int r) { return ((kBlurCols + 2 * r) * 3 + 3) & ~3; }
+__host__ __device__ inline size_t blur_lds_bytes(int r) {
+    const int rows_in = blur_tile_rows(r) + 2 * r;
+    return (size_t)rows_in * blur_in_stride(r) + (size_t)rows_in * kBlurOutBytes * sizeof(uint16_t);
+}
+
+__global__ __launch_bounds__(kBlurThreads) void k_box_blur(const BlurArgs P) {
+    extern __shared__ __align__(16) uint8_t blur_lds[];
+    int vi = 0;
+    for (int i = 1; i < P.n_views; ++i) vi = blockIdx.x >= P.view[i].first ? i : vi;    // first blocks ascend
+    const BlurView &V = P.view[vi];
+    const uint8_t *__restrict__ img = V.img;
+    uint8_t *__restrict__ out = V.out;
+    const int w = V.w, h = V.h, r = P.r, n = 2 * r + 1, th = P.th;
+    const unsigned tile = blockIdx.x - V.first;
+    const int tile_y = (int)(tile / V.tiles_x), tile_x = (int)(tile - (unsigned)tile_y * V.tiles_x);
+    const int x0 = tile_x * kBlurCols, y0 = tile_y * th;
+    const int rows_in = th + 2 * r, cols_in = kBlurCols + 2 * r, in_stride = blur_in_stride(r);
+    uint8_t *tin = blur_lds;
+    uint16_t *hs = (uint16_t *)(blur_lds + (size_t)rows_in * in_stride);
+    const int tid = threadIdx.x;
+    const long long total = (long long)h * w * 3;
+
+    // load: pixels [xa, xb) of every row, to LDS columns [ca, cb)
+    const int xa = max(x0 - r, 0), xb = min(x0 + kBlurCols + r, w);
+    const int ca = xa - (x0 - r), cb = xb - (x0 - r);
+    {
+        const int nb = (xb - xa) * 3, ndm = (nb + 6) >> 2;      // dwords that cover nb bytes at any alignment
+        for (int it = tid; it < rows_in * ndm; it += kBlurThreads) {
+            const int ry = it / ndm, d = it - ry * ndm;
+            const int sy = min(max(y0 - r + ry, 0), h - 1);
+            const long long g = ((long long)sy * w + xa) * 3;
+            const long long p = g - (long long)((uintptr_t)(img + g) & 3u) + 4 * d;
+            const long long lo = p > g ? p : g, hi = p + 4 < g + nb ? p + 4 : g + nb;
+            if (lo >= hi) continue;
+            unsigned v = 0u;
+            if (p >= 0 && p + 4 <= total) {
+                v = *(const unsigned *)(img + p);
+            } else {
+                for (long long q = lo; q < hi; ++q) v |= (unsigned)img[q] << (8 * (int)(q - p));
+            }
+            uint8_t *dst = tin + ry * in_stride + ca * 3 + (int)(p - g);
+            for (long long q = lo; q < hi; ++q) dst[(int)(q - p)] = (uint8_t)(v >> (8 * (int)(q - p)));
+        }
+    }
+    __syncthreads();
+    {   // the columns beside the picture: the row's first / last pixel
+        const int pad = ca + (cols_in - cb);
+        for (int it = tid; it < rows_in * pad * 3; it += kBlurThreads) {
+            const int ry = it / (pad * 3), e = it - ry * (pad * 3), pc = e / 3, c = e - pc * 3;
+            const int col = pc < ca ? pc : cb + (pc - ca);
+            tin[ry * in_stride + col * 3 + c] = tin[ry * in_stride + (pc < ca ? ca : cb - 1) * 3 + c];
+        }
+    }
+    __syncthreads();
+    // rows: hs[ry][ob] = the sum of tin[ry][ob + 3 j], j = 0 .. 2 r
+    for (int it = tid; it < rows_in * (kBlurOutBytes / kBlurRun); it += kBlurThreads) {
+        const int ry = it / (kBlurOutBytes / kBlurRun), e = it - ry * (kBlurOutBytes / kBlurRun), run = e / 3, c = e - run * 3;
+        const uint8_t *src = tin + ry * in_stride + run * kBlurRun * 3 + c;
+        uint16_t *dst = hs + ry * kBlurOutBytes + run * kBlurRun * 3 + c;
+        unsigned s = 0u;
+        for (int j = 0; j < n; ++j) s += src[3 * j];
+        dst[0] = (uint16_t)s;
+#pragma unroll
+        for (int i = 1; i < kBlurRun; ++i) {
+            s += (unsigned)src[3 * (i - 1 + n)] - (unsigned)src[3 * (i - 1)];
+            dst[3 * i] = (uint16_t)s;
+        }
+    }
+    __syncthreads();
+    // cols: the sums of n row sums, the quotient, the byte over the dead input tile
+    uint8_t *tout = tin;
+    const unsigned n2 = (unsigned)(n * n), half = n2 >> 1;
+    for (int it = tid; it < (th / kBlurRun) * kBlurOutBytes; it += kBlurThreads) {
+        const int run = it / kBlurOutBytes, ob = it - run * kBlurOutBytes;
+        const uint16_t *src = hs + run * kBlurRun * kBlurOutBytes + ob;
+        uint8_t *dst = tout + run * kBlurRun * kBlurOutBytes + ob;
+        unsigned s = 0u;
+        for (int j = 0; j < n; ++j) s += src[j * kBlurOutBytes];
+        dst[0] = (uint8_t)ramp_quotient(s + half, n2);
+#pragma unroll
+        for (int i = 1; i < kBlurRun; ++i) {
+            s += (unsigned)src[(i - 1 + n) * kBlurOutBytes] - (unsigned)src[(i - 1) * kBlurOutBytes];
+            dst[i * kBlurOutBytes] = (uint8_t)ramp_quotient(s + half, n2);
+        }
+    }
+    __syncthreads();
+    // store: pixels [x0, xe) of rows [y0, y0 + rows_out)
+    const int rows_out = min(th, h - y0), nb = (min(x0 + kBlurCols, w) - x0) * 3;
+    constexpr int ndm = (kBlurOutBytes + 6) >> 2;
+    for (int it = tid; it < rows_out * ndm; it += kBlurThreads) {
+        const int oy = it / ndm, d = it - oy * ndm;
+        const long long g = ((long long)(y0 + oy) * w + x0) * 3;
+        const long long p = g - (long long)((uintptr_t)(out + g) & 3u) + 4 * d;
+        const long long lo = p > g ? p : g, hi = p + 4 < g + nb ? p + 4 : g + nb;
+        if (lo >= hi) continue;
+        const uint8_t *src = tout + oy * kBlurOutBytes + (int)(p - g);
+        if (lo == p && hi == p + 4) {
+            *(unsigned *)(out + p) = (unsigned)src[0] | ((unsigned)src[1] << 8) | ((unsigned)src[2] << 16) | ((unsigned)src[3] << 24);
+        } else {
+            for (long long q = lo; q < hi; ++q) out[q] = src[(int)(q - p)];
+        }
     }
 }
 
@@ -683,17 +904,59 @@ int panorama_check(int center_h, int center_w, const int *img_h, const int *img_
     return APAP_OK;
 }
 
+int panorama_band_check(int band, const char *who) {
+    if (band < 0 || band > APAP_PANORAMA_MAX_BAND) return fail(APAP_ERR_INVALID_ARG, "%s: band = %d (0 .. %d)", who, band, APAP_PANORAMA_MAX_BAND);
+    return APAP_OK;
+}
+
+// k_box_blur of radius r = 1 .. APAP_PANORAMA_MAX_BAND over n = 1 .. kViews pictures (img, out, h, w set; checked by the caller).
+static int blur_launch(apap_ctx *ctx, const BlurView *views, int n, int r, void *stream) {
+    BlurArgs B;
+    std::memset(&B, 0, sizeof(B));
+    B.r = r;
+    B.th = blur_tile_rows(r);
+    B.n_views = n;
+    unsigned long long blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        B.view[i] = views[i];
+        B.view[i].tiles_x = (unsigned)((views[i].w + kBlurCols - 1) / kBlurCols);
+        B.view[i].first = (unsigned)blocks;
+        blocks += (unsigned long long)B.view[i].tiles_x * (unsigned)((views[i].h + B.th - 1) / B.th);
+    }
+    if (blocks >= (1ull << 31)) return apap::fail(APAP_ERR_INVALID_ARG, "k_box_blur: 2^31 tiles or more");
+    hipStream_t s = (hipStream_t)stream;
+    {
+        apap::ProfScope prof(ctx, APAP_PROF_WARP, s);
+        hipLaunchKernelGGL(k_box_blur, dim3((unsigned)blocks), dim3(kBlurThreads), blur_lds_bytes(r), s, B);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "k_box_blur launch");
+    return APAP_OK;
+}
+
+static bool blur_picture(int h, int w) { return h >= 1 && w >= 1 && (unsigned long long)h * (unsigned long long)w * 3ull < (1ull << 31); }
+
+int box_blur_check(int h, int w, int radius, const char *who) {
+    if (radius < 0 || radius > APAP_PANORAMA_MAX_BAND)
+        return fail(APAP_ERR_INVALID_ARG, "%s: radius = %d (0 .. %d)", who, radius, APAP_PANORAMA_MAX_BAND);
+    if (!blur_picture(h, w)) return fail(APAP_ERR_INVALID_ARG, "%s: picture %d x %d (at least 1 pixel, below 2 GiB)", who, h, w);
+    return APAP_OK;
+}
+
 // The checks of the device forms that follow panorama_check, the warp's own set-up of every layer into its slice of the
-// workspace, and the kernel arguments all three kernels share (`out` is left NULL).
+// workspace, and the kernel arguments all three kernels share (`out` is left NULL).  band (NULL for every other blend): the
+// low-pass pictures of the views into their slots behind the layers' slices, one k_box_blur launch, and their pointers.
 static int panorama_prepare(apap_ctx *ctx, const PanoGeometry &G, const int *b, void *d_work, size_t work_bytes, int *d_status,
-                            void *stream, const char *who, PanoArgs &A) {
+                            void *stream, const char *who, PanoArgs &A, const int *band = nullptr) {
     const int n_layers = G.n_layers;
     if (!G.d_center || !G.d_imgs || !G.d_Hfwd || !G.d_mesh_w || !G.d_mesh_h || !d_work || !d_status)
         return apap::fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
     for (int k = 0; k < n_layers; ++k)
         if (!G.d_imgs[k] || !G.d_Hfwd[k] || !G.d_mesh_w[k] || !G.d_mesh_h[k])
             return apap::fail(APAP_ERR_INVALID_ARG, "%s: layer %d: null device pointer", who, k);
-    const size_t need = apap_panorama_workspace_bytes(G.mesh_rows, G.mesh_cols, G.final_w, G.final_h, n_layers);
+    const size_t need = band ? apap_panorama_band_workspace_bytes(G.center_h, G.center_w, G.img_h, G.img_w, G.mesh_rows, G.mesh_cols, G.final_w,
+                                                                  G.final_h, n_layers, *band)
+                             : apap_panorama_workspace_bytes(G.mesh_rows, G.mesh_cols, G.final_w, G.final_h, n_layers);
     if (work_bytes < need) return apap::fail(APAP_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, work_bytes, need);
     if (((uintptr_t)d_work & 255) != 0) return apap::fail(APAP_ERR_INVALID_ARG, "%s: workspace must be 256-byte aligned", who);
 
@@ -723,15 +986,42 @@ static int panorama_prepare(apap_ctx *ctx, const PanoGeometry &G, const int *b, 
     A.n_layers = n_layers;
     A.col_blocks = (A.W + kStripCols - 1) / kStripCols;
     A.clast = (unsigned)G.center_h * (unsigned)G.center_w * 3u - 4u;
-    return APAP_OK;
+    if (!band) return APAP_OK;
+    // band = 0: B = I.  Else view v's low-pass picture in slot v; a view whose picture (pointer and size) an earlier view has
+    // reads that view's and is not blurred again.
+    BlurView todo[kViews];
+    int n_todo = 0;
+    const uint8_t *blurred[kViews];
+    for (int v = 0; v <= n_layers; ++v) {
+        const uint8_t *img = v ? G.d_imgs[v - 1] : G.d_center;
+        const int h = v ? G.img_h[v - 1] : G.center_h, wd = v ? G.img_w[v - 1] : G.center_w;
+        blurred[v] = img;
+        if (*band > 0) {
+            int same = -1;
+            for (int u = 0; u < v && same < 0; ++u)
+                if ((u ? G.d_imgs[u - 1] : G.d_center) == img && (u ? G.img_h[u - 1] : G.center_h) == h && (u ? G.img_w[u - 1] : G.center_w) == wd)
+                    same = u;
+            if (same >= 0) {
+                blurred[v] = blurred[same];
+            } else {
+                blurred[v] = (const uint8_t *)w;
+                todo[n_todo++] = BlurView{img, (uint8_t *)w, h, wd, 0u, 0u};
+            }
+            w += up256((size_t)h * wd * 3);
+        }
+        if (v) A.layer[v - 1].blur = blurred[v];
+        else A.center_blur = blurred[v];
+    }
+    return n_todo ? blur_launch(ctx, todo, n_todo, *band, stream) : APAP_OK;
 }
 
 // k_panorama over the canvas.  gain_q (host, n_layers + 1 values) or d_gain (device) selects the gained forms.
 static int panorama_launch(apap_ctx *ctx, PanoArgs &A, int mode, const int *ramp, const int *gain_q, const int *d_gain, uint8_t *d_out,
-                           void *stream) {
+                           void *stream, bool band = false) {
     A.out = d_out;
     A.ramp = ramp ? *ramp : 0;
-    const unsigned row_blocks = (unsigned)((A.H + kWaves * kRows - 1) / (kWaves * kRows));
+    const int rows = kWaves * strip_rows(band ? APAP_PANORAMA_BAND : APAP_PANORAMA_RAMP);
+    const unsigned row_blocks = (unsigned)((A.H + rows - 1) / rows);
     const dim3 grid((unsigned)A.col_blocks * row_blocks);       // W H < 2^31: below 2^31 blocks
     hipStream_t s = (hipStream_t)stream;
     const bool bilinear = apap::opt(ctx, APAP_OPT_WARP_SAMPLING) == APAP_SAMPLING_BILINEAR;
@@ -740,7 +1030,8 @@ static int panorama_launch(apap_ctx *ctx, PanoArgs &A, int mode, const int *ramp
         // APAP_OPT_WARP_SAMPLING: the option the pair warps read (the set-up phases above do not depend on it)
 #define APAP_LAUNCH_PANORAMA(S, GAIN, ARGS)                                                                                       \
     do {                                                                                                                          \
-        if (ramp) hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_RAMP, S, GAIN>), grid, dim3(kWaves * 64), 0, s, ARGS);             \
+        if (band) hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_BAND, S, GAIN>), grid, dim3(kWaves * 64), 0, s, ARGS);             \
+        else if (ramp) hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_RAMP, S, GAIN>), grid, dim3(kWaves * 64), 0, s, ARGS);        \
         else if (mode == APAP_PANORAMA_MEAN) hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_MEAN, S, GAIN>), grid, dim3(kWaves * 64), 0, s, ARGS); \
         else hipLaunchKernelGGL((k_panorama<APAP_PANORAMA_PASTE, S, GAIN>), grid, dim3(kWaves * 64), 0, s, ARGS);                 \
     } while (0)
@@ -813,8 +1104,10 @@ int panorama_gain_check(int n_views, const int *step, const int *gain_q, const d
 int panorama_run(apap_ctx *ctx, const PanoGeometry &G, const PanoJob &J, void *d_work, size_t work_bytes, int *d_status, void *stream,
                  const char *who) {
     int b[4];
-    int rc = panorama_check(G.center_h, G.center_w, G.img_h, G.img_w, G.mesh_rows, G.mesh_cols, G.n_w, G.n_h, G.final_w, G.final_h, G.off_x,
-                            G.off_y, G.n_layers, J.mode, J.ramp, b, who);
+    int rc = J.band ? panorama_band_check(*J.band, who) : APAP_OK;
+    if (rc) return rc;
+    rc = panorama_check(G.center_h, G.center_w, G.img_h, G.img_w, G.mesh_rows, G.mesh_cols, G.n_w, G.n_h, G.final_w, G.final_h, G.off_x,
+                        G.off_y, G.n_layers, J.mode, J.ramp, b, who);
     if (rc) return rc;
     const bool stats = J.what == kPanoStats || J.what == kPanoAuto;
     if (J.what != kPanoPlain &&
@@ -826,7 +1119,7 @@ int panorama_run(apap_ctx *ctx, const PanoGeometry &G, const PanoJob &J, void *d
     if (J.what == kPanoAuto && (!J.d_g || !J.d_q || !J.d_flag)) return fail(APAP_ERR_INVALID_ARG, "%s: null gain output", who);
     if (J.what != kPanoStats && !J.d_out) return fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
     PanoArgs A;
-    if ((rc = panorama_prepare(ctx, G, b, d_work, work_bytes, d_status, stream, who, A))) return rc;
+    if ((rc = panorama_prepare(ctx, G, b, d_work, work_bytes, d_status, stream, who, A, J.band))) return rc;
     if (stats && (rc = stats_launch(ctx, A, J.step, J.d_N, J.d_S, stream))) return rc;
     if (J.what == kPanoStats) return APAP_OK;
     if (J.what == kPanoAuto) {
@@ -836,7 +1129,7 @@ int panorama_run(apap_ctx *ctx, const PanoGeometry &G, const PanoJob &J, void *d
         if (e != hipSuccess) return hip_fail(e, "k_panorama_gain_solve launch");
     }
     return panorama_launch(ctx, A, J.mode, J.ramp, J.what == kPanoGain ? J.gain_q : nullptr, J.what == kPanoAuto ? J.d_q : nullptr, J.d_out,
-                           stream);
+                           stream, J.band != nullptr);
 }
 
 int panorama_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs, const int *img_h,
@@ -966,6 +1259,48 @@ int apap_panorama_ramp_device(apap_ctx *ctx, const uint8_t *d_center, int center
     return apap::panorama_device(ctx, d_center, center_h, center_w, d_imgs, img_h, img_w, d_Hfwd, mesh_rows, mesh_cols, d_mesh_w, n_w,
                                  d_mesh_h, n_h, final_w, final_h, off_x, off_y, n_layers, APAP_PANORAMA_RAMP, &ramp, d_out, d_work,
                                  work_bytes, d_status, stream, "apap_panorama_ramp_device");
+}
+
+size_t apap_panorama_band_workspace_bytes(int center_h, int center_w, const int *img_h, const int *img_w, const int *mesh_rows,
+                                          const int *mesh_cols, const int *final_w, const int *final_h, int n_layers, int band) {
+    const size_t base = apap_panorama_workspace_bytes(mesh_rows, mesh_cols, final_w, final_h, n_layers);
+    if (base == 0 || !img_h || !img_w || band < 0 || band > APAP_PANORAMA_MAX_BAND || !apap::blur_picture(center_h, center_w)) return 0;
+    size_t total = base + (band ? apap::up256((size_t)center_h * center_w * 3) : 0);
+    for (int k = 0; k < n_layers; ++k) {
+        if (!apap::blur_picture(img_h[k], img_w[k])) return 0;
+        if (band) total += apap::up256((size_t)img_h[k] * img_w[k] * 3);
+    }
+    return total;
+}
+
+int apap_box_blur_device(apap_ctx *ctx, const uint8_t *d_img, int h, int w, int radius, uint8_t *d_out, void *stream) {
+    const char *who = "apap_box_blur_device";
+    const int rc = apap::box_blur_check(h, w, radius, who);
+    if (rc) return rc;
+    if (!d_img || !d_out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
+    const size_t bytes = (size_t)h * w * 3;
+    if (d_img < d_out + bytes && d_out < d_img + bytes) return apap::fail(APAP_ERR_INVALID_ARG, "%s: the output overlaps the picture", who);
+    if (radius == 0) {
+        const hipError_t e = hipMemcpyAsync(d_out, d_img, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        return e == hipSuccess ? APAP_OK : hip_fail(e, "apap_box_blur_device: copy");
+    }
+    const BlurView v{d_img, d_out, h, w, 0u, 0u};
+    return apap::blur_launch(ctx, &v, 1, radius, stream);
+}
+
+int apap_panorama_band_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                              const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows,
+                              const int *mesh_cols, const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h,
+                              const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers,
+                              int ramp, int band, const int *gain_q, uint8_t *d_out, void *d_work, size_t work_bytes, int *d_status,
+                              void *stream) {
+    const apap::PanoGeometry G{d_center, center_h, center_w, d_imgs, img_h, img_w, d_Hfwd, mesh_rows, mesh_cols, d_mesh_w, n_w, d_mesh_h,
+                               n_h, final_w, final_h, off_x, off_y, n_layers};
+    apap::PanoJob J;
+    J.what = gain_q ? apap::kPanoGain : apap::kPanoPlain;
+    J.mode = APAP_PANORAMA_BAND; J.ramp = &ramp; J.band = &band;
+    J.gain_q = gain_q; J.d_out = d_out;
+    return apap::panorama_run(ctx, G, J, d_work, work_bytes, d_status, stream, "apap_panorama_band_device");
 }
 
 }  // extern "C"

@@ -617,8 +617,38 @@ def panorama_workspace_bytes(layers):
     return _native.lib().apap_panorama_workspace_bytes(_ip(mr), _ip(mc), _ip(fw), _ip(fh), len(layers))
 
 
+def panorama_band_workspace_bytes(center, layers, band):
+    """Scratch of ``hip_panorama(blend="band", band=band)``: ``panorama_workspace_bytes(layers)`` and, for ``band`` > 0, a
+    256-byte aligned slot per view (the centre, then every layer) for its low-pass picture.  0 for invalid arguments."""
+    band = _native.panorama_band_radius(band, "panorama_band_workspace_bytes")
+    layers, (fw, fh, _, _) = _native.panorama_geometry(layers, "panorama_band_workspace_bytes")
+    ih, iw = _i32([l.img.shape[0] for l in layers]), _i32([l.img.shape[1] for l in layers])
+    mr = _i32([l.local_homography.shape[0] for l in layers])
+    mc = _i32([l.local_homography.shape[1] for l in layers])
+    return _native.lib().apap_panorama_band_workspace_bytes(int(center.shape[0]), int(center.shape[1]), _ip(ih), _ip(iw), _ip(mr), _ip(mc),
+                                                            _ip(fw), _ip(fh), len(layers), band)
+
+
+def hip_box_blur(img, radius, out=None, ctx=None):
+    """``apap_box_blur_device`` on the current stream, not synchronised: the two-band blend's low-pass picture of ``img``, a
+    contiguous (h, w, 3) uint8 device tensor, for ``radius`` 0 .. 32 (``_native.box_blur`` on device tensors).  ``out``: a
+    tensor like ``img`` to write into, not ``img`` itself."""
+    who = "hip_box_blur"
+    radius = _native.panorama_band_radius(radius, who)
+    _needs_device(img, who)
+    if img.dtype != torch.uint8 or not img.is_contiguous() or img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError(f"{who}: the picture must be a contiguous uint8 (h, w, 3) tensor")
+    if out is None:
+        out = torch.empty_like(img)
+    if out.dtype != torch.uint8 or out.shape != img.shape or not out.is_contiguous() or out.device != img.device:
+        raise ValueError(f"{who}: out must be a contiguous uint8 tensor of shape {tuple(img.shape)} on {img.device}")
+    _native.check(_native.lib().apap_box_blur_device(_native._h(ctx), img.data_ptr(), img.shape[0], img.shape[1], radius, out.data_ptr(),
+                                                     _stream(img.device)))
+    return out
+
+
 def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, work=None, ramp=32, sampling=None, gain=None,
-                 gain_step=4, sigma_n=10.0, sigma_g=0.1, return_gains=False):
+                 gain_step=4, sigma_n=10.0, sigma_g=0.1, return_gains=False, band=8):
     """``apap_panorama_device`` (``blend="ramp"``: ``apap_panorama_ramp_device`` with the ramp width ``ramp``, an integer 1 ..
     256 that the other blends ignore) on the current stream of the tensors' device, no host synchronisation: the centre picture and
     every layer on one canvas in one fused pass (``apap.panorama`` on device tensors).  ``center`` (h, w, 3) uint8; a layer is
@@ -634,7 +664,13 @@ def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, 
     (``apap_panorama_auto_gain_device``): the overlap statistics on every ``gain_step``-th canvas row and column, the solve
     on the device and the gained blend, one after the other on the stream - nothing waits for the host.  With
     ``return_gains=True`` and ``"auto"`` a fourth value follows: ``_native.PanoramaGains`` of device tensors (``gains``
-    float64, ``q`` int32, ``N``, ``S`` int64 holding the uint64 statistics), not synchronised."""
+    float64, ``q`` int32, ``N``, ``S`` int64 holding the uint64 statistics), not synchronised.
+
+    ``blend="band"``: ``apap_panorama_band_device``, the two-band blend of ``apap.panorama`` with the ramp width ``ramp`` and
+    the low-pass radius ``band``, an integer 0 .. 32 that every other blend ignores; ``work`` is used when it holds
+    ``panorama_band_workspace_bytes(center, layers, band)``.  K + 1 integers as ``gain`` go into the same call.  With
+    ``gain="auto"`` the statistics run on the stream, the call WAITS for them once, solves on the host and enqueues the blend
+    under the gains it found (``return_gains`` then gives host arrays); there is no fused resident form of that."""
     who = "hip_panorama"
     _native.sampling_value(sampling, who)
     _needs_device(center, who)
@@ -644,7 +680,20 @@ def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, 
         raise ValueError(f"{who}: gain must be None, 'auto' or K + 1 integers; got {gain!r}")
     if return_gains and not auto:
         raise ValueError(f"{who}: return_gains goes with gain='auto'")
-    if gain is None:
+    is_band = blend == "band"
+    host_gains = None
+    if is_band:
+        _native.panorama_entry("ramp", ramp, who)
+        band = _native.panorama_band_radius(band, who)
+        if auto:        # the statistics, one wait, the solve on the host; then the blend under q
+            N, S, _ = hip_panorama_gain_stats(center, layers, step=gain_step, status=status, ctx=ctx, work=work, sampling=sampling)
+            N, S = N.cpu().numpy().view(np.uint64), S.cpu().numpy().view(np.uint64)
+            g, q, _ = _native.panorama_gain_solve(N, S, sigma_n, sigma_g)
+            host_gains = _native.PanoramaGains(g, q, N, S)
+            gain, auto = q, False
+        entry = _native.lib().apap_panorama_band_device
+        tail = [int(ramp), band]
+    elif gain is None:
         entry, mode = _native.panorama_entry(blend, ramp, who, device_form=True)
         tail = [mode]
     else:
@@ -658,6 +707,8 @@ def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, 
     elif gain is not None:
         q_host = _native.panorama_gain_q(gain, n + 1, who)
         tail.append(_ip(q_host))
+    elif is_band:
+        tail.append(None)       # apap_panorama_band_device takes NULL for no gains
 
     def tensor(t, dtype, name, k):
         if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
@@ -688,7 +739,11 @@ def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, 
     nw, nh = _i32([t.numel() for t in mws]), _i32([t.numel() for t in mhs])
     table = [_addrs([t.data_ptr() for t in ts]) for ts in (imgs, grids, mws, mhs)]
     p_mr, p_mc, p_fw, p_fh = _ip(mr), _ip(mc), _ip(fw), _ip(fh)
-    work = _scratch(work, _native.lib().apap_panorama_workspace_bytes(p_mr, p_mc, p_fw, p_fh, n), dev)
+    if is_band:
+        need = _native.lib().apap_panorama_band_workspace_bytes(center.shape[0], center.shape[1], _ip(ih), _ip(iw), p_mr, p_mc, p_fw, p_fh, n, band)
+    else:
+        need = _native.lib().apap_panorama_workspace_bytes(p_mr, p_mc, p_fw, p_fh, n)
+    work = _scratch(work, need, dev)
     after = []
     if auto:
         gains = _native.PanoramaGains(torch.empty(n + 1, dtype=torch.float64, device=dev), torch.empty(n + 1, dtype=torch.int32, device=dev),
@@ -701,7 +756,7 @@ def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, 
             _native._h(ctx), center.data_ptr(), center.shape[0], center.shape[1], table[0], _ip(ih), _ip(iw), table[1], p_mr, p_mc,
             table[2], _ip(nw), table[3], _ip(nh), p_fw, p_fh, _ip(ox), _ip(oy), n, *tail, out.data_ptr(), *after, work.data_ptr(),
             work.numel(), status.data_ptr(), _stream(dev)))
-    return (out, (W, H, OX, OY), status, gains) if return_gains else (out, (W, H, OX, OY), status)
+    return (out, (W, H, OX, OY), status, host_gains or gains) if return_gains else (out, (W, H, OX, OY), status)
 
 
 def hip_panorama_gain_stats(center, layers, step=4, N=None, S=None, status=None, ctx=None, work=None, sampling=None):

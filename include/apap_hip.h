@@ -999,6 +999,53 @@ int apap_panorama_auto_gain_device(apap_ctx *ctx, const uint8_t *d_center, int c
                                    unsigned long long *d_N, unsigned long long *d_S, double *d_g, int *d_q, int *d_flag, void *d_work,
                                    size_t work_bytes, int *d_status, void *stream);
 
+/* ------------------------------------------------- panorama: the two-band blend ---------------------------------------- */
+/* Low spatial frequencies blended over the ramp's wide region, fine detail taken from ONE view, so that misregistration
+ * cannot double it (Brown & Lowe, IJCV 2007, section 7, with two bands; DESIGN.md "Panorama, two-band blend"; in numpy, exact
+ * integers: tests/panorama_band_spec.py).  Canvas, layer geometry, coordinates, the strict bounds test, truncation, presence
+ * and sampling are the panorama's, unchanged; view 0 is the centre, view k layer k - 1.
+ *   low-pass    of an h x w x 3 picture I with radius r = `band`, 0 .. APAP_PANORAMA_MAX_BAND, n = 2 r + 1:
+ *               T[y][x][c] = the sum of I[clamp(y + dy, 0, h - 1)][clamp(x + dx, 0, w - 1)][c] over |dx|, |dy| <= r (the border
+ *               is replicated), B = (T + (n^2 >> 1)) / n^2 rounded down; r = 0 gives B = I.  The blur lives in SOURCE space,
+ *               once per picture - not on the warped canvas: the blend stays in the one canvas pass and needs no canvas-sized
+ *               intermediate, the choice the ramp made for its weights.  apap_box_blur[_device] compute B alone.
+ *   per pixel   for every view v: c_v, the panorama's sample of I_v (the pixel (ix, iy), or the fixed-point blend of four
+ *               taps under APAP_SAMPLING_BILINEAR); b_v, the sample of B_v at the same place (the same pixel; the same taps
+ *               and weights); D_v = min(x + 1, w - x, y + 1, h - y), the uncapped border distance of the source pixel
+ *               (x, y) = (ix, iy), (X - OX, Y - OY) for the centre; w_v = min(D_v, ramp), the ramp blend's weight.
+ *               v is present iff any byte of c_v is non-zero (b_v may be 0 for a present view).  With gain_q,
+ *               c'_v = gain(c_v, q_v) and b'_v = gain(b_v, q_v), min(255, (c q + 2048) >> 12); without, c' = c and b' = b.
+ *               L = floor(sum w_v b'_v / sum w_v) per channel over the present views; s = the present view with the largest
+ *               D_v, the lowest index on ties; out = clip(L + c'_s - b'_s, 0, 255) per channel, (0, 0, 0) where no view is
+ *               present.  Where one view is present the output is its (gained) sample whatever `band` is; band = 0 is
+ *               apap_panorama_ramp byte for byte.
+ * apap_panorama_band[_device]: apap_panorama_ramp[_device]'s arguments with `band` and gain_q (n_layers + 1 HOST ints, or NULL
+ * for no gains) after `ramp`.  d_work: at least apap_panorama_band_workspace_bytes(...) bytes, 256-byte aligned:
+ * apap_panorama_workspace_bytes(...) and, for band > 0, a 256-byte aligned slot per view for its low-pass picture; 0 for
+ * invalid arguments.  Refused before any device is touched (APAP_ERR_INVALID_ARG): band outside 0 .. APAP_PANORAMA_MAX_BAND,
+ * then whatever apap_panorama_ramp refuses, then a q of gain_q outside 1024 .. 16383.  Without a GPU the host-buffer forms
+ * return APAP_ERR_NO_DEVICE; the device forms only enqueue on `stream`.  The band is not a mode of apap_panorama[_device] or of
+ * the gain entry points.
+ * apap_box_blur[_device]: out = B of the h x w x 3 picture (at least 1 pixel, below 2 GiB) for radius 0 .. 32; `out` must not
+ * overlap the picture. */
+#define APAP_PANORAMA_BAND 3
+#define APAP_PANORAMA_MAX_BAND 32
+int apap_box_blur(apap_ctx *ctx, const uint8_t *img, int h, int w, int radius, uint8_t *out, int device);
+int apap_box_blur_device(apap_ctx *ctx, const uint8_t *d_img, int h, int w, int radius, uint8_t *d_out, void *stream);
+size_t apap_panorama_band_workspace_bytes(int center_h, int center_w, const int *img_h, const int *img_w, const int *mesh_rows,
+                                          const int *mesh_cols, const int *final_w, const int *final_h, int n_layers, int band);
+int apap_panorama_band(apap_ctx *ctx, const uint8_t *center, int center_h, int center_w, const uint8_t *const *imgs, const int *img_h,
+                       const int *img_w, const float *const *Hfwd, const int *mesh_rows, const int *mesh_cols,
+                       const double *const *mesh_w, const int *n_w, const double *const *mesh_h, const int *n_h, const int *final_w,
+                       const int *final_h, const int *off_x, const int *off_y, int n_layers, int ramp, int band, const int *gain_q,
+                       uint8_t *out, int *status, int device);
+int apap_panorama_band_device(apap_ctx *ctx, const uint8_t *d_center, int center_h, int center_w, const uint8_t *const *d_imgs,
+                              const int *img_h, const int *img_w, const float *const *d_Hfwd, const int *mesh_rows,
+                              const int *mesh_cols, const double *const *d_mesh_w, const int *n_w, const double *const *d_mesh_h,
+                              const int *n_h, const int *final_w, const int *final_h, const int *off_x, const int *off_y, int n_layers,
+                              int ramp, int band, const int *gain_q, uint8_t *d_out, void *d_work, size_t work_bytes, int *d_status,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif
