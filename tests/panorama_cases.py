@@ -94,6 +94,15 @@ def strip_edges(width):
     return build(517, (300, 17), specs)
 
 
+def strip_case(width):
+    """``strip_edges`` at a canvas one column short of a wave's 256, exactly that wide and one column wider; 33 rows: one more
+    than two blocks of 16."""
+    specs = [(100, 33, placement(width - 100.0, 0.0), 2, 3), (70, 20, placement(width - 119.0, 6.0, 0.01), 4, 4)]
+    case = build(width, (200, 30), specs)
+    assert geometry.panorama_size(case["center"].shape, case["layers"])[0] == width
+    return case
+
+
 def single_c1():
     """K = 1 at C1's size: 768 x 768 pictures, a 20 x 20 mesh."""
     return build(768, (768, 768), [(768, 768, np.array([[1.02, 0.01, 12.3], [-0.015, 0.99, 8.4], [2.5e-5, -5e-5, 1.0]]), 20, 20)])

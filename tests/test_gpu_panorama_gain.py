@@ -27,10 +27,8 @@ _cases = {}
 
 
 def strip_case(width):
-    """``panorama_cases.strip_edges`` at a canvas one column short of a wave's 256, exactly that wide and one column wider; 33
-    rows: one more than two blocks of 16."""
-    specs = [(100, 33, E.placement(width - 100.0, 0.0), 2, 3), (70, 20, E.placement(width - 119.0, 6.0, 0.01), 4, 4)]
-    case = E.build(width, (200, 30), specs)
+    """``panorama_cases.strip_case``: canvases 255, 256 and 257 wide here."""
+    case = E.strip_case(width)
     assert S.panorama_size(case["center"].shape, case["geometries"])[0] == width
     return case
 
