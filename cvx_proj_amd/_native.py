@@ -100,7 +100,10 @@ SIGNATURES = {
     "apap_ctx_destroy": (None, [_vp]),
     "apap_ctx_set_option": (C.c_int, [_vp, C.c_int, C.c_int]),
     "apap_ctx_get_option": (C.c_int, [_vp, C.c_int, _i32p]),
+    "apap_ctx_set_short_chain": (C.c_int, [_vp, C.c_int]),
+    "apap_ctx_get_short_chain": (C.c_int, [_vp, _i32p]),
     "apap_ctx_profile_read": (C.c_int, [_vp, _f32p, _i32p]),
+    "apap_ctx_profile_k1_chunks": (C.c_int, [_vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "apap_host_prepare": (C.c_int, [_f32p, _f32p, C.c_int] + [_f32p] * 10),
     "apap_host_dlt_rows": (C.c_int, [_f32p, _f32p, C.c_int, _f32p]),
     "apap_host_prepare_pts": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int] + [_f32p] * 6 + [_f64p] * 4),
@@ -321,13 +324,25 @@ class Context:
               "plan_slots": OPT_PLAN_SLOTS, "warp_sampling": OPT_WARP_SAMPLING}
 
     def set(self, name, value):
-        check(lib().apap_ctx_set_option(self._h, self._NAMES[name], int(value)))
+        if name == "short_chain":       # a switch of the context beside the option table (apap_ctx_set_short_chain)
+            check(lib().apap_ctx_set_short_chain(self._h, int(value)))
+        else:
+            check(lib().apap_ctx_set_option(self._h, self._NAMES[name], int(value)))
         return self
 
     def get(self, name):
         v = C.c_int(0)
-        check(lib().apap_ctx_get_option(self._h, self._NAMES[name], C.byref(v)))
+        if name == "short_chain":
+            check(lib().apap_ctx_get_short_chain(self._h, C.byref(v)))
+        else:
+            check(lib().apap_ctx_get_option(self._h, self._NAMES[name], C.byref(v)))
         return v.value
+
+    def profile_k1_chunks(self):
+        """``(chunks K1 ran on the short weight chain, chunks K1 ran)`` in the profiled launches since the previous read."""
+        short, every = C.c_uint(0), C.c_uint(0)
+        check(lib().apap_ctx_profile_k1_chunks(self._h, C.byref(short), C.byref(every)))
+        return short.value, every.value
 
     def profile_read(self):
         """``{kernel slot name: (milliseconds, launches)}`` since the previous read."""

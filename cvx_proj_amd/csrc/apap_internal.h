@@ -28,6 +28,7 @@ enum { S_TABLE, S_VERT, S_DENORM, S_H, S_WORK, S_W, S_IMG, S_OUT, S_MESHW, S_MES
 // in the library is mutable after load.
 struct apap_ctx {
     int opt[APAP_OPT_COUNT] = {APAP_VARIANT_AUTO, APAP_EIGEN_AUTO, 1, 0, 4096, 1, 1 << 20, 4096, 1, 0, 0, 30, 0, 0, APAP_SAMPLING_NEAREST};
+    int short_chain = 1;    // apap_ctx_set_short_chain: K1's short weight chain where a chunk proves it (apap_exp_long.h)
     std::vector<apap::ProfSpan> spans;
     apap::DevSlot slots[apap::S_COUNT];
     std::mutex mu;   // serialises the host-buffer entry points that share this context's pool
@@ -41,6 +42,8 @@ struct apap_ctx {
     // resident blocks of k_assemble_mfma's three forms on device k1_slots_dev (0: not asked yet), for the paired launch
     int k1_slots[3] = {0, 0, 0};
     int k1_slots_dev = -1;
+    // two device words k_assemble_mfma counts its chunks in under APAP_OPT_PROFILE (apap_ctx_profile_k1_chunks); made on first use
+    void *k1_chunk_counts = nullptr;
 };
 
 namespace apap {

@@ -18,6 +18,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "apap_exp_long.h"
 #include "apap_internal.h"
 #include "apap_row_term.h"
 #include "apap_warp_dev.h"
@@ -188,15 +189,18 @@ __constant__ double kExp2Tab[kExpN] = {
     0x1.fd3c22b8f71f1p+0, 0x1.fdecbe15f6314p+0, 0x1.fe9d96b2a23d9p+0, 0x1.ff4eaca4391b6p+0};
 
 __device__ __forceinline__ double exp_neg_scaled(double yu, const double *tab /* LDS */) {
-    constexpr double L = 0x1.62e42fefa39efp-1 / kExpN;  // ln2 / 512
     const int nk = (int)(-yu);                          // truncates toward zero and saturates
     const double f = __builtin_amdgcn_fract(yu);
     const double t = tab[nk & (kExpN - 1)];
-    double p = fma(f, L * L * L * L / 24, -(L * L * L / 6));
-    p = fma(f, p, L * L / 2);
-    p = fma(f, p, -L);
-    p = fma(f, p, 1.0);
+    const double p = apap::exp_long_poly(f, 1.0);       // the degree-4 polynomial, one definition for both chains and the host check
     return __builtin_ldexp(t * p, nk >> kExpBits);
+}
+// The short chain of k_assemble_mfma (apap_exp_long.h): for 0 <= yu < ylim, where the scaling is in the table entry and the
+// clamp is idle - no mask, no shift, no ldexp, no max; `top` = the long table's last entry, the one of floor(yu) = 0.
+static_assert(apap::kExpTabN == kExpN, "the long table extends kExp2Tab");
+__device__ __forceinline__ double exp_neg_short(double yu, const double *top /* LDS */) {
+    const int nk = (int)(-yu);
+    return top[nk] * apap::exp_long_poly(__builtin_amdgcn_fract(yu), 0.5);
 }
 
 // w^2 for the MFMA variant; `scaled_inv_sigma2` = kExpScale * 2 / sigma^2.  The square root is
@@ -205,24 +209,29 @@ __device__ __forceinline__ double exp_neg_scaled(double yu, const double *tab /*
 // Two entries, one chain from x = fma(dx, dx, row term) on (cell_weight_sq_of): cell_weight_sq_tab forms the distance's row
 // term fma(dy, dy, 1e-300), dy = vy - sy, itself; cell_weight_sq_row takes it from its caller (k_assemble_mfma reads it from a
 // side table where a block shares it, apap_row_term.h).
+// kShort: the short chain from yu on (`tab` = its `top`); only where the caller has proved yu < ylim for the whole chunk.
+template <bool kShort = false>
 __device__ __forceinline__ double cell_weight_sq_of(double x, double scaled_inv_sigma2, double gamma2, const double *tab) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y;
     const double e = fma(-g, y, 1.0);
     const double c = fma(e, 0.375, 0.5);
     g = fma(g * e, c, g);
-    return fmax(exp_neg_scaled(g * scaled_inv_sigma2, tab), gamma2);
+    if constexpr (kShort) return exp_neg_short(g * scaled_inv_sigma2, tab);
+    else return fmax(exp_neg_scaled(g * scaled_inv_sigma2, tab), gamma2);
 }
+template <bool kShort = false>
 __device__ __forceinline__ double cell_weight_sq_tab(double vx, double vy, double sx, double sy,
                                                      double scaled_inv_sigma2, double gamma2, const double *tab) {
     const double dx = vx - sx;
     const double dy = vy - sy;
-    return cell_weight_sq_of(fma(dx, dx, fma(dy, dy, 1e-300)), scaled_inv_sigma2, gamma2, tab);
+    return cell_weight_sq_of<kShort>(fma(dx, dx, fma(dy, dy, 1e-300)), scaled_inv_sigma2, gamma2, tab);
 }
+template <bool kShort = false>
 __device__ __forceinline__ double cell_weight_sq_row(double vx, double sx, double row_term,
                                                      double scaled_inv_sigma2, double gamma2, const double *tab) {
     const double dx = vx - sx;
-    return cell_weight_sq_of(fma(dx, dx, row_term), scaled_inv_sigma2, gamma2, tab);
+    return cell_weight_sq_of<kShort>(fma(dx, dx, row_term), scaled_inv_sigma2, gamma2, tab);
 }
 
 // w^2 in float32 for the opt-in tolerance tier (APAP_OPT_WEIGHTS_F32 with APAP_OPT_MOMENTS = 24): v_sqrt_f32 and
@@ -316,6 +325,15 @@ struct ExpTableStage {
     __device__ __forceinline__ void publish(double *s_exp2, int tid) const {
 #pragma unroll
         for (int i = 0; i < kPerThread; ++i) s_exp2[(tid + i * kThreads) & (kExpN - 1)] = v[i];
+    }
+    // The long table of k_assemble_mfma (apap_exp_long.h; `s` = its kExpLong entries): kExp2Tab in its place, and the entries
+    // beyond it from the values the thread holds anyway - thread t's second one, kExp2Tab[256 + t], halved, is entry
+    // kExpLongZero - (256 - t); thread 0 writes the 2 of floor(yu) = 0.
+    __device__ __forceinline__ void publish_long(double *s, int tid) const {
+        static_assert(kThreads == 256 && kPerThread == 2, "one entry beyond kExp2Tab per thread");
+        publish(s + apap::kExpLongZero, tid);
+        if (tid == 0) s[apap::kExpLong - 1] = 2.0;
+        else if (256 - tid <= apap::kExpLongZero) s[apap::kExpLongZero - (256 - tid)] = 0.5 * v[1];
     }
 };
 
@@ -443,6 +461,15 @@ struct CellWeight {
     // (The float32 chain has no such entry: k1_mfma_tiles never shares the term there.)
     __device__ __forceinline__ double sq_row(double sx, double row_term) const {
         return cell_weight_sq_row(vx, sx, row_term, scaled_inv_sigma2, gamma2, exp2);
+    }
+    // The same two entries on the short chain (k_assemble_mfma with float64 weights, in a chunk that k1_mfma_tiles has proved;
+    // exp2 is then the long table's T part, apap_exp_long.h).
+    __device__ __forceinline__ double sq_short(Xy s) const {
+        static_assert(!kW32, "the float32 chain has no table");
+        return cell_weight_sq_tab<true>(vx, vy, s.x, s.y, scaled_inv_sigma2, gamma2, exp2 + apap::kExpTabN);
+    }
+    __device__ __forceinline__ double sq_row_short(double sx, double row_term) const {
+        return cell_weight_sq_row<true>(vx, sx, row_term, scaled_inv_sigma2, gamma2, exp2 + apap::kExpTabN);
     }
 };
 
@@ -686,11 +713,19 @@ __global__ __launch_bounds__(256) void k_assemble_valu(const double *__restrict_
 // group.  Any other block (arbitrary vertices, a mesh narrower than a tile, a pair of tiles on three rows) runs the loop as it
 // was, with the same instruction counts.  The float32-weight form never shares.  tests/test_gpu_k1_row_term.py solves every
 // problem in both ways and compares the workspaces byte for byte; profiles/k1_row_term.txt has the measurements.
+// The short chain (float64 weights; apap_exp_long.h): after yu the chain masks and shifts the table index, scales the product
+// by ldexp and clamps it at gamma^2 - four of its vector instructions that compute something known in advance wherever yu
+// stays below the table's reach and the clamp's onset.  Every pass of the chunk loop therefore exists in a second, short form
+// (exp_neg_short: one LDS entry that carries the scaling, times the polynomial) which a block runs for a chunk it has proved
+// (see "The short chain's proof" in the body); from the first chunk that fails, the block runs the passes as they were.  The
+// exp table in LDS is 768 entries for it, kExp2Tab in the middle, so the full passes read what they always read.  Same bits
+// either way: tests/test_gpu_k1_short_chain.py solves every problem with apap_ctx_set_short_chain at 1 and 0, compares the
+// workspaces byte for byte, tools/exp_long_check.cpp compares the two chains on the CPU; profiles/k1_short_chain.txt.
 template <int kWaves, bool kM24, bool kW32, int kGroups, bool kLevel>
 __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 256], double *s_exp2, double (&s_row)[2][kChunk][2],
                                               const double *__restrict__ table, const double *__restrict__ vertices, int cells,
-                                              int cells_pad, double gamma2, double inv_sigma2, double *__restrict__ slab, int tile,
-                                              const K1Block &blk) {
+                                              int cells_pad, double gamma2, double inv_sigma2, double ylim2, double *__restrict__ slab,
+                                              int tile, const K1Block &blk, unsigned int *__restrict__ chunk_counts) {
     constexpr int kThreads = kWaves * 64;
     const int tid = threadIdx.x;
     ExpTableStage<kThreads> exp_stage;      // register-staged (see there)
@@ -702,7 +737,8 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
     CellWeight<kW32> weight[kGroups];
 #pragma unroll
     for (int t = 0; t < kGroups; ++t)
-        weight[t].set(cell_vertex(vertices, (tile + t) * (16 * kWaves) + wave * 16 + col, cells), inv_sigma2, gamma2, s_exp2);
+        weight[t].set(cell_vertex(vertices, (tile + t) * (16 * kWaves) + wave * 16 + col, cells), inv_sigma2, gamma2,
+                      kW32 ? s_exp2 : s_exp2 + apap::kExpLongZero);     // (float64 weights: the long table, kExp2Tab inside it)
     const int p_begin = blk.p_begin, p_end = blk.p_end, nchunks = blk.nchunks;
 
     // Does the block share the row term?  A: the vy of its first cell; B: the first vy in cell order that is not A (through
@@ -746,6 +782,68 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
         for (int t = 0; t < kGroups; ++t)
             off_row[t] = apap::row_read_off(0, 0, kgrp, apap::row_value(__double_as_longlong(weight[t].vy), a_bits));
     }
+    // The short chain's proof (float64 weights; apap_exp_long.h): a chunk runs the short body when every one of its 64 rows -
+    // the zero rows past the split's end like any other - has a scaled distance below ylim to EVERY cell of the block:
+    //     (max(|x - x0|, |x - x1|)^2 + max(|y - y0|, |y - y1|)^2 + 1e-300) scaled_inv_sigma2^2 < ylim^2
+    // with [x0, x1] x [y0, y1] the bounding box of the block's cells (the clamped lanes of an overhang included), found once
+    // per block: every wave looks at all the block's cells, as for the vote above, and keeps the box in scalar registers.
+    // Every wave proves every chunk for itself, a pass ahead: with the loads that stage chunk c + 1 lane l asks for the (x, y)
+    // of that chunk's row l - 16 bytes through the same window, so a row past the split's end is the zero row that is staged -
+    // and takes the vote after the steps of chunk c, when the answer has long arrived.  All waves vote on the same 64 rows
+    // against the same box: the verdict is block-uniform with no word of LDS, no barrier and no latency of its own.  Written
+    // so that a NaN or an infinity fails: in a keypoint or the scale through the compare, in a vertex (which min and max would
+    // drop) through `short_lim` = 0.  ylim2 = 0 (apap_ctx_set_short_chain(ctx, 0), gamma >= 1) fails every chunk without a look.
+    constexpr bool kCanShort = !kW32;
+    double box_x0 = 0.0, box_x1 = 0.0, box_y0 = 0.0, box_y1 = 0.0, short_k2 = 0.0, short_lim = 0.0;
+    bool box_finite = true;
+    if constexpr (kCanShort) {      // the lane's own cells; the wave's minima and maxima follow in box_reduce
+        const int first = tile * (16 * kWaves);
+#pragma unroll
+        for (int t = 0; t < kGroups; ++t) {
+            const double2 v = cell_vertex(vertices, first + 64 * t + lane, cells);
+            box_finite = box_finite && __builtin_fabs(v.x) < __builtin_inf() && __builtin_fabs(v.y) < __builtin_inf();
+            box_x0 = t ? fmin(box_x0, v.x) : v.x, box_x1 = t ? fmax(box_x1, v.x) : v.x;
+            box_y0 = t ? fmin(box_y0, v.y) : v.y, box_y1 = t ? fmax(box_y1, v.y) : v.y;
+        }
+    }
+    // The wave's minima and maxima by data-parallel moves, no LDS round trip: a scan over each row of 16 lanes (the value of
+    // the lane 1, 2, 4, 8 to the left; a lane that has none keeps its own), then lane 15 of rows 0 and 2 into rows 1 and 3 and
+    // lane 31 into rows 2 and 3: lane 63 holds the wave's.  (Called once the first chunk's loads have been issued, and not
+    // at all where the short chain is switched off or gamma rules it out.)
+    auto box_reduce = [&]() {
+        auto from = [](double v, auto ctrl, auto rows) {
+            const long long b = __double_as_longlong(v);
+            const int lo = __builtin_amdgcn_update_dpp((int)b, (int)b, decltype(ctrl)::value, decltype(rows)::value, 0xf, false);
+            const int hi = __builtin_amdgcn_update_dpp((int)(b >> 32), (int)(b >> 32), decltype(ctrl)::value, decltype(rows)::value, 0xf, false);
+            return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+        };
+        auto stage = [&](auto ctrl, auto rows) {
+            box_x0 = fmin(box_x0, from(box_x0, ctrl, rows)), box_x1 = fmax(box_x1, from(box_x1, ctrl, rows));
+            box_y0 = fmin(box_y0, from(box_y0, ctrl, rows)), box_y1 = fmax(box_y1, from(box_y1, ctrl, rows));
+        };
+        using std::integral_constant;
+        stage(integral_constant<int, 0x111>{}, integral_constant<int, 0xf>{});      // row_shr:1
+        stage(integral_constant<int, 0x112>{}, integral_constant<int, 0xf>{});      // row_shr:2
+        stage(integral_constant<int, 0x114>{}, integral_constant<int, 0xf>{});      // row_shr:4
+        stage(integral_constant<int, 0x118>{}, integral_constant<int, 0xf>{});      // row_shr:8
+        stage(integral_constant<int, 0x142>{}, integral_constant<int, 0xa>{});      // row_bcast:15 into rows 1 and 3
+        stage(integral_constant<int, 0x143>{}, integral_constant<int, 0xc>{});      // row_bcast:31 into rows 2 and 3
+        auto last = [](double v) {
+            const long long b = __double_as_longlong(v);
+            return __longlong_as_double((long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(b >> 32), 63) << 32) |
+                                                    (unsigned)__builtin_amdgcn_readlane((int)b, 63)));
+        };
+        box_x0 = last(box_x0), box_x1 = last(box_x1), box_y0 = last(box_y0), box_y1 = last(box_y1);
+        short_k2 = last(weight[0].scaled_inv_sigma2 * weight[0].scaled_inv_sigma2);
+        short_lim = __all(box_finite) ? ylim2 : 0.0;
+    };
+    const int off_proof = lane * kTableRowBytes + 30 * 8;       // row `lane` of a chunk's window: its (x, y)
+    auto chunk_proved = [&](double2 s) {
+        const double ax = fmax(__builtin_fabs(s.x - box_x0), __builtin_fabs(s.x - box_x1));
+        const double ay = fmax(__builtin_fabs(s.y - box_y0), __builtin_fabs(s.y - box_y1));
+        const double d2 = fma(ax, ax, fma(ay, ay, 1e-300));
+        return __all(d2 * short_k2 < short_lim) != 0;
+    };
     // The staging's per-thread constants (ChunkWindow): the byte offset of the thread's first piece in a chunk of the table
     // and in its LDS image, and where a row term's owner finds its keypoint's y (column 31).
     static_assert(kThreads == 256, "four pieces a thread, 16 rows apart");
@@ -790,7 +888,16 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
     if constexpr (kCanShare) {
         if (row_owner && nchunks > 0) row_y0 = row_fetch(first_window);
     }
-    exp_stage.publish(s_exp2, tid);  // visible after the barrier
+    bool proved = false;        // the verdict on the next chunk to run (block-uniform)
+    if constexpr (kCanShort) {
+        if (ylim2 > 0.0 && nchunks > 0) {   // (block-uniform; otherwise no chunk is ever looked at)
+            const double2 xy0 = first_window.load16(off_proof);
+            box_reduce();
+            proved = chunk_proved(xy0);
+        }
+    }
+    if constexpr (kW32) exp_stage.publish(s_exp2, tid);  // visible after the barrier
+    else exp_stage.publish_long(s_exp2, tid);
     if (nchunks > 0) window_store(lds[0], stage);
     if constexpr (kCanShare) {
         if (row_owner && nchunks > 0) row_publish(0, row_y0);
@@ -811,13 +918,23 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
     // the one of a block that shares it - the keypoint's x and the lane's term from LDS, x = fma(dx, dx, term), and the terms
     // of chunk c + 1 written where chunk c + 1 is staged.
     const int nfull = (p_end - p_begin) / kChunk;
+    int short_chunks = 0;       // the chunks this block ran on the short chain (counted under APAP_OPT_PROFILE)
     auto chunks = [&](auto row_tag) {
         constexpr bool kRow = decltype(row_tag)::value;
         // w^2 of group t for the keypoint of step s: the weight chain's two entries
-        auto w2_row = [&](int t, double sx, const unsigned char *rbuf, int s) {
-            return weight[t].sq_row(sx, *reinterpret_cast<const double *>(rbuf + off_row[t] + apap::kRowStepBytes * s));
+        // (short_tag: std::true_type in a chunk that chunk_proved has passed - the short chain - and std::false_type for the
+        // chain as it has always been)
+        auto w2_row = [&](auto short_tag, int t, double sx, const unsigned char *rbuf, int s) {
+            const double term = *reinterpret_cast<const double *>(rbuf + off_row[t] + apap::kRowStepBytes * s);
+            if constexpr (decltype(short_tag)::value) return weight[t].sq_row_short(sx, term);
+            else return weight[t].sq_row(sx, term);
         };
-        for (int c = 0; c < nfull; ++c) {
+        auto w2_xy = [&](auto short_tag, int t, typename CellWeight<kW32>::Xy xy) {
+            if constexpr (decltype(short_tag)::value) return weight[t].sq_short(xy);
+            else return weight[t].sq(xy);
+        };
+        // one whole chunk, c: the next one's loads, 16 steps, the next one's stores, the barrier
+        auto whole = [&](int c, auto short_tag) {
             if constexpr (kLevel) {
                 if (4 * c < nfull) __builtin_amdgcn_s_setprio(3);           // the level is an immediate of the instruction
                 else if (4 * c < 2 * nfull) __builtin_amdgcn_s_setprio(2);
@@ -834,10 +951,12 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
             // waits (vmcnt 3, 2, 1, 0) stand in front of the four LDS stores at the end of the pass in all six chunk loops.
             ChunkStage<kThreads> next;
             double row_y = 0.0;
+            double2 next_xy = make_double2(0.0, 0.0);   // (short passes: row `lane` of the next chunk, for its proof)
             {
                 const int next_row = p_begin + (c + 1) * kChunk;
                 const ChunkWindow window(table, next_row, c + 1 < nchunks ? p_end : next_row);
                 window_load(next, window);
+                if constexpr (decltype(short_tag)::value) next_xy = window.load16(off_proof);
                 if constexpr (kRow) {
                     if (row_owner) row_y = row_fetch(window);
                 }
@@ -856,8 +975,8 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
                     double w2[8];
 #pragma unroll
                     for (int g = 0; g < 8; ++g) {
-                        if constexpr (kRow) w2[g] = w2_row(0, *reinterpret_cast<const double *>(buf + off_xy + 1024 * (s0 + g)), rbuf, s0 + g);
-                        else w2[g] = weight[0].sq(buf + off_xy + 1024 * (s0 + g));
+                        if constexpr (kRow) w2[g] = w2_row(short_tag, 0, *reinterpret_cast<const double *>(buf + off_xy + 1024 * (s0 + g)), rbuf, s0 + g);
+                        else w2[g] = w2_xy(short_tag, 0, CellWeight<kW32>::read(buf + off_xy + 1024 * (s0 + g)));
                     }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -875,11 +994,11 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
                         if constexpr (kRow) {       // the keypoint's x once for both groups, each group its own term
                             const double sx = *reinterpret_cast<const double *>(buf + off_xy + 1024 * (s0 + g));
 #pragma unroll
-                            for (int t = 0; t < kGroups; ++t) w2[g][t] = w2_row(t, sx, rbuf, s0 + g);
+                            for (int t = 0; t < kGroups; ++t) w2[g][t] = w2_row(short_tag, t, sx, rbuf, s0 + g);
                         } else {
                             const auto xy = CellWeight<kW32>::read(buf + off_xy + 1024 * (s0 + g));
 #pragma unroll
-                            for (int t = 0; t < kGroups; ++t) w2[g][t] = weight[t].sq(xy);
+                            for (int t = 0; t < kGroups; ++t) w2[g][t] = w2_xy(short_tag, t, xy);
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -892,31 +1011,53 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
             if constexpr (kRow) {
                 if (row_owner) row_publish((c + 1) & 1, row_y);
             }
+            bool next_proved = false;
+            if constexpr (decltype(short_tag)::value) next_proved = chunk_proved(next_xy);
             __syncthreads();
-        }
-        if (nfull < nchunks) {      // the partial last chunk (staged and published by the loop's last pass, or by the prologue)
+            return next_proved;
+        };
+        // the partial last chunk (staged and published by the last whole pass, or by the prologue)
+        auto partial = [&](auto short_tag) {
             const unsigned char *buf = lds[nfull & 1];
             const unsigned char *rbuf = reinterpret_cast<const unsigned char *>(s_row[nfull & 1]);
             const int steps_here = (p_end - p_begin - nfull * kChunk + 3) >> 2;
             for (int s1 = 0; s1 < steps_here; ++s1) {
                 if constexpr (kGroups == 1) {
                     double w2;
-                    if constexpr (kRow) w2 = w2_row(0, *reinterpret_cast<const double *>(buf + off_xy + 1024 * s1), rbuf, s1);
-                    else w2 = weight[0].sq(buf + off_xy + 1024 * s1);
+                    if constexpr (kRow) w2 = w2_row(short_tag, 0, *reinterpret_cast<const double *>(buf + off_xy + 1024 * s1), rbuf, s1);
+                    else w2 = w2_xy(short_tag, 0, CellWeight<kW32>::read(buf + off_xy + 1024 * s1));
                     sums[0].step(w2, buf + off_b0 + 1024 * s1, buf + off_b1 + 1024 * s1);
                 } else {
                     double w2[kGroups];
                     if constexpr (kRow) {
                         const double sx = *reinterpret_cast<const double *>(buf + off_xy + 1024 * s1);
 #pragma unroll
-                        for (int t = 0; t < kGroups; ++t) w2[t] = w2_row(t, sx, rbuf, s1);
+                        for (int t = 0; t < kGroups; ++t) w2[t] = w2_row(short_tag, t, sx, rbuf, s1);
                     } else {
                         const auto xy = CellWeight<kW32>::read(buf + off_xy + 1024 * s1);
 #pragma unroll
-                        for (int t = 0; t < kGroups; ++t) w2[t] = weight[t].sq(xy);
+                        for (int t = 0; t < kGroups; ++t) w2[t] = w2_xy(short_tag, t, xy);
                     }
                     step2(w2, buf + off_b0 + 1024 * s1, buf + off_b1 + 1024 * s1);
                 }
+            }
+        };
+        // Short passes while the chunks prove themselves, each pass proving the next; from the first chunk that does not, the
+        // passes as they have always been, with no further look: a launch that never qualifies pays for one vote per block.
+        // Either body gives the same bits, so where the switch happens changes no sum.
+        int c = 0;
+        if constexpr (kCanShort) {
+            for (; proved && c < nfull; ++c) proved = whole(c, std::true_type{});
+        }
+        short_chunks = c;       // (for the profile's count alone)
+        for (; c < nfull; ++c) whole(c, std::false_type{});
+        if (nfull < nchunks) {
+            if constexpr (kCanShort) {
+                if (proved) ++short_chunks;
+                if (proved) partial(std::true_type{});
+                else partial(std::false_type{});
+            } else {
+                partial(std::false_type{});
             }
             __syncthreads();    // the chunk buffers become the stages below: no wave may still be reading the partial chunk
         }
@@ -926,6 +1067,12 @@ __device__ __forceinline__ void k1_mfma_tiles(unsigned char (&lds)[2][kChunk * 2
         else chunks(std::false_type{});
     } else {
         chunks(std::false_type{});
+    }
+    // Under APAP_OPT_PROFILE the launch counts its chunks (apap_ctx_profile_k1_chunks): per block, how many ran the short
+    // passes and how many there were.  A null pointer otherwise: one scalar compare per block, outside every loop.
+    if (chunk_counts != nullptr && tid == 0) {
+        atomicAdd(chunk_counts, (unsigned int)short_chunks);
+        atomicAdd(chunk_counts + 1, (unsigned int)nchunks);
     }
 
     // The sums leave in whole lines (line_column, line_cell): each wave turns a group's D registers round in a stage of its
@@ -975,9 +1122,10 @@ __global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__r
                                                        const double *__restrict__ vertices, int cells,
                                                        int cells_pad, double gamma2, double inv_sigma2,
                                                        int pts_per_split, double *__restrict__ moments,
-                                                       BatchStride bs, K1Pairs pp) {
+                                                       BatchStride bs, K1Pairs pp, double ylim2, unsigned int *__restrict__ chunk_counts) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2][kChunk * 256];
-    __shared__ double s_exp2[kExpN];
+    // float64 weights: the long table (apap_exp_long.h), 6 KiB - 32768 + 6144 + 2048 = 40960 bytes, four blocks in a CU's 160 KiB
+    __shared__ double s_exp2[kW32 ? kExpN : apap::kExpLong];
     __shared__ __attribute__((aligned(16))) double s_row[2][kChunk][2];     // the shared row terms (apap_row_term.h)
     int tile = blockIdx.x, split = blockIdx.y;
     bool paired = false;
@@ -986,11 +1134,11 @@ __global__ __launch_bounds__(kWaves * 64) void k_assemble_mfma(const double *__r
     constexpr int kSums = kM24 ? 24 : kMoments;
     double *slab = moments + (long long)blockIdx.z * bs.moments + (size_t)split * kSums * cells_pad;
     if (paired)
-        k1_mfma_tiles<kWaves, kM24, kW32, 2, true>(lds, s_exp2, s_row, table, vertices, cells, cells_pad, gamma2, inv_sigma2, slab, tile, blk);
+        k1_mfma_tiles<kWaves, kM24, kW32, 2, true>(lds, s_exp2, s_row, table, vertices, cells, cells_pad, gamma2, inv_sigma2, ylim2, slab, tile, blk, chunk_counts);
     else if (pp.pairs > 0)
-        k1_mfma_tiles<kWaves, kM24, kW32, 1, true>(lds, s_exp2, s_row, table, vertices, cells, cells_pad, gamma2, inv_sigma2, slab, tile, blk);
+        k1_mfma_tiles<kWaves, kM24, kW32, 1, true>(lds, s_exp2, s_row, table, vertices, cells, cells_pad, gamma2, inv_sigma2, ylim2, slab, tile, blk, chunk_counts);
     else        // the plain grid: the loop as it has always been
-        k1_mfma_tiles<kWaves, kM24, kW32, 1, false>(lds, s_exp2, s_row, table, vertices, cells, cells_pad, gamma2, inv_sigma2, slab, tile, blk);
+        k1_mfma_tiles<kWaves, kM24, kW32, 1, false>(lds, s_exp2, s_row, table, vertices, cells, cells_pad, gamma2, inv_sigma2, ylim2, slab, tile, blk, chunk_counts);
 }
 
 // --------------------------------------------------------------------------------
@@ -2785,6 +2933,7 @@ void apap_ctx_destroy(apap_ctx *ctx) {
     for (void *st : ctx->streams)
         if (st) (void)hipStreamDestroy((hipStream_t)st);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+    if (ctx->k1_chunk_counts) (void)hipFree(ctx->k1_chunk_counts);
     delete ctx;
 }
 
@@ -2817,6 +2966,33 @@ int apap_ctx_set_option(apap_ctx *ctx, int option, int value) {
 int apap_ctx_get_option(const apap_ctx *ctx, int option, int *value) {
     if (!value || option < 0 || option >= APAP_OPT_COUNT) return apap::fail(APAP_ERR_INVALID_ARG, "apap_ctx_get_option: bad argument");
     *value = apap::opt(ctx, option);
+    return APAP_OK;
+}
+
+int apap_ctx_set_short_chain(apap_ctx *ctx, int value) {
+    if (!ctx) return apap::fail(APAP_ERR_INVALID_ARG, "apap_ctx_set_short_chain: null context (NULL means the defaults and cannot be changed)");
+    if (value != 0 && value != 1) return apap::fail(APAP_ERR_INVALID_ARG, "apap_ctx_set_short_chain: value %d is not 0 or 1", value);
+    ctx->short_chain = value;
+    return APAP_OK;
+}
+
+int apap_ctx_get_short_chain(const apap_ctx *ctx, int *value) {
+    if (!value) return apap::fail(APAP_ERR_INVALID_ARG, "apap_ctx_get_short_chain: null argument");
+    *value = ctx ? ctx->short_chain : 1;
+    return APAP_OK;
+}
+
+int apap_ctx_profile_k1_chunks(apap_ctx *ctx, unsigned int *short_chunks, unsigned int *chunks) {
+    if (!ctx || !short_chunks || !chunks) return apap::fail(APAP_ERR_INVALID_ARG, "apap_ctx_profile_k1_chunks: null argument");
+    *short_chunks = *chunks = 0;
+    if (!ctx->k1_chunk_counts) return APAP_OK;      // no profiled launch of the kernel yet
+    unsigned int both[2] = {0, 0};
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(both, ctx->k1_chunk_counts, sizeof(both), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemset(ctx->k1_chunk_counts, 0, sizeof(both));
+    if (e != hipSuccess) return hip_fail(e, "apap_ctx_profile_k1_chunks");
+    *short_chunks = both[0];
+    *chunks = both[1];
     return APAP_OK;
 }
 
@@ -2912,7 +3088,7 @@ static int solve_batch_impl(apap_ctx *ctx, const double *d_tables, int n, const 
             {{k_assemble_mfma4<1, 8, false>, k_assemble_mfma4<1, 6, false>, k_assemble_mfma4<1, 6, true>}, 1},
             {{k_assemble_mfma4<2, 8, false>, k_assemble_mfma4<2, 6, false>, k_assemble_mfma4<2, 6, true>}, 2},
         };
-        using K1Mfma = void (*)(const double *, int, const double *, int, int, double, double, int, double *, BatchStride, K1Pairs);
+        using K1Mfma = void (*)(const double *, int, const double *, int, int, double, double, int, double *, BatchStride, K1Pairs, double, unsigned int *);
         static const K1Mfma k1_mfma[3] = {k_assemble_mfma<4, false, false>, k_assemble_mfma<4, true, false>, k_assemble_mfma<4, true, true>};
         static_assert(APAP_VARIANT_MFMA == APAP_VARIANT_VALU + 1 && APAP_VARIANT_MFMA4 == APAP_VARIANT_VALU + 2 &&
                       APAP_VARIANT_MFMA4X2 == APAP_VARIANT_VALU + 3, "k1[] is indexed by the variant");
@@ -2949,8 +3125,20 @@ static int solve_batch_impl(apap_ctx *ctx, const double *d_tables, int n, const 
             const int pairs = apap::plan_pairs(p.cell_tiles, p.splits, batch, slots);
             const K1Pairs pp{pairs, p.splits, p.cell_tiles};
             const dim3 grid = pairs > 0 ? dim3(p.cell_tiles * p.splits - pairs, 1, 1) : dim3(p.cell_tiles, p.splits, batch);
+            // the short chain's limit, squared (apap_exp_long.h; 0: every chunk runs the full chain)
+            const double ylim = (ctx ? ctx->short_chain : 1) ? apap::exp_long_limit(gamma2) : 0.0;
+            // under APAP_OPT_PROFILE the launch also counts its chunks, in two device words the context keeps
+            unsigned int *chunk_counts = nullptr;
+            if (ctx && ctx->opt[APAP_OPT_PROFILE]) {
+                if (!ctx->k1_chunk_counts) {
+                    hipError_t e = hipMalloc(&ctx->k1_chunk_counts, 2 * sizeof(unsigned int));
+                    if (e == hipSuccess) e = hipMemset(ctx->k1_chunk_counts, 0, 2 * sizeof(unsigned int));
+                    if (e != hipSuccess) return hip_fail(e, "apap_solve_device (chunk counts)");
+                }
+                chunk_counts = (unsigned int *)ctx->k1_chunk_counts;
+            }
             hipLaunchKernelGGL(k1_mfma[form], grid, dim3(256), 0, s, d_tables, n, d_vertices, cells, p.cells_pad, gamma2, inv_sigma2,
-                               p.pts_per_split, moments, bs, pp);
+                               p.pts_per_split, moments, bs, pp, ylim * ylim, chunk_counts);
         } else {
             const auto &k = k1[p.variant > APAP_VARIANT_MFMA && p.variant <= APAP_VARIANT_MFMA4X2 ? p.variant - APAP_VARIANT_VALU : 0];
             const dim3 grid((p.cell_tiles + k.tiles - 1) / k.tiles, p.splits, batch);

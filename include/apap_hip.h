@@ -192,9 +192,21 @@ apap_ctx *apap_ctx_create(void);
 void apap_ctx_destroy(apap_ctx *ctx); /* frees the pooled device buffers and pending events; NULL is a no-op */
 int apap_ctx_set_option(apap_ctx *ctx, int option, int value);
 int apap_ctx_get_option(const apap_ctx *ctx, int option, int *value); /* ctx may be NULL: the defaults */
+/* K1's short weight chain, a switch of the context beside the option table (which stays as it is: APAP_OPT_COUNT options).
+ * 1 (default): K1's 16x16x4 kernel with float64 weights runs a 64-keypoint chunk on a shorter weight chain - the exp table's
+ * entry already scaled, no clamp at gamma^2 - where it has proved, from the chunk's keypoints and the bounding box of the
+ * block's cells, that the scaling is one the table holds and the clamp is idle.  0: every chunk runs the full chain.  The
+ * moment slabs and the grids are the same bits for both values: the switch exists for tests and for A/B measurements.
+ * set: ctx must not be NULL, value 0 or 1.  get: ctx may be NULL (the default). */
+int apap_ctx_set_short_chain(apap_ctx *ctx, int value);
+int apap_ctx_get_short_chain(const apap_ctx *ctx, int *value);
 /* Waits for the events recorded since the previous read and returns, per slot, the summed
  * milliseconds and the number of launches. */
 int apap_ctx_profile_read(apap_ctx *ctx, float *ms, int *launches);
+/* Under APAP_OPT_PROFILE K1's 16x16x4 kernel also counts, per block, the 64-keypoint chunks it ran and how many of them on
+ * the short weight chain (apap_ctx_set_short_chain).  Waits for the device, returns both sums since the previous read and
+ * clears them; zeros when no such launch was profiled.  (A paired block counts its chunks once, not once per tile.) */
+int apap_ctx_profile_k1_chunks(apap_ctx *ctx, unsigned int *short_chunks, unsigned int *chunks);
 
 /* ------------------------------------------------------------ host-only helpers --- */
 /* No GPU needed.  They restate, in C and in float32 exactly as numpy evaluates the
