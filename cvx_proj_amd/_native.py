@@ -259,6 +259,17 @@ SIGNATURES.update({
     "apap_panorama_band": (C.c_int, _PANO_GEOMETRY + [C.c_int, C.c_int, _i32p, _u8p, _i32p, C.c_int]),
     "apap_panorama_band_device": (C.c_int, _PANO_GEOMETRY_DEVICE + [C.c_int, C.c_int, _i32p, _vp, _vp, C.c_size_t, _vp, _vp]),
 })
+# the fundamental matrix: the argument lists of apap_find_homography_ransac / apap_ransac_device; the batch forms put the pair
+# table (host ints) and the number of pairs where those have n
+SIGNATURES.update({
+    "apap_find_fundamental_ransac": SIGNATURES["apap_find_homography_ransac"],
+    "apap_find_fundamental_ransac_batch": (C.c_int, [_vp, _f32p, _f32p, _i32p, C.c_int, C.c_double, C.c_int, C.c_ulonglong, _f64p,
+                                                     _u8p, _i32p, C.c_int]),
+    "apap_fundamental_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "apap_fundamental_device": SIGNATURES["apap_ransac_device"],
+    "apap_fundamental_batch_device": (C.c_int, [_vp, _vp, _vp, _i32p, C.c_int, C.c_double, C.c_int, C.c_ulonglong, _vp, _vp, _vp,
+                                                _vp, C.c_size_t, _vp]),
+})
 
 _lib = None
 _torch_at_load = False      # was torch in the process when the library was loaded?  (cvx_proj_amd.resident refuses otherwise)
@@ -726,6 +737,90 @@ def find_homography_ransac(src, dst, thresh=5.0, iterations=RANSAC_ITERATIONS, s
     if inliers.value < 4:
         return None, mask.reshape(-1, 1)
     return H.reshape(3, 3), mask.reshape(-1, 1)
+
+
+FUNDAMENTAL_MIN_POINTS = 8
+FUNDAMENTAL_MAX_PAIRS = 65535
+
+
+def fundamental_arguments(lengths, thresh, iterations, who):
+    """The checks of the fundamental-matrix entry points, made before the library (or a device) is touched: pairs of at least
+    8 matches, ``thresh`` >= 0 (not NaN), 1 <= ``iterations`` <= 2^24.  Returns the int32 offsets (len + 1)."""
+    lengths = [int(x) for x in lengths]
+    if not 1 <= len(lengths) <= FUNDAMENTAL_MAX_PAIRS:
+        raise ValueError(f"{who}: {len(lengths)} pairs (1 .. {FUNDAMENTAL_MAX_PAIRS})")
+    if any(x < FUNDAMENTAL_MIN_POINTS for x in lengths):
+        raise ValueError(f"{who}: a fundamental matrix needs {FUNDAMENTAL_MIN_POINTS} matches; got {lengths}")
+    if sum(lengths) > np.iinfo(np.int32).max:
+        raise ValueError(f"{who}: {sum(lengths)} matches in all exceed the int32 offsets")
+    if not float(thresh) >= 0.0:
+        raise ValueError(f"{who}: thresh = {thresh} (>= 0)")
+    if not 1 <= int(iterations) <= 1 << 24:
+        raise ValueError(f"{who}: iterations = {iterations} (1 .. 2^24)")
+    off = np.zeros(len(lengths) + 1, np.int32)
+    off[1:] = np.cumsum(lengths)
+    return off
+
+
+def fundamental_workspace_layout(n_pairs, iterations):
+    """Byte offsets of the parts of the resident forms' workspace (include/apap_hip.h): ``dict(offsets, boxes, hyps, winners,
+    counts, total)``."""
+    up = lambda b: (b + 255) // 256 * 256      # noqa: E731
+    sizes = (("offsets", (n_pairs + 1) * 4), ("boxes", n_pairs * 64), ("hyps", n_pairs * iterations * 72),
+             ("winners", n_pairs * 72), ("counts", n_pairs * iterations * 4))
+    out, at = {}, 0
+    for name, b in sizes:
+        out[name] = at
+        at += up(b)
+    out["total"] = at
+    return out
+
+
+def _match_points(src, dst, who):
+    s = np.ascontiguousarray(src, dtype=np.float32).reshape(-1, 2)
+    d = np.ascontiguousarray(dst, dtype=np.float32).reshape(-1, 2)
+    if s.shape != d.shape:
+        raise ValueError(f"{who}: src and dst must have the same number of points; got {s.shape} and {d.shape}")
+    return s, d
+
+
+def find_fundamental_ransac_batch(pairs, thresh=3.0, iterations=RANSAC_ITERATIONS, seed=RANSAC_SEED, device=-1, ctx=None):
+    """``apap_find_fundamental_ransac_batch``: ``pairs`` is a sequence of ``(src, dst)``, each (n, 2) with n >= 8; one call, one
+    set of kernel launches.  Returns a list of ``(F (3, 3) float64 or None, mask (n, 1) uint8)``, each what
+    ``find_fundamental_ransac`` gives for that pair alone."""
+    who = "find_fundamental_ransac_batch"
+    pts = [_match_points(s, d, who) for s, d in pairs]
+    off = fundamental_arguments([len(s) for s, _ in pts], thresh, iterations, who)
+    src = np.concatenate([s for s, _ in pts])
+    dst = np.concatenate([d for _, d in pts])
+    F = np.zeros((len(pts), 9), dtype=np.float64)
+    mask = np.zeros(len(src), dtype=np.uint8)
+    inliers = np.zeros(len(pts), dtype=np.int32)
+    check(lib().apap_find_fundamental_ransac_batch(_h(ctx), _ptr(src, C.c_float), _ptr(dst, C.c_float), _ip(off), len(pts),
+                                                   float(thresh), int(iterations), C.c_ulonglong(seed), _ptr(F, C.c_double),
+                                                   _ptr(mask, C.c_uint8), _ip(inliers), device))
+    out = []
+    for p in range(len(pts)):
+        m = mask[off[p]:off[p + 1]].reshape(-1, 1)
+        out.append((None if inliers[p] < FUNDAMENTAL_MIN_POINTS or not np.isfinite(F[p]).all() else F[p].reshape(3, 3), m))
+    return out
+
+
+def find_fundamental_ransac(src, dst, thresh=3.0, iterations=RANSAC_ITERATIONS, seed=RANSAC_SEED, device=-1, ctx=None):
+    """``cv.findFundamentalMat(src, dst, cv.FM_RANSAC, thresh)`` with this repository's estimator (include/apap_hip.h):
+    ``(F (3, 3) float64 or None, mask (n, 1) uint8)``; ``dst_h^T F src_h = 0``, ``|dst^T F src|`` at most the distance in
+    pixels of ``dst`` from the epipolar line of ``src``.  ``None`` (and a cleared mask) when fewer than 8 matches agree."""
+    s, d = _match_points(src, dst, "find_fundamental_ransac")
+    fundamental_arguments([len(s)], thresh, iterations, "find_fundamental_ransac")
+    F = np.zeros(9, dtype=np.float64)
+    mask = np.zeros(len(s), dtype=np.uint8)
+    inliers = C.c_int(0)
+    check(lib().apap_find_fundamental_ransac(_h(ctx), _ptr(s, C.c_float), _ptr(d, C.c_float), len(s), float(thresh), int(iterations),
+                                             C.c_ulonglong(seed), _ptr(F, C.c_double), _ptr(mask, C.c_uint8),
+                                             C.byref(inliers), device))
+    if inliers.value < FUNDAMENTAL_MIN_POINTS or not np.isfinite(F).all():
+        return None, mask.reshape(-1, 1)
+    return F.reshape(3, 3), mask.reshape(-1, 1)
 
 
 # ---------------------------------------------------------------- spectral weights (spectral_method.py:66-133)

@@ -818,6 +818,51 @@ int apap_find_homography_ransac(apap_ctx *ctx, const float *src, const float *ds
     return APAP_OK;
 }
 
+int apap_find_fundamental_ransac_batch(apap_ctx *ctx, const float *src, const float *dst, const int *pair_offset, int n_pairs,
+                                       double thresh, int iterations, unsigned long long seed, double *F_out, uint8_t *mask_out,
+                                       int *inliers_out, int device) {
+    const char *who = "apap_find_fundamental_ransac_batch";
+    if (!src || !dst || !F_out || !mask_out || !inliers_out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc = apap::fundamental_check(pair_offset, n_pairs, thresh, iterations, who);
+    if (rc) return rc;
+    std::vector<int> result((size_t)n_pairs * 2, 0);   // before the HostCall: a download writes it
+    const size_t first = (size_t)pair_offset[0], N = (size_t)pair_offset[n_pairs] - first;   // the device arrays start at the first pair
+    const std::vector<int> rel = relative_offsets(pair_offset, n_pairs);
+    {
+        HostCall call(ctx);
+        if ((rc = call.select(device))) return rc;
+        Layout io = call.layout(S_AUX);
+        const Part d_src = io.take(N * 2 * sizeof(float)), d_dst = io.take(N * 2 * sizeof(float));
+        const Part d_F = io.take((size_t)n_pairs * 9 * sizeof(double)), d_mask = io.take(N);
+        const Part d_result = io.take(result.size() * sizeof(int));
+        call.alloc(io);
+        const Part work = call.slot(S_WORK, apap_fundamental_workspace_bytes((int)N, n_pairs, iterations));
+        call.up(d_src, src + first * 2);
+        call.up(d_dst, dst + first * 2);
+        if ((rc = call.rc())) return rc;
+        rc = apap_fundamental_batch_device(ctx, d_src.as<const float>(), d_dst.as<const float>(), rel.data(), n_pairs, thresh, iterations,
+                                           seed, d_F.as<double>(), d_mask.as<uint8_t>(), d_result.as<int>(), work.as<void>(), work.bytes,
+                                           call.stream());
+        if (rc) return rc;
+        call.down(F_out, d_F);
+        call.down(mask_out + first, d_mask);
+        call.down(result.data(), d_result);
+        if ((rc = call.wait())) return rc;
+    }
+    for (int p = 0; p < n_pairs; ++p) {
+        inliers_out[p] = result[2 * (size_t)p + 1];
+        if (std::isnan(F_out[9 * (size_t)p]))   // no model: cv.findFundamentalMat returns None
+            memset(mask_out + pair_offset[p], 0, (size_t)(pair_offset[p + 1] - pair_offset[p]));
+    }
+    return APAP_OK;
+}
+
+int apap_find_fundamental_ransac(apap_ctx *ctx, const float *src, const float *dst, int n, double thresh, int iterations,
+                                 unsigned long long seed, double *F_out, uint8_t *mask_out, int *inliers_out, int device) {
+    const int off[2] = {0, n};
+    return apap_find_fundamental_ransac_batch(ctx, src, dst, off, 1, thresh, iterations, seed, F_out, mask_out, inliers_out, device);
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ spectral weights (spectral_method.py:66-133)

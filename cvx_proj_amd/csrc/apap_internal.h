@@ -214,6 +214,8 @@ int spectral_em_batch_check(const int *pair_offset, int n_pairs, const int *pair
 int local_model_check(int n, int cells, double gamma, double sigma, const double *params, const char *who);
 // The argument checks of the descriptor matcher's entry points (apap_match.hip) that need no device pointer.
 int match_check(const int *q_offset, const int *t_offset, int n_pairs, const char *who);
+// The argument checks of the fundamental-matrix entry points (apap_fundamental.hip) that need no device pointer.
+int fundamental_check(const int *pair_offset, int n_pairs, double thresh, int iterations, const char *who);
 // `bytes` rounded up to the 256-byte boundary on which every part of a workspace or pooled buffer starts.
 inline size_t up256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 

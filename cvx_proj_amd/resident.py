@@ -216,6 +216,47 @@ class WarpPlan:
         return out
 
 
+def fundamental_workspace_bytes(n_total, n_pairs=1, iterations=_native.RANSAC_ITERATIONS):
+    """Workspace of ``hip_fundamental`` / ``hip_fundamental_batch`` for ``n_pairs`` pairs of ``n_total`` matches in all
+    (``_native.fundamental_workspace_layout`` names its parts); 0 for invalid arguments."""
+    return _native.lib().apap_fundamental_workspace_bytes(int(n_total), int(n_pairs), int(iterations))
+
+
+def hip_fundamental_batch(src, dst, pair_lengths, thresh=3.0, iterations=_native.RANSAC_ITERATIONS, seed=_native.RANSAC_SEED,
+                          ctx=None, work=None):
+    """``apap_fundamental_batch_device`` on the current stream of the tensors' device, no host synchronisation: the fundamental
+    matrices of many pairs in five kernel launches.  src / dst (N, 2) float32, the pairs concatenated, pair p of
+    ``pair_lengths[p]`` >= 8 matches (a host list).  Returns (F (P, 3, 3) float64 - all NaN where a pair has no model -, mask
+    (N,) uint8: the winning hypothesis's inliers, result (P, 2) int32: {winning hypothesis, its inlier count}) as device
+    tensors.  ``F[p]`` is what ``hip_spectral`` / ``hip_spectral_em`` take as their ``F``, and ``F`` what
+    ``hip_spectral_em_batch`` takes.  ``work`` (uint8) is used when it holds ``fundamental_workspace_bytes(N, P, iterations)``;
+    afterwards it holds every hypothesis and count.  Same bytes as ``_native.find_fundamental_ransac_batch``."""
+    who = "hip_fundamental_batch"
+    _needs_device(src, who)
+    dev = src.device
+    off = _native.fundamental_arguments(pair_lengths, thresh, iterations, who)
+    N, P = int(off[-1]), len(off) - 1
+    _contiguous(((src, torch.float32), (dst, torch.float32)), dev, who)
+    if src.shape != (N, 2) or dst.shape != src.shape:
+        raise ValueError(f"{who}: shapes ({N}, 2), ({N}, 2) expected; got {tuple(src.shape)} and {tuple(dst.shape)}")
+    F = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
+    mask = torch.empty(N, dtype=torch.uint8, device=dev)
+    result = torch.empty((P, 2), dtype=torch.int32, device=dev)
+    work = _scratch(work, fundamental_workspace_bytes(N, P, iterations), dev)
+    _native.check(_native.lib().apap_fundamental_batch_device(
+        _native._h(ctx), src.data_ptr(), dst.data_ptr(), _ip(off), P, float(thresh), int(iterations), ctypes.c_ulonglong(seed),
+        F.data_ptr(), mask.data_ptr(), result.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
+    return F, mask, result
+
+
+def hip_fundamental(src, dst, thresh=3.0, iterations=_native.RANSAC_ITERATIONS, seed=_native.RANSAC_SEED, ctx=None, work=None):
+    """``apap_fundamental_device``: one pair, the batch of one (see ``hip_fundamental_batch``).  Returns (F (3, 3) float64, mask
+    (n,) uint8, result (2,) int32) as device tensors, not synchronised."""
+    _needs_device(src, "hip_fundamental")
+    F, mask, result = hip_fundamental_batch(src, dst, [src.shape[0]], thresh, iterations, seed, ctx=ctx, work=work)
+    return F[0], mask, result[0]
+
+
 def spectral_workspace_bytes(n):
     """Scratch of ``hip_spectral`` for ``n`` matches: O(n), no n x n buffer."""
     return _native.lib().apap_spectral_workspace_bytes(n)

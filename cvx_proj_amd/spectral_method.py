@@ -14,6 +14,8 @@ runs), the part that needs neither OpenCV nor cvxpy: ``calculate_M`` (:66-133) a
   synchronisation (``apap_spectral_em``): calculate_M with Hg = the previous round's H_pred, then model_solve.
 * ``warp_results``: the two ``image_warping`` calls of the ``-s`` option (:227-229) as one batched kernel launch.
 * ``skew_symmetric_transform``, ``fundamental``, ``get_fundamental``: utils.py:162-186, host numpy.
+* ``estimate_fundamental``, ``estimate_fundamental_batch``, ``match_fundamental``: F from the matches themselves (GPU RANSAC,
+  ``apap_find_fundamental_ransac``), for pairs that have no calibration spreadsheet.
 
 Keypoints and matches are duck-typed: anything with ``.pt`` and ``.queryIdx`` / ``.trainIdx`` (OpenCV's KeyPoint / DMatch
 or simple stand-ins).  ``opts`` is any object with ``epi_weight``, ``affinity_eps``, ``aff_thresh``, ``em_radius`` and
@@ -31,7 +33,7 @@ from . import _native
 
 __all__ = ["calculate_M", "spectral_weights", "SpectralResult", "recompute_matching", "match_RANSAC", "cv_to_array",
            "normalized_feature", "model_solve", "spectral_em", "spectral_em_batch", "spectral_em_grid", "EMRound", "EMResult", "warp_results", "skew_symmetric_transform", "fundamental",
-           "get_fundamental"]
+           "get_fundamental", "estimate_fundamental", "estimate_fundamental_batch", "match_fundamental"]
 
 
 class SpectralResult(NamedTuple):
@@ -379,6 +381,32 @@ def fundamental(Rc, Ro, tc, to, K):
     ss_t = skew_symmetric_transform(tr)
     K_inv = np.linalg.inv(K)
     return K_inv.T @ ss_t @ Rr @ K_inv
+
+
+def estimate_fundamental(src_pts, dst_pts, thresh=3.0, iterations=_native.RANSAC_ITERATIONS, seed=_native.RANSAC_SEED, device=-1,
+                         ctx=None):
+    """F from the matches alone, for a pair without calibration: ``cv.findFundamentalMat(src_pts, dst_pts, cv.FM_RANSAC,
+    thresh)`` with this repository's GPU estimator (include/apap_hip.h; 8-point RANSAC on the Sampson distance, re-fitted to
+    its inliers, rank 2).  ``src_pts`` (the centre picture's) and ``dst_pts`` (n, 2), n >= 8, as ``cv_to_array`` returns them.
+    Returns ``(F (3, 3) float64 or None, mask (n,) float32)`` with ``dst_h^T F src_h = 0`` - the F that calculate_M,
+    spectral_weights and spectral_em take - scaled so that ``|dst^T F src|`` is at most the distance in pixels of ``dst`` from
+    the epipolar line of ``src``.  ``None`` when fewer than 8 matches agree."""
+    F, mask = _native.find_fundamental_ransac(src_pts, dst_pts, thresh, iterations, seed, device=device, ctx=ctx)
+    return F, mask.astype(np.float32).ravel()
+
+
+def estimate_fundamental_batch(pairs, thresh=3.0, iterations=_native.RANSAC_ITERATIONS, seed=_native.RANSAC_SEED, device=-1,
+                               ctx=None):
+    """``estimate_fundamental`` for a sequence of ``(src_pts, dst_pts)`` in one call (the number of kernel launches does not grow
+    with the number of pairs): a list of ``(F or None, mask float32)``, each equal to the pair's own call."""
+    got = _native.find_fundamental_ransac_batch(pairs, thresh, iterations, seed, device=device, ctx=ctx)
+    return [(F, mask.astype(np.float32).ravel()) for F, mask in got]
+
+
+def match_fundamental(kpts_cp, kpts_op, matches, thresh=3.0, device=-1, ctx=None):
+    """The counterpart of ``match_RANSAC`` for the epipolar geometry: ``(F, mask float32)`` of the matched keypoints."""
+    src_pts, dst_pts = cv_to_array(kpts_cp, kpts_op, matches)
+    return estimate_fundamental(src_pts, dst_pts, thresh, device=device, ctx=ctx)
 
 
 def get_fundamental(case_idx, center_idx, img_idx, root="../diff_1/raw_data"):

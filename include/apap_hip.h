@@ -480,6 +480,47 @@ int apap_ransac_device(apap_ctx *ctx, const float *d_src, const float *d_dst, in
                        unsigned long long seed, double *d_H_best, uint8_t *d_mask, int *d_result, void *d_work,
                        size_t work_bytes, void *stream);
 
+/* Fundamental matrix from matches, the contract of
+ *     F, mask = cv.findFundamentalMat(src_pts, dst_pts, cv.FM_RANSAC, thresh)
+ * src (the centre picture's points), dst (the other picture's): n x 2 float32, n >= 8; dst_h^T F src_h = 0, the convention
+ * of calculate_M's epipolar score (F @ homo_src, dotted with homo_dst).  `iterations` 8-point hypotheses drawn by the
+ * counter-based sampler of the seed homography (`seed`; 8 draws a hypothesis) on coordinates normalised by each picture's
+ * bounding box, each reduced by Gaussian elimination with complete pivoting (no rank constraint); a match is an inlier when
+ * its squared Sampson distance is <= thresh^2 (pixels); the first hypothesis with the most inliers wins.  F is re-fitted on
+ * the device to the winner's inliers (A^T A in one fixed summation order, cyclic Jacobi, rank 2 by a Jacobi SVD), scaled so
+ * that max_k |(F src_k)[:2]| = 1 over all n matches - |dst^T F src| is then at most the distance in pixels of dst from the
+ * epipolar line of src - and signed so that its first entry of largest magnitude is positive.
+ * F_out: 9 doubles, row-major; mask_out: n bytes 0/1; *inliers_out: the winner's count.  Fewer than 8 inliers, or a
+ * degenerate scale, is "no model" (cv returns None): F_out is nine NaN and the host-buffer call clears mask_out.
+ * thresh >= 0 (inf allowed), 1 <= iterations <= 2^24.  This is this repository's estimator, not OpenCV's (sampler, adaptive
+ * stopping and polish differ): tests/fundamental_spec.py is its specification, bit for bit.
+ * The batch forms take pair_offset[0 .. n_pairs] (HOST ints, as apap_match_descriptors_batch): pair p holds rows
+ * pair_offset[p] .. pair_offset[p + 1] - 1 of src / dst / mask, 1 <= n_pairs <= 65535; F_out 9 doubles and inliers_out one
+ * int per pair.  A pair's results are those of its own call; the number of kernel launches does not depend on n_pairs. */
+int apap_find_fundamental_ransac(apap_ctx *ctx, const float *src, const float *dst, int n, double thresh, int iterations,
+                                 unsigned long long seed, double *F_out, uint8_t *mask_out, int *inliers_out, int device);
+int apap_find_fundamental_ransac_batch(apap_ctx *ctx, const float *src, const float *dst, const int *pair_offset, int n_pairs,
+                                       double thresh, int iterations, unsigned long long seed, double *F_out, uint8_t *mask_out,
+                                       int *inliers_out, int device);
+/* Workspace of the resident forms for n_pairs pairs of n_total matches in all (0 for invalid arguments).  Its parts, each
+ * rounded up to a multiple of 256 bytes, in this order (every one is written in full by a call, none needs a set-up):
+ *     offsets   (n_pairs + 1) ints            the pair table
+ *     boxes     n_pairs x 8 doubles           centre x, centre y, scale, extent of src's bounding box, then of dst's
+ *     hyps      n_pairs x iterations x 9 doubles   every hypothesis, de-normalised (nine NaN: a zero or non-finite pivot)
+ *     winners   n_pairs x 9 doubles           the winning hypothesis
+ *     counts    n_pairs x iterations ints     every hypothesis's inliers */
+size_t apap_fundamental_workspace_bytes(int n_total, int n_pairs, int iterations);
+/* Resident forms: device pointers but pair_offset; d_F 9 doubles a pair (nine NaN: no model), d_mask the winner's inliers
+ * (rows as src; not cleared when there is no model), d_result 2 ints a pair = {winning hypothesis, its inlier count}.
+ * d_work 256-byte aligned, points and d_F 8-byte aligned.  Five launches on `stream`, timed under APAP_PROF_RANSAC; no
+ * wait.  d_F feeds apap_spectral_device / apap_spectral_em_device / apap_spectral_em_batch_device as their d_F. */
+int apap_fundamental_device(apap_ctx *ctx, const float *d_src, const float *d_dst, int n, double thresh, int iterations,
+                            unsigned long long seed, double *d_F, uint8_t *d_mask, int *d_result, void *d_work, size_t work_bytes,
+                            void *stream);
+int apap_fundamental_batch_device(apap_ctx *ctx, const float *d_src, const float *d_dst, const int *pair_offset, int n_pairs,
+                                  double thresh, int iterations, unsigned long long seed, double *d_F, uint8_t *d_mask,
+                                  int *d_result, void *d_work, size_t work_bytes, void *stream);
+
 /* ------------------------------------------------- spectral match weighting --- */
 /* calculate_M of spectral_method.py:66-133, the step every shell driver of the reference runs:
  *     M_ii = match_score_i + epi_weight / (1 + |dst_i^T F src_i|)                              (:104-114)
