@@ -37,8 +37,6 @@ namespace {
 
 using apap::grey_at, apap::reflect, apap::up256;
 
-inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
-
 constexpr int kTW = APAP_CORNER_TILE_W, kTH = APAP_CORNER_TILE_H;
 constexpr int kThreads = 256;
 constexpr int kMaxRadius = APAP_CORNER_MAX_RADIUS;
@@ -399,9 +397,9 @@ int apap_corner_detect_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs,
     hipStream_t s = (hipStream_t)stream;
     // from pageable memory in stream order: the copy returns once its source has been consumed
     hipError_t e = hipMemcpyAsync(d_work, tab.data(), (size_t)n_images * sizeof(CornerImage), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return hip_fail(e, "apap_corner_detect_batch_device: descriptor upload");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_corner_detect_batch_device: descriptor upload");
     e = hipMemsetAsync(w + L.counters, 0, (size_t)n_images * sizeof(CornerCount), s);
-    if (e != hipSuccess) return hip_fail(e, "apap_corner_detect_batch_device: counters");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_corner_detect_batch_device: counters");
     const CornerImage *d_tab = (const CornerImage *)d_work;
     CornerCount *d_cnt = (CornerCount *)(w + L.counters);
     if (radius <= kSmallRadius)
@@ -409,11 +407,11 @@ int apap_corner_detect_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs,
     else
         hipLaunchKernelGGL(k_corner_tile<kMaxRadius>, dim3(tiles, (unsigned)n_images), dim3(kThreads), 0, s, d_tab, d_cnt, radius);
     e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_corner_detect_batch_device: tile launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_corner_detect_batch_device: tile launch");
     hipLaunchKernelGGL(k_corner_select, dim3((unsigned)n_images), dim3(kSelThreads), 0, s, d_tab, (const CornerCount *)d_cnt, max_corners,
                        quality_permille, d_pts, d_response, d_count);
     e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_corner_detect_batch_device: select launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_corner_detect_batch_device: select launch");
     return APAP_OK;
 }
 

@@ -24,8 +24,6 @@
 
 namespace {
 
-inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
-
 constexpr int kMaxProblems = 65535;   // grid.y
 constexpr int kClasses = 4;           // rows-per-block classes of the matvec: 4, 8, 16, 32
 
@@ -252,7 +250,7 @@ int spectral_em_batch_run(apap_ctx *ctx, const float *d_src, const float *d_dst,
     // both tables go up from pageable memory in stream order: the copies return once their source has been consumed
     hipError_t e = hipMemcpyAsync(d_tab, tab.data(), (size_t)B * sizeof(EmProb), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_lists, lists.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return hip_fail(e, "apap_spectral_em_batch_device: descriptor upload");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_spectral_em_batch_device: descriptor upload");
     std::vector<SpecState> states(sync_each ? (size_t)B : 0);
     for (int k = 0; k < em_steps; ++k) {
         {
@@ -273,7 +271,7 @@ int spectral_em_batch_run(apap_ctx *ctx, const float *d_src, const float *d_dst,
                 if (sync_each) {
                     e = hipMemcpyAsync(states.data(), d_states, (size_t)B * sizeof(SpecState), hipMemcpyDeviceToHost, s);
                     if (e == hipSuccess) e = hipStreamSynchronize(s);
-                    if (e != hipSuccess) return hip_fail(e, "apap_spectral_em_batch_device: cycle");
+                    if (e != hipSuccess) return apap::hip_fail(e, "apap_spectral_em_batch_device: cycle");
                     bool all = true;
                     for (int b = 0; b < B; ++b) all = all && states[b].done;
                     if (all) break;
@@ -285,7 +283,7 @@ int spectral_em_batch_run(apap_ctx *ctx, const float *d_src, const float *d_dst,
         hipLaunchKernelGGL(k_model_solve_b, dim3(B), dim3(kW), 0, s, d_tab, k);
     }
     e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_spectral_em_batch_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_spectral_em_batch_device launch");
     return APAP_OK;
 }
 

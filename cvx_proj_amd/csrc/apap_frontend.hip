@@ -9,10 +9,9 @@
 #include <cstdint>
 
 #include "apap_internal.h"
+#include "apap_ransac_dev.h"
 
 namespace {
-
-inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
 
 // --------------------------------------------------------------------------------
 // Histogram equalisation of an interleaved uint8 image, all channels in one pass.
@@ -303,7 +302,7 @@ int launch_equalize(apap_ctx *ctx, const uint8_t *d_img, size_t bytes, int total
                            d_out);
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_equalize_hist_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_equalize_hist_device launch");
     return APAP_OK;
 }
 
@@ -317,15 +316,11 @@ int launch_equalize(apap_ctx *ctx, const uint8_t *d_img, size_t bytes, int total
 // R2 k_ransac_score: one block per hypothesis counts the points within the threshold.
 // R3 k_ransac_select: first hypothesis with the most inliers, its matrix and its mask.
 // A few thousand tiny solves and a few million point tests: launch-latency-bound, no roofline.
+// The sampler, the consensus count and the selection are apap_ransac_dev.h's, shared with the
+// fundamental matrix (apap_fundamental.hip); the system, its elimination and the predicate are here.
 // --------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    unsigned long long z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 constexpr int kHypLanes = 64;
+using apap::kConsensusThreads;  // the block of R2 and R3
 
 __global__ __launch_bounds__(kHypLanes) void k_ransac_hyp(const float *__restrict__ src, const float *__restrict__ dst,
                                                           int n, int iterations, unsigned long long seed,
@@ -335,23 +330,8 @@ __global__ __launch_bounds__(kHypLanes) void k_ransac_hyp(const float *__restric
     const int h = blockIdx.x * kHypLanes + t;
     if (h >= iterations) return;  // lane-private work below: no barriers
 #define A(r, c) sys[(r) * 9 + (c)][t]
-    // four distinct indices: draw j is taken modulo n - j, then stepped over the earlier picks
-    // in ascending order
-    int pick[4];
-    for (int j = 0; j < 4; ++j) {
-        const unsigned int r = (unsigned int)(splitmix64(seed + 4ull * (unsigned long long)h + (unsigned long long)j) >> 32);
-        int p = (int)(r % (unsigned int)(n - j));
-        int prev[3];
-        for (int k = 0; k < j; ++k) prev[k] = pick[k];
-        for (int a = 1; a < j; ++a) {  // insertion sort of at most three earlier picks
-            const int v = prev[a];
-            int b = a - 1;
-            while (b >= 0 && prev[b] > v) { prev[b + 1] = prev[b]; --b; }
-            prev[b + 1] = v;
-        }
-        for (int k = 0; k < j; ++k) p += (p >= prev[k]) ? 1 : 0;
-        pick[j] = p;
-    }
+    int pick[4];  // four distinct indices
+    apap::draw_distinct<4>(seed, h, n, pick);
     for (int j = 0; j < 4; ++j) {
         const double x = (double)src[2 * pick[j]], y = (double)src[2 * pick[j] + 1];
         const double u = (double)dst[2 * pick[j]], v = (double)dst[2 * pick[j] + 1];
@@ -410,63 +390,22 @@ __device__ __forceinline__ bool ransac_inlier(const double (&h)[9], double x, do
     return dx * dx + dy * dy <= thr2;  // NaN compares false
 }
 
-__global__ __launch_bounds__(256) void k_ransac_score(const float *__restrict__ src, const float *__restrict__ dst, int n,
-                                                      const double *__restrict__ H, double thr2,
-                                                      int *__restrict__ counts) {
-    __shared__ int s_part[4];
-    double h[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) h[i] = H[(size_t)blockIdx.x * 9 + i];
-    int c = 0;
-    for (int k = threadIdx.x; k < n; k += 256) {
-        const float2 s = reinterpret_cast<const float2 *>(src)[k];
-        const float2 d = reinterpret_cast<const float2 *>(dst)[k];
-        c += ransac_inlier(h, (double)s.x, (double)s.y, (double)d.x, (double)d.y, thr2) ? 1 : 0;
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+__global__ __launch_bounds__(kConsensusThreads) void k_ransac_score(const float *__restrict__ src,
+                                                                    const float *__restrict__ dst, int n,
+                                                                    const double *__restrict__ H, double thr2,
+                                                                    int *__restrict__ counts) {
+    apap::consensus_score(src, dst, apap::MatchRange{0, n}, H + (size_t)blockIdx.x * 9, thr2, ransac_inlier,
+                          counts + blockIdx.x);
 }
 
-__global__ __launch_bounds__(256) void k_ransac_select(const float *__restrict__ src, const float *__restrict__ dst, int n,
-                                                       const double *__restrict__ H, const int *__restrict__ counts,
-                                                       int iterations, double thr2, double *__restrict__ H_best,
-                                                       uint8_t *__restrict__ mask, int *__restrict__ result) {
-    __shared__ int s_cnt[256], s_idx[256];
-    int bc = -1, bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < iterations; i += 256) {  // ascending: strictly greater keeps the first
-        const int c = counts[i];
-        if (c > bc) { bc = c; bi = i; }
-    }
-    s_cnt[threadIdx.x] = bc;
-    s_idx[threadIdx.x] = bi;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if (threadIdx.x < d) {
-            const int oc = s_cnt[threadIdx.x + d], oi = s_idx[threadIdx.x + d];
-            if (oc > s_cnt[threadIdx.x] || (oc == s_cnt[threadIdx.x] && oi < s_idx[threadIdx.x])) {
-                s_cnt[threadIdx.x] = oc;
-                s_idx[threadIdx.x] = oi;
-            }
-        }
-        __syncthreads();
-    }
-    const int best = s_idx[0];
-    double h[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) h[i] = H[(size_t)best * 9 + i];
-    if (threadIdx.x < 9) H_best[threadIdx.x] = h[threadIdx.x];
-    if (threadIdx.x == 0) {
-        result[0] = best;
-        result[1] = s_cnt[0];
-    }
-    for (int k = threadIdx.x; k < n; k += 256) {
-        const float2 s = reinterpret_cast<const float2 *>(src)[k];
-        const float2 d = reinterpret_cast<const float2 *>(dst)[k];
-        mask[k] = ransac_inlier(h, (double)s.x, (double)s.y, (double)d.x, (double)d.y, thr2) ? 1 : 0;
-    }
+__global__ __launch_bounds__(kConsensusThreads) void k_ransac_select(const float *__restrict__ src,
+                                                                     const float *__restrict__ dst, int n,
+                                                                     const double *__restrict__ H,
+                                                                     const int *__restrict__ counts, int iterations,
+                                                                     double thr2, double *__restrict__ H_best,
+                                                                     uint8_t *__restrict__ mask, int *__restrict__ result) {
+    apap::consensus_select(src, dst, apap::MatchRange{0, n}, H, counts, iterations, thr2, ransac_inlier, H_best, mask,
+                           result);
 }
 
 }  // namespace
@@ -499,13 +438,13 @@ int apap_ransac_device(apap_ctx *ctx, const float *d_src, const float *d_dst, in
         apap::ProfScope prof(ctx, APAP_PROF_RANSAC, s);
         hipLaunchKernelGGL(k_ransac_hyp, dim3((iterations + kHypLanes - 1) / kHypLanes), dim3(kHypLanes), 0, s, d_src,
                            d_dst, n, iterations, seed, H);
-        hipLaunchKernelGGL(k_ransac_score, dim3(iterations), dim3(256), 0, s, d_src, d_dst, n, (const double *)H, thr2,
-                           counts);
-        hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(256), 0, s, d_src, d_dst, n, (const double *)H,
+        hipLaunchKernelGGL(k_ransac_score, dim3(iterations), dim3(kConsensusThreads), 0, s, d_src, d_dst, n,
+                           (const double *)H, thr2, counts);
+        hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(kConsensusThreads), 0, s, d_src, d_dst, n, (const double *)H,
                            (const int *)counts, iterations, thr2, d_H_best, d_mask, d_result);
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_ransac_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_ransac_device launch");
     return APAP_OK;
 }
 

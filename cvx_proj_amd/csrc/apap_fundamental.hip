@@ -1,7 +1,9 @@
 // Fundamental matrix from matches by RANSAC, the contract of cv.findFundamentalMat(src, dst, cv.FM_RANSAC, thresh)
 // (specification: tests/fundamental_spec.py, bit for bit; DESIGN.md "Fundamental matrix from matches").  The sibling of the
 // seed homography's R1-R3 (apap_frontend.hip), for a batch of pairs: blockIdx.y is the pair in every kernel, the pairs'
-// offsets come from a table in the workspace, and the number of launches does not depend on the number of pairs.
+// offsets come from a table in the workspace, and the number of launches does not depend on the number of pairs.  The
+// sampler of F2 and the bodies of F3 and F4 are apap_ransac_dev.h's, shared with R1-R3; the system, its elimination and the
+// predicate are here.
 // F1 k_fund_box:    the bounding boxes of a pair's two point sets -> centre and scale of the normalisation.
 // F2 k_fund_hyp:    one lane per hypothesis - the counter-based sampler (8 draws), the 8 x 9 system reduced by Gaussian
 //    elimination with complete pivoting on a lane-private system kept in LDS (dynamic row and column indices; index-major
@@ -19,24 +21,15 @@
 #include <vector>
 
 #include "apap_internal.h"
+#include "apap_ransac_dev.h"
 
 namespace {
-
-inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
 
 constexpr int kMinPoints = 8;
 constexpr int kMaxPairs = 65535;      // gridDim.y
 constexpr int kHypLanes = 64;
-constexpr int kThreads = 256;
+constexpr int kThreads = apap::kConsensusThreads;      // every block but the hypotheses'
 constexpr int kSweepCap = 30;
-
-// restated from apap_frontend.hip (that source stays as it is)
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    unsigned long long z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // The parts of the workspace (include/apap_hip.h documents them): byte offsets, each a multiple of 256.
 struct FundLayout {
@@ -146,32 +139,17 @@ __global__ __launch_bounds__(kHypLanes) void k_fund_hyp(const float *__restrict_
     const int pair = blockIdx.y, k0 = offset[pair], n = offset[pair + 1] - k0;
     const Norm ns = load_norm(boxes + (size_t)pair * 8), nd = load_norm(boxes + (size_t)pair * 8 + 4);
 #define A(r, c) sys[(r) * 9 + (c)][t]
-    // eight distinct indices: draw j is taken modulo n - j, then stepped over the earlier picks in ascending order;
-    // `sorted` holds the earlier picks in ascending order (compare-exchange insertion: every index is a constant)
-    int sorted[8];
+    int pick[8];      // eight distinct matches of the pair
+    apap::draw_distinct<8>(seed, h, n, pick);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const unsigned int r = (unsigned int)(splitmix64(seed + 8ull * (unsigned long long)h + (unsigned long long)j) >> 32);
-        int p = (int)(r % (unsigned int)(n - j));
-#pragma unroll
-        for (int k = 0; k < j; ++k) p += (p >= sorted[k]) ? 1 : 0;
-        {
-            const float2 s = reinterpret_cast<const float2 *>(src)[k0 + p];
-            const float2 d = reinterpret_cast<const float2 *>(dst)[k0 + p];
-            const double x = ((double)s.x - ns.cx) * ns.s, y = ((double)s.y - ns.cy) * ns.s;
-            const double u = ((double)d.x - nd.cx) * nd.s, v = ((double)d.y - nd.cy) * nd.s;
-            A(j, 0) = u * x; A(j, 1) = u * y; A(j, 2) = u;
-            A(j, 3) = v * x; A(j, 4) = v * y; A(j, 5) = v;
-            A(j, 6) = x; A(j, 7) = y; A(j, 8) = 1.0;
-        }
-        int v = p;
-#pragma unroll
-        for (int k = 0; k < j; ++k) {
-            const int lo = min(sorted[k], v), hi = max(sorted[k], v);
-            sorted[k] = lo;
-            v = hi;
-        }
-        sorted[j] = v;
+        const float2 s = reinterpret_cast<const float2 *>(src)[k0 + pick[j]];
+        const float2 d = reinterpret_cast<const float2 *>(dst)[k0 + pick[j]];
+        const double x = ((double)s.x - ns.cx) * ns.s, y = ((double)s.y - ns.cy) * ns.s;
+        const double u = ((double)d.x - nd.cx) * nd.s, v = ((double)d.y - nd.cy) * nd.s;
+        A(j, 0) = u * x; A(j, 1) = u * y; A(j, 2) = u;
+        A(j, 3) = v * x; A(j, 4) = v * y; A(j, 5) = v;
+        A(j, 6) = x; A(j, 7) = y; A(j, 8) = 1.0;
     }
     for (int c = 0; c < 9; ++c) perm[c][t] = c;
     bool ok = true;
@@ -257,23 +235,9 @@ __device__ __forceinline__ bool fund_inlier(const double (&f)[9], double x, doub
 __global__ __launch_bounds__(kThreads) void k_fund_score(const float *__restrict__ src, const float *__restrict__ dst,
                                                          const int *__restrict__ offset, const double *__restrict__ hyps,
                                                          int iterations, double thr2, int *__restrict__ counts) {
-    __shared__ int s_part[kThreads / 64];
     const int pair = blockIdx.y, k0 = offset[pair], n = offset[pair + 1] - k0;
     const size_t slot = (size_t)pair * iterations + blockIdx.x;
-    double f[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) f[i] = hyps[slot * 9 + i];
-    const float2 *s2 = reinterpret_cast<const float2 *>(src) + k0, *d2 = reinterpret_cast<const float2 *>(dst) + k0;
-    int c = 0;
-    for (int k = threadIdx.x; k < n; k += kThreads) {
-        const float2 s = s2[k], d = d2[k];
-        c += fund_inlier(f, (double)s.x, (double)s.y, (double)d.x, (double)d.y, thr2) ? 1 : 0;
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[slot] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    apap::consensus_score(src, dst, apap::MatchRange{k0, n}, hyps + slot * 9, thr2, fund_inlier, counts + slot);
 }
 
 // ---------------------------------------------------------------- F4
@@ -282,41 +246,9 @@ __global__ __launch_bounds__(kThreads) void k_fund_select(const float *__restric
                                                           const int *__restrict__ counts, int iterations, double thr2,
                                                           double *__restrict__ winners, uint8_t *__restrict__ mask,
                                                           int *__restrict__ result) {
-    __shared__ int s_cnt[kThreads], s_idx[kThreads];
     const int pair = blockIdx.y, k0 = offset[pair], n = offset[pair + 1] - k0;
-    const int *cnt = counts + (size_t)pair * iterations;
-    int bc = -1, bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < iterations; i += kThreads) {      // ascending: strictly greater keeps the first
-        const int c = cnt[i];
-        if (c > bc) { bc = c; bi = i; }
-    }
-    s_cnt[threadIdx.x] = bc;
-    s_idx[threadIdx.x] = bi;
-    __syncthreads();
-    for (int d = kThreads / 2; d > 0; d >>= 1) {
-        if (threadIdx.x < d) {
-            const int oc = s_cnt[threadIdx.x + d], oi = s_idx[threadIdx.x + d];
-            if (oc > s_cnt[threadIdx.x] || (oc == s_cnt[threadIdx.x] && oi < s_idx[threadIdx.x])) {
-                s_cnt[threadIdx.x] = oc;
-                s_idx[threadIdx.x] = oi;
-            }
-        }
-        __syncthreads();
-    }
-    const int best = s_idx[0];
-    double f[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) f[i] = hyps[((size_t)pair * iterations + best) * 9 + i];
-    if (threadIdx.x < 9) winners[(size_t)pair * 9 + threadIdx.x] = f[threadIdx.x];
-    if (threadIdx.x == 0) {
-        result[2 * pair] = best;
-        result[2 * pair + 1] = s_cnt[0];
-    }
-    const float2 *s2 = reinterpret_cast<const float2 *>(src) + k0, *d2 = reinterpret_cast<const float2 *>(dst) + k0;
-    for (int k = threadIdx.x; k < n; k += kThreads) {
-        const float2 s = s2[k], d = d2[k];
-        mask[(size_t)k0 + k] = fund_inlier(f, (double)s.x, (double)s.y, (double)d.x, (double)d.y, thr2) ? 1 : 0;
-    }
+    apap::consensus_select(src, dst, apap::MatchRange{k0, n}, hyps + (size_t)pair * iterations * 9, counts + (size_t)pair * iterations,
+                           iterations, thr2, fund_inlier, winners + (size_t)pair * 9, mask, result + 2 * pair);
 }
 
 // ---------------------------------------------------------------- F5
@@ -615,7 +547,7 @@ int apap_fundamental_batch_device(apap_ctx *ctx, const float *d_src, const float
     int *d_counts = (int *)(w + L.counts);
     // from pageable memory in stream order: the copy returns once its source has been consumed
     hipError_t e = hipMemcpyAsync(d_offset, pair_offset, ((size_t)n_pairs + 1) * sizeof(int), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return hip_fail(e, "apap_fundamental_batch_device: offset upload");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_fundamental_batch_device: offset upload");
     const double thr2 = thresh * thresh;
     {
         apap::ProfScope prof(ctx, APAP_PROF_RANSAC, s);
@@ -631,7 +563,7 @@ int apap_fundamental_batch_device(apap_ctx *ctx, const float *d_src, const float
                            (const double *)d_boxes, (const uint8_t *)d_mask, (const int *)d_result, d_F);
     }
     e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_fundamental_batch_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_fundamental_batch_device launch");
     return APAP_OK;
 }
 

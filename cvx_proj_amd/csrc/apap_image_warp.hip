@@ -33,8 +33,6 @@
 
 namespace {
 
-inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
-
 constexpr int kMaxSide = APAP_IMAGE_WARP_MAX_SIDE;
 constexpr int kMaxProblems = APAP_IMAGE_WARP_MAX_PROBLEMS;
 constexpr int kThreads = 256;
@@ -313,10 +311,10 @@ int apap_image_warp_batch_device(apap_ctx *ctx, const uint8_t *const *d_bases, c
     hipStream_t s = (hipStream_t)stream;
     // from pageable memory in stream order: the copy returns once its source has been consumed
     hipError_t e = hipMemcpyAsync(d_work, tab.data(), (size_t)n_problems * sizeof(WarpProblem), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return hip_fail(e, "apap_image_warp_batch_device: descriptor upload");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_image_warp_batch_device: descriptor upload");
     hipLaunchKernelGGL(k_image_warp, dim3(blocks), dim3(kThreads), 0, s, (const WarpProblem *)d_work, n_problems);
     e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_image_warp_batch_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_image_warp_batch_device launch");
     return APAP_OK;
 }
 

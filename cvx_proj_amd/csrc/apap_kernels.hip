@@ -2841,7 +2841,6 @@ __global__ __launch_bounds__(256) void k_blend(const uint8_t *__restrict__ a, co
     }
 }
 
-inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
 using apap::ProfScope;
 
 }  // namespace
@@ -2990,7 +2989,7 @@ int apap_ctx_profile_k1_chunks(apap_ctx *ctx, unsigned int *short_chunks, unsign
     hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(both, ctx->k1_chunk_counts, sizeof(both), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemset(ctx->k1_chunk_counts, 0, sizeof(both));
-    if (e != hipSuccess) return hip_fail(e, "apap_ctx_profile_k1_chunks");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_ctx_profile_k1_chunks");
     *short_chunks = both[0];
     *chunks = both[1];
     return APAP_OK;
@@ -3007,7 +3006,7 @@ int apap_ctx_profile_read(apap_ctx *ctx, float *ms, int *launches) {
         float t = 0.0f;
         hipError_t e = hipEventSynchronize((hipEvent_t)sp.b);
         if (e == hipSuccess) e = hipEventElapsedTime(&t, (hipEvent_t)sp.a, (hipEvent_t)sp.b);
-        if (e != hipSuccess) rc = hip_fail(e, "apap_ctx_profile_read");
+        if (e != hipSuccess) rc = apap::hip_fail(e, "apap_ctx_profile_read");
         ms[sp.slot] += t;
         launches[sp.slot] += 1;
         (void)hipEventDestroy((hipEvent_t)sp.a);
@@ -3071,7 +3070,7 @@ static int solve_batch_impl(apap_ctx *ctx, const double *d_tables, int n, const 
             hipLaunchKernelGGL(k_solve_small<true>, grid, dim3(kSmallThreads), 0, s, d_tables, n, d_vertices, cells, gamma, inv_sigma,
                                d_denorms, pick_rank, careful, d_H, bs, we);
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "apap_solve_device launch");
+        if (e != hipSuccess) return apap::hip_fail(e, "apap_solve_device launch");
         return APAP_OK;
     }
     {
@@ -3106,12 +3105,12 @@ static int solve_batch_impl(apap_ctx *ctx, const double *d_tables, int n, const 
             if (slots == 0 && batch == 1) {
                 int dev = 0;
                 hipError_t e = hipGetDevice(&dev);
-                if (e != hipSuccess) return hip_fail(e, "apap_solve_device (hipGetDevice)");
+                if (e != hipSuccess) return apap::hip_fail(e, "apap_solve_device (hipGetDevice)");
                 if (!ctx || ctx->k1_slots_dev != dev || ctx->k1_slots[form] == 0) {
                     int per_cu = 0, cus = 0;
                     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(k1_mfma[form]), 256, 0);
                     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                    if (e != hipSuccess) return hip_fail(e, "apap_solve_device (resident blocks of K1)");
+                    if (e != hipSuccess) return apap::hip_fail(e, "apap_solve_device (resident blocks of K1)");
                     slots = per_cu * cus;
                     if (ctx) {
                         if (ctx->k1_slots_dev != dev) ctx->k1_slots[0] = ctx->k1_slots[1] = ctx->k1_slots[2] = 0;
@@ -3133,7 +3132,7 @@ static int solve_batch_impl(apap_ctx *ctx, const double *d_tables, int n, const 
                 if (!ctx->k1_chunk_counts) {
                     hipError_t e = hipMalloc(&ctx->k1_chunk_counts, 2 * sizeof(unsigned int));
                     if (e == hipSuccess) e = hipMemset(ctx->k1_chunk_counts, 0, 2 * sizeof(unsigned int));
-                    if (e != hipSuccess) return hip_fail(e, "apap_solve_device (chunk counts)");
+                    if (e != hipSuccess) return apap::hip_fail(e, "apap_solve_device (chunk counts)");
                 }
                 chunk_counts = (unsigned int *)ctx->k1_chunk_counts;
             }
@@ -3158,7 +3157,7 @@ static int solve_batch_impl(apap_ctx *ctx, const double *d_tables, int n, const 
                            d_tables, n, d_vertices, gamma, inv_sigma, careful, trace_floor, we);
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_solve_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_solve_device launch");
     return APAP_OK;
 }
 
@@ -3215,7 +3214,7 @@ int apap_weights_device(apap_ctx *ctx, const double *d_table, int n, const doubl
     hipLaunchKernelGGL(k_weights, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_table, n, d_vertices, cells,
                        gamma, 1.0 / (sigma * sigma), d_W);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_weights_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_weights_device launch");
     return APAP_OK;
 }
 
@@ -3425,7 +3424,7 @@ int warp_impl(apap_ctx *ctx, const WarpArgs &a) {
                                a.status);
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_warp_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_warp_device launch");
     return APAP_OK;
 }
 
@@ -3557,7 +3556,7 @@ int apap_warp_coords_device(apap_ctx *ctx, const float *d_Hfwd, int mesh_rows, i
     hipLaunchKernelGGL(k_warp_coords, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, hinv_pad, mesh_cols,
                        lut, final_w, final_h, off_x, off_y, d_coords);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_warp_coords_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_warp_coords_device launch");
     return APAP_OK;
 }
 
@@ -3567,7 +3566,7 @@ int apap_flatten_device(apap_ctx *ctx, const float *d_H, int cells, double *d_ou
     hipLaunchKernelGGL(k_flatten, dim3((cells + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_H, cells, d_out,
                        d_status);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_flatten_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_flatten_device launch");
     return APAP_OK;
 }
 
@@ -3577,7 +3576,7 @@ int apap_blend_device(apap_ctx *ctx, const uint8_t *d_a, const uint8_t *d_b, int
     const int blocks = (int)((pixels + 255) / 256 < 16384 ? (pixels + 255) / 256 : 16384);
     hipLaunchKernelGGL(k_blend, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_a, d_b, pixels, d_out);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_blend_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_blend_device launch");
     return APAP_OK;
 }
 

@@ -27,8 +27,6 @@
 
 namespace {
 
-inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
-
 constexpr int kLocalChunk = APAP_LOCAL_MODEL_CHUNK;   // cells whose scratch apap_local_model_workspace_bytes asks for
 constexpr int kMaxGridY = 65535;
 constexpr size_t kInfoUnit = 256;                     // a cell's info block when the caller wants none
@@ -150,7 +148,7 @@ int apap_local_model_solve_device(apap_ctx *ctx, const float *d_pts_c, const flo
         }
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_local_model_solve_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_local_model_solve_device launch");
     return APAP_OK;
 }
 

@@ -34,8 +34,6 @@
 
 namespace {
 
-inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
-
 constexpr int kDim = APAP_MATCH_DIM;
 constexpr int kMatchQ = APAP_MATCH_QUERY_TILE;    // queries per block
 constexpr int kMatchT = APAP_MATCH_TRAIN_CHUNK;   // train rows per chunk
@@ -308,12 +306,12 @@ int apap_match_descriptors_batch_device(apap_ctx *ctx, const float *d_q, const f
     MatchPart *d_parts = (MatchPart *)((char *)d_work + table_bytes(n_pairs));
     // from pageable memory in stream order: the copy returns once its source has been consumed
     hipError_t e = hipMemcpyAsync(d_tab, tab.data(), (size_t)n_pairs * sizeof(MatchPair), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return hip_fail(e, "apap_match_descriptors_batch_device: descriptor upload");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_match_descriptors_batch_device: descriptor upload");
     hipLaunchKernelGGL(k_match_sweep, dim3(max_blocks, n_pairs), dim3(kThreads), 0, s, d_q, d_t, d_tab, d_parts);
     hipLaunchKernelGGL(k_match_merge, dim3((max_nq + kThreads - 1) / kThreads, n_pairs), dim3(kThreads), 0, s, d_tab, d_parts, d_idx,
                        d_dist, d_idx2, d_dist2);
     e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_match_descriptors_batch_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_match_descriptors_batch_device launch");
     return APAP_OK;
 }
 

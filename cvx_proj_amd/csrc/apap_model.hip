@@ -23,8 +23,6 @@
 
 namespace {
 
-inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
-
 // The kernels of one problem: the bodies of apap_model_dev.h on this launch's blocks.
 __global__ __launch_bounds__(kW) void k_model_tsqr(const float2 *__restrict__ pc, const float2 *__restrict__ po,
                                                    const float *__restrict__ w, int n, int per_block, ModelScalars sc,
@@ -81,7 +79,7 @@ int apap_model_solve_device(apap_ctx *ctx, const float *d_pts_c, const float *d_
     hipStream_t s = (hipStream_t)stream;
     model_launch(L, sc, d_pts_c, d_pts_o, d_weights, d_H, d_info, d_status, d_work, s);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_model_solve_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_model_solve_device launch");
     return APAP_OK;
 }
 
@@ -133,7 +131,7 @@ int spectral_em_run(apap_ctx *ctx, const float *d_src, const float *d_dst, const
         model_launch(L, sc, d_src, d_dst, rm, d_H + 9 * k, d_info + (size_t)k * APAP_MODEL_INFO, d_status, d_model_work, s);
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_spectral_em_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_spectral_em_device launch");
     return APAP_OK;
 }
 

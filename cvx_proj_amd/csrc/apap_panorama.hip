@@ -57,8 +57,6 @@
 
 namespace {
 
-inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
-
 constexpr int kMaxLayers = APAP_PANORAMA_MAX_LAYERS;
 constexpr int kRows = 4;            // canvas rows of a strip (one wave)
 constexpr int kBandRows = 2;        // ... of the two-band blend, which holds two gathers' pixels at a time
@@ -930,7 +928,7 @@ static int blur_launch(apap_ctx *ctx, const BlurView *views, int n, int r, void 
         hipLaunchKernelGGL(k_box_blur, dim3((unsigned)blocks), dim3(kBlurThreads), blur_lds_bytes(r), s, B);
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_box_blur launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "k_box_blur launch");
     return APAP_OK;
 }
 
@@ -1051,7 +1049,7 @@ static int panorama_launch(apap_ctx *ctx, PanoArgs &A, int mode, const int *ramp
 #undef APAP_LAUNCH_PANORAMA
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_panorama launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "k_panorama launch");
     return APAP_OK;
 }
 
@@ -1061,7 +1059,7 @@ static int stats_launch(apap_ctx *ctx, const PanoArgs &A, int step, unsigned lon
     const size_t bytes = (size_t)(A.n_layers + 1) * (A.n_layers + 1) * sizeof(unsigned long long);
     hipError_t e = hipMemsetAsync(d_N, 0, bytes, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_S, 0, bytes, s);
-    if (e != hipSuccess) return hip_fail(e, "panorama statistics: zero fill");
+    if (e != hipSuccess) return apap::hip_fail(e, "panorama statistics: zero fill");
     StatsArgs P;
     std::memset(&P, 0, sizeof(P));
     P.A = A;
@@ -1082,7 +1080,7 @@ static int stats_launch(apap_ctx *ctx, const PanoArgs &A, int step, unsigned lon
             hipLaunchKernelGGL((k_panorama_stats<APAP_SAMPLING_NEAREST>), grid, dim3(kStatWaves * 64), 0, s, P);
     }
     e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_panorama_stats launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "k_panorama_stats launch");
     return APAP_OK;
 }
 
@@ -1126,7 +1124,7 @@ int panorama_run(apap_ctx *ctx, const PanoGeometry &G, const PanoJob &J, void *d
         hipLaunchKernelGGL(k_panorama_gain_solve, dim3(1), dim3(64), 0, (hipStream_t)stream, J.d_N, J.d_S, G.n_layers + 1, J.sigma_n,
                            J.sigma_g, J.d_g, J.d_q, J.d_flag);
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "k_panorama_gain_solve launch");
+        if (e != hipSuccess) return apap::hip_fail(e, "k_panorama_gain_solve launch");
     }
     return panorama_launch(ctx, A, J.mode, J.ramp, J.what == kPanoGain ? J.gain_q : nullptr, J.what == kPanoAuto ? J.d_q : nullptr, J.d_out,
                            stream, J.band != nullptr);
@@ -1282,7 +1280,7 @@ int apap_box_blur_device(apap_ctx *ctx, const uint8_t *d_img, int h, int w, int 
     if (d_img < d_out + bytes && d_out < d_img + bytes) return apap::fail(APAP_ERR_INVALID_ARG, "%s: the output overlaps the picture", who);
     if (radius == 0) {
         const hipError_t e = hipMemcpyAsync(d_out, d_img, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        return e == hipSuccess ? APAP_OK : hip_fail(e, "apap_box_blur_device: copy");
+        return e == hipSuccess ? APAP_OK : apap::hip_fail(e, "apap_box_blur_device: copy");
     }
     const BlurView v{d_img, d_out, h, w, 0u, 0u};
     return apap::blur_launch(ctx, &v, 1, radius, stream);

@@ -35,8 +35,6 @@ namespace {
 
 using apap::grey_at, apap::reflect;
 
-inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
-
 constexpr int kDim = APAP_SIFT_DIM;
 constexpr int kSamples = APAP_SIFT_SAMPLES;
 constexpr int kTaps = APAP_SIFT_TAPS;
@@ -328,11 +326,11 @@ int apap_sift_describe_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs,
     hipStream_t s = (hipStream_t)stream;
     // from pageable memory in stream order: the copy returns once its source has been consumed
     hipError_t e = hipMemcpyAsync(d_work, tab.data(), (size_t)n_images * sizeof(SiftImage), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return hip_fail(e, "apap_sift_describe_batch_device: descriptor upload");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_sift_describe_batch_device: descriptor upload");
     hipLaunchKernelGGL(k_sift_describe, dim3(blocks), dim3(kThreads), 0, s, (const SiftImage *)d_work, n_images, d_pts, d_out, k_begin,
                        k_end, K);
     e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_sift_describe_batch_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_sift_describe_batch_device launch");
     return APAP_OK;
 }
 

@@ -30,8 +30,6 @@
 
 namespace {
 
-inline int hip_fail(hipError_t e, const char *what) { return apap::hip_fail((int)e, what); }
-
 // The kernels of one problem: the bodies of apap_spectral_dev.h on this launch's blocks.
 __global__ __launch_bounds__(kSpecThreads) void k_spec_setup(const float *__restrict__ src, const float *__restrict__ dst,
                                                              const float *__restrict__ cf, const float *__restrict__ of, int n,
@@ -138,7 +136,7 @@ int spectral_run(apap_ctx *ctx, const float *d_src, const float *d_dst, const fl
                 int done = 0;
                 hipError_t e = hipMemcpyAsync(&done, &P.st->done, sizeof(int), hipMemcpyDeviceToHost, s);
                 if (e == hipSuccess) e = hipStreamSynchronize(s);
-                if (e != hipSuccess) return hip_fail(e, "apap_spectral_device: cycle");
+                if (e != hipSuccess) return apap::hip_fail(e, "apap_spectral_device: cycle");
                 if (done) break;
             }
         }
@@ -146,7 +144,7 @@ int spectral_run(apap_ctx *ctx, const float *d_src, const float *d_dst, const fl
                            d_info, d_status);
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_spectral_device launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_spectral_device launch");
     return APAP_OK;
 }
 
@@ -164,7 +162,7 @@ int spectral_affinity_run(const float *d_src, const float *d_dst, const float *d
     spec_launch_setup(L, P, d_src, d_dst, d_c, d_o, d_F, sc, nullptr, nullptr, s);
     hipLaunchKernelGGL(k_spec_affinity, dim3((n + kSpecThreads - 1) / kSpecThreads, n), dim3(kSpecThreads), 0, s, P, n, sc.rcp, d_M);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "apap_spectral_affinity launch");
+    if (e != hipSuccess) return apap::hip_fail(e, "apap_spectral_affinity launch");
     return APAP_OK;
 }
 

@@ -216,3 +216,38 @@ def ransac_core(name):
     if name not in _cores:
         _cores[name] = F.ransac_core(*ransac_cases()[name])
     return _cores[name]
+
+
+# ---------------------------------------------------------------- the sampler's smallest pools
+# The sampler is one template (csrc/apap_ransac_dev.h) at 4 draws (homography) and at 8 (fundamental matrix).  Its smallest
+# pools: n = K, where the last draw is taken modulo 1 and every pick is forced by the step-over, and n = K + 1; 65
+# iterations, so that the second block of hypotheses has one live lane; the default seed and one whose counter wraps.
+POOL_ITERATIONS = 65
+POOL_SEEDS = {"default": None, "wrap": (1 << 64) - 5}
+SMALL_POOLS = [("homography", 4), ("homography", 5), ("fundamental", 8), ("fundamental", 9)]
+
+
+def small_pool_case(model, n, seed_name):
+    """A clean scene of n matches: a ``ransac_cases`` tuple for the homography, a ``fundamental_cases.Case`` for the
+    fundamental matrix (its specification's default seed is its own)."""
+    seed = POOL_SEEDS[seed_name]
+    if model == "homography":
+        src, dst, _, _ = TF.ransac_case(n, 0.0, seed=n)
+        return src, dst, 5.0, POOL_ITERATIONS, F.RANSAC_SEED if seed is None else seed
+    import fundamental_cases as C
+    s = C.two_pose_scene(n, 300 + n, noise=0.5)
+    settings = {} if seed is None else {"seed": seed}
+    return C.Case(f"pool n{n} {seed_name}", s.src, s.dst, 3.0, POOL_ITERATIONS, **settings)
+
+
+def small_pool_core(model, n, seed_name):
+    """The specification's answer for ``small_pool_case``, computed once."""
+    key = (model, n, seed_name)
+    if key not in _cores:
+        case = small_pool_case(model, n, seed_name)
+        if model == "homography":
+            _cores[key] = F.ransac_core(*case)
+        else:
+            import fundamental_cases as C
+            _cores[key] = C.expected(case)
+    return _cores[key]

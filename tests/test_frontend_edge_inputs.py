@@ -177,3 +177,25 @@ def test_ransac_thresholds_whose_squares_are_zero_and_infinite():
         assert huge["count"] == len(src)
     nan_rows = np.isnan(E.ransac_core("duplicates, thresh 1e+200")["H"]).any(axis=1)
     assert nan_rows.any() and not E.ransac_core("duplicates, thresh 1e+200")["counts"][nan_rows].any()
+
+
+@pytest.mark.parametrize("seed_name", list(E.POOL_SEEDS))
+@pytest.mark.parametrize("model,n", E.SMALL_POOLS)
+def test_small_pools_force_the_last_picks_and_still_give_a_model(model, n, seed_name):
+    """n = K: every hypothesis draws a permutation of all n matches; n = K + 1: all but one.  The winner keeps at least K
+    inliers, so neither wrapper's "no model" branch hides the comparison."""
+    K = {"homography": 4, "fundamental": 8}[model]
+    assert n in (K, K + 1) and E.POOL_ITERATIONS == E.HYP_LANES + 1
+    case, core = E.small_pool_case(model, n, seed_name), E.small_pool_core(model, n, seed_name)
+    if model == "homography":
+        picks, seed = core["picks"], case[4]
+    else:
+        import fundamental_spec as S
+        picks, seed = S.sample(n, E.POOL_ITERATIONS, case.seed), case.seed
+        assert np.isfinite(core["F"]).all()
+    assert picks.shape == (E.POOL_ITERATIONS, K)
+    assert all(len(set(p.tolist())) == K and 0 <= p.min() and p.max() < n for p in picks)
+    assert len({tuple(p.tolist()) for p in picks}) > 1                                      # not one sample 65 times
+    assert core["count"] >= K and not np.isnan(core["H"][core["best"]]).any()
+    if seed_name == "wrap":
+        assert seed + K * 2 > 2 ** 64 > seed         # the counter wraps inside hypothesis 0 (K = 8) or 1 (K = 4)

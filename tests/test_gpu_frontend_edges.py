@@ -5,7 +5,9 @@ body, the shortest and longest tails, aligned and unaligned stores, images that 
 builder's wave boundaries, the grid-stride loop, the workspace's zero-on-return contract, error codes.  RANSAC: the last
 partial block of hypotheses, the scoring stride at 255 / 256 / 257 points, the tie rule of the selection, all-NaN and partly
 NaN tables, a wrapping counter, thresholds whose squares are 0 and inf, a best count of 3 and of 4, argument checks.  The
-yardstick is oracle/frontend_oracle.py everywhere, byte for byte."""
+yardstick is oracle/frontend_oracle.py everywhere, byte for byte.  Last, the sampler that the seed homography shares with the
+fundamental matrix (csrc/apap_ransac_dev.h) at its smallest pools, n = K and K + 1 for K = 4 and 8 draws: the fundamental
+cases against tests/fundamental_spec.py."""
 import ctypes
 
 import numpy as np
@@ -300,3 +302,19 @@ def test_find_homography_on_nan_tables_and_a_wrapping_seed(native_gpu, name):
     assert (H is None) == (H_ref is None) == (name == "all NaN")
     if H is not None:
         assert np.array_equal(H, H_ref), np.abs(H - H_ref).max()        # the re-fit is the hot path: bit-exact float32
+
+
+# ---------------------------------------------------------------- the shared sampler at its smallest pools, both estimators
+@pytest.mark.parametrize("seed_name", list(E.POOL_SEEDS))
+@pytest.mark.parametrize("model,n", E.SMALL_POOLS)
+def test_sampler_smallest_pools_are_bit_identical_to_both_specifications(native_gpu, model, n, seed_name):
+    """n = 4 / 5 through apap_ransac_device and n = 8 / 9 through apap_fundamental_batch_device at 65 iterations: the last
+    draw modulo 1 and modulo 2, one live lane in the second block of hypotheses, a wrapping counter.  Every hypothesis, count,
+    the winner, the mask (and F) against the estimator's own specification."""
+    case, core = E.small_pool_case(model, n, seed_name), E.small_pool_core(model, n, seed_name)
+    if model == "homography":
+        TF.assert_ransac_equals_core(TF.ransac_device(native_gpu, *case), core)
+    else:
+        import test_gpu_fundamental as TG
+        got = TG.run_resident(native_gpu, case.src, case.dst, [0, n], case.thresh, case.iterations, case.seed)
+        TG.check_pair(got, 0, slice(0, n), core, case.name)
