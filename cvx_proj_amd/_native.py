@@ -271,6 +271,21 @@ SIGNATURES.update({
                                                 _vp, C.c_size_t, _vp]),
 })
 
+# notch denoising (apap_denoise.hip)
+SIGNATURES.update({
+    "apap_fft_twiddles": (C.c_int, [C.c_int, _f64p]),
+    "apap_fft2": (C.c_int, [_vp, _f64p, _f64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "apap_fft2_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "apap_fft2_device": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "apap_notch_spectrum": (C.c_int, [_vp, _f64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "apap_notch_spectrum_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "apap_notch_denoise": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
+                                     C.c_int]),
+    "apap_notch_denoise_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "apap_notch_denoise_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            _vp, _vp, C.c_size_t, _vp]),
+})
+
 _lib = None
 _torch_at_load = False      # was torch in the process when the library was loaded?  (cvx_proj_amd.resident refuses otherwise)
 
@@ -715,6 +730,61 @@ def equalize_hist(img, device=-1, ctx=None):
     out = np.empty_like(a)
     check(lib().apap_equalize_hist(_h(ctx), _ptr(a, C.c_uint8), a.shape[0], a.shape[1], channels, _ptr(out, C.c_uint8), device))
     return out
+
+
+FFT_MIN_LENGTH, FFT_MAX_LENGTH = 2, 4096     # APAP_FFT_MIN_LENGTH, APAP_FFT_MAX_LENGTH
+NOTCH_MAX_R = 6                              # APAP_NOTCH_MAX_R
+DENOISE_OUT = {"float64": 0, "uint8": 1}     # APAP_DENOISE_OUT_F64, APAP_DENOISE_OUT_U8
+DENOISE_MAX_PLANES = 65535
+
+
+def fft_twiddles(n):
+    """``apap_fft_twiddles``: (n, 2) float64, cos and sin of -2 pi k / n - the table the kernels read.  Needs no device."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"fft_twiddles: n={n}")
+    out = np.empty((n, 2), dtype=np.float64)
+    check(lib().apap_fft_twiddles(n, _ptr(out, C.c_double)))
+    return out
+
+
+def _spectra(x, who):
+    """``x`` as contiguous complex128 (planes, h, w), and whether it came as one plane."""
+    a = np.array(x, dtype=np.complex128, order="C")     # a copy: the in-place entry points may write it
+    if a.ndim not in (2, 3) or a.size == 0:
+        raise ValueError(f"{who}: a (h, w) or (planes, h, w) complex array expected; got {a.shape}")
+    return (a[None] if a.ndim == 2 else a), a.ndim == 2
+
+
+def fft2(x, inverse=False, device=-1, ctx=None):
+    """``apap_fft2``: the engine's 2-D transform of one (h, w) or several (planes, h, w) complex128 planes; lengths 5-smooth,
+    2 .. 4096.  The inverse is scaled by 1 / (h w)."""
+    a, one = _spectra(x, "fft2")
+    out = np.empty_like(a)
+    check(lib().apap_fft2(_h(ctx), _ptr(a.view(np.float64), C.c_double), _ptr(out.view(np.float64), C.c_double), a.shape[0], a.shape[1],
+                          a.shape[2], 1 if inverse else 0, device))
+    return out[0] if one else out
+
+
+def notch_spectrum(f, spacing=48, r=5, sn=9, device=-1, ctx=None):
+    """``apap_notch_spectrum``: the notch schedule on shifted spectra ((h, w) or (planes, h, w) complex); returns new arrays."""
+    a, one = _spectra(f, "notch_spectrum")
+    check(lib().apap_notch_spectrum(_h(ctx), _ptr(a.view(np.float64), C.c_double), a.shape[0], a.shape[1], a.shape[2], int(spacing),
+                                    int(r), int(sn), device))
+    return a[0] if one else a
+
+
+def notch_denoise(imgs, spacing=48, r=5, sn=9, equalize=True, out="float64", device=-1, ctx=None):
+    """``apap_notch_denoise``: uint8 pictures (n, h, w, c), c <= 4, all planes in one call; float64 or uint8 of that shape."""
+    a = np.ascontiguousarray(imgs, dtype=np.uint8)
+    if a.ndim != 4 or a.size == 0:
+        raise ValueError(f"notch_denoise: (n, h, w, c) uint8 pictures expected; got {a.shape}")
+    if out not in DENOISE_OUT:
+        raise ValueError(f"notch_denoise: out={out!r} ('float64' or 'uint8')")
+    res = np.empty(a.shape, dtype=np.float64 if out == "float64" else np.uint8)
+    check(lib().apap_notch_denoise(_h(ctx), _ptr(a, C.c_uint8), a.shape[0], a.shape[1], a.shape[2], a.shape[3], 1 if equalize else 0,
+                                   int(spacing), int(r), int(sn), DENOISE_OUT[out], res.ctypes.data_as(C.c_void_p), device))
+    return res
 
 
 WARP_GEOMETRY, WARP_CELLS, WARP_GATHER, WARP_ALL = 1, 2, 4, 7      # phases of apap_warp_batch_device

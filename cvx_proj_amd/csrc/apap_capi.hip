@@ -863,6 +863,61 @@ int apap_find_fundamental_ransac(apap_ctx *ctx, const float *src, const float *d
     return apap_find_fundamental_ransac_batch(ctx, src, dst, off, 1, thresh, iterations, seed, F_out, mask_out, inliers_out, device);
 }
 
+// ---- notch denoising (apap_denoise.hip): every argument is checked before a device is looked for
+int apap_fft2(apap_ctx *ctx, const double *in, double *out, int planes, int h, int w, int inverse, int device) {
+    const char *who = "apap_fft2";
+    int rc = apap::fft_check(planes, h, w, who);
+    if (rc) return rc;
+    if (!in || !out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    const Part d_f = call.slot(S_OUT, (size_t)planes * h * w * 16), work = call.slot(S_WORK, apap_fft2_workspace_bytes(planes, h, w));
+    call.up(d_f, in);
+    if ((rc = call.rc())) return rc;
+    rc = apap_fft2_device(ctx, d_f.as<const double>(), d_f.as<double>(), planes, h, w, inverse, work.as<void>(), work.bytes, call.stream());
+    if (rc) return rc;
+    call.down(out, d_f);
+    return call.wait();
+}
+
+int apap_notch_spectrum(apap_ctx *ctx, double *f, int planes, int h, int w, int spacing, int r, int sn, int device) {
+    const char *who = "apap_notch_spectrum";
+    if (planes < 1 || planes > apap::kDenoiseMaxPlanes || h < 1 || w < 1 || h > APAP_FFT_MAX_LENGTH || w > APAP_FFT_MAX_LENGTH)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: %d planes of %d x %d (1 .. %d planes, sides 1 .. %d)", who, planes, h, w,
+                          apap::kDenoiseMaxPlanes, APAP_FFT_MAX_LENGTH);
+    int rc = apap::notch_check(spacing, r, sn, who);
+    if (rc) return rc;
+    if (!f) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    const Part d_f = call.slot(S_OUT, (size_t)planes * h * w * 16);
+    call.up(d_f, f);
+    if ((rc = call.rc())) return rc;
+    if ((rc = apap_notch_spectrum_device(ctx, d_f.as<double>(), planes, h, w, spacing, r, sn, call.stream()))) return rc;
+    call.down(f, d_f);
+    return call.wait();
+}
+
+int apap_notch_denoise(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, int w, int channels, int equalize, int spacing,
+                       int r, int sn, int out_type, void *out, int device) {
+    const char *who = "apap_notch_denoise";
+    int rc = apap::denoise_check(n_images, h, w, channels, spacing, r, sn, out_type, who);
+    if (rc) return rc;
+    if (!imgs || !out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    const size_t values = (size_t)n_images * h * w * channels;
+    const Part d_img = call.slot(S_IMG, values), d_out = call.slot(S_OUT, values * (out_type == APAP_DENOISE_OUT_U8 ? 1 : 8));
+    const Part work = call.slot(S_WORK, apap_notch_denoise_workspace_bytes(n_images, h, w, channels));
+    call.up(d_img, imgs);
+    if ((rc = call.rc())) return rc;
+    rc = apap_notch_denoise_device(ctx, d_img.as<const uint8_t>(), n_images, h, w, channels, equalize, spacing, r, sn, out_type,
+                                   d_out.as<void>(), work.as<void>(), work.bytes, call.stream());
+    if (rc) return rc;
+    call.down(out, d_out);
+    return call.wait();
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ spectral weights (spectral_method.py:66-133)

@@ -216,6 +216,12 @@ int local_model_check(int n, int cells, double gamma, double sigma, const double
 int match_check(const int *q_offset, const int *t_offset, int n_pairs, const char *who);
 // The argument checks of the fundamental-matrix entry points (apap_fundamental.hip) that need no device pointer.
 int fundamental_check(const int *pair_offset, int n_pairs, double thresh, int iterations, const char *who);
+// The argument checks of the notch denoising's entry points (apap_denoise.hip) that need no device pointer: the planes of a
+// call (the grid's second dimension) and the transform's lengths; the notch's parameters; all of a denoising call's.
+constexpr int kDenoiseMaxPlanes = 65535;
+int fft_check(int planes, int h, int w, const char *who);
+int notch_check(int spacing, int r, int sn, const char *who);
+int denoise_check(int n_images, int h, int w, int channels, int spacing, int r, int sn, int out_type, const char *who);
 // `bytes` rounded up to the 256-byte boundary on which every part of a workspace or pooled buffer starts.
 inline size_t up256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 

@@ -257,6 +257,55 @@ def hip_fundamental(src, dst, thresh=3.0, iterations=_native.RANSAC_ITERATIONS, 
     return F[0], mask, result[0]
 
 
+def hip_fft2(x, inverse=False, ctx=None, work=None, out=None):
+    """``apap_fft2_device`` on the current stream of the tensor's device: the 2-D transform of an (h, w) or (planes, h, w)
+    complex128 tensor, 5-smooth lengths 2 .. 4096; the inverse is scaled by 1 / (h w).  ``out`` may be ``x`` itself.  ``work``
+    (uint8, 256-byte aligned) receives the twiddle tables and, for h > 1024, a turned copy of the planes.  Same bytes as ``_native.fft2``.  Not synchronised."""
+    who = "hip_fft2"
+    _needs_device(x, who)
+    dev = x.device
+    _contiguous(((x, torch.complex128),), dev, who)
+    if x.dim() not in (2, 3) or x.numel() == 0:
+        raise ValueError(f"{who}: an (h, w) or (planes, h, w) tensor expected; got {tuple(x.shape)}")
+    planes, h, w = (1, *x.shape) if x.dim() == 2 else x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _contiguous(((out, torch.complex128),), dev, who)
+        if out.shape != x.shape:
+            raise ValueError(f"{who}: out must have the shape of x")
+    work = _scratch(work, max(_native.lib().apap_fft2_workspace_bytes(int(planes), int(h), int(w)), 256), dev)
+    _native.check(_native.lib().apap_fft2_device(_native._h(ctx), x.data_ptr(), out.data_ptr(), int(planes), int(h), int(w),
+                                                 1 if inverse else 0, work.data_ptr(), work.numel(), _stream(dev)))
+    return out
+
+
+def notch_denoise_workspace_bytes(n_images, h, w, channels):
+    """Workspace of ``hip_notch_denoise`` (0 for invalid arguments): twiddles, planes x h x w complex128 (twice for h > 1024), the
+    equalised pictures."""
+    return _native.lib().apap_notch_denoise_workspace_bytes(int(n_images), int(h), int(w), int(channels))
+
+
+def hip_notch_denoise(imgs, spacing=48, r=5, sn=9, equalize=True, out="float64", ctx=None, work=None):
+    """``apap_notch_denoise_device`` on the current stream of the tensor's device, no host synchronisation: uint8 pictures
+    (h, w), (h, w, c) or (n, h, w, c), c <= 4; returns a float64 or uint8 tensor of that shape.  The uint8 result is what
+    ``hip_corner_detect`` takes, so a resident chain denoises and then detects without a host trip.  Same bytes as
+    ``denoise.notch_denoise``."""
+    who = "hip_notch_denoise"
+    _needs_device(imgs, who)
+    dev = imgs.device
+    _contiguous(((imgs, torch.uint8),), dev, who)
+    if imgs.dim() not in (2, 3, 4) or imgs.numel() == 0 or out not in _native.DENOISE_OUT:
+        raise ValueError(f"{who}: uint8 pictures (h, w), (h, w, c) or (n, h, w, c) and out 'float64' or 'uint8' expected")
+    n, h, w, c = {2: (1, *imgs.shape, 1), 3: (1, *imgs.shape), 4: tuple(imgs.shape)}[imgs.dim()]
+    res = torch.empty(imgs.shape, dtype=torch.float64 if out == "float64" else torch.uint8, device=dev)
+    work = _scratch(work, max(notch_denoise_workspace_bytes(n, h, w, c), 256), dev)
+    _native.check(_native.lib().apap_notch_denoise_device(
+        _native._h(ctx), imgs.data_ptr(), int(n), int(h), int(w), int(c), 1 if equalize else 0, int(spacing), int(r), int(sn),
+        _native.DENOISE_OUT[out], res.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
+    return res
+
+
 def spectral_workspace_bytes(n):
     """Scratch of ``hip_spectral`` for ``n`` matches: O(n), no n x n buffer."""
     return _native.lib().apap_spectral_workspace_bytes(n)

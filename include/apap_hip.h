@@ -521,6 +521,54 @@ int apap_fundamental_batch_device(apap_ctx *ctx, const float *d_src, const float
                                   double thresh, int iterations, unsigned long long seed, double *d_F, uint8_t *d_mask,
                                   int *d_result, void *d_work, size_t work_bytes, void *stream);
 
+/* ------------------------------------------------- notch denoising of periodic noise --- */
+/* apply_median_filter of pyviz/median_filter.py on uint8 planes of h rows x w columns:
+ *     plane = equalizeHist(plane); F = fftshift(fft2(plane))                                    (:130-136)
+ *     for i in 2 .. sn - 1: the calls (i, i), (j, i) and (i, j) for j < i with radii (r, 5 r), then (0, i) and (i, 0) with
+ *         radii (3, 3 r); a call (a, b) makes four assignments F[D <= r1] = median(F[D <= r2]), D the distance from
+ *         (w / 2 +- a spacing, h / 2 +- b spacing), in place and in order                        (:97-126, :143-155)
+ *     out = |ifft2(ifftshift(F))|                                                               (:160-162)
+ * np.median of complex values orders them by real part, then imaginary part, and returns (a + b) / 2 of the two middle
+ * ones for an even count; discs are clipped to the plane, an empty one assigns nothing.  Everything is complex128.  The
+ * transform is this library's own (mixed radix 4, 2, 3, 5 Stockham, rows then columns; the inverse columns then rows with
+ * the conjugate table, scaled once by the double 1.0 / (h w)); the magnitude is sqrt(re re + im im) of the scaled value, the
+ * uint8 output min(255, floor(x + 0.5)).  tests/denoise_spec.py is the specification, byte for byte.
+ * Lengths: 5-smooth, APAP_FFT_MIN_LENGTH .. APAP_FFT_MAX_LENGTH each.  1 <= r <= APAP_NOTCH_MAX_R, sn >= 2 and
+ * spacing > max(6 r, 5 r + 3): then no write disc meets another centre's read disc, and every distinct centre is
+ * evaluated from the spectrum as it was (one block each).  There is no CPU path: ERR_NO_DEVICE without a device. */
+#define APAP_FFT_MIN_LENGTH 2
+#define APAP_FFT_MAX_LENGTH 4096
+#define APAP_NOTCH_MAX_R 6
+#define APAP_DENOISE_OUT_F64 0
+#define APAP_DENOISE_OUT_U8 1
+/* out[2 k], out[2 k + 1] = cos, sin of -2 pi k / n, k = 0 .. n - 1, correctly rounded from extended precision; (1, 0) at
+ * k = 0.  Host only: the table the kernels read and the specification reads. */
+int apap_fft_twiddles(int n, double *out);
+/* 2-D transform of `planes` complex128 planes (interleaved re, im; h x w each).  in == out is allowed.  The resident form's
+ * workspace (256-byte aligned) receives the two twiddle tables and, for h > 1024, a turned copy of the planes: columns that
+ * long do not fit a strip of four in LDS, so the planes are transposed through LDS tiles, their columns transformed as rows
+ * (the same arithmetic) and transposed back - every global access of every pass covers 64 consecutive bytes or the plane's width. */
+int apap_fft2(apap_ctx *ctx, const double *in, double *out, int planes, int h, int w, int inverse, int device);
+size_t apap_fft2_workspace_bytes(int planes, int h, int w);
+int apap_fft2_device(apap_ctx *ctx, const double *d_in, double *d_out, int planes, int h, int w, int inverse, void *d_work,
+                     size_t work_bytes, void *stream);
+/* The notch step alone, in place, on `planes` SHIFTED spectra (fftshift's layout) of any h, w in 1 .. 4096: one launch. */
+int apap_notch_spectrum(apap_ctx *ctx, double *f, int planes, int h, int w, int spacing, int r, int sn, int device);
+int apap_notch_spectrum_device(apap_ctx *ctx, double *d_f, int planes, int h, int w, int spacing, int r, int sn, void *stream);
+/* The whole chain on n_images pictures of one shape, `channels` (1 .. 4) interleaved channels each, n_images * channels <=
+ * 65535 planes.  equalize = 0 skips the equalisation.  out: the pictures' layout, float64 (APAP_DENOISE_OUT_F64) or uint8
+ * (APAP_DENOISE_OUT_U8, what apap_corner_detect reads).  The spectrum is kept unshifted; the shift is index arithmetic in
+ * the notch kernel.  Launches of the resident form: the equalisation's own per picture, then five whatever the number of
+ * planes - forward rows (reads the uint8 plane), forward columns, notch, inverse columns, inverse rows (writes only the
+ * magnitude) - or, for h > 1024, seven: the spectrum is transposed once before the column transform and once after the inverse
+ * one, and the notch works on the turned copy.  Workspace (256-byte aligned, no contract between calls): the two twiddle
+ * tables, planes x h x w complex128 (twice for h > 1024), the equalised pictures, the equalisation's own workspace. */
+int apap_notch_denoise(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, int w, int channels, int equalize, int spacing,
+                       int r, int sn, int out_type, void *out, int device);
+size_t apap_notch_denoise_workspace_bytes(int n_images, int h, int w, int channels);
+int apap_notch_denoise_device(apap_ctx *ctx, const uint8_t *d_imgs, int n_images, int h, int w, int channels, int equalize,
+                              int spacing, int r, int sn, int out_type, void *d_out, void *d_work, size_t work_bytes, void *stream);
+
 /* ------------------------------------------------- spectral match weighting --- */
 /* calculate_M of spectral_method.py:66-133, the step every shell driver of the reference runs:
  *     M_ii = match_score_i + epi_weight / (1 + |dst_i^T F src_i|)                              (:104-114)
