@@ -286,6 +286,19 @@ SIGNATURES.update({
                                             _vp, _vp, C.c_size_t, _vp]),
 })
 
+# co-visibility tracks and triangulation (apap_sfm.hip)
+SIGNATURES.update({
+    "apap_covis_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "apap_covis_tracks": (C.c_int, [_vp, _f32p, _i32p, _i32p, C.c_int, C.c_float, _i32p, _f32p, _i32p, _i32p, C.c_int]),
+    "apap_covis_tracks_device": (C.c_int, [_vp, _vp, _vp, _i32p, C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "apap_triangulate_rays": (C.c_int, [_vp, _f64p, _f64p, _i32p, C.c_int, _f64p, _f64p, _i32p, C.c_int]),
+    "apap_triangulate_rays_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "apap_triangulate_tracks": (C.c_int, [_vp, _i32p, _f32p, C.c_int, C.c_int, _f32p, _i32p, _f64p, _f64p, _f64p, C.c_int, C.c_int,
+                                          _i32p, C.c_int, _f64p, _f64p, _i32p, C.c_int]),
+    "apap_triangulate_tracks_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _i32p, _vp, _vp, _vp, C.c_int, C.c_int,
+                                                 _i32p, C.c_int, _vp, _vp, _vp, _vp]),
+})
+
 _lib = None
 _torch_at_load = False      # was torch in the process when the library was loaded?  (cvx_proj_amd.resident refuses otherwise)
 
@@ -785,6 +798,154 @@ def notch_denoise(imgs, spacing=48, r=5, sn=9, equalize=True, out="float64", dev
     check(lib().apap_notch_denoise(_h(ctx), _ptr(a, C.c_uint8), a.shape[0], a.shape[1], a.shape[2], a.shape[3], 1 if equalize else 0,
                                    int(spacing), int(r), int(sn), DENOISE_OUT[out], res.ctypes.data_as(C.c_void_p), device))
     return res
+
+
+COVIS_MAX_VIEWS = 8                     # APAP_COVIS_MAX_VIEWS
+COVIS_MAX_POINTS = 65536                # APAP_COVIS_MAX_POINTS
+COVIS_EPS = np.float32(0.1)             # has_affinity's 1e-1, as the float the kernels compare with
+STATUS_COVIS_BOUND = 64                 # APAP_STATUS_COVIS_BOUND
+
+
+def covis_arguments(views, eps, who):
+    """The checks of the co-visibility entry points, made before the library (or a device) is touched: 1 .. 8 views, each
+    ``(pts (n, 2), idx (n,))`` with n >= 0, at most 65 536 observations in all, ``eps`` finite and >= 0.  Returns (pts (N, 2)
+    float32, idx (N,) int32, offsets (V + 1,) int32, eps as float32)."""
+    views = list(views)
+    if not 1 <= len(views) <= COVIS_MAX_VIEWS:
+        raise ValueError(f"{who}: {len(views)} views (1 .. {COVIS_MAX_VIEWS})")
+    pts, idx = [], []
+    for v, view in enumerate(views):
+        if len(view) != 2:
+            raise ValueError(f"{who}: view {v} must be (pts (n, 2), idx (n,))")
+        p, i = np.asarray(view[0]), np.asarray(view[1])
+        if i.size and not np.issubdtype(i.dtype, np.integer):
+            raise ValueError(f"{who}: view {v}: idx must be integers; got {i.dtype}")
+        if p.size and not np.issubdtype(p.dtype, np.floating):
+            raise ValueError(f"{who}: view {v}: pts must be floating point; got {p.dtype}")
+        p = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 2) if p.size % 2 == 0 else None
+        if p is None or i.ndim > 1 or len(p) != i.size:
+            raise ValueError(f"{who}: view {v}: pts (n, 2) and idx (n,) expected; got {np.shape(view[0])} and {np.shape(view[1])}")
+        if i.size and (i.min() < np.iinfo(np.int32).min or i.max() > np.iinfo(np.int32).max):
+            raise ValueError(f"{who}: view {v}: idx exceeds int32")
+        pts.append(p)
+        idx.append(i.astype(np.int32).reshape(-1))
+    n = sum(len(p) for p in pts)
+    if n > COVIS_MAX_POINTS:
+        raise ValueError(f"{who}: {n} observations in all (at most {COVIS_MAX_POINTS}: the first-candidate scan is quadratic)")
+    e = np.float32(eps)
+    if not (e >= 0 and np.isfinite(e)):
+        raise ValueError(f"{who}: eps = {eps} (finite, >= 0)")
+    off = np.zeros(len(views) + 1, np.int32)
+    off[1:] = np.cumsum([len(p) for p in pts])
+    return np.ascontiguousarray(np.concatenate(pts)), np.ascontiguousarray(np.concatenate(idx)), off, e
+
+
+def covis_workspace_layout(n_points, n_views):
+    """Byte offsets of the parts of the resident form's workspace (include/apap_hip.h): ``dict(offsets, first, owner, rank,
+    total)``."""
+    up = lambda b: (b + 255) // 256 * 256      # noqa: E731
+    ints = max(n_points, 1) * 4
+    out, at = {}, 0
+    for name, b in (("offsets", (n_views + 1) * 4), ("first", ints), ("owner", ints), ("rank", ints)):
+        out[name] = at
+        at += up(b)
+    out["total"] = at
+    return out
+
+
+def covis_tracks(views, eps=COVIS_EPS, device=-1, ctx=None):
+    """``apap_covis_tracks``: the reference's ``get_covid`` over ``views`` = [(pts (n_v, 2) float32, idx (n_v,) int32), ...],
+    view 0 first.  Returns (table (T, V) int32, track_pts (T, 2) float32, point_track (N,) int32)."""
+    pts, idx, off, e = covis_arguments(views, eps, "covis_tracks")
+    N, V = len(pts), len(off) - 1
+    table = np.empty((N, V), np.int32)
+    track_pts = np.empty((N, 2), np.float32)
+    point_track = np.empty(N, np.int32)
+    T = C.c_int(0)
+    check(lib().apap_covis_tracks(_h(ctx), _ptr(pts, C.c_float), _ip(idx), _ip(off), V, C.c_float(float(e)), _ip(table),
+                                  _ptr(track_pts, C.c_float), _ip(point_track), C.byref(T), device))
+    return table[:T.value].copy(), track_pts[:T.value].copy(), point_track
+
+
+def _rays(origins, dirs, who):
+    o = np.ascontiguousarray(origins, dtype=np.float64)
+    d = np.ascontiguousarray(dirs, dtype=np.float64)
+    if o.size % 3 or o.size != d.size:
+        raise ValueError(f"{who}: origins and dirs of 3 doubles a ray expected; got {o.shape} and {d.shape}")
+    return o.reshape(-1, 3), d.reshape(-1, 3)
+
+
+def ray_offsets(ray_offset, n_rays, who):
+    """``ray_offset`` as int32 (T + 1,): starts at 0, ascends, ends at ``n_rays``."""
+    off = np.asarray(ray_offset)
+    if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError(f"{who}: ray_offset must be a 1-D integer array of T + 1 entries")
+    if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != n_rays:
+        raise ValueError(f"{who}: ray_offset must start at 0, ascend and end at the number of rays ({n_rays})")
+    return np.ascontiguousarray(off, dtype=np.int32)
+
+
+def triangulate_rays(origins, dirs, ray_offset, device=-1, ctx=None):
+    """``apap_triangulate_rays``: the reference's ``solve_3d_position`` for T tracks at once; track k owns rays
+    ``ray_offset[k] .. ray_offset[k + 1] - 1`` of ``origins`` / ``dirs`` ((R, 3) float64).  Returns (X (T, 3) float64, lam_min
+    (T,) float64: A's smallest eigenvalue before the clamp at 1e-3, n_rays (T,) int32); a track without rays is NaN, NaN, 0."""
+    who = "triangulate_rays"
+    o, d = _rays(origins, dirs, who)
+    off = ray_offsets(ray_offset, len(o), who)
+    T = len(off) - 1
+    X, lam, n = np.empty((T, 3)), np.empty(T), np.empty(T, np.int32)
+    check(lib().apap_triangulate_rays(_h(ctx), _dp(o), _dp(d), _ip(off), T, _dp(X), _dp(lam), _ip(n), device))
+    return X, lam, n
+
+
+def triangulate_tables(n_views, dst_lengths, cams, center_cam, view_cam, min_views, who):
+    """The host tables of the track triangulation, checked as the library checks them (before a device is touched): 1 .. 8
+    views, one point count >= 0 per view, ``center_cam`` and every ``view_cam[v]`` among the ``cams`` cameras, ``min_views``
+    >= 1.  Returns (dst_offset (V + 1,) int32, view_cam (V,) int32)."""
+    if not 1 <= n_views <= COVIS_MAX_VIEWS:
+        raise ValueError(f"{who}: {n_views} views (1 .. {COVIS_MAX_VIEWS})")
+    if len(dst_lengths) != n_views or any(int(x) < 0 for x in dst_lengths):
+        raise ValueError(f"{who}: one set of other-picture points per view expected ({n_views}); got {len(dst_lengths)}")
+    cam = np.asarray(view_cam)
+    if cam.shape != (n_views,) or not np.issubdtype(cam.dtype, np.integer) or (cam < 0).any() or (cam >= cams).any():
+        raise ValueError(f"{who}: view_cam must name a camera 0 .. {cams - 1} for each of the {n_views} views; got {view_cam}")
+    if not 0 <= int(center_cam) < cams:
+        raise ValueError(f"{who}: center_cam = {center_cam} (0 .. {cams - 1})")
+    if int(min_views) < 1:
+        raise ValueError(f"{who}: min_views = {min_views} (>= 1)")
+    off = np.zeros(n_views + 1, np.int32)
+    off[1:] = np.cumsum([int(x) for x in dst_lengths])
+    return off, np.ascontiguousarray(cam, dtype=np.int32)
+
+
+def triangulate_tracks(table, track_pts, dst_pts, K_inv, Rs, origins, center_cam, view_cam, min_views=2, device=-1, ctx=None):
+    """``apap_triangulate_tracks``: the loop of the reference's ``covid_3d_optimize`` for every track at once.  ``table``
+    (T, V) int32 and ``track_pts`` (T, 2) float32 as ``covis_tracks`` returns them; ``dst_pts``: per view the other picture's
+    points (n_v, 2) float32 that the table's column indexes; ``K_inv`` (3, 3), ``Rs`` (C, 3, 3), ``origins`` (C, 3) float64;
+    the centre picture is camera ``center_cam``, view v camera ``view_cam[v]``.  Returns (X (T, 3), lam_min (T,), n_rays (T,)
+    int32); a track seen in fewer than ``min_views`` views is NaN, NaN, 0."""
+    who = "triangulate_tracks"
+    tb = np.asarray(table)
+    if tb.ndim != 2 or not (np.issubdtype(tb.dtype, np.integer) or tb.size == 0):
+        raise ValueError(f"{who}: table (T, V) of integers expected; got {tb.shape} {tb.dtype}")
+    T, V = tb.shape
+    tb = np.ascontiguousarray(tb, dtype=np.int32)
+    tp = np.ascontiguousarray(track_pts, dtype=np.float32)
+    if tp.shape != (T, 2):
+        raise ValueError(f"{who}: track_pts ({T}, 2) expected; got {tp.shape}")
+    dst = [np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 2) for d in dst_pts]
+    K = np.ascontiguousarray(K_inv, dtype=np.float64)
+    R = np.ascontiguousarray(Rs, dtype=np.float64)
+    o = np.ascontiguousarray(origins, dtype=np.float64)
+    if K.size != 9 or R.ndim < 2 or R.size % 9 or R.size == 0 or o.size != R.size // 3:
+        raise ValueError(f"{who}: K_inv (3, 3), Rs (C, 3, 3) and origins (C, 3) expected; got {K.shape}, {R.shape}, {o.shape}")
+    R = R.reshape(-1, 9)
+    off, cam = triangulate_tables(V, [len(d) for d in dst], len(R), center_cam, view_cam, min_views, who)
+    flat = np.ascontiguousarray(np.concatenate(dst)) if dst else np.zeros((0, 2), np.float32)
+    X, lam, n = np.empty((T, 3)), np.empty(T), np.empty(T, np.int32)
+    check(lib().apap_triangulate_tracks(_h(ctx), _ip(tb), _ptr(tp, C.c_float), T, V, _ptr(flat, C.c_float), _ip(off), _dp(K), _dp(R),
+                                        _dp(o), len(R), int(center_cam), _ip(cam), int(min_views), _dp(X), _dp(lam), _ip(n), device))
+    return X, lam, n
 
 
 WARP_GEOMETRY, WARP_CELLS, WARP_GATHER, WARP_ALL = 1, 2, 4, 7      # phases of apap_warp_batch_device

@@ -918,6 +918,109 @@ int apap_notch_denoise(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, 
     return call.wait();
 }
 
+// ---- co-visibility tracks and triangulation (apap_sfm.hip): every argument is checked before a device is looked for
+int apap_covis_tracks(apap_ctx *ctx, const float *pts, const int *idx, const int *view_offset, int n_views, float eps, int *table_out,
+                      float *track_pts_out, int *point_track_out, int *n_tracks_out, int device) {
+    const char *who = "apap_covis_tracks";
+    int rc = apap::covis_check(view_offset, n_views, eps, who);
+    if (rc) return rc;
+    if (!pts || !idx || !table_out || !track_pts_out || !point_track_out || !n_tracks_out)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    int result[2] = {0, 0};   // tracks, status: downloads write it
+    const size_t N = (size_t)view_offset[n_views];
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    Layout io = call.layout(S_AUX);
+    const Part d_pts = io.take(N * 2 * sizeof(float)), d_idx = io.take(N * sizeof(int)), d_table = io.take(N * n_views * sizeof(int));
+    const Part d_tpts = io.take(N * 2 * sizeof(float)), d_ptrack = io.take(N * sizeof(int)), d_result = io.take(sizeof(result));
+    call.alloc(io);
+    const Part work = call.slot(S_WORK, apap_covis_workspace_bytes((int)N, n_views));
+    call.up(d_pts, pts);
+    call.up(d_idx, idx);
+    call.zero(d_result);
+    if ((rc = call.rc())) return rc;
+    rc = apap_covis_tracks_device(ctx, d_pts.as<const float>(), d_idx.as<const int>(), view_offset, n_views, eps, d_table.as<int>(),
+                                  d_tpts.as<float>(), d_ptrack.as<int>(), d_result.as<int>(), d_result.as<int>() + 1, work.as<void>(),
+                                  work.bytes, call.stream());
+    if (rc) return rc;
+    call.down(result, d_result);
+    if ((rc = call.wait())) return rc;
+    if (result[1] & APAP_STATUS_COVIS_BOUND) return apap::fail(APAP_ERR_HIP, "%s: the resolver reached its round bound", who);
+    // only the rows that exist: what lies behind them in the caller's arrays stays
+    const size_t T = (size_t)result[0];
+    call.down(table_out, d_table.first(T * n_views * sizeof(int)));
+    call.down(track_pts_out, d_tpts.first(T * 2 * sizeof(float)));
+    call.down(point_track_out, d_ptrack);
+    *n_tracks_out = result[0];
+    return call.wait();
+}
+
+int apap_triangulate_rays(apap_ctx *ctx, const double *origins, const double *dirs, const int *ray_offset, int n_tracks, double *X_out,
+                          double *lam_min_out, int *n_rays_out, int device) {
+    const char *who = "apap_triangulate_rays";
+    if (n_tracks < 0) return apap::fail(APAP_ERR_INVALID_ARG, "%s: %d tracks (>= 0)", who, n_tracks);
+    if (!origins || !dirs || !ray_offset || !X_out || !lam_min_out || !n_rays_out)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    if (ray_offset[0] != 0) return apap::fail(APAP_ERR_INVALID_ARG, "%s: ray_offset[0] = %d (the rays start at 0)", who, ray_offset[0]);
+    for (int k = 0; k < n_tracks; ++k)
+        if (ray_offset[k + 1] < ray_offset[k]) return apap::fail(APAP_ERR_INVALID_ARG, "%s: ray_offset is not ascending at track %d", who, k);
+    HostCall call(ctx);
+    int rc = call.select(device);
+    if (rc) return rc;
+    const size_t R = (size_t)ray_offset[n_tracks], T = (size_t)n_tracks;
+    Layout io = call.layout(S_AUX);
+    const Part d_o = io.take(R * 3 * sizeof(double)), d_d = io.take(R * 3 * sizeof(double)), d_off = io.take((T + 1) * sizeof(int));
+    const Part d_X = io.take(T * 3 * sizeof(double)), d_lam = io.take(T * sizeof(double)), d_n = io.take(T * sizeof(int));
+    call.alloc(io);
+    call.up(d_o, origins);
+    call.up(d_d, dirs);
+    call.up(d_off, ray_offset);
+    if ((rc = call.rc())) return rc;
+    rc = apap_triangulate_rays_device(ctx, d_o.as<const double>(), d_d.as<const double>(), d_off.as<const int>(), (int)R, n_tracks,
+                                      d_X.as<double>(), d_lam.as<double>(), d_n.as<int>(), call.stream());
+    if (rc) return rc;
+    call.down(X_out, d_X);
+    call.down(lam_min_out, d_lam);
+    call.down(n_rays_out, d_n);
+    return call.wait();
+}
+
+int apap_triangulate_tracks(apap_ctx *ctx, const int *table, const float *track_pts, int n_tracks, int n_views, const float *dst_pts,
+                            const int *dst_offset, const double *Kinv, const double *R, const double *origins, int n_cams,
+                            int center_cam, const int *view_cam, int min_views, double *X_out, double *lam_min_out, int *n_rays_out,
+                            int device) {
+    const char *who = "apap_triangulate_tracks";
+    int rc = apap::triangulate_tracks_check(n_tracks, n_views, dst_offset, n_cams, center_cam, view_cam, min_views, who);
+    if (rc) return rc;
+    if (!table || !track_pts || !dst_pts || !Kinv || !R || !origins || !X_out || !lam_min_out || !n_rays_out)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    const size_t T = (size_t)n_tracks, D = (size_t)dst_offset[n_views];
+    Layout io = call.layout(S_AUX);
+    const Part d_table = io.take(T * n_views * sizeof(int)), d_tpts = io.take(T * 2 * sizeof(float)), d_dst = io.take(D * 2 * sizeof(float));
+    const Part d_K = io.take(9 * sizeof(double)), d_R = io.take((size_t)n_cams * 9 * sizeof(double));
+    const Part d_o = io.take((size_t)n_cams * 3 * sizeof(double));
+    const Part d_X = io.take(T * 3 * sizeof(double)), d_lam = io.take(T * sizeof(double)), d_n = io.take(T * sizeof(int));
+    call.alloc(io);
+    call.up(d_table, table);
+    call.up(d_tpts, track_pts);
+    call.up(d_dst, dst_pts);
+    call.up(d_K, Kinv);
+    call.up(d_R, R);
+    call.up(d_o, origins);
+    if ((rc = call.rc())) return rc;
+    rc = apap_triangulate_tracks_device(ctx, d_table.as<const int>(), d_tpts.as<const float>(), nullptr, n_tracks, n_views,
+                                        d_dst.as<const float>(), dst_offset, d_K.as<const double>(), d_R.as<const double>(),
+                                        d_o.as<const double>(), n_cams, center_cam, view_cam, min_views, d_X.as<double>(),
+                                        d_lam.as<double>(), d_n.as<int>(), call.stream());
+    if (rc) return rc;
+    call.down(X_out, d_X);
+    call.down(lam_min_out, d_lam);
+    call.down(n_rays_out, d_n);
+    return call.wait();
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ spectral weights (spectral_method.py:66-133)

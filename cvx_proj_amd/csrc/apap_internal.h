@@ -222,6 +222,10 @@ constexpr int kDenoiseMaxPlanes = 65535;
 int fft_check(int planes, int h, int w, const char *who);
 int notch_check(int spacing, int r, int sn, const char *who);
 int denoise_check(int n_images, int h, int w, int channels, int spacing, int r, int sn, int out_type, const char *who);
+// The argument checks of the co-visibility and triangulation entry points (apap_sfm.hip) that need no device pointer.
+int covis_check(const int *view_offset, int n_views, float eps, const char *who);
+int triangulate_tracks_check(int max_tracks, int n_views, const int *dst_offset, int n_cams, int center_cam, const int *view_cam,
+                             int min_views, const char *who);
 // `bytes` rounded up to the 256-byte boundary on which every part of a workspace or pooled buffer starts.
 inline size_t up256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 

@@ -306,6 +306,104 @@ def hip_notch_denoise(imgs, spacing=48, r=5, sn=9, equalize=True, out="float64",
     return res
 
 
+def covis_workspace_bytes(n_points, n_views):
+    """Workspace of ``hip_covis_tracks`` (``_native.covis_workspace_layout`` names its parts); 0 for invalid arguments."""
+    return _native.lib().apap_covis_workspace_bytes(int(n_points), int(n_views))
+
+
+def hip_covis_tracks(pts, idx, view_lengths, eps=_native.COVIS_EPS, status=None, ctx=None, work=None):
+    """``apap_covis_tracks_device`` on the current stream of the tensors' device, no host synchronisation: the reference's
+    ``get_covid``.  pts (N, 2) float32 and idx (N,) int32 hold the views' observations one after the other, view v of
+    ``view_lengths[v]`` >= 0 (a host list of 1 .. 8 lengths, N <= 65 536).  Returns (table (N, V) int32, track_pts (N, 2)
+    float32, point_track (N,) int32, n_tracks (1,) int32) as device tensors: table and track_pts are sized for the worst
+    case and only their first n_tracks rows are written.  ``status`` (one int32, zeroed): see APAP_STATUS_COVIS_BOUND.  Same
+    bytes as ``_native.covis_tracks``."""
+    who = "hip_covis_tracks"
+    _needs_device(pts, who)
+    dev = pts.device
+    lengths = [int(x) for x in view_lengths]
+    if not 1 <= len(lengths) <= _native.COVIS_MAX_VIEWS or any(x < 0 for x in lengths):
+        raise ValueError(f"{who}: 1 .. {_native.COVIS_MAX_VIEWS} views of >= 0 observations; got {lengths}")
+    N, V = sum(lengths), len(lengths)
+    if N > _native.COVIS_MAX_POINTS:
+        raise ValueError(f"{who}: {N} observations in all (at most {_native.COVIS_MAX_POINTS}: the first-candidate scan is quadratic)")
+    e = np.float32(eps)
+    if not (e >= 0 and np.isfinite(e)):
+        raise ValueError(f"{who}: eps = {eps} (finite, >= 0)")
+    _contiguous(((pts, torch.float32), (idx, torch.int32)), dev, who)
+    if pts.shape != (N, 2) or idx.shape != (N,):
+        raise ValueError(f"{who}: shapes ({N}, 2) and ({N},) expected; got {tuple(pts.shape)} and {tuple(idx.shape)}")
+    off = np.zeros(V + 1, np.int32)
+    off[1:] = np.cumsum(lengths)
+    rows = max(N, 1)        # (an empty tensor has no address)
+    table = torch.empty((rows, V), dtype=torch.int32, device=dev)
+    track_pts = torch.empty((rows, 2), dtype=torch.float32, device=dev)
+    point_track = torch.empty(rows, dtype=torch.int32, device=dev)
+    n_tracks = torch.empty(1, dtype=torch.int32, device=dev)
+    status = _status(status, (1,), dev, who)
+    src_pts, src_idx = (pts, idx) if N else (track_pts, point_track)
+    work = _scratch(work, covis_workspace_bytes(N, V), dev)
+    _native.check(_native.lib().apap_covis_tracks_device(
+        _native._h(ctx), src_pts.data_ptr(), src_idx.data_ptr(), _ip(off), V, ctypes.c_float(float(e)), table.data_ptr(),
+        track_pts.data_ptr(), point_track.data_ptr(), n_tracks.data_ptr(), status.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
+    return table[:N], track_pts[:N], point_track[:N], n_tracks
+
+
+def hip_triangulate_rays(origins, dirs, ray_offset, ctx=None):
+    """``apap_triangulate_rays_device`` on the current stream, no host synchronisation: origins, dirs (R, 3) float64 and
+    ray_offset (T + 1,) int32 device tensors; a range of ray_offset that is reversed or leaves 0 .. R counts as empty.
+    Returns (X (T, 3) float64, lam_min (T,) float64, n_rays (T,) int32).  Same bytes as ``_native.triangulate_rays``."""
+    who = "hip_triangulate_rays"
+    _needs_device(origins, who)
+    dev = origins.device
+    _contiguous(((origins, torch.float64), (dirs, torch.float64), (ray_offset, torch.int32)), dev, who)
+    if origins.dim() != 2 or origins.shape[1] != 3 or dirs.shape != origins.shape or ray_offset.dim() != 1 or ray_offset.numel() < 1:
+        raise ValueError(f"{who}: origins, dirs (R, 3) and ray_offset (T + 1,) expected")
+    T, R = ray_offset.numel() - 1, origins.shape[0]
+    X = torch.empty((T, 3), dtype=torch.float64, device=dev)
+    lam = torch.empty(T, dtype=torch.float64, device=dev)
+    n = torch.empty(T, dtype=torch.int32, device=dev)
+    if T and R:
+        _native.check(_native.lib().apap_triangulate_rays_device(_native._h(ctx), origins.data_ptr(), dirs.data_ptr(), ray_offset.data_ptr(),
+                                                                 R, T, X.data_ptr(), lam.data_ptr(), n.data_ptr(), _stream(dev)))
+    elif T:
+        X.fill_(float("nan")), lam.fill_(float("nan")), n.zero_()
+    return X, lam, n
+
+
+def hip_triangulate_tracks(table, track_pts, n_tracks, dst_pts, dst_lengths, K_inv, Rs, origins, center_cam, view_cam, min_views=2, ctx=None):
+    """``apap_triangulate_tracks_device`` on the current stream, no host synchronisation: what ``hip_covis_tracks`` returns
+    (table (rows, V) int32, track_pts (rows, 2) float32, n_tracks (1,) int32 or None for every row) goes in as it is.  dst_pts
+    (D, 2) float32: the views' other-picture points one after the other, view v of ``dst_lengths[v]`` (host list); K_inv (3, 3),
+    Rs (C, 3, 3), origins (C, 3) float64 device tensors; ``center_cam`` and ``view_cam`` (host) name cameras.  Returns (X (rows,
+    3), lam_min (rows,), n_rays (rows,) int32); rows behind n_tracks are not written.  Same bytes as
+    ``_native.triangulate_tracks``."""
+    who = "hip_triangulate_tracks"
+    _needs_device(table, who)
+    dev = table.device
+    if table.dim() != 2:
+        raise ValueError(f"{who}: table (rows, V) expected; got {tuple(table.shape)}")
+    rows, V = table.shape
+    off, cam = _native.triangulate_tables(V, list(dst_lengths), max(Rs.numel() // 9, 1), center_cam, view_cam, min_views, who)
+    tensors = [(table, torch.int32), (track_pts, torch.float32), (dst_pts, torch.float32), (K_inv, torch.float64), (Rs, torch.float64),
+               (origins, torch.float64)] + ([(n_tracks, torch.int32)] if n_tracks is not None else [])
+    _contiguous(tensors, dev, who)
+    cams = Rs.numel() // 9
+    if track_pts.shape != (rows, 2) or dst_pts.shape != (int(off[-1]), 2) or K_inv.numel() != 9 or Rs.numel() != cams * 9 or cams < 1 \
+            or origins.numel() != cams * 3 or (n_tracks is not None and n_tracks.numel() != 1):
+        raise ValueError(f"{who}: track_pts ({rows}, 2), dst_pts ({int(off[-1])}, 2), K_inv (3, 3), Rs (C, 3, 3), origins (C, 3) expected")
+    X = torch.empty((rows, 3), dtype=torch.float64, device=dev)
+    lam = torch.empty(rows, dtype=torch.float64, device=dev)
+    n = torch.empty(rows, dtype=torch.int32, device=dev)
+    if rows:
+        d_dst = dst_pts if dst_pts.numel() else track_pts       # (an empty tensor has no address; no index can point into it)
+        _native.check(_native.lib().apap_triangulate_tracks_device(
+            _native._h(ctx), table.data_ptr(), track_pts.data_ptr(), n_tracks.data_ptr() if n_tracks is not None else None, rows, V,
+            d_dst.data_ptr(), _ip(off), K_inv.data_ptr(), Rs.data_ptr(), origins.data_ptr(), cams, int(center_cam), _ip(cam),
+            int(min_views), X.data_ptr(), lam.data_ptr(), n.data_ptr(), _stream(dev)))
+    return X, lam, n
+
+
 def spectral_workspace_bytes(n):
     """Scratch of ``hip_spectral`` for ``n`` matches: O(n), no n x n buffer."""
     return _native.lib().apap_spectral_workspace_bytes(n)

@@ -22,7 +22,7 @@ import numpy as np
 from . import _native
 
 __all__ = ["get_base_path", "get_path", "imread", "equalize_hist", "visualize_equalized_hist", "get_no_scat_img",
-           "get_features", "save2mat", "image_warping", "image_warping_batch"]
+           "get_features", "save2mat", "image_warping", "image_warping_batch", "world_frame_ray_dir"]
 
 DEFAULT_ROOT = "../diff_1/raw_data"     # utils.py:28
 
@@ -110,6 +110,19 @@ def get_features(case_idx: int = 1, pic_id: int = 1, center_id: int = 3, root: s
     raw_kpts_op = feat_mat[3:-1, :].T
     raw_kpts_cp = feat_mat[:2, :].T
     return raw_kpts_cp, raw_kpts_op
+
+
+def world_frame_ray_dir(K_inv, pix, Rs):
+    """utils.py:188-202 without its prints: pixels ``pix`` (n, 2, 1), one rotation each ``Rs`` (n, 3, 3) -> unit ray directions
+    in the world frame (n, 3, 1) float64.  ``cam = K_inv (u, v, 1)``, the axes turned to (cam_x, cam_z, -cam_y), normalised,
+    rotated.  Host numpy: it is the small-input form of what ``sfm_test.covid_3d_optimize`` computes per track on the GPU."""
+    pix = np.asarray(pix, dtype=np.float64).reshape(-1, 2)
+    Rs = np.asarray(Rs, dtype=np.float64).reshape(-1, 3, 3)
+    K = np.asarray(K_inv, dtype=np.float64).reshape(3, 3)
+    cam = pix[:, 0, None] * K[:, 0] + pix[:, 1, None] * K[:, 1] + K[:, 2]
+    w = np.stack([cam[:, 0], cam[:, 2], -cam[:, 1]], axis=1)
+    w = w / np.sqrt((w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2])[:, None]
+    return ((Rs[:, :, 0] * w[:, 0, None] + Rs[:, :, 1] * w[:, 1, None]) + Rs[:, :, 2] * w[:, 2, None])[:, :, None]
 
 
 def savemat_f64(file_name, name, arr):

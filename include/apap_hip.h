@@ -569,6 +569,67 @@ size_t apap_notch_denoise_workspace_bytes(int n_images, int h, int w, int channe
 int apap_notch_denoise_device(apap_ctx *ctx, const uint8_t *d_imgs, int n_images, int h, int w, int channels, int equalize,
                               int spacing, int r, int sn, int out_type, void *d_out, void *d_work, size_t work_bytes, void *stream);
 
+/* ------------------------------------------------- co-visibility tracks and triangulation --- */
+/* get_covid of pyviz/sfm_test.py:79-95 (with has_affinity :23-28) for V views of one centre picture, 1 <= V <=
+ * APAP_COVIS_MAX_VIEWS.  View v holds view_offset[v + 1] - view_offset[v] >= 0 observations, the views concatenated
+ * (view_offset[0] = 0, at most APAP_COVIS_MAX_POINTS in all: the first-candidate scan is quadratic, a spatial grid for more is
+ * out of scope); an observation is a centre-picture point pts[2 g], pts[2 g + 1] (float32) and an index idx[g] into that
+ * view's other-picture keypoints.  The reference's sequence is the definition: every observation of view 0 opens a track, in
+ * order; every later observation, in order, joins the FIRST track, in track order, whose point q has fabsf(q.x - p.x) < eps
+ * and fabsf(q.y - p.y) < eps (float32, strict; NaN matches nothing) and sets that track's column v (a later observation of
+ * the same view overwrites an earlier one), or opens a new track at the end.  eps is finite and >= 0; the reference's is 0.1f.
+ *   table        n_tracks x V ints: the index seen in each view or -1        track_pts  n_tracks x 2 floats: the founder's point
+ *   point_track  one int an observation: the track it ended in               n_tracks   one int
+ * table and track_pts are sized for the worst case (as many tracks as observations); rows behind n_tracks are not written.
+ * tests/sfm_spec.py is the specification; the kernels (csrc/apap_sfm.hip) equal it bit for bit.  No CPU path.
+ *
+ * Workspace of the resident form (256-byte aligned, no contract between calls), parts rounded up to 256 bytes, in order:
+ *     offsets  (V + 1) ints                     the view table
+ *     first    max(n_points, 1) ints            per observation the first earlier in-box position; the resolver moves it on
+ *     owner    max(n_points, 1) ints            the position that founded the observation's track
+ *     rank     max(n_points, 1) ints            a founder's track
+ * apap_covis_workspace_bytes returns 0 for invalid arguments.
+ * The resident form takes device pointers but view_offset, allocates nothing and does not wait: one fill and five launches
+ * on `stream`.  d_status (zeroed by the caller): APAP_STATUS_COVIS_BOUND is OR-ed in if the resolver's round count reached
+ * its structural bound (every undecided observation then opens a track); the host-buffer form returns APAP_ERR_HIP for it. */
+#define APAP_COVIS_MAX_VIEWS 8
+#define APAP_COVIS_MAX_POINTS 65536
+#define APAP_STATUS_COVIS_BOUND 64
+size_t apap_covis_workspace_bytes(int n_points, int n_views);
+int apap_covis_tracks(apap_ctx *ctx, const float *pts, const int *idx, const int *view_offset, int n_views, float eps, int *table_out,
+                      float *track_pts_out, int *point_track_out, int *n_tracks_out, int device);
+int apap_covis_tracks_device(apap_ctx *ctx, const float *d_pts, const int *d_idx, const int *view_offset, int n_views, float eps,
+                             int *d_table, float *d_track_pts, int *d_point_track, int *d_n_tracks, int *d_status, void *d_work,
+                             size_t work_bytes, void *stream);
+/* solve_3d_position of pyviz/sfm_test.py:125-136 for many tracks at once, float64: for a track's rays (o_k, d_k) in order
+ * A = sum (I - d d^T), p = sum (I - d d^T) o; A = V diag(lam) V^T by cyclic Jacobi; X = V diag(1 / max(lam, 1e-3)) V^T p.
+ * The clamp is on every eigenvalue and has no sign rule (the reference scales its last singular value by s / |s|, which is
+ * 0 / 0 at exact degeneracy).  Per track: X 3 doubles, lam_min (the smallest eigenvalue before the clamp), n_rays.  A track
+ * without rays has X and lam_min NaN and n_rays 0; a non-finite X is stored as three canonical NaN.
+ * apap_triangulate_rays: track k owns rays ray_offset[k] .. ray_offset[k + 1] - 1 of origins / dirs (3 doubles a ray).  The
+ * host form refuses offsets that do not start at 0 or descend; the resident form reads them on the device and treats a range
+ * that is reversed or outside 0 .. n_rays_total as empty.
+ * apap_triangulate_tracks: the rays are built from the tracks (covid_3d_optimize :139-167, world_frame_ray_dir of
+ * utils.py:188-202): the centre picture's ray through track_pts[k] with camera center_cam first, then for every view v,
+ * ascending, whose column holds an index inside 0 .. dst_offset[v + 1] - dst_offset[v] - 1 the ray through that point of
+ * dst_pts (float32 pairs, the views concatenated) with camera view_cam[v].  A pixel (u, v) of camera c gives
+ * cam = Kinv (u, v, 1), w = (cam_x, cam_z, -cam_y) / |.|, d = R_c w; the ray starts at origins[c].  Kinv 9 doubles, R n_cams x 9,
+ * origins n_cams x 3.  A track seen in fewer than min_views >= 1 views (the reference: 2) has no rays.  The resident form
+ * takes device pointers but dst_offset and view_cam (they travel in the kernel argument: no workspace), reads the number of
+ * tracks from *d_n_tracks (NULL: max_tracks), capped at max_tracks, and writes nothing behind it.  One launch each, no wait. */
+int apap_triangulate_rays(apap_ctx *ctx, const double *origins, const double *dirs, const int *ray_offset, int n_tracks, double *X_out,
+                          double *lam_min_out, int *n_rays_out, int device);
+int apap_triangulate_rays_device(apap_ctx *ctx, const double *d_origins, const double *d_dirs, const int *d_ray_offset, int n_rays_total,
+                                 int n_tracks, double *d_X, double *d_lam_min, int *d_n_rays, void *stream);
+int apap_triangulate_tracks(apap_ctx *ctx, const int *table, const float *track_pts, int n_tracks, int n_views, const float *dst_pts,
+                            const int *dst_offset, const double *Kinv, const double *R, const double *origins, int n_cams,
+                            int center_cam, const int *view_cam, int min_views, double *X_out, double *lam_min_out, int *n_rays_out,
+                            int device);
+int apap_triangulate_tracks_device(apap_ctx *ctx, const int *d_table, const float *d_track_pts, const int *d_n_tracks, int max_tracks,
+                                   int n_views, const float *d_dst_pts, const int *dst_offset, const double *d_Kinv, const double *d_R,
+                                   const double *d_origins, int n_cams, int center_cam, const int *view_cam, int min_views, double *d_X,
+                                   double *d_lam_min, int *d_n_rays, void *stream);
+
 /* ------------------------------------------------- spectral match weighting --- */
 /* calculate_M of spectral_method.py:66-133, the step every shell driver of the reference runs:
  *     M_ii = match_score_i + epi_weight / (1 + |dst_i^T F src_i|)                              (:104-114)
