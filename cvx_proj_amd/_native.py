@@ -299,6 +299,23 @@ SIGNATURES.update({
                                                  _i32p, C.c_int, _vp, _vp, _vp, _vp]),
 })
 
+# dark-channel dehazing (apap_dehaze.hip)
+_u16p = C.POINTER(C.c_uint16)
+SIGNATURES.update({
+    "apap_dehaze_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "apap_dark_channel": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, C.c_int]),
+    "apap_dark_channel_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "apap_atmospheric_light": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, C.c_int]),
+    "apap_atmospheric_light_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "apap_transmission": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _u16p, C.c_int]),
+    "apap_transmission_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp,
+                                           C.c_size_t, _vp]),
+    "apap_dehaze": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, _u16p, _u8p,
+                              C.c_int]),
+    "apap_dehaze_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp,
+                                     _vp, C.c_size_t, _vp]),
+})
+
 _lib = None
 _torch_at_load = False      # was torch in the process when the library was loaded?  (cvx_proj_amd.resident refuses otherwise)
 
@@ -946,6 +963,60 @@ def triangulate_tracks(table, track_pts, dst_pts, K_inv, Rs, origins, center_cam
     check(lib().apap_triangulate_tracks(_h(ctx), _ip(tb), _ptr(tp, C.c_float), T, V, _ptr(flat, C.c_float), _ip(off), _dp(K), _dp(R),
                                         _dp(o), len(R), int(center_cam), _ip(cam), int(min_views), _dp(X), _dp(lam), _ip(n), device))
     return X, lam, n
+
+
+DEHAZE_MAX_RADIUS = 32                       # APAP_DEHAZE_MAX_RADIUS: of the minimum's window and of the guided filter's
+DEHAZE_ONE = 4096                            # the transmission's unit: 12 fractional bits
+# the kernels' tile sides (rows, cols) and the pixels a block of the selection scans at a time: APAP_DEHAZE_*_TILE_*, _AIR_CHUNK
+DEHAZE_TILES = {"min": (16, 128), "ab": (16, 64), "recover": (16, 64)}
+DEHAZE_AIR_CHUNK = 1024
+DEHAZE_MAX_IMAGES = 65535
+
+
+def _pictures(imgs, who):
+    """``imgs`` as contiguous uint8 (n, h, w, c), c = 1 or 3."""
+    a = np.ascontiguousarray(imgs, dtype=np.uint8)
+    if a.ndim != 4 or a.size == 0 or a.shape[3] not in (1, 3):
+        raise ValueError(f"{who}: (n, h, w, 1) or (n, h, w, 3) uint8 pictures expected; got {a.shape}")
+    return a
+
+
+def dark_channel(imgs, radius=7, device=-1, ctx=None):
+    """``apap_dark_channel``: (n, h, w) uint8, the window minimum of the channel minimum of (n, h, w, c) pictures."""
+    a = _pictures(imgs, "dark_channel")
+    out = np.empty(a.shape[:3], dtype=np.uint8)
+    check(lib().apap_dark_channel(_h(ctx), _ptr(a, C.c_uint8), a.shape[0], a.shape[1], a.shape[2], a.shape[3], int(radius),
+                                  _ptr(out, C.c_uint8), device))
+    return out
+
+
+def atmospheric_light(imgs, radius=7, device=-1, ctx=None):
+    """``apap_atmospheric_light``: (n, c) uint8, the atmospheric light of each of (n, h, w, c) pictures."""
+    a = _pictures(imgs, "atmospheric_light")
+    out = np.empty((a.shape[0], a.shape[3]), dtype=np.uint8)
+    check(lib().apap_atmospheric_light(_h(ctx), _ptr(a, C.c_uint8), a.shape[0], a.shape[1], a.shape[2], a.shape[3], int(radius),
+                                       _ptr(out, C.c_uint8), device))
+    return out
+
+
+def transmission(imgs, radius=7, omega_q=243, t0_q=410, refine=30, eps=64, device=-1, ctx=None):
+    """``apap_transmission``: (n, h, w) uint16 with 12 fractional bits, refined by the guided filter (refine > 0) or not."""
+    a = _pictures(imgs, "transmission")
+    out = np.empty(a.shape[:3], dtype=np.uint16)
+    check(lib().apap_transmission(_h(ctx), _ptr(a, C.c_uint8), a.shape[0], a.shape[1], a.shape[2], a.shape[3], int(radius), int(omega_q),
+                                  int(t0_q), int(refine), int(eps), _ptr(out, C.c_uint16), device))
+    return out
+
+
+def dehaze(imgs, radius=7, omega_q=243, t0_q=410, refine=30, eps=64, parts=False, device=-1, ctx=None):
+    """``apap_dehaze``: the dehazed (n, h, w, c) uint8 pictures; with ``parts`` also t (n, h, w) uint16 and A (n, c) uint8."""
+    a = _pictures(imgs, "dehaze")
+    out = np.empty(a.shape, dtype=np.uint8)
+    t = np.empty(a.shape[:3], dtype=np.uint16) if parts else None
+    A = np.empty((a.shape[0], a.shape[3]), dtype=np.uint8) if parts else None
+    check(lib().apap_dehaze(_h(ctx), _ptr(a, C.c_uint8), a.shape[0], a.shape[1], a.shape[2], a.shape[3], int(radius), int(omega_q), int(t0_q),
+                            int(refine), int(eps), _ptr(out, C.c_uint8), _ptr(t, C.c_uint16), _ptr(A, C.c_uint8), device))
+    return (out, t, A) if parts else out
 
 
 WARP_GEOMETRY, WARP_CELLS, WARP_GATHER, WARP_ALL = 1, 2, 4, 7      # phases of apap_warp_batch_device

@@ -1021,6 +1021,57 @@ int apap_triangulate_tracks(apap_ctx *ctx, const int *table, const float *track_
     return call.wait();
 }
 
+// ---- dehazing (apap_dehaze.hip): one host-buffer call for its four entry points; an output that is NULL is not computed
+static int dehaze_host(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, int w, int channels, int radius, int omega_q, int t0_q,
+                       int refine, int eps, uint8_t *dark, uint8_t *A, uint16_t *t, uint8_t *J, int device, const char *who) {
+    int rc = apap::dehaze_check(n_images, h, w, channels, radius, omega_q, t0_q, refine, eps, who);
+    if (rc) return rc;
+    if (!imgs || !(dark || A || t || J)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    const size_t N = (size_t)n_images * h * w;
+    const Part d_img = call.slot(S_IMG, N * channels);
+    Layout lay = call.layout(S_OUT);
+    const Part d_dark = lay.take(dark ? N : 0), d_A = lay.take(A ? (size_t)n_images * channels : 0), d_t = lay.take(t ? N * 2 : 0),
+               d_J = lay.take(J ? N * channels : 0);
+    call.alloc(lay);
+    const Part work = call.slot(S_WORK, apap_dehaze_workspace_bytes(n_images, h, w, channels, refine));
+    call.up(d_img, imgs);
+    if ((rc = call.rc())) return rc;
+    rc = apap::dehaze_run(d_img.as<const uint8_t>(), n_images, h, w, channels, radius, omega_q, t0_q, refine, eps,
+                          dark ? d_dark.as<uint8_t>() : nullptr, A ? d_A.as<uint8_t>() : nullptr, t ? d_t.as<uint16_t>() : nullptr,
+                          J ? d_J.as<uint8_t>() : nullptr, work.as<void>(), work.bytes, call.stream(), who);
+    if (rc) return rc;
+    if (dark) call.down(dark, d_dark);
+    if (A) call.down(A, d_A);
+    if (t) call.down(t, d_t);
+    if (J) call.down(J, d_J);
+    return call.wait();
+}
+
+int apap_dark_channel(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, int w, int channels, int radius, uint8_t *dark, int device) {
+    if (!dark) return apap::fail(APAP_ERR_INVALID_ARG, "apap_dark_channel: null argument");
+    return dehaze_host(ctx, imgs, n_images, h, w, channels, radius, 0, 1, 0, 1, dark, nullptr, nullptr, nullptr, device, "apap_dark_channel");
+}
+
+int apap_atmospheric_light(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, int w, int channels, int radius, uint8_t *A, int device) {
+    if (!A) return apap::fail(APAP_ERR_INVALID_ARG, "apap_atmospheric_light: null argument");
+    return dehaze_host(ctx, imgs, n_images, h, w, channels, radius, 0, 1, 0, 1, nullptr, A, nullptr, nullptr, device, "apap_atmospheric_light");
+}
+
+int apap_transmission(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, int w, int channels, int radius, int omega_q, int t0_q,
+                      int refine, int eps, uint16_t *t, int device) {
+    if (!t) return apap::fail(APAP_ERR_INVALID_ARG, "apap_transmission: null argument");
+    return dehaze_host(ctx, imgs, n_images, h, w, channels, radius, omega_q, t0_q, refine, eps, nullptr, nullptr, t, nullptr, device,
+                       "apap_transmission");
+}
+
+int apap_dehaze(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, int w, int channels, int radius, int omega_q, int t0_q, int refine,
+                int eps, uint8_t *out, uint16_t *t, uint8_t *A, int device) {
+    if (!out) return apap::fail(APAP_ERR_INVALID_ARG, "apap_dehaze: null argument");
+    return dehaze_host(ctx, imgs, n_images, h, w, channels, radius, omega_q, t0_q, refine, eps, nullptr, A, t, out, device, "apap_dehaze");
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ spectral weights (spectral_method.py:66-133)

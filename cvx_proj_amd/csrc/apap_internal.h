@@ -226,6 +226,11 @@ int denoise_check(int n_images, int h, int w, int channels, int spacing, int r, 
 int covis_check(const int *view_offset, int n_views, float eps, const char *who);
 int triangulate_tracks_check(int max_tracks, int n_views, const int *dst_offset, int n_cams, int center_cam, const int *view_cam,
                              int min_views, const char *who);
+// The dehazing (apap_dehaze.hip).  dehaze_check: the arguments that need no device pointer.  dehaze_run: every check, then the
+// stages that the outputs asked for (any of d_dark, d_A, d_t, d_J may be null) on `stream`; does not wait.
+int dehaze_check(int n_images, int h, int w, int channels, int radius, int omega_q, int t0_q, int refine, int eps, const char *who);
+int dehaze_run(const uint8_t *d_imgs, int n_images, int h, int w, int channels, int radius, int omega_q, int t0_q, int refine, int eps,
+               uint8_t *d_dark, uint8_t *d_A, uint16_t *d_t, uint8_t *d_J, void *d_work, size_t work_bytes, void *stream, const char *who);
 // `bytes` rounded up to the 256-byte boundary on which every part of a workspace or pooled buffer starts.
 inline size_t up256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 

@@ -835,6 +835,42 @@ def hip_box_blur(img, radius, out=None, ctx=None):
     return out
 
 
+def dehaze_workspace_bytes(n_images, h, w, channels, refine=30):
+    """Workspace of ``hip_dehaze`` (0 for invalid arguments): the counts and the winners' words, the dark channel, the raw
+    transmission (3 bytes a pixel) and, with refinement, the guided filter's coefficients (12 more)."""
+    return _native.lib().apap_dehaze_workspace_bytes(int(n_images), int(h), int(w), int(channels), int(refine))
+
+
+def hip_dehaze(imgs, radius=7, omega=0.95, t0=0.1, refine=30, eps=64, return_parts=False, out=None, work=None, ctx=None):
+    """``apap_dehaze_device`` on the current stream of the tensor's device, no host synchronisation: uint8 pictures (h, w),
+    (h, w, 3), (n, h, w, 1) or (n, h, w, 3); returns a uint8 tensor of that shape (``out`` when given: a tensor like ``imgs``, not
+    ``imgs`` itself), or with ``return_parts`` ``(J, t, A)`` with t uint16 of the pictures' (n, h, w) or (h, w) and A uint8
+    (n, channels) or (channels,).  The result is what ``hip_corner_detect``, ``hip_sift_describe``, ``hip_notch_denoise`` and
+    ``hip_panorama`` take, so a resident chain dehazes and then detects without a host trip.  Same bytes as ``dehaze.dehaze``."""
+    from .dehaze import dehaze_arguments
+    who = "hip_dehaze"
+    q = dehaze_arguments(radius, omega, t0, refine, eps, who=who)
+    _needs_device(imgs, who)
+    dev = imgs.device
+    _contiguous(((imgs, torch.uint8),), dev, who)
+    if imgs.dim() not in (2, 3, 4) or imgs.numel() == 0 or (imgs.dim() == 3 and imgs.shape[2] != 3) or (imgs.dim() == 4 and imgs.shape[3] not in (1, 3)):
+        raise ValueError(f"{who}: uint8 pictures (h, w), (h, w, 3), (n, h, w, 1) or (n, h, w, 3) expected; got {tuple(imgs.shape)}")
+    n, h, w, c = {2: (1, *imgs.shape, 1), 3: (1, *imgs.shape), 4: tuple(imgs.shape)}[imgs.dim()]
+    if out is None:
+        out = torch.empty_like(imgs)
+    elif out.dtype != torch.uint8 or out.shape != imgs.shape or not out.is_contiguous() or out.device != dev or out.data_ptr() == imgs.data_ptr():
+        raise ValueError(f"{who}: out must be another contiguous uint8 tensor of shape {tuple(imgs.shape)} on {dev}")
+    t = A = None
+    if return_parts:
+        t = torch.empty((n, h, w) if imgs.dim() == 4 else (h, w), dtype=torch.uint16, device=dev)
+        A = torch.empty((n, c) if imgs.dim() == 4 else (c,), dtype=torch.uint8, device=dev)
+    work = _scratch(work, max(dehaze_workspace_bytes(n, h, w, c, q[3]), 256), dev)
+    _native.check(_native.lib().apap_dehaze_device(
+        _native._h(ctx), imgs.data_ptr(), int(n), int(h), int(w), int(c), *q, out.data_ptr(), t.data_ptr() if return_parts else None,
+        A.data_ptr() if return_parts else None, work.data_ptr(), work.numel(), _stream(dev)))
+    return (out, t, A) if return_parts else out
+
+
 def hip_panorama(center, layers, blend="mean", out=None, status=None, ctx=None, work=None, ramp=32, sampling=None, gain=None,
                  gain_step=4, sigma_n=10.0, sigma_g=0.1, return_gains=False, band=8):
     """``apap_panorama_device`` (``blend="ramp"``: ``apap_panorama_ramp_device`` with the ramp width ``ramp``, an integer 1 ..

@@ -630,6 +630,54 @@ int apap_triangulate_tracks_device(apap_ctx *ctx, const int *d_table, const floa
                                    const double *d_origins, int n_cams, int center_cam, const int *view_cam, int min_views, double *d_X,
                                    double *d_lam_min, int *d_n_rays, void *stream);
 
+/* ------------------------------------------------- dark-channel dehazing with guided refinement --- */
+/* Single-picture dehazing by the dark channel prior (He, Sun, Tang, CVPR 2009) with the guided filter (ECCV 2010) refining
+ * the transmission, in exact integers; tests/dehaze_spec.py is the specification, byte for byte.  A picture I is uint8, h x w
+ * with 1 (grey) or 3 (BGR) interleaved channels, h, w >= 1, N = h w < 2^31.  Every window is (2 r + 1)^2 with the border
+ * replicated; every division is a floor division.
+ *     D = window min (radius) of m = min_c I_c                                                   the dark channel, uint8
+ *     k = max(1, N / 1000); T = the largest level v with #{D >= v} >= k; among ALL pixels with D >= T the one with the
+ *         largest I_0 + I_1 + I_2, the lowest index among equals, gives A; each channel raised to at least 1
+ *     n = min(4096, min_c (4096 I_c) / A_c); Dn = window min (radius) of n; p = 4096 - ((omega_q Dn + 128) >> 8)
+ *     refine = rho > 0, W = (2 rho + 1)^2, S the box sum of radius rho, G = the grey value of apap_corner_detect:
+ *         covN = W S(G p) - S(G) S(p); varN = W S(G G) - S(G)^2; a_q = (4096 covN) / (varN + eps W^2)
+ *         b_q = 4096 S(p) - a_q S(G); t = (S(a_q) G W + S(b_q)) / (4096 W^2)            all in int64; rho = 0: t = p
+ *     t = clip(t, t0_q, 4096), uint16 with 12 fractional bits
+ *     J_c = clip(A_c + (8192 (I_c - A_c) + t) / (2 t), 0, 255)                  round-half-up of A + (I - A) / t
+ * radius, refine 0 .. APAP_DEHAZE_MAX_RADIUS; omega_q = rint(256 omega), 0 .. 256; t0_q = max(1, rint(4096 t0)), 1 .. 4096;
+ * eps 1 .. 65535 in grey levels squared.  All pictures of a call (1 .. 65535, one shape) share the launches: five, or four
+ * without refinement.  The histogram and the selection use integer atomics only: no result depends on a launch or an order.
+ * The resident forms take one workspace (256-byte aligned, apap_dehaze_workspace_bytes with the call's refine, or 0 where the
+ * entry point has none; contents do not matter, no contract between calls).  No CPU path: ERR_NO_DEVICE without a device.
+ * The tile sides of the kernels (tests place pictures at one less, equal and one more): */
+#define APAP_DEHAZE_MAX_RADIUS 32
+#define APAP_DEHAZE_MIN_TILE_ROWS 16
+#define APAP_DEHAZE_MIN_TILE_COLS 128
+#define APAP_DEHAZE_AB_TILE_ROWS 16
+#define APAP_DEHAZE_AB_TILE_COLS 64
+#define APAP_DEHAZE_REC_TILE_ROWS 16
+#define APAP_DEHAZE_REC_TILE_COLS 64
+#define APAP_DEHAZE_AIR_CHUNK 1024
+size_t apap_dehaze_workspace_bytes(int n_images, int h, int w, int channels, int refine);
+/* dark: n_images x h x w uint8. */
+int apap_dark_channel(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, int w, int channels, int radius, uint8_t *dark, int device);
+int apap_dark_channel_device(apap_ctx *ctx, const uint8_t *d_imgs, int n_images, int h, int w, int channels, int radius, uint8_t *d_dark,
+                             void *d_work, size_t work_bytes, void *stream);
+/* A: n_images x channels uint8. */
+int apap_atmospheric_light(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, int w, int channels, int radius, uint8_t *A, int device);
+int apap_atmospheric_light_device(apap_ctx *ctx, const uint8_t *d_imgs, int n_images, int h, int w, int channels, int radius, uint8_t *d_A,
+                                  void *d_work, size_t work_bytes, void *stream);
+/* t: n_images x h x w uint16, refined (refine > 0) or not, clipped. */
+int apap_transmission(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, int w, int channels, int radius, int omega_q, int t0_q,
+                      int refine, int eps, uint16_t *t, int device);
+int apap_transmission_device(apap_ctx *ctx, const uint8_t *d_imgs, int n_images, int h, int w, int channels, int radius, int omega_q, int t0_q,
+                             int refine, int eps, uint16_t *d_t, void *d_work, size_t work_bytes, void *stream);
+/* out: the pictures' layout, uint8 (what apap_corner_detect reads).  t and A as above where the pointer is not NULL. */
+int apap_dehaze(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, int w, int channels, int radius, int omega_q, int t0_q, int refine,
+                int eps, uint8_t *out, uint16_t *t, uint8_t *A, int device);
+int apap_dehaze_device(apap_ctx *ctx, const uint8_t *d_imgs, int n_images, int h, int w, int channels, int radius, int omega_q, int t0_q,
+                       int refine, int eps, uint8_t *d_out, uint16_t *d_t, uint8_t *d_A, void *d_work, size_t work_bytes, void *stream);
+
 /* ------------------------------------------------- spectral match weighting --- */
 /* calculate_M of spectral_method.py:66-133, the step every shell driver of the reference runs:
  *     M_ii = match_score_i + epi_weight / (1 + |dst_i^T F src_i|)                              (:104-114)
