@@ -970,6 +970,7 @@ DEHAZE_ONE = 4096                            # the transmission's unit: 12 fract
 # the kernels' tile sides (rows, cols) and the pixels a block of the selection scans at a time: APAP_DEHAZE_*_TILE_*, _AIR_CHUNK
 DEHAZE_TILES = {"min": (16, 128), "ab": (16, 64), "recover": (16, 64)}
 DEHAZE_AIR_CHUNK = 1024
+DEHAZE_AIR_MAX_BLOCKS = 1024                 # APAP_DEHAZE_AIR_MAX_BLOCKS: the selection's grid; a larger picture takes passes
 DEHAZE_MAX_IMAGES = 65535
 
 

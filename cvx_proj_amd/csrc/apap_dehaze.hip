@@ -33,7 +33,7 @@ constexpr int kAbRows = APAP_DEHAZE_AB_TILE_ROWS, kAbCols = APAP_DEHAZE_AB_TILE_
 constexpr int kRecRows = APAP_DEHAZE_REC_TILE_ROWS, kRecCols = APAP_DEHAZE_REC_TILE_COLS;   // D5
 constexpr int kRun = 4;                                       // outputs of one running sum
 constexpr int kAirChunk = APAP_DEHAZE_AIR_CHUNK;              // consecutive pixels a block of D2 scans at a time
-constexpr int kAirMaxBlocks = 1024;
+constexpr int kAirMaxBlocks = APAP_DEHAZE_AIR_MAX_BLOCKS;    // of D2's grid: a larger picture is scanned in passes
 constexpr int kOne = 4096;                                    // 12 fractional bits
 static_assert(kMinRows * kMinCols % kThreads == 0 && kAbRows * kAbCols == kRun * kThreads && kRecRows * kRecCols == kRun * kThreads, "tiles");
 static_assert(kAbCols % kRun == 0 && kRecCols % kRun == 0 && kRecRows % kRun == 0, "runs");

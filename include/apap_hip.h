@@ -658,6 +658,8 @@ int apap_triangulate_tracks_device(apap_ctx *ctx, const int *d_table, const floa
 #define APAP_DEHAZE_REC_TILE_ROWS 16
 #define APAP_DEHAZE_REC_TILE_COLS 64
 #define APAP_DEHAZE_AIR_CHUNK 1024
+/* the selection's grid is at most this many blocks: a picture of more than AIR_MAX_BLOCKS x AIR_CHUNK pixels takes them in passes */
+#define APAP_DEHAZE_AIR_MAX_BLOCKS 1024
 size_t apap_dehaze_workspace_bytes(int n_images, int h, int w, int channels, int refine);
 /* dark: n_images x h x w uint8. */
 int apap_dark_channel(apap_ctx *ctx, const uint8_t *imgs, int n_images, int h, int w, int channels, int radius, uint8_t *dark, int device);

@@ -10,6 +10,9 @@ from cvx_proj_amd import _native      # its constants need neither the library n
 # the kernels' tile sides and the pixels a block of the selection scans at a time (include/apap_hip.h): the cases follow them
 TILES = dict(_native.DEHAZE_TILES)
 AIR_CHUNK = _native.DEHAZE_AIR_CHUNK
+AIR_MAX_BLOCKS = _native.DEHAZE_AIR_MAX_BLOCKS
+AIR_PASS = AIR_MAX_BLOCKS * AIR_CHUNK         # pixels the selection's whole grid scans at a time: a larger picture takes passes
+AIR_PASSES_SHAPE = (1027, 1025)               # 1 052 675 pixels: a second pass of five chunks, the last one of three pixels
 
 DEFAULTS = dict(radius=7, omega_q=243, t0_q=410, refine=30, eps=64)
 
@@ -69,6 +72,27 @@ def _two_best(h, w):
     return img
 
 
+def air_place(i, n_pixels):
+    """(block, pass, pixels of its chunk) of pixel ``i`` in the selection's scan of ``n_pixels`` pixels: block b takes the
+    chunks b, b + grid, b + 2 grid, ... of AIR_CHUNK consecutive pixels, grid = min(chunks, AIR_MAX_BLOCKS)."""
+    chunks = (n_pixels + AIR_CHUNK - 1) // AIR_CHUNK
+    grid = min(chunks, AIR_MAX_BLOCKS)
+    chunk = i // AIR_CHUNK
+    return chunk % grid, chunk // grid, min(AIR_CHUNK, n_pixels - chunk * AIR_CHUNK)
+
+
+AIR_TIES_AT = (7, AIR_PASS + 7, AIR_PASS + AIR_CHUNK + 3)      # block 0's first pass, block 0's second, block 1's second
+
+
+def _marked(h, w, seed, marks):
+    """A dim background (channels 10 .. 109) with the pixels of ``marks`` (flat index -> colour) far brighter."""
+    img = (picture(h, w, seed, 3) % 100 + 10).astype(np.uint8)
+    flat = img.reshape(-1, 3)
+    for at, colour in marks.items():
+        flat[at] = colour
+    return img
+
+
 def _floor_clips(h, w):
     """A bright plain with single pixels darker and (in two channels) brighter than A: the refinement, close to a box mean under
     the largest eps, holds t on the floor at them, and the recovery leaves 0 .. 255 on both sides."""
@@ -106,6 +130,12 @@ def cases():
         "air_constant": (_constant(70, 70, (100, 150, 200)), P(radius=3, refine=4)),
         "air_two_best": (_two_best(40, 40), P(radius=0, refine=0)),
         "air_black": (np.zeros((33, 35, 3), np.uint8), P(radius=2, refine=2)),
+        # more pixels than the selection's grid scans at once: the only bright pixel is the last one, in the second pass's
+        # partial chunk; and three equally bright ones in different passes and blocks, the first of which must win
+        "air_second_pass": (_marked(*AIR_PASSES_SHAPE, 19, {AIR_PASSES_SHAPE[0] * AIR_PASSES_SHAPE[1] - 1: (250, 252, 255)}),
+                            P(radius=0, refine=1)),
+        "air_ties_across_passes": (_marked(*AIR_PASSES_SHAPE, 20, dict(zip(AIR_TIES_AT, ((250, 240, 230), (230, 240, 250), (240, 240, 240))))),
+                                   P(radius=0, refine=0)),
         # transmission
         "cap_grey": (picture(45, 47, 12), P(radius=1, refine=2)),
         "cap_bgr": (picture(45, 47, 13, 3), P(radius=3, refine=2)),

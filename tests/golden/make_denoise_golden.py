@@ -7,8 +7,10 @@ It imports the reference's ``median_filter.py`` in place (nothing is copied) beh
 stubs - the module only names them - and runs its ``median_filter`` over the schedule of ``apply_median_filter`` (:143-155,
 with each case's r, spacing and sn: the list ``denoise_spec.notch_schedule`` gives, which the fixture's
 ``schedule_default`` - recorded from the reference's own ``apply_median_filter`` - pins) on the seeded complex128 spectra of tests/denoise_cases.py.  No transform is involved, so
-numpy's FFT dtype cannot enter.  For the small cases the fixture stores the positions the reference changed and their new
-values; for 768 x 768 with the defaults the SHA-256 of the result and the medians of its discs.
+numpy's FFT dtype cannot enter.  For the cases marked "points" the fixture stores the positions the reference changed and their
+new values; for those marked "digest" (768 x 768 with the defaults, and r = 6, whose written discs would take 90 KB as
+positions) the SHA-256 of the result and the medians of its discs.  Entries the committed fixture already holds must come out
+bit for bit as they are: the generator asserts it before it writes.
 
 It also runs the reference's whole ``apply_median_filter`` (equalisation stubbed by the oracle's) once on a seeded picture and
 prints its distance from tests/denoise_spec.py: under a numpy whose ``fft2`` keeps float32 input in complex64 that distance is
@@ -90,6 +92,12 @@ def main():
             out[f"{name}_sha256"] = np.frombuffer(hashlib.sha256(np.ascontiguousarray(got).tobytes()).digest(), np.uint8)
             out[f"{name}_medians"] = np.array([t["median"] for t in trace if t["n"]], np.complex128)
     path = os.path.join(HERE, "denoise_notch_ref.npz")
+    if os.path.exists(path):    # a new case adds entries; what the fixture held before stays, bit for bit
+        with np.load(path) as before:
+            for key in before.files:
+                assert key in out and out[key].dtype == before[key].dtype and out[key].shape == before[key].shape \
+                    and out[key].tobytes() == before[key].tobytes(), f"{key} differs from the committed fixture"
+            print("the", len(before.files), "entries of the fixture as it was are unchanged;", len(out) - len(before.files), "added")
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path), "bytes")
     # the reference's whole chain under the installed numpy, for DESIGN.md

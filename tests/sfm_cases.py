@@ -83,6 +83,32 @@ def chain_views(length):
     return [_view([(500.0, 500.0)], 7), (pts, np.arange(length, dtype=np.int32))]
 
 
+def interlocked_views(far=1500, length=1100, spaced=False):
+    """Three views.  View 0: ``far`` points far from the rest (so the later views do not start at a round position).  Views 1
+    and 2: chains of ``length`` points 0.09 px apart on one row, the second chain half a step beside the first - point k of
+    view 2 has points k and k + 1 of view 1 and its own predecessor in its box, in that order, and only every second point of
+    view 1 founds a track: for odd k the walk passes a decided observation that founded nothing and goes on behind it.
+    With ``spaced`` a far-away point (each founds a track of its own) follows every point of view 1's chain, so that the next
+    in-box observation is not the next position."""
+    k = np.arange(length)
+    row = np.full(length, 5.0, F32)
+    chain1 = np.stack([(10.0 + 0.09 * k).astype(F32), row], axis=1)
+    chain2 = np.stack([(10.045 + 0.09 * k).astype(F32), row], axis=1)
+    away = np.stack([(1000.0 + 3.0 * np.arange(far)).astype(F32), np.full(far, 900.0, F32)], axis=1)
+    if spaced:
+        between = np.stack([(1000.0 + 3.0 * k).astype(F32), np.full(length, 1800.0, F32)], axis=1)
+        chain1 = np.stack([chain1, between], axis=1).reshape(-1, 2)
+    return [(away, np.arange(far, dtype=np.int32)), (chain1, 10000 + np.arange(len(chain1), dtype=np.int32)),
+            (chain2, 20000 + np.arange(length, dtype=np.int32))]
+
+
+# The resolver (csrc/apap_sfm.hip, k_covis_resolve) is one workgroup of this many threads; thread t owns the observations
+# n0 + t, n0 + t + RESOLVE_THREADS, ...  The cases below give a thread several links of one chain.
+RESOLVE_THREADS = 1024
+LONG_CHAIN = 2200                    # chain_views(LONG_CHAIN): three links of one chain per thread
+LARGE_RANDOM = dict(n_total=12000, n_views=8, seed=9)
+
+
 # ------------------------------------------------------------------ triangulation
 def rotation(q):
     """The rotation of a quaternion (w, x, y, z), not normalised: + - * / only."""

@@ -31,6 +31,9 @@ def test_the_cases_follow_the_kernels_tiles(native):
     assert {"min": (value("MIN_TILE_ROWS"), value("MIN_TILE_COLS")), "ab": (value("AB_TILE_ROWS"), value("AB_TILE_COLS")),
             "recover": (value("REC_TILE_ROWS"), value("REC_TILE_COLS"))} == native.DEHAZE_TILES
     assert value("AIR_CHUNK") == native.DEHAZE_AIR_CHUNK and value("MAX_RADIUS") == native.DEHAZE_MAX_RADIUS == S.MAX_RADIUS == S.MAX_REFINE
+    assert value("AIR_MAX_BLOCKS") == native.DEHAZE_AIR_MAX_BLOCKS == C.AIR_MAX_BLOCKS and C.AIR_PASS == C.AIR_MAX_BLOCKS * C.AIR_CHUNK
+    source = open(os.path.join(os.path.dirname(native.__file__), "csrc", "apap_dehaze.hip")).read()
+    assert "kAirMaxBlocks = APAP_DEHAZE_AIR_MAX_BLOCKS;" in source and "kAirChunk = APAP_DEHAZE_AIR_CHUNK;" in source     # the kernel's own
     assert native.DEHAZE_ONE == S.ONE
 
 
@@ -70,6 +73,41 @@ def test_airlight_cases():
     assert (sums[1:-1][c["D"].ravel()[1:-1] >= c["kT"][1]] < first.sum()).all() and (c["A"] == img[0, 0]).all()
     c = terms("air_black")
     assert not c["img"].any() and (c["A"] == 1).all()
+
+
+def test_airlight_cases_beyond_one_pass_of_the_grid():
+    """The selection runs min(chunks, AIR_MAX_BLOCKS) blocks; block b scans the chunks b, b + grid, ...  Both cases have more
+    pixels than one pass of the whole grid takes, and their marked pixels are the only ones that can win."""
+    h, w = C.AIR_PASSES_SHAPE
+    N = h * w
+    assert N > C.AIR_MAX_BLOCKS * C.AIR_CHUNK == C.AIR_PASS and N % C.AIR_CHUNK != 0 and N < 2 * C.AIR_PASS
+    last_block = C.air_place(N - 1, N)[0]
+
+    def candidates(c, marked):
+        """The marked pixels are candidates (D >= T); every other candidate's sum is smaller than theirs."""
+        flat = c["img"].reshape(-1, 3).astype(int)
+        D, T = c["D"].ravel(), c["kT"][1]
+        sums = flat.sum(axis=1)
+        assert c["img"].shape == (h, w, 3) and c["p"]["radius"] == 0 and (D[list(marked)] >= T).all()
+        others = np.ones(N, bool)
+        others[list(marked)] = False
+        assert len({int(sums[m]) for m in marked}) == 1 and (sums[others & (D >= T)] < sums[marked[0]]).all()
+        assert (others & (D >= T)).sum() >= c["kT"][0]          # and there are such: T lies among the background's levels
+        return flat
+
+    c = terms("air_second_pass")
+    flat = candidates(c, [N - 1])
+    block, turn, chunk = C.air_place(N - 1, N)
+    assert turn == 1 and chunk < C.AIR_CHUNK and block == last_block > 0 and c["p"]["refine"] == 1       # the second pass's partial chunk
+    assert (c["A"] == flat[N - 1]).all() and (flat[:C.AIR_PASS] < c["A"].astype(int)).all()     # no pixel of the first pass comes near
+
+    c = terms("air_ties_across_passes")
+    at = list(C.AIR_TIES_AT)
+    flat = candidates(c, at)
+    assert at == [7, 2 ** 20 + 7, 2 ** 20 + 1024 + 3] or (C.AIR_CHUNK, C.AIR_MAX_BLOCKS) != (1024, 1024)
+    assert [C.air_place(i, N)[:2] for i in at] == [(0, 0), (0, 1), (1, 1)] and c["p"]["refine"] == 0
+    assert len({tuple(flat[i]) for i in at}) == 3 and all((flat[at[0]] != flat[i]).any() for i in at[1:])      # unlike colours
+    assert (c["A"] == flat[at[0]]).all()                      # the lowest index among equals, whatever the launch
 
 
 def test_transmission_cases():

@@ -391,6 +391,26 @@ def test_solve_leaves_cells_warp_ready(native, cfg, batch):
     assert torch.equal(a.gather(imgs.flip(0).contiguous()).flip(0), out_a) and torch.equal(H_a2.view(batch, -1, 9).flip(0), H_a.view(batch, -1, 9))
 
 
+def warp_stamps(mesh_rows, mesh_cols, final_w, final_h):
+    """warp_stamp (csrc/apap_warp_dev.h: the word behind the lut) and warp_stamp16 (csrc/apap_kernels.hip: the high half of every
+    row entry of the fast tables), restated."""
+    s = (((mesh_rows * 0x9E3779B1) ^ (mesh_cols * 0x85EBCA77) ^ (final_w * 0xC2B2AE3D) ^ (final_h * 0x27D4EB2F)) & 0xFFFFFFFF) | 1
+    return s, ((s >> 12) & 0xFFFF) | 1
+
+
+def unstamped_garbage(nbytes, stamps, seed):
+    """``nbytes`` seeded random bytes in which no aligned 32-bit word is the stamp or carries the 16-bit stamp in its high half.
+    The strip kernel trusts a row entry whose high half is the stamp - 15 free bits - so unseeded garbage held such a word for
+    one wave in about twenty runs of the test below, and that wave then took the entry's low half for a cell row: a read far
+    outside the per-cell records.  Garbage that happens to carry the valid stamp is not an unprepared workspace."""
+    stamp32, stamp16 = stamps
+    g = np.random.default_rng(seed).integers(0, 256, nbytes, dtype=np.uint8)
+    words = g[:nbytes // 4 * 4].view(np.uint32)
+    words[((words >> 16) == stamp16) | (words == stamp32)] ^= np.uint32(0x00020000)
+    assert not (((words >> 16) == stamp16) | (words == stamp32)).any()
+    return g
+
+
 def test_gather_on_an_unprepared_workspace_reports_and_touches_nothing(native):
     """A gather on a workspace whose lookup tables were never built (zeroed or full of garbage), or were built for another mesh
     shape or canvas size, must not use the tables' values as indices: the canvas stays untouched and bit 2 of the status word is
@@ -412,6 +432,11 @@ def test_gather_on_an_unprepared_workspace_reports_and_touches_nothing(native):
             plan = D.WarpPlan(p.mesh, (rows, cols), p.final_w, p.final_h, p.off_x, p.off_y, dev, ctx=ctx)
             plan.cells(Hd)
             good = plan.work.clone()
+            # the stamps as the prepared tables carry them: the word behind the lut, and one row entry per canvas row
+            stamps = warp_stamps(rows, cols, p.final_w, p.final_h)
+            words = good.cpu().numpy()[:good.numel() // 4 * 4].view(np.uint32)
+            assert (words == stamps[0]).any()
+            assert opts.get("warp_rows", 1) < 2 or int(((words >> 16) == stamps[1]).sum()) >= p.final_h     # the strip kernel's forms
             out = torch.full((1, p.final_h, p.final_w, 3), 7, dtype=torch.uint8, device=dev)
             plan.gather(img, out=out)
             assert int(plan.status.cpu()[0]) == 0 and np.array_equal(out[0].cpu().numpy(), ref), opts
@@ -419,7 +444,7 @@ def test_gather_on_an_unprepared_workspace_reports_and_touches_nothing(native):
                 if what == "zeros":
                     plan.work.zero_()
                 elif what == "garbage":
-                    plan.work.copy_(torch.randint(0, 256, plan.work.shape, dtype=torch.uint8, device=dev))
+                    plan.work.copy_(torch.from_numpy(unstamped_garbage(plan.work.numel(), stamps, seed=len(opts) + sum(opts.values()))).to(dev))
                 else:
                     plan.work.copy_(good)
                 if what == "other canvas":        # tables of a canvas one row shorter, in the same (large enough) workspace

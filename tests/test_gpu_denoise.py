@@ -1,6 +1,8 @@
 """The notch-denoising kernels (csrc/apap_denoise.hip) on the MI355X against tests/denoise_spec.py, byte for byte: the
-transform in both directions at every radix mix, at the longest rows and columns and with a partial column strip; the notch
-step on the spectra that tests/golden/denoise_notch_ref.npz pins against the reference; the whole chain in float64 and uint8;
+transform in both directions at every radix mix, at the longest rows and columns, with partial column strips and strips of 13, 7
+and 5 columns; the notch step on the spectra that tests/golden/denoise_notch_ref.npz pins against the reference, the largest
+disc (r = 6) and a schedule longer than the launch keeps among them; the whole chain in float64 and uint8, tall planes in a
+batch, four channels, pictures whose discs are all ties;
 and the contracts - guard bytes around every output, a workspace whose prior contents do not matter, pooled buffers reused."""
 import numpy as np
 import pytest
@@ -52,6 +54,9 @@ def same(a, b):
 # above 1024 rows the planes are turned through 32 x 32 tiles: whole and partial tiles in both directions
 FFT_SHAPES = [(2, 2), (3, 5), (4, 4), (8, 2), (27, 25), (30, 32), (81, 64), (125, 128), (120, 144), (2, 4096), (4096, 2), (4, 3840),
               (2160, 4), (32, 20), (1024, 6), (2048, 3), (2160, 20), (1080, 32), (1125, 45), (1280, 64)]
+# column strips of 13, 7 and 5 columns; the column pass's first launch of 1024 threads; the longest lengths with the most
+# radix-3 and radix-5 stages (tests/denoise_cases.py; tests/test_denoise_spec.py asserts that they are that)
+FFT_SHAPES += list(C.FFT_STRIP_SHAPES) + [C.FFT_THRESHOLD_SHAPE] + list(C.FFT_LONG_SHAPES)
 
 
 @pytest.mark.parametrize("shape", FFT_SHAPES)
@@ -66,7 +71,7 @@ def test_fft2_both_directions(native_gpu, shape):
 def test_fft2_planes_and_resident_form(native_gpu):
     import torch
     from cvx_proj_amd import resident
-    for shape in ((27, 25), (120, 144), (1024, 6), (1080, 36)):
+    for shape in ((27, 25), (120, 144), (1024, 6), (1080, 36), (300, 27)):
         x = np.stack([C.spectrum(*shape, seed=60 + k) for k in range(3)])
         f = native_gpu.fft2(x)
         for k in range(3):
@@ -83,6 +88,9 @@ def test_fft2_planes_and_resident_form(native_gpu):
             assert same(resident.hip_fft2(d_x, inverse=inverse).cpu().numpy(), native_gpu.fft2(x, inverse=inverse))
         d_x = torch.from_numpy(x[0].copy()).to(device())
         assert resident.hip_fft2(d_x, out=d_x) is d_x and same(d_x.cpu().numpy(), f[0])       # in place
+        # ... and back in place: by strips of 16, 4 and 13 columns, and (1080 rows) through the turned copy
+        assert resident.hip_fft2(d_x, inverse=True, out=d_x) is d_x
+        assert same(d_x.cpu().numpy(), S.fft2_spec(f[0], S.twiddles(shape[0]), S.twiddles(shape[1]), inverse=True))
 
 
 @pytest.mark.parametrize("name", list(C.NOTCH_CASES))
@@ -111,7 +119,7 @@ def test_notch_spectrum(native_gpu, name, golden):
 # h, w, channels, spacing, r, sn, equalize
 DENOISE_CASES = [(120, 144, 0, 9, 1, 9, True), (90, 100, 0, 14, 2, 9, True), (27, 25, 0, 9, 1, 3, True), (150, 160, 3, 14, 2, 9, True),
                  (768, 768, 0, 48, 5, 9, True), (120, 144, 0, 9, 1, 9, False), (90, 100, 2, 14, 2, 9, False), (75, 81, 0, 9, 1, 5, True),
-                 (1080, 96, 2, 14, 2, 9, True), (1200, 50, 0, 9, 1, 9, False)]
+                 (1080, 96, 2, 14, 2, 9, True), (1200, 50, 0, 9, 1, 9, False)] + C.CHAIN_EDGE_CASES
 
 
 @pytest.mark.parametrize("h,w,channels,spacing,r,sn,equalize", DENOISE_CASES)
@@ -142,6 +150,29 @@ def test_batch_and_reference_signature(native_gpu):
     assert same(eq, st["equalized"]) and same(new, st["out"])
     assert same(log0, np.log(1 + np.sqrt(st["spectrum"].real ** 2 + st["spectrum"].imag ** 2)))
     assert same(log1, np.log(1 + np.sqrt(st["filtered"].real ** 2 + st["filtered"].imag ** 2)))
+
+
+def test_a_batch_of_tall_pictures(native_gpu):
+    """Two pictures of two channels and 1080 rows: four planes through the turned copy and the notch on it in one call."""
+    from cvx_proj_amd import denoise
+    b = C.TALL_BATCH
+    pics = np.stack([C.picture(b["h"], b["w"], seed=84 + k, channels=b["channels"]) for k in range(b["count"])])
+    p = dict(spacing=b["spacing"], r=b["r"], sn=b["sn"])
+    got = denoise.notch_denoise_batch(pics, **p)
+    for k in range(b["count"]):
+        assert same(got[k], denoise.notch_denoise(pics[k], **p)) and same(got[k], S.denoise_spec(pics[k], **p))
+
+
+@pytest.mark.parametrize("name", list(C.tie_pictures()))
+@pytest.mark.parametrize("equalize", [True, False])
+def test_pictures_whose_discs_are_all_ties(native_gpu, name, equalize):
+    from cvx_proj_amd import denoise
+    pic = C.tie_pictures()[name]
+    want = S.denoise_spec(pic, equalize=equalize, **C.TIE_PARAMS)
+    assert same(denoise.notch_denoise(pic, equalize=equalize, **C.TIE_PARAMS), want)
+    assert same(denoise.notch_denoise(pic, equalize=equalize, out="uint8", **C.TIE_PARAMS), S.to_uint8(want))
+    if name == "constant_30x32":
+        assert (want == 100.0).all()
 
 
 @pytest.mark.parametrize("out", ["float64", "uint8"])

@@ -1,6 +1,7 @@
 """The co-visibility and triangulation kernels (csrc/apap_sfm.hip) on the MI355X against tests/sfm_spec.py, bit for bit: the
 tracks (table, track_pts, point_track, T) on every case of tests/sfm_cases.py and on seeded inputs at the scan's tile and
-block edges, with eight views, with every point identical and with a chain longer than a block; the positions (X, lam_min,
+block edges, with eight views, with every point identical, with a chain longer than a block, with chains that give a thread of
+the resolver several links and make its walk go on behind a joiner, and on 12 000 observations; the positions (X, lam_min,
 n_rays) at the launch's block edges, for every ray count 2 .. 9, where the clamp fires, below min_views and with a NaN
 pixel; and the contracts - guard bytes around every output, a workspace whose prior contents do not matter, rows behind T
 untouched, resident forms that give the host forms' bytes."""
@@ -125,6 +126,25 @@ def test_tracks_of_a_chain_longer_than_a_block(native_gpu):
     views = C.chain_views(300)
     table, _, _ = check_tracks(native_gpu, views)
     assert len(table) == 1 + 150          # every second point of the chain opens a track
+
+
+def test_tracks_of_a_chain_with_three_links_per_resolver_thread(native_gpu):
+    table, _, _ = check_tracks(native_gpu, C.chain_views(C.LONG_CHAIN))
+    assert len(table) == 1101
+
+
+@pytest.mark.parametrize("spaced", [False, True])
+def test_tracks_of_interlocked_chains(native_gpu, spaced):
+    """Chains longer than the resolver's workgroup in two views, the second's points between the first's: every second walk
+    passes an observation that joined another track and goes on behind it (tests/test_sfm_inputs.py asserts that).  With
+    ``spaced`` the position behind the joiner holds a far-away founder, not the next in-box observation."""
+    table, _, _ = check_tracks(native_gpu, C.interlocked_views(spaced=spaced))
+    assert len(table) == (3151 if spaced else 2051)
+
+
+def test_tracks_of_twelve_thousand_observations(native_gpu):
+    table, _, _ = check_tracks(native_gpu, C.random_views(**C.LARGE_RANDOM))
+    assert len(table) == 4806 and int(((table >= 0).sum(1) > 1).sum()) == 3445
 
 
 # ------------------------------------------------------------------ triangulation
