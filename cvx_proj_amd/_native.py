@@ -1189,7 +1189,8 @@ def spectral_affinity(src, dst, c_feats, o_feats, F, params=None, device=-1, ctx
 
 
 # ---------------------------------------------------------------- M-step and EM loop (spectral_method.py:165-241)
-MODEL_LMS, MODEL_SDP = 0, 1
+MODEL_LMS, MODEL_SDP, MODEL_HUBER = 0, 1, 2      # HUBER: M in the du slot (APAP_MODEL_HUBER_M), n <= 2^20
+MODEL_HUBER_THREADS = 256                        # APAP_MODEL_HUBER_THREADS
 MODEL_PARAMS = 6
 MODEL_INFO = 24
 MODEL_INFO_OBJECTIVE, MODEL_INFO_R, MODEL_INFO_T, MODEL_INFO_GAP, MODEL_INFO_ITERS, MODEL_INFO_STATUS, MODEL_INFO_COUNT = range(7)
@@ -1198,7 +1199,8 @@ MODEL_FLOOR = 1e-3      # model_solve: `if w <= 1e-3: continue`
 
 
 def model_params(mode, du=1.0, dv=1.0, floor=MODEL_FLOOR, swap=True, max_iter=0):
-    """The ``params`` block of the M-step entry points (``floor=None`` keeps every match; max_iter 0 = 80)."""
+    """The ``params`` block of the M-step entry points (``floor=None`` keeps every match; max_iter 0 = the mode's default:
+    80 interior-point iterations, 100 Huber steps).  Mode MODEL_HUBER takes M as ``du``; ``dv`` is ignored."""
     return np.array([mode, du, dv, -np.inf if floor is None else floor, 1.0 if swap else 0.0, max_iter], dtype=np.float64)
 
 

@@ -148,6 +148,7 @@ int spectral_em_batch_check(const int *pair_offset, int n_pairs, const int *pair
         int r;
         if ((rc = spec_check_params(spec_params + (size_t)b * APAP_SPECTRAL_PARAMS, &sc, &r, msg))) return rc;
         if ((rc = model_check_params(model_params + (size_t)b * APAP_MODEL_PARAMS, &msc, msg))) return rc;
+        if ((rc = model_check_huber(msc, -1, msg))) return rc;
         if (b && r != restarts)
             return apap::fail(APAP_ERR_INVALID_ARG, "%s: problem %d: max_restarts %d differs from problem 0's %d (the cap fixes how "
                                                     "many cycles are enqueued: it must be equal across a batch)", who, b, r, restarts);

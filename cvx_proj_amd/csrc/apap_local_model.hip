@@ -81,8 +81,9 @@ namespace apap {
 // Every argument check of the two entry points that needs no pointer into device or caller memory but `params`.
 int local_model_check(int n, int cells, double gamma, double sigma, const double *params, const char *who) {
     ModelScalars sc;
-    const int rc = model_check_params(params, &sc, who);
+    int rc = model_check_params(params, &sc, who);
     if (rc) return rc;
+    if ((rc = model_check_huber(sc, -1, who))) return rc;
     if (sc.du < 0.0 || sc.dv < 0.0) return apap::fail(APAP_ERR_INVALID_ARG, "%s: du / dv negative", who);
     if (n < 1 || n > (1 << 26)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (need 1 .. 2^26 matches)", who, n);
     if (cells < 1 || cells > APAP_LOCAL_MODEL_MAX_CELLS)

@@ -7,6 +7,8 @@
 //   M2 k_model_solve  one wave: folds the block factors three at a time in block order, equilibrates, checks the rank,
 //                     solves (LMS: back-substitution; SDP: interior-point method on the 18 x 18 LMI), applies model.py's
 //                     float32 tail.
+//   M3 k_model_huber  mode HUBER only, after M1 and M2 in LMS mode: one workgroup of 256; from M2's h0 the whole Newton / line
+//                     search iteration on sum phi_M(A h - rhs) and its duality gap, the rows regenerated on every pass.
 //
 // Why 18 x 18: with P = [u v q] = K X(h) and K = Q R, P^T P = (R X)^T (R X), so [[I_2n, P], [P^T, D]] >= 0 (D = diag(r, r,
 // t)) holds exactly when D - (R X)^T (R X) >= 0, i.e. when [[I_15, R X], [(R X)^T, D]] >= 0 (Schur complement, twice).
@@ -36,6 +38,13 @@ __global__ __launch_bounds__(kW) void k_model_solve(const double *__restrict__ R
     model_solve_body(Rb, cnt, nb, sc, H, info, status);
 }
 
+__global__ __launch_bounds__(kHuberThreads) void k_model_huber(const float2 *__restrict__ pc, const float2 *__restrict__ po,
+                                                               const float *__restrict__ w, int n, ModelScalars sc,
+                                                               float *__restrict__ H, double *__restrict__ info,
+                                                               int *__restrict__ status) {
+    model_huber_body(pc, po, w, n, sc, H, info, status);
+}
+
 int model_check_device_args(int n, const void *d_pc, const void *d_po, const void *d_w, const void *d_H, const void *d_info,
                             const void *d_work, size_t work_bytes, size_t need, const char *who) {
     if (!d_pc || !d_po || !d_w || !d_H || !d_info || !d_work) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
@@ -46,7 +55,8 @@ int model_check_device_args(int n, const void *d_pc, const void *d_po, const voi
     return APAP_OK;
 }
 
-// M1 + M2 on `stream` (both entry points and every round of the EM loop).
+// M1 + M2 on `stream` (both entry points and every round of the EM loop).  Mode HUBER: M1 and M2 in LMS mode give the count,
+// the degenerate status and h0; the Huber kernel starts from them and reports the status word itself.
 void model_launch(const ModelLayout &L, const ModelScalars &sc, const float *d_pc, const float *d_po, const float *d_w,
                   float *d_H, double *d_info, int *d_status, void *d_work, hipStream_t s) {
     char *b = (char *)d_work;
@@ -54,7 +64,15 @@ void model_launch(const ModelLayout &L, const ModelScalars &sc, const float *d_p
     int *cnt = (int *)(b + L.cnt);
     hipLaunchKernelGGL(k_model_tsqr, dim3(L.nb), dim3(kW), 0, s, (const float2 *)d_pc, (const float2 *)d_po, d_w, L.n, L.per_block,
                        sc, Rb, cnt);
-    hipLaunchKernelGGL(k_model_solve, dim3(1), dim3(kW), 0, s, Rb, cnt, L.nb, sc, d_H, d_info, d_status);
+    if (sc.mode != APAP_MODEL_HUBER) {
+        hipLaunchKernelGGL(k_model_solve, dim3(1), dim3(kW), 0, s, Rb, cnt, L.nb, sc, d_H, d_info, d_status);
+        return;
+    }
+    ModelScalars lms = sc;
+    lms.mode = APAP_MODEL_LMS;
+    hipLaunchKernelGGL(k_model_solve, dim3(1), dim3(kW), 0, s, Rb, cnt, L.nb, lms, d_H, d_info, (int *)nullptr);
+    hipLaunchKernelGGL(k_model_huber, dim3(1), dim3(kHuberThreads), 0, s, (const float2 *)d_pc, (const float2 *)d_po, d_w, L.n, sc,
+                       d_H, d_info, d_status);
 }
 
 }  // namespace
@@ -73,6 +91,7 @@ int apap_model_solve_device(apap_ctx *ctx, const float *d_pts_c, const float *d_
     ModelScalars sc;
     int rc = model_check_params(params, &sc, who);
     if (rc) return rc;
+    if ((rc = model_check_huber(sc, n, who))) return rc;
     if (n < 1 || n > (1 << 26)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (need 1 .. 2^26 matches)", who, n);
     const ModelLayout L = model_layout(n);
     if ((rc = model_check_device_args(n, d_pts_c, d_pts_o, d_weights, d_H, d_info, d_work, work_bytes, L.total, who))) return rc;
@@ -108,6 +127,7 @@ int spectral_em_run(apap_ctx *ctx, const float *d_src, const float *d_dst, const
     ModelScalars sc;
     int rc = model_check_params(model_params, &sc, who);
     if (rc) return rc;
+    if ((rc = model_check_huber(sc, n, who))) return rc;
     sc.use_floor = 1;   // model_solve: `if w <= 1e-3: continue`, swap default
     sc.floor = 1e-3;
     sc.swap = 1;

@@ -436,6 +436,23 @@ __device__ __forceinline__ double pow2_near(double x) {
     return ldexp(1.0, m >= 0.70710678118654752440 ? e : e - 1);
 }
 
+// The tail of model_solve_body for the Huber kernel (model.py:50-56): float32 solution, [2, 2] = 1; with `invert`
+// numpy.linalg.inv (fp64 LU, cast back) and / [2, 2] in float32.  ORs APAP_STATUS_SINGULAR into `word` when the inverse meets a
+// zero pivot.  (M2 keeps its own lines, so that its code is what it was.)
+__device__ __forceinline__ void model_tail(const double (&h)[8], bool invert, float (&sol)[9], int &word) {
+    for (int k = 0; k < 8; ++k) sol[k] = (float)h[k];
+    sol[8] = 1.0f;
+    if (invert) {
+        double m[9], r[9];
+        for (int k = 0; k < 9; ++k) m[k] = (double)sol[k];
+        if (!apap::inv3(m, r)) word |= APAP_STATUS_SINGULAR;
+        float q[9];
+        for (int k = 0; k < 9; ++k) q[k] = (float)r[k];
+        const float d = q[8];
+        for (int k = 0; k < 9; ++k) sol[k] = q[k] / d;
+    }
+}
+
 __device__ __forceinline__ void model_solve_body(const double *__restrict__ Rb, const int *__restrict__ cnt, int nb,
                                                     ModelScalars sc, float *__restrict__ H, double *__restrict__ info,
                                                     int *__restrict__ status) {
@@ -545,24 +562,375 @@ __device__ __forceinline__ void model_solve_body(const double *__restrict__ Rb, 
     if (word && status) atomicOr(status, word);
 }
 
+// ---- Huber M-step (include/apap_hip.h; tests/huber_spec.py is the numpy specification) --------------------------------------
+// One workgroup per problem, after M1 and M2 ran in LMS mode: the rows (k_row's columns 0..8) are regenerated from pc, po, w
+// on every pass, match i always by thread i mod kHuberThreads in ascending order; a pass's sums are per-thread fp64
+// accumulations, one butterfly per wave and the waves' partial sums added in wave order by thread 0, which also does the
+// 8 x 8 work in LDS.  Unknowns are equilibrated: h'' = h / s, s_k = 1 / pow2_near(column norm), exact powers of two.
+constexpr int kHuberThreads = APAP_MODEL_HUBER_THREADS;
+constexpr int kHuberWaves = kHuberThreads / kW;
+constexpr int kHuberDefaultIters = 100;   // accepted steps (DESIGN.md "Huber M-step" has the counts behind it)
+constexpr int kHuberHalvings = 11;        // alpha = 1, 1/2, .., 2^-10
+constexpr int kHuberMaxN = 1 << 20;
+constexpr int kHuberAcc = 46;             // 36 Gram entries, 8 of the right-hand side, f, the clipped count
+
+enum { kHuberNewton = 0, kHuberMajorise = 1, kHuberDual = 2 };
+
+struct HuberLds {
+    double part[kHuberWaves][kHuberAcc];
+    double tot[kHuberAcc];
+    double G[64], y[8];
+    double s[8], h[8], d[8];
+    double f;
+    int nclip, ok, move;
+};
+
+// Row 2 i + odd of the scaled A, and rhs, of match i.
+__device__ __forceinline__ void huber_row(double (&as)[8], double &rhs, float2 c, float2 o, float w, int odd, const ModelScalars &sc,
+                                          const double (&s)[8]) {
+    double a[kC];
+    k_row(a, c, o, w, odd, sc);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) as[k] = a[k] * s[k];
+    rhs = -a[8];
+}
+
+__device__ __forceinline__ double huber_dot(const double (&as)[8], const double (&v)[8]) {
+    double r = as[0] * v[0];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) r += as[k] * v[k];
+    return r;
+}
+
+// The sums of `acc` over the workgroup into L.tot (valid on thread 0 only, which goes on to use them; the caller ends the
+// step with a barrier).
+template <int K>
+__device__ __forceinline__ void huber_reduce(double (&acc)[K], HuberLds &L, int tid) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = wsum(acc[k]);
+    if ((tid & (kW - 1)) == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) L.part[tid / kW][k] = acc[k];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 0; k < K; ++k) {
+            double t = L.part[0][k];
+            for (int v = 1; v < kHuberWaves; ++v) t += L.part[v][k];
+            L.tot[k] = t;
+        }
+    }
+}
+
+// Thread 0: L.d = G^-1 b for the packed upper triangle in L.tot[0..35] by Cholesky; false when G is not positive definite.
+__device__ bool huber_chol_solve(HuberLds &L, double sign) {
+    double *G = L.G;
+    int e = 0;
+    for (int k = 0; k < 8; ++k)
+        for (int l = k; l < 8; ++l, ++e) G[k * 8 + l] = G[l * 8 + k] = L.tot[e];
+    for (int k = 0; k < 8; ++k) {
+        double p = G[k * 8 + k];
+        for (int j = 0; j < k; ++j) p -= G[k * 8 + j] * G[k * 8 + j];
+        if (!(p > 0.0) || isinf(p)) return false;
+        const double d = sqrt(p);
+        G[k * 8 + k] = d;
+        for (int i = k + 1; i < 8; ++i) {
+            double t = G[i * 8 + k];
+            for (int j = 0; j < k; ++j) t -= G[i * 8 + j] * G[k * 8 + j];
+            G[i * 8 + k] = t / d;
+        }
+    }
+    for (int i = 0; i < 8; ++i) {
+        double t = sign * L.tot[36 + i];
+        for (int j = 0; j < i; ++j) t -= G[i * 8 + j] * L.y[j];
+        L.y[i] = t / G[i * 8 + i];
+    }
+    for (int i = 7; i >= 0; --i) {
+        double t = L.y[i];
+        for (int j = i + 1; j < 8; ++j) t -= G[j * 8 + i] * L.d[j];
+        L.d[i] = t / G[i * 8 + i];
+    }
+    for (int i = 0; i < 8; ++i)
+        if (!isfinite(L.d[i])) return false;
+    return true;
+}
+
+// One pass at L.h: f, the clipped count, and G d = b solved into L.d (L.ok):
+//   kHuberNewton    G = sum of a a^T over the unclipped rows, b = -(sum a r over them + M sum sign(r) a over the clipped)
+//   kHuberMajorise  G = sum omega a a^T, b = -sum omega a r, omega = min(1, M / |r|) over all rows
+//   kHuberDual      G = A^T A, b = A^T y, y = 2 clip(r, -M, M)
+__device__ __forceinline__ void huber_pass_gram(const float2 *__restrict__ pc, const float2 *__restrict__ po,
+                                                const float *__restrict__ w, int n, const ModelScalars &sc, HuberLds &L, int tid,
+                                                int kind) {
+    const double M = sc.du;
+    double s[8], h[8], acc[kHuberAcc];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        s[k] = L.s[k];
+        h[k] = L.h[k];
+    }
+#pragma unroll
+    for (int k = 0; k < kHuberAcc; ++k) acc[k] = 0.0;
+    for (int i = tid; i < n; i += kHuberThreads) {
+        const float wi = w[i];
+        if (sc.use_floor && !((double)wi > sc.floor)) continue;
+        const float2 c = pc[i], o = po[i];
+#pragma unroll
+        for (int odd = 0; odd < 2; ++odd) {
+            double as[8], rhs;
+            huber_row(as, rhs, c, o, wi, odd, sc, s);
+            const double r = huber_dot(as, h) - rhs;
+            const double ar = fabs(r);
+            const bool clipped = ar > M;
+            const double sg = r > 0.0 ? M : -M;
+            double omega, coef;
+            if (kind == kHuberMajorise) {
+                omega = clipped ? M / ar : 1.0;
+                coef = omega * r;
+            } else if (kind == kHuberDual) {
+                omega = 1.0;
+                coef = clipped ? 2.0 * sg : 2.0 * r;
+            } else {
+                omega = clipped ? 0.0 : 1.0;
+                coef = clipped ? sg : r;
+            }
+            int e = 0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const double t = omega * as[k];
+#pragma unroll
+                for (int l = k; l < 8; ++l, ++e) acc[e] += t * as[l];
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc[36 + k] += as[k] * coef;
+            acc[44] += clipped ? 2.0 * M * ar - M * M : r * r;
+            acc[45] += clipped ? 1.0 : 0.0;
+        }
+    }
+    huber_reduce(acc, L, tid);
+    if (tid == 0) {
+        L.f = L.tot[44];
+        L.nclip = (int)L.tot[45];
+        L.ok = huber_chol_solve(L, kind == kHuberDual ? 1.0 : -1.0);
+    }
+    __syncthreads();
+}
+
+// f(L.h + alpha L.d) for the kHuberHalvings step lengths and whether the clipped set at alpha = 1 is the one at L.h.  Thread 0
+// then moves L.h: L.move = 2 when `newton` and the full step keeps the clipped set without raising f (the minimiser of the
+// piece is the minimiser of f), 1 for the step length of the smallest f below L.f (the largest among equals), 0 for none.
+__device__ __forceinline__ void huber_pass_line(const float2 *__restrict__ pc, const float2 *__restrict__ po,
+                                                const float *__restrict__ w, int n, const ModelScalars &sc, HuberLds &L, int tid,
+                                                bool newton) {
+    const double M = sc.du;
+    double s[8], h[8], d[8], acc[kHuberHalvings + 1];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        s[k] = L.s[k];
+        h[k] = L.h[k];
+        d[k] = L.d[k];
+    }
+#pragma unroll
+    for (int k = 0; k <= kHuberHalvings; ++k) acc[k] = 0.0;
+    for (int i = tid; i < n; i += kHuberThreads) {
+        const float wi = w[i];
+        if (sc.use_floor && !((double)wi > sc.floor)) continue;
+        const float2 c = pc[i], o = po[i];
+#pragma unroll
+        for (int odd = 0; odd < 2; ++odd) {
+            double as[8], rhs;
+            huber_row(as, rhs, c, o, wi, odd, sc, s);
+            const double r = huber_dot(as, h) - rhs;
+            const double ad = huber_dot(as, d);
+            double alpha = 1.0;
+#pragma unroll
+            for (int j = 0; j < kHuberHalvings; ++j, alpha *= 0.5) {
+                const double rr = r + alpha * ad;
+                const double ar = fabs(rr);
+                acc[j] += ar > M ? 2.0 * M * ar - M * M : rr * rr;
+            }
+            const double r1 = r + ad;
+            const int s0 = r > M ? 1 : (r < -M ? -1 : 0), s1 = r1 > M ? 1 : (r1 < -M ? -1 : 0);
+            acc[kHuberHalvings] += s0 != s1 ? 1.0 : 0.0;
+        }
+    }
+    huber_reduce(acc, L, tid);
+    if (tid == 0) {
+        if (newton && L.tot[kHuberHalvings] == 0.0 && L.tot[0] <= L.f) {
+            for (int k = 0; k < 8; ++k) L.h[k] += L.d[k];
+            L.move = 2;
+        } else {
+            int best = 0;
+            for (int j = 1; j < kHuberHalvings; ++j)
+                if (L.tot[j] < L.tot[best]) best = j;
+            if (L.tot[best] < L.f) {
+                const double alpha = ldexp(1.0, -best);
+                for (int k = 0; k < 8; ++k) L.h[k] += alpha * L.d[k];
+                L.move = 1;
+            } else {
+                L.move = 0;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ void model_huber_body(const float2 *__restrict__ pc, const float2 *__restrict__ po,
+                                                 const float *__restrict__ w, int n, ModelScalars sc, float *__restrict__ H,
+                                                 double *__restrict__ info, int *__restrict__ status) {
+    __shared__ HuberLds L;
+    const int tid = threadIdx.x;
+    const double M = sc.du;
+    const int word0 = (int)info[APAP_MODEL_INFO_STATUS];   // M2's, in LMS mode (workgroup-uniform)
+    if (word0 & APAP_STATUS_MODEL_DEGENERATE) {            // LMS's outputs stay
+        if (tid == 0 && status) atomicOr(status, word0);
+        return;
+    }
+    // column norms -> scales; h'' = h0 / s
+    {
+        double acc[8], one[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            acc[k] = 0.0;
+            one[k] = 1.0;
+        }
+        for (int i = tid; i < n; i += kHuberThreads) {
+            const float wi = w[i];
+            if (sc.use_floor && !((double)wi > sc.floor)) continue;
+            const float2 c = pc[i], o = po[i];
+#pragma unroll
+            for (int odd = 0; odd < 2; ++odd) {
+                double a[8], rhs;
+                huber_row(a, rhs, c, o, wi, odd, sc, one);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc[k] += a[k] * a[k];
+            }
+        }
+        huber_reduce(acc, L, tid);
+        if (tid == 0) {
+            for (int k = 0; k < 8; ++k) {
+                const double p = pow2_near(sqrt(L.tot[k]));
+                L.s[k] = 1.0 / p;
+                L.h[k] = info[APAP_MODEL_INFO_H + k] * p;
+            }
+        }
+        __syncthreads();
+    }
+    int iters = 0;
+    bool untouched = false;
+    for (bool first = true;; first = false) {
+        huber_pass_gram(pc, po, w, n, sc, L, tid, kHuberNewton);
+        if (first && L.nclip == 0) {
+            untouched = true;
+            break;
+        }
+        if (iters == sc.max_iter) break;
+        int move = 0;
+        if (L.ok) {
+            huber_pass_line(pc, po, w, n, sc, L, tid, true);
+            move = L.move;
+        }
+        if (move == 0) {   // no Newton point, or no step length along it lowers f: one majorise-minimise step
+            huber_pass_gram(pc, po, w, n, sc, L, tid, kHuberMajorise);
+            if (!L.ok) break;
+            huber_pass_line(pc, po, w, n, sc, L, tid, false);
+            move = L.move;
+            if (move == 0) break;
+        }
+        ++iters;
+        if (move == 2) break;
+    }
+    // the gap of L.h: z = (A^T A)^-1 A^T y into L.d, then y' = y - A z
+    huber_pass_gram(pc, po, w, n, sc, L, tid, kHuberDual);
+    const double f = L.f;
+    double gap = 0.0;
+    if (f != 0.0) {   // workgroup-uniform
+        double s[8], h[8], z[8], acc[2] = {0.0, 0.0}, big = 0.0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            s[k] = L.s[k];
+            h[k] = L.h[k];
+            z[k] = L.d[k];
+        }
+        for (int i = tid; i < n; i += kHuberThreads) {
+            const float wi = w[i];
+            if (sc.use_floor && !((double)wi > sc.floor)) continue;
+            const float2 c = pc[i], o = po[i];
+#pragma unroll
+            for (int odd = 0; odd < 2; ++odd) {
+                double as[8], rhs;
+                huber_row(as, rhs, c, o, wi, odd, sc, s);
+                const double r = huber_dot(as, h) - rhs;
+                const double y = 2.0 * fmin(fmax(r, -M), M);
+                const double yp = y - huber_dot(as, z);
+                acc[0] += yp * yp;
+                acc[1] += rhs * yp;
+                big = fmax(big, fabs(yp));
+            }
+        }
+#pragma unroll
+        for (int o = kW / 2; o > 0; o >>= 1) big = fmax(big, __shfl_xor(big, o));
+        if ((tid & (kW - 1)) == 0) L.part[tid / kW][2] = big;
+        huber_reduce(acc, L, tid);
+        if (tid == 0) {
+            for (int v = 1; v < kHuberWaves; ++v) big = fmax(big, L.part[v][2]);
+            const double theta = big > 0.0 ? fmin(1.0, 2.0 * M / big) : 1.0;
+            const double D = -theta * theta * L.tot[0] / 4.0 - theta * L.tot[1];
+            gap = L.ok ? (f - D) / f : INFINITY;
+            if (!(gap == gap)) gap = INFINITY;
+        }
+    }
+    if (tid != 0) return;
+    int word = untouched ? word0 : 0;
+    if (!untouched) {
+        double h[8];
+        for (int k = 0; k < 8; ++k) h[k] = L.s[k] * L.h[k];
+        float sol[9];
+        model_tail(h, sc.swap != 0, sol, word);
+        for (int k = 0; k < 9; ++k) H[k] = sol[k];
+        for (int k = 0; k < 8; ++k) info[APAP_MODEL_INFO_H + k] = h[k];
+    }
+    if (!(gap <= kGapTol)) word |= APAP_STATUS_MODEL_NO_CONVERGENCE;
+    info[APAP_MODEL_INFO_OBJECTIVE] = f;
+    info[APAP_MODEL_INFO_GAP] = gap;
+    info[APAP_MODEL_INFO_ITERS] = (double)iters;
+    info[APAP_MODEL_INFO_STATUS] = (double)word;
+    if (word && status) atomicOr(status, word);
+}
+
 int model_check_params(const double *params, ModelScalars *sc, const char *who) {
     if (!params) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null params", who);
     const double mode = params[APAP_MODEL_MODE], swap = params[APAP_MODEL_SWAP], it = params[APAP_MODEL_MAX_ITER];
-    if (mode != APAP_MODEL_LMS && mode != APAP_MODEL_SDP) return apap::fail(APAP_ERR_INVALID_ARG, "%s: mode %g (0 = LMS, 1 = SDP)", who, mode);
+    if (mode != APAP_MODEL_LMS && mode != APAP_MODEL_SDP && mode != APAP_MODEL_HUBER)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: mode %g (0 = LMS, 1 = SDP, 2 = Huber)", who, mode);
     if (swap != 0.0 && swap != 1.0) return apap::fail(APAP_ERR_INVALID_ARG, "%s: swap %g (0 or 1)", who, swap);
     if (!(it >= 0.0 && it <= 10000.0)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: max_iter %g out of range", who, it);
     const double du = params[APAP_MODEL_DU], dv = params[APAP_MODEL_DV], fl = params[APAP_MODEL_FLOOR];
     if (!std::isfinite(du) || !std::isfinite(dv)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: du / dv not finite", who);
     if (std::isnan(fl)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: weight floor is NaN", who);
+    if (mode == APAP_MODEL_HUBER && !(du > 1e-2))   // model.py:36: huber_param > 1e-2 selects the Huber loss
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: Huber M %g (need a finite M > 1e-2)", who, du);
     sc->mode = (int)mode;
     sc->swap = (int)swap;
-    sc->max_iter = it == 0.0 ? kDefaultIters : (int)it;
+    sc->max_iter = it != 0.0 ? (int)it : mode == APAP_MODEL_HUBER ? kHuberDefaultIters : kDefaultIters;
     sc->use_floor = fl != -INFINITY;
     sc->floor = fl;
     sc->du = du;
     sc->dv = dv;
     sc->du32 = (float)du;   // np.float32([[self.du, 0]]) (model.py:85)
     sc->dv32 = (float)dv;
+    return APAP_OK;
+}
+
+// The Huber M-step exists for one problem per call (apap_model.hip): `n` is that call's match count, or -1 from the entry
+// points that have no Huber kernel (the batch, the per-cell solve), which refuse the mode by name.
+int model_check_huber(const ModelScalars &sc, int n, const char *who) {
+    if (sc.mode != APAP_MODEL_HUBER) return APAP_OK;
+    if (n < 0)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: the Huber M-step (mode 2) is not available here: use apap_model_solve or "
+                                                "apap_spectral_em", who);
+    if (n > kHuberMaxN)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (the Huber M-step serves 1 .. 2^20 matches)", who, n);
     return APAP_OK;
 }
 

@@ -1,7 +1,12 @@
 """The homography solvers of the reference's ``pyviz/model.py`` (the M-step of the spectral method) on the GPU, without cvxpy.
 
 * ``LMSSolver(max_iter, huber_param=-1.0)``: min ||A h - rhs||^2, the exact least-squares solution (a QR of the rows and
-  back-substitution in fp64).  The Huber loss (``huber_param > 1e-2``) is not implemented: NotImplementedError.
+  back-substitution in fp64).  With ``huber_param > 1e-2`` the reference minimises the Huber loss instead; under that
+  spelling this class still raises NotImplementedError: the Huber loss is ``HuberSolver``.
+* ``HuberSolver(max_iter, huber_param)``: min sum_j phi_M(r_j), r = A h - rhs, phi_M(r) = r^2 for |r| <= M and
+  2 M |r| - M^2 beyond (cvxpy's ``huber(x, M)``, M = huber_param > 1e-2), solved to a relative duality gap of 1e-10 by
+  Newton steps on the active quadratic piece with a halving line search, inside one kernel launch (include/apap_hip.h,
+  DESIGN.md "Huber M-step").  ``.last.gap`` is a certificate computed from the rows: it does not depend on the method.
 * ``SDPSolver(max_iter, du=1.0, dv=1.0)``: min r + t subject to the reference's (2N+3)-sized LMI, solved exactly (to a
   relative duality gap of 1e-10) on an equivalent 18 x 18 LMI by a primal-dual interior-point method (include/apap_hip.h,
   DESIGN.md "M-step and EM loop").  The reference hands the same programme to SCS with ``max_iters = max_iter``; its answer
@@ -27,15 +32,15 @@ import numpy as np
 
 from . import _native
 
-__all__ = ["SDPSolver", "LMSSolver", "ModelResult"]
+__all__ = ["SDPSolver", "LMSSolver", "HuberSolver", "ModelResult"]
 
 
 class ModelResult(NamedTuple):
     h: np.ndarray          # (8,) float64: the solution before the float32 tail
-    objective: float       # SDP: r + t; LMS: ||A h - rhs||^2
-    gap: float             # SDP: tr(S Z) / (r + t) of the returned iterate; LMS: 0
-    iterations: int        # interior-point iterations (LMS: 0)
-    status: int            # APAP_STATUS_* bits (STATUS_MODEL_NO_CONVERGENCE: the iteration cap was hit)
+    objective: float       # SDP: r + t; LMS: ||A h - rhs||^2; Huber: sum phi_M(A h - rhs)
+    gap: float             # SDP: tr(S Z) / (r + t) of the returned iterate; LMS: 0; Huber: the relative duality gap of h
+    iterations: int        # interior-point iterations (LMS: 0); Huber: accepted steps
+    status: int            # APAP_STATUS_* bits (STATUS_MODEL_NO_CONVERGENCE: the gap stayed above 1e-10)
     r: float               # SDP: r (NaN for LMS)
     t: float               # SDP: t (NaN for LMS)
     Z: np.ndarray          # SDP: (3, 3) dual block (order u, v, q), the optimality certificate (NaN for LMS)
@@ -53,7 +58,9 @@ def result_of(info):
 
 def warn_no_convergence(res, stacklevel=3):
     if res.status & _native.STATUS_MODEL_NO_CONVERGENCE:
-        warnings.warn(f"SDP: the interior-point method stopped at relative gap {res.gap:.3e} after {res.iterations} iterations "
+        # the SDP reports r and t, the Huber M-step leaves them NaN
+        method = "Huber: the Newton iteration" if np.isnan(res.r) else "SDP: the interior-point method"
+        warnings.warn(f"{method} stopped at relative gap {res.gap:.3e} after {res.iterations} iterations "
                       "(target 1e-10); the best iterate is returned", RuntimeWarning, stacklevel=stacklevel)
 
 
@@ -125,3 +132,18 @@ class SDPSolver(LMSSolver):
 
     def _announce(self, n):
         print(f"Start solving SDP Problem... point num: {n}")
+
+
+class HuberSolver(LMSSolver):
+    def __init__(self, max_iter, huber_param, *, device=-1, ctx=None) -> None:
+        """The reference's ``LMSSolver(max_iter, huber_param)`` with ``huber_param > 1e-2`` (model.py:36-41).  ``max_iter``:
+        kept for the signature; the iteration here stops at a relative duality gap of 1e-10 (or after 100 steps)."""
+        if not huber_param > 1e-2:
+            raise ValueError(f"HuberSolver needs huber_param > 1e-2 (got {huber_param!r}); at or below it the reference solves "
+                             "least squares: LMSSolver")
+        if not np.isfinite(huber_param):
+            raise ValueError(f"HuberSolver needs a finite huber_param (got {huber_param!r})")
+        super().__init__(max_iter, huber_param, device=device, ctx=ctx)
+
+    def _params(self, swap):
+        return _native.model_params(_native.MODEL_HUBER, float(self.huber_param), floor=None, swap=swap)

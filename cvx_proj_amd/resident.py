@@ -440,6 +440,28 @@ def model_workspace_bytes(n):
     return _native.lib().apap_model_workspace_bytes(n)
 
 
+def hip_model_solve(pts_c, pts_o, weights, params, status=None, ctx=None, work=None):
+    """``apap_model_solve_device`` on the current stream of the tensors' device: one M-step (LMS, SDP or Huber) on resident
+    data.  pts_c / pts_o (n, 2) float32, weights (n,) float32 on the device; ``params``: host ``_native.model_params(...)``.
+    Returns (H (3, 3) float32, info (24,) float64) as device tensors, not synchronised: a degenerate or singular solve shows in
+    info[MODEL_INFO_STATUS] and in ``status`` (int32, 1 element, OR-ed into), not as an exception."""
+    _needs_device(pts_c, "hip_model_solve")
+    dev, n = pts_c.device, pts_c.shape[0]
+    _contiguous(((pts_c, torch.float32), (pts_o, torch.float32), (weights, torch.float32)), dev, "hip_model_solve")
+    if pts_c.shape != (n, 2) or pts_o.shape != pts_c.shape or weights.shape != (n,):
+        raise ValueError("hip_model_solve: shapes (n, 2), (n, 2), (n,) expected")
+    mp = np.ascontiguousarray(params, dtype=np.float64)
+    if mp.shape != (_native.MODEL_PARAMS,):
+        raise ValueError(f"hip_model_solve: params must hold {_native.MODEL_PARAMS} values")
+    H = torch.empty((3, 3), dtype=torch.float32, device=dev)
+    info = torch.empty(_native.MODEL_INFO, dtype=torch.float64, device=dev)
+    work = _scratch(work, model_workspace_bytes(n), dev)
+    _native.check(_native.lib().apap_model_solve_device(
+        _native._h(ctx), pts_c.data_ptr(), pts_o.data_ptr(), weights.data_ptr(), n, _dp(mp), H.data_ptr(), info.data_ptr(),
+        None if status is None else status.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
+    return H, info
+
+
 def hip_spectral_em(src, dst, c_feats, o_feats, F, spec_params, model_params, em_steps, mask, status=None, ctx=None, work=None):
     """``apap_spectral_em_device`` on the current stream of the tensors' device: ``em_steps`` rounds of calculate_M and the
     M-step on resident data, no host synchronisation: every spectral restart cycle is enqueued (those after convergence return

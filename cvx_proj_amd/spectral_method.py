@@ -9,7 +9,8 @@ runs), the part that needs neither OpenCV nor cvxpy: ``calculate_M`` (:66-133) a
 * ``recompute_matching``, ``match_RANSAC``, ``cv_to_array``, ``normalized_feature``: the reference's helpers.
   ``match_RANSAC`` uses THIS REPOSITORY's GPU RANSAC (``_native.find_homography_ransac``), not OpenCV's: sampler, adaptive
   stopping and refinement differ, so its mask is not cv.findHomography's (as in ``baseline_stitch_test``).
-* ``model_solve`` (:165-186): the M-step, model.py's LMSSolver / SDPSolver on the GPU (cvx_proj_amd/model.py).
+* ``model_solve`` (:165-186): the M-step, model.py's LMSSolver / SDPSolver on the GPU (cvx_proj_amd/model.py);
+  ``loss="huber"`` (with ``lms=True`` and a parameter > 1e-2) runs the Huber M-step, HuberSolver.
 * ``spectral_em``: the EM loop of ``spectral_method()`` (:188-241) on arrays, every round on the device without a host
   synchronisation (``apap_spectral_em``): calculate_M with Hg = the previous round's H_pred, then model_solve.
 * ``warp_results``: the two ``image_warping`` calls of the ``-s`` option (:227-229) as one batched kernel launch.
@@ -166,13 +167,30 @@ def calculate_M(kpts_cp, feats_cp, kpts_op, feats_op, F, matches, opts, verbose=
 
 
 # ------------------------------------------------------------------ M-step and EM loop (:165-241)
+def _check_loss(loss, lms, param):
+    """``loss``: None (the solver follows from ``lms`` and the parameter alone) or "huber" (needs lms and a parameter > 1e-2)."""
+    if loss is None:
+        return False
+    if loss != "huber":
+        raise ValueError(f"loss must be None or 'huber'; got {loss!r}")
+    if not lms:
+        raise ValueError("loss='huber' needs lms=True (the Huber loss belongs to LMSSolver)")
+    if not param > 1e-2:
+        raise ValueError(f"loss='huber' needs a Huber parameter > 1e-2; got {param!r}")
+    return True
+
+
 def model_solve(kpts_cp, kpts_op, matches, weights, param=0.5, max_iter=8000, verbose=False, swap=True, lms=True, device=-1,
-                ctx=None):
+                ctx=None, loss=None):
     """spectral_method.py:165-186: the matches with weight > 1e-3 (in order) into LMSSolver(max_iter, param) or
     SDPSolver(max_iter, param, param).  Note the reference's defaults: lms=True with param=0.5 is the Huber loss, which
-    raises NotImplementedError here."""
-    from .model import LMSSolver, SDPSolver, solve_params
-    solver = LMSSolver(max_iter, param, device=device, ctx=ctx) if lms else SDPSolver(max_iter, param, param, device=device, ctx=ctx)
+    raises NotImplementedError under that spelling; ``loss="huber"`` (with lms=True and param > 1e-2, else ValueError) runs
+    it: HuberSolver(max_iter, param)."""
+    from .model import HuberSolver, LMSSolver, SDPSolver, solve_params
+    if _check_loss(loss, lms, param):
+        solver = HuberSolver(max_iter, param, device=device, ctx=ctx)
+    else:
+        solver = LMSSolver(max_iter, param, device=device, ctx=ctx) if lms else SDPSolver(max_iter, param, param, device=device, ctx=ctx)
     params = solver._params(swap)
     params[3] = _native.MODEL_FLOOR
     src, dst = cv_to_array(kpts_cp, kpts_op, matches)
@@ -201,7 +219,9 @@ class EMResult(NamedTuple):
     H_save: np.ndarray          # (3, 3) float64: inv(H_pred of the last round), normalised (:235-236)
 
 
-def _model_mode(lms, fluc, huber_param):
+def _model_mode(lms, fluc, huber_param, loss=None):
+    if _check_loss(loss, lms, huber_param):
+        return _native.model_params(_native.MODEL_HUBER, float(huber_param))
     if lms:
         if huber_param > 1e-2:
             raise NotImplementedError("spectral_em with lms=True and huber_param > 1e-2 (the Huber loss) is not implemented on "
@@ -212,15 +232,17 @@ def _model_mode(lms, fluc, huber_param):
 
 def spectral_em(src_pts, dst_pts, c_feats, o_feats, F, *, em_steps=2, lms=False, fluc=0.5, huber_param=-1.0, epi_weight=0.5,
                 affinity_eps=30.0, aff_thresh=0.5, em_radius=6.0, score_thresh=0.4, max_restarts=None, mask=None, swap=True,
-                device=-1, ctx=None):
+                device=-1, ctx=None, loss=None):
     """The EM loop of spectral_method() (:188-241) on arrays: ``em_steps`` rounds of calculate_M (Hg = the previous round's
     H_pred) and model_solve(ransac_mask, param = huber_param if lms else fluc), all enqueued on the device at once.  The
     first round's initial mask: ``mask``, else the GPU RANSAC of this repository (as spectral_weights; ``swap`` sets only the
     direction of that RANSAC, as in match_RANSAC).  The M-step always inverts and normalises its solution (model_solve's
     default swap=True, which spectral_method() uses).  Returns an EMResult.  Raises as model_solve (IndexError when a round selects no match, ValueError for a degenerate selection,
-    LinAlgError for a singular solution); warns as spectral_weights and the SDP solver."""
+    LinAlgError for a singular solution); warns as spectral_weights and the SDP solver.  ``loss="huber"`` (with lms=True and
+    huber_param > 1e-2, else ValueError) runs the Huber M-step in every round; without it that spelling raises
+    NotImplementedError."""
     from .model import result_of, warn_no_convergence
-    mp = _model_mode(lms, fluc, huber_param)
+    mp = _model_mode(lms, fluc, huber_param, loss)
     src = np.ascontiguousarray(src_pts, dtype=np.float32)
     dst = np.ascontiguousarray(dst_pts, dtype=np.float32)
     sp = _native.spectral_params(epi_weight, affinity_eps, aff_thresh, em_radius, score_thresh,

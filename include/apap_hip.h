@@ -752,21 +752,41 @@ int apap_spectral_affinity(apap_ctx *ctx, const float *src, const float *dst, co
  * APAP_ERR_INVALID_ARG with them so.  Once the kernels ran both hold their results and the call returns APAP_ERR_INVALID_ARG
  * when APAP_STATUS_MODEL_DEGENERATE is set (H is NaN), APAP_ERR_SINGULAR when the inverse met a zero pivot (numpy:
  * LinAlgError), APAP_OK otherwise, also when the iteration cap was hit (the status word is in
- * info_out[APAP_MODEL_INFO_STATUS]).  n >= 1. */
+ * info_out[APAP_MODEL_INFO_STATUS]).  n >= 1.
+ *
+ *   HUBER (LMSSolver, huber_param = M > 1e-2):  min sum_j phi_M(r_j), r = A h - rhs (fp64),
+ *        phi_M(r) = r^2 if |r| <= M, 2 M |r| - M^2 otherwise (cvxpy's huber(x, M))                (model.py:36-41)
+ * on the same rows as LMS, from the least-squares solution h0: Newton steps on the quadratic piece of the current clipped
+ * set (8 x 8 Cholesky, power-of-two column scales) with a halving line search, a majorise-minimise step where that fails,
+ * all inside one launch of one workgroup of APAP_MODEL_HUBER_THREADS threads; match i is always summed by thread
+ * i mod APAP_MODEL_HUBER_THREADS in ascending order, then one fixed tree, so a call is deterministic.  M travels in the
+ * APAP_MODEL_DU slot (the reference's single `param` is either fluc or huber_param); the DV slot is ignored but must be
+ * finite.  M not finite or <= 1e-2, or n > 2^20 (one workgroup serves a problem): APAP_ERR_INVALID_ARG before any device
+ * is touched.  The info block: OBJECTIVE = f(h) at the returned h, ITERS = the accepted steps, R, T, Z = NaN, and
+ *     GAP = (f(h) - D) / f(h) (0 when f(h) = 0),  D = -sum y'^2 / 4 - rhs^T y',
+ *     y' = theta (y - A (A^T A)^-1 A^T y),  y = 2 clip(r, -M, M),  theta = min(1, 2 M / max|.|):
+ * D bounds the optimum from below for any h (the Fenchel dual, phi*(y) = y^2 / 4 on |y| <= 2 M subject to A^T y = 0), so
+ * the gap certifies the returned h whatever the method did.  APAP_STATUS_MODEL_NO_CONVERGENCE is set exactly when GAP is
+ * above 1e-10 (the iterate with the lowest f is returned: every accepted step lowers f).  When no row is clipped at h0 the
+ * least-squares outputs stay as they are (H byte-identical to LMS, ITERS 0).  Degenerate input behaves as in LMS.
+ * apap_spectral_em_batch* and apap_local_model_solve* refuse mode HUBER (APAP_ERR_INVALID_ARG). */
 #define APAP_MODEL_LMS 0
 #define APAP_MODEL_SDP 1
-#define APAP_MODEL_MODE 0      /* APAP_MODEL_LMS or APAP_MODEL_SDP                                              */
-#define APAP_MODEL_DU 1        /* SDPSolver's du (model_solve: fluc)                                            */
+#define APAP_MODEL_HUBER 2
+#define APAP_MODEL_HUBER_THREADS 256 /* the width of the Huber M-step's workgroup                               */
+#define APAP_MODEL_MODE 0      /* APAP_MODEL_LMS, APAP_MODEL_SDP or APAP_MODEL_HUBER                            */
+#define APAP_MODEL_DU 1        /* SDPSolver's du (model_solve: fluc); HUBER: M                                  */
+#define APAP_MODEL_HUBER_M APAP_MODEL_DU
 #define APAP_MODEL_DV 2        /* SDPSolver's dv (model_solve: fluc)                                            */
 #define APAP_MODEL_FLOOR 3     /* keep the matches with weight > floor (model_solve: 1e-3); -inf keeps them all  */
 #define APAP_MODEL_SWAP 4      /* 1: invert and normalise the solution (model.py:53-55)                          */
-#define APAP_MODEL_MAX_ITER 5  /* interior-point iteration cap; 0 = the default, 80                              */
+#define APAP_MODEL_MAX_ITER 5  /* iteration cap; 0 = the default: 80 (SDP, interior point), 100 (HUBER, steps)   */
 #define APAP_MODEL_PARAMS 6
-#define APAP_MODEL_INFO_OBJECTIVE 0 /* r + t (SDP) or ||A h - rhs||^2 (LMS)                                      */
+#define APAP_MODEL_INFO_OBJECTIVE 0 /* r + t (SDP), ||A h - rhs||^2 (LMS) or f(h) (HUBER)                        */
 #define APAP_MODEL_INFO_R 1         /* SDP: r                                                                   */
 #define APAP_MODEL_INFO_T 2         /* SDP: t                                                                   */
-#define APAP_MODEL_INFO_GAP 3       /* SDP: tr(S Z) / (r + t) of the returned iterate (0 for LMS)                */
-#define APAP_MODEL_INFO_ITERS 4     /* SDP: interior-point iterations                                           */
+#define APAP_MODEL_INFO_GAP 3       /* SDP: tr(S Z) / (r + t) of the returned iterate (0 for LMS); HUBER: above   */
+#define APAP_MODEL_INFO_ITERS 4     /* SDP: interior-point iterations; HUBER: accepted steps                    */
 #define APAP_MODEL_INFO_STATUS 5    /* status word (APAP_STATUS_MODEL_*, APAP_STATUS_SINGULAR)                  */
 #define APAP_MODEL_INFO_COUNT 6     /* selected matches                                                          */
 #define APAP_MODEL_INFO_Z 7         /* SDP: 9 doubles, the dual 3 x 3 block (order u, v, q): the certificate      */
