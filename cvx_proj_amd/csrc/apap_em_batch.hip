@@ -128,33 +128,41 @@ void launch_matvec(int blocks, int count, const EmProb *tab, const int *list, in
     hipLaunchKernelGGL(k_spec_matvec_b<R>, dim3(blocks, count), dim3(kSpecThreads), 0, s, tab, list, j);
 }
 
-}  // namespace
-
-namespace apap {
-
-// Every argument check of the batch entry points that needs no device pointer (the messages name the problem).
-int spectral_em_batch_check(const int *pair_offset, int n_pairs, const int *pair_of, const double *spec_params,
-                            const double *model_params, int n_problems, int em_steps, const char *who) {
+// Every argument check of the batch entry points that needs no device pointer (the messages name the problem).  With `tab`,
+// it is sized to the batch and every problem's parsed scalars go to its descriptor, the batch's cycle cap to `restarts_out`.
+int batch_check(const int *pair_offset, int n_pairs, const int *pair_of, const double *spec_params, const double *model_params,
+                int n_problems, int em_steps, const char *who, std::vector<EmProb> *tab, int *restarts_out) {
     int rc = check_shape(pair_offset, n_pairs, pair_of, n_problems, who);
     if (rc) return rc;
     if (em_steps < 1 || em_steps > 64) return apap::fail(APAP_ERR_INVALID_ARG, "%s: em_steps %d (1 .. 64)", who, em_steps);
     if (!spec_params || !model_params) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null params", who);
+    if (tab) tab->assign((size_t)n_problems, EmProb{});
     int restarts = 0;
     char msg[96];
     for (int b = 0; b < n_problems; ++b) {
         snprintf(msg, sizeof msg, "%s: problem %d", who, b);
-        SpecScalars sc;
-        ModelScalars msc;
+        EmProb mine, &d = tab ? (*tab)[b] : mine;
         int r;
-        if ((rc = spec_check_params(spec_params + (size_t)b * APAP_SPECTRAL_PARAMS, &sc, &r, msg))) return rc;
-        if ((rc = model_check_params(model_params + (size_t)b * APAP_MODEL_PARAMS, &msc, msg))) return rc;
-        if ((rc = model_check_huber(msc, -1, msg))) return rc;
+        if ((rc = spec_check_params(spec_params + (size_t)b * APAP_SPECTRAL_PARAMS, &d.sc, &r, msg))) return rc;
+        if ((rc = model_check_params(model_params + (size_t)b * APAP_MODEL_PARAMS, &d.msc, msg))) return rc;
+        if ((rc = model_check_huber(d.msc, -1, msg))) return rc;
         if (b && r != restarts)
             return apap::fail(APAP_ERR_INVALID_ARG, "%s: problem %d: max_restarts %d differs from problem 0's %d (the cap fixes how "
                                                     "many cycles are enqueued: it must be equal across a batch)", who, b, r, restarts);
         restarts = r;
     }
+    if (restarts_out) *restarts_out = restarts;
     return APAP_OK;
+}
+
+}  // namespace
+
+namespace apap {
+
+// batch_check for the host-buffer entry point (apap_capi.hip), which checks before it stages anything.
+int spectral_em_batch_check(const int *pair_offset, int n_pairs, const int *pair_of, const double *spec_params,
+                            const double *model_params, int n_problems, int em_steps, const char *who) {
+    return batch_check(pair_offset, n_pairs, pair_of, spec_params, model_params, n_problems, em_steps, who, nullptr, nullptr);
 }
 
 // The body of apap_spectral_em_batch_device; sync_each = 1 (the host-buffer entry point) waits for every restart cycle and
@@ -166,20 +174,15 @@ int spectral_em_batch_run(apap_ctx *ctx, const float *d_src, const float *d_dst,
                           double *d_info, double *d_segment, float *d_ransac_mask, float *d_original_mask, double *d_spec_info,
                           int *d_status, void *d_work, size_t work_bytes, void *stream, int sync_each) {
     const char *who = "apap_spectral_em_batch_device";
-    int rc = spectral_em_batch_check(pair_offset, n_pairs, pair_of, spec_params, model_params, n_problems, em_steps, who);
+    std::vector<EmProb> tab;
+    int restarts = 0;
+    int rc = batch_check(pair_offset, n_pairs, pair_of, spec_params, model_params, n_problems, em_steps, who, &tab, &restarts);
     if (rc) return rc;
     const int B = n_problems;
-    std::vector<EmProb> tab((size_t)B);
     std::vector<int> lists((size_t)B);
-    int restarts = 0;
     size_t need = 0;
-    for (int b = 0; b < B; ++b) {   // checked above: these cannot fail
-        EmProb &d = tab[b];
-        (void)spec_check_params(spec_params + (size_t)b * APAP_SPECTRAL_PARAMS, &d.sc, &restarts, who);
-        (void)model_check_params(model_params + (size_t)b * APAP_MODEL_PARAMS, &d.msc, who);
-        d.msc.use_floor = 1;   // as apap_spectral_em_device: model_solve's `if w <= 1e-3: continue`, swap
-        d.msc.floor = 1e-3;
-        d.msc.swap = 1;
+    for (int b = 0; b < B; ++b) {
+        model_em_scalars(tab[b].msc);   // as apap_spectral_em_device
         need += problem_bytes(pair_len(pair_offset, pair_of[b]));
     }
     if (!d_src || !d_dst || !d_c_feats || !d_o_feats || !d_F || !d_mask_in || !d_work)

@@ -74,18 +74,15 @@ __global__ __launch_bounds__(kW) void k_local_solve(const LocalArgs a) {
                      a.status ? a.status + cell : nullptr);
 }
 
-}  // namespace
-
-namespace apap {
-
-// Every argument check of the two entry points that needs no pointer into device or caller memory but `params`.
-int local_model_check(int n, int cells, double gamma, double sigma, const double *params, const char *who) {
-    ModelScalars sc;
+// Every argument check of the two entry points that needs no pointer into device or caller memory but `params`; the parsed
+// scalars go to `sc_out` when it is given.
+int local_check(int n, int cells, double gamma, double sigma, const double *params, const char *who, ModelScalars *sc_out) {
+    ModelScalars mine, &sc = sc_out ? *sc_out : mine;
     int rc = model_check_params(params, &sc, who);
     if (rc) return rc;
     if ((rc = model_check_huber(sc, -1, who))) return rc;
     if (sc.du < 0.0 || sc.dv < 0.0) return apap::fail(APAP_ERR_INVALID_ARG, "%s: du / dv negative", who);
-    if (n < 1 || n > (1 << 26)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (need 1 .. 2^26 matches)", who, n);
+    if ((rc = model_check_n(n, who))) return rc;
     if (cells < 1 || cells > APAP_LOCAL_MODEL_MAX_CELLS)
         return apap::fail(APAP_ERR_INVALID_ARG, "%s: cells=%d (need 1 .. %d)", who, cells, APAP_LOCAL_MODEL_MAX_CELLS);
     if (!(sigma > 0.0) || !std::isfinite(sigma)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: sigma %g (need a finite sigma > 0)", who, sigma);
@@ -93,12 +90,21 @@ int local_model_check(int n, int cells, double gamma, double sigma, const double
     return APAP_OK;
 }
 
+}  // namespace
+
+namespace apap {
+
+// local_check for the host-buffer entry point (apap_capi.hip), which checks before it stages anything.
+int local_model_check(int n, int cells, double gamma, double sigma, const double *params, const char *who) {
+    return local_check(n, cells, gamma, sigma, params, who, nullptr);
+}
+
 }  // namespace apap
 
 extern "C" {
 
 size_t apap_local_model_workspace_bytes(int n, int cells) {
-    if (n < 1 || n > (1 << 26) || cells < 1 || cells > APAP_LOCAL_MODEL_MAX_CELLS) return 0;
+    if (n < 1 || n > kModelMaxN || cells < 1 || cells > APAP_LOCAL_MODEL_MAX_CELLS) return 0;
     return (size_t)std::min(cells, kLocalChunk) * cell_bytes(model_layout(n));
 }
 
@@ -106,7 +112,8 @@ int apap_local_model_solve_device(apap_ctx *ctx, const float *d_pts_c, const flo
                                   const double *d_vertices, int cells, double gamma, double sigma, const double *params,
                                   float *d_H, double *d_info, int *d_status, void *d_work, size_t work_bytes, void *stream) {
     const char *who = "apap_local_model_solve_device";
-    int rc = apap::local_model_check(n, cells, gamma, sigma, params, who);
+    LocalArgs a{};
+    int rc = local_check(n, cells, gamma, sigma, params, who, &a.sc);
     if (rc) return rc;
     if (!d_pts_c || !d_pts_o || !d_vertices || !d_H || !d_work) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
     const ModelLayout L = model_layout(n);
@@ -117,8 +124,6 @@ int apap_local_model_solve_device(apap_ctx *ctx, const float *d_pts_c, const flo
         return apap::fail(APAP_ERR_INVALID_ARG, "%s: workspace must be 256-byte, points and vertices 8-byte aligned", who);
     const int chunk = (int)std::min<size_t>(std::min<size_t>(work_bytes / unit, (size_t)cells), (size_t)kMaxGridY);
 
-    LocalArgs a{};
-    (void)model_check_params(params, &a.sc, who);   // checked above: cannot fail
     a.pc = (const float2 *)d_pts_c;
     a.po = (const float2 *)d_pts_o;
     a.mw = d_match_weights;

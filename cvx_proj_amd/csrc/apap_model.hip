@@ -45,10 +45,10 @@ __global__ __launch_bounds__(kHuberThreads) void k_model_huber(const float2 *__r
     model_huber_body(pc, po, w, n, sc, H, info, status);
 }
 
-int model_check_device_args(int n, const void *d_pc, const void *d_po, const void *d_w, const void *d_H, const void *d_info,
+// The pointer, workspace and alignment checks of both entry points; n has passed model_check_n by then.
+int model_check_device_args(const void *d_pc, const void *d_po, const void *d_w, const void *d_H, const void *d_info,
                             const void *d_work, size_t work_bytes, size_t need, const char *who) {
     if (!d_pc || !d_po || !d_w || !d_H || !d_info || !d_work) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
-    if (n < 1 || n > (1 << 26)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (need 1 .. 2^26 matches)", who, n);
     if (work_bytes < need) return apap::fail(APAP_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, work_bytes, need);
     if (((uintptr_t)d_work & 255) != 0 || ((uintptr_t)d_pc & 7) != 0 || ((uintptr_t)d_po & 7) != 0)
         return apap::fail(APAP_ERR_INVALID_ARG, "%s: workspace must be 256-byte and points 8-byte aligned", who);
@@ -92,9 +92,9 @@ int apap_model_solve_device(apap_ctx *ctx, const float *d_pts_c, const float *d_
     int rc = model_check_params(params, &sc, who);
     if (rc) return rc;
     if ((rc = model_check_huber(sc, n, who))) return rc;
-    if (n < 1 || n > (1 << 26)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (need 1 .. 2^26 matches)", who, n);
+    if ((rc = model_check_n(n, who))) return rc;
     const ModelLayout L = model_layout(n);
-    if ((rc = model_check_device_args(n, d_pts_c, d_pts_o, d_weights, d_H, d_info, d_work, work_bytes, L.total, who))) return rc;
+    if ((rc = model_check_device_args(d_pts_c, d_pts_o, d_weights, d_H, d_info, d_work, work_bytes, L.total, who))) return rc;
     hipStream_t s = (hipStream_t)stream;
     model_launch(L, sc, d_pts_c, d_pts_o, d_weights, d_H, d_info, d_status, d_work, s);
     const hipError_t e = hipGetLastError();
@@ -128,17 +128,15 @@ int spectral_em_run(apap_ctx *ctx, const float *d_src, const float *d_dst, const
     int rc = model_check_params(model_params, &sc, who);
     if (rc) return rc;
     if ((rc = model_check_huber(sc, n, who))) return rc;
-    sc.use_floor = 1;   // model_solve: `if w <= 1e-3: continue`, swap default
-    sc.floor = 1e-3;
-    sc.swap = 1;
+    model_em_scalars(sc);
     if (em_steps < 1 || em_steps > 64) return apap::fail(APAP_ERR_INVALID_ARG, "%s: em_steps %d (1 .. 64)", who, em_steps);
     if (!d_mask_in) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null initial mask", who);
-    if (n < 1 || n > (1 << 26)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (need 1 .. 2^26 matches)", who, n);
+    if ((rc = model_check_n(n, who))) return rc;
     if (!d_segment || !d_ransac_mask || !d_original_mask || !d_spec_info)
         return apap::fail(APAP_ERR_INVALID_ARG, "%s: null spectral output", who);
     const size_t spec_bytes = apap_spectral_workspace_bytes(n);
     const ModelLayout L = model_layout(n);
-    if ((rc = model_check_device_args(n, d_src, d_dst, d_ransac_mask, d_H, d_info, d_work, work_bytes, spec_bytes + L.total, who)))
+    if ((rc = model_check_device_args(d_src, d_dst, d_ransac_mask, d_H, d_info, d_work, work_bytes, spec_bytes + L.total, who)))
         return rc;
     void *d_model_work = (char *)d_work + spec_bytes;
     hipStream_t s = (hipStream_t)stream;

@@ -1,6 +1,7 @@
-// Device half of the M-step, shared by apap_model.hip (one problem per launch) and apap_em_batch.hip (one launch for a
-// batch of problems): constants, workspace layout, the interior-point method and the bodies of M1 and M2.  A body takes
-// the index of its block within its problem as `bx`; both forms run the same arithmetic in the same order.
+// Device half of the M-step, shared by apap_model.hip (one problem per launch), apap_em_batch.hip (one launch for a batch
+// of problems) and apap_local_model.hip (one problem per mesh cell): constants, workspace layout, the interior-point method
+// and the bodies of M1, M2 and the Huber kernel, every step that two of them share defined once.  A body takes the index of
+// its block within its problem as `bx`; every form runs the same arithmetic in the same order.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,15 +38,9 @@ ModelLayout model_layout(int n) {
     if (rounds < kMinRounds) rounds = kMinRounds;
     L.per_block = rounds * kPair;
     L.nb = (n + L.per_block - 1) / L.per_block;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) / 256 * 256;
-        return at;
-    };
-    L.R = take((size_t)L.nb * kC * kC * sizeof(double));
-    L.cnt = take((size_t)L.nb * sizeof(int));
-    L.total = off;
+    L.R = 0;
+    L.cnt = L.R + apap::up256((size_t)L.nb * kC * kC * sizeof(double));
+    L.total = L.cnt + apap::up256((size_t)L.nb * sizeof(int));
     return L;
 }
 
@@ -54,6 +49,10 @@ struct ModelScalars {
     float du32, dv32;
     double floor, du, dv;
 };
+
+// Whether a match of weight `w` takes part (model_solve: `if w <= floor: continue`).  numpy 1.x compares the float32 scalar
+// with the Python float in float64, and so does this: float32(1e-3) > 1e-3 is kept.  A NaN weight is dropped.
+__device__ __forceinline__ bool model_selected(float w, const ModelScalars &sc) { return !sc.use_floor || (double)w > sc.floor; }
 
 __device__ __forceinline__ double wsum(double v) {
 #pragma unroll
@@ -138,7 +137,7 @@ __device__ __forceinline__ void model_tsqr_body(const float2 *__restrict__ pc, c
         if (r >= 0 && r < 2 * kPair && i < end) {
             const float2 c = pc[i];
             const float wi = weight(i, c);
-            keep = !sc.use_floor || (double)wi > sc.floor;   // numpy 1.x: float32 scalar vs Python float in float64
+            keep = model_selected(wi, sc);
             if (keep) k_row(a, c, po[i], wi, r & 1, sc);
         }
         if (lane >= kC && !keep) {
@@ -250,37 +249,49 @@ __device__ void inverse_from_chol(const double *T, double *W2, double *Si, int l
     __syncthreads();
 }
 
-// 10 x 10 Cholesky solve of M dx = rhs on lane 0 (M in L.M, overwritten); dx to L.dx.  false: M not positive definite.
-__device__ bool schur_solve(Lds &L, int lane) {
+// Serial Cholesky solve of the N x N system M x = b on one thread: M = L L^T in place (row-major, the lower triangle is read
+// and overwritten), L y = b, L^T x = y.  b and y may be the same array.  One operation order for every caller: pivot
+// p = M[kk] - sum M[kj]^2, column (M[ik] - sum M[ij] M[kj]) / d.  `reject(p)` is the caller's test of a pivot: at the
+// first rejected one the factorisation stops, x is left as it was and the result is false.  The factor loop is unrolled by
+// name: rolled, as the compiler leaves it at N = 8, the Huber call measured 10 - 20 us (3 - 5 %) slower.
+template <int N, class Reject>
+__device__ __forceinline__ bool chol_solve(double *M, const double *b, double *y, double *x, Reject reject) {
+    bool good = true;
+#pragma unroll
+    for (int k = 0; k < N && good; ++k) {
+        double p = M[k * N + k];
+        for (int j = 0; j < k; ++j) p -= M[k * N + j] * M[k * N + j];
+        if (reject(p)) good = false;
+        const double d = sqrt(p);
+        M[k * N + k] = d;
+        for (int i = k + 1; i < N; ++i) {
+            double s = M[i * N + k];
+            for (int j = 0; j < k; ++j) s -= M[i * N + j] * M[k * N + j];
+            M[i * N + k] = s / d;
+        }
+    }
+    if (good) {
+        for (int i = 0; i < N; ++i) {
+            double s = b[i];
+            for (int j = 0; j < i; ++j) s -= M[i * N + j] * y[j];
+            y[i] = s / M[i * N + i];
+        }
+        for (int i = N - 1; i >= 0; --i) {
+            double s = y[i];
+            for (int j = i + 1; j < N; ++j) s -= M[j * N + i] * x[j];
+            x[i] = s / M[i * N + i];
+        }
+    }
+    return good;
+}
+
+// 10 x 10 Cholesky solve of M dx = rhs on lane 0 (M in L.M, overwritten); dx to L.dx.  false: M not positive definite.  The
+// only test is the pivot's sign: a stricter one would change which iterate an SDP that leaves the cone returns.  Forced
+// inline: left to the compiler, the two calls in ipm() become calls of one out-of-line function.
+__device__ __forceinline__ bool schur_solve(Lds &L, int lane) {
     if (lane == 0) {
-        double *M = L.M;
-        bool good = true;
-        for (int k = 0; k < kV && good; ++k) {
-            double p = M[k * kV + k];
-            for (int j = 0; j < k; ++j) p -= M[k * kV + j] * M[k * kV + j];
-            if (!(p > 0.0)) good = false;
-            const double d = sqrt(p);
-            M[k * kV + k] = d;
-            for (int i = k + 1; i < kV; ++i) {
-                double s = M[i * kV + k];
-                for (int j = 0; j < k; ++j) s -= M[i * kV + j] * M[k * kV + j];
-                M[i * kV + k] = s / d;
-            }
-        }
-        if (good) {
-            double y[kV];
-            for (int i = 0; i < kV; ++i) {
-                double s = L.rhs[i];
-                for (int j = 0; j < i; ++j) s -= M[i * kV + j] * y[j];
-                y[i] = s / M[i * kV + i];
-            }
-            for (int i = kV - 1; i >= 0; --i) {
-                double s = y[i];
-                for (int j = i + 1; j < kV; ++j) s -= M[j * kV + i] * L.dx[j];
-                L.dx[i] = s / M[i * kV + i];
-            }
-        }
-        L.flag = good;
+        double y[kV];
+        L.flag = chol_solve<kV>(L.M, L.rhs, y, L.dx, [](double p) { return !(p > 0.0); });
     }
     __syncthreads();
     return L.flag != 0;
@@ -436,9 +447,8 @@ __device__ __forceinline__ double pow2_near(double x) {
     return ldexp(1.0, m >= 0.70710678118654752440 ? e : e - 1);
 }
 
-// The tail of model_solve_body for the Huber kernel (model.py:50-56): float32 solution, [2, 2] = 1; with `invert`
-// numpy.linalg.inv (fp64 LU, cast back) and / [2, 2] in float32.  ORs APAP_STATUS_SINGULAR into `word` when the inverse meets a
-// zero pivot.  (M2 keeps its own lines, so that its code is what it was.)
+// The tail of M2 and of the Huber kernel (model.py:50-56): float32 solution, [2, 2] = 1; with `invert` numpy.linalg.inv
+// (fp64 LU, cast back) and / [2, 2] in float32.  ORs APAP_STATUS_SINGULAR into `word` when the inverse meets a zero pivot.
 __device__ __forceinline__ void model_tail(const double (&h)[8], bool invert, float (&sol)[9], int &word) {
     for (int k = 0; k < 8; ++k) sol[k] = (float)h[k];
     sol[8] = 1.0f;
@@ -535,19 +545,8 @@ __device__ __forceinline__ void model_solve_body(const double *__restrict__ Rb, 
     if (lane != 0) return;
     double h[8];
     for (int k = 0; k < 8; ++k) h[k] = degenerate ? NAN : sigma * L.d[k] * hq[k];
-    // model.py:50-56: float32 solution, [2, 2] = 1; with swap numpy.linalg.inv (fp64 LU, cast back) and / [2, 2] in float32
     float sol[9];
-    for (int k = 0; k < 8; ++k) sol[k] = (float)h[k];
-    sol[8] = 1.0f;
-    if (sc.swap && !degenerate) {
-        double m[9], r[9];
-        for (int k = 0; k < 9; ++k) m[k] = (double)sol[k];
-        if (!apap::inv3(m, r)) word |= APAP_STATUS_SINGULAR;
-        float q[9];
-        for (int k = 0; k < 9; ++k) q[k] = (float)r[k];
-        const float d = q[8];
-        for (int k = 0; k < 9; ++k) sol[k] = q[k] / d;
-    }
+    model_tail(h, sc.swap && !degenerate, sol, word);
     for (int k = 0; k < 9; ++k) H[k] = degenerate ? NAN : sol[k];
     info[APAP_MODEL_INFO_OBJECTIVE] = objective;
     info[APAP_MODEL_INFO_R] = r_out;
@@ -602,6 +601,37 @@ __device__ __forceinline__ double huber_dot(const double (&as)[8], const double 
     return r;
 }
 
+// The residual of a row at h.
+__device__ __forceinline__ double huber_residual(const double (&as)[8], const double (&h)[8], double rhs) {
+    return huber_dot(as, h) - rhs;
+}
+
+// phi_M(r): r^2 within [-M, M], 2 M |r| - M^2 beyond.
+__device__ __forceinline__ double huber_phi(double r, double M) {
+    const double ar = fabs(r);
+    return ar > M ? 2.0 * M * ar - M * M : r * r;
+}
+
+// The walk of every pass: f(as, rhs) for row 2 i + odd (scaled by s) of every selected match i = tid, tid + kHuberThreads, ..
+// in ascending order, even row first.  Which matches a thread sums, and in which order, is what makes every entry form give
+// the same bytes: it is decided here and nowhere else.  `f` captures the caller's accumulators by reference; all of this
+// is inlined, so they stay in registers.
+template <class F>
+__device__ __forceinline__ void huber_rows(const float2 *__restrict__ pc, const float2 *__restrict__ po, const float *__restrict__ w,
+                                           int n, const ModelScalars &sc, const double (&s)[8], int tid, F f) {
+    for (int i = tid; i < n; i += kHuberThreads) {
+        const float wi = w[i];
+        if (!model_selected(wi, sc)) continue;
+        const float2 c = pc[i], o = po[i];
+#pragma unroll
+        for (int odd = 0; odd < 2; ++odd) {
+            double as[8], rhs;
+            huber_row(as, rhs, c, o, wi, odd, sc, s);
+            f(as, rhs);
+        }
+    }
+}
+
 // The sums of `acc` over the workgroup into L.tot (valid on thread 0 only, which goes on to use them; the caller ends the
 // step with a barrier).
 template <int K>
@@ -628,28 +658,9 @@ __device__ bool huber_chol_solve(HuberLds &L, double sign) {
     int e = 0;
     for (int k = 0; k < 8; ++k)
         for (int l = k; l < 8; ++l, ++e) G[k * 8 + l] = G[l * 8 + k] = L.tot[e];
-    for (int k = 0; k < 8; ++k) {
-        double p = G[k * 8 + k];
-        for (int j = 0; j < k; ++j) p -= G[k * 8 + j] * G[k * 8 + j];
-        if (!(p > 0.0) || isinf(p)) return false;
-        const double d = sqrt(p);
-        G[k * 8 + k] = d;
-        for (int i = k + 1; i < 8; ++i) {
-            double t = G[i * 8 + k];
-            for (int j = 0; j < k; ++j) t -= G[i * 8 + j] * G[k * 8 + j];
-            G[i * 8 + k] = t / d;
-        }
-    }
-    for (int i = 0; i < 8; ++i) {
-        double t = sign * L.tot[36 + i];
-        for (int j = 0; j < i; ++j) t -= G[i * 8 + j] * L.y[j];
-        L.y[i] = t / G[i * 8 + i];
-    }
-    for (int i = 7; i >= 0; --i) {
-        double t = L.y[i];
-        for (int j = i + 1; j < 8; ++j) t -= G[j * 8 + i] * L.d[j];
-        L.d[i] = t / G[i * 8 + i];
-    }
+    for (int i = 0; i < 8; ++i) L.y[i] = sign * L.tot[36 + i];
+    // besides the sign, an infinite pivot (an overflowed Gram entry) and a non-finite solution are refused
+    if (!chol_solve<8>(G, L.y, L.y, L.d, [](double p) { return !(p > 0.0) || isinf(p); })) return false;
     for (int i = 0; i < 8; ++i)
         if (!isfinite(L.d[i])) return false;
     return true;
@@ -671,42 +682,36 @@ __device__ __forceinline__ void huber_pass_gram(const float2 *__restrict__ pc, c
     }
 #pragma unroll
     for (int k = 0; k < kHuberAcc; ++k) acc[k] = 0.0;
-    for (int i = tid; i < n; i += kHuberThreads) {
-        const float wi = w[i];
-        if (sc.use_floor && !((double)wi > sc.floor)) continue;
-        const float2 c = pc[i], o = po[i];
-#pragma unroll
-        for (int odd = 0; odd < 2; ++odd) {
-            double as[8], rhs;
-            huber_row(as, rhs, c, o, wi, odd, sc, s);
-            const double r = huber_dot(as, h) - rhs;
-            const double ar = fabs(r);
-            const bool clipped = ar > M;
-            const double sg = r > 0.0 ? M : -M;
-            double omega, coef;
-            if (kind == kHuberMajorise) {
-                omega = clipped ? M / ar : 1.0;
-                coef = omega * r;
-            } else if (kind == kHuberDual) {
-                omega = 1.0;
-                coef = clipped ? 2.0 * sg : 2.0 * r;
-            } else {
-                omega = clipped ? 0.0 : 1.0;
-                coef = clipped ? sg : r;
-            }
-            int e = 0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const double t = omega * as[k];
-#pragma unroll
-                for (int l = k; l < 8; ++l, ++e) acc[e] += t * as[l];
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) acc[36 + k] += as[k] * coef;
-            acc[44] += clipped ? 2.0 * M * ar - M * M : r * r;
-            acc[45] += clipped ? 1.0 : 0.0;
+    huber_rows(pc, po, w, n, sc, s, tid, [&](const double (&as)[8], double rhs) {
+        const double r = huber_residual(as, h, rhs);
+        const double ar = fabs(r);
+        const bool clipped = ar > M;
+        const double sg = r > 0.0 ? M : -M;
+        double omega, coef;
+        if (kind == kHuberMajorise) {
+            omega = clipped ? M / ar : 1.0;
+            coef = omega * r;
+        } else if (kind == kHuberDual) {
+            // y = 2 clip(r, -M, M).  Not the gap walk's fmin / fmax spelling: the two differ at a NaN residual (NaN here,
+            // -2 M there), so each keeps its own.
+            omega = 1.0;
+            coef = clipped ? 2.0 * sg : 2.0 * r;
+        } else {
+            omega = clipped ? 0.0 : 1.0;
+            coef = clipped ? sg : r;
         }
-    }
+        int e = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const double t = omega * as[k];
+#pragma unroll
+            for (int l = k; l < 8; ++l, ++e) acc[e] += t * as[l];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[36 + k] += as[k] * coef;
+        acc[44] += huber_phi(r, M);
+        acc[45] += clipped ? 1.0 : 0.0;
+    });
     huber_reduce(acc, L, tid);
     if (tid == 0) {
         L.f = L.tot[44];
@@ -732,28 +737,16 @@ __device__ __forceinline__ void huber_pass_line(const float2 *__restrict__ pc, c
     }
 #pragma unroll
     for (int k = 0; k <= kHuberHalvings; ++k) acc[k] = 0.0;
-    for (int i = tid; i < n; i += kHuberThreads) {
-        const float wi = w[i];
-        if (sc.use_floor && !((double)wi > sc.floor)) continue;
-        const float2 c = pc[i], o = po[i];
+    huber_rows(pc, po, w, n, sc, s, tid, [&](const double (&as)[8], double rhs) {
+        const double r = huber_residual(as, h, rhs);
+        const double ad = huber_dot(as, d);
+        double alpha = 1.0;
 #pragma unroll
-        for (int odd = 0; odd < 2; ++odd) {
-            double as[8], rhs;
-            huber_row(as, rhs, c, o, wi, odd, sc, s);
-            const double r = huber_dot(as, h) - rhs;
-            const double ad = huber_dot(as, d);
-            double alpha = 1.0;
-#pragma unroll
-            for (int j = 0; j < kHuberHalvings; ++j, alpha *= 0.5) {
-                const double rr = r + alpha * ad;
-                const double ar = fabs(rr);
-                acc[j] += ar > M ? 2.0 * M * ar - M * M : rr * rr;
-            }
-            const double r1 = r + ad;
-            const int s0 = r > M ? 1 : (r < -M ? -1 : 0), s1 = r1 > M ? 1 : (r1 < -M ? -1 : 0);
-            acc[kHuberHalvings] += s0 != s1 ? 1.0 : 0.0;
-        }
-    }
+        for (int j = 0; j < kHuberHalvings; ++j, alpha *= 0.5) acc[j] += huber_phi(r + alpha * ad, M);
+        const double r1 = r + ad;
+        const int s0 = r > M ? 1 : (r < -M ? -1 : 0), s1 = r1 > M ? 1 : (r1 < -M ? -1 : 0);
+        acc[kHuberHalvings] += s0 != s1 ? 1.0 : 0.0;
+    });
     huber_reduce(acc, L, tid);
     if (tid == 0) {
         if (newton && L.tot[kHuberHalvings] == 0.0 && L.tot[0] <= L.f) {
@@ -794,18 +787,10 @@ __device__ __forceinline__ void model_huber_body(const float2 *__restrict__ pc, 
             acc[k] = 0.0;
             one[k] = 1.0;
         }
-        for (int i = tid; i < n; i += kHuberThreads) {
-            const float wi = w[i];
-            if (sc.use_floor && !((double)wi > sc.floor)) continue;
-            const float2 c = pc[i], o = po[i];
+        huber_rows(pc, po, w, n, sc, one, tid, [&](const double (&a)[8], double) {
 #pragma unroll
-            for (int odd = 0; odd < 2; ++odd) {
-                double a[8], rhs;
-                huber_row(a, rhs, c, o, wi, odd, sc, one);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) acc[k] += a[k] * a[k];
-            }
-        }
+            for (int k = 0; k < 8; ++k) acc[k] += a[k] * a[k];
+        });
         huber_reduce(acc, L, tid);
         if (tid == 0) {
             for (int k = 0; k < 8; ++k) {
@@ -852,22 +837,14 @@ __device__ __forceinline__ void model_huber_body(const float2 *__restrict__ pc, 
             h[k] = L.h[k];
             z[k] = L.d[k];
         }
-        for (int i = tid; i < n; i += kHuberThreads) {
-            const float wi = w[i];
-            if (sc.use_floor && !((double)wi > sc.floor)) continue;
-            const float2 c = pc[i], o = po[i];
-#pragma unroll
-            for (int odd = 0; odd < 2; ++odd) {
-                double as[8], rhs;
-                huber_row(as, rhs, c, o, wi, odd, sc, s);
-                const double r = huber_dot(as, h) - rhs;
-                const double y = 2.0 * fmin(fmax(r, -M), M);
-                const double yp = y - huber_dot(as, z);
-                acc[0] += yp * yp;
-                acc[1] += rhs * yp;
-                big = fmax(big, fabs(yp));
-            }
-        }
+        huber_rows(pc, po, w, n, sc, s, tid, [&](const double (&as)[8], double rhs) {
+            const double r = huber_residual(as, h, rhs);
+            const double y = 2.0 * fmin(fmax(r, -M), M);   // -2 M at a NaN residual (huber_pass_gram's spelling gives NaN)
+            const double yp = y - huber_dot(as, z);
+            acc[0] += yp * yp;
+            acc[1] += rhs * yp;
+            big = fmax(big, fabs(yp));
+        });
 #pragma unroll
         for (int o = kW / 2; o > 0; o >>= 1) big = fmax(big, __shfl_xor(big, o));
         if ((tid & (kW - 1)) == 0) L.part[tid / kW][2] = big;
@@ -932,6 +909,20 @@ int model_check_huber(const ModelScalars &sc, int n, const char *who) {
     if (n > kHuberMaxN)
         return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (the Huber M-step serves 1 .. 2^20 matches)", who, n);
     return APAP_OK;
+}
+
+constexpr int kModelMaxN = 1 << 26;
+
+int model_check_n(int n, const char *who) {
+    if (n < 1 || n > kModelMaxN) return apap::fail(APAP_ERR_INVALID_ARG, "%s: n=%d (need 1 .. 2^26 matches)", who, n);
+    return APAP_OK;
+}
+
+// What the EM loop fixes, whatever the caller's block says: model_solve's `if w <= 1e-3: continue` and its swap default.
+void model_em_scalars(ModelScalars &sc) {
+    sc.use_floor = 1;
+    sc.floor = 1e-3;
+    sc.swap = 1;
 }
 
 }  // namespace
