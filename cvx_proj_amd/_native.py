@@ -194,6 +194,18 @@ SIGNATURES = {
     "apap_match_descriptors_batch": (C.c_int, [_vp, _f32p, _f32p, _i32p, _i32p, C.c_int, _i32p, _f32p, _i32p, _f32p, C.c_int]),
     "apap_match_descriptors_batch_device": (C.c_int, [_vp, _vp, _vp, _i32p, _i32p, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
                                                       _vp]),
+    "apap_guided_records": (C.c_int, [_vp, _f32p, C.c_int, _f64p, C.c_int, _f64p, C.c_int]),
+    "apap_guided_records_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "apap_match_guided_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "apap_match_guided": (C.c_int, [_vp, _f64p, _f32p, C.c_int, _f64p, _f32p, C.c_int, C.c_int, C.c_double, _i32p, _f32p, _i32p,
+                                    _f32p, _i32p, _i32p, _f32p, C.c_int]),
+    "apap_match_guided_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, C.c_size_t, _vp]),
+    "apap_match_guided_batch_workspace_bytes": (C.c_size_t, [_i32p, _i32p, C.c_int]),
+    "apap_match_guided_batch": (C.c_int, [_vp, _f64p, _f64p, _f32p, _f32p, _i32p, _i32p, C.c_int, C.c_int, _f64p, _i32p, _f32p,
+                                          _i32p, _f32p, _i32p, _i32p, _f32p, C.c_int]),
+    "apap_match_guided_batch_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32p, _i32p, C.c_int, C.c_int, _f64p, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "apap_sift_window": (C.c_int, [_f32p]),
     "apap_sift_taps": (C.c_int, [_f32p]),
     "apap_sift_workspace_bytes": (C.c_size_t, [C.c_int]),
@@ -1450,6 +1462,112 @@ def match_descriptors_batch(q, t, q_lengths, t_lengths, second=True, device=-1, 
                                              len(qo) - 1, _ptr(idx, C.c_int), _ptr(dist, C.c_float), _ptr(idx2, C.c_int),
                                              _ptr(dist2, C.c_float), device))
     return idx, dist, idx2, dist2
+
+
+# ---------------------------------------------------------------- guided descriptor matching: the matcher under a gate
+GUIDED_REC_POINT, GUIDED_REC_PROJECT, GUIDED_REC_LINE = 0, 1, 2     # APAP_GUIDED_REC_*
+GUIDED_POINT, GUIDED_LINE = 0, 1                                    # APAP_GUIDED_*: the gate
+GUIDED_QUERY_TILE = 256         # APAP_GUIDED_QUERY_TILE: queries per block, one per lane
+GUIDED_TRAIN_CHUNK = 128        # APAP_GUIDED_TRAIN_CHUNK: train records per staged chunk
+GUIDED_DRAIN = 64               # APAP_GUIDED_DRAIN: survivors a wave sums at once
+GUIDED_WANT_BLOCKS = 1024       # APAP_GUIDED_WANT_BLOCKS
+GUIDED_WHAT = {"point": GUIDED_REC_POINT, "project": GUIDED_REC_PROJECT, "line": GUIDED_REC_LINE}
+GUIDED_KIND = {"point": GUIDED_POINT, "line": GUIDED_LINE}
+
+
+def guided_splits(nq, nt):
+    """``match_splits`` for the guided matcher's tiling: (splits of the train axis, chunks of each)."""
+    q_tiles = -(-int(nq) // GUIDED_QUERY_TILE)
+    chunks = -(-int(nt) // GUIDED_TRAIN_CHUNK)
+    per = -(-chunks // min(chunks, -(-GUIDED_WANT_BLOCKS // q_tiles)))
+    return -(-chunks // per), per
+
+
+def guided_what(what):
+    """'point' | 'project' | 'line' (or the constant) -> APAP_GUIDED_REC_*."""
+    if what not in GUIDED_WHAT and what not in GUIDED_WHAT.values():
+        raise ValueError(f"what must be one of {sorted(GUIDED_WHAT)}; got {what!r}")
+    return GUIDED_WHAT.get(what, what)
+
+
+def guided_kind(kind):
+    """'point' | 'line' (or the constant) -> APAP_GUIDED_POINT / APAP_GUIDED_LINE."""
+    if kind not in GUIDED_KIND and kind not in GUIDED_KIND.values():
+        raise ValueError(f"kind must be one of {sorted(GUIDED_KIND)}; got {kind!r}")
+    return GUIDED_KIND.get(kind, kind)
+
+
+def guided_r2(r2, n_pairs):
+    """The squared radius of every pair (a number, or one per pair) as float64: >= 0 or +inf, as the library checks it."""
+    r2 = np.ascontiguousarray(np.broadcast_to(np.asarray(r2, dtype=np.float64), (n_pairs,)))
+    if not np.all(r2 >= 0):
+        raise ValueError(f"r2 must be >= 0 (or +inf); got {r2.tolist()}")
+    return r2
+
+
+def as_guided_model(model, what):
+    """The 3 x 3 model of a record as 9 contiguous float64, or None; 'project' and 'line' need one."""
+    if model is None:
+        if what != GUIDED_REC_POINT:
+            raise ValueError("records: a model is needed unless what='point'")
+        return None
+    m = np.ascontiguousarray(model, dtype=np.float64)
+    if m.size != 9:
+        raise ValueError(f"records: the model must hold 9 values; got {m.shape}")
+    return m.reshape(9)
+
+
+def as_guided_records(rec, n, name):
+    rec = np.ascontiguousarray(rec, dtype=np.float64)
+    if rec.shape != (n, 3):
+        raise ValueError(f"{name} must be ({n}, 3) float64 records; got {rec.shape}")
+    return rec
+
+
+def guided_records(pts, model=None, what="point", device=-1, ctx=None):
+    """``apap_guided_records``: the (n, 3) float64 records of ``pts`` (n, 2) float32 under ``model`` (3 x 3, float64)."""
+    what = guided_what(what)
+    pts = np.ascontiguousarray(pts, dtype=np.float32)
+    if pts.ndim != 2 or pts.shape[1] != 2 or not 1 <= len(pts) <= MATCH_MAX_ROWS:
+        raise ValueError(f"records: pts must be (n, 2) with 1 <= n <= 2^24; got {pts.shape}")
+    m = as_guided_model(model, what)
+    rec = np.empty((len(pts), 3), np.float64)
+    check(lib().apap_guided_records(_h(ctx), _ptr(pts, C.c_float), len(pts), _ptr(m, C.c_double), what, _ptr(rec, C.c_double), device))
+    return rec
+
+
+def match_guided_batch(q, t, rec_q, rec_t, q_lengths, t_lengths, kind, r2, second=True, count=True, reverse=False, device=-1,
+                       ctx=None):
+    """``apap_match_guided_batch``: ``match_descriptors_batch`` under the gate ``kind`` with the squared radius ``r2`` (a number
+    or one per pair).  Returns (idx, dist, idx2, dist2, count, ridx, rdist): the first five laid out like ``q``, the
+    last two like ``t``; whatever was not asked for is ``None``."""
+    kind = guided_kind(kind)
+    q, t = as_descriptors(q, "q"), as_descriptors(t, "t")
+    if len(q_lengths) != len(t_lengths):
+        raise ValueError(f"match_guided_batch: {len(q_lengths)} query counts, {len(t_lengths)} train counts")
+    qo, to = match_offsets(q_lengths, "q_lengths"), match_offsets(t_lengths, "t_lengths")
+    if qo[-1] != len(q) or to[-1] != len(t):
+        raise ValueError(f"match_guided_batch: the counts sum to {qo[-1]} and {to[-1]} rows; got {len(q)} and {len(t)}")
+    rec_q, rec_t = as_guided_records(rec_q, len(q), "rec_q"), as_guided_records(rec_t, len(t), "rec_t")
+    r2 = guided_r2(r2, len(qo) - 1)
+    idx, dist = np.empty(len(q), np.int32), np.empty(len(q), np.float32)
+    idx2, dist2 = (np.empty(len(q), np.int32), np.empty(len(q), np.float32)) if second else (None, None)
+    cnt = np.empty(len(q), np.int32) if count else None
+    ridx, rdist = (np.empty(len(t), np.int32), np.empty(len(t), np.float32)) if reverse else (None, None)
+    check(lib().apap_match_guided_batch(_h(ctx), _ptr(rec_q, C.c_double), _ptr(rec_t, C.c_double), _ptr(q, C.c_float),
+                                        _ptr(t, C.c_float), _ptr(qo, C.c_int), _ptr(to, C.c_int), len(qo) - 1, kind,
+                                        _ptr(r2, C.c_double), _ptr(idx, C.c_int), _ptr(dist, C.c_float), _ptr(idx2, C.c_int),
+                                        _ptr(dist2, C.c_float), _ptr(cnt, C.c_int), _ptr(ridx, C.c_int), _ptr(rdist, C.c_float), device))
+    return idx, dist, idx2, dist2, cnt, ridx, rdist
+
+
+def match_guided(q, t, rec_q, rec_t, kind, r2, second=True, count=True, reverse=False, device=-1, ctx=None):
+    """``apap_match_guided``: one pair (the batch of one)."""
+    q, t = as_descriptors(q, "q"), as_descriptors(t, "t")
+    if not 1 <= len(q) <= MATCH_MAX_ROWS or not 1 <= len(t) <= MATCH_MAX_ROWS:
+        raise ValueError(f"match_guided: {len(q)} queries, {len(t)} train rows (1 .. 2^24 each)")
+    return match_guided_batch(q, t, rec_q, rec_t, [len(q)], [len(t)], kind, r2, second=second, count=count, reverse=reverse,
+                              device=device, ctx=ctx)
 
 
 # ---------------------------------------------------------------- descriptor extraction: SIFT at given keypoints

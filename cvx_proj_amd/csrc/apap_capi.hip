@@ -1385,6 +1385,79 @@ int apap_match_descriptors(apap_ctx *ctx, const float *q, int nq, const float *t
     return apap_match_descriptors_batch(ctx, q, t, qo, to, 1, idx, dist, idx2, dist2, device);
 }
 
+// ------------------------------------------------------------------ guided descriptor matching (apap_match_guided.hip)
+int apap_guided_records(apap_ctx *ctx, const float *pts, int n, const double *model, int what, double *rec_out, int device) {
+    const char *who = "apap_guided_records";
+    int rc = apap::guided_records_check(n, model, what, who);
+    if (rc) return rc;
+    if (!pts || !rec_out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    Layout io = call.layout(S_AUX);
+    const Part d_pts = io.take((size_t)n * 2 * sizeof(float)), d_model = io.take(model ? 9 * sizeof(double) : 0);
+    const Part d_rec = io.take((size_t)n * 3 * sizeof(double));
+    call.alloc(io);
+    call.up(d_pts, pts);
+    if (model) call.up(d_model, model);
+    if ((rc = call.rc())) return rc;
+    rc = apap_guided_records_device(ctx, d_pts.as<const float>(), n, model ? d_model.as<const double>() : nullptr, what,
+                                    d_rec.as<double>(), call.stream());
+    if (rc) return rc;
+    call.down(rec_out, d_rec);
+    return call.wait();
+}
+
+int apap_match_guided_batch(apap_ctx *ctx, const double *rec_q, const double *rec_t, const float *q, const float *t,
+                            const int *q_offset, const int *t_offset, int n_pairs, int kind, const double *r2, int *idx, float *dist,
+                            int *idx2, float *dist2, int *count, int *ridx, float *rdist, int device) {
+    const char *who = "apap_match_guided_batch";
+    if (!rec_q || !rec_t || !q || !t || !q_offset || !t_offset || !r2 || !idx || !dist)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    if (!ridx != !rdist) return apap::fail(APAP_ERR_INVALID_ARG, "%s: ridx and rdist go together (both or neither)", who);
+    int rc = apap::guided_check(q_offset, t_offset, n_pairs, kind, r2, who);
+    if (rc) return rc;
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    const size_t q0 = (size_t)q_offset[0], t0 = (size_t)t_offset[0];   // the device arrays start at the first pair
+    const size_t NQ = (size_t)q_offset[n_pairs] - q0, NT = (size_t)t_offset[n_pairs] - t0;
+    const std::vector<int> qrel = relative_offsets(q_offset, n_pairs), trel = relative_offsets(t_offset, n_pairs);
+    Layout io = call.layout(S_AUX);
+    const size_t row = APAP_MATCH_DIM * sizeof(float), rec = 3 * sizeof(double);
+    const Part d_q = io.take(NQ * row), d_t = io.take(NT * row), d_rq = io.take(NQ * rec), d_rt = io.take(NT * rec);
+    const Part d_idx = io.take(NQ * sizeof(int)), d_dist = io.take(NQ * sizeof(float));
+    const Part d_idx2 = io.take(idx2 ? NQ * sizeof(int) : 0), d_dist2 = io.take(dist2 ? NQ * sizeof(float) : 0);
+    const Part d_count = io.take(count ? NQ * sizeof(int) : 0);
+    const Part d_ridx = io.take(ridx ? NT * sizeof(int) : 0), d_rdist = io.take(ridx ? NT * sizeof(float) : 0);
+    call.alloc(io);
+    const Part work = call.slot(S_WORK, apap_match_guided_batch_workspace_bytes(qrel.data(), trel.data(), n_pairs));
+    call.up(d_q, q + q0 * APAP_MATCH_DIM);
+    call.up(d_t, t + t0 * APAP_MATCH_DIM);
+    call.up(d_rq, rec_q + q0 * 3);
+    call.up(d_rt, rec_t + t0 * 3);
+    if ((rc = call.rc())) return rc;
+    rc = apap_match_guided_batch_device(ctx, d_rq.as<const double>(), d_rt.as<const double>(), d_q.as<const float>(),
+                                        d_t.as<const float>(), qrel.data(), trel.data(), n_pairs, kind, r2, d_idx.as<int>(),
+                                        d_dist.as<float>(), idx2 ? d_idx2.as<int>() : nullptr, dist2 ? d_dist2.as<float>() : nullptr,
+                                        count ? d_count.as<int>() : nullptr, ridx ? d_ridx.as<int>() : nullptr,
+                                        ridx ? d_rdist.as<float>() : nullptr, work.as<void>(), work.bytes, call.stream());
+    if (rc) return rc;
+    call.down(idx + q0, d_idx);
+    call.down(dist + q0, d_dist);
+    if (idx2) call.down(idx2 + q0, d_idx2);
+    if (dist2) call.down(dist2 + q0, d_dist2);
+    if (count) call.down(count + q0, d_count);
+    if (ridx) call.down(ridx + t0, d_ridx);
+    if (ridx) call.down(rdist + t0, d_rdist);
+    return call.wait();
+}
+
+int apap_match_guided(apap_ctx *ctx, const double *rec_q, const float *q, int nq, const double *rec_t, const float *t, int nt,
+                      int kind, double r2, int *idx, float *dist, int *idx2, float *dist2, int *count, int *ridx, float *rdist,
+                      int device) {
+    const int qo[2] = {0, nq}, to[2] = {0, nt};
+    return apap_match_guided_batch(ctx, rec_q, rec_t, q, t, qo, to, 1, kind, &r2, idx, dist, idx2, dist2, count, ridx, rdist, device);
+}
+
 // ------------------------------------------------------------------ descriptor extraction (apap_sift.hip)
 int apap_sift_describe_batch(apap_ctx *ctx, const uint8_t *const *imgs, const int *heights, const int *widths, const int *channels,
                              int n_images, const float *pts, const int *pt_offset, float *out, int device) {

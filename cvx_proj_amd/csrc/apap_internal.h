@@ -214,6 +214,10 @@ int spectral_em_batch_check(const int *pair_offset, int n_pairs, const int *pair
 int local_model_check(int n, int cells, double gamma, double sigma, const double *params, const char *who);
 // The argument checks of the descriptor matcher's entry points (apap_match.hip) that need no device pointer.
 int match_check(const int *q_offset, const int *t_offset, int n_pairs, const char *who);
+// The argument checks of the guided matcher's entry points (apap_match_guided.hip) that need no device pointer: match_check,
+// then the kind and every pair's r2; and those of its records.
+int guided_check(const int *q_offset, const int *t_offset, int n_pairs, int kind, const double *r2, const char *who);
+int guided_records_check(int n, const void *model, int what, const char *who);
 // The argument checks of the fundamental-matrix entry points (apap_fundamental.hip) that need no device pointer.
 int fundamental_check(const int *pair_offset, int n_pairs, double thresh, int iterations, const char *who);
 // The argument checks of the notch denoising's entry points (apap_denoise.hip) that need no device pointer: the planes of a

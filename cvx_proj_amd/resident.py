@@ -628,6 +628,84 @@ def hip_match_descriptors(q, t, second=True, ctx=None, work=None):
     return hip_match_descriptors_batch(q, t, [q.shape[0]], [t.shape[0]], second=second, ctx=ctx, work=work)
 
 
+def hip_guided_records(pts, model=None, what="point", ctx=None):
+    """``apap_guided_records_device`` on the current stream, no host synchronisation: the (n, 3) float64 records of ``pts``
+    (n, 2) float32, a contiguous device tensor.  ``model``: a 3 x 3 (or 9-element) tensor on the same device - a device ``H`` of
+    ``find_homography`` or ``hip_spectral_em`` (float32 is widened on the device, exactly), a device ``F`` of
+    ``hip_fundamental`` - or ``None`` with ``what='point'``."""
+    _needs_device(pts, "hip_guided_records")
+    what = _native.guided_what(what)
+    dev = pts.device
+    if pts.dtype != torch.float32 or not pts.is_contiguous() or pts.dim() != 2 or pts.shape[1] != 2:
+        raise ValueError("hip_guided_records: pts must be a contiguous float32 (n, 2) tensor")
+    if model is None:
+        if what != _native.GUIDED_REC_POINT:
+            raise ValueError("hip_guided_records: a model is needed unless what='point'")
+    else:
+        if model.device != dev or model.numel() != 9:
+            raise ValueError(f"hip_guided_records: the model must hold 9 values on {dev}")
+        model = model.to(torch.float64).contiguous()
+    rec = torch.empty((pts.shape[0], 3), dtype=torch.float64, device=dev)
+    _native.check(_native.lib().apap_guided_records_device(
+        _native._h(ctx), pts.data_ptr(), pts.shape[0], None if model is None else model.data_ptr(), what, rec.data_ptr(), _stream(dev)))
+    return rec
+
+
+def guided_workspace_bytes(q_lengths, t_lengths=None):
+    """Scratch of ``hip_guided_match(…)`` as ``guided_workspace_bytes(nq, nt)``, or of ``hip_guided_match_batch`` with the
+    pairs' row counts.  0 for invalid arguments."""
+    if np.ndim(q_lengths) == 0:
+        return _native.lib().apap_match_guided_workspace_bytes(int(q_lengths), int(t_lengths))
+    qo, to = _native.match_offsets(q_lengths, "q_lengths"), _native.match_offsets(t_lengths, "t_lengths")
+    return _native.lib().apap_match_guided_batch_workspace_bytes(_ip(qo), _ip(to), min(len(qo), len(to)) - 1)
+
+
+def hip_guided_match_batch(q, t, rec_q, rec_t, q_lengths, t_lengths, kind, r2, second=True, count=True, reverse=False, ctx=None,
+                           work=None):
+    """``apap_match_guided_batch_device`` on the current stream of the tensors' device, no host synchronisation.  q / t:
+    contiguous float32 (N, 128) device tensors, rec_q / rec_t: contiguous float64 (N, 3) records (``hip_guided_records``), the
+    pairs concatenated; ``q_lengths``, ``t_lengths`` and the squared radius ``r2`` (a number, or one per pair) stay on the host.  Returns (idx,
+    dist, idx2, dist2, count, ridx, rdist), not synchronised: the first five laid out like ``q``, the last two like ``t``,
+    ``None`` for what was not asked for.  Same bytes as ``_native.match_guided_batch``, and per pair as ``hip_guided_match``."""
+    _needs_device(q, "hip_guided_match_batch")
+    dev = q.device
+    kind = _native.guided_kind(kind)
+    for x in (q, t):
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.device != dev or x.dim() != 2 or x.shape[1] != _native.MATCH_DIM:
+            raise ValueError(f"hip_guided_match_batch: descriptors must be contiguous float32 (n, {_native.MATCH_DIM}) tensors on {dev}")
+    for x, d in ((rec_q, q), (rec_t, t)):
+        if x.dtype != torch.float64 or not x.is_contiguous() or x.device != dev or tuple(x.shape) != (d.shape[0], 3):
+            raise ValueError(f"hip_guided_match_batch: records must be contiguous float64 ({d.shape[0]}, 3) tensors on {dev}")
+    if len(q_lengths) != len(t_lengths):
+        raise ValueError(f"hip_guided_match_batch: {len(q_lengths)} query counts, {len(t_lengths)} train counts")
+    qo, to = _native.match_offsets(q_lengths, "q_lengths"), _native.match_offsets(t_lengths, "t_lengths")
+    if qo[-1] != q.shape[0] or to[-1] != t.shape[0]:
+        raise ValueError(f"hip_guided_match_batch: the counts sum to {qo[-1]} and {to[-1]} rows; got {q.shape[0]} and {t.shape[0]}")
+    r2 = _native.guided_r2(r2, len(qo) - 1)
+    nq, nt = q.shape[0], t.shape[0]
+
+    def out(n, dtype, wanted=True):
+        return torch.empty(n, dtype=dtype, device=dev) if wanted else None
+    idx, dist = out(nq, torch.int32), out(nq, torch.float32)
+    idx2, dist2, cnt = out(nq, torch.int32, second), out(nq, torch.float32, second), out(nq, torch.int32, count)
+    ridx, rdist = out(nt, torch.int32, reverse), out(nt, torch.float32, reverse)
+    p_qo, p_to = _ip(qo), _ip(to)
+    work = _scratch(work, _native.lib().apap_match_guided_batch_workspace_bytes(p_qo, p_to, len(qo) - 1), dev)
+    ptr = lambda x: None if x is None else x.data_ptr()      # noqa: E731
+    _native.check(_native.lib().apap_match_guided_batch_device(
+        _native._h(ctx), rec_q.data_ptr(), rec_t.data_ptr(), q.data_ptr(), t.data_ptr(), p_qo, p_to, len(qo) - 1, kind,
+        _dp(r2), idx.data_ptr(), dist.data_ptr(), ptr(idx2), ptr(dist2), ptr(cnt), ptr(ridx), ptr(rdist),
+        work.data_ptr(), work.numel(), _stream(dev)))
+    return idx, dist, idx2, dist2, cnt, ridx, rdist
+
+
+def hip_guided_match(q, t, rec_q, rec_t, kind, r2, second=True, count=True, reverse=False, ctx=None, work=None):
+    """``apap_match_guided_device``: one pair, the batch of one (see ``hip_guided_match_batch``)."""
+    _needs_device(q, "hip_guided_match")
+    return hip_guided_match_batch(q, t, rec_q, rec_t, [q.shape[0]], [t.shape[0]], kind, r2, second=second, count=count,
+                                  reverse=reverse, ctx=ctx, work=work)
+
+
 def _image_table(imgs, dev, who):
     """The checks of a list of uint8 images on ``dev``, (h, w) grey or (h, w, 3) BGR - what ``_native.as_sift_image`` asks of a
     host array, with its side limits - and the batch entry points' (addresses, heights, widths, channels)."""

@@ -941,6 +941,71 @@ int apap_match_descriptors_batch_device(apap_ctx *ctx, const float *d_q, const f
                                         const int *t_offset, int n_pairs, int *d_idx, float *d_dist, int *d_idx2, float *d_dist2,
                                         void *d_work, size_t work_bytes, void *stream);
 
+/* ------------------------------------------------- guided descriptor matching: nearest and second-nearest under a gate --- */
+/* What recompute_matching's docstring asks for (spectral_method.py:35-64): apap_match_descriptors' answer, searched for every
+ * query only among the train rows that a geometric model allows - a homography within a radius, an epipolar line within a
+ * distance, a local-homography grid (DESIGN.md "Guided matching"; operation by operation in tests/guided_match_spec.py).
+ * Records: each keypoint of either side carries three float64, built by apap_guided_records[_device] from pts (n x 2
+ * float32) and model (9 doubles, row-major; a DEVICE pointer in the _device form).  With X = (double)x, Y = (double)y, every
+ * operation a single IEEE float64 operation in the order written:
+ *   APAP_GUIDED_REC_POINT     (X, Y, 1); the model is ignored and may be NULL
+ *   APAP_GUIDED_REC_PROJECT   u = (M0 X + M1 Y) + M2, v = (M3 X + M4 Y) + M5, s = (M6 X + M7 Y) + M8: (u / s, v / s, 1)
+ *   APAP_GUIDED_REC_LINE      ((M0 X + M1 Y) + M2, (M3 X + M4 Y) + M5, (M6 X + M7 Y) + M8)
+ * A NULL model is refused for the last two.  Non-finite coordinates and s = 0 are no errors: they give the record that IEEE
+ * arithmetic gives.  n outside 1 .. 2^24 and an unknown `what` are refused.
+ * Gate of a query record A and a train record B, under r2 (one double per pair; >= 0 or +inf, NaN and negative refused):
+ *   APAP_GUIDED_POINT   dx = B0 - A0, dy = B1 - A1, g = dx dx + dy dy; the pair passes iff g < r2
+ *   APAP_GUIDED_LINE    e = (A0 B0 + A1 B1) + A2, n = A0 A0 + A1 A1; the pair passes iff e e < r2 n
+ * The test is strict (the reference's dist < em_radius) and a NaN anywhere fails it: r2 = 0 passes nothing, r2 = +inf passes
+ * every pair of finite POINT records.
+ * Match: d2(i, j) is apap_match_descriptors' float32 value, bit for bit.  Over the train rows j that pass query i's gate:
+ *   idx, dist, idx2, dist2   as apap_match_descriptors': ordered by (d2, j), a NaN or infinite d2 never selected, dist the
+ *                            correctly rounded float32 square root, an empty slot -1 / +inf; idx2, dist2 may be NULL
+ *   count   nq int32, may be NULL: the train rows that pass the gate, whatever their d2
+ *   ridx, rdist   nt int32 / float32, both NULL to skip: for every train row the best query under the same predicate and the
+ *                 same d2, ordered by (d2, i) - what a mutual check needs, without a second call
+ * The outputs are a function of the inputs alone: no nq x nt buffer, no floating-point atomics, the same bytes from every
+ * entry point below, whatever the launch geometry and whatever else is in a batch.
+ * Batch: as apap_match_descriptors_batch - HOST q_offset / t_offset of n_pairs + 1 entries, records and descriptors
+ * concatenated, outputs laid out like the queries (ridx, rdist like the train rows), indices counted from the pair's own first
+ * row; one kind per call, r2[p] per pair (a HOST array in every form).  The launches do not depend on n_pairs (an upload of
+ * the pairs' table, a fill when ridx is asked for, two kernels); every pair's outputs equal its own single call's byte for
+ * byte (the single call is the batch of one).
+ * Refused before any device is touched: what apap_match_descriptors refuses, an unknown kind, a bad r2, ridx without rdist or
+ * the converse.  Without a GPU the host-buffer forms return APAP_ERR_NO_DEVICE: there is no CPU fallback.  The _device forms
+ * only enqueue on `stream` and do not wait.  d_work: at least apap_match_guided[_batch]_workspace_bytes (0 for invalid
+ * arguments; a 256-byte multiple): the table, 8 bytes per train row, 24 bytes per query and split of its pair's train axis.
+ * The tiling (for tests and sizing; no output depends on it): a block takes APAP_GUIDED_QUERY_TILE queries, one per lane; the
+ * train records go in chunks of APAP_GUIDED_TRAIN_CHUNK, dealt to min(chunks, ceil(APAP_GUIDED_WANT_BLOCKS / query tiles))
+ * splits of equal length (the last may be shorter); a wave sums its survivors' d2 whenever APAP_GUIDED_DRAIN of them wait. */
+#define APAP_GUIDED_REC_POINT 0
+#define APAP_GUIDED_REC_PROJECT 1
+#define APAP_GUIDED_REC_LINE 2
+#define APAP_GUIDED_POINT 0
+#define APAP_GUIDED_LINE 1
+#define APAP_GUIDED_QUERY_TILE 256
+#define APAP_GUIDED_TRAIN_CHUNK 128
+#define APAP_GUIDED_DRAIN 64
+#define APAP_GUIDED_WANT_BLOCKS 1024
+int apap_guided_records(apap_ctx *ctx, const float *pts, int n, const double *model, int what, double *rec_out, int device);
+int apap_guided_records_device(apap_ctx *ctx, const float *d_pts, int n, const double *d_model, int what, double *d_rec_out,
+                               void *stream);
+size_t apap_match_guided_workspace_bytes(int nq, int nt);
+int apap_match_guided(apap_ctx *ctx, const double *rec_q, const float *q, int nq, const double *rec_t, const float *t, int nt,
+                      int kind, double r2, int *idx, float *dist, int *idx2, float *dist2, int *count, int *ridx, float *rdist,
+                      int device);
+int apap_match_guided_device(apap_ctx *ctx, const double *d_rec_q, const float *d_q, int nq, const double *d_rec_t, const float *d_t,
+                             int nt, int kind, double r2, int *d_idx, float *d_dist, int *d_idx2, float *d_dist2, int *d_count,
+                             int *d_ridx, float *d_rdist, void *d_work, size_t work_bytes, void *stream);
+size_t apap_match_guided_batch_workspace_bytes(const int *q_offset, const int *t_offset, int n_pairs);
+int apap_match_guided_batch(apap_ctx *ctx, const double *rec_q, const double *rec_t, const float *q, const float *t,
+                            const int *q_offset, const int *t_offset, int n_pairs, int kind, const double *r2, int *idx, float *dist,
+                            int *idx2, float *dist2, int *count, int *ridx, float *rdist, int device);
+int apap_match_guided_batch_device(apap_ctx *ctx, const double *d_rec_q, const double *d_rec_t, const float *d_q, const float *d_t,
+                                   const int *q_offset, const int *t_offset, int n_pairs, int kind, const double *r2, int *d_idx,
+                                   float *d_dist, int *d_idx2, float *d_dist2, int *d_count, int *d_ridx, float *d_rdist,
+                                   void *d_work, size_t work_bytes, void *stream);
+
 /* ------------------------------------------------- descriptor extraction: SIFT at given keypoints --- */
 /* What coarse_matching asks of OpenCV before it matches (utils.py:142-151): cv.SIFT.create().compute(img, [cv.KeyPoint(x, y, 1)
  * ...]), one 128-d descriptor per given keypoint (size 1, default angle, octave 0).  The definition - OpenCV 4.x's, restated
