@@ -214,6 +214,21 @@ SIGNATURES = {
     "apap_sift_describe_batch": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, _f32p, _i32p, _f32p, C.c_int]),
     "apap_sift_describe_batch_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, _vp, _i32p, _vp, _vp,
                                                   C.c_size_t, _vp]),
+    "apap_sift_orient_window": (C.c_int, [_f32p]),
+    "apap_sift_descr_window": (C.c_int, [_f32p]),
+    "apap_sift_orient_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "apap_sift_orient": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, _f32p, C.c_int]),
+    "apap_sift_orient_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "apap_sift_orient_batch": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, _f32p, _i32p, _f32p, C.c_int]),
+    "apap_sift_orient_batch_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, _vp, _i32p, _vp, _vp,
+                                                C.c_size_t, _vp]),
+    "apap_sift_describe_oriented": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, _f32p, _f32p, _f32p, C.c_int]),
+    "apap_sift_describe_oriented_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t,
+                                                     _vp]),
+    "apap_sift_describe_oriented_batch": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, _f32p, _i32p, _f32p,
+                                                    _f32p, _f32p, C.c_int]),
+    "apap_sift_describe_oriented_batch_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), _i32p, _i32p, _i32p, C.c_int, _vp, _i32p, _vp,
+                                                           _vp, _vp, _vp, C.c_size_t, _vp]),
     "apap_corner_workspace_bytes": (C.c_size_t, [_i32p, _i32p, C.c_int, C.c_int]),
     "apap_corner_detect": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _i64p, _i32p, C.c_int]),
     "apap_corner_detect_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
@@ -1654,6 +1669,93 @@ def sift_describe(img, pts, device=-1, ctx=None):
     check(lib().apap_sift_describe(_h(ctx), _ptr(img, C.c_uint8), img.shape[0], img.shape[1], ch, _ptr(pts, C.c_float), len(pts),
                                    _ptr(out, C.c_float), device))
     return out
+
+
+# ---------------------------------------------------------------- keypoint orientation and the descriptor at an orientation
+SIFT_ORIENT_SAMPLES = 25        # APAP_SIFT_ORIENT_SAMPLES: the offsets |i|, |j| <= 2
+SIFT_DESCR_SAMPLES = 121        # APAP_SIFT_DESCR_SAMPLES: the offsets |i|, |j| <= 5
+SIFT_ORIENT_PATCH = 25          # APAP_SIFT_ORIENT_PATCH: the side of the grey patch one keypoint reads
+SIFT_ORIENT_MIN_SIDE = 13
+
+
+def sift_orient_window():
+    """``apap_sift_orient_window`` (host only): the 25 float32 weights of the orientation samples, (i, j) ascending."""
+    out = np.empty(SIFT_ORIENT_SAMPLES, np.float32)
+    check(lib().apap_sift_orient_window(_ptr(out, C.c_float)))
+    return out
+
+
+def sift_descr_window():
+    """``apap_sift_descr_window`` (host only): the 121 float32 weights of the oriented descriptor's samples, (i, j) ascending."""
+    out = np.empty(SIFT_DESCR_SAMPLES, np.float32)
+    check(lib().apap_sift_descr_window(_ptr(out, C.c_float)))
+    return out
+
+
+def as_sift_orient_image(img, name="img"):
+    """``as_sift_image`` with the oriented entry points' smallest side, 13."""
+    img, ch = as_sift_image(img, name)
+    if min(img.shape[:2]) < SIFT_ORIENT_MIN_SIDE:
+        raise ValueError(f"{name}: sides must be {SIFT_ORIENT_MIN_SIDE} .. {SIFT_MAX_SIDE}; got {img.shape[:2]}")
+    return img, ch
+
+
+def as_sift_angles(angles, n, name="angles"):
+    """Keypoint angles (n,) as contiguous float32, each in [0, 360] (``cv.KeyPoint.angle``)."""
+    angles = np.ascontiguousarray(angles, dtype=np.float32)
+    if angles.shape != (n,):
+        raise ValueError(f"{name} must be ({n},); got {angles.shape}")
+    if not np.all((angles >= 0) & (angles <= 360)):
+        raise ValueError(f"{name} must lie in [0, 360]")
+    return angles
+
+
+def _sift_batch_args(imgs, pts, lengths, who):
+    got = [as_sift_orient_image(im, f"imgs[{m}]") for m, im in enumerate(imgs)]
+    pts = as_sift_points(pts)
+    if len(got) != len(lengths):
+        raise ValueError(f"{who}: {len(got)} images, {len(lengths)} keypoint counts")
+    off = sift_offsets(lengths)
+    if off[-1] != len(pts):
+        raise ValueError(f"{who}: the counts sum to {off[-1]} keypoints; got {len(pts)}")
+    return got, pts, off
+
+
+def sift_orient_batch(imgs, pts, lengths, device=-1, ctx=None):
+    """``apap_sift_orient_batch``: the dominant orientation of every keypoint, many images in one call.  Arguments as
+    ``sift_describe_batch`` (sides from 13).  Returns float32 (N,) angles in [0, 360), ``cv.KeyPoint.angle``'s convention; a
+    keypoint with no valid sample, or on a flat patch, has angle 0."""
+    got, pts, off = _sift_batch_args(imgs, pts, lengths, "sift_orient_batch")
+    ptrs, hs, ws, cs = _image_table(got)
+    angles = np.empty(len(pts), np.float32)
+    check(lib().apap_sift_orient_batch(_h(ctx), ptrs, _ip(hs), _ip(ws), _ip(cs), len(got), _ptr(pts, C.c_float), _ip(off),
+                                       _ptr(angles, C.c_float), device))
+    return angles
+
+
+def sift_orient(img, pts, device=-1, ctx=None):
+    """``apap_sift_orient``: float32 (n,) orientations at ``pts`` (n, 2) of one uint8 image (see ``sift_orient_batch``)."""
+    return sift_orient_batch([img], pts, [len(as_sift_points(pts))], device=device, ctx=ctx)
+
+
+def sift_describe_oriented_batch(imgs, pts, lengths, angles=None, device=-1, ctx=None):
+    """``apap_sift_describe_oriented_batch``: the SIFT descriptors of ``KeyPoint(x, y, 1, angle)``, many images in one call.
+    ``angles`` (N,) in [0, 360]: returns float32 (N, 128).  ``angles=None``: orientation and descriptor in one pass; returns
+    ``(feats, angles)``, the same bytes as ``sift_orient_batch`` followed by the call with its angles."""
+    got, pts, off = _sift_batch_args(imgs, pts, lengths, "sift_describe_oriented_batch")
+    ptrs, hs, ws, cs = _image_table(got)
+    out = np.empty((len(pts), SIFT_DIM), np.float32)
+    given = None if angles is None else as_sift_angles(angles, len(pts))
+    found = np.empty(len(pts), np.float32) if angles is None else None
+    check(lib().apap_sift_describe_oriented_batch(
+        _h(ctx), ptrs, _ip(hs), _ip(ws), _ip(cs), len(got), _ptr(pts, C.c_float), _ip(off),
+        None if given is None else _ptr(given, C.c_float), None if found is None else _ptr(found, C.c_float), _ptr(out, C.c_float), device))
+    return out if angles is not None else (out, found)
+
+
+def sift_describe_oriented(img, pts, angles=None, device=-1, ctx=None):
+    """``apap_sift_describe_oriented``: one image (see ``sift_describe_oriented_batch``; the single call is the batch of one)."""
+    return sift_describe_oriented_batch([img], pts, [len(as_sift_points(pts))], angles=angles, device=device, ctx=ctx)
 
 
 # ---------------------------------------------------------------- corner detection: exact integer Harris corners

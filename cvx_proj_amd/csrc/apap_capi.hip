@@ -1494,6 +1494,78 @@ int apap_sift_describe(apap_ctx *ctx, const uint8_t *img, int h, int w, int chan
     return apap_sift_describe_batch(ctx, &img, &h, &w, &channels, 1, pts, off, out, device);
 }
 
+// ------------------------------------------------------------------ keypoint orientation (apap_sift_orient.hip)
+// The three host-buffer forms in one: angles out only (out null), descriptors at given angles (angles_in), or both.
+static int sift_oriented_host(apap_ctx *ctx, const char *who, const uint8_t *const *imgs, const int *heights, const int *widths,
+                              const int *channels, int n_images, const float *pts, const int *pt_offset, const float *angles_in,
+                              float *angles_out, float *out, int device) {
+    if (!imgs || !pts || (!angles_in && !angles_out)) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    if (angles_in && angles_out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: angles are given: angles_out must be null", who);
+    int rc = apap::sift_orient_check(heights, widths, channels, n_images, pt_offset, who);
+    if (rc) return rc;
+    for (int m = 0; m < n_images; ++m)
+        if (!imgs[m]) return apap::fail(APAP_ERR_INVALID_ARG, "%s: image %d: null pointer", who, m);
+    const size_t k0 = (size_t)pt_offset[0], N = (size_t)pt_offset[n_images] - k0;   // the device arrays start at the first image
+    for (size_t k = 0; k < 2 * N; ++k)
+        if (!std::isfinite(pts[2 * k0 + k]))
+            return apap::fail(APAP_ERR_INVALID_ARG, "%s: keypoint %zu has a non-finite coordinate", who, k0 + k / 2);
+    for (size_t k = 0; angles_in && k < N; ++k)
+        if (!(angles_in[k0 + k] >= 0.f && angles_in[k0 + k] <= 360.f))
+            return apap::fail(APAP_ERR_INVALID_ARG, "%s: keypoint %zu: angle %g is not in [0, 360]", who, k0 + k, (double)angles_in[k0 + k]);
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    const std::vector<int> rel = relative_offsets(pt_offset, n_images);
+    const std::vector<Part> d_img = image_parts(call, heights, widths, channels, n_images);
+    Layout io = call.layout(S_AUX);
+    const Part d_pts = io.take(N * 2 * sizeof(float)), d_ang = io.take(N * sizeof(float));
+    const Part d_out = io.take(out ? N * APAP_SIFT_DIM * sizeof(float) : 0);
+    call.alloc(io);
+    const Part work = call.slot(S_WORK, apap_sift_orient_workspace_bytes(n_images));
+    const std::vector<const uint8_t *> d_imgs = upload_images(call, d_img, imgs);
+    call.up(d_pts, pts + 2 * k0);
+    if (angles_in) call.up(d_ang, angles_in + k0);
+    if ((rc = call.rc())) return rc;
+    const float *in = angles_in ? d_ang.as<const float>() : nullptr;
+    float *ang_out = angles_in ? nullptr : d_ang.as<float>();
+    if (out)
+        rc = apap_sift_describe_oriented_batch_device(ctx, d_imgs.data(), heights, widths, channels, n_images, d_pts.as<const float>(),
+                                                      rel.data(), in, ang_out, d_out.as<float>(), work.as<void>(), work.bytes, call.stream());
+    else
+        rc = apap_sift_orient_batch_device(ctx, d_imgs.data(), heights, widths, channels, n_images, d_pts.as<const float>(), rel.data(),
+                                           ang_out, work.as<void>(), work.bytes, call.stream());
+    if (rc) return rc;
+    if (angles_out) call.down(angles_out + k0, d_ang);
+    if (out) call.down(out + k0 * APAP_SIFT_DIM, d_out);
+    return call.wait();
+}
+
+int apap_sift_orient_batch(apap_ctx *ctx, const uint8_t *const *imgs, const int *heights, const int *widths, const int *channels,
+                           int n_images, const float *pts, const int *pt_offset, float *angles, int device) {
+    return sift_oriented_host(ctx, "apap_sift_orient_batch", imgs, heights, widths, channels, n_images, pts, pt_offset, nullptr, angles,
+                              nullptr, device);
+}
+
+int apap_sift_orient(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, const float *pts, int n, float *angles, int device) {
+    const int off[2] = {0, n};
+    return sift_oriented_host(ctx, "apap_sift_orient", &img, &h, &w, &channels, 1, pts, off, nullptr, angles, nullptr, device);
+}
+
+int apap_sift_describe_oriented_batch(apap_ctx *ctx, const uint8_t *const *imgs, const int *heights, const int *widths,
+                                      const int *channels, int n_images, const float *pts, const int *pt_offset, const float *angles,
+                                      float *angles_out, float *out, int device) {
+    const char *who = "apap_sift_describe_oriented_batch";
+    if (!out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    return sift_oriented_host(ctx, who, imgs, heights, widths, channels, n_images, pts, pt_offset, angles, angles_out, out, device);
+}
+
+int apap_sift_describe_oriented(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, const float *pts, int n,
+                                const float *angles, float *angles_out, float *out, int device) {
+    const char *who = "apap_sift_describe_oriented";
+    if (!out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    const int off[2] = {0, n};
+    return sift_oriented_host(ctx, who, &img, &h, &w, &channels, 1, pts, off, angles, angles_out, out, device);
+}
+
 // ------------------------------------------------------------------ corner detection (apap_corner.hip)
 int apap_corner_detect_batch(apap_ctx *ctx, const uint8_t *const *imgs, const int *heights, const int *widths, const int *channels,
                              int n_images, int max_corners, int radius, int quality_permille, float *pts, long long *response,

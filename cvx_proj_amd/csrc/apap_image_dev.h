@@ -12,6 +12,7 @@ namespace apap {
 // reflect-101, once, then clamped.  One reflection is all that either caller needs, for images of 7 pixels a side or more:
 //   k_sift_describe: a valid sample reads indices -6 .. n + 5 only, which reflect once into 0 .. n - 1 for n >= 7; the clamp
 //     keeps what an invalid sample would read (and never uses) inside the image;
+//   k_sift_orient (apap_sift_orient.hip): its 25 x 25 patch reads -12 .. n + 11, one reflection for n >= 13, its smallest side;
 //   k_corner_tile: positions more than one pixel outside the image are staged but never used (a gradient outside the image
 //     is taken at its reflection, whose Sobel window reaches one pixel outside at most).
 __device__ __forceinline__ int reflect(int i, int n) {

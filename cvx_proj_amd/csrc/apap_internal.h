@@ -255,6 +255,11 @@ inline int image_channels_check(int m, int c, const char *who) {
 }
 // The argument checks of the descriptor extraction's entry points (apap_sift.hip) that need no device pointer.
 int sift_check(const int *heights, const int *widths, const int *channels, int n_images, const int *pt_offset, const char *who);
+// The 13 taps of the base image's Gaussian in float64 (apap_sift.hip): both descriptor kernels round them to float32.
+void sift_taps_f64(double *g);
+// sift_check, then the oriented entry points' own smallest side (apap_sift_orient.hip): 13, one reflection of the 25 x 25 patch.
+constexpr int kOrientMinSide = 13;
+int sift_orient_check(const int *heights, const int *widths, const int *channels, int n_images, const int *pt_offset, const char *who);
 // The argument checks of the corner detector's entry points (apap_corner.hip) that need no device pointer.
 int corner_check(const int *heights, const int *widths, const int *channels, int n_images, int max_corners, int radius,
                  int quality_permille, const char *who);

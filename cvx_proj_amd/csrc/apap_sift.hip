@@ -14,6 +14,7 @@
 //      spatial shares (OpenCV's v1 = v * f, v0 = v - v1);
 //   4. every lane gathers two of the 128 bins (lane and lane + 64: the same column and orientation, two rows apart) in one
 //      pass over the samples in ascending order, each adding its share (or 0) - a fixed order, no atomics;
+//   (steps 1, 2 and 5, the image table and atan2 are apap_sift_dev.h's, shared with apap_sift_orient.hip)
 //   5. sum of squares by a fixed binary tree (bins b and b + 64, then lanes l and l ^ 32, ^ 16 .. ^ 1), clamp at 0.2 of the
 //      norm, the same tree again, scale to 512, round, saturate; two coalesced 256-byte stores.
 // Every operation is one IEEE float32 operation (the sources are built with -ffp-contract=off; sqrt and the division are the
@@ -28,20 +29,20 @@
 #include <cstdint>
 #include <vector>
 
-#include "apap_image_dev.h"
 #include "apap_internal.h"
+#include "apap_sift_dev.h"
 
 namespace {
 
-using apap::grey_at, apap::reflect;
+using apap::SiftImage;
 
-constexpr int kDim = APAP_SIFT_DIM;
+constexpr int kDim = apap::kSiftDim;
 constexpr int kSamples = APAP_SIFT_SAMPLES;
-constexpr int kTaps = APAP_SIFT_TAPS;
+constexpr int kTaps = apap::kSiftTaps;
 constexpr int kPatch = APAP_SIFT_PATCH;
 constexpr int kBase = kPatch - (kTaps - 1);        // 9: the base-image patch
-constexpr int kPerBlock = APAP_SIFT_BLOCK_KEYPOINTS;
-constexpr int kThreads = 64 * kPerBlock;
+constexpr int kPerBlock = apap::kSiftPerBlock;
+constexpr int kThreads = apap::kSiftThreads;
 constexpr int kWinCols = APAP_SIFT_WINDOW_COLS;
 constexpr int kMaxRows = 1 << 24;
 static_assert(kDim == 128 && kSamples == 49 && kTaps == 13 && kPatch == 21 && kBase == 9 && kPerBlock == 4, "the lane mapping below is for these");
@@ -51,14 +52,6 @@ struct SiftConst {   // the constants of the kernel, a kernel argument: made on 
     float w[kSamples], fr[kSamples], fc[kSamples];   // window weight, fractions of rbin and cbin
     int r0[kSamples], c0[kSamples];                  // floor(rbin), floor(cbin): -1 .. 3
 };
-
-struct alignas(16) SiftImage {   // one image, in device memory
-    const uint8_t *img;
-    int h, w, c;
-    int k0;                      // its first keypoint: a row of the concatenated arrays (the next image's k0 ends it)
-    int pad[2];
-};
-static_assert(sizeof(SiftImage) == 32, "SiftImage");
 
 // The 49 x 8 window table (include/apap_hip.h): rbin, cbin, weight, frac(rbin), frac(cbin), floor(rbin), floor(cbin), 0.
 void window_f64(double *t) {
@@ -81,20 +74,10 @@ void window_f64(double *t) {
         }
 }
 
-void taps_f64(double *g) {
-    const double sigma2 = 1.6 * 1.6 - 0.5 * 0.5;   // sigma = sqrt(1.6^2 - 0.5^2)
-    double sum = 0.0;
-    for (int t = 0; t < kTaps; ++t) {
-        g[t] = std::exp(-(double)((t - 6) * (t - 6)) / (2.0 * sigma2));
-        sum += g[t];
-    }
-    for (int t = 0; t < kTaps; ++t) g[t] /= sum;
-}
-
 SiftConst make_const() {
     SiftConst K;
     double g[kTaps], t[kSamples * kWinCols];
-    taps_f64(g);
+    apap::sift_taps_f64(g);
     window_f64(t);
     for (int i = 0; i < kTaps; ++i) K.taps[i] = (float)g[i];
     for (int k = 0; k < kSamples; ++k) {
@@ -105,38 +88,6 @@ SiftConst make_const() {
         K.c0[k] = (int)t[k * kWinCols + 6];
     }
     return K;
-}
-
-// atan2(y, x) in degrees, in [0, 360]: |error| <= 2e-6 rad against the exact value (tests/sift_spec.py measures it).
-// a = min(|x|, |y|) / max(|x|, |y|) in [0, 1]; atan(a) = a p(a^2), p of degree 7 (a near-minimax fit, 3.8e-8 in exact
-// arithmetic), Horner with a multiply and an add per step; then the octant: pi/2 - r, pi - r, -r.  atan2(0, 0) = 0.
-__device__ __forceinline__ float atan2_deg(float y, float x) {
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    if (mx == 0.f) return 0.f;
-    const float a = mn / mx, s = a * a;
-    float p = -4.054558929e-03f;
-    p = p * s + 2.186292969e-02f;
-    p = p * s + -5.591228977e-02f;
-    p = p * s + 9.642194957e-02f;
-    p = p * s + -1.390862912e-01f;
-    p = p * s + 1.994656622e-01f;
-    p = p * s + -3.332985938e-01f;
-    p = p * s + 9.999993443e-01f;
-    float r = a * p;
-    if (ay > ax) r = 1.570796371e+00f - r;
-    if (x < 0.f) r = 3.141592741e+00f - r;
-    if (y < 0.f) r = -r;
-    float deg = r * 5.729578018e+01f;
-    if (deg < 0.f) deg = deg + 360.f;
-    return deg;
-}
-
-__device__ __forceinline__ float tree_sum(float a, float b) {   // bins (l, l + 64), then lanes l ^ 32, ^ 16 .. ^ 1
-    float s = a + b;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s = s + __shfl_xor(s, m);
-    return s;
 }
 
 __global__ __launch_bounds__(kThreads) void k_sift_describe(const SiftImage *__restrict__ tab, int n_images,
@@ -154,16 +105,7 @@ __global__ __launch_bounds__(kThreads) void k_sift_describe(const SiftImage *__r
     const long long row = (long long)k_begin + (long long)blockIdx.x * kPerBlock + wv;
     const bool live = row < k_end;
 
-    // the image of this keypoint: the last entry whose first keypoint is not after it
-    int lo = 0, hi = n_images - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (live && tab[mid].k0 <= row)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    const SiftImage I = tab[lo];
+    const SiftImage I = apap::sift_image_of(tab, n_images, row, live);   // the image of this keypoint
 
     // pt = (rint(x), rint(y)), round half to even; a keypoint that has no valid sample (or a non-finite coordinate) is all zeros
     int px = 0, py = 0;
@@ -178,34 +120,7 @@ __global__ __launch_bounds__(kThreads) void k_sift_describe(const SiftImage *__r
     }
     float *patch = s_patch[wv], *hb = s_hb[wv], *base = s_base[wv];
 
-    if (work) {
-        for (int at = lane; at < kPatch * kPatch; at += 64) {
-            const int pr = at / kPatch, pc = at - pr * kPatch;
-            const int y = reflect(py - 10 + pr, I.h), x = reflect(px - 10 + pc, I.w);
-            patch[at] = (float)grey_at(I.img, y, x, I.w, I.c);
-        }
-    }
-    __syncthreads();
-    if (work) {
-        for (int at = lane; at < kPatch * kBase; at += 64) {
-            const int r = at / kBase, c = at - r * kBase;
-            float acc = 0.f;
-#pragma unroll
-            for (int t = 0; t < kTaps; ++t) acc = acc + K.taps[t] * patch[r * kPatch + c + t];
-            hb[at] = acc;
-        }
-    }
-    __syncthreads();
-    if (work) {
-        for (int at = lane; at < kBase * kBase; at += 64) {
-            const int r = at / kBase, c = at - r * kBase;
-            float acc = 0.f;
-#pragma unroll
-            for (int t = 0; t < kTaps; ++t) acc = acc + K.taps[t] * hb[(r + t) * kBase + c];
-            base[at] = acc;
-        }
-    }
-    __syncthreads();
+    apap::sift_base_patch<kPatch>(I, py, px, work, lane, K.taps, patch, hb, base);
     if (work && lane < kSamples) {
         const int k = lane, i = k / 7 - 3, j = k - (k / 7) * 7 - 3;
         const int r = 4 + i, c = 4 + j;
@@ -214,7 +129,7 @@ __global__ __launch_bounds__(kThreads) void k_sift_describe(const SiftImage *__r
         const float dy = base[(r - 1) * kBase + c] - base[(r + 1) * kBase + c];
         float mag = sqrtf(dx * dx + dy * dy) * K.w[k];
         if (!valid) mag = 0.f;
-        const float obin = (atan2_deg(dy, dx) - 361.f) * 2.222222276e-02f;   // 8 / 360
+        const float obin = (apap::sift_atan2_deg(dy, dx) - 361.f) * 2.222222276e-02f;   // 8 / 360
         const float o0f = floorf(obin), fo = obin - o0f;                     // o0f in -9 .. -1
         const float fr = K.fr[k], fc = K.fc[k];
         const float v_r1 = mag * fr, v_r0 = mag - v_r1;
@@ -247,22 +162,22 @@ __global__ __launch_bounds__(kThreads) void k_sift_describe(const SiftImage *__r
             }
         }
     }
-    const float n1 = tree_sum(h[0] * h[0], h[1] * h[1]);
-    const float thr = 0.2f * sqrtf(n1);
-    h[0] = fminf(h[0], thr);
-    h[1] = fminf(h[1], thr);
-    const float n2 = tree_sum(h[0] * h[0], h[1] * h[1]);
-    const float scale = 512.f / fmaxf(sqrtf(n2), FLT_EPSILON);
-    float *o = out + (size_t)row * kDim;
-    o[lane] = fminf(fmaxf(rintf(h[0] * scale), 0.f), 255.f);
-    o[lane + 64] = fminf(fmaxf(rintf(h[1] * scale), 0.f), 255.f);
+    apap::sift_finish(h[0], h[1], out, row, lane);
 }
-
-size_t table_bytes(int n_images) { return apap::up256((size_t)n_images * sizeof(SiftImage)); }
 
 }  // namespace
 
 namespace apap {
+
+void sift_taps_f64(double *g) {
+    const double sigma2 = 1.6 * 1.6 - 0.5 * 0.5;   // sigma = sqrt(1.6^2 - 0.5^2)
+    double sum = 0.0;
+    for (int t = 0; t < kTaps; ++t) {
+        g[t] = std::exp(-(double)((t - 6) * (t - 6)) / (2.0 * sigma2));
+        sum += g[t];
+    }
+    for (int t = 0; t < kTaps; ++t) g[t] /= sum;
+}
 
 // The argument checks of the descriptor extraction's entry points that need no device pointer.
 int sift_check(const int *heights, const int *widths, const int *channels, int n_images, const int *pt_offset, const char *who) {
@@ -296,12 +211,12 @@ int apap_sift_window(float *out) {
 int apap_sift_taps(float *out) {
     if (!out) return apap::fail(APAP_ERR_INVALID_ARG, "apap_sift_taps: null argument");
     double g[kTaps];
-    taps_f64(g);
+    apap::sift_taps_f64(g);
     for (int t = 0; t < kTaps; ++t) out[t] = (float)g[t];
     return APAP_OK;
 }
 
-size_t apap_sift_workspace_bytes(int n_images) { return n_images < 1 || n_images > apap::kMaxImages ? 0 : table_bytes(n_images); }
+size_t apap_sift_workspace_bytes(int n_images) { return n_images < 1 || n_images > apap::kMaxImages ? 0 : apap::sift_table_bytes(n_images); }
 
 int apap_sift_describe_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs, const int *heights, const int *widths,
                                     const int *channels, int n_images, const float *d_pts, const int *pt_offset, float *d_out,
@@ -310,26 +225,17 @@ int apap_sift_describe_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs,
     (void)ctx;
     int rc = apap::sift_check(heights, widths, channels, n_images, pt_offset, who);
     if (rc) return rc;
-    if (!d_imgs || !d_pts || !d_out || !d_work) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
-    for (int m = 0; m < n_images; ++m)
-        if (!d_imgs[m]) return apap::fail(APAP_ERR_INVALID_ARG, "%s: image %d: null device pointer", who, m);
-    const size_t need = table_bytes(n_images);
-    if (work_bytes < need) return apap::fail(APAP_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, work_bytes, need);
-    if (((uintptr_t)d_work & 255) != 0 || ((uintptr_t)d_pts & 7) != 0 || ((uintptr_t)d_out & 3) != 0)
-        return apap::fail(APAP_ERR_INVALID_ARG, "%s: workspace must be 256-byte, keypoints 8-byte and descriptors 4-byte aligned", who);
-
-    std::vector<SiftImage> tab((size_t)n_images);
-    for (int m = 0; m < n_images; ++m) tab[m] = SiftImage{d_imgs[m], heights[m], widths[m], channels[m], pt_offset[m], {0, 0}};
+    if (!d_pts || !d_out) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
+    if (((uintptr_t)d_pts & 7) != 0 || ((uintptr_t)d_out & 3) != 0)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: keypoints must be 8-byte and descriptors 4-byte aligned", who);
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = apap::sift_table_upload(d_imgs, heights, widths, channels, n_images, pt_offset, d_work, work_bytes, s, who))) return rc;
     const int k_begin = pt_offset[0], k_end = pt_offset[n_images];
     const unsigned blocks = (unsigned)(((long long)k_end - k_begin + kPerBlock - 1) / kPerBlock);
     const SiftConst K = make_const();
-    hipStream_t s = (hipStream_t)stream;
-    // from pageable memory in stream order: the copy returns once its source has been consumed
-    hipError_t e = hipMemcpyAsync(d_work, tab.data(), (size_t)n_images * sizeof(SiftImage), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return apap::hip_fail(e, "apap_sift_describe_batch_device: descriptor upload");
     hipLaunchKernelGGL(k_sift_describe, dim3(blocks), dim3(kThreads), 0, s, (const SiftImage *)d_work, n_images, d_pts, d_out, k_begin,
                        k_end, K);
-    e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return apap::hip_fail(e, "apap_sift_describe_batch_device launch");
     return APAP_OK;
 }

@@ -760,14 +760,86 @@ def hip_sift_describe(img, pts, ctx=None, work=None):
     return hip_sift_describe_batch([img], pts, [pts.shape[0]], ctx=ctx, work=work)
 
 
-def hip_describe_and_match(c_img, o_img, pts_c, pts_o, second=True, ctx=None):
+def sift_orient_workspace_bytes(n_images=1):
+    """Scratch of the ``hip_sift_orient*`` and ``hip_sift_describe_oriented*`` calls of ``n_images`` images: 32 bytes per image,
+    a 256-byte multiple.  0 for an invalid count."""
+    return _native.lib().apap_sift_orient_workspace_bytes(int(n_images))
+
+
+def _oriented_args(imgs, pts, lengths, who):
+    _needs_device(pts, who)
+    dev = pts.device
+    if pts.dtype != torch.float32 or not pts.is_contiguous() or pts.dim() != 2 or pts.shape[1] != 2:
+        raise ValueError(f"{who}: keypoints must be a contiguous float32 (n, 2) tensor")
+    imgs = list(imgs)
+    if len(imgs) != len(lengths):
+        raise ValueError(f"{who}: {len(imgs)} images, {len(lengths)} keypoint counts")
+    table = _image_table(imgs, dev, who)
+    for m, im in enumerate(imgs):
+        if min(im.shape[:2]) < _native.SIFT_ORIENT_MIN_SIDE:
+            raise ValueError(f"{who}: imgs[{m}]: sides must be {_native.SIFT_ORIENT_MIN_SIDE} .. {_native.SIFT_MAX_SIDE}; got {tuple(im.shape[:2])}")
+    off = _native.sift_offsets(lengths)
+    if off[-1] != pts.shape[0]:
+        raise ValueError(f"{who}: the counts sum to {off[-1]} keypoints; got {pts.shape[0]}")
+    return dev, len(imgs), table, off
+
+
+def hip_sift_orient_batch(imgs, pts, lengths, ctx=None, work=None):
+    """``apap_sift_orient_batch_device`` on the current stream, no host synchronisation: the dominant orientation of every
+    keypoint, many images in one kernel launch.  Arguments as ``hip_sift_describe_batch`` (sides from 13).  Returns float32 (N,)
+    angles in [0, 360); a keypoint with no valid sample or a non-finite coordinate has angle 0."""
+    dev, n, (ptrs, hs, ws, cs), off = _oriented_args(imgs, pts, lengths, "hip_sift_orient_batch")
+    angles = torch.empty(pts.shape[0], dtype=torch.float32, device=dev)
+    work = _scratch(work, sift_orient_workspace_bytes(n), dev)
+    _native.check(_native.lib().apap_sift_orient_batch_device(
+        _native._h(ctx), ptrs, _ip(hs), _ip(ws), _ip(cs), n, pts.data_ptr(), _ip(off), angles.data_ptr(), work.data_ptr(), work.numel(),
+        _stream(dev)))
+    return angles
+
+
+def hip_sift_orient(img, pts, ctx=None, work=None):
+    """``apap_sift_orient_device``: one image, the batch of one (see ``hip_sift_orient_batch``)."""
+    _needs_device(pts, "hip_sift_orient")
+    return hip_sift_orient_batch([img], pts, [pts.shape[0]], ctx=ctx, work=work)
+
+
+def hip_sift_describe_oriented_batch(imgs, pts, lengths, angles=None, ctx=None, work=None):
+    """``apap_sift_describe_oriented_batch_device`` on the current stream, no host synchronisation.  ``angles``: a contiguous
+    float32 (N,) device tensor of ``cv.KeyPoint.angle`` values - returns the float32 (N, 128) descriptors at them (a zero row
+    for an angle outside [0, 360]).  ``angles=None``: orientation and descriptor in one launch - returns ``(feats, angles)``,
+    the same bytes as ``hip_sift_orient_batch`` followed by the call with its angles."""
+    who = "hip_sift_describe_oriented_batch"
+    dev, n, (ptrs, hs, ws, cs), off = _oriented_args(imgs, pts, lengths, who)
+    if angles is not None and (angles.dtype != torch.float32 or not angles.is_contiguous() or angles.device != dev or
+                               tuple(angles.shape) != (pts.shape[0],)):
+        raise ValueError(f"{who}: angles must be a contiguous float32 ({pts.shape[0]},) tensor on {dev}")
+    out = torch.empty((pts.shape[0], _native.SIFT_DIM), dtype=torch.float32, device=dev)
+    found = torch.empty(pts.shape[0], dtype=torch.float32, device=dev) if angles is None else None
+    work = _scratch(work, sift_orient_workspace_bytes(n), dev)
+    _native.check(_native.lib().apap_sift_describe_oriented_batch_device(
+        _native._h(ctx), ptrs, _ip(hs), _ip(ws), _ip(cs), n, pts.data_ptr(), _ip(off), None if angles is None else angles.data_ptr(),
+        None if found is None else found.data_ptr(), out.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
+    return out if angles is not None else (out, found)
+
+
+def hip_sift_describe_oriented(img, pts, angles=None, ctx=None, work=None):
+    """``apap_sift_describe_oriented_device``: one image, the batch of one (see ``hip_sift_describe_oriented_batch``)."""
+    _needs_device(pts, "hip_sift_describe_oriented")
+    return hip_sift_describe_oriented_batch([img], pts, [pts.shape[0]], angles=angles, ctx=ctx, work=work)
+
+
+def hip_describe_and_match(c_img, o_img, pts_c, pts_o, second=True, ctx=None, oriented=False):
     """Both images described in one batched launch, then ``hip_match_descriptors`` of the centre image's descriptors against
     the other's: three kernels on the current stream, nothing returns to the host in between.  Returns (idx, dist, idx2, dist2,
     feats_c, feats_o): the matcher's four outputs (``idx2`` and ``dist2`` ``None`` without ``second``) and the float32 (n, 128)
-    descriptors, views of one tensor."""
+    descriptors, views of one tensor.  ``oriented``: every keypoint described in its own dominant orientation (the fused
+    ``hip_sift_describe_oriented_batch``), so that the match survives an in-plane rotation between the images."""
     _needs_device(pts_c, "hip_describe_and_match")
     nc, no = pts_c.shape[0], pts_o.shape[0]
-    feats = hip_sift_describe_batch([c_img, o_img], torch.cat([pts_c, pts_o]), [nc, no], ctx=ctx)
+    if oriented:
+        feats, _ = hip_sift_describe_oriented_batch([c_img, o_img], torch.cat([pts_c, pts_o]), [nc, no], ctx=ctx)
+    else:
+        feats = hip_sift_describe_batch([c_img, o_img], torch.cat([pts_c, pts_o]), [nc, no], ctx=ctx)
     return hip_match_descriptors(feats[:nc], feats[nc:], second=second, ctx=ctx) + (feats[:nc], feats[nc:])
 
 
@@ -812,19 +884,19 @@ def hip_corner_detect(img, max_corners, radius=5, quality_permille=10, ctx=None,
     return pts[0], resp[0], count[0]
 
 
-def hip_detect_describe_match(c_img, o_img, max_corners, radius=5, quality_permille=10, second=True, ctx=None):
+def hip_detect_describe_match(c_img, o_img, max_corners, radius=5, quality_permille=10, second=True, ctx=None, oriented=False):
     """From two uint8 device images to matches: both images' corners in one batched call, their descriptors in one batched
     call, then ``hip_match_descriptors`` of the centre image's descriptors against the other's.  Between detection and
     description the two corner counts (8 bytes) are read back: the chain's only host synchronisation, needed because the
     describe and match entry points take their lengths on the host.  Returns (idx, dist, idx2, dist2, feats_c, feats_o, pts_c,
     pts_o): ``hip_describe_and_match``'s six outputs and the float32 (n, 2) corners.  An image without corners is refused
-    (``ValueError``): there is nothing to describe or match."""
+    (``ValueError``): there is nothing to describe or match.  ``oriented``: as ``hip_describe_and_match``."""
     pts, _, count = hip_corner_detect_batch([c_img, o_img], max_corners, radius, quality_permille, ctx=ctx)
     nc, no = (int(x) for x in count.tolist())
     if nc < 1 or no < 1:
         raise ValueError(f"hip_detect_describe_match: {nc} and {no} corners; both images need at least one")
     pts_c, pts_o = pts[0, :nc], pts[1, :no]
-    return hip_describe_and_match(c_img, o_img, pts_c, pts_o, second=second, ctx=ctx) + (pts_c, pts_o)
+    return hip_describe_and_match(c_img, o_img, pts_c, pts_o, second=second, ctx=ctx, oriented=oriented) + (pts_c, pts_o)
 
 
 def image_warp_workspace_bytes(n_problems=1):

@@ -1055,6 +1055,57 @@ int apap_sift_describe_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs,
                                     const int *channels, int n_images, const float *d_pts, const int *pt_offset, float *d_out,
                                     void *d_work, size_t work_bytes, void *stream);
 
+/* ------------------------------------------------- keypoint orientation and the descriptor at an orientation --- */
+/* What the entry points above leave out: the keypoint's dominant orientation and a descriptor taken in it, so that matching
+ * survives an in-plane rotation of the second picture.  OpenCV 4.x's calcOrientationHist and calcSIFTDescriptor for a size-1,
+ * octave-0 keypoint; the definition is in DESIGN.md "Keypoint orientation" and, operation by operation, in
+ * tests/sift_orient_spec.py.  grey, base, pt, the gradients, atan2 and the rule that a sample counts only if 0 < r < h - 1 and
+ * 0 < c < w - 1 are those of apap_sift_describe.
+ *   angle   the 25 samples |i|, |j| <= 2 vote with weight exp(-(i^2 + j^2) / (2 0.75^2)) x magnitude for bin rint(ang / 10) of
+ *           36; OpenCV's circular 1 4 6 4 1 smoothing; the FIRST largest bin, refined by the parabola through its neighbours;
+ *           angle = 360 - 10 bin in [0, 360): cv.KeyPoint.angle.  Only the dominant peak is used (OpenCV adds a keypoint for
+ *           every peak of 0.8 of it): row k stays keypoint k.  A keypoint without a valid sample, or a flat patch, has angle 0.
+ *   out     ori = 360 - angle; the 121 samples |i|, |j| <= 5, rotated by ori (the library's own sin and cos, <= 2.1e-7) into
+ *           the 4 x 4 x 8 bins, weight exp(-(i^2 + j^2) / 18); then as apap_sift_describe.  APAP_SIFT_DIM float32 a keypoint.
+ * Single IEEE float32 operations in a fixed order: the same bytes from every entry point.
+ *   apap_sift_orient*              angles out (one float32 a keypoint)
+ *   apap_sift_describe_oriented*   angles non-null: the descriptors at those angles, each in [0, 360], and angles_out must be
+ *                                  null; angles null: orientation and descriptor in one pass (the patch read and blurred once),
+ *                                  the angles written to angles_out, which must not be null then
+ *   apap_sift_orient_window        host only: the APAP_SIFT_ORIENT_SAMPLES float32 weights of the orientation samples, (i, j)
+ *   apap_sift_descr_window         ascending; the APAP_SIFT_DESCR_SAMPLES weights of the descriptor samples, likewise
+ * Batches, pt_offset, the counts, channels, alignments and the workspace (apap_sift_orient_workspace_bytes) are those of
+ * apap_sift_describe_batch; angles are addressed like keypoints (row pt_offset[m] + k).  Sides are 13 .. 32768: a keypoint reads
+ * an APAP_SIFT_ORIENT_PATCH x APAP_SIFT_ORIENT_PATCH patch of the grey image under one reflection.  The host-buffer forms refuse a
+ * non-finite coordinate and an angle that is not in [0, 360] before any device is touched; the _device forms give such a
+ * keypoint a zero row, and angle 0 from the orientation. */
+#define APAP_SIFT_ORIENT_SAMPLES 25
+#define APAP_SIFT_DESCR_SAMPLES 121
+#define APAP_SIFT_ORIENT_PATCH 25
+int apap_sift_orient_window(float *out);
+int apap_sift_descr_window(float *out);
+size_t apap_sift_orient_workspace_bytes(int n_images);
+int apap_sift_orient(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, const float *pts, int n, float *angles, int device);
+int apap_sift_orient_device(apap_ctx *ctx, const uint8_t *d_img, int h, int w, int channels, const float *d_pts, int n, float *d_angles,
+                            void *d_work, size_t work_bytes, void *stream);
+int apap_sift_orient_batch(apap_ctx *ctx, const uint8_t *const *imgs, const int *heights, const int *widths, const int *channels,
+                           int n_images, const float *pts, const int *pt_offset, float *angles, int device);
+int apap_sift_orient_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs, const int *heights, const int *widths, const int *channels,
+                                  int n_images, const float *d_pts, const int *pt_offset, float *d_angles, void *d_work, size_t work_bytes,
+                                  void *stream);
+int apap_sift_describe_oriented(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, const float *pts, int n,
+                                const float *angles, float *angles_out, float *out, int device);
+int apap_sift_describe_oriented_device(apap_ctx *ctx, const uint8_t *d_img, int h, int w, int channels, const float *d_pts, int n,
+                                       const float *d_angles, float *d_angles_out, float *d_out, void *d_work, size_t work_bytes,
+                                       void *stream);
+int apap_sift_describe_oriented_batch(apap_ctx *ctx, const uint8_t *const *imgs, const int *heights, const int *widths,
+                                      const int *channels, int n_images, const float *pts, const int *pt_offset, const float *angles,
+                                      float *angles_out, float *out, int device);
+int apap_sift_describe_oriented_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs, const int *heights, const int *widths,
+                                             const int *channels, int n_images, const float *d_pts, const int *pt_offset,
+                                             const float *d_angles, float *d_angles_out, float *d_out, void *d_work, size_t work_bytes,
+                                             void *stream);
+
 /* ------------------------------------------------- corner detection: exact integer Harris corners --- */
 /* The keypoints that apap_sift_describe takes, from the image alone: integer pixel corners (the descriptor rounds its
  * coordinates and reads the base level only, so nothing finer could be used).  Everything is integer arithmetic - no float,
