@@ -1422,13 +1422,19 @@ MATCH_MAX_ROWS = 1 << 24        # queries / train rows of one pair
 MATCH_MAX_PAIRS = 65535
 
 
-def match_splits(nq, nt):
-    """Into how many splits the train axis of an (nq, nt) pair is cut, and of how many chunks each (the last may be shorter):
+def train_splits(nq, nt, q_tile, chunk, want):
+    """Into how many splits the train axis of an (nq, nt) pair is cut, and of how many chunks each (the last may be shorter),
+    by a matcher whose blocks take ``q_tile`` queries and chunks of ``chunk`` train rows and that wants about ``want`` blocks:
     the rule of include/apap_hip.h.  No output depends on it; tests use it to place shapes at its edges."""
-    q_tiles = -(-int(nq) // MATCH_QUERY_TILE)
-    chunks = -(-int(nt) // MATCH_TRAIN_CHUNK)
-    per = -(-chunks // min(chunks, -(-MATCH_WANT_BLOCKS // q_tiles)))
+    q_tiles = -(-int(nq) // q_tile)
+    chunks = -(-int(nt) // chunk)
+    per = -(-chunks // min(chunks, -(-want // q_tiles)))
     return -(-chunks // per), per
+
+
+def match_splits(nq, nt):
+    """``train_splits`` for the exact matcher's tiling."""
+    return train_splits(nq, nt, MATCH_QUERY_TILE, MATCH_TRAIN_CHUNK, MATCH_WANT_BLOCKS)
 
 
 def as_descriptors(a, name="descriptors"):
@@ -1444,6 +1450,22 @@ def match_offsets(lengths, name):
     return _offsets(lengths, name, "a pair", "pairs", "rows", MATCH_MAX_PAIRS, MATCH_MAX_ROWS)
 
 
+def _match_batch_args(q, t, q_lengths, t_lengths, who):
+    """The descriptors and row counts of a batch call of either matcher -> (q, t, query offsets, train offsets), checked."""
+    q, t = as_descriptors(q, "q"), as_descriptors(t, "t")
+    if len(q_lengths) != len(t_lengths):
+        raise ValueError(f"{who}: {len(q_lengths)} query counts, {len(t_lengths)} train counts")
+    qo, to = match_offsets(q_lengths, "q_lengths"), match_offsets(t_lengths, "t_lengths")
+    if qo[-1] != len(q) or to[-1] != len(t):
+        raise ValueError(f"{who}: the counts sum to {qo[-1]} and {to[-1]} rows; got {len(q)} and {len(t)}")
+    return q, t, qo, to
+
+
+def _match_out(n, dtype, wanted=True):
+    """An output of ``n`` rows, or None where the caller did not ask for it."""
+    return np.empty(n, dtype) if wanted else None
+
+
 def match_descriptors(q, t, second=True, device=-1, ctx=None):
     """``apap_match_descriptors``: for every row of ``q`` (nq, 128) the nearest row of ``t`` (nt, 128) under the L2 distance,
     exactly (float32 sum of squared differences; exact for integer descriptors in 0 .. 255), and with ``second`` the
@@ -1453,8 +1475,8 @@ def match_descriptors(q, t, second=True, device=-1, ctx=None):
     q, t = as_descriptors(q, "q"), as_descriptors(t, "t")
     if not 1 <= len(q) <= MATCH_MAX_ROWS or not 1 <= len(t) <= MATCH_MAX_ROWS:
         raise ValueError(f"match_descriptors: {len(q)} queries, {len(t)} train rows (1 .. 2^24 each)")
-    idx, dist = np.empty(len(q), np.int32), np.empty(len(q), np.float32)
-    idx2, dist2 = (np.empty(len(q), np.int32), np.empty(len(q), np.float32)) if second else (None, None)
+    idx, dist = _match_out(len(q), np.int32), _match_out(len(q), np.float32)
+    idx2, dist2 = _match_out(len(q), np.int32, second), _match_out(len(q), np.float32, second)
     check(lib().apap_match_descriptors(_h(ctx), _ptr(q, C.c_float), len(q), _ptr(t, C.c_float), len(t), _ptr(idx, C.c_int),
                                        _ptr(dist, C.c_float), _ptr(idx2, C.c_int), _ptr(dist2, C.c_float), device))
     return idx, dist, idx2, dist2
@@ -1465,14 +1487,9 @@ def match_descriptors_batch(q, t, q_lengths, t_lengths, second=True, device=-1, 
     the pairs' descriptors concatenated, pair p of ``q_lengths[p]`` queries and ``t_lengths[p]`` train rows.  Returns the four
     arrays of ``match_descriptors`` laid out like ``q``; a pair's indices count from its own first train row, and its outputs
     equal its own single call's byte for byte."""
-    q, t = as_descriptors(q, "q"), as_descriptors(t, "t")
-    if len(q_lengths) != len(t_lengths):
-        raise ValueError(f"match_descriptors_batch: {len(q_lengths)} query counts, {len(t_lengths)} train counts")
-    qo, to = match_offsets(q_lengths, "q_lengths"), match_offsets(t_lengths, "t_lengths")
-    if qo[-1] != len(q) or to[-1] != len(t):
-        raise ValueError(f"match_descriptors_batch: the counts sum to {qo[-1]} and {to[-1]} rows; got {len(q)} and {len(t)}")
-    idx, dist = np.empty(len(q), np.int32), np.empty(len(q), np.float32)
-    idx2, dist2 = (np.empty(len(q), np.int32), np.empty(len(q), np.float32)) if second else (None, None)
+    q, t, qo, to = _match_batch_args(q, t, q_lengths, t_lengths, "match_descriptors_batch")
+    idx, dist = _match_out(len(q), np.int32), _match_out(len(q), np.float32)
+    idx2, dist2 = _match_out(len(q), np.int32, second), _match_out(len(q), np.float32, second)
     check(lib().apap_match_descriptors_batch(_h(ctx), _ptr(q, C.c_float), _ptr(t, C.c_float), _ptr(qo, C.c_int), _ptr(to, C.c_int),
                                              len(qo) - 1, _ptr(idx, C.c_int), _ptr(dist, C.c_float), _ptr(idx2, C.c_int),
                                              _ptr(dist2, C.c_float), device))
@@ -1491,11 +1508,8 @@ GUIDED_KIND = {"point": GUIDED_POINT, "line": GUIDED_LINE}
 
 
 def guided_splits(nq, nt):
-    """``match_splits`` for the guided matcher's tiling: (splits of the train axis, chunks of each)."""
-    q_tiles = -(-int(nq) // GUIDED_QUERY_TILE)
-    chunks = -(-int(nt) // GUIDED_TRAIN_CHUNK)
-    per = -(-chunks // min(chunks, -(-GUIDED_WANT_BLOCKS // q_tiles)))
-    return -(-chunks // per), per
+    """``train_splits`` for the guided matcher's tiling: (splits of the train axis, chunks of each)."""
+    return train_splits(nq, nt, GUIDED_QUERY_TILE, GUIDED_TRAIN_CHUNK, GUIDED_WANT_BLOCKS)
 
 
 def guided_what(what):
@@ -1557,18 +1571,13 @@ def match_guided_batch(q, t, rec_q, rec_t, q_lengths, t_lengths, kind, r2, secon
     or one per pair).  Returns (idx, dist, idx2, dist2, count, ridx, rdist): the first five laid out like ``q``, the
     last two like ``t``; whatever was not asked for is ``None``."""
     kind = guided_kind(kind)
-    q, t = as_descriptors(q, "q"), as_descriptors(t, "t")
-    if len(q_lengths) != len(t_lengths):
-        raise ValueError(f"match_guided_batch: {len(q_lengths)} query counts, {len(t_lengths)} train counts")
-    qo, to = match_offsets(q_lengths, "q_lengths"), match_offsets(t_lengths, "t_lengths")
-    if qo[-1] != len(q) or to[-1] != len(t):
-        raise ValueError(f"match_guided_batch: the counts sum to {qo[-1]} and {to[-1]} rows; got {len(q)} and {len(t)}")
+    q, t, qo, to = _match_batch_args(q, t, q_lengths, t_lengths, "match_guided_batch")
     rec_q, rec_t = as_guided_records(rec_q, len(q), "rec_q"), as_guided_records(rec_t, len(t), "rec_t")
     r2 = guided_r2(r2, len(qo) - 1)
-    idx, dist = np.empty(len(q), np.int32), np.empty(len(q), np.float32)
-    idx2, dist2 = (np.empty(len(q), np.int32), np.empty(len(q), np.float32)) if second else (None, None)
-    cnt = np.empty(len(q), np.int32) if count else None
-    ridx, rdist = (np.empty(len(t), np.int32), np.empty(len(t), np.float32)) if reverse else (None, None)
+    idx, dist = _match_out(len(q), np.int32), _match_out(len(q), np.float32)
+    idx2, dist2 = _match_out(len(q), np.int32, second), _match_out(len(q), np.float32, second)
+    cnt = _match_out(len(q), np.int32, count)
+    ridx, rdist = _match_out(len(t), np.int32, reverse), _match_out(len(t), np.float32, reverse)
     check(lib().apap_match_guided_batch(_h(ctx), _ptr(rec_q, C.c_double), _ptr(rec_t, C.c_double), _ptr(q, C.c_float),
                                         _ptr(t, C.c_float), _ptr(qo, C.c_int), _ptr(to, C.c_int), len(qo) - 1, kind,
                                         _ptr(r2, C.c_double), _ptr(idx, C.c_int), _ptr(dist, C.c_float), _ptr(idx2, C.c_int),

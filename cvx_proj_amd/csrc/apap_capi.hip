@@ -1348,6 +1348,31 @@ int apap_local_model_solve(apap_ctx *ctx, const float *pts_c, const float *pts_o
 }
 
 // ------------------------------------------------------------------ descriptor matching (apap_match.hip)
+// What the host-buffer batch calls of the two matchers stage alike: the offsets relative to the first pair (the device arrays
+// start there), the parts of the descriptors and of the four common outputs, their uploads and downloads.
+struct MatchIo {
+    size_t q0, t0, NQ, NT;
+    std::vector<int> qrel, trel;
+    Part d_q, d_t, d_idx, d_dist, d_idx2, d_dist2;
+    MatchIo(Layout &io, const int *q_offset, const int *t_offset, int n_pairs, bool idx2, bool dist2)
+        : q0((size_t)q_offset[0]), t0((size_t)t_offset[0]), NQ((size_t)q_offset[n_pairs] - q0), NT((size_t)t_offset[n_pairs] - t0),
+          qrel(relative_offsets(q_offset, n_pairs)), trel(relative_offsets(t_offset, n_pairs)) {
+        const size_t row = APAP_MATCH_DIM * sizeof(float);
+        d_q = io.take(NQ * row), d_t = io.take(NT * row), d_idx = io.take(NQ * sizeof(int)), d_dist = io.take(NQ * sizeof(float));
+        d_idx2 = io.take(idx2 ? NQ * sizeof(int) : 0), d_dist2 = io.take(dist2 ? NQ * sizeof(float) : 0);
+    }
+    void up(HostCall &call, const float *q, const float *t) const {
+        call.up(d_q, q + q0 * APAP_MATCH_DIM);
+        call.up(d_t, t + t0 * APAP_MATCH_DIM);
+    }
+    void down(HostCall &call, int *idx, float *dist, int *idx2, float *dist2) const {
+        call.down(idx + q0, d_idx);
+        call.down(dist + q0, d_dist);
+        if (idx2) call.down(idx2 + q0, d_idx2);
+        if (dist2) call.down(dist2 + q0, d_dist2);
+    }
+};
+
 int apap_match_descriptors_batch(apap_ctx *ctx, const float *q, const float *t, const int *q_offset, const int *t_offset,
                                  int n_pairs, int *idx, float *dist, int *idx2, float *dist2, int device) {
     const char *who = "apap_match_descriptors_batch";
@@ -1356,26 +1381,17 @@ int apap_match_descriptors_batch(apap_ctx *ctx, const float *q, const float *t, 
     if (rc) return rc;
     HostCall call(ctx);
     if ((rc = call.select(device))) return rc;
-    const size_t q0 = (size_t)q_offset[0], t0 = (size_t)t_offset[0];   // the device arrays start at the first pair
-    const size_t NQ = (size_t)q_offset[n_pairs] - q0, NT = (size_t)t_offset[n_pairs] - t0;
-    const std::vector<int> qrel = relative_offsets(q_offset, n_pairs), trel = relative_offsets(t_offset, n_pairs);
     Layout io = call.layout(S_AUX);
-    const size_t row = APAP_MATCH_DIM * sizeof(float);
-    const Part d_q = io.take(NQ * row), d_t = io.take(NT * row), d_idx = io.take(NQ * sizeof(int)), d_dist = io.take(NQ * sizeof(float));
-    const Part d_idx2 = io.take(idx2 ? NQ * sizeof(int) : 0), d_dist2 = io.take(dist2 ? NQ * sizeof(float) : 0);
+    const MatchIo m(io, q_offset, t_offset, n_pairs, idx2, dist2);
     call.alloc(io);
-    const Part work = call.slot(S_WORK, apap_match_batch_workspace_bytes(qrel.data(), trel.data(), n_pairs));
-    call.up(d_q, q + q0 * APAP_MATCH_DIM);
-    call.up(d_t, t + t0 * APAP_MATCH_DIM);
+    const Part work = call.slot(S_WORK, apap_match_batch_workspace_bytes(m.qrel.data(), m.trel.data(), n_pairs));
+    m.up(call, q, t);
     if ((rc = call.rc())) return rc;
-    rc = apap_match_descriptors_batch_device(ctx, d_q.as<const float>(), d_t.as<const float>(), qrel.data(), trel.data(), n_pairs,
-                                             d_idx.as<int>(), d_dist.as<float>(), idx2 ? d_idx2.as<int>() : nullptr,
-                                             dist2 ? d_dist2.as<float>() : nullptr, work.as<void>(), work.bytes, call.stream());
+    rc = apap_match_descriptors_batch_device(ctx, m.d_q.as<const float>(), m.d_t.as<const float>(), m.qrel.data(), m.trel.data(),
+                                             n_pairs, m.d_idx.as<int>(), m.d_dist.as<float>(), idx2 ? m.d_idx2.as<int>() : nullptr,
+                                             dist2 ? m.d_dist2.as<float>() : nullptr, work.as<void>(), work.bytes, call.stream());
     if (rc) return rc;
-    call.down(idx + q0, d_idx);
-    call.down(dist + q0, d_dist);
-    if (idx2) call.down(idx2 + q0, d_idx2);
-    if (dist2) call.down(dist2 + q0, d_dist2);
+    m.down(call, idx, dist, idx2, dist2);
     return call.wait();
 }
 
@@ -1418,36 +1434,28 @@ int apap_match_guided_batch(apap_ctx *ctx, const double *rec_q, const double *re
     if (rc) return rc;
     HostCall call(ctx);
     if ((rc = call.select(device))) return rc;
-    const size_t q0 = (size_t)q_offset[0], t0 = (size_t)t_offset[0];   // the device arrays start at the first pair
-    const size_t NQ = (size_t)q_offset[n_pairs] - q0, NT = (size_t)t_offset[n_pairs] - t0;
-    const std::vector<int> qrel = relative_offsets(q_offset, n_pairs), trel = relative_offsets(t_offset, n_pairs);
     Layout io = call.layout(S_AUX);
-    const size_t row = APAP_MATCH_DIM * sizeof(float), rec = 3 * sizeof(double);
-    const Part d_q = io.take(NQ * row), d_t = io.take(NT * row), d_rq = io.take(NQ * rec), d_rt = io.take(NT * rec);
-    const Part d_idx = io.take(NQ * sizeof(int)), d_dist = io.take(NQ * sizeof(float));
-    const Part d_idx2 = io.take(idx2 ? NQ * sizeof(int) : 0), d_dist2 = io.take(dist2 ? NQ * sizeof(float) : 0);
-    const Part d_count = io.take(count ? NQ * sizeof(int) : 0);
+    const MatchIo m(io, q_offset, t_offset, n_pairs, idx2, dist2);
+    const size_t NQ = m.NQ, NT = m.NT, rec = 3 * sizeof(double);
+    const Part d_rq = io.take(NQ * rec), d_rt = io.take(NT * rec), d_count = io.take(count ? NQ * sizeof(int) : 0);
     const Part d_ridx = io.take(ridx ? NT * sizeof(int) : 0), d_rdist = io.take(ridx ? NT * sizeof(float) : 0);
     call.alloc(io);
-    const Part work = call.slot(S_WORK, apap_match_guided_batch_workspace_bytes(qrel.data(), trel.data(), n_pairs));
-    call.up(d_q, q + q0 * APAP_MATCH_DIM);
-    call.up(d_t, t + t0 * APAP_MATCH_DIM);
-    call.up(d_rq, rec_q + q0 * 3);
-    call.up(d_rt, rec_t + t0 * 3);
+    const Part work = call.slot(S_WORK, apap_match_guided_batch_workspace_bytes(m.qrel.data(), m.trel.data(), n_pairs));
+    m.up(call, q, t);
+    call.up(d_rq, rec_q + m.q0 * 3);
+    call.up(d_rt, rec_t + m.t0 * 3);
     if ((rc = call.rc())) return rc;
-    rc = apap_match_guided_batch_device(ctx, d_rq.as<const double>(), d_rt.as<const double>(), d_q.as<const float>(),
-                                        d_t.as<const float>(), qrel.data(), trel.data(), n_pairs, kind, r2, d_idx.as<int>(),
-                                        d_dist.as<float>(), idx2 ? d_idx2.as<int>() : nullptr, dist2 ? d_dist2.as<float>() : nullptr,
-                                        count ? d_count.as<int>() : nullptr, ridx ? d_ridx.as<int>() : nullptr,
-                                        ridx ? d_rdist.as<float>() : nullptr, work.as<void>(), work.bytes, call.stream());
+    rc = apap_match_guided_batch_device(ctx, d_rq.as<const double>(), d_rt.as<const double>(), m.d_q.as<const float>(),
+                                        m.d_t.as<const float>(), m.qrel.data(), m.trel.data(), n_pairs, kind, r2, m.d_idx.as<int>(),
+                                        m.d_dist.as<float>(), idx2 ? m.d_idx2.as<int>() : nullptr,
+                                        dist2 ? m.d_dist2.as<float>() : nullptr, count ? d_count.as<int>() : nullptr,
+                                        ridx ? d_ridx.as<int>() : nullptr, ridx ? d_rdist.as<float>() : nullptr, work.as<void>(),
+                                        work.bytes, call.stream());
     if (rc) return rc;
-    call.down(idx + q0, d_idx);
-    call.down(dist + q0, d_dist);
-    if (idx2) call.down(idx2 + q0, d_idx2);
-    if (dist2) call.down(dist2 + q0, d_dist2);
-    if (count) call.down(count + q0, d_count);
-    if (ridx) call.down(ridx + t0, d_ridx);
-    if (ridx) call.down(rdist + t0, d_rdist);
+    m.down(call, idx, dist, idx2, dist2);
+    if (count) call.down(count + m.q0, d_count);
+    if (ridx) call.down(ridx + m.t0, d_ridx);
+    if (ridx) call.down(rdist + m.t0, d_rdist);
     return call.wait();
 }
 

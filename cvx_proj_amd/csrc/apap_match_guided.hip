@@ -5,8 +5,10 @@
 // 3 x 3 model, or the line that the model makes of it).  The gate of a (query, train) pair is 6 float64 operations on the two
 // records, each a single IEEE operation in the written order; the comparison is strict and a NaN fails it.
 //
-//     d2(i, j) = sum_k (q[i, k] - t[j, k])^2          float32, acc = 0, then d = q - t, acc = fmaf(d, d, acc), k ascending:
-//                                                     the three lines of k_match_sweep's loop, restated; the same bits.
+//     d2(i, j) = sum_k (q[i, k] - t[j, k])^2          float32, from acc = 0 by the matcher's d2_step, k ascending
+//
+// The step, the order of the candidates, the pair's record, the split of the train axis and the finish are the matcher's own
+// (apap_match_dev.h).
 //
 // Candidates are ordered by (d2, train index), the reverse side by (d2, query index); a NaN or infinite d2 is counted by the
 // gate and never selected.  Both orders are total, so no output depends on how the rows are cut into tiles, chunks and splits
@@ -25,16 +27,11 @@
 // dist, idx2, dist2, count; the same thread turns train row i's packed minimum into ridx, rdist.
 //
 // A batch is the same launches with the pair in blockIdx.y; the single call is the batch of one.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
-#include <vector>
-
-#include "apap_internal.h"
+#include "apap_match_dev.h"
 
 namespace {
+
+using namespace apap;
 
 constexpr int kDim = APAP_MATCH_DIM;
 constexpr int kGuidedQ = APAP_GUIDED_QUERY_TILE;     // queries per block, one per lane
@@ -42,51 +39,17 @@ constexpr int kGuidedT = APAP_GUIDED_TRAIN_CHUNK;    // train records per staged
 constexpr int kGuidedDrain = APAP_GUIDED_DRAIN;      // survivors a wave sums at once
 constexpr int kThreads = 256, kWave = 64;
 constexpr int kGroup = 4;                            // train records gated between two looks at the ballots
-constexpr int kMaxRows = 1 << 24;
 constexpr unsigned long long kNone = ~0ull;          // a train row that no query has reached
 static_assert(kDim == 128 && kGuidedQ == kThreads && kGuidedDrain == kWave && kGuidedT % kGroup == 0, "the thread mapping below is for these");
 static_assert(kMaxRows <= (1 << 24), "a list entry packs the row into 24 bits");
+constexpr MatchTiling kTiling{kGuidedQ, kGuidedT, APAP_GUIDED_WANT_BLOCKS, 1};   // the batch's partials are rounded once, together
 
-struct GuidedPart {   // a query's running result over some train rows: (d2, index) of the best and of the runner-up, gate passes
-    float d1;
-    int i1;
-    float d2;
-    int i2;
+struct GuidedPart {   // a query's running result over some train rows, and how many of them passed the gate
+    Top2 m;
     int count;
     int pad;
 };
 static_assert(sizeof(GuidedPart) == 24, "GuidedPart");
-
-struct alignas(16) GuidedPair {   // one pair, in device memory
-    int q0, t0, nq, nt;           // first query / train row in the concatenated arrays, counts
-    int q_tiles, splits, cps;     // blocks along the queries, splits of the train axis, chunks per split
-    int rb0;                      // the pair's first train row in the workspace's packed minima
-    long long part0;              // first partial of the pair: partial of (split s, query i) at part0 + s nq + i
-    double r2;
-};
-static_assert(sizeof(GuidedPair) == 48, "GuidedPair");
-
-// (da, ia) before (db, ib) in the order of the candidates.  An empty slot is (+inf, -1): no candidate is infinite.
-__device__ __forceinline__ bool before(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
-
-__device__ __forceinline__ void take(GuidedPart &m, float d, int j) {
-    if (before(d, j, m.d1, m.i1)) {
-        m.d2 = m.d1;
-        m.i2 = m.i1;
-        m.d1 = d;
-        m.i1 = j;
-    } else if (before(d, j, m.d2, m.i2)) {
-        m.d2 = d;
-        m.i2 = j;
-    }
-}
-
-__device__ __forceinline__ GuidedPart merge(GuidedPart a, const GuidedPart &b) {
-    if (b.i1 >= 0) take(a, b.d1, b.i1);
-    if (b.i2 >= 0) take(a, b.d2, b.i2);
-    a.count += b.count;
-    return a;
-}
 
 __global__ __launch_bounds__(kThreads) void k_guided_records(const float *__restrict__ pts, int n, const double *__restrict__ model,
                                                              int what, double *__restrict__ rec) {
@@ -115,13 +78,12 @@ __global__ __launch_bounds__(kThreads) void k_guided_records(const float *__rest
 template <int kKind>
 __global__ __launch_bounds__(kThreads) void k_guided_sweep(const double *__restrict__ rec_q, const double *__restrict__ rec_t,
                                                            const float *__restrict__ q, const float *__restrict__ t,
-                                                           const GuidedPair *__restrict__ tab, GuidedPart *__restrict__ parts,
+                                                           const MatchPair *__restrict__ tab, GuidedPart *__restrict__ parts,
                                                            unsigned long long *__restrict__ rbest) {
-    const GuidedPair P = tab[blockIdx.y];
+    const MatchPair P = tab[blockIdx.y];
     if (blockIdx.x >= (unsigned)(P.q_tiles * P.splits)) return;
-    const int qt = blockIdx.x % P.q_tiles, sp = blockIdx.x / P.q_tiles;
-    const int n_chunks = (P.nt + kGuidedT - 1) / kGuidedT;
-    const int c_begin = sp * P.cps, c_end = min(n_chunks, c_begin + P.cps);
+    const PairRun<kGuidedT> run(P, blockIdx.x);
+    const int qt = run.qt;
 
     __shared__ __attribute__((aligned(16))) double2 bs[kGuidedT];            // the chunk's records: the two coordinates
     __shared__ int lists[kThreads / kWave][2 * kGuidedDrain];                 // a wave's survivors: lane << 24 | train row
@@ -137,7 +99,7 @@ __global__ __launch_bounds__(kThreads) void k_guided_sweep(const double *__restr
     const float *qp = q + (size_t)P.q0 * kDim, *tp = t + (size_t)P.t0 * kDim;
     const int wave_q0 = qt * kGuidedQ + (tid - lane);   // the query of this wave's lane 0
 
-    GuidedPart best{INFINITY, -1, INFINITY, -1, 0, 0};
+    GuidedPart best{empty_top2(), 0, 0};
     int fill = 0;   // entries in the wave's list; wave-uniform
 
     // entries [fill - n, fill) of the list: lane e sums entry e, then every result goes to its owner lane
@@ -154,10 +116,7 @@ __global__ __launch_bounds__(kThreads) void k_guided_sweep(const double *__restr
                 const float4 av = a[c], bv = b[c];
                 const float qa[4] = {av.x, av.y, av.z, av.w}, tv[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float d = qa[k] - tv[k];
-                    acc = fmaf(d, d, acc);
-                }
+                for (int k = 0; k < 4; ++k) acc = d2_step(acc, qa[k], tv[k]);
             }
             // acc is finite here: not negative and not -0, so its bits order as it does
             if (rbest && acc < INFINITY)
@@ -166,12 +125,12 @@ __global__ __launch_bounds__(kThreads) void k_guided_sweep(const double *__restr
         for (int e = 0; e < n; ++e) {
             const int en = __shfl(entry, e);
             const float d = __shfl(acc, e);
-            if (lane == (en >> 24) && d < INFINITY) take(best, d, en & 0xFFFFFF);
+            if (lane == (en >> 24) && d < INFINITY) take(best.m, d, en & 0xFFFFFF);
         }
         fill -= n;
     };
 
-    for (int chunk = c_begin; chunk < c_end; ++chunk) {
+    for (int chunk = run.c_begin; chunk < run.c_end; ++chunk) {
         const int rows = min(kGuidedT, P.nt - chunk * kGuidedT);
         __syncthreads();   // the previous chunk has been consumed
         // rows are walked in groups of kGroup: the chunk's last group is filled up with NaN, which passes no gate
@@ -211,25 +170,24 @@ __global__ __launch_bounds__(kThreads) void k_guided_sweep(const double *__restr
         }
     }
     if (fill > 0) drain(fill);
-    if (valid) parts[P.part0 + (long long)sp * P.nq + i] = best;
+    if (valid) parts[P.part0 + (long long)run.sp * P.nq + i] = best;
 }
 
-__global__ __launch_bounds__(kThreads) void k_guided_finish(const GuidedPair *__restrict__ tab, const GuidedPart *__restrict__ parts,
+__global__ __launch_bounds__(kThreads) void k_guided_finish(const MatchPair *__restrict__ tab, const GuidedPart *__restrict__ parts,
                                                             const unsigned long long *__restrict__ rbest, int *__restrict__ idx,
                                                             float *__restrict__ dist, int *__restrict__ idx2, float *__restrict__ dist2,
                                                             int *__restrict__ count, int *__restrict__ ridx, float *__restrict__ rdist) {
-    const GuidedPair P = tab[blockIdx.y];
+    const MatchPair P = tab[blockIdx.y];
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i < P.nq) {
         GuidedPart m = parts[P.part0 + i];
-        for (int s = 1; s < P.splits; ++s) m = merge(m, parts[P.part0 + (long long)s * P.nq + i]);
-        // float32(sqrt in float64) is the correctly rounded float32 square root: 53 >= 2 * 24 + 2 bits
-        const size_t o = (size_t)P.q0 + i;
-        idx[o] = m.i1;
-        dist[o] = m.i1 >= 0 ? (float)sqrt((double)m.d1) : INFINITY;
-        if (idx2) idx2[o] = m.i2;
-        if (dist2) dist2[o] = m.i2 >= 0 ? (float)sqrt((double)m.d2) : INFINITY;
-        if (count) count[o] = m.count;
+        for (int s = 1; s < P.splits; ++s) {
+            const GuidedPart b = parts[P.part0 + (long long)s * P.nq + i];
+            m.m = merge(m.m, b.m);
+            m.count += b.count;
+        }
+        write_top2(m.m, (size_t)P.q0 + i, idx, dist, idx2, dist2);
+        if (count) count[(size_t)P.q0 + i] = m.count;
     }
     if (ridx && i < P.nt) {
         const size_t o = (size_t)P.t0 + i;
@@ -239,24 +197,6 @@ __global__ __launch_bounds__(kThreads) void k_guided_finish(const GuidedPair *__
     }
 }
 
-// How a pair of (nq, nt) rows is cut: a function of the pair alone.
-struct GuidedPlan {
-    int q_tiles, splits, cps;
-    size_t parts;   // partials: one per query and split
-};
-
-GuidedPlan plan_guided(int nq, int nt) {
-    GuidedPlan p;
-    p.q_tiles = (nq + kGuidedQ - 1) / kGuidedQ;
-    const int n_chunks = (nt + kGuidedT - 1) / kGuidedT;
-    const int want = std::min(n_chunks, (APAP_GUIDED_WANT_BLOCKS + p.q_tiles - 1) / p.q_tiles);
-    p.cps = (n_chunks + want - 1) / want;
-    p.splits = (n_chunks + p.cps - 1) / p.cps;
-    p.parts = (size_t)p.splits * nq;
-    return p;
-}
-
-size_t table_bytes(int n_pairs) { return apap::up256((size_t)n_pairs * sizeof(GuidedPair)); }
 size_t reverse_bytes(size_t train_rows) { return apap::up256(train_rows * sizeof(unsigned long long)); }
 
 }  // namespace
@@ -304,9 +244,8 @@ int apap_guided_records_device(apap_ctx *ctx, const float *d_pts, int n, const d
 
 size_t apap_match_guided_batch_workspace_bytes(const int *q_offset, const int *t_offset, int n_pairs) {
     if (apap::match_check(q_offset, t_offset, n_pairs, "apap_match_guided_batch_workspace_bytes")) return 0;
-    size_t parts = 0;
-    for (int p = 0; p < n_pairs; ++p) parts += plan_guided(q_offset[p + 1] - q_offset[p], t_offset[p + 1] - t_offset[p]).parts;
-    return table_bytes(n_pairs) + reverse_bytes((size_t)t_offset[n_pairs] - (size_t)t_offset[0]) + apap::up256(parts * sizeof(GuidedPart));
+    return pair_table_bytes(n_pairs) + reverse_bytes((size_t)t_offset[n_pairs] - (size_t)t_offset[0]) +
+           apap::up256(kTiling.parts(q_offset, t_offset, n_pairs) * sizeof(GuidedPart));
 }
 
 size_t apap_match_guided_workspace_bytes(int nq, int nt) {
@@ -320,46 +259,24 @@ int apap_match_guided_batch_device(apap_ctx *ctx, const double *d_rec_q, const d
                                    void *d_work, size_t work_bytes, void *stream) {
     const char *who = "apap_match_guided_batch_device";
     (void)ctx;
-    const int rc = apap::guided_check(q_offset, t_offset, n_pairs, kind, r2, who);
+    int rc = apap::guided_check(q_offset, t_offset, n_pairs, kind, r2, who);
     if (rc) return rc;
-    if (!d_rec_q || !d_rec_t || !d_q || !d_t || !d_idx || !d_dist || !d_work)
-        return apap::fail(APAP_ERR_INVALID_ARG, "%s: null device pointer", who);
-    if (!d_ridx != !d_rdist) return apap::fail(APAP_ERR_INVALID_ARG, "%s: ridx and rdist go together (both or neither)", who);
     const size_t need = apap_match_guided_batch_workspace_bytes(q_offset, t_offset, n_pairs);
-    if (work_bytes < need) return apap::fail(APAP_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, work_bytes, need);
-    if (((uintptr_t)d_work & 255) != 0 || ((uintptr_t)d_q & 15) != 0 || ((uintptr_t)d_t & 15) != 0)
-        return apap::fail(APAP_ERR_INVALID_ARG, "%s: workspace must be 256-byte and descriptors 16-byte aligned", who);
+    if ((rc = match_device_check(d_rec_q && d_rec_t && d_q && d_t && d_idx && d_dist && d_work, !d_ridx == !d_rdist, d_q, d_t, d_work,
+                                 work_bytes, need, who)))
+        return rc;
 
     // the workspace: the pairs' table, the train rows' packed minima (from t_offset[0] on), the partials
     const size_t train_rows = (size_t)t_offset[n_pairs] - (size_t)t_offset[0];
-    const size_t at_rbest = table_bytes(n_pairs), at_parts = at_rbest + reverse_bytes(train_rows);
-    std::vector<GuidedPair> tab((size_t)n_pairs);
-    size_t off = 0;   // in partials
-    int max_blocks = 0, max_rows = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-        GuidedPair &d = tab[p];
-        d.q0 = q_offset[p];
-        d.t0 = t_offset[p];
-        d.nq = q_offset[p + 1] - q_offset[p];
-        d.nt = t_offset[p + 1] - t_offset[p];
-        const GuidedPlan plan = plan_guided(d.nq, d.nt);
-        d.q_tiles = plan.q_tiles;
-        d.splits = plan.splits;
-        d.cps = plan.cps;
-        d.rb0 = t_offset[p] - t_offset[0];
-        d.part0 = (long long)off;
-        d.r2 = r2[p];
-        off += plan.parts;
-        max_blocks = std::max(max_blocks, plan.q_tiles * plan.splits);
-        max_rows = std::max(max_rows, std::max(d.nq, d_ridx ? d.nt : 0));
-    }
+    const size_t at_rbest = pair_table_bytes(n_pairs), at_parts = at_rbest + reverse_bytes(train_rows);
     hipStream_t s = (hipStream_t)stream;
-    GuidedPair *d_tab = (GuidedPair *)d_work;
+    MatchPair *d_tab = (MatchPair *)d_work;
     unsigned long long *d_rbest = d_ridx ? (unsigned long long *)((char *)d_work + at_rbest) : nullptr;
     GuidedPart *d_parts = (GuidedPart *)((char *)d_work + at_parts);
-    // from pageable memory in stream order: the copy returns once its source has been consumed
-    hipError_t e = hipMemcpyAsync(d_tab, tab.data(), (size_t)n_pairs * sizeof(GuidedPair), hipMemcpyHostToDevice, s);
+    PairExtent ext;
+    hipError_t e = upload_pair_table(kTiling, q_offset, t_offset, n_pairs, r2, d_tab, s, &ext);
     if (e != hipSuccess) return apap::hip_fail(e, "apap_match_guided_batch_device: descriptor upload");
+    const int max_blocks = ext.max_blocks, max_rows = std::max(ext.max_nq, d_ridx ? ext.max_nt : 0);
     if (d_ridx && (e = hipMemsetAsync((char *)d_work + at_rbest, 0xFF, train_rows * sizeof(unsigned long long), s)) != hipSuccess)
         return apap::hip_fail(e, "apap_match_guided_batch_device: reverse fill");
     if (kind == APAP_GUIDED_LINE)

@@ -579,14 +579,43 @@ def hip_local_model_solve(pts_c, pts_o, vertices, gamma, sigma, params, match_we
     return H, info, status
 
 
+def _match_workspace(single, batch, q_lengths, t_lengths):
+    """A matcher's scratch from its two library functions: of one (nq, nt) pair, or of the pairs' row counts."""
+    if np.ndim(q_lengths) == 0:
+        return single(int(q_lengths), int(t_lengths))
+    qo, to = _native.match_offsets(q_lengths, "q_lengths"), _native.match_offsets(t_lengths, "t_lengths")
+    return batch(_ip(qo), _ip(to), min(len(qo), len(to)) - 1)
+
+
+def _match_batch_args(q, t, q_lengths, t_lengths, who):
+    """``_native._match_batch_args`` for device tensors: the checks of a batch call of either matcher -> (query offsets, train
+    offsets)."""
+    dev = q.device
+    for x in (q, t):
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.device != dev or x.dim() != 2 or x.shape[1] != _native.MATCH_DIM:
+            raise ValueError(f"{who}: descriptors must be contiguous float32 (n, {_native.MATCH_DIM}) tensors on {dev}")
+    if len(q_lengths) != len(t_lengths):
+        raise ValueError(f"{who}: {len(q_lengths)} query counts, {len(t_lengths)} train counts")
+    qo, to = _native.match_offsets(q_lengths, "q_lengths"), _native.match_offsets(t_lengths, "t_lengths")
+    if qo[-1] != q.shape[0] or to[-1] != t.shape[0]:
+        raise ValueError(f"{who}: the counts sum to {qo[-1]} and {to[-1]} rows; got {q.shape[0]} and {t.shape[0]}")
+    return qo, to
+
+
+def _match_out(dev):
+    """The allocator of a matcher's outputs on ``dev``: ``out(n, dtype, wanted)``, None for what was not asked for."""
+    return lambda n, dtype, wanted=True: torch.empty(n, dtype=dtype, device=dev) if wanted else None
+
+
+def _ptr(x):
+    return None if x is None else x.data_ptr()
+
+
 def match_workspace_bytes(q_lengths, t_lengths=None):
     """Scratch of ``hip_match_descriptors(q, t)`` as ``match_workspace_bytes(nq, nt)``, or of ``hip_match_descriptors_batch``
     as ``match_workspace_bytes(q_lengths, t_lengths)`` with the pairs' row counts: 16 bytes per query and split of its pair's
     train axis.  0 for invalid arguments."""
-    if np.ndim(q_lengths) == 0:
-        return _native.lib().apap_match_workspace_bytes(int(q_lengths), int(t_lengths))
-    qo, to = _native.match_offsets(q_lengths, "q_lengths"), _native.match_offsets(t_lengths, "t_lengths")
-    return _native.lib().apap_match_batch_workspace_bytes(_ip(qo), _ip(to), min(len(qo), len(to)) - 1)
+    return _match_workspace(_native.lib().apap_match_workspace_bytes, _native.lib().apap_match_batch_workspace_bytes, q_lengths, t_lengths)
 
 
 def hip_match_descriptors_batch(q, t, q_lengths, t_lengths, second=True, ctx=None, work=None):
@@ -599,25 +628,14 @@ def hip_match_descriptors_batch(q, t, q_lengths, t_lengths, second=True, ctx=Non
     descriptors by ``idx`` into ``hip_spectral_em``'s inputs - is plain tensor indexing and stays with the caller."""
     _needs_device(q, "hip_match_descriptors_batch")
     dev = q.device
-    for x in (q, t):
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.device != dev or x.dim() != 2 or x.shape[1] != _native.MATCH_DIM:
-            raise ValueError(f"hip_match_descriptors_batch: descriptors must be contiguous float32 (n, {_native.MATCH_DIM}) tensors on {dev}")
-    if len(q_lengths) != len(t_lengths):
-        raise ValueError(f"hip_match_descriptors_batch: {len(q_lengths)} query counts, {len(t_lengths)} train counts")
-    qo, to = _native.match_offsets(q_lengths, "q_lengths"), _native.match_offsets(t_lengths, "t_lengths")
-    if qo[-1] != q.shape[0] or to[-1] != t.shape[0]:
-        raise ValueError(f"hip_match_descriptors_batch: the counts sum to {qo[-1]} and {to[-1]} rows; got {q.shape[0]} and {t.shape[0]}")
-    n = q.shape[0]
-    idx = torch.empty(n, dtype=torch.int32, device=dev)
-    dist = torch.empty(n, dtype=torch.float32, device=dev)
-    idx2 = torch.empty(n, dtype=torch.int32, device=dev) if second else None
-    dist2 = torch.empty(n, dtype=torch.float32, device=dev) if second else None
+    qo, to = _match_batch_args(q, t, q_lengths, t_lengths, "hip_match_descriptors_batch")
+    n, out = q.shape[0], _match_out(dev)
+    idx, dist, idx2, dist2 = out(n, torch.int32), out(n, torch.float32), out(n, torch.int32, second), out(n, torch.float32, second)
     p_qo, p_to = _ip(qo), _ip(to)
     work = _scratch(work, _native.lib().apap_match_batch_workspace_bytes(p_qo, p_to, len(qo) - 1), dev)
     _native.check(_native.lib().apap_match_descriptors_batch_device(
-        _native._h(ctx), q.data_ptr(), t.data_ptr(), p_qo, p_to, len(qo) - 1, idx.data_ptr(),
-        dist.data_ptr(), None if idx2 is None else idx2.data_ptr(), None if dist2 is None else dist2.data_ptr(), work.data_ptr(),
-        work.numel(), _stream(dev)))
+        _native._h(ctx), q.data_ptr(), t.data_ptr(), p_qo, p_to, len(qo) - 1, idx.data_ptr(), dist.data_ptr(), _ptr(idx2), _ptr(dist2),
+        work.data_ptr(), work.numel(), _stream(dev)))
     return idx, dist, idx2, dist2
 
 
@@ -654,10 +672,8 @@ def hip_guided_records(pts, model=None, what="point", ctx=None):
 def guided_workspace_bytes(q_lengths, t_lengths=None):
     """Scratch of ``hip_guided_match(…)`` as ``guided_workspace_bytes(nq, nt)``, or of ``hip_guided_match_batch`` with the
     pairs' row counts.  0 for invalid arguments."""
-    if np.ndim(q_lengths) == 0:
-        return _native.lib().apap_match_guided_workspace_bytes(int(q_lengths), int(t_lengths))
-    qo, to = _native.match_offsets(q_lengths, "q_lengths"), _native.match_offsets(t_lengths, "t_lengths")
-    return _native.lib().apap_match_guided_batch_workspace_bytes(_ip(qo), _ip(to), min(len(qo), len(to)) - 1)
+    return _match_workspace(_native.lib().apap_match_guided_workspace_bytes, _native.lib().apap_match_guided_batch_workspace_bytes,
+                            q_lengths, t_lengths)
 
 
 def hip_guided_match_batch(q, t, rec_q, rec_t, q_lengths, t_lengths, kind, r2, second=True, count=True, reverse=False, ctx=None,
@@ -670,31 +686,20 @@ def hip_guided_match_batch(q, t, rec_q, rec_t, q_lengths, t_lengths, kind, r2, s
     _needs_device(q, "hip_guided_match_batch")
     dev = q.device
     kind = _native.guided_kind(kind)
-    for x in (q, t):
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.device != dev or x.dim() != 2 or x.shape[1] != _native.MATCH_DIM:
-            raise ValueError(f"hip_guided_match_batch: descriptors must be contiguous float32 (n, {_native.MATCH_DIM}) tensors on {dev}")
+    qo, to = _match_batch_args(q, t, q_lengths, t_lengths, "hip_guided_match_batch")
     for x, d in ((rec_q, q), (rec_t, t)):
         if x.dtype != torch.float64 or not x.is_contiguous() or x.device != dev or tuple(x.shape) != (d.shape[0], 3):
             raise ValueError(f"hip_guided_match_batch: records must be contiguous float64 ({d.shape[0]}, 3) tensors on {dev}")
-    if len(q_lengths) != len(t_lengths):
-        raise ValueError(f"hip_guided_match_batch: {len(q_lengths)} query counts, {len(t_lengths)} train counts")
-    qo, to = _native.match_offsets(q_lengths, "q_lengths"), _native.match_offsets(t_lengths, "t_lengths")
-    if qo[-1] != q.shape[0] or to[-1] != t.shape[0]:
-        raise ValueError(f"hip_guided_match_batch: the counts sum to {qo[-1]} and {to[-1]} rows; got {q.shape[0]} and {t.shape[0]}")
     r2 = _native.guided_r2(r2, len(qo) - 1)
-    nq, nt = q.shape[0], t.shape[0]
-
-    def out(n, dtype, wanted=True):
-        return torch.empty(n, dtype=dtype, device=dev) if wanted else None
+    nq, nt, out = q.shape[0], t.shape[0], _match_out(dev)
     idx, dist = out(nq, torch.int32), out(nq, torch.float32)
     idx2, dist2, cnt = out(nq, torch.int32, second), out(nq, torch.float32, second), out(nq, torch.int32, count)
     ridx, rdist = out(nt, torch.int32, reverse), out(nt, torch.float32, reverse)
     p_qo, p_to = _ip(qo), _ip(to)
     work = _scratch(work, _native.lib().apap_match_guided_batch_workspace_bytes(p_qo, p_to, len(qo) - 1), dev)
-    ptr = lambda x: None if x is None else x.data_ptr()      # noqa: E731
     _native.check(_native.lib().apap_match_guided_batch_device(
         _native._h(ctx), rec_q.data_ptr(), rec_t.data_ptr(), q.data_ptr(), t.data_ptr(), p_qo, p_to, len(qo) - 1, kind,
-        _dp(r2), idx.data_ptr(), dist.data_ptr(), ptr(idx2), ptr(dist2), ptr(cnt), ptr(ridx), ptr(rdist),
+        _dp(r2), idx.data_ptr(), dist.data_ptr(), _ptr(idx2), _ptr(dist2), _ptr(cnt), _ptr(ridx), _ptr(rdist),
         work.data_ptr(), work.numel(), _stream(dev)))
     return idx, dist, idx2, dist2, cnt, ridx, rdist
 

@@ -2,7 +2,8 @@
 
 * Integer-valued descriptors: d2 in int64 - exact - a stable arg-sort for the nearest and the runner-up (ties to the lowest
   index), and ``np.sqrt(np.float32(d2))``, numpy's correctly rounded float32 square root.
-* Float descriptors: d2 in float64 from the float32 inputs, against which the float32 kernel is held to a derived bound.
+* Float descriptors: d2 in float64 from the float32 inputs, against which the float32 kernel is held to a derived bound;
+  and ``match_f32``, the kernel's own float32 sum restated step by step (``fmaf`` rounds once), which pins its bytes.
 """
 import numpy as np
 
@@ -71,6 +72,57 @@ def match_int(q, t):
         dist2 = np.where(idx2 >= 0, np.sqrt(np.float32(d[rows, np.maximum(idx2, 0)])), np.float32(np.inf)).astype(np.float32)
         out.append((idx, dist, idx2, dist2))
     return tuple(np.concatenate(x) for x in zip(*out))
+
+
+def fmaf(a, b, c):
+    """float32(a * b + c) with one rounding, of float32 arrays: C's fmaf, restated in float64.
+
+    The product of two float32 is exact in float64 (48 bits).  The float64 sum p + c is not: s = fl(p + c) and its error e
+    (Knuth's TwoSum, exact) are.  Where e != 0 the true sum lies strictly between s and its neighbour on e's side, and the one
+    of the two whose last mantissa bit is odd is the sum rounded to odd; rounding that to float32 is rounding the true sum
+    (53 >= 24 + 2 bits: Boldo and Melquiond, "Emulation of a FMA and correctly rounded sums", 2008).  A plain float64 add
+    fails where p + c lies just off the middle of two float32: it rounds onto the middle, and the cast then goes to even."""
+    a, b, c = (np.asarray(x, dtype=np.float32).astype(np.float64) for x in (a, b, c))
+    with np.errstate(invalid="ignore", over="ignore"):
+        p = a * b
+        s = p + c
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)
+        inexact = np.isfinite(s) & (e != 0)      # e is NaN where s is not finite
+        even = (s.view(np.int64) & 1) == 0
+        odd = np.where(inexact & even, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+        return odd.astype(np.float32)
+
+
+def d2_f32(q, t):
+    """The matcher's squared distances (nq, nt) of float32 descriptors, bit for bit: float32 from acc = 0, then for k
+    ascending d = q[i, k] - t[j, k] and acc = fmaf(d, d, acc)."""
+    q, t = np.asarray(q, dtype=np.float32), np.asarray(t, dtype=np.float32)
+    acc = np.zeros((len(q), len(t)), np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(DIM):
+            d = q[:, None, k] - t[None, :, k]
+            acc = fmaf(d, d, acc)
+    return acc
+
+
+def match_f32(q, t):
+    """(idx, dist, idx2, dist2) of float32 descriptors as the matcher defines them: d2_f32, the candidates - the finite d2 -
+    in the order (d2, train index), and float32(sqrt(float64(d2))), the correctly rounded float32 root; -1 and +inf where
+    there is no candidate."""
+    d = d2_f32(q, t)
+    d[~np.isfinite(d)] = np.inf
+    rows = np.arange(len(d))
+    order = np.argsort(d, axis=1, kind="stable")      # stable: equal d2 stay in the order of the index
+    out = []
+    for col in (0, 1):
+        if col < d.shape[1]:
+            i = order[:, col]
+            v = d[rows, i]
+            out += [np.where(np.isinf(v), -1, i).astype(np.int32), np.sqrt(v.astype(np.float64)).astype(np.float32)]
+        else:
+            out += [np.full(len(d), -1, np.int32), np.full(len(d), np.inf, np.float32)]
+    return tuple(out)
 
 
 def filters(idx, dist, dist2, back_idx, ratio=None, cross_check=False):

@@ -45,9 +45,15 @@ def test_the_source_keeps_the_projects_rules():
     assert "getenv" not in text and not re.search(r"cooperative_groups|grid\.sync|hipLaunchCooperativeKernel", text)
     assert not re.search(r"atomicAdd|atomicMin\s*\(\s*\(?\s*float|atomicMax", text)      # the one atomic is an integer minimum
     assert not re.search(r"^\s*(static\s+)?(int|bool)\s+g_\w+\s*=", text, flags=re.M)
-    # the matcher's three-line d2 loop, restated
-    assert re.search(r"const float d = qa\[k\] - tv\[k\];\s*acc = fmaf\(d, d, acc\);", text)
-    assert "apap_match_guided" not in open(os.path.join(ROOT, "cvx_proj_amd", "csrc", "apap_match.hip")).read()
+    # the matcher's d2 step - the subtraction, then the fused multiply-add - is written once, in the header both sources
+    # include, and both sum by it: neither spells a sum of its own
+    matcher = open(os.path.join(ROOT, "cvx_proj_amd", "csrc", "apap_match.hip")).read()
+    shared = open(os.path.join(ROOT, "cvx_proj_amd", "csrc", "apap_match_dev.h")).read()
+    assert len(re.findall(r"const float d = q - t;\s*return fmaf\(d, d, acc\);", shared)) == 1 and shared.count("fmaf(") == 1
+    for source in (text, matcher):
+        assert '#include "apap_match_dev.h"' in source and "fmaf(" not in source and "_rn(" not in source
+    assert "acc = d2_step(acc, qa[k], tv[k]);" in text and "acc[a][b] = d2_step(acc[a][b], qa[a], tv[b]);" in matcher
+    assert "apap_match_guided" not in matcher
 
 
 def test_workspace_sizes(native):
