@@ -343,8 +343,26 @@ SIGNATURES.update({
                                      _vp, C.c_size_t, _vp]),
 })
 
+# the image pyramid and its pack (apap_pyramid.hip)
+_PTRS = C.POINTER(C.c_void_p)
+SIGNATURES.update({
+    "apap_pyramid_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i64p, _i32p, _i32p]),
+    "apap_pyramid_level_caps": (C.c_int, [C.c_int, C.c_int, C.c_int, _i32p]),
+    "apap_pyramid_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "apap_pyramid_build": (C.c_int, [_vp, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, C.c_int]),
+    "apap_pyramid_build_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "apap_pyramid_build_batch": (C.c_int, [_vp, _PTRS, _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _u8p, C.c_int]),
+    "apap_pyramid_build_batch_device": (C.c_int, [_vp, _PTRS, _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp,
+                                                  C.c_size_t, _vp]),
+    "apap_pyramid_keypoints_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "apap_pyramid_keypoints": (C.c_int, [_vp, _f32p, _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, _f32p, _f32p, _i32p, _i64p,
+                                         _i32p, C.c_int]),
+    "apap_pyramid_keypoints_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, _vp, _vp, _vp, _vp, _i32p,
+                                                _vp, C.c_size_t, _vp]),
+})
+
 _lib = None
-_torch_at_load = False      # was torch in the process when the library was loaded?  (cvx_proj_amd.resident refuses otherwise)
+_torch_at_load = False     # was torch in the process when the library was loaded?  (cvx_proj_amd.resident refuses otherwise)
 
 
 def lib():
@@ -1791,12 +1809,13 @@ def corner_params(max_corners, radius, quality_permille, who="corner_detect"):
     return max_corners, radius, quality_permille
 
 
-def corner_detect_batch(imgs, max_corners, radius=5, quality_permille=10, device=-1, ctx=None):
+def corner_detect_batch(imgs, max_corners, radius=5, quality_permille=10, device=-1, ctx=None, full=False):
     """``apap_corner_detect_batch``: exact integer Harris corners (include/apap_hip.h "corner detection") of many images in
     one call (two kernel launches, whatever their number).  ``imgs``: a sequence of (h, w) grey or (h, w, 3) BGR uint8 arrays
     of any shapes.  Returns a list of ``(pts, response)`` per image: float32 (n, 2) integer-valued (x, y) and int64 (n,), by
     response descending then index ascending, ``n <= max_corners``; an image's outputs equal its own single call's byte for
-    byte.  ``max_corners`` beyond the largest image's bound on the corner count asks for no more rows than that bound."""
+    byte.  ``max_corners`` beyond the largest image's bound on the corner count asks for no more rows than that bound.
+    With ``full``: the slabs as the library wrote them, ``(pts (n, rows, 2), response (n, rows), count (n,))``."""
     got = [as_sift_image(im, f"imgs[{m}]") for m, im in enumerate(imgs)]
     if not 1 <= len(got) <= CORNER_MAX_IMAGES:
         raise ValueError(f"corner_detect_batch: {len(got)} images (1 .. {CORNER_MAX_IMAGES})")
@@ -1808,6 +1827,8 @@ def corner_detect_batch(imgs, max_corners, radius=5, quality_permille=10, device
     count = np.empty(len(got), np.int32)
     check(lib().apap_corner_detect_batch(_h(ctx), ptrs, _ip(hs), _ip(ws), _ip(cs), len(got), rows, radius, quality_permille,
                                          _ptr(pts, C.c_float), _ptr(resp, C.c_longlong), _ip(count), device))
+    if full:
+        return pts, resp, count
     return [(pts[m, :count[m]].copy(), resp[m, :count[m]].copy()) for m in range(len(got))]
 
 
@@ -1827,6 +1848,102 @@ def corner_detect(img, max_corners, radius=5, quality_permille=10, device=-1, ct
     if full:
         return pts, resp, count.value
     return pts[:count.value].copy(), resp[:count.value].copy()
+
+
+# ---------------------------------------------------------------- image pyramid: levels at scales 2^-k and (3/4) 2^-k
+PYRAMID_MAX_LEVELS = 16                 # APAP_PYRAMID_MAX_LEVELS
+PYRAMID_MIN_SIDE = 32                   # APAP_PYRAMID_MIN_SIDE
+PYRAMID_TILE_W, PYRAMID_TILE_H = 64, 32   # APAP_PYRAMID_TILE_W, APAP_PYRAMID_TILE_H: the source tile of a block
+
+
+def pyramid_levels_arg(n_levels, who="pyramid"):
+    n_levels = int(n_levels)
+    if not 1 <= n_levels <= PYRAMID_MAX_LEVELS:
+        raise ValueError(f"{who}: levels must be 1 .. {PYRAMID_MAX_LEVELS}; got {n_levels}")
+    return n_levels
+
+
+def as_pyramid_image(img, name="img"):
+    """``as_sift_image`` with the pyramid's smallest side, 32."""
+    img, ch = as_sift_image(img, name)
+    if min(img.shape[:2]) < PYRAMID_MIN_SIDE:
+        raise ValueError(f"{name}: sides must be {PYRAMID_MIN_SIDE} .. {SIFT_MAX_SIDE}; got {img.shape[:2]}")
+    return img, ch
+
+
+def pyramid_layout(h, w, n_levels=6, half_steps=True):
+    """``apap_pyramid_layout`` (host only): ``(heights, widths, offsets, scale_num, scale_shift)`` of the levels that exist,
+    at most ``n_levels`` - int32 arrays of their number, ``offsets`` int64 with one more entry: level l lies at byte
+    ``offsets[l]`` of the level buffer, whose size is ``offsets[-1]``; its scale is ``scale_num[l] / 2 ** scale_shift[l]``."""
+    n_levels = pyramid_levels_arg(n_levels, "pyramid_layout")
+    hs, ws, num, shift = (np.zeros(n_levels, np.int32) for _ in range(4))
+    off = np.zeros(n_levels + 1, np.int64)
+    n = lib().apap_pyramid_layout(int(h), int(w), n_levels, int(bool(half_steps)), _ip(hs), _ip(ws), _ptr(off, C.c_longlong), _ip(num),
+                                  _ip(shift))
+    if n < 1:
+        raise ApapValueError(ERR_INVALID_ARG, lib().apap_last_error().decode("utf-8", "replace"))
+    return hs[:n].copy(), ws[:n].copy(), off[:n + 1].copy(), num[:n].copy(), shift[:n].copy()
+
+
+def pyramid_level_caps(max_corners, n_levels=6, half_steps=True):
+    """``apap_pyramid_level_caps`` (host only): the corner budget of every level, int32 (n_levels,) - a constant number of
+    corners per unit area, at least 16 and at most ``max_corners``."""
+    n_levels = pyramid_levels_arg(n_levels, "pyramid_level_caps")
+    caps = np.zeros(n_levels, np.int32)
+    check(lib().apap_pyramid_level_caps(int(max_corners), n_levels, int(bool(half_steps)), _ip(caps)))
+    return caps
+
+
+def pyramid_batch(imgs, n_levels=6, half_steps=True, device=-1, ctx=None):
+    """``apap_pyramid_build_batch``: the grey pyramids of many uint8 pictures, (h, w) grey or (h, w, 3) BGR of any shapes from
+    32 a side, in one call (1 + ceil((n_levels - 1) / 2) kernel launches at most, whatever their number).  Returns a list per
+    picture of its levels, uint8 (h_l, w_l) arrays: level 0 the grey picture, even levels halved k times, odd levels the
+    3/4 reduction halved k times (``half_steps=False``: halvings only); fewer than ``n_levels`` where the next level would
+    have a side under 32.  A picture's levels equal its own single call's byte for byte."""
+    n_levels = pyramid_levels_arg(n_levels, "pyramid_batch")
+    got = [as_pyramid_image(im, f"imgs[{m}]") for m, im in enumerate(imgs)]
+    if not 1 <= len(got) <= CORNER_MAX_IMAGES:
+        raise ValueError(f"pyramid_batch: {len(got)} images (1 .. {CORNER_MAX_IMAGES})")
+    lays = [pyramid_layout(a.shape[0], a.shape[1], n_levels, half_steps) for a, _ in got]
+    buf = np.empty(sum(int(lay[2][-1]) for lay in lays), np.uint8)
+    ptrs, hs, ws, cs = _image_table(got)
+    check(lib().apap_pyramid_build_batch(_h(ctx), ptrs, _ip(hs), _ip(ws), _ip(cs), len(got), n_levels, int(bool(half_steps)),
+                                         _ptr(buf, C.c_uint8), device))
+    out, at = [], 0
+    for lh, lw, off, _, _ in lays:
+        out.append([buf[at + off[k]:at + off[k] + int(lh[k]) * int(lw[k])].reshape(lh[k], lw[k]).copy() for k in range(len(lh))])
+        at += int(off[-1])
+    return out
+
+
+def pyramid(img, n_levels=6, half_steps=True, device=-1, ctx=None):
+    """``apap_pyramid_build``: the list of grey levels of one uint8 picture (see ``pyramid_batch``; the batch of one)."""
+    return pyramid_batch([img], n_levels, half_steps, device=device, ctx=ctx)[0]
+
+
+def pyramid_keypoints(slab_pts, slab_response, counts, scale_num, scale_shift, level_index, device=-1, ctx=None):
+    """``apap_pyramid_keypoints``: the pack.  ``slab_pts`` (n, rows, 2) float32 and ``slab_response`` (n, rows) int64: the
+    batched detector's slabs over n level images; ``counts`` (n,): the rows to keep of each (the detector's count clamped to
+    the level's cap); ``scale_num``, ``scale_shift``, ``level_index`` (n,): each level image's scale and level number.
+    Returns ``(pts, level_pts, level, response, level_offset)``: float32 (N, 2) base-frame coordinates, float32 (N, 2) level
+    coordinates, int32 (N,), int64 (N,) and int32 (n + 1,) offsets."""
+    slab_pts = np.ascontiguousarray(slab_pts, dtype=np.float32)
+    slab_response = np.ascontiguousarray(slab_response, dtype=np.int64)
+    if slab_pts.ndim != 3 or slab_pts.shape[2] != 2 or slab_response.shape != slab_pts.shape[:2] or slab_pts.shape[1] < 1:
+        raise ValueError(f"pyramid_keypoints: slabs must be (n, rows, 2) and (n, rows); got {slab_pts.shape} and {slab_response.shape}")
+    n, rows = slab_pts.shape[:2]
+    counts, num, shift, index = (_i32(np.asarray(a).reshape(-1)) for a in (counts, scale_num, scale_shift, level_index))
+    if not 1 <= n <= CORNER_MAX_IMAGES or any(len(a) != n for a in (counts, num, shift, index)):
+        raise ValueError(f"pyramid_keypoints: {n} level images (1 .. {CORNER_MAX_IMAGES}) need as many counts, scales and indices")
+    if counts.min() < 0 or counts.max() > rows:
+        raise ValueError(f"pyramid_keypoints: counts must be 0 .. {rows}; got {counts.tolist()}")
+    N = int(counts.sum())
+    pts, lpts = np.empty((N, 2), np.float32), np.empty((N, 2), np.float32)
+    level, resp, off = np.empty(N, np.int32), np.empty(N, np.int64), np.empty(n + 1, np.int32)
+    check(lib().apap_pyramid_keypoints(_h(ctx), _ptr(slab_pts, C.c_float), _ptr(slab_response, C.c_longlong), rows, _ip(counts), _ip(num),
+                                       _ip(shift), _ip(index), n, _ptr(pts, C.c_float), _ptr(lpts, C.c_float), _ip(level),
+                                       _ptr(resp, C.c_longlong), _ip(off), device))
+    return pts, lpts, level, resp, off
 
 
 # ---------------------------------------------------------------- global warp and blend: image_warping of utils.py:93-127

@@ -1610,6 +1610,82 @@ int apap_corner_detect(apap_ctx *ctx, const uint8_t *img, int h, int w, int chan
     return apap_corner_detect_batch(ctx, &img, &h, &w, &channels, 1, max_corners, radius, quality_permille, pts, response, count, device);
 }
 
+// ------------------------------------------------------------------ image pyramid (apap_pyramid.hip)
+int apap_pyramid_build_batch(apap_ctx *ctx, const uint8_t *const *imgs, const int *heights, const int *widths, const int *channels,
+                             int n_images, int n_levels, int half_steps, uint8_t *levels, int device) {
+    const char *who = "apap_pyramid_build_batch";
+    if (!imgs || !levels) return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc = apap::pyramid_check(heights, widths, channels, n_images, n_levels, who);
+    if (rc) return rc;
+    for (int m = 0; m < n_images; ++m)
+        if (!imgs[m]) return apap::fail(APAP_ERR_INVALID_ARG, "%s: image %d: null pointer", who, m);
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    // every level of every picture: its place in `levels` (and in the device buffer alike) and its bytes
+    std::vector<size_t> at, bytes;
+    size_t total = 0;
+    for (int m = 0; m < n_images; ++m) {
+        int lh[APAP_PYRAMID_MAX_LEVELS], lw[APAP_PYRAMID_MAX_LEVELS];
+        long long off[APAP_PYRAMID_MAX_LEVELS + 1];
+        const int n = apap_pyramid_layout(heights[m], widths[m], n_levels, half_steps, lh, lw, off, nullptr, nullptr);
+        for (int l = 0; l < n; ++l) {
+            at.push_back(total + (size_t)off[l]);
+            bytes.push_back((size_t)lh[l] * lw[l]);
+        }
+        total += (size_t)off[n];
+    }
+    const std::vector<Part> d_img = image_parts(call, heights, widths, channels, n_images);
+    const Part d_levels = call.slot(S_OUT, total);
+    const Part work = call.slot(S_WORK, apap_pyramid_workspace_bytes(n_images, n_levels));
+    const std::vector<const uint8_t *> d_imgs = upload_images(call, d_img, imgs);
+    if ((rc = call.rc())) return rc;
+    rc = apap_pyramid_build_batch_device(ctx, d_imgs.data(), heights, widths, channels, n_images, n_levels, half_steps,
+                                         d_levels.as<uint8_t>(), d_levels.bytes, work.as<void>(), work.bytes, call.stream());
+    if (rc) return rc;
+    for (size_t k = 0; k < at.size(); ++k) call.down(levels + at[k], Part{d_levels.base, at[k], bytes[k]});   // the levels alone
+    return call.wait();
+}
+
+int apap_pyramid_build(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, int n_levels, int half_steps, uint8_t *levels,
+                       int device) {
+    return apap_pyramid_build_batch(ctx, &img, &h, &w, &channels, 1, n_levels, half_steps, levels, device);
+}
+
+int apap_pyramid_keypoints(apap_ctx *ctx, const float *slab_pts, const long long *slab_response, int slab_rows, const int *counts,
+                           const int *scale_num, const int *scale_shift, const int *level_index, int n_level_images, float *pts,
+                           float *level_pts, int *level, long long *response, int *level_offset, int device) {
+    const char *who = "apap_pyramid_keypoints";
+    if (!slab_pts || !slab_response || !pts || !level_pts || !level || !response || !level_offset)
+        return apap::fail(APAP_ERR_INVALID_ARG, "%s: null argument", who);
+    int rc = apap::pyramid_keypoints_check(slab_rows, counts, scale_num, scale_shift, level_index, n_level_images, who);
+    if (rc) return rc;
+    HostCall call(ctx);
+    if ((rc = call.select(device))) return rc;
+    size_t N = 0;
+    for (int m = 0; m < n_level_images; ++m) N += (size_t)counts[m];
+    const size_t rows = (size_t)n_level_images * (size_t)slab_rows;
+    Layout io = call.layout(S_AUX);
+    const Part d_spts = io.take(rows * 2 * sizeof(float)), d_sresp = io.take(rows * sizeof(long long));
+    const Part d_pts = io.take(N * 2 * sizeof(float)), d_lpts = io.take(N * 2 * sizeof(float));
+    const Part d_level = io.take(N * sizeof(int)), d_resp = io.take(N * sizeof(long long));
+    call.alloc(io);
+    const Part work = call.slot(S_WORK, apap_pyramid_keypoints_workspace_bytes(n_level_images));
+    call.up(d_spts, slab_pts);
+    call.up(d_sresp, slab_response);
+    if ((rc = call.rc())) return rc;
+    rc = apap_pyramid_keypoints_device(ctx, d_spts.as<const float>(), d_sresp.as<const long long>(), slab_rows, counts, scale_num,
+                                       scale_shift, level_index, n_level_images, d_pts.as<float>(), d_lpts.as<float>(), d_level.as<int>(),
+                                       d_resp.as<long long>(), level_offset, work.as<void>(), work.bytes, call.stream());
+    if (rc) return rc;
+    if (N) {
+        call.down(pts, d_pts);
+        call.down(level_pts, d_lpts);
+        call.down(level, d_level);
+        call.down(response, d_resp);
+    }
+    return call.wait();
+}
+
 // ------------------------------------------------------------------ global warp and blend (apap_image_warp.hip)
 int apap_image_warp_batch(apap_ctx *ctx, const uint8_t *const *bases, const int *base_h, const int *base_w, const uint8_t *const *srcs,
                           const int *src_h, const int *src_w, const double *M, const int *canvas_w, const int *canvas_h,

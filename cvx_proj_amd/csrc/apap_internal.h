@@ -263,6 +263,10 @@ int sift_orient_check(const int *heights, const int *widths, const int *channels
 // The argument checks of the corner detector's entry points (apap_corner.hip) that need no device pointer.
 int corner_check(const int *heights, const int *widths, const int *channels, int n_images, int max_corners, int radius,
                  int quality_permille, const char *who);
+// The argument checks of the image pyramid's entry points (apap_pyramid.hip) that need no device pointer, and of its pack's.
+int pyramid_check(const int *heights, const int *widths, const int *channels, int n_images, int n_levels, const char *who);
+int pyramid_keypoints_check(int slab_rows, const int *counts, const int *scale_num, const int *scale_shift, const int *level_index,
+                            int n_level_images, const char *who);
 // The argument checks of the global warp's entry points (apap_image_warp.hip) that need no device pointer.
 int image_warp_check(const int *base_h, const int *base_w, const int *src_h, const int *src_w, const double *M, const int *canvas_w,
                      const int *canvas_h, const int *off_x, const int *off_y, const int *direct_blend, int n_problems,

@@ -904,6 +904,129 @@ def hip_detect_describe_match(c_img, o_img, max_corners, radius=5, quality_permi
     return hip_describe_and_match(c_img, o_img, pts_c, pts_o, second=second, ctx=ctx, oriented=oriented) + (pts_c, pts_o)
 
 
+def pyramid_workspace_bytes(n_images=1, levels=6):
+    """Scratch of ``hip_pyramid`` / ``hip_pyramid_batch``: 64 bytes per picture and level, a 256-byte multiple.  0 for invalid
+    arguments."""
+    return _native.lib().apap_pyramid_workspace_bytes(int(n_images), int(levels))
+
+
+def hip_pyramid_batch(imgs, levels=6, half_steps=True, ctx=None, work=None):
+    """``apap_pyramid_build_batch_device`` on the current stream of the tensors' device, no host synchronisation: the grey
+    pyramids of many uint8 device pictures, (h, w) grey or (h, w, 3) BGR of any shapes from 32 a side, in
+    1 + ceil((levels - 1) / 2) kernel launches at most.  Returns a list per picture of its levels, uint8 (h_l, w_l) views of
+    one buffer (every level on a 256-byte boundary), not synchronised: what ``hip_corner_detect_batch`` and
+    ``hip_sift_describe_batch`` take as images.  Same bytes as ``_native.pyramid_batch``, and per picture as ``hip_pyramid``."""
+    who = "hip_pyramid_batch"
+    levels = _native.pyramid_levels_arg(levels, who)
+    imgs = list(imgs)
+    if not imgs:
+        raise ValueError(f"{who}: no image")
+    _needs_device(imgs[0], who)
+    dev = imgs[0].device
+    ptrs, hs, ws, cs = _image_table(imgs, dev, who)
+    for m, im in enumerate(imgs):
+        if min(im.shape[:2]) < _native.PYRAMID_MIN_SIDE:
+            raise ValueError(f"{who}: imgs[{m}]: sides must be {_native.PYRAMID_MIN_SIDE} .. {_native.SIFT_MAX_SIDE}; got {tuple(im.shape[:2])}")
+    lays = [_native.pyramid_layout(im.shape[0], im.shape[1], levels, half_steps) for im in imgs]
+    buf = torch.empty(sum(int(lay[2][-1]) for lay in lays), dtype=torch.uint8, device=dev)
+    work = _scratch(work, pyramid_workspace_bytes(len(imgs), levels), dev)
+    _native.check(_native.lib().apap_pyramid_build_batch_device(
+        _native._h(ctx), ptrs, _ip(hs), _ip(ws), _ip(cs), len(imgs), levels, int(bool(half_steps)), buf.data_ptr(), buf.numel(),
+        work.data_ptr(), work.numel(), _stream(dev)))
+    out, at = [], 0
+    for lh, lw, off, _, _ in lays:
+        out.append([buf[at + int(off[k]):at + int(off[k]) + int(lh[k]) * int(lw[k])].view(int(lh[k]), int(lw[k])) for k in range(len(lh))])
+        at += int(off[-1])
+    return out
+
+
+def hip_pyramid(img, levels=6, half_steps=True, work=None, ctx=None):
+    """``apap_pyramid_build_device``: the list of grey levels of one uint8 device picture; the batch of one (see
+    ``hip_pyramid_batch``)."""
+    return hip_pyramid_batch([img], levels, half_steps, ctx=ctx, work=work)[0]
+
+
+def hip_pyramid_keypoints(slab_pts, slab_response, counts, scale_num, scale_shift, level_index, ctx=None, work=None):
+    """``apap_pyramid_keypoints_device`` on the current stream, no host synchronisation: the pack.  ``slab_pts`` (n, rows, 2)
+    float32 and ``slab_response`` (n, rows) int64: ``hip_corner_detect_batch``'s slabs over n level images; ``counts``,
+    ``scale_num``, ``scale_shift``, ``level_index``: HOST sequences of n ints (the rows to keep of each level image, its scale
+    and its level number).  Returns ``(pts, level_pts, level, response, level_offset)``: float32 (N, 2) base-frame
+    coordinates, float32 (N, 2) level coordinates, int32 (N,), int64 (N,) device tensors and a host int32 (n + 1,) array."""
+    who = "hip_pyramid_keypoints"
+    _needs_device(slab_pts, who)
+    dev = slab_pts.device
+    _contiguous([(slab_pts, torch.float32), (slab_response, torch.int64)], dev, who)
+    if slab_pts.dim() != 3 or slab_pts.shape[2] != 2 or tuple(slab_response.shape) != tuple(slab_pts.shape[:2]) or slab_pts.shape[1] < 1:
+        raise ValueError(f"{who}: slabs must be (n, rows, 2) and (n, rows); got {tuple(slab_pts.shape)} and {tuple(slab_response.shape)}")
+    n, rows = slab_pts.shape[:2]
+    counts, num, shift, index = (_i32(np.asarray(a).reshape(-1)) for a in (counts, scale_num, scale_shift, level_index))
+    if not 1 <= n <= _native.CORNER_MAX_IMAGES or any(len(a) != n for a in (counts, num, shift, index)):
+        raise ValueError(f"{who}: {n} level images (1 .. {_native.CORNER_MAX_IMAGES}) need as many counts, scales and indices")
+    if counts.min() < 0 or counts.max() > rows:
+        raise ValueError(f"{who}: counts must be 0 .. {rows}; got {counts.tolist()}")
+    N = int(counts.sum())
+    pts, lpts = (torch.empty((N, 2), dtype=torch.float32, device=dev) for _ in range(2))
+    level = torch.empty(N, dtype=torch.int32, device=dev)
+    resp = torch.empty(N, dtype=torch.int64, device=dev)
+    off = np.empty(n + 1, np.int32)
+    work = _scratch(work, _native.lib().apap_pyramid_keypoints_workspace_bytes(n), dev)
+    # an empty tensor has no address: the library asks for one, and follows none when N = 0
+    ptr = lambda t: t.data_ptr() if N else work.data_ptr()      # noqa: E731
+    _native.check(_native.lib().apap_pyramid_keypoints_device(
+        _native._h(ctx), slab_pts.data_ptr(), slab_response.data_ptr(), rows, _ip(counts), _ip(num), _ip(shift), _ip(index), n, ptr(pts),
+        ptr(lpts), ptr(level), ptr(resp), _ip(off), work.data_ptr(), work.numel(), _stream(dev)))
+    return pts, lpts, level, resp, off
+
+
+def hip_pyramid_detect_describe(imgs, max_corners, levels=6, half_steps=True, radius=5, quality_permille=10, ctx=None, oriented=False):
+    """Per picture ``(pts, feats, level, response)`` over its pyramid, all pictures together: the pyramids in one batched call,
+    one batched detection over all level images, the level counts (4 bytes each) read back - the chain's only host
+    synchronisation - the pack, and one batched description with the level images as the images.  Device tensors: float32
+    (n, 2) base-frame keypoints, float32 (n, 128) descriptors, int32 (n,) levels, int64 (n,) responses."""
+    who = "hip_pyramid_detect_describe"
+    levels = _native.pyramid_levels_arg(levels, who)
+    max_corners, radius, quality_permille = _native.corner_params(max_corners, radius, quality_permille, who)
+    pyrs = hip_pyramid_batch(imgs, levels, half_steps, ctx=ctx)
+    flat = [a for lv in pyrs for a in lv]
+    slab_pts, slab_resp, count = hip_corner_detect_batch(flat, max_corners, radius, quality_permille, ctx=ctx)
+    caps = _native.pyramid_level_caps(max_corners, levels, half_steps)
+    num, shift, index = [], [], []
+    for lv in pyrs:
+        _, _, _, n, s = _native.pyramid_layout(lv[0].shape[0], lv[0].shape[1], levels, half_steps)
+        num += n.tolist()
+        shift += s.tolist()
+        index += range(len(lv))
+    keep = np.minimum(count.cpu().numpy(), caps[index])
+    pts, lpts, level, resp, off = hip_pyramid_keypoints(slab_pts, slab_resp, keep, num, shift, index, ctx=ctx)
+    full = [(a, int(k)) for a, k in zip(flat, keep) if k > 0]      # the batch takes no image without a keypoint
+    if not full:
+        feats = torch.zeros((0, _native.SIFT_DIM), dtype=torch.float32, device=pts.device)
+    elif oriented:
+        feats, _ = hip_sift_describe_oriented_batch([a for a, _ in full], lpts, [k for _, k in full], ctx=ctx)
+    else:
+        feats = hip_sift_describe_batch([a for a, _ in full], lpts, [k for _, k in full], ctx=ctx)
+    out, m0 = [], 0
+    for lv in pyrs:
+        a, b = int(off[m0]), int(off[m0 + len(lv)])
+        out.append((pts[a:b], feats[a:b], level[a:b], resp[a:b]))
+        m0 += len(lv)
+    return out
+
+
+def hip_pyramid_detect_describe_match(c_img, o_img, max_corners, levels=6, half_steps=True, radius=5, quality_permille=10, second=True,
+                                      ctx=None, oriented=False):
+    """From two uint8 device images to matches that survive a change of scale between them: ``hip_pyramid_detect_describe`` of
+    both pictures, then ``hip_match_descriptors`` of the centre image's descriptors against the other's.  One host
+    synchronisation, the level counts, where ``hip_detect_describe_match`` reads its two.  Returns (idx, dist, idx2, dist2,
+    feats_c, feats_o, pts_c, pts_o) as ``hip_detect_describe_match`` does, the keypoints in the pictures' own frames.  A
+    picture without corners on any level is refused (``ValueError``)."""
+    (pc, fc, _, _), (po, fo, _, _) = hip_pyramid_detect_describe([c_img, o_img], max_corners, levels, half_steps, radius, quality_permille,
+                                                                 ctx=ctx, oriented=oriented)
+    if pc.shape[0] < 1 or po.shape[0] < 1:
+        raise ValueError(f"hip_pyramid_detect_describe_match: {pc.shape[0]} and {po.shape[0]} corners; both images need at least one")
+    return hip_match_descriptors(fc, fo, second=second, ctx=ctx) + (fc, fo, pc, po)
+
+
 def image_warp_workspace_bytes(n_problems=1):
     """Scratch of ``hip_image_warp`` / ``hip_image_warp_batch`` of ``n_problems`` problems: 144 bytes per problem, a 256-byte
     multiple, no contract on its contents.  0 for an invalid count."""

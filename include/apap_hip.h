@@ -1152,6 +1152,67 @@ int apap_corner_detect_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs,
                                     const int *channels, int n_images, int max_corners, int radius, int quality_permille,
                                     float *d_pts, long long *d_response, int *d_count, void *d_work, size_t work_bytes, void *stream);
 
+/* ------------------------------------------------- image pyramid: grey levels at scales 2^-k and (3/4) 2^-k --- */
+/* What lets detection and matching survive a change of scale: the corner detector and the descriptor run on every level as
+ * on any other image, and the pack brings the levels' corners back into the base picture's frame.  Everything is integer
+ * arithmetic; the definition is in DESIGN.md "Image pyramid and scale" and, in numpy int64, in tests/pyramid_spec.py:
+ *   grey     level 0: (h, w) uint8 as it is; (h, w, 3) uint8 is BGR, grey = (3735 B + 19235 G + 9798 R + 16384) >> 15
+ *   H(g)     shape ((h + 1) >> 1, (w + 1) >> 1); H(g)[y, x] = (sum_{i,j = -2..2} b_i b_j g[r(2y + i, h), r(2x + j, w)] + 128) >> 8,
+ *            b = (1, 4, 6, 4, 1), r = reflect-101; one rounding at the end
+ *   Q(g)     shape ((3h) >> 2, (3w) >> 2); per axis output 3k + r reads sources 4k + r and 4k + r + 1 with weights (5, 1),
+ *            (3, 3), (1, 5) for r = 0, 1, 2 - linear interpolation at 4x/3 + 1/6; Q(g)[y, x] = (sum of wy wx g + 18) / 36
+ *   levels   half_steps != 0: level 2k = H^k(level 0), scale 2^-k; level 2k + 1 = H^k(Q(level 0)), scale (3/4) 2^-k.
+ *            half_steps = 0: level k = H^k(level 0).  The levels stop before the first with a side under
+ *            APAP_PYRAMID_MIN_SIDE: apap_pyramid_layout returns how many there are, 1 .. n_levels
+ *   scale    scale_num[l] / 2^scale_shift[l]: 1 / 2^k, or 3 / 2^(k + 2)
+ *   base     the base-frame coordinate of level pixel x: x 2^k, or (2^(k + 3) x + 1) / 6 as one float64 division of the exact
+ *            integer, rounded to float32; the same for y
+ *   caps     the corner budget of level l at max_corners: min(max_corners, max(16, max_corners >> 2k)), or on a 3/4 level
+ *            min(max_corners, max(16, (9 max_corners) >> (2k + 4))): apap_pyramid_level_caps, caps[n_levels]
+ * apap_pyramid_layout (host only): heights, widths, scale_num, scale_shift [n_levels] and offsets [n_levels + 1] (any may be
+ * NULL): level l lies at byte offsets[l] of the picture's level buffer, a 256-byte multiple, row-major uint8; offsets[count]
+ * is the buffer's size.  Returns 0 for invalid arguments.  Level 0 is always written, for a grey picture too.
+ * Batch: n_images pictures of their own shapes and channels, one n_levels and half_steps; their level buffers lie back to
+ * back in `levels` in the order of the pictures (each a 256-byte multiple).  One upload and 1 + ceil((n_levels - 1) / 2)
+ * launches at most, whatever n_images; a picture's levels equal its own single call's byte for byte.  Bytes of the buffer
+ * outside the levels are not written.
+ * apap_pyramid_keypoints: the pack.  Input: the batched detector's slabs over n_level_images level images (d_slab_pts
+ * (n_level_images, slab_rows, 2), d_slab_response (n_level_images, slab_rows)) and, per level image, HOST counts (0 ..
+ * slab_rows: the detector's count clamped to the level's cap), scale_num, scale_shift and level_index.  Output: the first
+ * counts[m] rows of every level image concatenated - pts (N, 2) float32 in the base frame, level_pts (N, 2) float32 as the
+ * detector wrote them (what the descriptor reads on the level image), level (N) int = level_index[m], response (N) long
+ * long - and HOST level_offset[n_level_images + 1].  One upload and one launch; none when N = 0.
+ * Refused before any device is touched: null pointers, sides outside APAP_PYRAMID_MIN_SIDE .. 32768, channels other than 1
+ * or 3, n_levels outside 1 .. APAP_PYRAMID_MAX_LEVELS, n_images (n_level_images) outside 1 .. 65535, a count outside 0 ..
+ * slab_rows, a short (APAP_ERR_WORKSPACE) or misaligned workspace or level buffer (256 bytes).  Without a GPU the host-buffer
+ * forms return APAP_ERR_NO_DEVICE.  The _device forms only enqueue on `stream` and do not wait.  A block takes a source tile
+ * of APAP_PYRAMID_TILE_W x APAP_PYRAMID_TILE_H pixels (for tests; no output depends on it). */
+#define APAP_PYRAMID_MAX_LEVELS 16
+#define APAP_PYRAMID_MIN_SIDE 32
+#define APAP_PYRAMID_TILE_W 64
+#define APAP_PYRAMID_TILE_H 32
+int apap_pyramid_layout(int h, int w, int n_levels, int half_steps, int *heights, int *widths, long long *offsets, int *scale_num,
+                        int *scale_shift);
+int apap_pyramid_level_caps(int max_corners, int n_levels, int half_steps, int *caps);
+size_t apap_pyramid_workspace_bytes(int n_images, int n_levels);
+int apap_pyramid_build(apap_ctx *ctx, const uint8_t *img, int h, int w, int channels, int n_levels, int half_steps, uint8_t *levels,
+                       int device);
+int apap_pyramid_build_device(apap_ctx *ctx, const uint8_t *d_img, int h, int w, int channels, int n_levels, int half_steps,
+                              uint8_t *d_levels, size_t levels_bytes, void *d_work, size_t work_bytes, void *stream);
+int apap_pyramid_build_batch(apap_ctx *ctx, const uint8_t *const *imgs, const int *heights, const int *widths, const int *channels,
+                             int n_images, int n_levels, int half_steps, uint8_t *levels, int device);
+int apap_pyramid_build_batch_device(apap_ctx *ctx, const uint8_t *const *d_imgs, const int *heights, const int *widths,
+                                    const int *channels, int n_images, int n_levels, int half_steps, uint8_t *d_levels,
+                                    size_t levels_bytes, void *d_work, size_t work_bytes, void *stream);
+size_t apap_pyramid_keypoints_workspace_bytes(int n_level_images);
+int apap_pyramid_keypoints(apap_ctx *ctx, const float *slab_pts, const long long *slab_response, int slab_rows, const int *counts,
+                           const int *scale_num, const int *scale_shift, const int *level_index, int n_level_images, float *pts,
+                           float *level_pts, int *level, long long *response, int *level_offset, int device);
+int apap_pyramid_keypoints_device(apap_ctx *ctx, const float *d_slab_pts, const long long *d_slab_response, int slab_rows,
+                                  const int *counts, const int *scale_num, const int *scale_shift, const int *level_index,
+                                  int n_level_images, float *d_pts, float *d_level_pts, int *d_level, long long *d_response,
+                                  int *level_offset, void *d_work, size_t work_bytes, void *stream);
+
 /* ------------------------------------------------- global warp and blend: image_warping of utils.py:93-127 --- */
 /* The output stage of spectral_method.py -s (:226-232): img2warp (h2 x w2 x 3 uint8) goes through one 3 x 3 homography onto
  * a canvas that bounds it and img_base (h1 x w1 x 3 uint8), and the base picture is pasted or mean-blended onto it.  The
